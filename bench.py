@@ -12,6 +12,13 @@ SH degree 0, 1080p).  The `roofline` object is measured on configs[2] (10 M Gaus
 224-byte records, 1080p), the configuration BASELINE.json quotes the HBM-read roofline on;
 `roofline_nocull` is the same scene seen from a camera that culls nothing.  `workloads` carries
 configs[3] (10 M at 3840x2160) and configs[4] (50 M, fp16 SH).  Prints ONE JSON line on rank 0.
+
+A plain run does only what `value` and `ms_per_step` need: it sets up (scene upload, sizing and settling
+frames), runs the W warm-up and the K timed steps, checks that no frame was skipped and prints the line.
+Everything else — the single-stream figure beside the frames in flight and their bit-identity check, the
+steady state, frame samples, stage timing, `roofline`, `workloads`, `cpu_baseline` — runs with `--full`.
+`--dump-outputs DIR` writes the image of the last timed step (DIR/image.npy, float32 [H, W, 4]); the scene
+and camera are fixed, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -81,10 +88,13 @@ def _camera(gs, wl):
 
 
 def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, warmup, timing_steps,
-                 frame_samples, rebalance=True, frames_in_flight=0, steady_frames=0):
+                 frame_samples, rebalance=True, frames_in_flight=0, steady_frames=0, lean=False, want_output=False):
     """Times `steps` pipelined frames between barriers (max over ranks), then `frame_samples`
     individually event-timed frames (median / min / p95), then a short run with HIP-event stage
-    timing.  Returns a dict (rank-0 view; per-rank numbers where world > 1)."""
+    timing.  Returns a dict (rank-0 view; per-rank numbers where world > 1).
+    lean: stop after the timed frames (a plain bench run): no single-stream run beside frames in flight,
+    no steady state, no samples, no stage timing, no comparison frames; only the skipped-frame check.
+    want_output: res["output"] = the image of the LAST timed frame (host float32 [H, W, 4], rank 0)."""
     from importlib import import_module
     par = import_module("wgpu_3dgs_core_amd.parallel")
     W, H = wl["width"], wl["height"]
@@ -106,12 +116,14 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
     pipe = [None]
     count = [0]
     band_flags = [None]          # [G] int32 on the device: OR of every finished frame's per-band flags
+    last_img = [None]            # N > 1: the last assembled frame
 
     def finish(i):
         # the flags word of every band travelled with the band: OR them up (one tiny kernel, no host
         # round trip); a non-zero word = some rank skipped a frame, which voids the measurement
         img = pipe[0].finish(i)
         torch.bitwise_or(band_flags[0], pipe[0].flags(i), out=band_flags[0])
+        last_img[0] = img
         return img
 
     # N > 1, frames in flight inside the rank: a band is a chain of small dependent kernels, so the rank's frames are
@@ -171,6 +183,29 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
             torch.cuda.synchronize()
         pipe[0] = par.FramePipeline(torch, dist, plan, rank, W, "cuda", depth=nl + 1)
         band_flags[0] = torch.zeros(world, dtype=torch.int32, device="cuda")
+
+    def check_skipped():
+        # no frame of this run may have been skipped (pair capacity): on one GPU the renderer's last result says
+        # so, on N the OR of the flags words that travelled with every band of every finished frame
+        if world > 1:
+            skipped_bands = [int(x) for x in band_flags[0].cpu().tolist()]
+            for rr in [r] + [l[0] for l in (rank_lanes[0] or [])[1:]]:
+                rr.set_frame_flags_target(None)
+        else:
+            skipped_bands = [int(r.wait_frame().flags)]
+        if any(skipped_bands):
+            raise RuntimeError("bench.py: a frame was skipped or flagged (per-band flags %s; bit 0/1 = pair capacity exceeded / "
+                               "skipped, bit 2 = radix rank watchdog): the timed region did not render every frame" % skipped_bands)
+        return skipped_bands
+
+    def release():
+        for rr, gs_s, _ in (rank_lanes[0] or [])[1:]:
+            rr.destroy()
+        r.destroy()
+        for _, gs_s, _ in (rank_lanes[0] or []):
+            gs_s.close()
+        buf.destroy()
+
     # Frames in flight (single GPU): F renderers (each its own scratch buffers) on F streams of F different
     # priorities take the frames in turn, so that the latency-bound sort chain of frame i + 1 runs under the
     # VALU-bound blend of frame i.  Different priorities because HIP gives each priority level its own hardware
@@ -179,12 +214,15 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
     # with two priorities).  The contract's W warm-up + K timed steps are run this way FIRST, straight after the
     # sizing frames like the single-stream region used to be (so that the two are not told apart by how long the GPU
     # has been busy); every frame is a whole frame, bit-identical to the single-stream one (checked at the end).
-    ring, dt2 = None, None
+    ring, dt2, output = None, None, None
     if world == 1 and frames_in_flight and frames_in_flight > 1:
         F = int(frames_in_flight)
         ring = gs.FrameRing(dev, F)
         targets = [par.band_target_ptr(gbuf, plan, rank, W)]
         extra = [gs.Buffer(dev, size=W * H * 16) for _ in range(F - 1)]
+        # --full --dump-outputs: a device copy of the last timed frame when it lands in gbuf, which the single-stream
+        # frames that follow reuse (allocated here, so that nothing but a queued device copy sits between the two regions)
+        keep = torch.empty((H, W, 4), dtype=torch.float32, device="cuda") if want_output and not lean else None
         targets += [b.device_ptr() for b in extra]
         for k in range(F):               # the sizing frame of every lane's renderer (blocking once each)
             ring.render(buf, gt, mt, cam, targets[k], check=True)
@@ -202,8 +240,38 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
             pstep()
         torch.cuda.synchronize()
         dt2 = time.perf_counter() - t0
+        last_target = (frame_no[0] - 1) % F
+
+        def target_image(k):
+            return (gbuf[:H].cpu().numpy() if k == 0 else
+                    extra[k - 1].download(ring.streams[k], np.float32).reshape(H, W, 4).copy())
+
+        if want_output and lean:     # the last timed frame's image; nothing else runs after it
+            output = target_image(last_target)
+        elif want_output and last_target == 0:
+            keep.copy_(gbuf[:H])     # queued ahead of the single-stream frames; read back in finish_in_flight
+        if lean:
+            flags = [int(fr_.flags) for fr_ in ring.wait()]
+            if any(flags):
+                raise RuntimeError("bench.py: a pipelined frame was skipped or flagged (per-lane flags %s)" % flags)
+            last = ring.renderers[last_target]
+            st, si = last.stats(), last.sort_info()
+            fl = dict(frames_in_flight=F, ms_per_step=dt2 * 1e3 / steps, value=wl["n"] / (dt2 / steps) / 1e6,
+                      unit="Msplats/s", stream_priorities=ring.priorities)
+            out = dict(ms_per_frame=None, visible=int(st.visible), pairs=int(st.pairs), launches=int(last.wait_frame().launches),
+                       sort_info=dict(rounds=int(si.rounds), tile_masks=int(si.tile_masks)), in_flight_run=fl,
+                       per_rank_ms=[fl["ms_per_step"]], band_plan=plan_kind, rank_lanes=1, output=output)
+            ring.close()
+            for b in extra:
+                b.release()
+            release()
+            del gbuf
+            return out
 
         def finish_in_flight():
+            nonlocal output
+            if want_output:          # the last timed frame's image: its target was not written since (gbuf: the copy)
+                output = keep.cpu().numpy() if last_target == 0 else target_image(last_target)
             psteady = None
             if steady_frames:
                 for _ in range(100):
@@ -252,6 +320,23 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
         dist.all_gather(allt, t)
         per_rank = [float(x.item()) * 1e3 / steps for x in allt]
         dt = max(float(x.item()) for x in allt)
+    if want_output and ring is None and rank == 0:     # the last timed frame's image (N > 1: assembled on rank 0)
+        output = (last_img[0] if world > 1 else gbuf)[:H].cpu().numpy()
+    if lean:
+        skipped_bands = check_skipped()
+        st, fr, si = r.stats(), r.wait_frame(), r.sort_info()
+        pairs = int(st.pairs)
+        if world > 1:   # totals over the bands
+            t = torch.tensor([pairs], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t)
+            pairs = int(t.item())
+        out = dict(ms_per_frame=dt * 1e3 / steps, visible=int(st.visible), pairs=pairs, launches=int(fr.launches),
+                   sort_info=dict(rounds=int(si.rounds), tile_masks=int(si.tile_masks)), in_flight_run=None,
+                   per_rank_ms=per_rank, bands=plan.bands, band_plan=plan_kind, skipped_band_flags=skipped_bands,
+                   rank_lanes=len(rank_lanes[0]) if rank_lanes[0] else 1, output=output)
+        release()
+        del gbuf
+        return out
 
     # Steady state (single GPU): the timed region above starts a few frames after an idle GPU and still sees the
     # clocks ramp (same-box fit of total time over K: ~14 us per frame more for the first ~50 frames, then 0.3075 ms
@@ -324,17 +409,7 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
                                    renderer=r, check=True)
         if plain is None or not torch.equal(plain[:H].view(torch.int32), img[:H].view(torch.int32)):
             raise RuntimeError("bench.py: the pipelined N-GPU frame differs from the synchronously exchanged one (rank %d)" % rank)
-    # no frame of this run may have been skipped (pair capacity): on one GPU the renderer's last result says
-    # so, on N the OR of the flags words that travelled with every band of every finished frame
-    if world > 1:
-        skipped_bands = [int(x) for x in band_flags[0].cpu().tolist()]
-        for rr in [r] + [l[0] for l in (rank_lanes[0] or [])[1:]]:
-            rr.set_frame_flags_target(None)
-    else:
-        skipped_bands = [int(r.wait_frame().flags)]
-    if any(skipped_bands):
-        raise RuntimeError("bench.py: a frame was skipped or flagged (per-band flags %s; bit 0/1 = pair capacity exceeded / "
-                           "skipped, bit 2 = radix rank watchdog): the timed region did not render every frame" % skipped_bands)
+    skipped_bands = check_skipped()
     checksum = float(img[:H].double().sum().item())
     fr = r.wait_frame()          # the LAST frame's result: its launches are a steady-state frame's (two rounds take ~36, the sizing frame 20)
     visible, pairs = int(st.visible), int(st.pairs)
@@ -348,7 +423,7 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
                stages_ms=stages, checksum=checksum, launches=int(fr.launches), pair_capacity=int(fr.pair_capacity),
                per_rank_ms=per_rank, render_ms_per_rank=render_ms, gather_ms_per_rank=gather_ms,
                bands=plan.bands, band_plan=plan_kind, skipped_band_flags=skipped_bands,
-               rank_lanes=len(rank_lanes[0]) if rank_lanes[0] else 1)
+               rank_lanes=len(rank_lanes[0]) if rank_lanes[0] else 1, output=output)
     si = r.sort_info()      # what the renderer chose for this workload
     out["sort_info"] = dict(depth_msd=int(si.depth_msd), depth_bucket_max=int(si.depth_bucket_max),
                             bucket_capacity=int(si.bucket_capacity), tile_msd=int(si.tile_msd), tile_masks=int(si.tile_masks),
@@ -358,12 +433,7 @@ def run_workload(gs, synth, torch, dist, dev, stream, rank, world, wl, steps, wa
         out["frame_ms"] = dict(samples=len(samples), median=samples[len(samples) // 2], min=samples[0],
                                p95=samples[min(len(samples) - 1, int(0.95 * len(samples)))], max=samples[-1],
                                timer="hipEvent pairs around single frames on the launch stream")
-    for rr, gs_s, _ in (rank_lanes[0] or [])[1:]:
-        rr.destroy()
-    r.destroy()
-    for _, gs_s, _ in (rank_lanes[0] or []):
-        gs_s.close()
-    buf.destroy()
+    release()
     del gbuf
     return out
 
@@ -762,6 +832,30 @@ def compact_line(line, detail_path, limit=3900):
     return c
 
 
+DUMP_LIMIT = 64 << 20      # bytes of all the files of --dump-outputs together
+DUMP_SAMPLE_SEED = 0x3D650002
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 / float64).  An array of [..., C] that would take the
+    whole budget is replaced by a fixed, seeded sample of its rows: <name>_sample.npy [k, C] and
+    <name>_sample_index.npy (the flat row indices, float64, ascending) — the same rows in every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes <= share - 4096:        # 4 KB for the .npy header
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            continue
+        rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+        k = min(rows.shape[0], share // (rows.shape[1] * a.itemsize + 8) // 2)    # rows + their float64 index, half the share
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.shape[0], size=k, replace=False))
+        np.save(os.path.join(out_dir, name + "_sample.npy"), rows[idx])
+        np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+
+
 def self_launch(args_list, n):
     """`python3 bench.py --gpus N` typed by hand (no torchrun around it): start the N ranks as a CHILD
     process tree — before this process has touched the GPU, and never by exec — relay rank 0's lines
@@ -813,10 +907,19 @@ def main():
                     help="file that receives the full record (every stage model, frame distribution, PMC figures); "
                          "stdout carries ONE compact JSON line (<= 4 KB) as its last line")
     ap.add_argument("--detail-stdout", action="store_true", help="also print the full record (before the compact line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the single-stream figure and the bit-identity check of the "
+                         "frames in flight, steady state, frame samples, stage timing, the roofline and extra workloads, the "
+                         "CPU baseline.  Without it a run sets up, warms up, times the --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step: DIR/image.npy, the RGBA image (float32 "
+                         "[H, W, 4]); an image over 64 MB is written as a fixed, seeded pixel sample instead")
     ap.add_argument("--launch-check", action="store_true",
                     help="only the launch plumbing (works without a GPU): every rank joins the process group, one "
                          "all_reduce, rank 0 prints a JSON line with the backend and the world size")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # typed by hand: become the launcher (nothing in this process has touched the GPU yet)
@@ -886,26 +989,30 @@ def main():
     assert tstream.cuda_stream != 0
     stream = dev.wrap_stream(tstream.cuda_stream)
 
-    def run(name, steps, warmup, samples, frames_in_flight=0, steady_frames=0):
+    def run(name, steps, warmup, samples, frames_in_flight=0, steady_frames=0, lean=False, want_output=False):
         return run_workload(gs, synth, torch, dist, dev, stream, rank, world, WORKLOADS[name], steps, warmup,
                             args.timing_steps, samples, rebalance=not args.no_rebalance, frames_in_flight=frames_in_flight,
-                            steady_frames=steady_frames)
+                            steady_frames=steady_frames, lean=lean, want_output=want_output)
 
     wl = WORKLOADS[args.workload]
     res = run(args.workload, args.steps, args.warmup, args.frame_samples,
               frames_in_flight=0 if args.no_in_flight else args.frames_in_flight,
-              steady_frames=0 if args.no_steady else 200)
-    rsteps, rwarm = max(5, min(args.steps, 20)), max(2, min(args.warmup, 5))
+              steady_frames=0 if args.no_steady else 200, lean=not args.full, want_output=args.dump_outputs is not None)
+    output = res.pop("output", None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": output})
     roof = nocull = None
-    if not args.no_roofline:
-        roof = run(args.roofline_workload, rsteps, rwarm, args.frame_samples)
-        if args.roofline_workload == "10m" and world == 1:
-            nocull = run("10m-nocull", rsteps, rwarm, 0)
     extras = {}
-    for name in [x for x in args.extra_workloads.split(",") if x]:
-        if name in (args.workload, args.roofline_workload) or args.no_roofline:
-            continue
-        extras[name] = run(name, min(rsteps, 10), rwarm, 20)
+    if args.full:
+        rsteps, rwarm = max(5, min(args.steps, 20)), max(2, min(args.warmup, 5))
+        if not args.no_roofline:
+            roof = run(args.roofline_workload, rsteps, rwarm, args.frame_samples)
+            if args.roofline_workload == "10m" and world == 1:
+                nocull = run("10m-nocull", rsteps, rwarm, 0)
+        for name in [x for x in args.extra_workloads.split(",") if x]:
+            if name in (args.workload, args.roofline_workload) or args.no_roofline:
+                continue
+            extras[name] = run(name, min(rsteps, 10), rwarm, 20)
 
     if rank == 0:
         def summary(w, rr, name=None):
@@ -926,7 +1033,7 @@ def main():
         # single GPU: the headline is measured with the frames in flight (run_workload), the single-stream
         # figure of the same W + K steps stays beside it
         fl = res.get("in_flight_run")
-        if fl and not fl["images_bit_identical"]:
+        if args.full and fl and not fl["images_bit_identical"]:
             raise RuntimeError("bench.py: the pipelined frames differ from the single-stream frame")
         head_ms = fl["ms_per_step"] if fl else res["ms_per_frame"]
         value = wl["n"] / (head_ms * 1e-3) / 1e6
@@ -947,7 +1054,7 @@ def main():
             "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": wl["label"], "gaussians": wl["n"], "visible": res["visible"],
-                       "pairs": res["pairs"], "sort_passes": res["sort_passes"], "sort_info": res.get("sort_info"),
+                       "pairs": res["pairs"], "sort_passes": res.get("sort_passes"), "sort_info": res.get("sort_info"),
                        "launches_per_frame": res["launches"],
                        "parallelism": "tile-row bands x%d + one %s all-gather (%s), %d frames in flight per rank" % (
                            world, "RCCL" if backend == "nccl" else "%s (rehearsal, host-staged)" % backend, res["band_plan"],
@@ -957,28 +1064,31 @@ def main():
                        "frames_in_flight": fl["frames_in_flight"] if fl else res.get("rank_lanes", 1),
                        # every lane is a renderer of its own: per-slot outputs, sort and pair buffers once per lane
                        "renderer_scratch_copies": fl["frames_in_flight"] if fl else res.get("rank_lanes", 1),
-                       "image_checksum": res["checksum"]},
-            "single_stream": {"ms_per_step": res["ms_per_frame"], "value": wl["n"] / (res["ms_per_frame"] * 1e-3) / 1e6,
-                              "unit": "Msplats/s", "steady_state": res.get("steady_state"),
-                              "note": "the same W + K frames on one stream, one frame at a time on the device"},
-            "frame_ms": res.get("frame_ms"),
-            "stages_ms": res["stages_ms"],
-            "stage_models": stage_models(wl, res),
-            "frame_bytes": frame_bytes_object(args.workload, wl, res),
+                       "image_checksum": res.get("checksum")},
             "in_flight_run": res.get("in_flight_run"),
-            "steady_state": (fl or {}).get("steady_state") or res.get("steady_state"),
-            "blend": blend_valu_object(res) if args.workload == "1m" and world == 1 else None,
             "hip_runtime": {"source": hiprt.info()["source"], "libamdhip64": hiprt.mapped()["libamdhip64"],
                             "compiled_version": gs.hip_versions()[0], "runtime_version": gs.hip_versions()[1],
                             "driver_version": gs.hip_versions()[2],
                             "launch_stream": "dedicated non-default stream (torch.cuda.Stream, current)"},
         }
+        if args.full:
+            line.update({
+                "single_stream": {"ms_per_step": res["ms_per_frame"], "value": wl["n"] / (res["ms_per_frame"] * 1e-3) / 1e6,
+                                  "unit": "Msplats/s", "steady_state": res.get("steady_state"),
+                                  "note": "the same W + K frames on one stream, one frame at a time on the device"},
+                "frame_ms": res.get("frame_ms"),
+                "stages_ms": res["stages_ms"],
+                "stage_models": stage_models(wl, res),
+                "frame_bytes": frame_bytes_object(args.workload, wl, res),
+                "steady_state": (fl or {}).get("steady_state") or res.get("steady_state"),
+                "blend": blend_valu_object(res) if args.workload == "1m" and world == 1 else None,
+            })
         if world > 1:
             line["distributed"] = {"backend": backend, "world_size": dist.get_world_size(),
                                    "per_rank_ms": res["per_rank_ms"], "per_rank_ms_min": min(res["per_rank_ms"]),
                                    "per_rank_ms_max": max(res["per_rank_ms"]),
-                                   "render_ms_per_rank": res["render_ms_per_rank"],
-                                   "gather_ms_per_rank": res["gather_ms_per_rank"], "bands": res["bands"],
+                                   "render_ms_per_rank": res.get("render_ms_per_rank"),
+                                   "gather_ms_per_rank": res.get("gather_ms_per_rank"), "bands": res["bands"],
                                    "band_plan": res["band_plan"], "skipped_band_flags": res["skipped_band_flags"]}
         if roof is not None:
             roof_wl = WORKLOADS[args.roofline_workload]
@@ -995,7 +1105,7 @@ def main():
                 line["roofline"]["achieved_nocull"] = line["roofline_nocull"]["achieved"]
         if extras:
             line["workloads"] = {k: summary(WORKLOADS[k], v, k) for k, v in extras.items()}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(wl, args.cpu_frames)
         detail_path = None
         try:

@@ -144,7 +144,7 @@ def test_bench_two_ranks_gloo_rehearsal_self_launched(tmp_path):
     the gathers, the compact line with its `distributed` object."""
     detail = tmp_path / "detail.json"
     res = _run(["--gpus", "2", "--backend", "gloo", "--force-device", "0", "--workload", "100k", "--steps", "3",
-                "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--frame-samples", "4", "--timing-steps", "2",
+                "--warmup", "1", "--full", "--no-roofline", "--no-cpu-baseline", "--frame-samples", "4", "--timing-steps", "2",
                 "--detail-out", str(detail)])
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-3000:])
     last = res.stdout.strip().splitlines()[-1]
@@ -159,11 +159,38 @@ def test_bench_two_ranks_gloo_rehearsal_self_launched(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_two_ranks_plain_run_dumps_the_assembled_image(tmp_path):
+    """the plain (no --full) N = 2 path on ONE GPU, gloo rehearsal: the timed frames, the skipped-band check, the pair
+    totals over the bands, and rank 0's last assembled frame as DIR/image.npy"""
+    import numpy as np
+    out = tmp_path / "out"
+    res = _run(["--gpus", "2", "--backend", "gloo", "--force-device", "0", "--workload", "100k", "--steps", "3",
+                "--warmup", "1", "--dump-outputs", str(out), "--detail-out", str(tmp_path / "detail.json")])
+    assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-3000:])
+    last = res.stdout.strip().splitlines()[-1]
+    assert len(last) <= 4096
+    j = json.loads(last)
+    assert j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+    assert j["config"]["frames_in_flight"] == 2 and j["config"]["pairs"] > 0
+    for k in ("roofline", "cpu_baseline", "workloads", "single_stream", "steady_state"):
+        assert k not in j, k
+    d = j["distributed"]
+    assert d["backend"] == "gloo" and d["world_size"] == 2 and len(d["per_rank_ms"]) == 2
+    assert d["skipped_band_flags"] == [0, 0]
+    assert os.listdir(out) == ["image.npy"]
+    img = np.load(out / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 4)
+    assert np.isfinite(img).all() and img[..., 3].max() > 0
+    y0, y1 = d["bands"][1]
+    assert img[y0 * 16:min(y1 * 16, 1080), :, 3].max() > 0          # the band rank 1 rendered reached rank 0's image
+
+
+@pytest.mark.gpu
 def test_bench_headline_runs_with_frames_in_flight(tmp_path):
     """the default: three renderers on three priority streams take the headline's frames in turn; the images must be
     bit-identical to the single-stream frame (bench.py raises otherwise) and the one-stream figure is reported too"""
     detail = tmp_path / "detail.json"
-    res = _run(["--workload", "100k", "--steps", "6", "--warmup", "2", "--no-roofline", "--no-cpu-baseline",
+    res = _run(["--workload", "100k", "--steps", "6", "--warmup", "2", "--full", "--no-roofline", "--no-cpu-baseline",
                 "--frame-samples", "4", "--timing-steps", "2", "--no-steady", "--detail-out", str(detail)])
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-3000:])
     j = json.loads(res.stdout.strip().splitlines()[-1])
@@ -177,7 +204,7 @@ def test_bench_headline_runs_with_frames_in_flight(tmp_path):
 @pytest.mark.gpu
 def test_bench_single_gpu_compact_line(tmp_path):
     detail = tmp_path / "detail.json"
-    res = _run(["--workload", "100k", "--steps", "3", "--warmup", "1", "--no-roofline", "--no-cpu-baseline",
+    res = _run(["--workload", "100k", "--steps", "3", "--warmup", "1", "--full", "--no-roofline", "--no-cpu-baseline",
                 "--frame-samples", "4", "--timing-steps", "2", "--no-in-flight", "--detail-out", str(detail)])
     assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-3000:])
     lines = res.stdout.strip().splitlines()
@@ -186,3 +213,52 @@ def test_bench_single_gpu_compact_line(tmp_path):
     assert j["n_gpus"] == 1 and j["hip"]["compiled"] and j["hip"]["runtime"]
     assert j["config"]["frames_in_flight"] == 1 and "single_stream" not in j        # --no-in-flight: one stream
     assert json.loads(detail.read_text())["hip_runtime"]["runtime_version"] == j["hip"]["runtime"]
+
+
+def test_dump_outputs_stays_in_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 / float64 files only, at most 64 MB in all; an image over the budget is replaced by the
+    same seeded pixel sample in every run."""
+    import numpy as np
+    import bench
+    small = np.random.default_rng(1).random((1080, 1920, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"image": small})
+    assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), small)
+    big = np.arange(2160 * 3840 * 4, dtype=np.float32).reshape(2160, 3840, 4)       # a 4K RGBA frame: 133 MB
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"image": big})
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["image_sample.npy", "image_sample_index.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+    for f in ("image_sample.npy", "image_sample_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    rows, idx = np.load(tmp_path / "b" / "image_sample.npy"), np.load(tmp_path / "b" / "image_sample_index.npy")
+    assert rows.dtype == np.float32 and idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(rows, big.reshape(-1, 4)[idx.astype(np.int64)])
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_its_image(tmp_path):
+    """a plain run (no --full) prints the headline only — the --steps timed frames, ms_per_step — and --dump-outputs writes
+    the last timed frame's image; frames in flight and one stream give the same image bit for bit"""
+    import numpy as np
+    images = []
+    for extra in ([], ["--no-in-flight"]):
+        out = tmp_path / ("out%d" % len(images))
+        res = _run(["--workload", "100k", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out),
+                    "--detail-out", str(tmp_path / "detail.json")] + extra)
+        assert res.returncode == 0, (res.stdout[-2000:], res.stderr[-3000:])
+        lines = res.stdout.strip().splitlines()
+        assert len(lines) == 1 and len(lines[0]) <= 4096
+        j = json.loads(lines[0])
+        assert j["steps"] == 7 and j["warmup"] == 2 and j["unit"] == "Msplats/s" and j["higher_is_better"] is True
+        assert j["dtype"] == "f32" and j["ms_per_step"] > 0
+        assert abs(j["value"] - 100_000 / (j["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * j["value"]
+        assert j["config"]["frames_in_flight"] == (1 if extra else 3)
+        for k in ("roofline", "cpu_baseline", "workloads", "single_stream", "steady_state"):
+            assert k not in j, k
+        assert os.listdir(out) == ["image.npy"]
+        img = np.load(out / "image.npy")
+        assert img.dtype == np.float32 and img.shape == (1080, 1920, 4)
+        assert np.isfinite(img).all() and img[..., 3].max() > 0
+        images.append(img)
+    assert np.array_equal(images[0].view(np.uint32), images[1].view(np.uint32))

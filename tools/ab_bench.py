@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(env_kv, wl, steps):
     env = dict(os.environ)
     env.update(env_kv)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--no-roofline", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", wl, "--no-roofline", "--no-cpu-baseline",
            "--no-in-flight", "--extra-workloads", "", "--steps", str(steps), "--warmup", "5", "--frame-samples", "50"]
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     if res.returncode != 0:

@@ -3,7 +3,7 @@
 # usage: tools/flight_sweep.sh "1m 10m 50m" "1 2 3"
 for wl in ${1:-"1m 10m"}; do
   for f in ${2:-"1 2 3"}; do
-    python3 bench.py --workload $wl --no-roofline --no-cpu-baseline --extra-workloads "" --steps 20 --warmup 5 --timing-steps 0 \
+    python3 bench.py --full --workload $wl --no-roofline --no-cpu-baseline --extra-workloads "" --steps 20 --warmup 5 --timing-steps 0 \
       --frame-samples 0 --frames-in-flight $f 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.read())

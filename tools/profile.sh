@@ -8,7 +8,7 @@ STEPS=${3:-5}
 OUT=$PWD/gpurun_out/prof_${TAG}_${WL}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python3 $PWD/bench.py --workload $WL --no-roofline --no-cpu-baseline --steps $STEPS --warmup 2 --timing-steps 0 --frames-in-flight 1"
+CMD="python3 $PWD/bench.py --full --workload $WL --no-roofline --no-cpu-baseline --steps $STEPS --warmup 2 --timing-steps 0 --frames-in-flight 1"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- $CMD > "$OUT/trace.log" 2>&1 || { tail -20 "$OUT/trace.log"; exit 1; }
 # The counter passes render the warm-up + timed frames only (no latency samples, no steady-state run): with those, a process

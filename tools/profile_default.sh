@@ -1,6 +1,6 @@
 #!/bin/bash
-# Runs on the GPU box (via gpurun): rocprofv3 kernel trace of the DEFAULT bench command, i.e. the
-# exact command whose JSON line the driver records.  usage: tools/profile_default.sh <tag>
+# Runs on an MI355X: rocprofv3 kernel trace of the default bench command with --full (the run that carries the
+# roofline figure this script compares with the trace).  usage: tools/profile_default.sh <tag>
 set -o pipefail
 TAG=${1:-r01}
 OUT=$PWD/gpurun_out/prof_${TAG}_default
@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 REPO=$PWD
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 $REPO/bench.py > "$OUT/bench.json" 2> "$OUT/trace.log" || { tail -20 "$OUT/trace.log"; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 $REPO/bench.py --full > "$OUT/bench.json" 2> "$OUT/trace.log" || { tail -20 "$OUT/trace.log"; exit 1; }
 cd - > /dev/null
 STATS=$(find "$OUT/trace" -name "*kernel_stats.csv" | head -1)
 cp "$STATS" "$OUT/kernel_stats.csv"

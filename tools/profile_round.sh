@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs on the GPU box (via gpurun): everything profiles/ holds for one round.
-#   1. rocprofv3 --kernel-trace --stats of the DEFAULT bench command (the line the driver records)
+#   1. rocprofv3 --kernel-trace --stats of the default bench command with --full (roofline and extra workloads included)
 #   2. per workload (1m, 10m, 10m-nocull): kernel trace + separate --pmc FETCH_SIZE / WRITE_SIZE passes
 #   3. SQ counters of the blend kernel at 1 M (VALU / SALU / LDS instruction counts, busy cycles)
 #   4. gpurun_out/profiles_out/pmc_traffic.json, stamped with the hash of the kernel sources
@@ -77,7 +77,7 @@ PY
 # the default command, traced (the JSON line goes to bench.json; PMC-derived fields come from the file above)
 cp "$OUT/pmc_traffic.json" "$REPO/profiles/pmc_traffic.json"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_default_trace" -o trace -- python3 $REPO/bench.py > "$OUT/${TAG}_bench_default_line.json" 2> "$OUT/${TAG}_bench_default.err" || { tail -20 "$OUT/${TAG}_bench_default.err"; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_default_trace" -o trace -- python3 $REPO/bench.py --full > "$OUT/${TAG}_bench_default_line.json" 2> "$OUT/${TAG}_bench_default.err" || { tail -20 "$OUT/${TAG}_bench_default.err"; exit 1; }
 cd - > /dev/null
 cp "$(find "$OUT/${TAG}_default_trace" -name "*kernel_stats.csv" | head -1)" "$OUT/${TAG}_bench_default_kernel_stats.csv"
 cp "$(find "$OUT/${TAG}_default_trace" -name "*kernel_trace.csv" | head -1)" "$OUT/${TAG}_default_kernel_trace.csv"
