@@ -232,6 +232,15 @@ pub struct gs_frame_stats {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct gs_aux_targets {
+    pub depth: *mut f32,
+    pub pick: *mut u32,
+    pub pick_threshold: f32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct gs_frame_result {
     pub gaussians: u64,
     pub visible: u64,
@@ -363,6 +372,7 @@ extern "C" {
     pub fn gs_renderer_set_frame_flags_target(r: *mut gs_renderer, device_word: *mut u32) -> gs_status;
     pub fn gs_renderer_stats(r: *mut gs_renderer, out: *mut gs_frame_stats) -> gs_status;
     pub fn gs_render_frame(r: *mut gs_renderer, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, gaussian_transform: *const gs_gaussian_transform_pod, model_transform: *const gs_model_transform_pod, camera: *const gs_camera, band_ty0: u32, band_ty1: u32, rgba_out_device: *mut f32) -> gs_status;
+    pub fn gs_render_frame_aux(r: *mut gs_renderer, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, gaussian_transform: *const gs_gaussian_transform_pod, model_transform: *const gs_model_transform_pod, camera: *const gs_camera, band_ty0: u32, band_ty1: u32, rgba_out_device: *mut f32, aux: *const gs_aux_targets) -> gs_status;
     pub fn gs_renderer_wait_frame(r: *mut gs_renderer, out: *mut gs_frame_result) -> gs_status;
     pub fn gs_renderer_sort_info(r: *mut gs_renderer, out: *mut gs_sort_info) -> gs_status;
     pub fn gs_renderer_set_sort_mode(r: *mut gs_renderer, depth_msd: i32, tile_msd: i32) -> gs_status;

@@ -621,6 +621,37 @@ gs_status gs_render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *gau
                           const gs_model_transform_pod *model_transform, const gs_camera *camera,
                           uint32_t band_ty0, uint32_t band_ty1, float *rgba_out_device);
 
+/* Depth and pick planes of a frame (no reference item: the viewer and the editor need them).  Both are
+ * full-image H x W row-major planes on the device, like rgba_out_device, and only the band's rows are written.
+ *   depth[p] = the sum over the splats pixel p blends of z' * (alpha * T), accumulated in blend order exactly as a colour
+ *              channel (D = fma(z', alpha T, D)), z' = the projected view depth (gs_projected.depth); no background term,
+ *              so a pixel without contributors holds 0.  The expected depth is depth / rgba.w (the caller divides).
+ *   pick[p]  = the CALLER'S index (position in the uploaded buffer) of the first splat, front to back, whose blend step
+ *              takes the pixel's transmittance T to <= 1 - pick_threshold (computed in f32), or GS_PICK_NONE.  The step
+ *              that finishes a pixel (T (1 - alpha) < 1e-4) is not blended, so it is not picked either.  0.5 picks the
+ *              median contributor; any accepted threshold up to 1/255 the first contributor (1 - threshold must
+ *              stay below 1 in f32: thresholds of 2^-25 or less are refused).
+ * The planes follow the RGBA target: a frame skipped for pair capacity leaves them untouched, and a two-round frame
+ * skipped in its second round leaves the first round's state in them (as in the image). */
+typedef struct gs_aux_targets {
+    float *depth;            /* device, H x W f32 (4-byte aligned), or NULL */
+    uint32_t *pick;          /* device, H x W u32 (4-byte aligned), or NULL */
+    float pick_threshold;    /* 2^-25 < t < 1; 0.5 = the median contributor */
+    uint32_t reserved;       /* 0 */
+} gs_aux_targets;
+#define GS_PICK_NONE 0xFFFFFFFFu
+
+/* gs_render_frame with the planes of `aux` written by the same blend launch (no extra kernel; the frame makes every other
+ * choice as it would without them).  aux == NULL, or both pointers NULL (the threshold is then not looked at): exactly
+ * gs_render_frame.  GS_ERR_INVALID_ARGUMENT, before anything is enqueued, for a nonzero `reserved`, and — with a plane —
+ * for a threshold outside (0, 1), NaN, or so small that 1 - threshold rounds to 1 in f32 (<= 2^-25), or a misaligned
+ * pointer. */
+gs_status gs_render_frame_aux(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *gaussians,
+                              const gs_gaussian_transform_pod *gaussian_transform,
+                              const gs_model_transform_pod *model_transform, const gs_camera *camera,
+                              uint32_t band_ty0, uint32_t band_ty1, float *rgba_out_device,
+                              const gs_aux_targets *aux);
+
 typedef struct gs_frame_result {
     uint64_t gaussians;       /* N */
     uint64_t visible;         /* V */

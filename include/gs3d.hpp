@@ -458,6 +458,13 @@ class Renderer {
                 const gs_camera &cam, float *rgba_device, uint32_t band_ty0 = 0, uint32_t band_ty1 = 0xffffffffu) {
         check(gs_render_frame(h_, s.raw(), g.raw(), &gt, &mt, &cam, band_ty0, band_ty1, rgba_device));
     }
+    // the same frame with its depth / pick planes (gs_render_frame_aux; aux == nullptr: render() above).  The band is
+    // spelled out (0, 0xffffffff: the whole image) so that no call of the overload above can mean this one.
+    template <class G>
+    void render(Stream &s, GaussiansBuffer<G> &g, const gs_gaussian_transform_pod &gt, const gs_model_transform_pod &mt,
+                const gs_camera &cam, float *rgba_device, uint32_t band_ty0, uint32_t band_ty1, const gs_aux_targets *aux) {
+        check(gs_render_frame_aux(h_, s.raw(), g.raw(), &gt, &mt, &cam, band_ty0, band_ty1, rgba_device, aux));
+    }
     // render() only enqueues; wait_frame() blocks until the frame is complete and throws
     // PairCapacityError when it exceeded the pair capacity (the next frame has larger buffers)
     gs_frame_result wait_frame() { gs_frame_result fr; check(gs_renderer_wait_frame(h_, &fr)); return fr; }
@@ -504,6 +511,14 @@ class FrameRing {
                   float *rgba_device, uint32_t band_ty0 = 0, uint32_t band_ty1 = 0xffffffffu) {
         const size_t lane = next_++ % renderers_.size();
         renderers_[lane]->render(*streams_[lane], g, gt, mt, cam, rgba_device, band_ty0, band_ty1);
+        return lane;
+    }
+    // the same with the lane's own depth / pick planes (a lane writes them while the next lanes run)
+    template <class G>
+    size_t render(GaussiansBuffer<G> &g, const gs_gaussian_transform_pod &gt, const gs_model_transform_pod &mt, const gs_camera &cam,
+                  float *rgba_device, uint32_t band_ty0, uint32_t band_ty1, const gs_aux_targets *aux) {
+        const size_t lane = next_++ % renderers_.size();
+        renderers_[lane]->render(*streams_[lane], g, gt, mt, cam, rgba_device, band_ty0, band_ty1, aux);
         return lane;
     }
     // blocks until the newest frame of `lane` is complete; throws as Renderer::wait_frame does

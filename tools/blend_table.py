@@ -51,7 +51,8 @@ def kernel_isa():
         out = os.path.join(d, "gs3d.s")
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", out, SRC], check=True, stderr=subprocess.DEVNULL)
         lines = open(out).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN2gs15k_blend_groupedILi0ELi4E"))
+    # the plain single-round instantiation <0, 4, false, false> (the AUX ones share the prefix)
+    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN2gs15k_blend_groupedILi0ELi4ELb0ELb0EJEE"))
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
     return lines[start:end]
 

@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import Camera, FrameResult, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
+from ._capi import AuxTargets, Camera, FrameResult, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
 
 _L = _capi.load()
 
@@ -1145,6 +1145,7 @@ class ComputeBundleBuilder:
 # ------------------------------------------------------------------------------------------------
 
 FRAME_FLAG_PAIR_OVERFLOW, FRAME_FLAG_SKIPPED, FRAME_FLAG_RANK_FAULT = 1, 2, 4     # gs_frame_result.flags
+PICK_NONE = 0xFFFFFFFF     # GS_PICK_NONE: a pixel of the pick plane whose transmittance never crossed the threshold
 STAGE_NAMES = ["repack", "preprocess", "scan", "depth_sort", "expand", "tile_sort", "ranges", "blend", "frame"]
 
 
@@ -1192,16 +1193,29 @@ class Renderer:
         _check(_L.gs_renderer_set_rounds(self._h, int(mode), int(first_round)))
 
     def render(self, stream, gaussians, gaussian_transform, model_transform, camera,
-               rgba_device_ptr, band=None, check=True):
+               rgba_device_ptr, band=None, check=True, depth_device_ptr=None, pick_device_ptr=None,
+               pick_threshold=0.5):
         """gs_render_frame.  check=True (the validated use: tests, one-off renders) waits for the
         frame and, if it exceeded the pair capacity sized from earlier frames, renders it again
         with the grown buffers; check=False only enqueues (the pipelined use: a viewer's frame
-        loop, bench.py) — call wait_frame() / synchronise the stream before reading the image."""
+        loop, bench.py) — call wait_frame() / synchronise the stream before reading the image.
+        depth_device_ptr / pick_device_ptr: H x W f32 / u32 device planes that the same frame fills
+        (gs_render_frame_aux): the depth sum (expected depth = depth / alpha) and the
+        caller's index of the Gaussian that takes the pixel's alpha to pick_threshold (PICK_NONE)."""
         b0, b1 = band if band is not None else (0, 0xFFFFFFFF)
+        aux = None
+        if depth_device_ptr is not None or pick_device_ptr is not None:
+            aux = AuxTargets(C.c_void_p(depth_device_ptr or 0), C.c_void_p(pick_device_ptr or 0),
+                             float(pick_threshold), 0)
         for attempt in range(4):
-            _check(_L.gs_render_frame(self._h, stream._h, gaussians._h, C.byref(gaussian_transform),
-                                      C.byref(model_transform), C.byref(camera), b0, b1,
-                                      C.c_void_p(rgba_device_ptr)))
+            if aux is None:
+                _check(_L.gs_render_frame(self._h, stream._h, gaussians._h, C.byref(gaussian_transform),
+                                          C.byref(model_transform), C.byref(camera), b0, b1,
+                                          C.c_void_p(rgba_device_ptr)))
+            else:
+                _check(_L.gs_render_frame_aux(self._h, stream._h, gaussians._h, C.byref(gaussian_transform),
+                                              C.byref(model_transform), C.byref(camera), b0, b1,
+                                              C.c_void_p(rgba_device_ptr), C.byref(aux)))
             if not check:
                 return None
             try:
@@ -1264,12 +1278,15 @@ class FrameRing:
     def __len__(self):
         return len(self.renderers)
 
-    def render(self, gaussians, gaussian_transform, model_transform, camera, rgba_device_ptr, band=None, check=False):
-        """enqueues one frame on the next lane; returns the lane's index (its stream: `streams[lane]`)"""
+    def render(self, gaussians, gaussian_transform, model_transform, camera, rgba_device_ptr, band=None, check=False,
+               depth_device_ptr=None, pick_device_ptr=None, pick_threshold=0.5):
+        """enqueues one frame on the next lane; returns the lane's index (its stream: `streams[lane]`).  The
+        depth / pick planes as in Renderer.render: a lane writes them while later lanes run, so each lane needs its own."""
         lane = self._next % len(self.renderers)
         self._next += 1
         self.renderers[lane].render(self.streams[lane], gaussians, gaussian_transform, model_transform, camera,
-                                    rgba_device_ptr, band=band, check=check)
+                                    rgba_device_ptr, band=band, check=check, depth_device_ptr=depth_device_ptr,
+                                    pick_device_ptr=pick_device_ptr, pick_threshold=pick_threshold)
         return lane
 
     def wait(self):

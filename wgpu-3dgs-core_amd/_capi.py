@@ -47,6 +47,11 @@ class FrameResult(C.Structure):
                 ("flags", u32), ("launches", u32)]
 
 
+class AuxTargets(C.Structure):
+    """gs_aux_targets: device depth / pick planes of a frame (gs_render_frame_aux)"""
+    _fields_ = [("depth", vp), ("pick", vp), ("pick_threshold", f32), ("reserved", u32)]
+
+
 class SortInfo(C.Structure):
     _fields_ = [("depth_msd", u32), ("depth_bucket_max", u32), ("bucket_capacity", u32), ("tile_msd", u32),
                 ("tile_bucket_max", u32), ("tile_masks", u32), ("rounds", u32), ("round1", u32), ("tiles_done", u32), ("partitioned", u32)]
@@ -189,6 +194,7 @@ SIGNATURES = {
     "gs_renderer_set_tile_masks": (i32, [vp, i32]),
     "gs_renderer_set_rounds": (i32, [vp, i32, u32]),
     "gs_render_frame": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp]),
+    "gs_render_frame_aux": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp]),
     "gs_renderer_download_projected": (i32, [vp, vp, vp, sz]),
     "gs_renderer_download_sorted": (i32, [vp, vp, vp, u64, vp]),
     "gs_renderer_download_ranges": (i32, [vp, vp, sz]),

@@ -2577,10 +2577,11 @@ static gs_status reserve_zeroed(DevArray &a, size_t bytes, hipStream_t st) {
     return GS_OK;
 }
 
-extern "C" gs_status gs_render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g,
-                                     const gs_gaussian_transform_pod *gt,
-                                     const gs_model_transform_pod *mt, const gs_camera *cam,
-                                     uint32_t band_ty0, uint32_t band_ty1, float *rgba) {
+// aux: the depth / pick planes (gs_render_frame_aux, checked there), or null.  Only launch_blend looks at it: the frame
+// makes every other choice as it would without it.
+static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g, const gs_gaussian_transform_pod *gt,
+                              const gs_model_transform_pod *mt, const gs_camera *cam, uint32_t band_ty0,
+                              uint32_t band_ty1, float *rgba, const gs_aux_targets *aux) {
     if (!r || !s || !g || !gt || !mt || !cam || !rgba)
         return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     if (g->buf->dev != r->dev || s->dev != r->dev)
@@ -2881,11 +2882,36 @@ extern "C" gs_status gs_render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_
                                                   {gs::k_blend_grouped<1, 2, true>, gs::k_blend_grouped<1, 4, true>},
                                                   {gs::k_blend_grouped<2, 2, true>, gs::k_blend_grouped<2, 4, true>}};
         if (round != 0u && groups == 1) return fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
-        const blend_fn blend = round != 0u ? tbl_rounds[mode][groups == 2 ? 0 : 1] : tbl[mode][groups == 1 ? 0 : groups == 2 ? 1 : 2];
         tile_keys.round = round;
-        hipLaunchKernelGGL(blend, dim3(band_tiles), dim3(gs::BLEND_THREADS), 0, st,
-                           (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
-                           (const uint32_t *)r->recs.ptr, fc, (float4 *)rgba, (const gs::FrameState *)r->state.ptr, tile_keys);
+        if (aux) {
+            // the depth / pick planes ride in the grouped blend (G = 4 where the plain frame would take k_blend)
+            typedef void (*aux_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
+                                   const gs::FrameState *, gs::TileKeys, gs::AuxIO);
+            static const aux_fn tbl_aux[2][3][2] = {
+                {{gs::k_blend_grouped<0, 2, false, true>, gs::k_blend_grouped<0, 4, false, true>},
+                 {gs::k_blend_grouped<1, 2, false, true>, gs::k_blend_grouped<1, 4, false, true>},
+                 {gs::k_blend_grouped<2, 2, false, true>, gs::k_blend_grouped<2, 4, false, true>}},
+                {{gs::k_blend_grouped<0, 2, true, true>, gs::k_blend_grouped<0, 4, true, true>},
+                 {gs::k_blend_grouped<1, 2, true, true>, gs::k_blend_grouped<1, 4, true, true>},
+                 {gs::k_blend_grouped<2, 2, true, true>, gs::k_blend_grouped<2, 4, true, true>}}};
+            gs::AuxIO aio;
+            aio.depth = aux->depth;
+            aio.pick = aux->pick;
+            aio.tcut = 1.0f - aux->pick_threshold;
+            aio.key_bias = r->key_bias;
+            aio.depth_keys = (const uint32_t *)r->depth.ptr;
+            aio.block_list = r->list_mode ? (const uint32_t *)r->block_list.ptr : nullptr;
+            aio.order = r->last_order ? (const uint32_t *)r->last_order->ptr : nullptr;
+            hipLaunchKernelGGL(tbl_aux[round != 0u ? 1 : 0][mode][groups == 2 ? 0 : 1], dim3(band_tiles), dim3(gs::BLEND_THREADS), 0, st,
+                               (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
+                               (const uint32_t *)r->recs.ptr, fc, (float4 *)rgba, (const gs::FrameState *)r->state.ptr, tile_keys,
+                               aio);
+        } else {
+            const blend_fn blend = round != 0u ? tbl_rounds[mode][groups == 2 ? 0 : 1] : tbl[mode][groups == 1 ? 0 : groups == 2 ? 1 : 2];
+            hipLaunchKernelGGL(blend, dim3(band_tiles), dim3(gs::BLEND_THREADS), 0, st,
+                               (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
+                               (const uint32_t *)r->recs.ptr, fc, (float4 *)rgba, (const gs::FrameState *)r->state.ptr, tile_keys);
+        }
         GS_HIP(hipGetLastError());
         r->launches++;
         return GS_OK;
@@ -3447,6 +3473,36 @@ extern "C" gs_status gs_render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_
         r->ev_pending = true;
     }
     return GS_OK;   // done_guard records the end-of-frame event
+}
+
+extern "C" gs_status gs_render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g,
+                                     const gs_gaussian_transform_pod *gt,
+                                     const gs_model_transform_pod *mt, const gs_camera *cam,
+                                     uint32_t band_ty0, uint32_t band_ty1, float *rgba) {
+    return render_frame(r, s, g, gt, mt, cam, band_ty0, band_ty1, rgba, nullptr);
+}
+
+extern "C" gs_status gs_render_frame_aux(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g,
+                                         const gs_gaussian_transform_pod *gt,
+                                         const gs_model_transform_pod *mt, const gs_camera *cam,
+                                         uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                                         const gs_aux_targets *aux) {
+    if (aux) {
+        if (aux->reserved != 0u) return fail(GS_ERR_INVALID_ARGUMENT, aux->reserved, 0, 0, "gs_aux_targets.reserved must be 0");
+        if (!aux->depth && !aux->pick) {
+            aux = nullptr;      // no planes: the plain frame, whatever the threshold says
+        } else {
+            // tcut = 1 - t in f32 must lie in (0, 1): a t below 2^-25 rounds it to 1, which no step can cross
+            const float tcut = 1.0f - aux->pick_threshold;
+            if (!(aux->pick_threshold > 0.0f && aux->pick_threshold < 1.0f) || !(tcut < 1.0f))
+                return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0,
+                            "the pick threshold must lie in (0, 1), and 1 - threshold must be below 1 in f32 (threshold > 2^-25)");
+            if (((uintptr_t)aux->depth & 3u) || ((uintptr_t)aux->pick & 3u))
+                return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)aux->depth, (uint64_t)(uintptr_t)aux->pick, 4,
+                            "the depth and pick planes must be 4-byte aligned");
+        }
+    }
+    return render_frame(r, s, g, gt, mt, cam, band_ty0, band_ty1, rgba, aux);
 }
 
 static gs_status download_sync(gs_renderer *r, void *dst, const void *src, size_t bytes) {

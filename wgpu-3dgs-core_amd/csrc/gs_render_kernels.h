@@ -3821,6 +3821,39 @@ __device__ __forceinline__ bool splat_touches_rect2(float mx, float my, float ca
     return (in_x && in_y) || !(fmaxf(mv, mh) < thr);
 }
 
+// Depth and pick planes of an aux frame (gs_render_frame_aux): full-image, row-major, H x W.
+constexpr uint32_t PICK_NONE = 0xffffffffu;
+struct AuxIO {
+    float *depth;                  // or null
+    uint32_t *pick;                // or null
+    float tcut;                    // pick: the first splat whose step takes T to <= tcut (= 1 - pick_threshold)
+    uint32_t key_bias;             // z' of a slot = bits(depth_keys[slot] + key_bias)
+    const uint32_t *depth_keys;    // per-slot depth keys of the frame (preprocess)
+    const uint32_t *block_list;    // list frame: block of every list position (slot = position * PP_CHUNK + lane); else null
+    const uint32_t *order;         // mirror order of the buffer: caller index of every mirror slot; null = identity
+};
+// slot -> the caller's Gaussian index: the device form of download_slot_map.  PICK_NONE stays PICK_NONE (it is no slot:
+// translating it would read far past the block list and the order).
+__device__ __forceinline__ uint32_t aux_caller_index(const AuxIO &aux, uint32_t slot) {
+    if (slot == PICK_NONE) return PICK_NONE;
+    if (aux.block_list) slot = aux.block_list[slot / (uint32_t)PP_CHUNK] * (uint32_t)PP_CHUNK + slot % (uint32_t)PP_CHUNK;
+    return aux.order ? aux.order[slot] : slot;
+}
+// 4-byte stores with the write policy of the image's (store16); mode 0 plain, 1 sc1, 2 nt, 3 sc0 sc1
+__device__ __forceinline__ void store4(void *p, uint32_t v, uint32_t mode) {
+    if (mode == 1u) asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
+    else if (mode == 2u) asm volatile("global_store_dword %0, %1, off nt" ::"v"(p), "v"(v) : "memory");
+    else if (mode == 3u) asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+    else *(uint32_t *)p = v;
+}
+__device__ __forceinline__ void aux_store(const AuxIO &aux, uint64_t pix, uint32_t depth_bits, uint32_t pick, uint32_t mode) {
+    if (aux.depth) store4(aux.depth + pix, depth_bits, mode);
+    if (aux.pick) store4(aux.pick + pix, pick, mode);
+}
+
+__device__ __forceinline__ AuxIO aux_io() { return AuxIO{}; }
+__device__ __forceinline__ AuxIO aux_io(AuxIO a) { return a; }
+
 // One workgroup (2 waves) = one 16x16 tile, wave h = pixel rows 8h..8h+7, two pixels per lane on
 // packed f32 — as k_blend — but the wave's 64 lanes are split into G lane groups that own
 // different sub-blocks of the half-tile (G = 2: two 8x8 blocks, G = 4: four 8x4 blocks) and walk
@@ -3833,19 +3866,24 @@ __device__ __forceinline__ bool splat_touches_rect2(float mx, float my, float ca
 // than the wave's longest simply idle.  Results are bit-identical to k_blend: culling only removes
 // (splat, block) pairs whose alpha is below 1/255 at every pixel of the block.
 // ROUNDS: the instantiation of two-round frames (TileKeys::round = 1 / 2); the single-round one carries none of it.
-template <int MODE, int G, bool ROUNDS = false>
+// AUX: the instantiation that also writes the depth and pick planes; its one extra argument, the
+// AuxIO, is a parameter pack that is empty in the plain instantiations, so that they keep the launch signature they share
+// with k_blend and the kernel-argument layout (and code) they had before the planes existed.
+template <int MODE, int G, bool ROUNDS = false, bool AUX = false, typename... AuxArg>
 __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__restrict__ ranges,
                                                                  const uint32_t *__restrict__ idx,
                                                                  const uint32_t *__restrict__ recs,
                                                                  FrameConsts fc, float4 *__restrict__ rgba,
-                                                                 const FrameState *__restrict__ state, TileKeys tk) {
+                                                                 const FrameState *__restrict__ state, TileKeys tk,
+                                                                 AuxArg... aux_arg) {
+    static_assert(sizeof...(AuxArg) == (AUX ? 1u : 0u), "the AUX blend takes one AuxIO, the plain one none");
     static_assert(G == 2 || G == 4, "lane groups per wave");
     if (state->overflow) return;              // frame skipped: see k_blend
     constexpr int GL = WAVE / G;              // lanes per group
     constexpr int BH = 16 / G;                // block height: G = 2 -> 8, G = 4 -> 4 (block width is 8; GL lanes x 2 pixels)
     constexpr int NL = 2 * G;                 // lists per tile
     constexpr uint32_t NULL_REC = BLEND_BATCH;
-    // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, pmin, opacity, r | g, b, -, -}.  The
+    // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, pmin, opacity, r | g, b, -, -} (AUX: {.. | g, b, z', slot}).  The
     // lists hold the records' BYTE OFFSETS (16 bits each), so a step's three LDS reads share one address
     // register and differ only in the instruction's immediate offset: no shift / mask per step.
     constexpr uint32_t RS = 48;
@@ -3886,13 +3924,29 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             live1 = s.w > 0.0f;
         }
     }
+    // AUX: the depth sum (D = fma(z', alpha T, D), as a colour channel) and the slot of the last splat blended
+    // while T was above tcut — the pick, once T has crossed tcut (final T > tcut: none)
+    f32x2 D = {0.0f, 0.0f};
+    uint32_t pk0 = PICK_NONE, pk1 = PICK_NONE;
+    const AuxIO aux = aux_io(aux_arg...);
+    if (AUX && ROUNDS && tk.round == 2u) {
+        if (in0) {
+            if (aux.depth) D.x = aux.depth[(uint64_t)py0 * fc.width + px];
+            if (aux.pick) pk0 = aux.pick[(uint64_t)py0 * fc.width + px];
+        }
+        if (in1) {
+            if (aux.depth) D.y = aux.depth[(uint64_t)py1 * fc.width + px];
+            if (aux.pick) pk1 = aux.pick[(uint64_t)py1 * fc.width + px];
+        }
+    }
     f32x2 pyf = {live0 ? (float)py0 + 0.5f : DEAD, live1 ? (float)py1 + 0.5f : DEAD};
     uint32_t remaining = __builtin_amdgcn_readfirstlane(
         (uint32_t)__popcll(__ballot(live0)) + (uint32_t)__popcll(__ballot(live1)));
     if (tid == 0) {   // the null record: power = 0 everywhere, pmin = 1 -> "power >= pmin" never holds
         *(float4 *)(s_rec + NULL_REC * (RS / 4)) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         *(float4 *)(s_rec + NULL_REC * (RS / 4) + 4) = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
-        *(float2 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float2(0.0f, 0.0f);
+        if constexpr (AUX) *(float4 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        else *(float2 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float2(0.0f, 0.0f);
     }
 
     for (uint32_t b0 = start; b0 < end; b0 += BLEND_BATCH) {
@@ -3913,7 +3967,8 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         float mx = 0.0f, my = 0.0f, ca = 0.0f, cb = 0.0f, cc = 0.0f, thr = 0.0f;
         const bool have = j < end;
         if (have) {
-            const uint32_t *rec = recs + (uint64_t)idx[j] * REC_WORDS;
+            const uint32_t slot = idx[j];
+            const uint32_t *rec = recs + (uint64_t)slot * REC_WORDS;
             const u32x4_a4 r0 = *(const u32x4_a4 *)(rec);
             const u32x4_a4 r1 = *(const u32x4_a4 *)(rec + 4);
             const uint32_t r2x = rec[8];
@@ -3925,7 +3980,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                   cull_rounding_slack(mx, my, ca, cb, cc, tx0, ty0);
             *(float4 *)(s_rec + tid * (RS / 4)) = make_float4(mx, my, ca, cb);
             *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(cc, pmin, u2f(r1.y), u2f(r1.z));
-            *(float2 *)(s_rec + tid * (RS / 4) + 8) = make_float2(u2f(r1.w), u2f(r2x));
+            if constexpr (AUX)
+                *(float4 *)(s_rec + tid * (RS / 4) + 8) =
+                    make_float4(u2f(r1.w), u2f(r2x), u2f(aux.depth_keys[slot] + aux.key_bias), u2f(slot));
+            else
+                *(float2 *)(s_rec + tid * (RS / 4) + 8) = make_float2(u2f(r1.w), u2f(r2x));
         }
         // The tile's 2G blocks form a grid of 2 columns x G rows (8 wide, BH high).  The exact
         // maximum of the concave exponent over a block comes from the block's two edges facing the
@@ -4043,7 +4102,17 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             p1 = power.y <= 0.0f && power.y >= BREC.y;                                                        \
         }                                                                                                     \
         if (__builtin_amdgcn_ballot_w64(p0 || p1) != 0ull) {                                                  \
-            const float2 cq = *(const float2 *)(rbase + ID + 32); /* g, b */                                  \
+            float2 cq; /* g, b */                                                                             \
+            float zq = 0.0f; /* AUX: depth, slot */                                                           \
+            uint32_t sq = 0u;                                                                                 \
+            if constexpr (AUX) {                                                                              \
+                const float4 c4 = *(const float4 *)(rbase + ID + 32);                                         \
+                cq = make_float2(c4.x, c4.y);                                                                 \
+                zq = c4.z;                                                                                    \
+                sq = f2u(c4.w);                                                                               \
+            } else {                                                                                          \
+                cq = *(const float2 *)(rbase + ID + 32);                                                      \
+            }                                                                                                 \
             f32x2 alpha;                                                                                      \
             if constexpr (MODE == 0) {                                                                        \
                 /* exp exactly as in k_blend */                                              \
@@ -4083,6 +4152,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             C0 = pk_fma(f32x2{BREC.w, BREC.w}, wgt, C0);                                                      \
             C1 = pk_fma(f32x2{cq.x, cq.x}, wgt, C1);                                                          \
             C2 = pk_fma(f32x2{cq.y, cq.y}, wgt, C2);                                                          \
+            if constexpr (AUX) {                                                                              \
+                D = pk_fma(f32x2{zq, zq}, wgt, D);                                                            \
+                pk0 = alpha_eff.x > 0.0f && T.x > aux.tcut ? sq : pk0;                                        \
+                pk1 = alpha_eff.y > 0.0f && T.y > aux.tcut ? sq : pk1;                                        \
+            }                                                                                                 \
             T = test_T;                                                                                       \
         }                                                                                                     \
     }
@@ -4112,6 +4186,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             if (in1)
                 store16(rgba + (uint64_t)py1 * fc.width + px,
                         make_uint4(f2u(C0.y), f2u(C1.y), f2u(C2.y), f2u(pyf.y == DEAD ? -T.y : T.y)), fc.wt_stores);
+            if constexpr (AUX) {   // the raw D and slot, resumed by round 2
+                if (in0) aux_store(aux, (uint64_t)py0 * fc.width + px, f2u(D.x), pk0, fc.wt_stores);
+                if (in1) aux_store(aux, (uint64_t)py1 * fc.width + px, f2u(D.y), pk1, fc.wt_stores);
+            }
             if (tid == 0 && end > start) atomicOr(tk.open + (tile >> 5), 1u << (tile & 31u));
             return;
         }
@@ -4132,6 +4210,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         o.z = __builtin_fmaf(T.y, fc.bg[2], C2.y);
         o.w = 1.0f - T.y;
         store16(rgba + (uint64_t)py1 * fc.width + px, make_uint4(f2u(o.x), f2u(o.y), f2u(o.z), f2u(o.w)), fc.wt_stores);
+    }
+    if constexpr (AUX) {
+        if (in0) aux_store(aux, (uint64_t)py0 * fc.width + px, f2u(D.x), T.x > aux.tcut ? PICK_NONE : aux_caller_index(aux, pk0), fc.wt_stores);
+        if (in1) aux_store(aux, (uint64_t)py1 * fc.width + px, f2u(D.y), T.y > aux.tcut ? PICK_NONE : aux_caller_index(aux, pk1), fc.wt_stores);
     }
 }
 
