@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "gs_policy.h"
 #include "gs_bundle_kernels.h"
 #include "gs_render_kernels.h"
 #include "gs_pack_kernels.h"
@@ -57,6 +58,73 @@ gs_status gs_fail(gs_status code, uint64_t a, uint64_t b, uint64_t c, const char
     } while (0)
 
 #define fail gs_fail
+
+// ------------------------------------------------------------------------------------------------
+// environment switches (gsp::Switches, gs_policy.h): read once, on the first use of any of them
+// ------------------------------------------------------------------------------------------------
+
+static bool env_on(const char *name) {      // NAME=1 switches on
+    const char *e = std::getenv(name);
+    return e && e[0] == '1';
+}
+static bool env_off(const char *name) {     // NAME=0 switches off
+    const char *e = std::getenv(name);
+    return e && e[0] == '0';
+}
+static long env_int(const char *name, long dflt) {
+    const char *e = std::getenv(name);
+    return e ? std::atol(e) : dflt;
+}
+// the three variables that are read again at every call (parallel_for, gs_device_create, buffer creation)
+static const char *env_now(const char *name) { return std::getenv(name); }
+
+static gsp::Switches read_switches() {
+    gsp::Switches s;
+    s.roctx = env_on("GS3D_ROCTX");
+    s.event_fence = env_on("GS3D_EVENT_FENCE");
+    s.frame_event = env_on("GS3D_FRAME_EVENT");
+    s.test_rank_fault = env_on("GS3D_TEST_RANK_FAULT");
+    if (const char *e = std::getenv("GS3D_TEST_RANK_WATCH")) {
+        s.test_rank_watch_set = true;
+        s.test_rank_watch = (uint32_t)std::strtoul(e, nullptr, 10);
+    }
+    s.rect_v1 = env_on("GS3D_RECT_V1");
+    s.rect32_off = env_off("GS3D_RECT32");
+    s.wt_stores = (int)env_int("GS3D_WT_STORES", s.wt_stores);
+    s.wt_records = (int)env_int("GS3D_WT_RECORDS", s.wt_records);
+    s.scan_rows_small_off = env_off("GS3D_SCAN_ROWS_SMALL");
+    s.nt_scatter = (int)env_int("GS3D_NT_SCATTER", s.nt_scatter);
+    s.chunk_hist_off = env_off("GS3D_CHUNK_HIST");
+    s.narrow_keys_off = env_off("GS3D_NARROW_KEYS");
+    s.xcd_remap_off = env_off("GS3D_XCD_REMAP");
+    s.xcd_remap_c = (int)env_int("GS3D_XCD_REMAP_C", s.xcd_remap_c);
+    s.depth_sort_large = (int)env_int("GS3D_DEPTH_SORT_LARGE", s.depth_sort_large);
+    s.tile_sort_large = (int)env_int("GS3D_TILE_SORT_LARGE", s.tile_sort_large);
+    s.tile_masks = (int)env_int("GS3D_TILE_MASKS", s.tile_masks);
+    s.depth_msd = (int)env_int("GS3D_DEPTH_MSD", s.depth_msd);
+    s.blend_groups = (int)env_int("GS3D_BLEND_GROUPS", s.blend_groups);
+    s.rounds = (int)env_int("GS3D_ROUNDS", s.rounds);
+    s.round1 = env_int("GS3D_ROUND1", s.round1);
+    s.round_partition = (int)env_int("GS3D_ROUND_PARTITION", s.round_partition);
+    s.force_banded = (int)env_int("GS3D_FORCE_BANDED", s.force_banded);
+    s.mask_rec = (int)env_int("GS3D_MASK_REC", s.mask_rec);
+    s.nt_loads = (int)env_int("GS3D_NT_LOADS", s.nt_loads);
+    s.block_cull_off = env_off("GS3D_BLOCK_CULL");
+    s.block_list = (int)env_int("GS3D_BLOCK_LIST", s.block_list);
+    s.pre_serial = env_off("GS3D_PRE_PIPELINE");
+    s.cursor_kernel = (int)env_int("GS3D_CURSOR_KERNEL", s.cursor_kernel);
+    s.expand_xcd = (int)env_int("GS3D_EXPAND_XCD", s.expand_xcd);
+    s.tile_msd = (int)env_int("GS3D_TILE_MSD", s.tile_msd);
+    s.tile_msd_auto = env_on("GS3D_TILE_MSD_AUTO");
+    s.ranges_in_blend = (int)env_int("GS3D_RANGES_IN_BLEND", s.ranges_in_blend);
+    s.ranges_search = (int)env_int("GS3D_RANGES_SEARCH", s.ranges_search);
+    return s;
+}
+
+static const gsp::Switches &switches() {
+    static const gsp::Switches s = read_switches();
+    return s;
+}
 
 extern "C" void gs_last_error(gs_error_info *out) {
     if (out) *out = t_err;
@@ -143,7 +211,7 @@ template <class F>
 static void parallel_for(size_t n, F fn) {
     unsigned hw = std::thread::hardware_concurrency();
     size_t threads = n < 65536 ? 1 : (hw ? (hw > 32 ? 32 : hw) : 4);
-    if (const char *e = std::getenv("GS3D_HOST_THREADS")) threads = std::atoi(e) > 0 ? (size_t)std::atoi(e) : threads;
+    if (const char *e = env_now("GS3D_HOST_THREADS")) threads = std::atoi(e) > 0 ? (size_t)std::atoi(e) : threads;
     if (threads <= 1) {
         fn((size_t)0, n);
         return;
@@ -254,7 +322,7 @@ struct gs_device {
     hipStream_t internal;  // for blocking helper work
     // probe result: returning LDS atomics hand out lane-ordered values.  Written by any renderer of the device whose rank
     // watchdog fired (gs_render_frame / gs_renderer_wait_frame, possibly from different host threads) and read once per
-    // frame (t_rank_fault) and by the stand-alone sorts: atomic, relaxed — it only ever goes from true to false.
+    // frame (SortCtx::fast_rank) and by the stand-alone sorts: atomic, relaxed — it only ever goes from true to false.
     std::atomic<bool> lds_atomic_ordered{false};
     // renderers of this device: gs_stream_destroy records the end-of-frame event of those whose last frame sits on the
     // stream that is going away (the event is otherwise recorded lazily, when the renderer moves to another stream)
@@ -314,7 +382,7 @@ extern "C" gs_status gs_device_create(int32_t ordinal, gs_device **out) {
     }
     // probe the LDS-atomic ordering the fast radix ranking relies on (gs_render_kernels.h)
     d->lds_atomic_ordered = false;
-    if (!std::getenv("GS3D_DISABLE_FAST_RANK")) {
+    if (!env_now("GS3D_DISABLE_FAST_RANK")) {
         uint32_t *bad = nullptr;
         if (hipMalloc((void **)&bad, 4) == hipSuccess) {
             uint32_t h = 1;
@@ -643,7 +711,7 @@ extern "C" gs_status gs_gaussians_buffer_from_buffer(gs_buffer *buffer, gs_sh_co
     g->planar = nullptr;
     g->planar_stride = 0;
     {   // default: spatial order on; GS3D_SPATIAL_ORDER=0 keeps the mirror in index order
-        const char *e = std::getenv("GS3D_SPATIAL_ORDER");
+        const char *e = env_now("GS3D_SPATIAL_ORDER");
         g->spatial = !(e && e[0] == '0');
     }
     g->order = nullptr;
@@ -1487,11 +1555,8 @@ struct gs_renderer {
     DevArray chunk_hist;                  // [chunks][256] first-digit histogram of every chunk's depth keys (PreOut::chunk_hist)
     bool list_mode = false;               // the last frame's per-slot arrays are in LIST space (k_block_cull ran)
     bool rank_inject_set = false;         // GS3D_TEST_RANK_FAULT: the watchdog's test hook has been armed
-    // Depth sort of the frame: MSD-first (one scatter on the top digit + k_bucket_sort) or the LSD passes.  The choice
-    // follows the largest top-digit bucket the last frames reported (FrameResult::depth_bucket_max): MSD-first while
-    // the buckets fit a workgroup's registers, LSD while they do not; a shape's first frame guesses from N.
-    bool depth_msd = false;               // mode of the last frame
-    uint32_t depth_bucket_seen = 0;       // newest reported bucket size the mode was chosen from (diagnostic)
+    gsp::SortFeedback sort_fb;            // which depth / tile sort, and what the choice rests on (gs_policy.h)
+    gsp::RoundsFeedback rounds_fb;        // one round or two, the length of round 1, partitioned or not (gs_policy.h)
     bool tile_msd = false;                // the tile sort of the last frame was MSD-first
     int depth_msd_req = -1, tile_msd_req = -1;   // gs_renderer_set_sort_mode: -1 = the renderer chooses
     int tile_masks_req = -1;              // gs_renderer_set_tile_masks
@@ -1501,24 +1566,9 @@ struct gs_renderer {
     int rounds_req = -1;                  // gs_renderer_set_rounds: -1 the renderer decides, 0 one round, 1 two
     uint32_t round1_req = 0;              // ... Gaussians of round 1 (0: a quarter of the visible ones)
     uint32_t round1 = 0;                  // Gaussians the last two-round frame's first round covered
-    // what the renderer's own choice of the rounds rests on: the pair count of a single-round frame of this shape (the
-    // sizing pass's, or the newest single-round report with the visible count it came with), the rounds of the frames
-    // behind the two result blocks, and the feedback state (the length of round 1 is scaled up while round 1 finishes
-    // too few tiles; past 3.4 x the renderer stays with one round until the shape changes)
-    uint64_t full_pairs = 0;
-    uint32_t full_pairs_v = 0, rounds_epoch = 0, rounds_fb_gen = 0;
-    uint8_t done_rounds[2] = {1, 1};
+    uint8_t done_rounds[2] = {1, 1};      // the rounds of the frames behind the two result blocks, and their round-1 lengths
     uint32_t done_round_k[2] = {0, 0};
-    float round_scale = 1.0f;
-    bool rounds_off = false;
-    uint32_t rounds_off_gen = 0;          // the frame that switched the rounds off (another try 512 frames later)
-    uint64_t round_cap = 0;               // the pair bound the last two-round frame used for its grids (0: the buffers' capacity)
-    uint32_t round_cap_k = 0;             // ... and the length of round 1 it was measured with
-    bool auto_deep = false;               // the renderer's last own choice (kept while no report is available)
-    bool auto_all_done = false;           // the newest two-round report of this shape: round 1 finished every tile (round 2 was skipped)
-    uint64_t auto_k = 0;
     bool wt_pairs = true;                 // k_pairs_emit stores write-through (gs::store16)
-    uint64_t tile_msd_fail_d = 0;         // pair count at which the MSD-first tile sort last reported an oversized bucket (0: never)
     bool state_tile_bmax_dirty = false;   // FrameState::tile_bucket_max holds a value of an MSD-first frame
     uint32_t cull_last_gen = 0, cull_last_groups = 0;   // frame / group count of the last k_block_cull (status tags)
     DevArray dkeys[2], dvals[2];          // (depth bits - bias, mirror slot), capacity N
@@ -1588,8 +1638,8 @@ extern "C" gs_status gs_renderer_create(gs_device *dev, gs_renderer **out) {
     for (int i = 0; i < 2 && e == hipSuccess; i++) {
         // no system-scope fence at the event: what the host reads after it (the frame result) lives in
         // coherent pinned memory, and images are fetched with copies that synchronise by themselves
-        static const bool fence = std::getenv("GS3D_EVENT_FENCE") && std::getenv("GS3D_EVENT_FENCE")[0] == '1';
-        e = hipEventCreateWithFlags(&r->done[i], hipEventDisableTiming | (fence ? 0u : hipEventDisableSystemFence));
+        // (GS3D_EVENT_FENCE=1 asks for the fence)
+        e = hipEventCreateWithFlags(&r->done[i], hipEventDisableTiming | (switches().event_fence ? 0u : hipEventDisableSystemFence));
         r->done_valid[i] = false;
         r->done_gen[i] = 0;
         r->done_shape[i] = 0;
@@ -1767,7 +1817,7 @@ extern "C" gs_status gs_renderer_sort_info(gs_renderer *r, gs_sort_info *out) {
     if (!r->have_frame) return GS_OK;
     GS_HIP(sync_last_frame(r));
     const gs::FrameResult &fr = last_result(r);
-    out->depth_msd = r->depth_msd ? 1u : 0u;
+    out->depth_msd = r->sort_fb.depth_msd ? 1u : 0u;
     out->depth_bucket_max = fr.gen == r->gen ? fr.depth_bucket_max : 0u;
     out->tile_msd = r->tile_msd ? 1u : 0u;
     out->tile_masks = r->tile_masks ? 1u : 0u;
@@ -1868,23 +1918,20 @@ static void make_frame_consts(const gs_gaussian_transform_pod *gt, const gs_mode
     // GS3D_RECT_V1=1 keeps the unclipped rect of spec version 1 (same images, more pairs) for A/B runs
     // and for the parity tests against the version-1 goldens.
     {
-        static const bool rect_v1 = std::getenv("GS3D_RECT_V1") && std::getenv("GS3D_RECT_V1")[0] == '1';
-        fc.clip_rect = gt->flags[0] == GS_DISPLAY_SPLAT && !rect_v1 ? 1u : 0u;
+        fc.clip_rect = gt->flags[0] == GS_DISPLAY_SPLAT && !switches().rect_v1 ? 1u : 0u;
         // rect version 4: small rects lose the tiles their splat cannot reach.  GS3D_TILE_MASKS=0: version 3
         // (make_frame_consts only records that the display mode allows it; gs_render_frame decides: gs_renderer_set_tile_masks)
         fc.tile_masks = fc.clip_rect;
     }
     fc.ellipse_pmin = -0.5f * (fc.max_std_dev * fc.max_std_dev);
     {   // packed 4-byte tile rects while both tile counts fit 8 bits (images up to 4096 px); GS3D_RECT32=0: always uint2
-        static const bool rect32_off = std::getenv("GS3D_RECT32") && std::getenv("GS3D_RECT32")[0] == '0';
-        fc.rect32 = !rect32_off && fc.tiles_x <= 256u && fc.tiles_y <= 256u && fc.tiles_x * fc.tiles_y <= 32768u ? 1u : 0u;
+        fc.rect32 = !switches().rect32_off && fc.tiles_x <= 256u && fc.tiles_y <= 256u && fc.tiles_x * fc.tiles_y <= 32768u ? 1u : 0u;
         // write-through stores of the 16-byte-per-lane outputs (gs::store16).  GS3D_WT_STORES=0/1
         // GS3D_WT_STORES: bit 0 = the pairs of k_pairs_emit, bit 1 = the image
-        static const int wt_env = std::getenv("GS3D_WT_STORES") ? std::atoi(std::getenv("GS3D_WT_STORES")) : 3;
+        const int wt_env = switches().wt_stores;
         fc.wt_stores = (wt_env & 2) ? 1u : 0u;
         fc.wt_pairs = (wt_env & 1) ? 1u : 0u;
-        static const int wtr_env = std::getenv("GS3D_WT_RECORDS") ? std::atoi(std::getenv("GS3D_WT_RECORDS")) : 0;
-        fc.wt_records = (uint32_t)wtr_env & 3u;
+        fc.wt_records = (uint32_t)switches().wt_records & 3u;
     }
     // block culling gain (see block_is_culled): size^2 |W R_m S_m|_2^2, the squared SPECTRAL norm of the linear part
     // whatever the caller's view and model matrices are: the largest eigenvalue of A = (WS)^T (WS), in double by the
@@ -1941,6 +1988,36 @@ static uint32_t first_digit_mask(uint32_t key_bits, uint32_t rb) {
     return (1u << bits) - 1u;
 }
 
+// What every sort launch of one frame (or of one stand-alone sort) needs.  The rank watchdog's words travel here:
+// `rank_fault` = FrameState::rank_fault while the frame sorts with the LDS-atomic rank (null in the stand-alone sorts,
+// which are not watched, and once the device has dropped to the ballot-based rank); `watch` = the watchdog's sample of
+// this frame (gs::k_sort_scatter: tile = watch mod live tiles, round = (watch / live tiles) mod ITEMS; the frame
+// generation, so that every position is visited over a few hundred frames).  `fast_rank` (FAST_RANK of the kernels) is
+// read ONCE per frame: every scatter of the frame ranks the same way, whatever another renderer's thread does.
+struct SortCtx {
+    const gs_device *dev = nullptr;
+    hipStream_t st = nullptr;
+    DevArray *ghist = nullptr, *digit_totals = nullptr;
+    uint32_t *rank_fault = nullptr;
+    uint32_t watch = 0;
+    bool fast_rank = false;
+    uint32_t *launches = nullptr;      // the frame's launch counter (null: not counted)
+    void count(uint32_t k) const {
+        if (launches) *launches += k;
+    }
+};
+
+// a sort outside a frame: not watched
+static SortCtx standalone_sort_ctx(const gs_device *dev, hipStream_t st, DevArray &ghist, DevArray &digit_totals) {
+    SortCtx c;
+    c.dev = dev;
+    c.st = st;
+    c.ghist = &ghist;
+    c.digit_totals = &digit_totals;
+    c.fast_rank = dev->lds_atomic_ordered.load(std::memory_order_relaxed);
+    return c;
+}
+
 // The frame's compacting first pass (see gs_render_kernels.h, COMPACT): dense keys in, the index is
 // the value, chunks without visible Gaussians are skipped, V comes out in *visible_out.
 struct SortCompact {
@@ -1950,19 +2027,35 @@ struct SortCompact {
     uint32_t dense_count = 0;        // N: the first pass runs over all slots (host bound: sizes the grid)
     const uint32_t *dense_count_dev = nullptr;   // optional device word: the slots that really hold data (list frames)
     const uint32_t *chunk_hist = nullptr;        // per-chunk histogram of the first digit, counted by the preprocess kernel
+    gs::CompactPred pred;            // which side of a partitioned two-round frame's depth threshold the pass keeps (default: all)
+    uint32_t *bucket_max = nullptr;  // receives the largest top-digit bucket (only the LSD sort's LAST pass reports it)
 };
 
-// Stable LSD radix sort of (key, u32 value) pairs on key bits [0, end_bit), RB bits per pass at
-// most (digit widths balanced over the passes), ping-ponging between side 0 and side 1; the side
-// holding the result is returned.  `sc` = host bound of the count (sizes the grid) and, optionally,
-// the device word holding the real count.  With `compact`, pass 0 reads keys[0] as the dense key
-// array of preprocess and ignores vals[0].
+// one radix pass (histogram -> row scan -> scatter): what varies from pass to pass.  Keys are typed by the launcher's
+// template arguments (KI in, KO out).
+struct RadixPass {
+    const void *kin = nullptr;
+    const uint32_t *vin = nullptr;
+    void *kout = nullptr;
+    uint32_t ko_shift = 0;
+    uint32_t *vout = nullptr;
+    gs::SortCount sc{0, nullptr};
+    uint32_t shift = 0, digit_mask = 0;
+    uint32_t nb = 0, sgrid = 0, xr = 0;          // tiles, padded grid and span of the XCD-aware order (xcd_span_for)
+    const uint32_t *chunk_vis = nullptr;         // COMPACT passes
+    uint32_t *visible_out = nullptr;
+    gs::CompactPred pred;
+    const uint32_t *chunk_hist = nullptr;        // ... whose histogram the preprocess kernel counted per chunk
+    uint32_t chunk_hist_words = (uint32_t)gs::PP_THREADS;
+    uint32_t *bucket_max = nullptr;              // the depth sort's pass on its top digit
+    uint32_t *bucket_starts = nullptr;           // the MSD-first sorts' scatter pass writes every bucket's start here
+};
+
 template <int TILE>
 static void launch_scan_rows(uint32_t rows, hipStream_t st, uint32_t *ghist, uint32_t stride, gs::SortCount sc,
                              uint32_t *totals) {
     // rows of up to SCAN_ROWS_SMALL_MAX blocks (stride = the host's bound of the block count): one wave per row
-    static const bool small_off = std::getenv("GS3D_SCAN_ROWS_SMALL") && std::getenv("GS3D_SCAN_ROWS_SMALL")[0] == '0';
-    if (stride <= gs::SCAN_ROWS_SMALL_MAX && !small_off)
+    if (stride <= gs::SCAN_ROWS_SMALL_MAX && !switches().scan_rows_small_off)
         hipLaunchKernelGGL((gs::k_sort_scan_rows_small<TILE>), dim3((rows + 3u) / 4u), dim3(256), 0, st, ghist, stride, sc,
                            totals, rows);
     else
@@ -1970,100 +2063,94 @@ static void launch_scan_rows(uint32_t rows, hipStream_t st, uint32_t *ghist, uin
                            totals);
 }
 
-// Watchdog word of the LDS-atomic rank for the scatters launched by the current gs_render_frame call (FrameState::
-// rank_fault; null outside a frame: the stand-alone sorts are not watched).  Thread-local instead of one more
-// parameter through five levels of sort templates.
-static thread_local uint32_t *t_rank_fault = nullptr;
-// ... and what else the frame hands its scatters the same way: the watchdog's sample of this frame (gs::k_sort_scatter:
-// tile = watch mod live tiles, round = (watch / live tiles) mod ITEMS; the frame generation, so that every position is
-// visited over a few hundred frames), and the word that receives the largest top-digit bucket of the depth sort
-// (only the LSD sort's LAST pass gets it: t_top_pass).
-static thread_local uint32_t t_watch = 0;
-static thread_local uint32_t *t_bucket_max = nullptr;
-static thread_local bool t_top_pass = false;
-static thread_local uint32_t *t_bucket_starts = nullptr;    // the MSD-first sorts' scatter pass writes every bucket's start here
-// ... and which side of a partitioned two-round frame's depth threshold the COMPACT pass keeps (gs::CompactPred; default: all)
-static thread_local gs::CompactPred t_compact_pred;
+// FAST_RANK of a kernel: chosen by the device probe and the frame's watchdog (SortCtx::fast_rank); fn(tag, rank_fault, watch)
+template <class F>
+static void with_rank(const SortCtx &c, F fn) {
+    if (c.fast_rank) fn(std::true_type(), c.rank_fault, c.rank_fault ? c.watch : 0u);
+    else fn(std::false_type(), (uint32_t *)nullptr, 0u);
+}
 
-// one scatter launch (FAST_RANK chosen by the device probe); KO = type of the keys the pass writes
+// one scatter launch; KO = type of the keys the pass writes
 template <typename KI, typename KO, int RB, bool COMPACT, int ITEMS>
-static void launch_scatter(const gs_device *dev, hipStream_t st, uint32_t sgrid, const KI *kin, const uint32_t *vin, KO *kout,
-                           uint32_t ko_shift, uint32_t *vout, gs::SortCount psc, uint32_t shift, uint32_t digit_mask,
-                           const uint32_t *ghist, const uint32_t *totals, const uint32_t *cv, uint32_t *vo, uint32_t pnb,
-                           uint32_t xr) {
+static void launch_scatter(const SortCtx &c, const RadixPass &p) {
     // inputs that cannot stay in the L2s anyway are read non-temporally (top bit of the last argument; see
     // k_sort_scatter).  GS3D_NT_SCATTER=0/1 forces.
-    static const int nt_env = std::getenv("GS3D_NT_SCATTER") ? std::atoi(std::getenv("GS3D_NT_SCATTER")) : -1;
-    const bool nt = !COMPACT && (nt_env >= 0 ? nt_env != 0 : (uint64_t)psc.count * (sizeof(KI) + 4u) > (32ull << 20));
-    const uint32_t xr_nt = xr | (nt ? 0x80000000u : 0u);
-    uint32_t *bmax = t_top_pass ? t_bucket_max : nullptr;
-    // FAST_RANK: chosen by the device probe and the frame's watchdog (t_rank_fault: null outside a frame and once the device
-    // has dropped to the ballot-based rank); PRED: a partitioned two-round frame's compacting pass (t_compact_pred)
-    auto go = [&](auto fast_tag, auto pred_tag, uint32_t *rf, uint32_t watch) {
-        constexpr bool FAST = decltype(fast_tag)::value, PRED = decltype(pred_tag)::value;
-        hipLaunchKernelGGL((gs::k_sort_scatter<KI, FAST, RB, COMPACT, ITEMS, KO, PRED>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st, kin, vin,
-                           kout, ko_shift, vout, psc, shift, digit_mask, ghist, totals, cv, vo, pnb, xr_nt, rf, watch, bmax, t_bucket_starts,
-                           PRED ? t_compact_pred : gs::CompactPred());
+    const int nt_env = switches().nt_scatter;
+    const bool nt = !COMPACT && (nt_env >= 0 ? nt_env != 0 : (uint64_t)p.sc.count * (sizeof(KI) + 4u) > (32ull << 20));
+    const uint32_t xr_nt = p.xr | (nt ? 0x80000000u : 0u);
+    const uint32_t *ghist = (const uint32_t *)c.ghist->ptr, *totals = (const uint32_t *)c.digit_totals->ptr;
+    // PRED: a partitioned two-round frame's compacting pass (RadixPass::pred)
+    auto go = [&](auto pred_tag) {
+        with_rank(c, [&](auto fast_tag, uint32_t *rf, uint32_t watch) {
+            constexpr bool FAST = decltype(fast_tag)::value, PRED = decltype(pred_tag)::value;
+            hipLaunchKernelGGL((gs::k_sort_scatter<KI, FAST, RB, COMPACT, ITEMS, KO, PRED>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st,
+                               (const KI *)p.kin, p.vin, (KO *)p.kout, p.ko_shift, p.vout, p.sc, p.shift, p.digit_mask, ghist, totals, p.chunk_vis,
+                               p.visible_out, p.nb, xr_nt, rf, watch, p.bucket_max, p.bucket_starts, PRED ? p.pred : gs::CompactPred());
+        });
     };
-    const bool fast = t_rank_fault || dev->lds_atomic_ordered.load(std::memory_order_relaxed);
-    uint32_t *rf = t_rank_fault;
-    const uint32_t watch = t_rank_fault ? t_watch : 0u;
     if constexpr (COMPACT) {
-        if (t_compact_pred.tau_dev) {
-            if (fast) go(std::true_type(), std::true_type(), rf, watch);
-            else go(std::false_type(), std::true_type(), (uint32_t *)nullptr, 0u);
+        if (p.pred.tau_dev) {
+            go(std::true_type());
             return;
         }
     }
-    if (fast) go(std::true_type(), std::false_type(), rf, watch);
-    else go(std::false_type(), std::false_type(), (uint32_t *)nullptr, 0u);
+    go(std::false_type());
 }
 
 // one radix pass: histogram -> row scan -> scatter
 template <typename KI, typename KO, int RB, bool COMPACT, int ITEMS>
-static void launch_pass(const gs_device *dev, hipStream_t st, uint32_t sgrid, const KI *kin, const uint32_t *vin, KO *kout,
-                        uint32_t ko_shift, uint32_t *vout, gs::SortCount psc, uint32_t shift, uint32_t digit_mask, DevArray &ghist,
-                        DevArray &digit_totals, const uint32_t *cv, uint32_t *vo, uint32_t pnb, uint32_t xr,
-                        const uint32_t *chunk_hist = nullptr, uint32_t chunk_hist_words = (uint32_t)gs::PP_THREADS) {
-    constexpr uint32_t R = 1u << RB;
+static void launch_pass(const SortCtx &c, const RadixPass &p) {
     constexpr int TILE = gs::SORT_THREADS * ITEMS;
-    // GS3D_CHUNK_HIST=0: the compacting pass counts its histogram from the keys again (A/B, tests)
-    static const bool chunk_hist_off = std::getenv("GS3D_CHUNK_HIST") && std::getenv("GS3D_CHUNK_HIST")[0] == '0';
+    uint32_t *ghist = (uint32_t *)c.ghist->ptr;
     bool summed = false;
     if constexpr (COMPACT && TILE % gs::PP_CHUNK == 0) {
-        if (chunk_hist && !chunk_hist_off) {
+        // GS3D_CHUNK_HIST=0: the compacting pass counts its histogram from the keys again (A/B, tests)
+        if (p.chunk_hist && !switches().chunk_hist_off) {
             // the preprocess kernel counted this digit per chunk: sum the chunks' rows instead of re-reading the keys
-            hipLaunchKernelGGL((gs::k_sort_hist_chunks<RB, ITEMS>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st, chunk_hist, psc,
-                               digit_mask, (uint32_t *)ghist.ptr, cv, pnb, xr, chunk_hist_words);
+            hipLaunchKernelGGL((gs::k_sort_hist_chunks<RB, ITEMS>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st, p.chunk_hist, p.sc,
+                               p.digit_mask, ghist, p.chunk_vis, p.nb, p.xr, p.chunk_hist_words);
             summed = true;
         }
     }
     if (!summed) {
         bool done = false;
         if constexpr (COMPACT) {
-            if (t_compact_pred.tau_dev) {
-                hipLaunchKernelGGL((gs::k_sort_hist<KI, RB, COMPACT, ITEMS, true>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st, kin, psc, shift,
-                                   digit_mask, (uint32_t *)ghist.ptr, cv, pnb, xr, t_compact_pred);
+            if (p.pred.tau_dev) {
+                hipLaunchKernelGGL((gs::k_sort_hist<KI, RB, COMPACT, ITEMS, true>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st,
+                                   (const KI *)p.kin, p.sc, p.shift, p.digit_mask, ghist, p.chunk_vis, p.nb, p.xr, p.pred);
                 done = true;
             }
         }
         if (!done)
-            hipLaunchKernelGGL((gs::k_sort_hist<KI, RB, COMPACT, ITEMS>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st, kin, psc, shift,
-                               digit_mask, (uint32_t *)ghist.ptr, cv, pnb, xr, gs::CompactPred());
+            hipLaunchKernelGGL((gs::k_sort_hist<KI, RB, COMPACT, ITEMS>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st, (const KI *)p.kin,
+                               p.sc, p.shift, p.digit_mask, ghist, p.chunk_vis, p.nb, p.xr, gs::CompactPred());
     }
-    (void)R;
-    launch_scan_rows<TILE>(digit_mask + 1u, st, (uint32_t *)ghist.ptr, pnb, psc, (uint32_t *)digit_totals.ptr);   // live rows only
-    launch_scatter<KI, KO, RB, COMPACT, ITEMS>(dev, st, sgrid, kin, vin, kout, ko_shift, vout, psc, shift, digit_mask,
-                                               (const uint32_t *)ghist.ptr, (const uint32_t *)digit_totals.ptr, cv, vo, pnb, xr);
+    launch_scan_rows<TILE>(p.digit_mask + 1u, c.st, ghist, p.nb, p.sc, (uint32_t *)c.digit_totals->ptr);   // live rows only
+    launch_scatter<KI, KO, RB, COMPACT, ITEMS>(c, p);
 }
 
-static uint32_t xcd_span_for(uint32_t pnb, uint32_t &sgrid);
+// XCD-aware tile order of a radix pass over `pnb` tiles (see run_sort_items): the span factor and the padded grid
+static uint32_t xcd_span_for(uint32_t pnb, uint32_t &sgrid) {
+    const int remap_c = switches().xcd_remap_c;
+    uint32_t xr = 0;
+    if (!switches().xcd_remap_off && pnb >= 256u) {
+        xr = 4u;
+        while (xr < 64u && xr * 2u * 256u <= pnb) xr *= 2u;
+        if (remap_c > 1) xr = (uint32_t)remap_c;
+    }
+    sgrid = xr ? 8u * xr * ((pnb + 8u * xr - 1u) / (8u * xr)) : pnb;
+    return xr;
+}
 
+// Stable LSD radix sort of (key, u32 value) pairs on key bits [0, end_bit), RB bits per pass at
+// most (digit widths balanced over the passes), ping-ponging between side 0 and side 1; the side
+// holding the result is returned.  `sc` = host bound of the count (sizes the grid) and, optionally,
+// the device word holding the real count.  With `compact`, pass 0 reads keys[0] as the dense key
+// array of preprocess and ignores vals[0].
 template <typename K, int RB, int ITEMS>
-static gs_status run_sort_items(const gs_device *dev, void *const keys[2], void *const vals[2], DevArray &ghist,
-                             DevArray &digit_totals, gs::SortCount sc, uint32_t end_bit, const SortCompact *compact,
-                             hipStream_t st, int &result_side, uint32_t &passes_out, uint32_t &launches,
-                             const gs::ExpandIO *source = nullptr) {
+static gs_status run_sort_items(const SortCtx &c, void *const keys[2], void *const vals[2], gs::SortCount sc, uint32_t end_bit,
+                                const SortCompact *compact, int &result_side, uint32_t &passes_out,
+                                const gs::ExpandIO *source = nullptr) {
     constexpr uint32_t R = 1u << RB;
     constexpr uint32_t TILE = (uint32_t)(gs::SORT_THREADS * ITEMS);
     uint32_t passes = (end_bit + RB - 1) / RB;
@@ -2072,98 +2159,90 @@ static gs_status run_sort_items(const gs_device *dev, void *const keys[2], void 
     result_side = 0;
     if (sc.count == 0 || passes == 0) return GS_OK;
     const uint32_t nb = (uint32_t)(((uint64_t)sc.count + TILE - 1) / TILE);
-    GS_TRY(dev_reserve(ghist, (size_t)nb * R * 4));
-    GS_TRY(dev_reserve(digit_totals, R * 4));
+    GS_TRY(dev_reserve(*c.ghist, (size_t)nb * R * 4));
+    GS_TRY(dev_reserve(*c.digit_totals, R * 4));
     int side = 0;
     uint32_t shift = 0;
-    for (uint32_t p = 0; p < passes; p++) {
+    for (uint32_t i = 0; i < passes; i++) {
         // balanced digit widths: e.g. 13 bits -> 7 + 6, 15 -> 8 + 7, 27 -> 9 + 9 + 9, 32 -> 8 + 8 + 8 + 8
-        const uint32_t bits = end_bit > shift ? (end_bit - shift + (passes - p) - 1) / (passes - p) : 0u;
-        const uint32_t digit_mask = (1u << bits) - 1u;
-        const bool first = compact && p == 0;
-        const K *kin = first ? (const K *)compact->dense_keys : (const K *)keys[side];
-        const uint32_t *vin = (const uint32_t *)vals[side];
+        const uint32_t bits = end_bit > shift ? (end_bit - shift + (passes - i) - 1) / (passes - i) : 0u;
+        const bool first = compact && i == 0, last = i == passes - 1;
+        RadixPass p;
+        p.shift = shift;
+        p.digit_mask = (1u << bits) - 1u;
+        p.kin = first ? (const void *)compact->dense_keys : keys[side];
+        p.vin = (const uint32_t *)vals[side];
         // the sorted depth keys themselves are never read (compact = the frame's depth sort): its last pass
         // writes the order only
-        K *kout = compact && p == passes - 1 ? (K *)nullptr : (K *)keys[side ^ 1];
-        uint32_t *vout = (uint32_t *)vals[side ^ 1];
-        const gs::SortCount psc = first ? gs::SortCount{compact->dense_count, compact->dense_count_dev} : sc;
-        const uint32_t pnb = first ? (uint32_t)(((uint64_t)compact->dense_count + TILE - 1) / TILE) : nb;
-        if (first) GS_TRY(dev_reserve(ghist, (size_t)pnb * R * 4));
-        const uint32_t *cv = first ? compact->chunk_vis : nullptr;
-        uint32_t *vo = first ? compact->visible_out : nullptr;
+        p.kout = compact && last ? nullptr : keys[side ^ 1];
+        p.vout = (uint32_t *)vals[side ^ 1];
+        p.sc = first ? gs::SortCount{compact->dense_count, compact->dense_count_dev} : sc;
+        p.nb = first ? (uint32_t)(((uint64_t)compact->dense_count + TILE - 1) / TILE) : nb;
+        if (first) GS_TRY(dev_reserve(*c.ghist, (size_t)p.nb * R * 4));
+        if (first) {
+            p.chunk_vis = compact->chunk_vis;
+            p.visible_out = compact->visible_out;
+            p.chunk_hist = compact->chunk_hist;
+        }
+        if (compact) p.pred = compact->pred;
         // XCD-aware tile order in the scatter (see scatter_tile_of): XCD x takes `xr` consecutive tiles
         // of every group of 8 * xr.  xr grows with the number of tiles (a group must stay a small part
         // of the pass) between 4 and 64.  GS3D_XCD_REMAP=0 disables, GS3D_XCD_REMAP_C=<n> forces a size.
-        uint32_t sgrid = 0;
-        const uint32_t xr = xcd_span_for(pnb, sgrid);
-        t_top_pass = compact != nullptr && p == passes - 1;   // the depth sort's pass on its top digit reports the largest bucket
-        if (source && p == 0) {
+        p.xr = xcd_span_for(p.nb, p.sgrid);
+        if (compact && last) p.bucket_max = compact->bucket_max;   // the depth sort's pass on its top digit reports the largest bucket
+        if (source && i == 0) {
             // the pairs come from the depth-ordered rects: k_pairs_emit writes this pass's input
             // (keys[side] / vals[side]) and its histogram at once
             if constexpr (sizeof(K) <= 4) {
                 gs::ExpandIO src = *source;
                 src.tvals = (uint32_t *)vals[side];
                 if (sizeof(K) == 2 && src.rect32)
-                    hipLaunchKernelGGL((gs::k_pairs_emit<K, RB, ITEMS, sizeof(K) == 2>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st,
-                                       src, digit_mask, (uint32_t *)ghist.ptr, (K *)keys[side], pnb, xr, 0u);
+                    hipLaunchKernelGGL((gs::k_pairs_emit<K, RB, ITEMS, sizeof(K) == 2>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st,
+                                       src, p.digit_mask, (uint32_t *)c.ghist->ptr, (K *)keys[side], p.nb, p.xr, 0u);
                 else
-                    hipLaunchKernelGGL((gs::k_pairs_emit<K, RB, ITEMS, false>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st, src,
-                                       digit_mask, (uint32_t *)ghist.ptr, (K *)keys[side], pnb, xr, 0u);
-                launch_scan_rows<(int)TILE>(digit_mask + 1u, st, (uint32_t *)ghist.ptr, pnb, psc, (uint32_t *)digit_totals.ptr);
-                launch_scatter<K, K, RB, false, ITEMS>(dev, st, sgrid, kin, vin, kout, 0u, vout, psc, shift, digit_mask,
-                                                       (const uint32_t *)ghist.ptr, (const uint32_t *)digit_totals.ptr, cv, vo, pnb, xr);
+                    hipLaunchKernelGGL((gs::k_pairs_emit<K, RB, ITEMS, false>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st, src,
+                                       p.digit_mask, (uint32_t *)c.ghist->ptr, (K *)keys[side], p.nb, p.xr, 0u);
+                launch_scan_rows<(int)TILE>(p.digit_mask + 1u, c.st, (uint32_t *)c.ghist->ptr, p.nb, p.sc, (uint32_t *)c.digit_totals->ptr);
+                launch_scatter<K, K, RB, false, ITEMS>(c, p);
             }
         } else if constexpr (sizeof(K) == 4) {
             // Narrow keys (the frame's depth sort only): the pass BEFORE the last stores key >> (shift of
             // the last pass) as u16 — all the last pass still needs — and the last pass runs on 16-bit keys:
             // 2 bytes less per element written, 2 x 2 bytes less read.  GS3D_NARROW_KEYS=0 switches it off.
-            static const bool narrow_on = !(std::getenv("GS3D_NARROW_KEYS") && std::getenv("GS3D_NARROW_KEYS")[0] == '0');
-            const bool narrow = narrow_on && compact && passes >= 2;
-            const bool writes_narrow = narrow && p == passes - 2, reads_narrow = narrow && p == passes - 1;
+            const bool narrow = !switches().narrow_keys_off && compact && passes >= 2;
+            const bool writes_narrow = narrow && i == passes - 2, reads_narrow = narrow && last;
             if (reads_narrow) {
-                launch_pass<uint16_t, uint16_t, RB, false, ITEMS>(dev, st, sgrid, (const uint16_t *)keys[side], vin, (uint16_t *)nullptr, 0u,
-                                                                  vout, psc, 0u, digit_mask, ghist, digit_totals, cv, vo, pnb, xr);
+                p.kout = nullptr;
+                p.shift = 0u;
+                launch_pass<uint16_t, uint16_t, RB, false, ITEMS>(c, p);
             } else if (writes_narrow) {
-                const uint32_t next_shift = shift + bits;
-                if (first)
-                    launch_pass<uint32_t, uint16_t, RB, true, ITEMS>(dev, st, sgrid, (const uint32_t *)kin, vin, (uint16_t *)keys[side ^ 1],
-                                                                     next_shift, vout, psc, shift, digit_mask, ghist, digit_totals, cv, vo, pnb, xr,
-                                                                     compact->chunk_hist);
-                else
-                    launch_pass<uint32_t, uint16_t, RB, false, ITEMS>(dev, st, sgrid, (const uint32_t *)kin, vin, (uint16_t *)keys[side ^ 1],
-                                                                      next_shift, vout, psc, shift, digit_mask, ghist, digit_totals, cv, vo, pnb, xr);
+                p.kout = keys[side ^ 1];
+                p.ko_shift = shift + bits;
+                if (first) launch_pass<uint32_t, uint16_t, RB, true, ITEMS>(c, p);
+                else launch_pass<uint32_t, uint16_t, RB, false, ITEMS>(c, p);
             } else if (first) {
-                launch_pass<K, K, RB, true, ITEMS>(dev, st, sgrid, kin, vin, kout, 0u, vout, psc, shift, digit_mask, ghist, digit_totals, cv, vo, pnb, xr,
-                                                   compact->chunk_hist);
+                launch_pass<K, K, RB, true, ITEMS>(c, p);
             } else {
-                launch_pass<K, K, RB, false, ITEMS>(dev, st, sgrid, kin, vin, kout, 0u, vout, psc, shift, digit_mask, ghist, digit_totals, cv, vo, pnb, xr);
+                launch_pass<K, K, RB, false, ITEMS>(c, p);
             }
         } else {
-            launch_pass<K, K, RB, false, ITEMS>(dev, st, sgrid, kin, vin, kout, 0u, vout, psc, shift, digit_mask, ghist, digit_totals, cv, vo, pnb, xr);
+            launch_pass<K, K, RB, false, ITEMS>(c, p);
         }
-        launches += 3;
+        c.count(3);
         shift += bits;
         side ^= 1;
     }
-    t_top_pass = false;
     GS_HIP(hipGetLastError());
     result_side = side;
     return GS_OK;
 }
 
-// XCD-aware tile order of a radix pass over `pnb` tiles (see run_sort_items): the span factor and the padded grid
-static uint32_t xcd_span_for(uint32_t pnb, uint32_t &sgrid) {
-    static const bool remap_on = !(std::getenv("GS3D_XCD_REMAP") && std::getenv("GS3D_XCD_REMAP")[0] == '0');
-    static const int remap_c = std::getenv("GS3D_XCD_REMAP_C") ? std::atoi(std::getenv("GS3D_XCD_REMAP_C")) : 0;
-    uint32_t xr = 0;
-    if (remap_on && pnb >= 256u) {
-        xr = 4u;
-        while (xr < 64u && xr * 2u * 256u <= pnb) xr *= 2u;
-        if (remap_c > 1) xr = (uint32_t)remap_c;
-    }
-    sgrid = xr ? 8u * xr * ((pnb + 8u * xr - 1u) / (8u * xr)) : pnb;
-    return xr;
+// the depth sorts' tile size from the host's bound of the count (see SortCfg): fn(integral_constant ITEMS)
+static int depth_sort_items(uint32_t n) { return n >= (4u << 20) ? gs::SortCfg<uint32_t>::ITEMS_LARGE : gs::SortCfg<uint32_t>::ITEMS; }
+template <class F>
+static gs_status with_depth_items(uint32_t n, F fn) {
+    if (n >= (4u << 20)) return fn(std::integral_constant<int, gs::SortCfg<uint32_t>::ITEMS_LARGE>());
+    return fn(std::integral_constant<int, gs::SortCfg<uint32_t>::ITEMS>());
 }
 
 // The histogram half of that pass on its own (partitioned two-round frames: gs::k_round_threshold needs the totals of the top
@@ -2186,33 +2265,59 @@ static gs_status run_top_digit_totals(gs_renderer *r, hipStream_t st, uint32_t d
     return GS_OK;
 }
 
+// k_bucket_sort behind an MSD-first scatter pass: the fields both sorts fill the same way (the caller sets nb, the
+// key / value arrays, bucket_max and the ranges), and the launch
+static gs::BucketSortIO bucket_sort_io(const SortCtx &c, gs_renderer *r, uint32_t low_bits) {
+    gs::BucketSortIO io;
+    io.totals = (const uint32_t *)r->digit_totals.ptr;
+    io.starts = (const uint32_t *)r->bucket_starts.ptr;
+    io.low_bits = low_bits;
+    io.keys_tmp = nullptr;
+    io.vals_tmp = nullptr;
+    io.ranges = nullptr;
+    io.num_tiles = 0;
+    io.rank_fault = c.rank_fault;
+    io.watch = c.watch;
+    return io;
+}
+template <typename K, int RBL, int THREADS>
+static void launch_bucket_sort(const SortCtx &c, const gs::BucketSortIO &io) {
+    with_rank(c, [&](auto fast_tag, uint32_t *, uint32_t) {
+        hipLaunchKernelGGL((gs::k_bucket_sort<K, RBL, THREADS, decltype(fast_tag)::value>), dim3(io.nb), dim3(THREADS), 0, c.st, io);
+    });
+}
+
 // The frame's depth sort, MSD-first (round 5; gs_render_kernels.h, "Bucket sort"): ONE compacting scatter pass on the TOP
 // 10 bits of the depth key — its histogram summed from the rows the preprocess kernel counted — then one workgroup per
 // bucket sorts the remaining low bits on its CU and writes the final order to vals[0].  4 launches instead of 9; right
 // when the buckets fit a workgroup (up to ~1-2 M visible Gaussians spread in depth), which the caller decides from the
 // bucket sizes the last frames reported.  `scratch_*`: two passes of the chunked fallback (oversized buckets).
 template <int ITEMS>
-static gs_status run_depth_msd_items(gs_renderer *r, hipStream_t st, const SortCompact &cp, uint32_t dbits, uint32_t top_range,
-                                     void *scratch_keys, void *scratch_vals, uint32_t *bucket_max, uint32_t &passes_out) {
+static gs_status run_depth_msd_items(const SortCtx &c, gs_renderer *r, const SortCompact &cp, uint32_t dbits, uint32_t top_range,
+                                     void *scratch_keys, void *scratch_vals, uint32_t &passes_out) {
     constexpr int RB = gs::MSD_TOP_BITS, RBL = gs::RADIX_BITS_MAX;     // top digit 10 bits; two bucket passes of up to 9 below it
     constexpr uint32_t R = 1u << RB, TILE = (uint32_t)(gs::SORT_THREADS * ITEMS);
-    const gs_device *dev = r->dev;
     const uint32_t low_bits = dbits - (uint32_t)RB;
-    const uint32_t pnb = (uint32_t)(((uint64_t)cp.dense_count + TILE - 1) / TILE);
-    GS_TRY(dev_reserve(r->ghist, (size_t)pnb * R * 4));
+    RadixPass p;
+    p.nb = (uint32_t)(((uint64_t)cp.dense_count + TILE - 1) / TILE);
+    GS_TRY(dev_reserve(r->ghist, (size_t)p.nb * R * 4));
     GS_TRY(dev_reserve(r->digit_totals, R * 4));
     GS_TRY(dev_reserve(r->bucket_starts, R * 4));
-    uint32_t sgrid = 0;
-    const uint32_t xr = xcd_span_for(pnb, sgrid);
-    const gs::SortCount psc{cp.dense_count, cp.dense_count_dev};
-    t_bucket_starts = (uint32_t *)r->bucket_starts.ptr;
-    launch_pass<uint32_t, uint32_t, RB, true, ITEMS>(dev, st, sgrid, cp.dense_keys, (const uint32_t *)nullptr, (uint32_t *)r->dkeys[1].ptr, 0u,
-                                                     (uint32_t *)r->dvals[1].ptr, psc, low_bits, R - 1u, r->ghist, r->digit_totals,
-                                                     cp.chunk_vis, cp.visible_out, pnb, xr, cp.chunk_hist, R / 2u);
-    t_bucket_starts = nullptr;
-    gs::BucketSortIO io;
-    io.totals = (const uint32_t *)r->digit_totals.ptr;
-    io.starts = (const uint32_t *)r->bucket_starts.ptr;
+    p.xr = xcd_span_for(p.nb, p.sgrid);
+    p.sc = gs::SortCount{cp.dense_count, cp.dense_count_dev};
+    p.kin = cp.dense_keys;
+    p.kout = r->dkeys[1].ptr;
+    p.vout = (uint32_t *)r->dvals[1].ptr;
+    p.shift = low_bits;
+    p.digit_mask = R - 1u;
+    p.chunk_vis = cp.chunk_vis;
+    p.visible_out = cp.visible_out;
+    p.pred = cp.pred;
+    p.chunk_hist = cp.chunk_hist;
+    p.chunk_hist_words = R / 2u;
+    p.bucket_starts = (uint32_t *)r->bucket_starts.ptr;
+    launch_pass<uint32_t, uint32_t, RB, true, ITEMS>(c, p);
+    gs::BucketSortIO io = bucket_sort_io(c, r, low_bits);
     io.nb = top_range < R ? top_range : R;          // digits past the far plane's cannot occur (their totals are zero)
     io.keys_in = r->dkeys[1].ptr;
     io.vals_in = (const uint32_t *)r->dvals[1].ptr;
@@ -2220,18 +2325,10 @@ static gs_status run_depth_msd_items(gs_renderer *r, hipStream_t st, const SortC
     io.vals_tmp = (uint32_t *)scratch_vals;
     io.keys_out = nullptr;                          // nobody reads the sorted depth keys
     io.vals_out = (uint32_t *)r->dvals[0].ptr;
-    io.low_bits = low_bits;
-    io.bucket_max = bucket_max;
-    io.ranges = nullptr;
-    io.num_tiles = 0;
-    io.rank_fault = t_rank_fault;
-    io.watch = t_watch;
-    if (t_rank_fault || dev->lds_atomic_ordered.load(std::memory_order_relaxed))
-        hipLaunchKernelGGL((gs::k_bucket_sort<uint32_t, RBL, gs::BKT_THREADS, true>), dim3(io.nb), dim3(gs::BKT_THREADS), 0, st, io);
-    else
-        hipLaunchKernelGGL((gs::k_bucket_sort<uint32_t, RBL, gs::BKT_THREADS, false>), dim3(io.nb), dim3(gs::BKT_THREADS), 0, st, io);
+    io.bucket_max = cp.bucket_max;
+    launch_bucket_sort<uint32_t, RBL, gs::BKT_THREADS>(c, io);
     GS_HIP(hipGetLastError());
-    r->launches += 4;
+    c.count(4);
     passes_out = 1u + (low_bits + RBL - 1u) / RBL;
     return GS_OK;
 }
@@ -2242,65 +2339,55 @@ static gs_status run_depth_msd_items(gs_renderer *r, hipStream_t st, const SortC
 // [start, end) ranges: no second histogram / row scan / scatter and no range kernel, 4 launches instead of 7.  Result on
 // side 0 (keys too: the parity tap rebuilds the 64-bit keys from them).
 template <int ITEMS>
-static gs_status run_tile_msd_items(gs_renderer *r, hipStream_t st, const gs::ExpandIO &eo, gs::SortCount tc, uint32_t tile_bits,
+static gs_status run_tile_msd_items(const SortCtx &c, gs_renderer *r, const gs::ExpandIO &eo, gs::SortCount tc, uint32_t tile_bits,
                                     uint32_t num_tiles, uint32_t *ranges, uint32_t *bucket_max, uint32_t &passes_out) {
     constexpr int RB = gs::MSD_TOP_BITS, RBL = 6;        // top digit 10 bits; up to 6 bits (65536 tiles) left for the buckets
     constexpr uint32_t R = 1u << RB, TILE = (uint32_t)(gs::SORT_THREADS * ITEMS);
-    const gs_device *dev = r->dev;
     const uint32_t low_bits = tile_bits - (uint32_t)RB;
-    const uint32_t pnb = (uint32_t)(((uint64_t)tc.count + TILE - 1) / TILE);
-    GS_TRY(dev_reserve(r->ghist, (size_t)pnb * R * 4));
+    RadixPass p;
+    p.nb = (uint32_t)(((uint64_t)tc.count + TILE - 1) / TILE);
+    GS_TRY(dev_reserve(r->ghist, (size_t)p.nb * R * 4));
     GS_TRY(dev_reserve(r->digit_totals, R * 4));
-    uint32_t sgrid = 0;
-    const uint32_t xr = xcd_span_for(pnb, sgrid);
+    p.xr = xcd_span_for(p.nb, p.sgrid);
     gs::ExpandIO src = eo;
     src.tvals = (uint32_t *)r->tvals[0].ptr;
     if (src.rect32)
-        hipLaunchKernelGGL((gs::k_pairs_emit<uint16_t, RB, ITEMS, true>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st, src, R - 1u,
-                           (uint32_t *)r->ghist.ptr, (uint16_t *)r->tkeys[0].ptr, pnb, xr, low_bits);
+        hipLaunchKernelGGL((gs::k_pairs_emit<uint16_t, RB, ITEMS, true>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st, src, R - 1u,
+                           (uint32_t *)r->ghist.ptr, (uint16_t *)r->tkeys[0].ptr, p.nb, p.xr, low_bits);
     else
-        hipLaunchKernelGGL((gs::k_pairs_emit<uint16_t, RB, ITEMS, false>), dim3(sgrid), dim3(gs::SORT_THREADS), 0, st, src, R - 1u,
-                           (uint32_t *)r->ghist.ptr, (uint16_t *)r->tkeys[0].ptr, pnb, xr, low_bits);
-    launch_scan_rows<(int)TILE>(R, st, (uint32_t *)r->ghist.ptr, pnb, tc, (uint32_t *)r->digit_totals.ptr);
+        hipLaunchKernelGGL((gs::k_pairs_emit<uint16_t, RB, ITEMS, false>), dim3(p.sgrid), dim3(gs::SORT_THREADS), 0, c.st, src, R - 1u,
+                           (uint32_t *)r->ghist.ptr, (uint16_t *)r->tkeys[0].ptr, p.nb, p.xr, low_bits);
+    launch_scan_rows<(int)TILE>(R, c.st, (uint32_t *)r->ghist.ptr, p.nb, tc, (uint32_t *)r->digit_totals.ptr);
     GS_TRY(dev_reserve(r->bucket_starts, R * 4));
-    t_bucket_starts = (uint32_t *)r->bucket_starts.ptr;
-    launch_scatter<uint16_t, uint16_t, RB, false, ITEMS>(dev, st, sgrid, (const uint16_t *)r->tkeys[0].ptr, (const uint32_t *)r->tvals[0].ptr,
-                                                         (uint16_t *)r->tkeys[1].ptr, 0u, (uint32_t *)r->tvals[1].ptr, tc, low_bits, R - 1u,
-                                                         (const uint32_t *)r->ghist.ptr, (const uint32_t *)r->digit_totals.ptr,
-                                                         (const uint32_t *)nullptr, (uint32_t *)nullptr, pnb, xr);
-    t_bucket_starts = nullptr;
-    gs::BucketSortIO io;
-    io.totals = (const uint32_t *)r->digit_totals.ptr;
-    io.starts = (const uint32_t *)r->bucket_starts.ptr;
+    p.kin = r->tkeys[0].ptr;
+    p.vin = (const uint32_t *)r->tvals[0].ptr;
+    p.kout = r->tkeys[1].ptr;
+    p.vout = (uint32_t *)r->tvals[1].ptr;
+    p.sc = tc;
+    p.shift = low_bits;
+    p.digit_mask = R - 1u;
+    p.bucket_starts = (uint32_t *)r->bucket_starts.ptr;
+    launch_scatter<uint16_t, uint16_t, RB, false, ITEMS>(c, p);
+    gs::BucketSortIO io = bucket_sort_io(c, r, low_bits);
     io.nb = ((num_tiles - 1u) >> low_bits) + 1u;
     io.keys_in = r->tkeys[1].ptr;
     io.vals_in = (const uint32_t *)r->tvals[1].ptr;
-    io.keys_tmp = nullptr;                          // one pass: the chunked path needs no scratch
-    io.vals_tmp = nullptr;
-    io.keys_out = r->tkeys[0].ptr;
+    io.keys_out = r->tkeys[0].ptr;                  // (one pass: the chunked path needs no scratch)
     io.vals_out = (uint32_t *)r->tvals[0].ptr;
-    io.low_bits = low_bits;
     io.bucket_max = bucket_max;
     io.ranges = ranges;
     io.num_tiles = num_tiles;
-    io.rank_fault = t_rank_fault;
-    io.watch = t_watch;
-    if (t_rank_fault || dev->lds_atomic_ordered.load(std::memory_order_relaxed))
-        hipLaunchKernelGGL((gs::k_bucket_sort<uint16_t, RBL, gs::BKT_THREADS_SMALL, true>), dim3(io.nb), dim3(gs::BKT_THREADS_SMALL), 0, st, io);
-    else
-        hipLaunchKernelGGL((gs::k_bucket_sort<uint16_t, RBL, gs::BKT_THREADS_SMALL, false>), dim3(io.nb), dim3(gs::BKT_THREADS_SMALL), 0, st, io);
+    launch_bucket_sort<uint16_t, RBL, gs::BKT_THREADS_SMALL>(c, io);
     GS_HIP(hipGetLastError());
-    r->launches += 4;
+    c.count(4);
     passes_out = low_bits ? 2u : 1u;
     return GS_OK;
 }
 
 // tile size from the host-side bound of the element count (see SortCfg)
 template <typename K, int RB>
-static gs_status run_sort_rb(const gs_device *dev, void *const keys[2], void *const vals[2], DevArray &ghist,
-                             DevArray &digit_totals, gs::SortCount sc, uint32_t end_bit, const SortCompact *compact,
-                             hipStream_t st, int &result_side, uint32_t &passes_out, uint32_t &launches,
-                             const gs::ExpandIO *source = nullptr) {
+static gs_status run_sort_rb(const SortCtx &c, void *const keys[2], void *const vals[2], gs::SortCount sc, uint32_t end_bit,
+                             const SortCompact *compact, int &result_side, uint32_t &passes_out, const gs::ExpandIO *source = nullptr) {
     const uint64_t bound = compact ? compact->dense_count : sc.count;
     if constexpr (gs::SortCfg<K>::ITEMS_LARGE != gs::SortCfg<K>::ITEMS) {
         // u32 keys: larger tiles for larger sorts.  u16 tile keys: a tile's digit runs should hold >= 32
@@ -2308,24 +2395,17 @@ static gs_status run_sort_rb(const gs_device *dev, void *const keys[2], void *co
         // twice as many workgroups per CU (10 M: emit + tile sort 376 -> 358 us); 8-bit digits (4K: 15
         // bits = 8 + 7) keep 8192-key tiles (848 vs 875 us with the small ones).
         bool large = bound >= (4u << 20);
-        if (sizeof(K) == 4) {
-            // GS3D_DEPTH_SORT_LARGE=0/1 forces 4096- / 8192-key tiles for 32-bit keys (A/B runs)
-            static const int force32 = std::getenv("GS3D_DEPTH_SORT_LARGE") ? std::atoi(std::getenv("GS3D_DEPTH_SORT_LARGE")) : -1;
-            if (force32 >= 0) large = force32 != 0;
-        }
+        // GS3D_DEPTH_SORT_LARGE=0/1 forces 4096- / 8192-key tiles for 32-bit keys (A/B runs)
+        if (sizeof(K) == 4 && switches().depth_sort_large >= 0) large = switches().depth_sort_large != 0;
         if (sizeof(K) == 2) {
             const uint32_t passes = (end_bit + RB - 1) / RB;
             large = passes ? (end_bit + passes - 1) / passes > 7u : false;
             // GS3D_TILE_SORT_LARGE=0/1 forces 4096- / 8192-key tiles for the 16-bit tile keys (A/B runs)
-            static const int force = std::getenv("GS3D_TILE_SORT_LARGE") ? std::atoi(std::getenv("GS3D_TILE_SORT_LARGE")) : -1;
-            if (force >= 0) large = force != 0;
+            if (switches().tile_sort_large >= 0) large = switches().tile_sort_large != 0;
         }
-        if (large)
-            return run_sort_items<K, RB, gs::SortCfg<K>::ITEMS_LARGE>(dev, keys, vals, ghist, digit_totals, sc, end_bit,
-                                                                    compact, st, result_side, passes_out, launches, source);
+        if (large) return run_sort_items<K, RB, gs::SortCfg<K>::ITEMS_LARGE>(c, keys, vals, sc, end_bit, compact, result_side, passes_out, source);
     }
-    return run_sort_items<K, RB, gs::SortCfg<K>::ITEMS>(dev, keys, vals, ghist, digit_totals, sc, end_bit, compact, st,
-                                                       result_side, passes_out, launches, source);
+    return run_sort_items<K, RB, gs::SortCfg<K>::ITEMS>(c, keys, vals, sc, end_bit, compact, result_side, passes_out, source);
 }
 
 // host-known count (spatial order build, stand-alone sort)
@@ -2334,9 +2414,8 @@ static gs_status sort_pairs_device(const gs_device *dev, void *const keys[2], vo
                                    DevArray &ghist, DevArray &digit_totals, uint32_t count,
                                    uint32_t end_bit, hipStream_t st, int &result_side,
                                    uint32_t &passes_out) {
-    uint32_t launches = 0;
-    return run_sort_rb<K, gs::RADIX_BITS>(dev, keys, vals, ghist, digit_totals, gs::SortCount{count, nullptr}, end_bit,
-                                          nullptr, st, result_side, passes_out, launches);
+    return run_sort_rb<K, gs::RADIX_BITS>(standalone_sort_ctx(dev, st, ghist, digit_totals), keys, vals, gs::SortCount{count, nullptr}, end_bit,
+                                          nullptr, result_side, passes_out);
 }
 
 // (Re)build the block-planar mirror on `st`.  A whole-buffer rebuild in spatial mode first computes
@@ -2512,8 +2591,7 @@ struct Roctx {
     int (*push)(const char *) = nullptr;
     int (*pop)() = nullptr;
     Roctx() {
-        const char *e = std::getenv("GS3D_ROCTX");
-        if (!e || e[0] != '1') return;
+        if (!switches().roctx) return;
         for (const char *name : {"librocprofiler-sdk-roctx.so", "libroctx64.so"}) {
             void *h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
             if (!h) continue;
@@ -2545,6 +2623,47 @@ struct RoctxRange {
     }
 };
 
+static const gsp::PolicyParams k_policy_params = {(uint32_t)gs::BKT_CAP, (uint32_t)gs::BKT_CAP_SMALL, (uint32_t)gs::MSD_TOP_BITS,
+                                                  (uint32_t)gs::RADIX_BITS_MAX};
+
+// ---- what the previous frames told us (never blocks: an unfinished frame is simply not consulted) ----
+// The snapshot carries the renderer's shape epoch of THIS moment.  gs_render_frame bumps the epoch later (stage_preprocess),
+// but only in a sizing frame (or with n == 0), and every rule that compares a report's epoch is guarded by !sizing: a
+// snapshot taken before the bump answers the same as a read behind it.
+static gsp::History read_history(gs_renderer *r) {
+    gsp::History h;
+    h.shape_epoch = r->shape_epoch;
+    for (int i = 0; i < 2; i++) {
+        if (switches().frame_event) {
+            if (!r->done_valid[i] || hipEventQuery(r->done[i]) != hipSuccess) continue;
+        } else if (!r->done_gen[i]) {
+            continue;
+        }
+        const gs::FrameResult &fr = r->results[i];
+        // gen is published last with a system-scope release (publish_result): read it first — and once more behind the
+        // fields (a frame two generations on may be overwriting the block while it is read)
+        if (__atomic_load_n(&fr.gen, __ATOMIC_ACQUIRE) != r->done_gen[i]) continue;
+        gsp::Report p;
+        p.pairs = fr.pairs_total;
+        p.visible = fr.visible;
+        const uint32_t f_flags = fr.flags;
+        p.depth_bucket_max = fr.depth_bucket_max;
+        p.tile_bucket_max = fr.tile_bucket_max;
+        p.tiles_done = fr.tiles_done;
+        p.tiles_open = fr.tiles_open;
+        p.round_pairs_max = fr.round_pairs_max;
+        if (__atomic_load_n(&fr.gen, __ATOMIC_ACQUIRE) != r->done_gen[i] || p.pairs > 0xfffffff0ull) continue;
+        p.gen = r->done_gen[i];
+        p.shape_epoch = r->done_shape[i];
+        p.rounds = r->done_rounds[i];
+        p.round_k = r->done_round_k[i];
+        h.rep[i] = p;
+        if (f_flags & gs::FRAME_FLAG_RANK_FAULT) h.rank_fault_seen = true;
+    }
+    (void)hipGetLastError();   // hipEventQuery reports hipErrorNotReady through the sticky error too
+    return h;
+}
+
 static gs_status reserve_pairs(gs_renderer *r, uint64_t pairs, bool wide) {
     if (pairs <= r->pair_capacity && r->tkeys[0].ptr && wide == r->wide_tiles) return GS_OK;
     uint64_t cap = pairs;
@@ -2560,9 +2679,6 @@ static gs_status reserve_pairs(gs_renderer *r, uint64_t pairs, bool wide) {
     return GS_OK;
 }
 
-// pair capacity for a frame expected to produce `d` pairs: 25 % head room for a moving camera
-static uint64_t capacity_for(uint64_t d) { return d + d / 4 + 65536; }
-
 static uint32_t float_bits(float f) {
     uint32_t u;
     std::memcpy(&u, &f, 4);
@@ -2577,160 +2693,88 @@ static gs_status reserve_zeroed(DevArray &a, size_t bytes, hipStream_t st) {
     return GS_OK;
 }
 
-// aux: the depth / pick planes (gs_render_frame_aux, checked there), or null.  Only launch_blend looks at it: the frame
-// makes every other choice as it would without it.
-static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g, const gs_gaussian_transform_pod *gt,
-                              const gs_model_transform_pod *mt, const gs_camera *cam, uint32_t band_ty0,
-                              uint32_t band_ty1, float *rgba, const gs_aux_targets *aux) {
-    if (!r || !s || !g || !gt || !mt || !cam || !rgba)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (g->buf->dev != r->dev || s->dev != r->dev)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    if (cam->width == 0 || cam->height == 0 || cam->width > 65535u * 16u || cam->height > 65535u * 16u)
-        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "bad image size");
-    if ((uintptr_t)rgba & 15u)
-        return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)rgba, 16, 0,
-                    "the RGBA frame must be 16-byte aligned (pixels are stored as float4)");
-    uint32_t mode = gt->flags[0];
-    if (mode > GS_DISPLAY_POINT)
-        return fail(GS_ERR_INVALID_ARGUMENT, mode, 0, 0, "unknown GaussianDisplayMode %u", mode);
-    if (!(cam->near_plane >= 0.0f))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the near plane must be >= 0 (depth keys are the bits of a positive float)");
-    GS_TRY(use_device(r->dev));
-    hipStream_t st = s->s;
-    GS_TRY(collect_timing(r));
-    // Frames of one renderer share its scratch buffers and result blocks, so they must run one after
-    // the other.  On one stream that is stream order; a caller that moves the renderer to ANOTHER
-    // stream gets the same guarantee from the previous frame's end-of-frame event (a device-side wait,
-    // the host does not block).
-    // No event at the end of every frame (round 4: it cost ~4 us of a pipelined 1 M frame).  The event a stream change
-    // needs is recorded on the PREVIOUS stream when the change happens (everything enqueued there is in front of it),
-    // and the capacity history reads the self-validating result blocks (gen stored last, read first and last)
-    // without asking an event first.  GS3D_FRAME_EVENT=1 restores the per-frame event (and the query in front of
-    // every history read).
-    static const bool frame_event = std::getenv("GS3D_FRAME_EVENT") && std::getenv("GS3D_FRAME_EVENT")[0] == '1';
-    if (r->have_frame && (st != r->last_stream || r->last_stream_gone)) {
-        // (a stream that has been destroyed since recorded the event on its way out: gs_stream_destroy; a new stream may
-        // have received the old handle's value, hence the flag and not the comparison alone)
-        if (!frame_event && !r->last_stream_gone) {
-            GS_HIP(hipEventRecord(r->done[r->gen & 1u], r->last_stream));
-            r->done_valid[r->gen & 1u] = true;
-        }
-        if (r->done_valid[r->gen & 1u]) GS_HIP(hipStreamWaitEvent(st, r->done[r->gen & 1u], 0));
-    }
-    const bool timing = r->timing && r->ev_valid;
-    static const char *const k_stage_names[ST_COUNT] = {"gs3d:repack", "gs3d:preprocess", "gs3d:sizing", "gs3d:depth_sort",
-                                                        "gs3d:expand", "gs3d:tile_sort", "gs3d:ranges", "gs3d:blend",
-                                                        "gs3d:end"};
-    RoctxRange range("gs3d:frame");
-    RoctxRange stage("gs3d:setup");
-    auto mark = [&](int i) {
+// stage boundaries of a frame: timing events and roctx ranges
+struct StageMarks {
+    gs_renderer *r;
+    hipStream_t st;
+    bool timing;
+    RoctxRange range{"gs3d:frame"};
+    RoctxRange stage{"gs3d:setup"};
+    void mark(int i) {
+        static const char *const k_stage_names[ST_COUNT] = {"gs3d:repack", "gs3d:preprocess", "gs3d:sizing", "gs3d:depth_sort",
+                                                            "gs3d:expand", "gs3d:tile_sort", "gs3d:ranges", "gs3d:blend",
+                                                            "gs3d:end"};
         if (timing) (void)hipEventRecord(r->ev[i], st);
         stage.next(k_stage_names[i]);
-    };
+    }
+};
 
+// From the frame's first launch on, kernels of this frame may be in the stream.  Whatever way the function is left — also
+// through GS_TRY / GS_HIP after an allocation or launch failure — the end-of-frame event of this
+// generation is recorded behind them, so the next frame on ANOTHER stream waits for exactly these
+// kernels before it touches the shared scratch and state buffers (a frame that failed half-way used
+// to leave done[gen & 1] pointing at frame gen - 2).  Its result block carries no `gen`, so the
+// capacity history skips it.
+struct DoneGuard {
+    gs_renderer *r;
+    hipStream_t st;
+    uint32_t gen;
+    bool record;
+    ~DoneGuard() {
+        if (record) {
+            (void)hipEventRecord(r->done[gen & 1u], st);
+            r->done_valid[gen & 1u] = true;
+        } else {
+            r->done_valid[gen & 1u] = false;      // recorded when (if) the renderer moves to another stream
+        }
+        r->done_gen[gen & 1u] = gen;
+        r->done_shape[gen & 1u] = r->shape_epoch;
+        r->done_rounds[gen & 1u] = r->two_round ? 2 : 1;
+        r->done_round_k[gen & 1u] = r->two_round ? r->round1 : 0u;
+    }
+};
+
+// What the stages of one frame share.  aux: the depth / pick planes (gs_render_frame_aux, checked there), or null.  Only
+// stage_blend looks at it: the frame makes every other choice as it would without it.
+struct Frame {
+    gs_renderer *r;
+    hipStream_t st;
+    gs_gaussians_buffer *g;
+    const gs_aux_targets *aux;
+    float *rgba;
+    StageMarks marks;
     gs::FrameConsts fc;
-    make_frame_consts(gt, mt, cam, band_ty0, band_ty1, fc);
-    size_t n64 = gs_gaussians_buffer_len(g);
-    {
-        // Tile rect version 4: pinned by the caller or the environment, otherwise on where the preprocess kernel waits for
-        // HBM long enough to hide the test's ~120 instructions per Gaussian: records of 200 bytes or more (f32 SH) in a
-        // scene beyond the Infinity Cache.  Same-box A/B, frame time with / without (gpurun_out/r05i/ab_masks3.txt): 10 M x
-        // 224 B at 4K 1.521 / 1.558 ms, at 1080p 0.926-0.951 / 0.926-0.959 (tile sort -12 us); 50 M x 144 B 3.37-3.45 /
-        // 3.31-3.37 (preprocess +65..130 us, tile sort -20..55); 1 M x 48 B 0.318 / 0.320 (preprocess +5 us).
-        static const int masks_env = std::getenv("GS3D_TILE_MASKS") ? std::atoi(std::getenv("GS3D_TILE_MASKS")) : -1;
-        const int pinned = r->tile_masks_req >= 0 ? r->tile_masks_req : masks_env;
-        const uint64_t pod_bytes = (uint64_t)gs::pod_words(g->sh, g->cov) * 4u;
-        const bool want = pinned >= 0 ? pinned != 0 : pod_bytes >= 200u && (uint64_t)n64 * pod_bytes > (512ull << 20);
-        fc.tile_masks = fc.tile_masks && want ? 1u : 0u;
-        r->tile_masks = fc.tile_masks != 0u;
-        r->wt_pairs = fc.wt_pairs != 0u;
-    }
-    if (n64 > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, n64, 0, 0, "too many Gaussians");
-    uint32_t n = (uint32_t)n64;
-    uint32_t nchunks = (n + gs::PP_CHUNK - 1) / gs::PP_CHUNK;
-    uint32_t num_tiles = fc.tiles_x * fc.tiles_y;
-    // one 256-Gaussian expansion chunk may touch at most 256 * num_tiles pairs: keep that inside 32 bits
-    if ((uint64_t)fc.tiles_x * fc.tiles_y > (1ull << 22))
-        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 2^22 tiles");
-    // tile rects are packed as 16-bit tile coordinates
-    if (fc.tiles_x > 0xffffu || fc.tiles_y > 0xffffu)
-        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 65535 tiles along one axis");
-    const bool wide = num_tiles > 65536u;
-    const size_t nn = n ? n : 1, nc = nchunks ? nchunks : 1;
-
-    // ---- what the previous frames told us (never blocks: an unfinished frame is simply not consulted) ----
-    uint64_t want_capacity = r->pair_capacity;
-    bool rank_fault_seen = false;
-    uint64_t hist_d[2] = {0, 0};
-    uint32_t hist_gen[2] = {0, 0};
-    uint32_t hist_v[2] = {0, 0};
-    uint32_t hist_bmax[2] = {0, 0}, hist_tmax[2] = {0, 0}, hist_tdone[2] = {0, 0}, hist_topen[2] = {0, 0}, hist_rmax[2] = {0, 0};
-    for (int i = 0; i < 2; i++) {
-        if (frame_event) {
-            if (!r->done_valid[i] || hipEventQuery(r->done[i]) != hipSuccess) continue;
-        } else if (!r->done_gen[i]) {
-            continue;
-        }
-        const gs::FrameResult &fr = r->results[i];
-        // gen is published last with a system-scope release (publish_result): read it first — and once more behind the
-        // fields (a frame two generations on may be overwriting the block while it is read)
-        if (__atomic_load_n(&fr.gen, __ATOMIC_ACQUIRE) != r->done_gen[i]) continue;
-        const uint64_t f_pairs = fr.pairs_total;
-        const uint32_t f_vis = fr.visible;
-        const uint32_t f_flags = fr.flags;
-        const uint32_t f_bmax = fr.depth_bucket_max, f_tmax = fr.tile_bucket_max, f_tdone = fr.tiles_done, f_topen = fr.tiles_open, f_rmax = fr.round_pairs_max;
-        if (__atomic_load_n(&fr.gen, __ATOMIC_ACQUIRE) != r->done_gen[i] || f_pairs > 0xfffffff0ull) continue;
-        hist_d[i] = f_pairs;
-        hist_gen[i] = r->done_gen[i];
-        hist_v[i] = f_vis;
-        hist_bmax[i] = f_bmax;
-        hist_tmax[i] = f_tmax;
-        hist_tdone[i] = f_tdone;
-        hist_topen[i] = f_topen;
-        hist_rmax[i] = f_rmax;
-        if (f_flags & gs::FRAME_FLAG_RANK_FAULT) rank_fault_seen = true;
-        // grow when the last measured D leaves less than 1/8 of head room
-        if (f_pairs + f_pairs / 8 > r->pair_capacity && capacity_for(f_pairs) > want_capacity)
-            want_capacity = capacity_for(f_pairs);
-    }
-    // A camera that keeps closing in: D grows frame over frame, and this frame is two or three frames
-    // ahead of the newest result (frames are pipelined).  Extrapolate the last step three frames ahead
-    // and size for that, so that a steady zoom does not run into the skip path.
-    // Only a TREND is extrapolated: both results must come from the current shape epoch (same N, image
-    // size and band — a switch from a band to the full frame, or a resize, is a discontinuity, not a zoom),
-    // and the extrapolation is capped at twice the newest D: one jump of the camera must not turn into
-    // pair buffers of 4 x D that never shrink.
-    if (hist_gen[0] && hist_gen[1] && (hist_gen[0] + 1u == hist_gen[1] || hist_gen[1] + 1u == hist_gen[0]) &&
-        r->done_shape[0] == r->shape_epoch && r->done_shape[1] == r->shape_epoch) {
-        const int newer = hist_gen[0] > hist_gen[1] ? 0 : 1;
-        const uint64_t d_new = hist_d[newer], d_old = hist_d[newer ^ 1];
-        if (d_new > d_old) {
-            uint64_t ahead = d_new + 3u * (d_new - d_old);
-            if (ahead > 2u * d_new) ahead = 2u * d_new;
-            if (ahead + ahead / 8 > r->pair_capacity && capacity_for(ahead) > want_capacity) want_capacity = capacity_for(ahead);
-        }
-    }
-    (void)hipGetLastError();   // hipEventQuery reports hipErrorNotReady through the sticky error too
     FrameShape shape;
-    shape.n = n;
-    shape.width = cam->width;
-    shape.height = cam->height;
-    shape.band0 = fc.band_ty0;
-    shape.band1 = fc.band_ty1;
-    const bool sizing = n != 0 && (r->pair_capacity == 0 || !(shape == r->shape));
-
-    mark(ST_REPACK);
-    GS_TRY(ensure_planar(g, st));
-    if (r->last_order != g->order) {
-        if (r->last_order) gs_buffer_release(r->last_order);
-        r->last_order = g->order ? gs_buffer_retain(g->order) : nullptr;
+    gsp::FrameNums nums;
+    gsp::History hist;
+    gsp::FramePlan plan;
+    SortCtx sort;
+    uint32_t mode, gen = 0, n = 0, nchunks = 0, num_tiles = 0, exp_grid = 0;
+    uint32_t near_bits = 0, far_bits = 0;
+    size_t nn = 1, nc = 1, nslots = 0;
+    gs::FrameState *state = nullptr;
+    gs::FrameResult *result = nullptr;
+    // slices of zero_region: tile ranges, the two rounds' super-chunk sums, the finished / open tile bits
+    uint32_t *zero = nullptr, *esb = nullptr, *esb2 = nullptr, *done_bits = nullptr, *open_bits = nullptr;
+    gs::TileKeys tile_keys{nullptr, nullptr, 0u, 0u, 0u, nullptr, nullptr};   // null keys: the blend reads its ranges from the range array
+    gsp::Requests requests() const {
+        gsp::Requests q;
+        q.depth_msd = r->depth_msd_req;
+        q.tile_msd = r->tile_msd_req;
+        q.tile_masks = r->tile_masks_req;
+        q.rounds = r->rounds_req;
+        q.round1 = r->round1_req;
+        return q;
     }
-    mark(ST_PRE);
+};
 
+// the frame's scratch that depends on N alone
+static gs_status reserve_frame_scratch(Frame &F) {
+    gs_renderer *r = F.r;
+    const size_t nn = F.nn, nc = F.nc;
     // per-slot outputs of preprocess: whole chunks — a list frame addresses them in list space, where the
     // buffer's last, partial block may sit anywhere and its lanes past N are written too (as "culled")
-    const size_t nslots = nc * (size_t)gs::PP_CHUNK;
+    const size_t nslots = F.nslots;
     GS_TRY(dev_reserve(r->recs, nslots * 4 * gs::REC_WORDS + 16));
     GS_TRY(dev_reserve(r->depth, nslots * 4));
     GS_TRY(dev_reserve(r->rect, nslots * 8));
@@ -2748,77 +2792,589 @@ static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
         // histogram of an MSD-first sort or of a partitioned two-round frame: 1024 rows): reserved HERE, in the frame that sizes
         // the scene, because growing them later means a hipFree under frames in flight — a device-wide wait at best (and under
         // rocprofv3 --pmc the 10 M bench hung in it: the first partitioned frame doubled `ghist` behind eight queued frames).
-        const size_t depth_tile = (size_t)gs::SORT_THREADS * (n >= (4u << 20) ? gs::SortCfg<uint32_t>::ITEMS_LARGE : gs::SortCfg<uint32_t>::ITEMS);
+        const size_t depth_tile = (size_t)gs::SORT_THREADS * depth_sort_items(F.n);
         GS_TRY(dev_reserve(r->ghist, ((size_t)nn + depth_tile - 1) / depth_tile * ((size_t)4 << gs::MSD_TOP_BITS)));
         GS_TRY(dev_reserve(r->digit_totals, (size_t)4 << gs::MSD_TOP_BITS));
     }
-    const uint32_t exp_grid = (n + gs::EXP_CHUNK - 1) / gs::EXP_CHUNK;   // V <= N
-    GS_TRY(dev_reserve(r->exp_sums, (size_t)(exp_grid ? exp_grid : 1) * 4));
-    GS_TRY(reserve_zeroed(r->state, sizeof(gs::FrameState), st));
-    {
-        // Watchdog of the LDS-atomic rank (scatter_ranked): a completed frame reported a rank that was not the
-        // ballot-based one -> this device sorts with the ballot-based rank from now on, and the flag is cleared in
-        // stream order (the kernels that could set it are no longer launched).
-        gs::FrameState *fs = (gs::FrameState *)r->state.ptr;
-        if (rank_fault_seen) {
-            // (the word is this renderer's own and is cleared whoever switched the device: see gs_renderer_wait_frame)
-            r->dev->lds_atomic_ordered.store(false);
-            GS_HIP(hipMemsetAsync(&fs->rank_fault, 0, sizeof(uint32_t), st));
-        }
-        // GS3D_TEST_RANK_FAULT=1 (tests): the watchdog's expectation is off by one, so it fires in the first frame
-        static const bool inject = std::getenv("GS3D_TEST_RANK_FAULT") && std::getenv("GS3D_TEST_RANK_FAULT")[0] == '1';
-        if (inject && !r->rank_inject_set) {
-            const uint32_t one = 1u;
-            GS_HIP(hipMemcpyAsync(&fs->rank_inject, &one, sizeof(one), hipMemcpyHostToDevice, st));
-            GS_HIP(hipStreamSynchronize(st));      // `one` lives on this stack frame
-            r->rank_inject_set = true;
-        }
-        // read ONCE per frame: every scatter of the frame ranks the same way, whatever another renderer's thread does
-        t_rank_fault = r->dev->lds_atomic_ordered.load() ? &fs->rank_fault : nullptr;
-        t_bucket_max = &fs->depth_bucket_max;
-        t_top_pass = false;
+    GS_TRY(dev_reserve(r->exp_sums, (size_t)(F.exp_grid ? F.exp_grid : 1) * 4));
+    GS_TRY(reserve_zeroed(r->state, sizeof(gs::FrameState), F.st));
+    return GS_OK;
+}
+
+// Watchdog of the LDS-atomic rank (scatter_ranked): a completed frame reported a rank that was not the
+// ballot-based one -> this device sorts with the ballot-based rank from now on, and the flag is cleared in
+// stream order (the kernels that could set it are no longer launched).  Fills the frame's sort context but its sample.
+static gs_status arm_rank_watchdog(Frame &F) {
+    gs_renderer *r = F.r;
+    gs::FrameState *fs = (gs::FrameState *)r->state.ptr;
+    if (F.hist.rank_fault_seen) {
+        // (the word is this renderer's own and is cleared whoever switched the device: see gs_renderer_wait_frame)
+        r->dev->lds_atomic_ordered.store(false);
+        GS_HIP(hipMemsetAsync(&fs->rank_fault, 0, sizeof(uint32_t), F.st));
     }
-    struct RankFaultScope {
-        ~RankFaultScope() {
-            t_rank_fault = nullptr;
-            t_bucket_max = nullptr;
-            t_top_pass = false;
+    // GS3D_TEST_RANK_FAULT=1 (tests): the watchdog's expectation is off by one, so it fires in the first frame
+    if (switches().test_rank_fault && !r->rank_inject_set) {
+        const uint32_t one = 1u;
+        GS_HIP(hipMemcpyAsync(&fs->rank_inject, &one, sizeof(one), hipMemcpyHostToDevice, F.st));
+        GS_HIP(hipStreamSynchronize(F.st));      // `one` lives on this stack frame
+        r->rank_inject_set = true;
+    }
+    F.sort.dev = r->dev;
+    F.sort.st = F.st;
+    F.sort.ghist = &r->ghist;
+    F.sort.digit_totals = &r->digit_totals;
+    F.sort.launches = &r->launches;
+    // read ONCE per frame: every scatter of the frame ranks the same way, whatever another renderer's thread does
+    F.sort.fast_rank = r->dev->lds_atomic_ordered.load();
+    F.sort.rank_fault = F.sort.fast_rank ? &fs->rank_fault : nullptr;
+    return GS_OK;
+}
+
+// The blend launch of one round (0: the frame's only one).
+static gs_status stage_blend(Frame &F, uint32_t round) {
+    gs_renderer *r = F.r;
+    if (!F.nums.band_tiles) return GS_OK;
+    const int groups = switches().blend_groups;
+    const uint32_t mode = F.mode;
+    typedef void (*blend_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
+                             const gs::FrameState *, gs::TileKeys);
+    static const blend_fn tbl[3][3] = {
+        {gs::k_blend<0>, gs::k_blend_grouped<0, 2>, gs::k_blend_grouped<0, 4>},
+        {gs::k_blend<1>, gs::k_blend_grouped<1, 2>, gs::k_blend_grouped<1, 4>},
+        {gs::k_blend<2>, gs::k_blend_grouped<2, 2>, gs::k_blend_grouped<2, 4>}};
+    static const blend_fn tbl_rounds[3][2] = {{gs::k_blend_grouped<0, 2, true>, gs::k_blend_grouped<0, 4, true>},
+                                              {gs::k_blend_grouped<1, 2, true>, gs::k_blend_grouped<1, 4, true>},
+                                              {gs::k_blend_grouped<2, 2, true>, gs::k_blend_grouped<2, 4, true>}};
+    if (round != 0u && groups == 1) return fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
+    F.tile_keys.round = round;
+    if (F.aux) {
+        // the depth / pick planes ride in the grouped blend (G = 4 where the plain frame would take k_blend)
+        typedef void (*aux_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
+                               const gs::FrameState *, gs::TileKeys, gs::AuxIO);
+        static const aux_fn tbl_aux[2][3][2] = {
+            {{gs::k_blend_grouped<0, 2, false, true>, gs::k_blend_grouped<0, 4, false, true>},
+             {gs::k_blend_grouped<1, 2, false, true>, gs::k_blend_grouped<1, 4, false, true>},
+             {gs::k_blend_grouped<2, 2, false, true>, gs::k_blend_grouped<2, 4, false, true>}},
+            {{gs::k_blend_grouped<0, 2, true, true>, gs::k_blend_grouped<0, 4, true, true>},
+             {gs::k_blend_grouped<1, 2, true, true>, gs::k_blend_grouped<1, 4, true, true>},
+             {gs::k_blend_grouped<2, 2, true, true>, gs::k_blend_grouped<2, 4, true, true>}}};
+        gs::AuxIO aio;
+        aio.depth = F.aux->depth;
+        aio.pick = F.aux->pick;
+        aio.tcut = 1.0f - F.aux->pick_threshold;
+        aio.key_bias = r->key_bias;
+        aio.depth_keys = (const uint32_t *)r->depth.ptr;
+        aio.block_list = r->list_mode ? (const uint32_t *)r->block_list.ptr : nullptr;
+        aio.order = r->last_order ? (const uint32_t *)r->last_order->ptr : nullptr;
+        hipLaunchKernelGGL(tbl_aux[round != 0u ? 1 : 0][mode][groups == 2 ? 0 : 1], dim3(F.nums.band_tiles), dim3(gs::BLEND_THREADS), 0, F.st,
+                           (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
+                           (const uint32_t *)r->recs.ptr, F.fc, (float4 *)F.rgba, (const gs::FrameState *)r->state.ptr, F.tile_keys,
+                           aio);
+    } else {
+        const blend_fn blend = round != 0u ? tbl_rounds[mode][groups == 2 ? 0 : 1] : tbl[mode][groups == 1 ? 0 : groups == 2 ? 1 : 2];
+        hipLaunchKernelGGL(blend, dim3(F.nums.band_tiles), dim3(gs::BLEND_THREADS), 0, F.st,
+                           (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
+                           (const uint32_t *)r->recs.ptr, F.fc, (float4 *)F.rgba, (const gs::FrameState *)r->state.ptr, F.tile_keys);
+    }
+    GS_HIP(hipGetLastError());
+    r->launches++;
+    return GS_OK;
+}
+
+// n == 0: nothing to project: clear the ranges, blend the background
+static gs_status stage_empty_frame(Frame &F) {
+    gs_renderer *r = F.r;
+    GS_TRY(dev_reserve(r->zero_region, (size_t)F.num_tiles * 8));
+    GS_HIP(hipMemsetAsync(r->zero_region.ptr, 0, (size_t)F.num_tiles * 8, F.st));
+    GS_TRY(reserve_pairs(r, 1, F.nums.wide));
+    hipLaunchKernelGGL(gs::k_publish_result, dim3(1), dim3(64), 0, F.st, F.result, F.state, F.gen, r->flags_target);
+    GS_HIP(hipGetLastError());
+    r->launches++;
+    for (int i : {ST_SCAN, ST_DSORT, ST_EXPAND, ST_TSORT, ST_RANGES}) F.marks.mark(i);
+    r->sort_passes = 0;
+    r->dsorted_side = r->tsorted_side = 0;
+    return GS_OK;
+}
+
+// Block list (k_block_cull, see gsp::plan_use_list): the surviving blocks, handed to the preprocess kernel through `po`
+static gs_status stage_block_cull(Frame &F, gs::PreOut &po) {
+    gs_renderer *r = F.r;
+    const uint32_t gen = F.gen, nchunks = F.nchunks;
+    const uint32_t groups = (nchunks + 255u) / 256u;
+    GS_TRY(dev_reserve(r->block_list, (size_t)nchunks * 4));
+    GS_TRY(dev_reserve(r->cull_status, (size_t)groups * 4));
+    // Tag of this frame's status words: 22 bits of the generation.  A word must never hold this tag
+    // before its group publishes: consecutive list frames over the same groups overwrite every word
+    // with the previous tag; in every other case (first use, a gap of frames without the list, another
+    // group count) the words are cleared first, and the tag 0 is skipped.
+    const uint32_t tag = (gen & 0x3fffffu) ? (gen & 0x3fffffu) : 0x3fffffu;
+    if (r->cull_last_gen + 1u != gen || r->cull_last_groups != groups || (gen & 0x3fffffu) <= 1u)
+        GS_HIP(hipMemsetAsync(r->cull_status.ptr, 0, (size_t)groups * 4, F.st));
+    r->cull_last_gen = gen;
+    r->cull_last_groups = groups;
+    hipLaunchKernelGGL(gs::k_block_cull, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds, nchunks, F.fc,
+                       (uint32_t *)r->block_list.ptr, F.state, (uint32_t *)r->cull_status.ptr, tag, groups);
+    GS_HIP(hipGetLastError());
+    r->launches++;
+    po.block_list = (const uint32_t *)r->block_list.ptr;
+    po.block_count = &F.state->list_blocks;
+    r->list_mode = true;
+    return GS_OK;
+}
+
+// First frame of this shape: measure D before sizing the pair buffers (the only blocking
+// step; steady-state frames take the capacity from the history instead)
+static gs_status stage_sizing(Frame &F) {
+    gs_renderer *r = F.r;
+    gs::ScanJob jt{(const uint32_t *)r->chunk_tiles.ptr, (uint32_t *)r->scan_tmp.ptr, r->host_counters, F.nchunks,
+                   r->list_mode ? &F.state->list_blocks : nullptr};
+    hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, F.st, jt, jt);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(F.st));
+    const uint32_t d = r->host_counters[0];
+    if (d == 0xffffffffu) {
+        r->shape = FrameShape();
+        return fail(GS_ERR_PAIR_OVERFLOW, F.n, 0, 0,
+                    "the frame needs more than 2^32 (tile, Gaussian) pairs; pair indices are 32-bit");
+    }
+    r->rounds_fb.full_pairs = d;              // (the visible count it belongs to comes with the frame's report)
+    r->rounds_fb.full_pairs_v = 0;
+    const uint64_t cap = gsp::capacity_for(d) > F.plan.want_capacity ? gsp::capacity_for(d) : F.plan.want_capacity;
+    return reserve_pairs(r, cap, F.nums.wide);
+}
+
+// the zero region and the pair buffers, the block list, the preprocess kernel and — a shape's first frame — the sizing pass
+static gs_status stage_preprocess(Frame &F) {
+    gs_renderer *r = F.r;
+    gs_gaussians_buffer *g = F.g;
+    const gsp::FramePlan &plan = F.plan;
+    const bool sizing = F.nums.sizing, wide = F.nums.wide;
+    // the clear job of this frame, spread over the preprocess grid: tile ranges + the
+    // expansion's super-chunk sums
+    const size_t ranges_words = (size_t)F.num_tiles * 2;                                   // even: keeps the u64 sums aligned
+    const size_t esb_words = 2 * ((size_t)F.exp_grid / gs::EXP_SB + 1);                    // u64 super-chunk sums of the expansion
+    const size_t done_words = ((size_t)F.num_tiles + 31) / 32 + 1;                        // two-round frames: finished tiles
+    // (a two-round frame needs the sums of both rounds and the bits; cleared in every frame: ~1 KB)
+    const size_t zero_words = ranges_words + 2 * esb_words + 2 * done_words;
+    GS_TRY(dev_reserve(r->zero_region, zero_words * 4));
+    F.zero = (uint32_t *)r->zero_region.ptr;
+    F.esb = F.zero + ranges_words;
+    F.esb2 = F.esb + esb_words;
+    F.done_bits = F.esb2 + esb_words;
+    F.open_bits = F.done_bits + done_words;
+
+    if (!sizing && plan.want_capacity > r->pair_capacity) GS_TRY(reserve_pairs(r, plan.want_capacity, wide));
+    if (!sizing) GS_TRY(reserve_pairs(r, r->pair_capacity, wide));   // key width may have changed
+
+    F.fc.mask_culled_records = plan.mask_culled_records;
+    F.fc.nt_loads = plan.nt_loads;
+    if (!plan.block_cull || !g->block_bounds) F.fc.cull_gain = 0.0f;
+
+    gs::PreOut po;
+    po.recs = (uint32_t *)r->recs.ptr;
+    po.rect = (uint2 *)r->rect.ptr;
+    po.depth = (uint32_t *)r->depth.ptr;
+    po.chunk_tiles = (uint32_t *)r->chunk_tiles.ptr;
+    po.chunk_vis = (uint32_t *)r->chunk_vis.ptr;
+    po.zero_ptr = F.zero;
+    po.zero_words = (uint32_t)zero_words;
+    po.key_bias = F.near_bits;
+    po.block_bounds = (const float *)g->block_bounds;
+    po.chunk_hist = (uint32_t *)r->chunk_hist.ptr;
+    const bool top_hist = plan.depth_msd || plan.partition;      // the chunk rows count the TOP 10 bits (else the LSD sort's first digit)
+    po.digit_mask = top_hist ? (1u << gs::MSD_TOP_BITS) - 1u : first_digit_mask(F.nums.dbits, depth_radix_bits(F.nums.dbits));
+    po.digit_shift = top_hist ? gsp::msd_low_bits(F.nums, k_policy_params) : 0u;
+    po.hist_words = top_hist ? (1u << gs::MSD_TOP_BITS) / 2u : (uint32_t)gs::PP_THREADS;
+    po.block_list = nullptr;
+    po.block_count = nullptr;
+    r->list_mode = false;
+    if (F.fc.cull_gain > 0.0f && plan.use_list) GS_TRY(stage_block_cull(F, po));
+    const int nt = F.fc.nt_loads ? 1 : 0;
+    hipLaunchKernelGGL((plan.banded ? k_tbl_preprocess_banded[nt][switches().pre_serial ? 0 : 1] : k_tbl_preprocess[nt])[g->sh][g->cov], dim3(F.nchunks),
+                       dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar, F.n, F.fc, po);
+    GS_HIP(hipGetLastError());
+    r->launches++;
+    F.marks.mark(ST_SCAN);
+    if (sizing) GS_TRY(stage_sizing(F));
+    if (!(r->shape == F.shape)) r->shape_epoch++;
+    r->shape = F.shape;
+    return GS_OK;
+}
+
+// ---- depth sort of the visible Gaussians; its first pass reads the dense per-slot keys and
+//      compacts (count V stays on the device, grids from N) ----
+// pred: which Gaussians the compacting first pass takes (all visible ones; or one side of a partitioned frame's
+// threshold); their count goes to *visible_out.  Returns the side of dvals that holds the order; adds its passes.
+static gs_status stage_depth_sort(Frame &F, const gs::CompactPred &pred, uint32_t *visible_out, const uint32_t *dense_dev, int &dside,
+                                  uint32_t &dpasses) {
+    gs_renderer *r = F.r;
+    const uint32_t n = F.n, dbits = F.nums.dbits;
+    void *k2[2] = {r->dkeys[0].ptr, r->dkeys[1].ptr};
+    void *v2[2] = {r->dvals[0].ptr, r->dvals[1].ptr};
+    SortCompact cp;
+    cp.dense_keys = (const uint32_t *)r->depth.ptr;
+    cp.chunk_vis = (const uint32_t *)r->chunk_vis.ptr;
+    cp.visible_out = visible_out;
+    cp.dense_count = n;
+    // list frame: only the surviving blocks' slots; round 2 of a partitioned frame: none when the gate found nothing left
+    cp.dense_count_dev = dense_dev ? dense_dev : r->list_mode ? &F.state->list_slots : nullptr;
+    // (a partitioned frame's chunk rows count the top digit of ALL visible keys: its passes count their own)
+    cp.chunk_hist = pred.tau_dev ? nullptr : (const uint32_t *)r->chunk_hist.ptr;
+    cp.pred = pred;
+    cp.bucket_max = &F.state->depth_bucket_max;
+    const gs::SortCount dc{n, visible_out};
+    uint32_t passes = 0;
+    if (F.plan.depth_msd) {
+        // scratch of the bucket kernel's chunked path: the LSD sort's side 0 keys and the (not yet written)
+        // depth-ordered rects — the dense keys themselves stay intact for the parity taps
+        const uint32_t top_range = ((F.far_bits - F.near_bits) >> gsp::msd_low_bits(F.nums, k_policy_params)) + 1u;
+        GS_TRY(with_depth_items(n, [&](auto items) {
+            return run_depth_msd_items<decltype(items)::value>(F.sort, r, cp, dbits, top_range, r->dkeys[0].ptr, r->sorted_rect.ptr, passes);
+        }));
+        dside = 0;
+    } else if (depth_radix_bits(dbits) == (uint32_t)gs::RADIX_BITS_MAX)
+        GS_TRY((run_sort_rb<uint32_t, gs::RADIX_BITS_MAX>(F.sort, k2, v2, dc, dbits, &cp, dside, passes)));
+    else
+        GS_TRY((run_sort_rb<uint32_t, gs::RADIX_BITS>(F.sort, k2, v2, dc, dbits, &cp, dside, passes)));
+    dpasses += passes;
+    return GS_OK;
+}
+
+// a partitioned frame: the totals of the top digit (the histogram half of the MSD-first sort's pass), then the cut;
+// pred1 = round 1: the keys in front of the threshold
+static gs_status stage_round_threshold(Frame &F, gs::CompactPred &pred1) {
+    gs_renderer *r = F.r;
+    const uint32_t *dense_dev = r->list_mode ? &F.state->list_slots : nullptr;
+    GS_TRY(with_depth_items(F.n, [&](auto items) { return run_top_digit_totals<decltype(items)::value>(r, F.st, F.n, dense_dev); }));
+    gs::ThresholdIO ti;
+    ti.totals = (const uint32_t *)r->digit_totals.ptr;
+    ti.state = F.state;
+    ti.target = F.plan.round_k;
+    ti.low_bits = gsp::msd_low_bits(F.nums, k_policy_params);
+    hipLaunchKernelGGL(gs::k_round_threshold, dim3(1), dim3(512), 0, F.st, ti);
+    GS_HIP(hipGetLastError());
+    r->launches += 3;
+    GS_TRY(dev_reserve(r->keep_bits, F.nslots / 8 + 64));
+    pred1.tau_dev = &F.state->depth_tau;
+    pred1.keep_bits = (const uint32_t *)r->keep_bits.ptr;      // (side 0 loads and ignores them)
+    pred1.side = 0u;
+    return GS_OK;
+}
+
+// the tile ranges of one round's sorted pairs (gsp::plan_ranges)
+static gs_status stage_tile_ranges(Frame &F, uint32_t round, bool tile_msd, int tside, gs::SortCount tc) {
+    gs_renderer *r = F.r;
+    const uint32_t capacity = F.plan.capacity, num_tiles = F.num_tiles;
+    const bool wide = F.nums.wide;
+    switch (gsp::plan_ranges(F.nums, switches(), capacity, tile_msd, round)) {
+    case gsp::RANGES_NONE: break;
+    case gsp::RANGES_IN_BLEND:
+        F.tile_keys.keys = r->tkeys[tside].ptr;
+        F.tile_keys.count_dev = &F.state->pairs;
+        F.tile_keys.count_bound = capacity;
+        F.tile_keys.wide = wide ? 1u : 0u;
+        break;
+    case gsp::RANGES_SEARCH:
+        if (wide)
+            hipLaunchKernelGGL(gs::k_tile_ranges_search<uint32_t>, dim3((num_tiles + 3u) / 4u), dim3(256), 0, F.st,
+                               (const uint32_t *)r->tkeys[tside].ptr, tc, F.zero, num_tiles);
+        else
+            hipLaunchKernelGGL(gs::k_tile_ranges_search<uint16_t>, dim3((num_tiles + 3u) / 4u), dim3(256), 0, F.st,
+                               (const uint16_t *)r->tkeys[tside].ptr, tc, F.zero, num_tiles);
+        GS_HIP(hipGetLastError());
+        r->launches++;
+        break;
+    case gsp::RANGES_PASS:
+        if (wide)
+            hipLaunchKernelGGL(gs::k_tile_ranges<uint32_t>, dim3((uint32_t)(((uint64_t)capacity + 1023) / 1024)), dim3(256), 0, F.st,
+                               (const uint32_t *)r->tkeys[tside].ptr, tc, F.zero);
+        else
+            hipLaunchKernelGGL(gs::k_tile_ranges<uint16_t>, dim3((uint32_t)(((uint64_t)capacity + 2047) / 2048)), dim3(256), 0, F.st,
+                               (const uint16_t *)r->tkeys[tside].ptr, tc, F.zero);
+        GS_HIP(hipGetLastError());
+        r->launches++;
+        break;
+    }
+    return GS_OK;
+}
+
+// ---- pairs in depth order, tile sort, tile ranges: once per round ----
+// round: 0 the frame's only one; 1: the nearest `limit` Gaussians of the depth order; 2: the survivors of
+// k_round2_write (order_r2).  Returns the side of tkeys / tvals that holds the sorted pairs and the tile sort's passes.
+static gs_status stage_pairs_round(Frame &F, uint32_t round, const uint32_t *order, const uint32_t *count_dev, uint32_t limit, uint32_t *esb_r,
+                                   int &tside, uint32_t &tpasses) {
+    gs_renderer *r = F.r;
+    hipStream_t st = F.st;
+    const uint32_t capacity = F.plan.capacity;
+    if (round <= 1u) F.marks.mark(ST_EXPAND);
+    gs::ExpandIO eo;
+    eo.order = order;
+    eo.rect = (const uint2 *)r->rect.ptr;
+    eo.sorted_rect = (uint2 *)r->sorted_rect.ptr;
+    eo.count_dev = count_dev;
+    eo.limit = limit;
+    eo.round = round;
+    eo.sums = (uint32_t *)r->exp_sums.ptr;
+    eo.sb_sums = (unsigned long long *)esb_r;
+    eo.tvals = (uint32_t *)r->tvals[0].ptr;
+    eo.state = F.state;
+    eo.result = F.result;
+    eo.capacity = capacity;
+    eo.tiles_x = F.fc.tiles_x;
+    eo.gen = F.gen;
+    eo.sb_bound = F.exp_grid / gs::EXP_SB + 1;
+    eo.rect32 = F.fc.rect32;
+    eo.flags_dev = r->flags_target;
+    eo.wt_stores = r->wt_pairs ? 1u : 0u;
+    const bool cursor_kernel = gsp::plan_cursor_kernel(switches(), eo.sb_bound);
+    eo.cursors = cursor_kernel ? (gs::PairCursorRec *)r->cursors.ptr : nullptr;
+    // XCD-aware span order of the gather: XCD x takes C consecutive spans of every group of 8 C, so that its L2
+    // serves part of the gather (neighbours in depth order are often neighbours in the mirror).  Same-box sweep
+    // (gpurun_out/r04q/ab*.log): C = 0 / 16 / 64 / 256 / 1024 -> 58.3 / 53.3 / 49.1 / 54.3 / 90.6 us at 10 M, 261 / 258 /
+    // 231 / 228 / 293 us at 50 M, 12.0 / - / 10.5 / 21 / 26 us at 1 M.  GS3D_EXPAND_XCD=<C> forces, 0 = dispatch order.
+    const int exp_xcd = switches().expand_xcd;
+    uint32_t count_grid = (F.exp_grid + gs::EXP_COUNT_CHUNKS - 1) / gs::EXP_COUNT_CHUNKS;
+    eo.xcd_chunk = 0;
+    if (exp_xcd > 0 && count_grid >= 256u) {
+        eo.xcd_chunk = (uint32_t)exp_xcd;
+        count_grid = 8u * eo.xcd_chunk * ((count_grid + 8u * eo.xcd_chunk - 1u) / (8u * eo.xcd_chunk));
+    }
+    if (eo.rect32)
+        hipLaunchKernelGGL(gs::k_expand_count<true>, dim3(count_grid), dim3(gs::EXP_CHUNK), 0, st, eo);
+    else
+        hipLaunchKernelGGL(gs::k_expand_count<false>, dim3(count_grid), dim3(gs::EXP_CHUNK), 0, st, eo);
+    r->launches++;
+    if (cursor_kernel) {
+        hipLaunchKernelGGL(gs::k_pairs_cursors, dim3(eo.sb_bound), dim3(gs::EXP_SB), 0, st, eo);
+        r->launches++;
+    }
+    GS_HIP(hipGetLastError());
+    if (round <= 1u) F.marks.mark(ST_TSORT);
+
+    // ---- stable sort on the tile id alone (pairs are generated in depth order by its first pass) ----
+    tside = 0;
+    const gs::SortCount tc{capacity, &F.state->pairs};
+    const bool tile_msd = round == 0u && F.plan.tile_msd;      // (gsp::plan_tile_msd)
+    r->tile_msd = tile_msd;
+    if (tile_msd) {
+        if (F.nums.tile_bits > (uint32_t)gs::MSD_TOP_BITS + 6u) return fail(GS_ERR_INVALID_ARGUMENT, F.nums.tile_bits, 0, 0, "tile id bits");
+        GS_TRY((run_tile_msd_items<gs::SortCfg<uint16_t>::ITEMS>(F.sort, r, eo, tc, F.nums.tile_bits, F.num_tiles, F.zero,
+                                                                  &F.state->tile_bucket_max, tpasses)));
+        tside = 0;
+    } else {
+        // (a frame whose tile sort is LSD reports no bucket size: the next result must not carry a stale one)
+        if (r->state_tile_bmax_dirty) GS_HIP(hipMemsetAsync(&F.state->tile_bucket_max, 0, sizeof(uint32_t), st));
+        void *k2[2] = {r->tkeys[0].ptr, r->tkeys[1].ptr};
+        void *v2[2] = {r->tvals[0].ptr, r->tvals[1].ptr};
+        if (F.nums.wide)
+            GS_TRY((run_sort_rb<uint32_t, gs::RADIX_BITS>(F.sort, k2, v2, tc, F.nums.tile_bits, nullptr, tside, tpasses, &eo)));
+        else
+            GS_TRY((run_sort_rb<uint16_t, gs::RADIX_BITS>(F.sort, k2, v2, tc, F.nums.tile_bits, nullptr, tside, tpasses, &eo)));
+    }
+    r->state_tile_bmax_dirty = tile_msd;
+    if (round <= 1u) F.marks.mark(ST_RANGES);
+    GS_TRY(stage_tile_ranges(F, round, tile_msd, tside, tc));
+    r->tsorted_side = tside;          // (stage_blend reads the pairs of THIS round: round 1's blend runs before the frame ends)
+    return GS_OK;
+}
+
+// Between the rounds: what round 1's blend left open decides which of the remaining Gaussians round 2 renders (the gate,
+// the box table, one bit per slot); then their depth order — a partitioned frame sorts them (the side of dvals comes
+// back in dside), the others are compacted out of the full order into order_r2.
+static gs_status stage_round2_select(Frame &F, int &dside, uint32_t &dpasses) {
+    gs_renderer *r = F.r;
+    hipStream_t st = F.st;
+    const uint32_t n = F.n, num_tiles = F.num_tiles, round_k = F.plan.round_k;
+    const bool partition = F.plan.partition;
+    if (!partition) GS_TRY(dev_reserve(r->order_r2, (F.nn + 1024) * 4));      // (its largest size at once; padded like the sorts' values)
+    gs::Round2IO ro;
+    ro.order = (const uint32_t *)r->dvals[dside].ptr + round_k;
+    ro.rect = (const uint2 *)r->rect.ptr;
+    ro.done = F.done_bits;
+    ro.open = F.open_bits;
+    ro.order_out = (uint32_t *)r->order_r2.ptr;
+    ro.state = F.state;
+    ro.first = round_k;
+    ro.groups = (n - round_k + gs::R2_GROUP - 1u) / gs::R2_GROUP;
+    ro.tiles_x = F.fc.tiles_x;
+    ro.num_tiles = num_tiles;
+    // (per-slot arrays cover whole chunks: nslots; a list frame's live in list space, bounded by the same)
+    ro.slots = (uint32_t)F.nslots;
+    GS_TRY(dev_reserve(r->keep_bits, F.nslots / 8 + 64));
+    ro.keep_bits = (uint32_t *)r->keep_bits.ptr;
+    const uint32_t bits_grid = (uint32_t)((F.nslots + 256u * gs::R2_SLOT_ITEMS - 1u) / (256u * gs::R2_SLOT_ITEMS));
+    {
+        typedef void (*bits_fn)(gs::Round2IO);
+        static const bits_fn tbl[2][2] = {{gs::k_round2_slot_bits<false, false>, gs::k_round2_slot_bits<false, true>},
+                                          {gs::k_round2_slot_bits<true, false>, gs::k_round2_slot_bits<true, true>}};
+        GS_TRY(dev_reserve(r->box_table, ((size_t)num_tiles + 8) * 2));
+        ro.box_table = (const uint16_t *)r->box_table.ptr;
+        hipLaunchKernelGGL(gs::k_round2_gate, dim3(1), dim3(256), 0, st, ro, F.nums.band_tiles, n,
+                           r->list_mode ? (const uint32_t *)&F.state->list_slots : (const uint32_t *)nullptr);
+        hipLaunchKernelGGL(gs::k_round2_box_table, dim3((num_tiles + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)F.done_bits,
+                           (uint16_t *)r->box_table.ptr, F.fc.tiles_x, F.fc.tiles_y, (const gs::FrameState *)F.state);
+        r->launches += 2;
+        const bool lds = num_tiles <= gs::R2_LDS_TILES;
+        const size_t lds_bytes = lds ? ((size_t)num_tiles + 7) / 8 * 16 : 0;
+        const uint32_t persistent = bits_grid < 1024u ? bits_grid : 1024u;      // (4 / 2 workgroups per CU at 1080p / 4K)
+        hipLaunchKernelGGL(tbl[F.fc.rect32 ? 1 : 0][lds ? 1 : 0], dim3(persistent), dim3(256), lds_bytes, st, ro);
+    }
+    GS_HIP(hipGetLastError());
+    r->launches++;
+    if (partition) {
+        // the depth sort of what is left: keys behind the threshold whose slot bit is set
+        gs::CompactPred pred2;
+        pred2.tau_dev = &F.state->depth_tau;
+        pred2.keep_bits = (const uint32_t *)r->keep_bits.ptr;
+        pred2.side = 1u;
+        GS_TRY(stage_depth_sort(F, pred2, &F.state->round2_visible, &F.state->round2_dense, dside, dpasses));
+    } else {
+        GS_TRY(dev_reserve(r->r2_scan, ((size_t)F.nn / gs::R2_GROUP + 1) * (2 * 4 + 32 * 8) + 64));      // (its largest size: never regrown under frames in flight)
+        ro.masks = (unsigned long long *)r->r2_scan.ptr;
+        ro.counts = (uint32_t *)(ro.masks + (size_t)ro.groups * 32);
+        ro.offsets = ro.counts + ro.groups;
+        hipLaunchKernelGGL(gs::k_round2_count, dim3(ro.groups), dim3(256), 0, st, ro);
+        gs::ScanJob js{ro.counts, ro.offsets, &F.state->round2_visible, ro.groups, nullptr};
+        hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, js, js);
+        hipLaunchKernelGGL(gs::k_round2_write, dim3(ro.groups), dim3(256), 0, st, ro);
+        r->launches += 3;
+    }
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+// everything between the preprocess kernel and the frame's last blend: depth sort, then one round of pairs or two
+static gs_status stage_sort_and_rounds(Frame &F) {
+    gs_renderer *r = F.r;
+    gs::FrameState *state = F.state;
+    const gsp::FramePlan &plan = F.plan;
+    int dside = 0, tside = 0;
+    uint32_t dpasses = 0, tpasses = 0;
+    gs::CompactPred pred1;
+    if (plan.partition) GS_TRY(stage_round_threshold(F, pred1));
+    GS_TRY(stage_depth_sort(F, pred1, plan.partition ? &state->round1_visible : &state->visible, nullptr, dside, dpasses));
+    r->two_round = plan.two_round;
+    r->round1 = plan.round_k;
+    if (!plan.two_round) {
+        GS_TRY(stage_pairs_round(F, 0u, (const uint32_t *)r->dvals[dside].ptr, &state->visible, 0xffffffffu, F.esb, tside, tpasses));
+    } else {
+        F.tile_keys.done = F.done_bits;
+        F.tile_keys.open = F.open_bits;
+        if (plan.partition)
+            GS_TRY(stage_pairs_round(F, 1u, (const uint32_t *)r->dvals[dside].ptr, &state->round1_visible, 0xffffffffu, F.esb, tside, tpasses));
+        else
+            GS_TRY(stage_pairs_round(F, 1u, (const uint32_t *)r->dvals[dside].ptr, &state->visible, plan.round_k, F.esb, tside, tpasses));
+        F.marks.mark(ST_BLEND);
+        GS_TRY(stage_blend(F, 1u));
+        GS_TRY(stage_round2_select(F, dside, dpasses));
+        GS_TRY(stage_pairs_round(F, 2u, plan.partition ? (const uint32_t *)r->dvals[dside].ptr : (const uint32_t *)r->order_r2.ptr,
+                                 &state->round2_visible, 0xffffffffu, F.esb2, tside, tpasses));
+    }
+    r->sort_passes = dpasses + tpasses;
+    r->dsorted_side = dside;
+    r->tsorted_side = tside;
+    return GS_OK;
+}
+
+// Frames of one renderer share its scratch buffers and result blocks, so they must run one after
+// the other.  On one stream that is stream order; a caller that moves the renderer to ANOTHER
+// stream gets the same guarantee from the previous frame's end-of-frame event (a device-side wait,
+// the host does not block).
+// No event at the end of every frame (round 4: it cost ~4 us of a pipelined 1 M frame).  The event a stream change
+// needs is recorded on the PREVIOUS stream when the change happens (everything enqueued there is in front of it),
+// and the capacity history reads the self-validating result blocks (gen stored last, read first and last)
+// without asking an event first.  GS3D_FRAME_EVENT=1 restores the per-frame event (and the query in front of
+// every history read).
+static gs_status take_over_stream(gs_renderer *r, hipStream_t st) {
+    if (r->have_frame && (st != r->last_stream || r->last_stream_gone)) {
+        // (a stream that has been destroyed since recorded the event on its way out: gs_stream_destroy; a new stream may
+        // have received the old handle's value, hence the flag and not the comparison alone)
+        if (!switches().frame_event && !r->last_stream_gone) {
+            GS_HIP(hipEventRecord(r->done[r->gen & 1u], r->last_stream));
+            r->done_valid[r->gen & 1u] = true;
         }
-    } rank_fault_scope;
+        if (r->done_valid[r->gen & 1u]) GS_HIP(hipStreamWaitEvent(st, r->done[r->gen & 1u], 0));
+    }
+    return GS_OK;
+}
+
+static gs_status check_frame_args(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g, const gs_gaussian_transform_pod *gt,
+                                  const gs_model_transform_pod *mt, const gs_camera *cam, float *rgba) {
+    if (!r || !s || !g || !gt || !mt || !cam || !rgba)
+        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (g->buf->dev != r->dev || s->dev != r->dev)
+        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (cam->width == 0 || cam->height == 0 || cam->width > 65535u * 16u || cam->height > 65535u * 16u)
+        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "bad image size");
+    if ((uintptr_t)rgba & 15u)
+        return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)rgba, 16, 0,
+                    "the RGBA frame must be 16-byte aligned (pixels are stored as float4)");
+    if (gt->flags[0] > GS_DISPLAY_POINT)
+        return fail(GS_ERR_INVALID_ARGUMENT, gt->flags[0], 0, 0, "unknown GaussianDisplayMode %u", gt->flags[0]);
+    if (!(cam->near_plane >= 0.0f))
+        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the near plane must be >= 0 (depth keys are the bits of a positive float)");
+    return GS_OK;
+}
+
+static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g, const gs_gaussian_transform_pod *gt,
+                              const gs_model_transform_pod *mt, const gs_camera *cam, uint32_t band_ty0,
+                              uint32_t band_ty1, float *rgba, const gs_aux_targets *aux) {
+    GS_TRY(check_frame_args(r, s, g, gt, mt, cam, rgba));
+    GS_TRY(use_device(r->dev));
+    hipStream_t st = s->s;
+    GS_TRY(collect_timing(r));
+    GS_TRY(take_over_stream(r, st));
+    Frame F{r, st, g, aux, rgba, StageMarks{r, st, r->timing && r->ev_valid}};
+    F.mode = gt->flags[0];
+    gs::FrameConsts &fc = F.fc;
+    make_frame_consts(gt, mt, cam, band_ty0, band_ty1, fc);
+    const size_t n64 = gs_gaussians_buffer_len(g);
+    gsp::FrameNums &nums = F.nums;
+    nums.pod_bytes = (uint64_t)gs::pod_words(g->sh, g->cov) * 4u;
+    // (make_frame_consts only records that the display mode allows rect version 4: gsp::plan_tile_masks decides)
+    F.plan.tile_masks = gsp::plan_tile_masks(fc.tile_masks != 0u, n64, nums.pod_bytes, F.requests(), switches());
+    fc.tile_masks = F.plan.tile_masks ? 1u : 0u;
+    r->tile_masks = F.plan.tile_masks;
+    r->wt_pairs = fc.wt_pairs != 0u;
+    if (n64 > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, n64, 0, 0, "too many Gaussians");
+    const uint32_t n = F.n = (uint32_t)n64;
+    F.nchunks = (n + gs::PP_CHUNK - 1) / gs::PP_CHUNK;
+    F.num_tiles = fc.tiles_x * fc.tiles_y;
+    // one 256-Gaussian expansion chunk may touch at most 256 * num_tiles pairs: keep that inside 32 bits
+    if ((uint64_t)fc.tiles_x * fc.tiles_y > (1ull << 22))
+        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 2^22 tiles");
+    // tile rects are packed as 16-bit tile coordinates
+    if (fc.tiles_x > 0xffffu || fc.tiles_y > 0xffffu)
+        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 65535 tiles along one axis");
+    F.nn = n ? n : 1;
+    F.nc = F.nchunks ? F.nchunks : 1;
+    F.nslots = F.nc * (size_t)gs::PP_CHUNK;
+    F.exp_grid = (n + gs::EXP_CHUNK - 1) / gs::EXP_CHUNK;   // V <= N
+
+    F.hist = read_history(r);
+    F.shape.n = n;
+    F.shape.width = cam->width;
+    F.shape.height = cam->height;
+    F.shape.band0 = fc.band_ty0;
+    F.shape.band1 = fc.band_ty1;
+
+    F.marks.mark(ST_REPACK);
+    GS_TRY(ensure_planar(g, st));
+    if (r->last_order != g->order) {
+        if (r->last_order) gs_buffer_release(r->last_order);
+        r->last_order = g->order ? gs_buffer_retain(g->order) : nullptr;
+    }
+    F.marks.mark(ST_PRE);
+    GS_TRY(reserve_frame_scratch(F));
+    GS_TRY(arm_rank_watchdog(F));
 
     r->gen++;
-    const uint32_t gen = r->gen;
-    {
-        // the rank watchdog's sample of this frame (GS3D_TEST_RANK_WATCH=<n> pins it: tests)
-        static const char *watch_env = std::getenv("GS3D_TEST_RANK_WATCH");
-        t_watch = watch_env ? (uint32_t)std::strtoul(watch_env, nullptr, 10) : gen;
-    }
-    // From here on kernels of this frame may be in the stream.  Whatever way the function is left — also
-    // through GS_TRY / GS_HIP after an allocation or launch failure — the end-of-frame event of this
-    // generation is recorded behind them, so the next frame on ANOTHER stream waits for exactly these
-    // kernels before it touches the shared scratch and state buffers (a frame that failed half-way used
-    // to leave done[gen & 1] pointing at frame gen - 2).  Its result block carries no `gen`, so the
-    // capacity history skips it.
-    struct DoneGuard {
-        gs_renderer *r;
-        hipStream_t st;
-        uint32_t gen;
-        bool record;
-        ~DoneGuard() {
-            if (record) {
-                (void)hipEventRecord(r->done[gen & 1u], st);
-                r->done_valid[gen & 1u] = true;
-            } else {
-                r->done_valid[gen & 1u] = false;      // recorded when (if) the renderer moves to another stream
-            }
-            r->done_gen[gen & 1u] = gen;
-            r->done_shape[gen & 1u] = r->shape_epoch;
-            r->done_rounds[gen & 1u] = r->two_round ? 2 : 1;
-            r->done_round_k[gen & 1u] = r->two_round ? r->round1 : 0u;
-        }
-    } done_guard{r, st, gen, frame_event};
-    gs::FrameState *state = (gs::FrameState *)r->state.ptr;
-    gs::FrameResult *result = &r->results[gen & 1u];
+    const uint32_t gen = F.gen = r->gen;
+    // the rank watchdog's sample of this frame (GS3D_TEST_RANK_WATCH=<n> pins it: tests)
+    F.sort.watch = switches().test_rank_watch_set ? switches().test_rank_watch : gen;
+    DoneGuard done_guard{r, st, gen, switches().frame_event};
+    F.state = (gs::FrameState *)r->state.ptr;
+    F.result = &r->results[gen & 1u];
     r->n = n;
     r->tiles_x = fc.tiles_x;
     r->tiles_y = fc.tiles_y;
@@ -2828,647 +3384,45 @@ static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
     r->have_frame = true;
     r->launches = 0;
     r->list_mode = false;
+    r->two_round = false;
 
     // depth keys = bits of the (positive) view depth minus the bits of the near plane: every visible
     // depth lies in (near, far), so only bit_length(bits(far) - bits(near)) bits need sorting — a
     // bound the host knows without looking at the scene
-    const uint32_t near_bits = float_bits(cam->near_plane > 0.0f ? cam->near_plane : 0.0f);
-    const uint32_t far_bits = cam->far_plane > 0.0f ? float_bits(cam->far_plane) : 0u;
-    const uint32_t dbits = far_bits > near_bits ? bit_length(far_bits - near_bits) : 0u;
-    r->key_bias = near_bits;
-    const uint32_t tile_bits = bit_length(num_tiles ? num_tiles - 1 : 0);
+    F.near_bits = float_bits(cam->near_plane > 0.0f ? cam->near_plane : 0.0f);
+    F.far_bits = cam->far_plane > 0.0f ? float_bits(cam->far_plane) : 0u;
+    r->key_bias = F.near_bits;
 
-    // ---- which depth sort (gs_renderer::depth_msd) ----
-    // MSD-first needs a top digit of 10 bits and at most two bucket passes (of 9) below it: 11..28 key bits (the bench's planes,
-    // 0.1 / 100, give 27); with fewer or more bits the LSD passes stand.
-    const uint32_t msd_low_bits = dbits > (uint32_t)gs::MSD_TOP_BITS ? dbits - (uint32_t)gs::MSD_TOP_BITS : 0u;
-    const bool msd_possible = n != 0 && dbits > (uint32_t)gs::MSD_TOP_BITS && msd_low_bits <= 2u * (uint32_t)gs::RADIX_BITS_MAX;
-    bool depth_msd = false;
-    if (msd_possible) {
-        static const int msd_env = std::getenv("GS3D_DEPTH_MSD") ? std::atoi(std::getenv("GS3D_DEPTH_MSD")) : -1;
-        const int newer = hist_gen[0] > hist_gen[1] ? 0 : 1;
-        const int pinned = r->depth_msd_req >= 0 ? r->depth_msd_req : msd_env;
-        if (pinned >= 0) {
-            depth_msd = pinned != 0;
-        } else if (!sizing && hist_gen[newer] && r->done_shape[newer] == r->shape_epoch && hist_bmax[newer]) {
-            // hysteresis: leave MSD-first when a bucket no longer fits the register path, come back below 7/8 of it
-            const uint32_t b = hist_bmax[newer];
-            r->depth_bucket_seen = b;
-            depth_msd = r->depth_msd ? b <= gs::BKT_CAP : b <= gs::BKT_CAP - gs::BKT_CAP / 8u;
-        } else if (sizing) {
-            // no report yet: the buckets of a scene this small probably fit (and if not, the bucket kernel's chunked path
-            // still sorts them correctly, and the report of this very frame corrects the choice)
-            depth_msd = n <= (4u << 20);
-        } else {
-            depth_msd = r->depth_msd;      // frames in flight between the sizing frame and its report: keep the guess
-        }
-    }
-    r->depth_msd = depth_msd;
+    // ---- the frame's plan (gs_policy.h): everything that is decided before the first launch ----
+    nums.n = n;
+    nums.gen = gen;
+    nums.num_tiles = F.num_tiles;
+    nums.tiles_y = fc.tiles_y;
+    nums.band_rows = fc.band_ty1 - fc.band_ty0;
+    nums.band_tiles = nums.band_rows * fc.tiles_x;
+    nums.dbits = F.far_bits > F.near_bits ? bit_length(F.far_bits - F.near_bits) : 0u;
+    nums.tile_bits = bit_length(F.num_tiles ? F.num_tiles - 1 : 0);
+    nums.wide = F.num_tiles > 65536u;
+    nums.sizing = n != 0 && (r->pair_capacity == 0 || !(F.shape == r->shape));
+    nums.pair_capacity = r->pair_capacity;
+    nums.has_sh = g->sh != GS_SH_NONE;
+    nums.has_order = g->order != nullptr;
+    gsp::plan_frame(F.hist, nums, F.requests(), switches(), k_policy_params, r->sort_fb, r->rounds_fb, F.plan);
+    r->partitioned = F.plan.partition;
 
-    gs::TileKeys tile_keys{nullptr, nullptr, 0u, 0u, 0u, nullptr, nullptr};   // null keys: the blend reads its ranges from the range array
-    // GS3D_BLEND_GROUPS = 1 (half-tile lists), 2 (8x8 blocks) or 4 (8x4 blocks, default)
-    static const int groups = std::getenv("GS3D_BLEND_GROUPS") ? std::atoi(std::getenv("GS3D_BLEND_GROUPS")) : 4;
-    uint32_t band_tiles = (fc.band_ty1 - fc.band_ty0) * fc.tiles_x;
-    // The blend launch of one round (0: the frame's only one).
-    auto launch_blend = [&](uint32_t round) -> gs_status {
-        if (!band_tiles) return GS_OK;
-        typedef void (*blend_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
-                                 const gs::FrameState *, gs::TileKeys);
-        static const blend_fn tbl[3][3] = {
-            {gs::k_blend<0>, gs::k_blend_grouped<0, 2>, gs::k_blend_grouped<0, 4>},
-            {gs::k_blend<1>, gs::k_blend_grouped<1, 2>, gs::k_blend_grouped<1, 4>},
-            {gs::k_blend<2>, gs::k_blend_grouped<2, 2>, gs::k_blend_grouped<2, 4>}};
-        static const blend_fn tbl_rounds[3][2] = {{gs::k_blend_grouped<0, 2, true>, gs::k_blend_grouped<0, 4, true>},
-                                                  {gs::k_blend_grouped<1, 2, true>, gs::k_blend_grouped<1, 4, true>},
-                                                  {gs::k_blend_grouped<2, 2, true>, gs::k_blend_grouped<2, 4, true>}};
-        if (round != 0u && groups == 1) return fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
-        tile_keys.round = round;
-        if (aux) {
-            // the depth / pick planes ride in the grouped blend (G = 4 where the plain frame would take k_blend)
-            typedef void (*aux_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
-                                   const gs::FrameState *, gs::TileKeys, gs::AuxIO);
-            static const aux_fn tbl_aux[2][3][2] = {
-                {{gs::k_blend_grouped<0, 2, false, true>, gs::k_blend_grouped<0, 4, false, true>},
-                 {gs::k_blend_grouped<1, 2, false, true>, gs::k_blend_grouped<1, 4, false, true>},
-                 {gs::k_blend_grouped<2, 2, false, true>, gs::k_blend_grouped<2, 4, false, true>}},
-                {{gs::k_blend_grouped<0, 2, true, true>, gs::k_blend_grouped<0, 4, true, true>},
-                 {gs::k_blend_grouped<1, 2, true, true>, gs::k_blend_grouped<1, 4, true, true>},
-                 {gs::k_blend_grouped<2, 2, true, true>, gs::k_blend_grouped<2, 4, true, true>}}};
-            gs::AuxIO aio;
-            aio.depth = aux->depth;
-            aio.pick = aux->pick;
-            aio.tcut = 1.0f - aux->pick_threshold;
-            aio.key_bias = r->key_bias;
-            aio.depth_keys = (const uint32_t *)r->depth.ptr;
-            aio.block_list = r->list_mode ? (const uint32_t *)r->block_list.ptr : nullptr;
-            aio.order = r->last_order ? (const uint32_t *)r->last_order->ptr : nullptr;
-            hipLaunchKernelGGL(tbl_aux[round != 0u ? 1 : 0][mode][groups == 2 ? 0 : 1], dim3(band_tiles), dim3(gs::BLEND_THREADS), 0, st,
-                               (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
-                               (const uint32_t *)r->recs.ptr, fc, (float4 *)rgba, (const gs::FrameState *)r->state.ptr, tile_keys,
-                               aio);
-        } else {
-            const blend_fn blend = round != 0u ? tbl_rounds[mode][groups == 2 ? 0 : 1] : tbl[mode][groups == 1 ? 0 : groups == 2 ? 1 : 2];
-            hipLaunchKernelGGL(blend, dim3(band_tiles), dim3(gs::BLEND_THREADS), 0, st,
-                               (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
-                               (const uint32_t *)r->recs.ptr, fc, (float4 *)rgba, (const gs::FrameState *)r->state.ptr, tile_keys);
-        }
-        GS_HIP(hipGetLastError());
-        r->launches++;
-        return GS_OK;
-    };
-    r->two_round = false;
-    // ---- one round, or two (DESIGN.md §4.2 "rounds"): decided before anything is launched, because a partitioned frame
-    //      changes what the preprocess kernel counts and what the depth sorts see ----
-    // A deep scene finishes most of its tiles on the nearest fraction of its Gaussians; everything behind them is
-    // emitted, sorted and staged for nothing.  Two rounds: the frame of the nearest K visible Gaussians first, whose
-    // blend leaves a bit per finished tile and the pixel state of the others; then the rest, without the Gaussians whose
-    // (small) rect lies in finished tiles, resumed by the same blend.  The image is the single round's, bit for bit: a
-    // tile's list is the concatenation of its two lists, and a dropped Gaussian touches finished pixels only.
-    static const int rounds_env = std::getenv("GS3D_ROUNDS") ? std::atoi(std::getenv("GS3D_ROUNDS")) : -1;
-    static const long round1_env = std::getenv("GS3D_ROUND1") ? std::atol(std::getenv("GS3D_ROUND1")) : 0;
-    uint32_t round_k = 0;
-    bool two_round = false;
-    if (r->rounds_epoch != r->shape_epoch) {      // a new shape: the feedback starts over
-        r->rounds_epoch = r->shape_epoch;
-        r->round_scale = 1.0f;
-        r->rounds_off = false;
-        r->auto_deep = false;
-        r->auto_k = 0;
-    }
-    if (band_tiles && groups != 1 && n > 4096u) {
-        const int newer = hist_gen[0] > hist_gen[1] ? 0 : 1;
-        const bool have = !sizing && hist_gen[newer] && r->done_shape[newer] == r->shape_epoch;
-        const uint32_t v_est = have ? hist_v[newer] : n;
-        if (have && r->done_rounds[newer] == 1) {
-            r->full_pairs = hist_d[newer];
-            r->full_pairs_v = hist_v[newer];
-        }
-        // pairs a single round would emit now: the measured count, scaled with the visible Gaussians since
-        const double d_full = r->full_pairs_v ? (double)r->full_pairs * (double)v_est / (double)r->full_pairs_v : (double)r->full_pairs;
-        // The renderer's own choice.  Measured (same-box A/B, gpurun_out/r05r): 10 M at 1080p (2 970 pairs per tile) -9 %,
-        // at 4K (1 716) -8 %, 50 M (14 800) -24 %; the 1 M scene (296 pairs per tile) finishes its tiles only at the end of
-        // their lists.  Round 1 is given ~250 pairs per tile: the bench scenes finish EVERY tile from ~170 on (k_round2_gate
-        // then skips round 2), and a shorter round 1 is a shorter tile sort (same-box sweep, gpurun_out/r05x/ab_k.txt: 10 M
-        // 0.813 / 0.801 / 0.790 / 0.786 ms at 400 / 270 / 210 / 170 pairs per tile, 50 M 2.07 / 2.06 / 2.02 / 2.02) — and a frame
-        // takes two rounds when that is at most a third of its Gaussians and the pairs to save outweigh the launches of a
-        // second round.  The feedback below lengthens a round 1 that turns out too short.
-        const double per_tile = d_full / (double)band_tiles;
-        double k_auto = per_tile > 0.0 ? (double)v_est * 250.0 / per_tile * (double)r->round_scale : 0.0;
-        if (have && r->done_rounds[newer] == 2 && hist_gen[newer] != r->rounds_fb_gen) {
-            // feedback: a round 1 that finishes less than 60 % of the tiles it has pairs for was too short (or the scene
-            // does not occlude)
-            r->rounds_fb_gen = hist_gen[newer];
-            if ((uint64_t)hist_tdone[newer] * 10u < ((uint64_t)hist_tdone[newer] + hist_topen[newer]) * 6u) {
-                r->round_scale *= 1.5f;
-                if (r->round_scale > 3.4f) {
-                    r->rounds_off = true;
-                    r->rounds_off_gen = r->gen;
-                }
-            } else if (hist_topen[newer] != 0u && (uint64_t)hist_topen[newer] * 10u <= (uint64_t)hist_tdone[newer] + hist_topen[newer] &&
-                       r->round_scale < 2.7f) {
-                // nearly there (at most a tenth of the tiles with pairs left open): a little longer and round 2 is skipped
-                r->round_scale *= 1.25f;
-            }
-        }
-        if (r->rounds_off && r->gen - r->rounds_off_gen > 512u) {
-            // ... but not for ever: the camera may have moved into a view that does occlude; another try every 512 frames
-            r->rounds_off = false;
-            r->round_scale = 1.0f;
-        }
-        bool deep = have && !r->rounds_off && d_full >= 12.0e6 && per_tile >= 1200.0 && k_auto * 3.0 <= (double)v_est;
-        if (!have && !sizing && r->rounds_epoch == r->shape_epoch) {
-            // frames in flight: no finished report to consult (both result blocks belong to frames still running):
-            // what the last frame with a report decided stands
-            deep = r->auto_deep && !r->rounds_off;
-            k_auto = (double)r->auto_k;
-        }
-        r->auto_deep = deep;
-        r->auto_k = (uint64_t)k_auto;
-        const int pinned = r->rounds_req >= 0 ? r->rounds_req : rounds_env;
-        two_round = pinned >= 0 ? pinned != 0 : deep;
-        const uint64_t k = r->round1_req ? r->round1_req : round1_env > 0 ? (uint64_t)round1_env : pinned > 0 && !deep ? v_est / 4u : (uint64_t)k_auto;
-        round_k = (uint32_t)((k + 2047u) / 2048u * 2048u < n ? (k + 2047u) / 2048u * 2048u : 0u);
-        if (round_k == 0u) two_round = false;
-    }
-    // A two-round frame is PARTITIONED when the depth keys have a top digit to cut at (and the frame is not the one that
-    // sizes the pair buffers): the preprocess kernel counts the top 10 bits of every key, k_round_threshold picks the digit
-    // boundary with at least round_k Gaussians in front of it, and each round's depth sort — LSD passes whose compacting
-    // first pass takes only its side of the boundary (gs::CompactPred) — sorts what that round renders: the nearest ones,
-    // then what k_round2_slot_bits keeps of the rest.  Otherwise round 2 is compacted out of the full depth order
-    // (k_round2_count / _write).
-    // Measured, same-box A/B.  With a round 2 that runs (gpurun_out/r05t/ab3.txt): 50 M 2.42 against 2.53 ms (depth-sort stage
-    // 0.318 against 0.462: a threshold + two sorts whose first pass streams the 200 MB of dense keys for 1-2 M survivors,
-    // against one full sort + the compaction), 10 M 0.908 against 0.865 (two first passes of ~50 us each at their launch-bound
-    // floors cost more than the full sort of 7 M keys saves).  With a round 2 that k_round2_gate skips — round 1 finished every
-    // tile — only round 1's sort remains (gpurun_out/r05x/ab_part.txt): 10 M 0.806 against 0.817, 4K 1.29 against 1.32, 50 M 2.00
-    // against 2.15.  So: from 32 M Gaussians, or when the newest two-round report of this shape says that round 1 finished
-    // every tile (kept while no report is available); GS3D_ROUND_PARTITION=0/1 forces.
-    static const int partition_env = std::getenv("GS3D_ROUND_PARTITION") ? std::atoi(std::getenv("GS3D_ROUND_PARTITION")) : -1;
-    bool partition_auto = n >= (32u << 20);
-    {
-        const int newer = hist_gen[0] > hist_gen[1] ? 0 : 1;
-        if (!sizing && hist_gen[newer] && r->done_shape[newer] == r->shape_epoch) {
-            if (r->done_rounds[newer] == 2) r->auto_all_done = hist_tdone[newer] == band_tiles && hist_topen[newer] == 0u;
-        } else if (sizing) {
-            r->auto_all_done = false;
-        }
-        partition_auto = partition_auto || r->auto_all_done;
-    }
-    const bool partition = two_round && !sizing && dbits > (uint32_t)gs::MSD_TOP_BITS && n < (1u << 30) &&
-                           (partition_env >= 0 ? partition_env != 0 : partition_auto);
-    r->partitioned = partition;
-    if (partition) {
-        depth_msd = false;
-        r->depth_msd = false;
-    }
     if (n == 0) {
-        // nothing to project: clear the ranges, blend the background
-        GS_TRY(dev_reserve(r->zero_region, (size_t)num_tiles * 8));
-        GS_HIP(hipMemsetAsync(r->zero_region.ptr, 0, (size_t)num_tiles * 8, st));
-        GS_TRY(reserve_pairs(r, 1, wide));
-        hipLaunchKernelGGL(gs::k_publish_result, dim3(1), dim3(64), 0, st, result, state, gen, r->flags_target);
-        GS_HIP(hipGetLastError());
-        r->launches++;
-        mark(ST_SCAN); mark(ST_DSORT); mark(ST_EXPAND); mark(ST_TSORT); mark(ST_RANGES);
-        r->sort_passes = 0;
-        r->dsorted_side = r->tsorted_side = 0;
+        GS_TRY(stage_empty_frame(F));
     } else {
-        // the clear job of this frame, spread over the preprocess grid: tile ranges + the
-        // expansion's super-chunk sums
-        const size_t ranges_words = (size_t)num_tiles * 2;                                   // even: keeps the u64 sums aligned
-        const size_t esb_words = 2 * ((size_t)exp_grid / gs::EXP_SB + 1);                    // u64 super-chunk sums of the expansion
-        const size_t done_words = ((size_t)num_tiles + 31) / 32 + 1;                        // two-round frames: finished tiles
-        // (a two-round frame needs the sums of both rounds and the bits; cleared in every frame: ~1 KB)
-        const size_t zero_words = ranges_words + 2 * esb_words + 2 * done_words;
-        GS_TRY(dev_reserve(r->zero_region, zero_words * 4));
-        uint32_t *zero = (uint32_t *)r->zero_region.ptr;
-        uint32_t *esb = zero + ranges_words;
-        uint32_t *esb2 = esb + esb_words;
-        uint32_t *done_bits = esb2 + esb_words;
-        uint32_t *open_bits = done_bits + done_words;
-
-        if (!sizing && want_capacity > r->pair_capacity) GS_TRY(reserve_pairs(r, want_capacity, wide));
-        if (!sizing) GS_TRY(reserve_pairs(r, r->pair_capacity, wide));   // key width may have changed
-
-        // Records with SH take the two-phase kernel (geometry chunks first, SH chunks only for the
-        // lanes that survive culling): with the mirror in spatial order whole 128-byte lines of
-        // culled Gaussians are never fetched; with a random order it costs the same as the
-        // single-phase kernel (measured).  GS3D_FORCE_BANDED=0/1 overrides for experiments.
-        static const int force_banded = std::getenv("GS3D_FORCE_BANDED") ? std::atoi(std::getenv("GS3D_FORCE_BANDED")) : -1;
-        const bool banded = g->sh != GS_SH_NONE && (force_banded >= 0 ? force_banded != 0 : true);
-        static const int mask_env = std::getenv("GS3D_MASK_REC") ? std::atoi(std::getenv("GS3D_MASK_REC")) : -1;
-        fc.mask_culled_records = mask_env >= 0 ? (uint32_t)mask_env : (g->order != nullptr ? 1u : 0u);
-        // Non-temporal loads of the mirror once it no longer fits the 256 MiB Infinity Cache: nothing of
-        // it survives until the next frame anyway (10 M x 224 B: preprocess 0.440 -> 0.421 ms); a mirror that
-        // does fit is re-read from the caches frame after frame and loses that with nt (1 M x 48 B:
-        // 22 -> 27 us).  GS3D_NT_LOADS=0/1 forces.
-        static const int nt_env = std::getenv("GS3D_NT_LOADS") ? std::atoi(std::getenv("GS3D_NT_LOADS")) : -1;
-        fc.nt_loads = nt_env >= 0 ? (uint32_t)nt_env : ((uint64_t)n * gs::pod_words(g->sh, g->cov) * 4u > (512ull << 20) ? 1u : 0u);
-        static const bool block_cull_off = std::getenv("GS3D_BLOCK_CULL") && std::getenv("GS3D_BLOCK_CULL")[0] == '0';
-        // SH-less records are 48 bytes: the block test (one more dependent load per workgroup)
-        // costs more than skipping them saves (measured at 1 M: +4 us on a 20 us kernel)
-        if (block_cull_off || !g->block_bounds || !banded) fc.cull_gain = 0.0f;
-
-        gs::PreOut po;
-        po.recs = (uint32_t *)r->recs.ptr;
-        po.rect = (uint2 *)r->rect.ptr;
-        po.depth = (uint32_t *)r->depth.ptr;
-        po.chunk_tiles = (uint32_t *)r->chunk_tiles.ptr;
-        po.chunk_vis = (uint32_t *)r->chunk_vis.ptr;
-        po.zero_ptr = zero;
-        po.zero_words = (uint32_t)zero_words;
-        po.key_bias = near_bits;
-        po.block_bounds = (const float *)g->block_bounds;
-        po.chunk_hist = (uint32_t *)r->chunk_hist.ptr;
-        const bool top_hist = depth_msd || partition;      // the chunk rows count the TOP 10 bits (else the LSD sort's first digit)
-        po.digit_mask = top_hist ? (1u << gs::MSD_TOP_BITS) - 1u : first_digit_mask(dbits, depth_radix_bits(dbits));
-        po.digit_shift = top_hist ? msd_low_bits : 0u;
-        po.hist_words = top_hist ? (1u << gs::MSD_TOP_BITS) / 2u : (uint32_t)gs::PP_THREADS;
-        po.block_list = nullptr;
-        po.block_count = nullptr;
-        // Block list (k_block_cull): one thread per block tests it, the survivors are handed to the first
-        // workgroups of the preprocess grid.  GS3D_BLOCK_LIST=0 keeps the test inside the preprocess kernel.
-        // It pays when most blocks are culled (a rank's band of 8 at 50 M: preprocess 0.57 -> 0.41 ms) and
-        // costs its launch when few are (whole 1080p frame at 10 M: +4 us), so it is taken when the newest
-        // finished frame of this shape saw less than half of the Gaussians, or — no such frame yet — when
-        // the frame is a band.  GS3D_BLOCK_LIST=0/1 forces.
-        static const int block_list_env = std::getenv("GS3D_BLOCK_LIST") ? std::atoi(std::getenv("GS3D_BLOCK_LIST")) : -1;
-        bool use_list = fc.band_ty1 - fc.band_ty0 < fc.tiles_y;
-        if (!sizing && (hist_gen[0] || hist_gen[1])) use_list = hist_v[hist_gen[0] > hist_gen[1] ? 0 : 1] < n / 2u;
-        if (block_list_env >= 0) use_list = block_list_env != 0;
-        // the list frame keeps its outputs in list space: list_slots = blocks * 1024 must fit 32 bits, and the
-        // look-back of k_block_cull is written for at most 2^20 groups of 256 blocks
-        if (n > 0xfffff000u) use_list = false;
-        r->list_mode = false;
-        if (fc.cull_gain > 0.0f && use_list) {
-            const uint32_t groups = (nchunks + 255u) / 256u;
-            GS_TRY(dev_reserve(r->block_list, (size_t)nchunks * 4));
-            GS_TRY(dev_reserve(r->cull_status, (size_t)groups * 4));
-            // Tag of this frame's status words: 22 bits of the generation.  A word must never hold this tag
-            // before its group publishes: consecutive list frames over the same groups overwrite every word
-            // with the previous tag; in every other case (first use, a gap of frames without the list, another
-            // group count) the words are cleared first, and the tag 0 is skipped.
-            const uint32_t tag = (gen & 0x3fffffu) ? (gen & 0x3fffffu) : 0x3fffffu;
-            if (r->cull_last_gen + 1u != gen || r->cull_last_groups != groups || (gen & 0x3fffffu) <= 1u)
-                GS_HIP(hipMemsetAsync(r->cull_status.ptr, 0, (size_t)groups * 4, st));
-            r->cull_last_gen = gen;
-            r->cull_last_groups = groups;
-            hipLaunchKernelGGL(gs::k_block_cull, dim3(groups), dim3(256), 0, st, (const float *)g->block_bounds, nchunks, fc,
-                               (uint32_t *)r->block_list.ptr, state, (uint32_t *)r->cull_status.ptr, tag, groups);
-            GS_HIP(hipGetLastError());
-            r->launches++;
-            po.block_list = (const uint32_t *)r->block_list.ptr;
-            po.block_count = &state->list_blocks;
-            r->list_mode = true;
-        }
-        // GS3D_PRE_PIPELINE=0: the two-phase kernel without the prefetch of the next Gaussian's geometry chunks
-        static const bool pre_serial = std::getenv("GS3D_PRE_PIPELINE") && std::getenv("GS3D_PRE_PIPELINE")[0] == '0';
-        const int nt = fc.nt_loads ? 1 : 0;
-        hipLaunchKernelGGL((banded ? k_tbl_preprocess_banded[nt][pre_serial ? 0 : 1] : k_tbl_preprocess[nt])[g->sh][g->cov], dim3(nchunks),
-                           dim3(gs::PP_THREADS), 0, st, (const uint4 *)g->planar, n, fc, po);
-        GS_HIP(hipGetLastError());
-        r->launches++;
-        mark(ST_SCAN);
-
-        if (sizing) {
-            // First frame of this shape: measure D before sizing the pair buffers (the only blocking
-            // step; steady-state frames take the capacity from the history instead)
-            gs::ScanJob jt{(const uint32_t *)r->chunk_tiles.ptr, (uint32_t *)r->scan_tmp.ptr, r->host_counters, nchunks,
-                           r->list_mode ? &state->list_blocks : nullptr};
-            hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, jt, jt);
-            GS_HIP(hipGetLastError());
-            GS_HIP(hipStreamSynchronize(st));
-            const uint32_t d = r->host_counters[0];
-            if (d == 0xffffffffu) {
-                r->shape = FrameShape();
-                return fail(GS_ERR_PAIR_OVERFLOW, n, 0, 0,
-                            "the frame needs more than 2^32 (tile, Gaussian) pairs; pair indices are 32-bit");
-            }
-            r->full_pairs = d;              // (the visible count it belongs to comes with the frame's report)
-            r->full_pairs_v = 0;
-            const uint64_t cap = capacity_for(d) > want_capacity ? capacity_for(d) : want_capacity;
-            GS_TRY(reserve_pairs(r, cap, wide));
-        }
-        if (!(r->shape == shape)) r->shape_epoch++;
-        r->shape = shape;
-        // A two-round frame sizes its grids — and bounds each round — by what a ROUND emitted last time, not by the single-round
-        // pair count that sized the buffers (50 M: 3 M pairs per round in buffers for 150 M: the emission's and the tile sort's
-        // 37 000 mostly empty workgroups cost 20-40 us per kernel): twice the larger round of the newest two-round report, with
-        // the usual head room.  A round that still outgrows it skips the frame like any pair overflow (the next one has the
-        // report); the first two-round frame of a shape, and any frame without a report, use the buffers' capacity.
-        uint32_t capacity = (uint32_t)r->pair_capacity;
-        if (two_round) {
-            const int newer = hist_gen[0] > hist_gen[1] ? 0 : 1;
-            uint64_t want = 0;
-            // (only a report of a frame whose round 1 was as long as this one's says anything about this frame's rounds)
-            if (!sizing && hist_gen[newer] && r->done_shape[newer] == r->shape_epoch && r->done_rounds[newer] == 2 && hist_rmax[newer] &&
-                r->done_round_k[newer] == round_k)
-                want = capacity_for(2ull * hist_rmax[newer]);
-            else if (!sizing && !hist_gen[newer] && r->round_cap && r->round_cap_k == round_k)
-                want = r->round_cap;          // frames in flight: the last bound stands
-            if (want && want < capacity) capacity = (uint32_t)want;
-            r->round_cap = want;
-            r->round_cap_k = round_k;
-        }
-        mark(ST_DSORT);
-
-        // ---- depth sort of the visible Gaussians; its first pass reads the dense per-slot keys and
-        //      compacts (count V stays on the device, grids from N) ----
-        int dside = 0;
-        uint32_t dpasses = 0;
-        // pred: which Gaussians the compacting first pass takes (all visible ones; or one side of a partitioned frame's
-        // threshold); their count goes to *visible_out
-        auto depth_sort = [&](const gs::CompactPred &pred, uint32_t *visible_out, const uint32_t *dense_dev = nullptr) -> gs_status {
-            void *k2[2] = {r->dkeys[0].ptr, r->dkeys[1].ptr};
-            void *v2[2] = {r->dvals[0].ptr, r->dvals[1].ptr};
-            SortCompact cp;
-            cp.dense_keys = (const uint32_t *)r->depth.ptr;
-            cp.chunk_vis = (const uint32_t *)r->chunk_vis.ptr;
-            cp.visible_out = visible_out;
-            cp.dense_count = n;
-            // list frame: only the surviving blocks' slots; round 2 of a partitioned frame: none when the gate found nothing left
-            cp.dense_count_dev = dense_dev ? dense_dev : r->list_mode ? &state->list_slots : nullptr;
-            // (a partitioned frame's chunk rows count the top digit of ALL visible keys: its passes count their own)
-            cp.chunk_hist = pred.tau_dev ? nullptr : (const uint32_t *)r->chunk_hist.ptr;
-            const gs::SortCount dc{n, visible_out};
-            t_compact_pred = pred;
-            struct PredScope {
-                ~PredScope() { t_compact_pred = gs::CompactPred(); }
-            } pred_scope;
-            uint32_t passes = 0;
-            if (depth_msd) {
-                // scratch of the bucket kernel's chunked path: the LSD sort's side 0 keys and the (not yet written)
-                // depth-ordered rects — the dense keys themselves stay intact for the parity taps
-                const uint32_t top_range = ((far_bits - near_bits) >> msd_low_bits) + 1u;
-                if (n >= (4u << 20))
-                    GS_TRY((run_depth_msd_items<gs::SortCfg<uint32_t>::ITEMS_LARGE>(r, st, cp, dbits, top_range, r->dkeys[0].ptr,
-                                                                                  r->sorted_rect.ptr, &state->depth_bucket_max, passes)));
-                else
-                    GS_TRY((run_depth_msd_items<gs::SortCfg<uint32_t>::ITEMS>(r, st, cp, dbits, top_range, r->dkeys[0].ptr,
-                                                                            r->sorted_rect.ptr, &state->depth_bucket_max, passes)));
-                dside = 0;
-            } else if (depth_radix_bits(dbits) == (uint32_t)gs::RADIX_BITS_MAX)
-                GS_TRY((run_sort_rb<uint32_t, gs::RADIX_BITS_MAX>(r->dev, k2, v2, r->ghist, r->digit_totals, dc, dbits, &cp,
-                                                                  st, dside, passes, r->launches)));
-            else
-                GS_TRY((run_sort_rb<uint32_t, gs::RADIX_BITS>(r->dev, k2, v2, r->ghist, r->digit_totals, dc, dbits, &cp, st,
-                                                              dside, passes, r->launches)));
-            dpasses += passes;
-            return GS_OK;
-        };
-        gs::CompactPred pred1;                  // round 1 of a partitioned frame: the keys in front of the threshold
-        if (partition) {
-            // the totals of the top digit (the histogram half of the MSD-first sort's pass), then the cut
-            if (n >= (4u << 20))
-                GS_TRY((run_top_digit_totals<gs::SortCfg<uint32_t>::ITEMS_LARGE>(r, st, n, r->list_mode ? &state->list_slots : nullptr)));
-            else
-                GS_TRY((run_top_digit_totals<gs::SortCfg<uint32_t>::ITEMS>(r, st, n, r->list_mode ? &state->list_slots : nullptr)));
-            gs::ThresholdIO ti;
-            ti.totals = (const uint32_t *)r->digit_totals.ptr;
-            ti.state = state;
-            ti.target = round_k;
-            ti.low_bits = msd_low_bits;
-            hipLaunchKernelGGL(gs::k_round_threshold, dim3(1), dim3(512), 0, st, ti);
-            GS_HIP(hipGetLastError());
-            r->launches += 3;
-            GS_TRY(dev_reserve(r->keep_bits, nslots / 8 + 64));
-            pred1.tau_dev = &state->depth_tau;
-            pred1.keep_bits = (const uint32_t *)r->keep_bits.ptr;      // (side 0 loads and ignores them)
-            pred1.side = 0u;
-        }
-        GS_TRY(depth_sort(pred1, partition ? &state->round1_visible : &state->visible));
-
-        // ---- pairs in depth order, tile sort, tile ranges: once per round ----
-        int tside = 0;
-        uint32_t tpasses = 0;
-        // round: 0 the frame's only one; 1: the nearest `limit` Gaussians of the depth order; 2: the survivors of
-        // k_round2_write (order_r2)
-        auto pairs_round = [&](uint32_t round, const uint32_t *order, const uint32_t *count_dev, uint32_t limit, uint32_t *esb_r) -> gs_status {
-            if (round <= 1u) mark(ST_EXPAND);
-            gs::ExpandIO eo;
-            eo.order = order;
-            eo.rect = (const uint2 *)r->rect.ptr;
-            eo.sorted_rect = (uint2 *)r->sorted_rect.ptr;
-            eo.count_dev = count_dev;
-            eo.limit = limit;
-            eo.round = round;
-            eo.sums = (uint32_t *)r->exp_sums.ptr;
-            eo.sb_sums = (unsigned long long *)esb_r;
-            eo.tvals = (uint32_t *)r->tvals[0].ptr;
-            eo.state = state;
-            eo.result = result;
-            eo.capacity = capacity;
-            eo.tiles_x = fc.tiles_x;
-            eo.gen = gen;
-            eo.sb_bound = exp_grid / gs::EXP_SB + 1;
-            eo.rect32 = fc.rect32;
-            eo.flags_dev = r->flags_target;
-            eo.wt_stores = r->wt_pairs ? 1u : 0u;
-            // Where a wave of k_pairs_emit starts: found by the wave itself (a search over the super-chunk
-            // sums: one step per 256 of them) or looked up in a table that k_pairs_cursors writes first.
-            // The table costs a launch and wins once the search needs more than one step (A/B on one box:
-            // 1 M 0.369 vs 0.366 ms, 10 M 1.227 vs 1.226, 50 M 4.60 vs 4.80).  GS3D_CURSOR_KERNEL=0/1 forces.
-            static const int cursor_env = std::getenv("GS3D_CURSOR_KERNEL") ? std::atoi(std::getenv("GS3D_CURSOR_KERNEL")) : -1;
-            const bool cursor_kernel = cursor_env >= 0 ? cursor_env != 0 : eo.sb_bound > 256u;
-            eo.cursors = cursor_kernel ? (gs::PairCursorRec *)r->cursors.ptr : nullptr;
-            // XCD-aware span order of the gather: XCD x takes C consecutive spans of every group of 8 C, so that its L2
-            // serves part of the gather (neighbours in depth order are often neighbours in the mirror).  Same-box sweep
-            // (gpurun_out/r04q/ab*.log): C = 0 / 16 / 64 / 256 / 1024 -> 58.3 / 53.3 / 49.1 / 54.3 / 90.6 us at 10 M, 261 / 258 /
-            // 231 / 228 / 293 us at 50 M, 12.0 / - / 10.5 / 21 / 26 us at 1 M.  GS3D_EXPAND_XCD=<C> forces, 0 = dispatch order.
-            static const int exp_xcd = std::getenv("GS3D_EXPAND_XCD") ? std::atoi(std::getenv("GS3D_EXPAND_XCD")) : 64;
-            uint32_t count_grid = (exp_grid + gs::EXP_COUNT_CHUNKS - 1) / gs::EXP_COUNT_CHUNKS;
-            eo.xcd_chunk = 0;
-            if (exp_xcd > 0 && count_grid >= 256u) {
-                eo.xcd_chunk = (uint32_t)exp_xcd;
-                count_grid = 8u * eo.xcd_chunk * ((count_grid + 8u * eo.xcd_chunk - 1u) / (8u * eo.xcd_chunk));
-            }
-            if (eo.rect32)
-                hipLaunchKernelGGL(gs::k_expand_count<true>, dim3(count_grid), dim3(gs::EXP_CHUNK), 0, st, eo);
-            else
-                hipLaunchKernelGGL(gs::k_expand_count<false>, dim3(count_grid), dim3(gs::EXP_CHUNK), 0, st, eo);
-            r->launches++;
-            if (cursor_kernel) {
-                hipLaunchKernelGGL(gs::k_pairs_cursors, dim3(eo.sb_bound), dim3(gs::EXP_SB), 0, st, eo);
-                r->launches++;
-            }
-            GS_HIP(hipGetLastError());
-            if (round <= 1u) mark(ST_TSORT);
-
-            // ---- stable sort on the tile id alone (pairs are generated in depth order by its first pass) ----
-            tside = 0;
-            const gs::SortCount tc{capacity, &state->pairs};
-            // Which tile sort (gs_renderer::tile_msd).  MSD-first needs u16 tile ids with more than 10 bits; its buckets are
-            // 2^(bits - 10) consecutive tiles, so what decides is the pair count: up to an average of a quarter of the register
-            // path's capacity per bucket it is tried, and a frame that reports a bucket beyond the capacity (FrameResult::
-            // tile_bucket_max, one frame late) sends the renderer back to the LSD passes until the pair count has dropped by
-            // a quarter below the count that failed.
-            bool tile_msd = false;
-            if (!wide && tile_bits > (uint32_t)gs::MSD_TOP_BITS && capacity != 0u && round == 0u) {
-                static const int tmsd_env = std::getenv("GS3D_TILE_MSD") ? std::atoi(std::getenv("GS3D_TILE_MSD")) : -1;
-                const int pinned = r->tile_msd_req >= 0 ? r->tile_msd_req : tmsd_env;
-                const int newer = hist_gen[0] > hist_gen[1] ? 0 : 1;
-                // pairs this frame is expected to hold: the newest report of this shape, else what sized the buffers
-                const uint64_t d_est = !sizing && hist_gen[newer] && r->done_shape[newer] == r->shape_epoch ? hist_d[newer]
-                                                                                                             : (uint64_t)capacity * 4u / 5u;
-                if (!sizing && hist_gen[newer] && r->done_shape[newer] == r->shape_epoch && hist_tmax[newer] > gs::BKT_CAP_SMALL)
-                    r->tile_msd_fail_d = d_est ? d_est : 1u;
-                if (sizing) r->tile_msd_fail_d = 0;
-                // Measured at 1 M (gpurun_out/r05c/kt_1m.txt): the 1020 buckets of ~2 500 pairs cost the bucket kernel 22 us (one
-                // 1024-thread workgroup with 157 KB of LDS per bucket: four rounds of workgroups whose fixed costs dominate) and
-                // the 10-bit first pass 6 us more than the 7-bit one — 60 us against the LSD sort's 55.  So the renderer does
-                // not choose it by itself (GS3D_TILE_MSD_AUTO=1 lets it); pinned, it is exact (tests/test_gpu_msd_sort.py).
-                static const bool tile_auto = std::getenv("GS3D_TILE_MSD_AUTO") && std::getenv("GS3D_TILE_MSD_AUTO")[0] == '1';
-                if (pinned >= 0)
-                    tile_msd = pinned != 0;
-                else
-                    tile_msd = tile_auto && d_est <= (uint64_t)gs::BKT_CAP_SMALL * 256u &&
-                               (r->tile_msd_fail_d == 0 || d_est < r->tile_msd_fail_d - r->tile_msd_fail_d / 4u);
-            }
-            r->tile_msd = tile_msd;
-            if (tile_msd) {
-                t_bucket_max = nullptr;
-                if (tile_bits > (uint32_t)gs::MSD_TOP_BITS + 6u) return fail(GS_ERR_INVALID_ARGUMENT, tile_bits, 0, 0, "tile id bits");
-                GS_TRY((run_tile_msd_items<gs::SortCfg<uint16_t>::ITEMS>(r, st, eo, tc, tile_bits, num_tiles, zero, &state->tile_bucket_max,
-                                                                              tpasses)));
-                tside = 0;
-            } else {
-                // (a frame whose tile sort is LSD reports no bucket size: the next result must not carry a stale one)
-                if (r->state_tile_bmax_dirty) GS_HIP(hipMemsetAsync(&state->tile_bucket_max, 0, sizeof(uint32_t), st));
-                void *k2[2] = {r->tkeys[0].ptr, r->tkeys[1].ptr};
-                void *v2[2] = {r->tvals[0].ptr, r->tvals[1].ptr};
-                const gs::ExpandIO *src = &eo;
-                if (wide)
-                    GS_TRY((run_sort_rb<uint32_t, gs::RADIX_BITS>(r->dev, k2, v2, r->ghist, r->digit_totals, tc, tile_bits, nullptr,
-                                                                  st, tside, tpasses, r->launches, src)));
-                else
-                    GS_TRY((run_sort_rb<uint16_t, gs::RADIX_BITS>(r->dev, k2, v2, r->ghist, r->digit_totals, tc, tile_bits, nullptr,
-                                                                  st, tside, tpasses, r->launches, src)));
-            }
-            r->state_tile_bmax_dirty = tile_msd;
-            if (round <= 1u) mark(ST_RANGES);
-            // Tile ranges, three ways (the MSD-first tile sort has written them already: k_bucket_sort).  (1) One pass over the sorted keys (k_tile_ranges).  (2) A 32-ary search per tile
-            // (k_tile_ranges_search) once reading every key again costs more than a few dependent probes per tile: from
-            // a pair capacity of 8 M (GS3D_RANGES_SEARCH=0/1 forces).  (3) The same search run by the blend workgroups
-            // themselves (blend_tile_range_wg): no launch in front of the blend, but a workgroup that waits for its
-            // probes is occupancy the VALU-bound blend misses — same-box A/B (gpurun_out/r04l/ab.log): blend +3.5 us at
-            // 1 M and 10 M, +10 us at 4K, +12 us at 50 M against 6.8 / 10.5 / 35 / 19 us of range kernel saved: frames
-            // +1.5 % at 1 M, +-0 at 10 M, -0.5 % at 50 M, -2.3 % at 4K.  It is taken where it pays: images of more than
-            // 16384 tiles, where neither stand-alone kernel is cheap (GS3D_RANGES_IN_BLEND=0/1 forces).
-            static const int in_blend_env = std::getenv("GS3D_RANGES_IN_BLEND") ? std::atoi(std::getenv("GS3D_RANGES_IN_BLEND")) : -1;
-            // (a two-round frame: always — the range array is cleared once per frame, and a launch per round is saved)
-            const bool ranges_in_blend = round != 0u || (in_blend_env >= 0 ? in_blend_env != 0 : num_tiles > 16384u);
-            static const int ranges_env = std::getenv("GS3D_RANGES_SEARCH") ? std::atoi(std::getenv("GS3D_RANGES_SEARCH")) : -1;
-            const bool ranges_search = ranges_env >= 0 ? ranges_env != 0 : capacity >= (8u << 20);
-            if (tile_msd) {
-                // nothing to do
-            } else if (capacity && ranges_in_blend) {
-                tile_keys.keys = r->tkeys[tside].ptr;
-                tile_keys.count_dev = &state->pairs;
-                tile_keys.count_bound = capacity;
-                tile_keys.wide = wide ? 1u : 0u;
-            } else if (capacity && ranges_search) {
-                if (wide)
-                    hipLaunchKernelGGL(gs::k_tile_ranges_search<uint32_t>, dim3((num_tiles + 3u) / 4u), dim3(256), 0, st,
-                                       (const uint32_t *)r->tkeys[tside].ptr, tc, zero, num_tiles);
-                else
-                    hipLaunchKernelGGL(gs::k_tile_ranges_search<uint16_t>, dim3((num_tiles + 3u) / 4u), dim3(256), 0, st,
-                                       (const uint16_t *)r->tkeys[tside].ptr, tc, zero, num_tiles);
-                GS_HIP(hipGetLastError());
-                r->launches++;
-            } else if (capacity) {
-                if (wide)
-                    hipLaunchKernelGGL(gs::k_tile_ranges<uint32_t>, dim3((uint32_t)(((uint64_t)capacity + 1023) / 1024)), dim3(256), 0, st,
-                                       (const uint32_t *)r->tkeys[tside].ptr, tc, zero);
-                else
-                    hipLaunchKernelGGL(gs::k_tile_ranges<uint16_t>, dim3((uint32_t)(((uint64_t)capacity + 2047) / 2048)), dim3(256), 0, st,
-                                       (const uint16_t *)r->tkeys[tside].ptr, tc, zero);
-                GS_HIP(hipGetLastError());
-                r->launches++;
-            }
-            r->tsorted_side = tside;          // (launch_blend reads the pairs of THIS round: round 1's blend runs before the frame ends)
-            return GS_OK;
-        };
-        if (!capacity) two_round = false;
-        r->two_round = two_round;
-        r->round1 = round_k;
-        if (!two_round) {
-            GS_TRY(pairs_round(0u, (const uint32_t *)r->dvals[dside].ptr, &state->visible, 0xffffffffu, esb));
-        } else {
-            tile_keys.done = done_bits;
-            tile_keys.open = open_bits;
-            if (partition)
-                GS_TRY(pairs_round(1u, (const uint32_t *)r->dvals[dside].ptr, &state->round1_visible, 0xffffffffu, esb));
-            else
-                GS_TRY(pairs_round(1u, (const uint32_t *)r->dvals[dside].ptr, &state->visible, round_k, esb));
-            mark(ST_BLEND);
-            GS_TRY(launch_blend(1u));
-            {
-                if (!partition) GS_TRY(dev_reserve(r->order_r2, (nn + 1024) * 4));      // (its largest size at once; padded like the sorts' values)
-                gs::Round2IO ro;
-                ro.order = (const uint32_t *)r->dvals[dside].ptr + round_k;
-                ro.rect = (const uint2 *)r->rect.ptr;
-                ro.done = done_bits;
-                ro.open = open_bits;
-                ro.order_out = (uint32_t *)r->order_r2.ptr;
-                ro.state = state;
-                ro.first = round_k;
-                ro.groups = (n - round_k + gs::R2_GROUP - 1u) / gs::R2_GROUP;
-                ro.tiles_x = fc.tiles_x;
-                ro.num_tiles = num_tiles;
-                // (per-slot arrays cover whole chunks: nslots; a list frame's live in list space, bounded by the same)
-                ro.slots = (uint32_t)nslots;
-                GS_TRY(dev_reserve(r->keep_bits, nslots / 8 + 64));
-                ro.keep_bits = (uint32_t *)r->keep_bits.ptr;
-                const uint32_t bits_grid = (uint32_t)((nslots + 256u * gs::R2_SLOT_ITEMS - 1u) / (256u * gs::R2_SLOT_ITEMS));
-                {
-                    typedef void (*bits_fn)(gs::Round2IO);
-                    static const bits_fn tbl[2][2] = {{gs::k_round2_slot_bits<false, false>, gs::k_round2_slot_bits<false, true>},
-                                                      {gs::k_round2_slot_bits<true, false>, gs::k_round2_slot_bits<true, true>}};
-                    GS_TRY(dev_reserve(r->box_table, ((size_t)num_tiles + 8) * 2));
-                    ro.box_table = (const uint16_t *)r->box_table.ptr;
-                    hipLaunchKernelGGL(gs::k_round2_gate, dim3(1), dim3(256), 0, st, ro, band_tiles, n,
-                                       r->list_mode ? (const uint32_t *)&state->list_slots : (const uint32_t *)nullptr);
-                    hipLaunchKernelGGL(gs::k_round2_box_table, dim3((num_tiles + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)done_bits,
-                                       (uint16_t *)r->box_table.ptr, fc.tiles_x, fc.tiles_y, (const gs::FrameState *)state);
-                    r->launches += 2;
-                    const bool lds = num_tiles <= gs::R2_LDS_TILES;
-                    const size_t lds_bytes = lds ? ((size_t)num_tiles + 7) / 8 * 16 : 0;
-                    const uint32_t persistent = bits_grid < 1024u ? bits_grid : 1024u;      // (4 / 2 workgroups per CU at 1080p / 4K)
-                    hipLaunchKernelGGL(tbl[fc.rect32 ? 1 : 0][lds ? 1 : 0], dim3(persistent), dim3(256), lds_bytes, st, ro);
-                }
-                GS_HIP(hipGetLastError());
-                r->launches++;
-                if (partition) {
-                    // the depth sort of what is left: keys behind the threshold whose slot bit is set
-                    gs::CompactPred pred2;
-                    pred2.tau_dev = &state->depth_tau;
-                    pred2.keep_bits = (const uint32_t *)r->keep_bits.ptr;
-                    pred2.side = 1u;
-                    GS_TRY(depth_sort(pred2, &state->round2_visible, &state->round2_dense));
-                } else {
-                    GS_TRY(dev_reserve(r->r2_scan, ((size_t)nn / gs::R2_GROUP + 1) * (2 * 4 + 32 * 8) + 64));      // (its largest size: never regrown under frames in flight)
-                    ro.masks = (unsigned long long *)r->r2_scan.ptr;
-                    ro.counts = (uint32_t *)(ro.masks + (size_t)ro.groups * 32);
-                    ro.offsets = ro.counts + ro.groups;
-                    hipLaunchKernelGGL(gs::k_round2_count, dim3(ro.groups), dim3(256), 0, st, ro);
-                    gs::ScanJob js{ro.counts, ro.offsets, &state->round2_visible, ro.groups, nullptr};
-                    hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, js, js);
-                    hipLaunchKernelGGL(gs::k_round2_write, dim3(ro.groups), dim3(256), 0, st, ro);
-                    r->launches += 3;
-                }
-                GS_HIP(hipGetLastError());
-            }
-            GS_TRY(pairs_round(2u, partition ? (const uint32_t *)r->dvals[dside].ptr : (const uint32_t *)r->order_r2.ptr, &state->round2_visible,
-                               0xffffffffu, esb2));
-        }
-        r->sort_passes = dpasses + tpasses;
-        r->dsorted_side = dside;
-        r->tsorted_side = tside;
+        GS_TRY(stage_preprocess(F));
+        // ... and what depends on the size of the pair buffers (the sizing pass may just have set it)
+        gsp::plan_pairs(F.hist, nums, r->pair_capacity, F.requests(), switches(), k_policy_params, r->sort_fb, r->rounds_fb, F.plan);
+        F.marks.mark(ST_DSORT);
+        GS_TRY(stage_sort_and_rounds(F));
     }
-    if (!r->two_round) mark(ST_BLEND);
-    GS_TRY(launch_blend(r->two_round ? 2u : 0u));
-    mark(ST_FRAME);
-    if (timing) {
+    if (!r->two_round) F.marks.mark(ST_BLEND);
+    GS_TRY(stage_blend(F, r->two_round ? 2u : 0u));
+    F.marks.mark(ST_FRAME);
+    if (F.marks.timing) {
         (void)hipEventRecord(r->ev[ST_COUNT], st);
         r->ev_pending = true;
     }
