@@ -58,6 +58,13 @@ pub const GS_KERNEL_TEST_MODEL_TRANSFORM: u32 = 3;
 pub const GS_KERNEL_UNPACK_SOA: u32 = 4;
 pub const GS_KERNEL_COUNT_: u32 = 5;
 
+// enum gs_select_op (passed as u32)
+pub const GS_SEL_SET: u32 = 0;
+pub const GS_SEL_OR: u32 = 1;
+pub const GS_SEL_AND: u32 = 2;
+pub const GS_SEL_ANDNOT: u32 = 3;
+pub const GS_SEL_XOR: u32 = 4;
+
 #[repr(C)] pub struct gs_device { _private: [u8; 0] }
 #[repr(C)] pub struct gs_stream { _private: [u8; 0] }
 #[repr(C)] pub struct gs_buffer { _private: [u8; 0] }
@@ -65,6 +72,7 @@ pub const GS_KERNEL_COUNT_: u32 = 5;
 #[repr(C)] pub struct gs_gaussians_buffer { _private: [u8; 0] }
 #[repr(C)] pub struct gs_bundle { _private: [u8; 0] }
 #[repr(C)] pub struct gs_renderer { _private: [u8; 0] }
+#[repr(C)] pub struct gs_selection { _private: [u8; 0] }
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -265,6 +273,15 @@ pub struct gs_sort_info {
     pub partitioned: u32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_frame_selection {
+    pub hide: *const gs_selection,
+    pub tint: *const gs_selection,
+    pub tint_rgba: [f32; 4],
+    pub reserved: [u32; 2],
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -381,6 +398,20 @@ extern "C" {
     pub fn gs_renderer_download_projected(r: *mut gs_renderer, proj_out: *mut gs_projected, tiles_touched_out: *mut u32, n: usize) -> gs_status;
     pub fn gs_renderer_download_sorted(r: *mut gs_renderer, keys_out: *mut u64, idx_out: *mut u32, capacity: u64, pairs_out: *mut u64) -> gs_status;
     pub fn gs_renderer_download_ranges(r: *mut gs_renderer, ranges_out: *mut u32, num_tiles: usize) -> gs_status;
+    pub fn gs_selection_create(dev: *mut gs_device, n: usize, out: *mut *mut gs_selection) -> gs_status;
+    pub fn gs_selection_destroy(sel: *mut gs_selection);
+    pub fn gs_selection_len(sel: *const gs_selection) -> usize;
+    pub fn gs_selection_clear(sel: *mut gs_selection, s: *mut gs_stream) -> gs_status;
+    pub fn gs_selection_fill(sel: *mut gs_selection, s: *mut gs_stream) -> gs_status;
+    pub fn gs_selection_invert(sel: *mut gs_selection, s: *mut gs_stream) -> gs_status;
+    pub fn gs_selection_combine(dst: *mut gs_selection, s: *mut gs_stream, op: u32, src: *const gs_selection) -> gs_status;
+    pub fn gs_selection_upload(sel: *mut gs_selection, s: *mut gs_stream, words: *const u32, nwords: usize) -> gs_status;
+    pub fn gs_selection_download(sel: *mut gs_selection, s: *mut gs_stream, words: *mut u32, nwords: usize) -> gs_status;
+    pub fn gs_selection_count(sel: *mut gs_selection, s: *mut gs_stream, out: *mut u64) -> gs_status;
+    pub fn gs_select_sphere(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, model_transform: *const gs_model_transform_pod, center: *const f32, radius: f32, op: u32) -> gs_status;
+    pub fn gs_select_box(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, model_transform: *const gs_model_transform_pod, world_to_box: *const f32, op: u32) -> gs_status;
+    pub fn gs_renderer_select_visible(r: *mut gs_renderer, s: *mut gs_stream, sel: *mut gs_selection, x0: f32, y0: f32, x1: f32, y1: f32, mask_plane_device: *const u8, op: u32) -> gs_status;
+    pub fn gs_render_frame_sel(r: *mut gs_renderer, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, gaussian_transform: *const gs_gaussian_transform_pod, model_transform: *const gs_model_transform_pod, camera: *const gs_camera, band_ty0: u32, band_ty1: u32, rgba_out_device: *mut f32, aux: *const gs_aux_targets, fs: *const gs_frame_selection) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

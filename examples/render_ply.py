@@ -25,6 +25,8 @@ def main():
     ap.add_argument("--pod", default="ShSingle/Cov3dRotScale")
     ap.add_argument("--depth", help="write the expected depth (depth / alpha) as a 16-bit PGM, near = dark")
     ap.add_argument("--pick", help="X,Y: print the index and record of the Gaussian picked at that pixel (median contributor)")
+    ap.add_argument("--crop", nargs=6, type=float, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="hide what lies outside this axis-aligned box (a device selection: the data is left alone)")
     args = ap.parse_args()
     sh, cov = args.pod.split("/")
     pod = getattr(gs, "GaussianPodWith%s%sConfigs" % (sh, cov))
@@ -45,9 +47,15 @@ def main():
     aux = args.depth or args.pick
     depth = gs.Buffer(dev, size=W * H * 4) if aux else None
     pick = gs.Buffer(dev, size=W * H * 4) if aux else None
+    hide = None
+    if args.crop:
+        hide = gs.Selection(dev, len(buf))
+        hide.select_box(stream, buf, gs.model_transform_pod(), gs.box_from_bounds(args.crop[:3], args.crop[3:]))
+        hide.invert(stream)
+        print("crop: %d of %d Gaussians hidden" % (hide.count(stream), len(buf)))
     r.render(stream, buf, gs.gaussian_transform_pod(1.0, mode, 3, False, 3.0), gs.model_transform_pod(), cam,
              img.device_ptr(), depth_device_ptr=depth.device_ptr() if aux else None,
-             pick_device_ptr=pick.device_ptr() if aux else None)
+             pick_device_ptr=pick.device_ptr() if aux else None, hide=hide)
     rgba = img.download(stream, np.float32).reshape(H, W, 4)
     st = r.stats()
     rgb8 = (np.clip(rgba[..., :3], 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)

@@ -331,6 +331,35 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     gs_gaussians_buffer *h_ = nullptr;
 };
 
+// ---- selections (gs3d.h gs_selection; no reference item) ------------------------------
+// One bit per Gaussian of a buffer, in the caller's index order, on the device.  Every call but download / count only
+// enqueues on the stream.
+class Selection {
+  public:
+    Selection(Device &d, size_t n) { check(gs_selection_create(d.raw(), n, &h_)); }
+    Selection(Selection &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Selection(const Selection &) = delete;
+    ~Selection() { gs_selection_destroy(h_); }
+    size_t len() const { return gs_selection_len(h_); }
+    size_t words() const { return (len() + 31) / 32; }
+    void clear(Stream &s) { check(gs_selection_clear(h_, s.raw())); }
+    void fill(Stream &s) { check(gs_selection_fill(h_, s.raw())); }
+    void invert(Stream &s) { check(gs_selection_invert(h_, s.raw())); }
+    void combine(Stream &s, gs_select_op op, const Selection &src) { check(gs_selection_combine(h_, s.raw(), op, src.h_)); }
+    void upload(Stream &s, const std::vector<uint32_t> &w) { check(gs_selection_upload(h_, s.raw(), w.data(), w.size())); }
+    std::vector<uint32_t> download(Stream &s) const { std::vector<uint32_t> w(words()); check(gs_selection_download(h_, s.raw(), w.data(), w.size())); return w; }
+    uint64_t count(Stream &s) const { uint64_t c = 0; check(gs_selection_count(h_, s.raw(), &c)); return c; }
+    template <class G>
+    void select_sphere(Stream &s, GaussiansBuffer<G> &g, const gs_model_transform_pod &mt, const float center[3], float radius,
+                       gs_select_op op = GS_SEL_SET) { check(gs_select_sphere(h_, s.raw(), g.raw(), &mt, center, radius, op)); }
+    template <class G>
+    void select_box(Stream &s, GaussiansBuffer<G> &g, const gs_model_transform_pod &mt, const float world_to_box[12],
+                    gs_select_op op = GS_SEL_SET) { check(gs_select_box(h_, s.raw(), g.raw(), &mt, world_to_box, op)); }
+    gs_selection *raw() const { return h_; }
+  private:
+    gs_selection *h_ = nullptr;
+};
+
 // GaussianTransformPod helpers (src/buffer/gaussian_transform.rs)
 inline std::optional<gs_gaussian_transform_pod> gaussian_transform_pod(float size, gs_display_mode mode, uint8_t sh_deg, bool no_sh0, float max_std_dev) {
     gs_gaussian_transform_pod p;
@@ -464,6 +493,24 @@ class Renderer {
     void render(Stream &s, GaussiansBuffer<G> &g, const gs_gaussian_transform_pod &gt, const gs_model_transform_pod &mt,
                 const gs_camera &cam, float *rgba_device, uint32_t band_ty0, uint32_t band_ty1, const gs_aux_targets *aux) {
         check(gs_render_frame_aux(h_, s.raw(), g.raw(), &gt, &mt, &cam, band_ty0, band_ty1, rgba_device, aux));
+    }
+    // ... and with the Gaussians of `hide` culled and tint_rgba mixed into the colour of those of `tint` (gs_render_frame_sel;
+    // either may be nullptr, both nullptr: the overload above)
+    template <class G>
+    void render(Stream &s, GaussiansBuffer<G> &g, const gs_gaussian_transform_pod &gt, const gs_model_transform_pod &mt,
+                const gs_camera &cam, float *rgba_device, uint32_t band_ty0, uint32_t band_ty1, const gs_aux_targets *aux,
+                const Selection *hide, const Selection *tint = nullptr, const float tint_rgba[4] = nullptr) {
+        gs_frame_selection fs{};
+        fs.hide = hide ? hide->raw() : nullptr;
+        fs.tint = tint ? tint->raw() : nullptr;
+        for (int c = 0; c < 4; c++) fs.tint_rgba[c] = tint_rgba ? tint_rgba[c] : 0.0f;
+        check(gs_render_frame_sel(h_, s.raw(), g.raw(), &gt, &mt, &cam, band_ty0, band_ty1, rgba_device, aux, &fs));
+    }
+    // the Gaussians the last frame kept whose mean lies in [x0, x1) x [y0, y1) (and on a nonzero byte of the H x W device
+    // plane `mask`, if given): sel = sel op that set.  Enqueued behind the frame; does not block.
+    void select_visible(Stream &s, Selection &sel, float x0, float y0, float x1, float y1, const uint8_t *mask_device = nullptr,
+                        gs_select_op op = GS_SEL_SET) {
+        check(gs_renderer_select_visible(h_, s.raw(), sel.raw(), x0, y0, x1, y1, mask_device, op));
     }
     // render() only enqueues; wait_frame() blocks until the frame is complete and throws
     // PairCapacityError when it exceeded the pair capacity (the next frame has larger buffers)

@@ -16,7 +16,7 @@ OUT = os.path.join(ROOT, "bindings", "rust", "gs3d_sys.rs")
 SCALARS = {"int32_t": "i32", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "uint16_t": "u16",
            "uint8_t": "u8", "int8_t": "i8", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
            "void": "c_void", "gs_status": "gs_status", "int": "i32"}
-ENUMS = {"gs_sh_config", "gs_cov3d_config", "gs_display_mode", "gs_kernel_id"}
+ENUMS = {"gs_sh_config", "gs_cov3d_config", "gs_display_mode", "gs_kernel_id", "gs_select_op"}
 
 
 def strip_comments(text):

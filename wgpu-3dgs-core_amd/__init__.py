@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import AuxTargets, Camera, FrameResult, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
+from ._capi import AuxTargets, Camera, FrameResult, FrameSelection, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
 
 _L = _capi.load()
 
@@ -1149,6 +1149,140 @@ PICK_NONE = 0xFFFFFFFF     # GS_PICK_NONE: a pixel of the pick plane whose trans
 STAGE_NAMES = ["repack", "preprocess", "scan", "depth_sort", "expand", "tile_sort", "ranges", "blend", "frame"]
 
 
+SEL_SET, SEL_OR, SEL_AND, SEL_ANDNOT, SEL_XOR = 0, 1, 2, 3, 4      # gs_select_op: dst = dst op src
+_SELECT_OPS = {"set": SEL_SET, "or": SEL_OR, "and": SEL_AND, "andnot": SEL_ANDNOT, "xor": SEL_XOR}
+
+
+def select_op(op):
+    """gs_select_op from its number or name ('set', 'or', 'and', 'andnot', 'xor'); ValueError for anything else."""
+    if isinstance(op, str):
+        if op.lower() not in _SELECT_OPS:
+            raise ValueError("unknown select op %r (one of %s)" % (op, ", ".join(_SELECT_OPS)))
+        return _SELECT_OPS[op.lower()]
+    if isinstance(op, (int, np.integer)) and not isinstance(op, bool) and SEL_SET <= int(op) <= SEL_XOR:
+        return int(op)
+    raise ValueError("unknown select op %r" % (op,))
+
+
+def selection_words(n):
+    """words of an n-bit selection: ceil(n / 32)"""
+    if int(n) < 0:
+        raise ValueError("a selection cannot have %d bits" % n)
+    return (int(n) + 31) // 32
+
+
+def frame_selection(hide=None, tint=None, tint_rgba=None):
+    """The gs_frame_selection of Renderer.render's keywords, or None for the plain frame.  Checked here, before any
+    device call: hide / tint must be Selections, tint_rgba goes with tint (four numbers: a finite colour, 0 <= a <= 1)."""
+    for name, sel in (("hide", hide), ("tint", tint)):
+        if sel is not None and not isinstance(sel, Selection):
+            raise TypeError("%s must be a Selection or None, not %s" % (name, type(sel).__name__))
+    if tint is None:
+        if tint_rgba is not None:
+            raise ValueError("tint_rgba without a tint selection")
+        if hide is None:
+            return None
+        rgba = (0.0, 0.0, 0.0, 0.0)
+    else:
+        if tint_rgba is None:
+            raise ValueError("a tint selection needs tint_rgba")
+        rgba = tuple(float(v) for v in tint_rgba)
+        if len(rgba) != 4:
+            raise ValueError("tint_rgba takes four numbers (r, g, b, a), got %d" % len(rgba))
+        if not all(np.isfinite(v) for v in rgba[:3]) or not 0.0 <= rgba[3] <= 1.0:
+            raise ValueError("tint_rgba: the colour must be finite and the alpha in [0, 1]")
+    fs = FrameSelection()
+    fs.hide = hide._h if hide is not None else None
+    fs.tint = tint._h if tint is not None else None
+    fs.tint_rgba[:] = rgba
+    fs._keep = (hide, tint)       # the handles stay alive as long as the struct
+    return fs
+
+
+class Selection:
+    """gs_selection: one bit per Gaussian of a buffer, in the caller's index order, on the device.
+    Every call but download / count only enqueues on the stream."""
+
+    def __init__(self, device, n):
+        selection_words(n)
+        h = C.c_void_p()
+        _check(_L.gs_selection_create(device._h, int(n), C.byref(h)))
+        self._h, self.device = h, device
+
+    def __len__(self):
+        return _L.gs_selection_len(self._h)
+
+    def clear(self, stream):
+        _check(_L.gs_selection_clear(self._h, stream._h))
+
+    def fill(self, stream):
+        _check(_L.gs_selection_fill(self._h, stream._h))
+
+    def invert(self, stream):
+        _check(_L.gs_selection_invert(self._h, stream._h))
+
+    def combine(self, stream, op, src):
+        """self = self op src"""
+        if not isinstance(src, Selection):
+            raise TypeError("src must be a Selection")
+        _check(_L.gs_selection_combine(self._h, stream._h, select_op(op), src._h))
+
+    def count(self, stream):
+        out = C.c_uint64()
+        _check(_L.gs_selection_count(self._h, stream._h, C.byref(out)))
+        return out.value
+
+    def upload(self, stream, bits):
+        """bits: a bool array of len(self), or the ceil(n / 32) packed uint32 words"""
+        a = np.asarray(bits)
+        if a.dtype == np.bool_:
+            if a.shape != (len(self),):
+                raise ValueError("%d flags for a selection of %d bits" % (a.size, len(self)))
+            a = np.packbits(a, bitorder="little")
+            a = np.concatenate([a, np.zeros(-len(a) % 4, np.uint8)]).view(np.uint32)
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        _check(_L.gs_selection_upload(self._h, stream._h, _ptr(a), len(a)))
+
+    def download_words(self, stream):
+        w = np.zeros(selection_words(len(self)), dtype=np.uint32)
+        _check(_L.gs_selection_download(self._h, stream._h, _ptr(w), len(w)))
+        return w
+
+    def download(self, stream):
+        """the selection as a bool array of len(self) (blocking)"""
+        w = self.download_words(stream)
+        return np.unpackbits(w.view(np.uint8), bitorder="little")[:len(self)].astype(np.bool_)
+
+    def select_sphere(self, stream, gaussians, model_transform, center, radius, op=SEL_SET):
+        """self = self op {Gaussians whose world position lies within `radius` of `center`} (gs_select_sphere)"""
+        c = (C.c_float * 3)(*[float(v) for v in center])
+        _check(_L.gs_select_sphere(self._h, stream._h, gaussians._h, C.byref(model_transform), c, float(radius),
+                                   select_op(op)))
+
+    def select_box(self, stream, gaussians, model_transform, world_to_box, op=SEL_SET):
+        """self = self op {Gaussians inside the unit box of `world_to_box`, a 3 x 4 matrix given as 12 numbers in
+        column-major order} (gs_select_box)"""
+        b = np.ascontiguousarray(world_to_box, dtype=np.float32).reshape(-1)
+        if b.size != 12:
+            raise ValueError("world_to_box takes 12 numbers (3 x 4, column-major)")
+        _check(_L.gs_select_box(self._h, stream._h, gaussians._h, C.byref(model_transform), _ptr(b), select_op(op)))
+
+    def destroy(self):
+        if self._h:
+            _L.gs_selection_destroy(self._h)
+            self._h = None
+
+
+def box_from_bounds(lo, hi):
+    """world_to_box (12 numbers, column-major 3 x 4) of the axis-aligned box [lo, hi]"""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    half, mid = 0.5 * (hi - lo), 0.5 * (hi + lo)
+    b = np.zeros((4, 3))
+    b[0, 0], b[1, 1], b[2, 2] = 1.0 / half
+    b[3] = -mid / half
+    return b.reshape(-1).astype(np.float32)
+
+
 class Renderer:
     """One render context (scratch buffers + stats) on a device: gs_render_frame."""
 
@@ -1194,21 +1328,29 @@ class Renderer:
 
     def render(self, stream, gaussians, gaussian_transform, model_transform, camera,
                rgba_device_ptr, band=None, check=True, depth_device_ptr=None, pick_device_ptr=None,
-               pick_threshold=0.5):
+               pick_threshold=0.5, hide=None, tint=None, tint_rgba=None):
         """gs_render_frame.  check=True (the validated use: tests, one-off renders) waits for the
         frame and, if it exceeded the pair capacity sized from earlier frames, renders it again
         with the grown buffers; check=False only enqueues (the pipelined use: a viewer's frame
         loop, bench.py) — call wait_frame() / synchronise the stream before reading the image.
         depth_device_ptr / pick_device_ptr: H x W f32 / u32 device planes that the same frame fills
         (gs_render_frame_aux): the depth sum (expected depth = depth / alpha) and the
-        caller's index of the Gaussian that takes the pixel's alpha to pick_threshold (PICK_NONE)."""
+        caller's index of the Gaussian that takes the pixel's alpha to pick_threshold (PICK_NONE).
+        hide / tint: Selections of the buffer's length (gs_render_frame_sel): the frame culls the
+        Gaussians of `hide` and mixes tint_rgba = (r, g, b, a) into the colour of those of `tint`."""
         b0, b1 = band if band is not None else (0, 0xFFFFFFFF)
+        fs = frame_selection(hide, tint, tint_rgba)
         aux = None
         if depth_device_ptr is not None or pick_device_ptr is not None:
             aux = AuxTargets(C.c_void_p(depth_device_ptr or 0), C.c_void_p(pick_device_ptr or 0),
                              float(pick_threshold), 0)
         for attempt in range(4):
-            if aux is None:
+            if fs is not None:
+                _check(_L.gs_render_frame_sel(self._h, stream._h, gaussians._h, C.byref(gaussian_transform),
+                                              C.byref(model_transform), C.byref(camera), b0, b1,
+                                              C.c_void_p(rgba_device_ptr), C.byref(aux) if aux is not None else None,
+                                              C.byref(fs)))
+            elif aux is None:
                 _check(_L.gs_render_frame(self._h, stream._h, gaussians._h, C.byref(gaussian_transform),
                                           C.byref(model_transform), C.byref(camera), b0, b1,
                                           C.c_void_p(rgba_device_ptr)))
@@ -1229,6 +1371,15 @@ class Renderer:
         fr = FrameResult()
         _check(_L.gs_renderer_wait_frame(self._h, C.byref(fr)))
         return fr
+
+    def select_visible(self, stream, selection, x0, y0, x1, y1, mask_device_ptr=None, op=SEL_SET):
+        """gs_renderer_select_visible: selection = selection op {Gaussians the LAST FRAME kept whose mean lies in
+        [x0, x1) x [y0, y1) and, with an H x W byte plane on the device, on a nonzero byte of it}.  Enqueued behind that
+        frame; does not block."""
+        if not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection")
+        _check(_L.gs_renderer_select_visible(self._h, stream._h, selection._h, float(x0), float(y0), float(x1), float(y1),
+                                             C.c_void_p(mask_device_ptr or 0), select_op(op)))
 
     def download_projected(self, n):
         proj = np.zeros(n, dtype=PROJECTED_DTYPE)
@@ -1279,14 +1430,17 @@ class FrameRing:
         return len(self.renderers)
 
     def render(self, gaussians, gaussian_transform, model_transform, camera, rgba_device_ptr, band=None, check=False,
-               depth_device_ptr=None, pick_device_ptr=None, pick_threshold=0.5):
+               depth_device_ptr=None, pick_device_ptr=None, pick_threshold=0.5, hide=None, tint=None, tint_rgba=None):
         """enqueues one frame on the next lane; returns the lane's index (its stream: `streams[lane]`).  The
-        depth / pick planes as in Renderer.render: a lane writes them while later lanes run, so each lane needs its own."""
+        depth / pick planes as in Renderer.render: a lane writes them while later lanes run, so each lane needs its own.
+        hide / tint / tint_rgba as in Renderer.render; the selections must have been filled on a stream the lane's stream is
+        ordered behind (or be synchronised) before the frame is enqueued."""
         lane = self._next % len(self.renderers)
         self._next += 1
         self.renderers[lane].render(self.streams[lane], gaussians, gaussian_transform, model_transform, camera,
                                     rgba_device_ptr, band=band, check=check, depth_device_ptr=depth_device_ptr,
-                                    pick_device_ptr=pick_device_ptr, pick_threshold=pick_threshold)
+                                    pick_device_ptr=pick_device_ptr, pick_threshold=pick_threshold, hide=hide, tint=tint,
+                                    tint_rgba=tint_rgba)
         return lane
 
     def wait(self):

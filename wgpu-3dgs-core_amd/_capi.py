@@ -52,6 +52,11 @@ class AuxTargets(C.Structure):
     _fields_ = [("depth", vp), ("pick", vp), ("pick_threshold", f32), ("reserved", u32)]
 
 
+class FrameSelection(C.Structure):
+    """gs_frame_selection: the hide / tint selections of a frame (gs_render_frame_sel)"""
+    _fields_ = [("hide", vp), ("tint", vp), ("tint_rgba", f32 * 4), ("reserved", u32 * 2)]
+
+
 class SortInfo(C.Structure):
     _fields_ = [("depth_msd", u32), ("depth_bucket_max", u32), ("bucket_capacity", u32), ("tile_msd", u32),
                 ("tile_bucket_max", u32), ("tile_masks", u32), ("rounds", u32), ("round1", u32), ("tiles_done", u32), ("partitioned", u32)]
@@ -198,6 +203,20 @@ SIGNATURES = {
     "gs_renderer_download_projected": (i32, [vp, vp, vp, sz]),
     "gs_renderer_download_sorted": (i32, [vp, vp, vp, u64, vp]),
     "gs_renderer_download_ranges": (i32, [vp, vp, sz]),
+    "gs_selection_create": (i32, [vp, sz, vp]),
+    "gs_selection_destroy": (None, [vp]),
+    "gs_selection_len": (sz, [vp]),
+    "gs_selection_clear": (i32, [vp, vp]),
+    "gs_selection_fill": (i32, [vp, vp]),
+    "gs_selection_invert": (i32, [vp, vp]),
+    "gs_selection_combine": (i32, [vp, vp, i32, vp]),
+    "gs_selection_upload": (i32, [vp, vp, vp, sz]),
+    "gs_selection_download": (i32, [vp, vp, vp, sz]),
+    "gs_selection_count": (i32, [vp, vp, vp]),
+    "gs_select_sphere": (i32, [vp, vp, vp, vp, vp, f32, i32]),
+    "gs_select_box": (i32, [vp, vp, vp, vp, vp, i32]),
+    "gs_renderer_select_visible": (i32, [vp, vp, vp, f32, f32, f32, f32, vp, i32]),
+    "gs_render_frame_sel": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

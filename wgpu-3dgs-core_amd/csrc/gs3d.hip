@@ -22,6 +22,7 @@
 #include "gs_policy.h"
 #include "gs_bundle_kernels.h"
 #include "gs_render_kernels.h"
+#include "gs_select_kernels.h"
 #include "gs_pack_kernels.h"
 #include "_gen_kernel_lib_src.h"
 
@@ -651,6 +652,12 @@ extern "C" void gs_download_release(gs_download *d) {
 // GaussiansBuffer<G>
 // ------------------------------------------------------------------------------------------------
 
+// ids of buffers and generations of selections: unique in the process, never 0
+static uint64_t next_object_id() {
+    static std::atomic<uint64_t> next{0};
+    return ++next;
+}
+
 struct gs_gaussians_buffer {
     gs_buffer *buf;
     int sh, cov;
@@ -673,6 +680,10 @@ struct gs_gaussians_buffer {
     // (several renderers keeping frames in flight on one buffer) wait for this event before reading it.
     hipEvent_t mirror_ready = nullptr;
     hipStream_t mirror_stream = nullptr;
+    // what a renderer's slot-ordered selection masks were gathered through: this buffer (ids are never
+    // reused, addresses are) and this build of its mirror order
+    uint64_t uid = next_object_id();
+    uint64_t order_epoch = 0;
     void mark(size_t lo, size_t hi) {
         if (lo >= hi) return;
         partial_since_order += hi - lo;
@@ -1534,6 +1545,19 @@ static void dev_free(DevArray &a) {
     a.bytes = 0;
 }
 
+// Gaussian selection: n bits in caller index order.  `generation` changes with every call that may
+// modify the bits (next_object_id: unique across selections), which is how a renderer knows its slot-ordered copy is stale.
+struct gs_selection {
+    gs_device *dev;
+    size_t n, nwords;
+    uint32_t *words;            // device, nwords (at least one word is allocated)
+    DevArray scratch;           // a plane of the same size for the select ops that scatter their bits (select_visible)
+    DevArray counter;           // gs_selection_count's device total
+    uint64_t generation;
+    uint32_t tail_mask() const { return (n & 31u) ? (1u << (n & 31u)) - 1u : 0xffffffffu; }
+    uint32_t grid() const { return nwords < 256u * 1024u ? (uint32_t)((nwords + 255u) / 256u) + 1u : 1024u; }
+};
+
 // stage indices of gs_frame_stats.stage_ms
 enum { ST_REPACK = 0, ST_PRE, ST_SCAN, ST_DSORT, ST_EXPAND, ST_TSORT, ST_RANGES, ST_BLEND, ST_FRAME, ST_COUNT };
 
@@ -1593,6 +1617,17 @@ struct gs_renderer {
     bool rect32;      // the last frame's tile rects are packed (gs::rect_pack32)
     uint32_t launches;                    // kernel launches of the last frame (diagnostic)
     uint32_t *flags_target = nullptr;     // device word that receives every frame's flags (gs_renderer_set_frame_flags_target)
+    // selection frames: the hide / tint masks in mirror-slot order, the per-block "fully hidden" flags,
+    // and what each copy was gathered from (SlotMaskKey; generation 0 = nothing cached)
+    struct SlotMaskKey {
+        uint64_t generation = 0, buffer = 0, order_epoch = 0, n = 0;
+        bool operator==(const SlotMaskKey &o) const {
+            return generation == o.generation && buffer == o.buffer && order_epoch == o.order_epoch && n == o.n;
+        }
+    };
+    DevArray sel_slots[2], sel_block_hidden;      // [0] hide, [1] tint
+    SlotMaskKey sel_key[2];
+    uint32_t width = 0, height = 0;       // image size of the last frame (gs_renderer_select_visible)
     hipStream_t last_stream;
     bool have_frame;                      // last_stream is meaningful (the null stream is a valid stream)
     bool last_stream_gone = false;        // ... but has been destroyed since (gs_stream_destroy recorded done[gen & 1] on it)
@@ -1693,7 +1728,7 @@ extern "C" void gs_renderer_destroy(gs_renderer *r) {
     DevArray *arrs[] = {&r->recs, &r->depth, &r->rect, &r->sorted_rect, &r->exp_sums, &r->cursors, &r->chunk_tiles, &r->chunk_vis,
                         &r->state, &r->zero_region, &r->order_r2, &r->keep_bits, &r->r2_scan, &r->box_table, &r->scan_tmp, &r->block_list, &r->cull_status, &r->chunk_hist, &r->dkeys[0], &r->dkeys[1], &r->dvals[0],
                         &r->dvals[1], &r->tkeys[0], &r->tkeys[1], &r->tvals[0], &r->tvals[1], &r->ghist,
-                        &r->digit_totals, &r->bucket_starts};
+                        &r->digit_totals, &r->bucket_starts, &r->sel_slots[0], &r->sel_slots[1], &r->sel_block_hidden};
     for (DevArray *a : arrs) dev_free(*a);
     if (r->host_counters) (void)hipHostFree(r->host_counters);
     if (r->results) (void)hipHostFree(r->results);
@@ -1871,6 +1906,13 @@ static preprocess_fn k_tbl_preprocess_banded[2][2][4][3] = {
     {GS_CFG_TABLE_X(gs::k_preprocess_banded, false, false), GS_CFG_TABLE_X(gs::k_preprocess_banded, true, false)},
     {GS_CFG_TABLE_X(gs::k_preprocess_banded, false, true), GS_CFG_TABLE_X(gs::k_preprocess_banded, true, true)}};
 static block_bounds_fn k_tbl_block_bounds[4][3] = GS_CFG_TABLE(gs::k_block_bounds);
+// the instantiations of selection frames: the same tables with a SelIO behind the PreOut
+typedef void (*preprocess_sel_fn)(const uint4 *, uint32_t, gs::FrameConsts, gs::PreOut, gs::SelIO);
+static preprocess_sel_fn k_tbl_preprocess_sel[2][4][3] = {GS_CFG_TABLE_X(gs::k_preprocess, false, gs::SelIO),
+                                                          GS_CFG_TABLE_X(gs::k_preprocess, true, gs::SelIO)};
+static preprocess_sel_fn k_tbl_preprocess_banded_sel[2][2][4][3] = {
+    {GS_CFG_TABLE_X(gs::k_preprocess_banded, false, false, gs::SelIO), GS_CFG_TABLE_X(gs::k_preprocess_banded, true, false, gs::SelIO)},
+    {GS_CFG_TABLE_X(gs::k_preprocess_banded, false, true, gs::SelIO), GS_CFG_TABLE_X(gs::k_preprocess_banded, true, true, gs::SelIO)}};
 
 // frame constants from the uniforms
 static void make_frame_consts(const gs_gaussian_transform_pod *gt, const gs_model_transform_pod *mt,
@@ -2505,6 +2547,7 @@ static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
         const bool want_order = g->spatial && len > 1;
         if (whole || want_order != (g->order != nullptr)) {
             // whole-buffer (re)mirror: this is where the spatial order is (re)computed or dropped
+            g->order_epoch++;
             if (want_order) {
                 GS_TRY(build_spatial_order(g, st, len));
             } else {
@@ -2742,6 +2785,7 @@ struct Frame {
     gs_gaussians_buffer *g;
     const gs_aux_targets *aux;
     float *rgba;
+    const gs_frame_selection *fs;     // hide / tint selections (gs_render_frame_sel, checked there), or null: the plain frame
     StageMarks marks;
     gs::FrameConsts fc;
     FrameShape shape;
@@ -2757,6 +2801,7 @@ struct Frame {
     // slices of zero_region: tile ranges, the two rounds' super-chunk sums, the finished / open tile bits
     uint32_t *zero = nullptr, *esb = nullptr, *esb2 = nullptr, *done_bits = nullptr, *open_bits = nullptr;
     gs::TileKeys tile_keys{nullptr, nullptr, 0u, 0u, 0u, nullptr, nullptr};   // null keys: the blend reads its ranges from the range array
+    gs::SelIO sel{};                  // selection frames: what the preprocess kernels read (stage_selection)
     gsp::Requests requests() const {
         gsp::Requests q;
         q.depth_msd = r->depth_msd_req;
@@ -2912,8 +2957,12 @@ static gs_status stage_block_cull(Frame &F, gs::PreOut &po) {
         GS_HIP(hipMemsetAsync(r->cull_status.ptr, 0, (size_t)groups * 4, F.st));
     r->cull_last_gen = gen;
     r->cull_last_groups = groups;
-    hipLaunchKernelGGL(gs::k_block_cull, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds, nchunks, F.fc,
-                       (uint32_t *)r->block_list.ptr, F.state, (uint32_t *)r->cull_status.ptr, tag, groups);
+    if (F.sel.block_hidden)
+        hipLaunchKernelGGL(gs::k_block_cull<const uint32_t *>, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds, nchunks,
+                           F.fc, (uint32_t *)r->block_list.ptr, F.state, (uint32_t *)r->cull_status.ptr, tag, groups, F.sel.block_hidden);
+    else
+        hipLaunchKernelGGL(gs::k_block_cull<>, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds, nchunks, F.fc,
+                           (uint32_t *)r->block_list.ptr, F.state, (uint32_t *)r->cull_status.ptr, tag, groups);
     GS_HIP(hipGetLastError());
     r->launches++;
     po.block_list = (const uint32_t *)r->block_list.ptr;
@@ -2941,6 +2990,42 @@ static gs_status stage_sizing(Frame &F) {
     r->rounds_fb.full_pairs_v = 0;
     const uint64_t cap = gsp::capacity_for(d) > F.plan.want_capacity ? gsp::capacity_for(d) : F.plan.want_capacity;
     return reserve_pairs(r, cap, F.nums.wide);
+}
+
+// Selection frames: the renderer's mirror-slot-ordered copies of the hide / tint masks.  A copy is
+// gathered again (k_selection_to_slots, one launch) only when its selection was modified since (every mutating call gives
+// the selection a new generation) or it was gathered through another buffer or another build of the mirror order.
+static gs_status stage_selection(Frame &F) {
+    gs_renderer *r = F.r;
+    const gs_selection *sels[2] = {F.fs->hide, F.fs->tint};
+    const uint64_t *slots[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; k++) {
+        if (!sels[k]) continue;
+        gs_renderer::SlotMaskKey key;
+        key.generation = sels[k]->generation;
+        key.buffer = F.g->uid;
+        key.order_epoch = F.g->order_epoch;
+        key.n = F.n;
+        GS_TRY(dev_reserve(r->sel_slots[k], F.nslots / 8));
+        if (k == 0) GS_TRY(dev_reserve(r->sel_block_hidden, F.nc * 4));
+        if (!(key == r->sel_key[k])) {
+            r->sel_key[k] = gs_renderer::SlotMaskKey();
+            hipLaunchKernelGGL(gs::k_selection_to_slots, dim3(F.nchunks), dim3(gs::PP_THREADS), 0, F.st, (const uint32_t *)sels[k]->words,
+                               F.g->order ? (const uint32_t *)F.g->order->ptr : nullptr, F.n, (uint64_t *)r->sel_slots[k].ptr,
+                               k == 0 ? (uint32_t *)r->sel_block_hidden.ptr : nullptr);
+            GS_HIP(hipGetLastError());
+            r->launches++;
+            r->sel_key[k] = key;
+        }
+        slots[k] = (const uint64_t *)r->sel_slots[k].ptr;
+    }
+    F.sel.hide = slots[0];
+    F.sel.tint = slots[1];
+    F.sel.block_hidden = slots[0] ? (const uint32_t *)r->sel_block_hidden.ptr : nullptr;
+    const float a = sels[1] ? F.fs->tint_rgba[3] : 0.0f;
+    F.sel.tint_keep = 1.0f - a;
+    for (int c = 0; c < 3; c++) F.sel.tint_add[c] = sels[1] ? a * F.fs->tint_rgba[c] : 0.0f;
+    return GS_OK;
 }
 
 // the zero region and the pair buffers, the block list, the preprocess kernel and — a shape's first frame — the sizing pass
@@ -2990,8 +3075,12 @@ static gs_status stage_preprocess(Frame &F) {
     r->list_mode = false;
     if (F.fc.cull_gain > 0.0f && plan.use_list) GS_TRY(stage_block_cull(F, po));
     const int nt = F.fc.nt_loads ? 1 : 0;
-    hipLaunchKernelGGL((plan.banded ? k_tbl_preprocess_banded[nt][switches().pre_serial ? 0 : 1] : k_tbl_preprocess[nt])[g->sh][g->cov], dim3(F.nchunks),
-                       dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar, F.n, F.fc, po);
+    if (F.fs)
+        hipLaunchKernelGGL((plan.banded ? k_tbl_preprocess_banded_sel[nt][switches().pre_serial ? 0 : 1] : k_tbl_preprocess_sel[nt])[g->sh][g->cov],
+                           dim3(F.nchunks), dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar, F.n, F.fc, po, F.sel);
+    else
+        hipLaunchKernelGGL((plan.banded ? k_tbl_preprocess_banded[nt][switches().pre_serial ? 0 : 1] : k_tbl_preprocess[nt])[g->sh][g->cov], dim3(F.nchunks),
+                           dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar, F.n, F.fc, po);
     GS_HIP(hipGetLastError());
     r->launches++;
     F.marks.mark(ST_SCAN);
@@ -3318,13 +3407,13 @@ static gs_status check_frame_args(gs_renderer *r, gs_stream *s, gs_gaussians_buf
 
 static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g, const gs_gaussian_transform_pod *gt,
                               const gs_model_transform_pod *mt, const gs_camera *cam, uint32_t band_ty0,
-                              uint32_t band_ty1, float *rgba, const gs_aux_targets *aux) {
+                              uint32_t band_ty1, float *rgba, const gs_aux_targets *aux, const gs_frame_selection *fs = nullptr) {
     GS_TRY(check_frame_args(r, s, g, gt, mt, cam, rgba));
     GS_TRY(use_device(r->dev));
     hipStream_t st = s->s;
     GS_TRY(collect_timing(r));
     GS_TRY(take_over_stream(r, st));
-    Frame F{r, st, g, aux, rgba, StageMarks{r, st, r->timing && r->ev_valid}};
+    Frame F{r, st, g, aux, rgba, fs, StageMarks{r, st, r->timing && r->ev_valid}};
     F.mode = gt->flags[0];
     gs::FrameConsts &fc = F.fc;
     make_frame_consts(gt, mt, cam, band_ty0, band_ty1, fc);
@@ -3379,6 +3468,8 @@ static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
     r->tiles_x = fc.tiles_x;
     r->tiles_y = fc.tiles_y;
     r->rect32 = fc.rect32 != 0u;
+    r->width = cam->width;
+    r->height = cam->height;
     r->last_stream = st;
     r->last_stream_gone = false;
     r->have_frame = true;
@@ -3413,6 +3504,7 @@ static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
     if (n == 0) {
         GS_TRY(stage_empty_frame(F));
     } else {
+        if (F.fs) GS_TRY(stage_selection(F));
         GS_TRY(stage_preprocess(F));
         // ... and what depends on the size of the pair buffers (the sizing pass may just have set it)
         gsp::plan_pairs(F.hist, nums, r->pair_capacity, F.requests(), switches(), k_policy_params, r->sort_fb, r->rounds_fb, F.plan);
@@ -3436,11 +3528,8 @@ extern "C" gs_status gs_render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_
     return render_frame(r, s, g, gt, mt, cam, band_ty0, band_ty1, rgba, nullptr);
 }
 
-extern "C" gs_status gs_render_frame_aux(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g,
-                                         const gs_gaussian_transform_pod *gt,
-                                         const gs_model_transform_pod *mt, const gs_camera *cam,
-                                         uint32_t band_ty0, uint32_t band_ty1, float *rgba,
-                                         const gs_aux_targets *aux) {
+// gs_aux_targets as the frame takes it: null when it names no plane
+static gs_status check_aux(const gs_aux_targets *&aux) {
     if (aux) {
         if (aux->reserved != 0u) return fail(GS_ERR_INVALID_ARGUMENT, aux->reserved, 0, 0, "gs_aux_targets.reserved must be 0");
         if (!aux->depth && !aux->pick) {
@@ -3456,7 +3545,50 @@ extern "C" gs_status gs_render_frame_aux(gs_renderer *r, gs_stream *s, gs_gaussi
                             "the depth and pick planes must be 4-byte aligned");
         }
     }
+    return GS_OK;
+}
+
+extern "C" gs_status gs_render_frame_aux(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g,
+                                         const gs_gaussian_transform_pod *gt,
+                                         const gs_model_transform_pod *mt, const gs_camera *cam,
+                                         uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                                         const gs_aux_targets *aux) {
+    GS_TRY(check_aux(aux));
     return render_frame(r, s, g, gt, mt, cam, band_ty0, band_ty1, rgba, aux);
+}
+
+static gs_status check_frame_selection(const gs_renderer *r, const gs_gaussians_buffer *g, const gs_frame_selection *&fs) {
+    if (!fs) return GS_OK;
+    if (fs->reserved[0] != 0u || fs->reserved[1] != 0u)
+        return fail(GS_ERR_INVALID_ARGUMENT, fs->reserved[0], fs->reserved[1], 0, "gs_frame_selection.reserved must be 0");
+    if (!fs->hide && !fs->tint) {
+        fs = nullptr;           // no selection: the plain frame, whatever the tint says
+        return GS_OK;
+    }
+    if (!r || !g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    const size_t len = gs_gaussians_buffer_len(g);
+    for (const gs_selection *sel : {fs->hide, fs->tint}) {
+        if (!sel) continue;
+        if (sel->dev != r->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the selection belongs to another device");
+        if (sel->n != len)
+            return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
+    }
+    if (fs->tint) {
+        const float *t = fs->tint_rgba;
+        if (!std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2]) || !(t[3] >= 0.0f && t[3] <= 1.0f))
+            return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the tint colour must be finite and its alpha in [0, 1]");
+    }
+    return GS_OK;
+}
+
+extern "C" gs_status gs_render_frame_sel(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g,
+                                         const gs_gaussian_transform_pod *gt,
+                                         const gs_model_transform_pod *mt, const gs_camera *cam,
+                                         uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                                         const gs_aux_targets *aux, const gs_frame_selection *fs) {
+    GS_TRY(check_aux(aux));
+    GS_TRY(check_frame_selection(r, g, fs));
+    return render_frame(r, s, g, gt, mt, cam, band_ty0, band_ty1, rgba, aux, fs);
 }
 
 static gs_status download_sync(gs_renderer *r, void *dst, const void *src, size_t bytes) {
@@ -3625,6 +3757,206 @@ extern "C" gs_status gs_renderer_download_ranges(gs_renderer *r, uint32_t *range
 // ------------------------------------------------------------------------------------------------
 // stand-alone primitives
 // ------------------------------------------------------------------------------------------------
+
+// ------------------------------------------------------------------------------------------------
+// Gaussian selections
+// ------------------------------------------------------------------------------------------------
+
+extern "C" gs_status gs_selection_create(gs_device *dev, size_t n, gs_selection **out) {
+    if (!dev || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (n > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, n, 0, 0, "too many Gaussians");
+    GS_TRY(use_device(dev));
+    gs_selection *sel = new gs_selection();
+    sel->dev = dev;
+    sel->n = n;
+    sel->nwords = (n + 31) / 32;
+    sel->words = nullptr;
+    sel->generation = next_object_id();
+    const size_t bytes = (sel->nwords ? sel->nwords : 1) * 4;
+    hipError_t e = hipMalloc((void **)&sel->words, bytes);
+    if (e == hipSuccess) e = hipMemset(sel->words, 0, bytes);
+    if (e != hipSuccess) {
+        if (sel->words) (void)hipFree(sel->words);
+        delete sel;
+        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "selection allocation failed: %s",
+                    hipGetErrorString(e));
+    }
+    *out = sel;
+    return GS_OK;
+}
+
+extern "C" void gs_selection_destroy(gs_selection *sel) {
+    if (!sel) return;
+    (void)hipSetDevice(sel->dev->ordinal);
+    (void)hipFree(sel->words);      // (synchronises the device: kernels that still read the mask finish first)
+    dev_free(sel->scratch);
+    dev_free(sel->counter);
+    delete sel;
+}
+
+extern "C" size_t gs_selection_len(const gs_selection *sel) { return sel ? sel->n : 0; }
+
+static gs_status check_selection(const gs_selection *sel, const gs_stream *s) {
+    if (!sel || !s) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (s->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    return use_device(sel->dev);
+}
+static gs_status check_select_op(gs_select_op op) {
+    if ((uint32_t)op > (uint32_t)GS_SEL_XOR) return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)op, 0, 0, "unknown gs_select_op %u", (unsigned)op);
+    return GS_OK;
+}
+
+static gs_status selection_unary(gs_selection *sel, gs_stream *s, uint32_t mode) {
+    GS_TRY(check_selection(sel, s));
+    sel->generation = next_object_id();
+    if (!sel->nwords) return GS_OK;
+    hipLaunchKernelGGL(gs::k_sel_unary, dim3(sel->grid()), dim3(256), 0, s->s, sel->words, (uint32_t)sel->nwords, sel->tail_mask(), mode);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+extern "C" gs_status gs_selection_clear(gs_selection *sel, gs_stream *s) { return selection_unary(sel, s, 0u); }
+extern "C" gs_status gs_selection_fill(gs_selection *sel, gs_stream *s) { return selection_unary(sel, s, 1u); }
+extern "C" gs_status gs_selection_invert(gs_selection *sel, gs_stream *s) { return selection_unary(sel, s, 2u); }
+
+// dst = dst op src over whole words on `st` (src: another selection's words, or dst's scratch plane)
+static gs_status selection_combine_words(gs_selection *dst, hipStream_t st, gs_select_op op, const uint32_t *src) {
+    dst->generation = next_object_id();
+    if (!dst->nwords) return GS_OK;
+    hipLaunchKernelGGL(gs::k_sel_combine, dim3(dst->grid()), dim3(256), 0, st, dst->words, src, (uint32_t)dst->nwords, (uint32_t)op);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" gs_status gs_selection_combine(gs_selection *dst, gs_stream *s, gs_select_op op, const gs_selection *src) {
+    GS_TRY(check_selection(dst, s));
+    GS_TRY(check_select_op(op));
+    if (!src || src->dev != dst->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the source selection is null or belongs to another device");
+    if (src->n != dst->n) return fail(GS_ERR_INVALID_ARGUMENT, src->n, dst->n, 0, "selection lengths differ: %zu != %zu", src->n, dst->n);
+    return selection_combine_words(dst, s->s, op, src->words);
+}
+
+extern "C" gs_status gs_selection_upload(gs_selection *sel, gs_stream *s, const uint32_t *words, size_t nwords) {
+    GS_TRY(check_selection(sel, s));
+    if (nwords != sel->nwords || (nwords && !words))
+        return fail(GS_ERR_INVALID_ARGUMENT, nwords, sel->nwords, 0, "a selection of %zu bits takes %zu words", sel->n, sel->nwords);
+    sel->generation = next_object_id();
+    if (!nwords) return GS_OK;
+    GS_HIP(hipMemcpyAsync(sel->words, words, nwords * 4, hipMemcpyHostToDevice, s->s));
+    return selection_unary(sel, s, 3u);      // bits past n of the last word are dropped
+}
+
+extern "C" gs_status gs_selection_download(gs_selection *sel, gs_stream *s, uint32_t *words, size_t nwords) {
+    GS_TRY(check_selection(sel, s));
+    if (nwords != sel->nwords || (nwords && !words))
+        return fail(GS_ERR_INVALID_ARGUMENT, nwords, sel->nwords, 0, "a selection of %zu bits takes %zu words", sel->n, sel->nwords);
+    if (!nwords) return GS_OK;
+    GS_HIP(hipStreamSynchronize(s->s));
+    hipError_t e = hipMemcpy(words, sel->words, nwords * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+extern "C" gs_status gs_selection_count(gs_selection *sel, gs_stream *s, uint64_t *out) {
+    GS_TRY(check_selection(sel, s));
+    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
+    *out = 0;
+    if (!sel->nwords) return GS_OK;
+    GS_TRY(dev_reserve(sel->counter, 8));
+    GS_HIP(hipMemsetAsync(sel->counter.ptr, 0, 8, s->s));
+    hipLaunchKernelGGL(gs::k_sel_count, dim3(sel->grid()), dim3(256), 0, s->s, (const uint32_t *)sel->words, (uint32_t)sel->nwords,
+                       (unsigned long long *)sel->counter.ptr);
+    GS_HIP(hipGetLastError());
+    GS_HIP(hipStreamSynchronize(s->s));
+    hipError_t e = hipMemcpy(out, sel->counter.ptr, 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
+// sphere / box: one thread per Gaussian of the AoS buffer, which is always current (the mirror is not needed)
+static gs_status select_shape(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_model_transform_pod *mt, bool box,
+                              const float *params, gs_select_op op) {
+    GS_TRY(check_selection(sel, s));
+    GS_TRY(check_select_op(op));
+    if (!g || !mt || !params) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (g->buf->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    const size_t len = gs_gaussians_buffer_len(g);
+    if (len != sel->n) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
+    gs::SelectShape sh;
+    gs::ModelTransform m;
+    std::memcpy(&m, mt, sizeof(m));
+    gs::model_transform_mat(m, sh.M);
+    std::memcpy(sh.P, params, 12 * sizeof(float));
+    sel->generation = next_object_id();
+    if (!len) return GS_OK;
+    const uint32_t n = (uint32_t)len, grid = (n + 255u) / 256u, pod_words = (uint32_t)(pod_stride(g) / 4);
+    if (box)
+        hipLaunchKernelGGL(gs::k_select_shape<true>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->words,
+                           (uint32_t)op);
+    else
+        hipLaunchKernelGGL(gs::k_select_shape<false>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->words,
+                           (uint32_t)op);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
+extern "C" gs_status gs_select_sphere(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_model_transform_pod *mt,
+                                      const float center[3], float radius, gs_select_op op) {
+    if (!center) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (!(radius >= 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the radius must be >= 0");
+    float p[12] = {center[0], center[1], center[2], radius * radius};
+    return select_shape(sel, s, g, mt, false, p, op);
+}
+
+extern "C" gs_status gs_select_box(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_model_transform_pod *mt,
+                                   const float world_to_box[12], gs_select_op op) {
+    return select_shape(sel, s, g, mt, true, world_to_box, op);
+}
+
+extern "C" gs_status gs_renderer_select_visible(gs_renderer *r, gs_stream *s, gs_selection *sel, float x0, float y0, float x1, float y1,
+                                                const uint8_t *mask, gs_select_op op) {
+    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    GS_TRY(check_selection(sel, s));
+    GS_TRY(check_select_op(op));
+    if (sel->dev != r->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (!r->have_frame) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the renderer has no last frame");
+    if (sel->n != r->n) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, r->n, 0, "the selection has %zu bits, the last frame %zu Gaussians", sel->n, (size_t)r->n);
+    hipStream_t st = s->s;
+    // behind the last frame; from here on the renderer's newest work is on `st`, so its next frame — on whatever stream —
+    // is ordered behind this call the way it is ordered behind a frame
+    GS_TRY(take_over_stream(r, st));
+    r->last_stream = st;
+    r->last_stream_gone = false;
+    if (!sel->nwords) {
+        sel->generation = next_object_id();
+        return GS_OK;
+    }
+    GS_TRY(dev_reserve(sel->scratch, sel->nwords * 4));
+    GS_HIP(hipMemsetAsync(sel->scratch.ptr, 0, sel->nwords * 4, st));
+    const size_t nchunks = ((size_t)r->n + gs::PP_CHUNK - 1) / gs::PP_CHUNK;
+    gs::VisibleIO io;
+    io.depth = (const uint32_t *)r->depth.ptr;
+    io.chunk_vis = (const uint32_t *)r->chunk_vis.ptr;
+    io.recs = (const uint32_t *)r->recs.ptr;
+    io.block_list = r->list_mode ? (const uint32_t *)r->block_list.ptr : nullptr;
+    io.list_blocks = &((const gs::FrameState *)r->state.ptr)->list_blocks;
+    io.order = r->last_order ? (const uint32_t *)r->last_order->ptr : nullptr;
+    io.n = (uint32_t)r->n;
+    io.nslots = (uint32_t)(nchunks * gs::PP_CHUNK);
+    io.x0 = x0; io.y0 = y0; io.x1 = x1; io.y1 = y1;
+    io.mask = mask;
+    io.width = r->width;
+    io.height = r->height;
+    io.scratch = (uint32_t *)sel->scratch.ptr;
+    hipLaunchKernelGGL(gs::k_select_visible, dim3(io.nslots / 256u), dim3(256), 0, st, io);
+    GS_HIP(hipGetLastError());
+    GS_TRY(selection_combine_words(sel, st, op, (const uint32_t *)sel->scratch.ptr));
+    if (switches().frame_event) {
+        // (per-frame events: the end-of-frame event moves behind this call, which `st` has ordered behind the frame)
+        GS_HIP(hipEventRecord(r->done[r->gen & 1u], st));
+        r->done_valid[r->gen & 1u] = true;
+    }
+    return GS_OK;
+}
 
 extern "C" gs_status gs_sort_pairs_u64(gs_device *dev, gs_stream *s, uint64_t *keys, uint32_t *values,
                                        uint64_t count, uint32_t end_bit) {

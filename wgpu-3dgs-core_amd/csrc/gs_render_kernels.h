@@ -983,6 +983,43 @@ struct PreOut {
 constexpr int MSD_TOP_BITS = 10;              // top digit of the MSD-first sorts: 1024 buckets
 constexpr int PRE_HIST_BINS = 1 << MSD_TOP_BITS;
 
+// Hide / tint masks of a selection frame (gs_render_frame_sel), in MIRROR-SLOT order: bit (slot & 63) of
+// word slot >> 6 (k_selection_to_slots), so the 64 Gaussians a wave projects together share one word.  The preprocess
+// kernels take it as a parameter pack that is empty in the plain instantiations (as the blend takes its AuxIO): those
+// keep their kernel-argument layout and their code.
+struct SelIO {
+    const uint64_t *hide;           // or null
+    const uint64_t *tint;           // or null
+    const uint32_t *block_hidden;   // [blocks] 1 = every Gaussian of the 1024-block is hidden; null without `hide`
+    float tint_keep;                // 1 - a
+    float tint_add[3];              // a * t, rounded once (on the host)
+};
+// this wave's word of a slot mask: `slot` is a multiple of 64 plus the lane, so the address is wave-uniform (one scalar load)
+__device__ __forceinline__ bool sel_bit(const uint64_t *mask, uint32_t slot) {
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(slot >> 6));
+    return (mask[w] >> (slot & 63u)) & 1ull;
+}
+// hidden = culled: no tiles, the rect of a culled Gaussian
+__device__ __forceinline__ uint32_t sel_hide(const SelIO &sel, uint32_t slot, uint32_t cnt, uint4 rec[3], uint32_t &rows) {
+    if (sel.hide && sel_bit(sel.hide, slot)) {
+        rec[2].z = rec[2].w = 0u;
+        rows = 0u;
+        return 0u;
+    }
+    return cnt;
+}
+// rgb' = (1 - a) rgb + a t behind the clamp at 0 of §3.2: both products and the sum rounded separately
+__device__ __forceinline__ void sel_tint(const SelIO &sel, uint32_t slot, uint4 rec[3]) {
+    if (sel.tint && sel_bit(sel.tint, slot)) {
+        rec[1].z = f2u(__fadd_rn(__fmul_rn(sel.tint_keep, u2f(rec[1].z)), sel.tint_add[0]));
+        rec[1].w = f2u(__fadd_rn(__fmul_rn(sel.tint_keep, u2f(rec[1].w)), sel.tint_add[1]));
+        rec[2].x = f2u(__fadd_rn(__fmul_rn(sel.tint_keep, u2f(rec[2].x)), sel.tint_add[2]));
+    }
+}
+__device__ __forceinline__ bool sel_block_hidden(const SelIO &sel, uint32_t block) {
+    return sel.block_hidden && sel.block_hidden[block] != 0u;
+}
+
 // this workgroup's share of the per-frame clear job
 __device__ __forceinline__ void pre_begin(const PreOut &io) {
     for (uint32_t i = blockIdx.x * PP_THREADS + threadIdx.x; i < io.zero_words; i += gridDim.x * PP_THREADS)
@@ -1049,13 +1086,23 @@ __device__ __forceinline__ void pre_finish_culled(const PreOut &io) {
 // look-back over the workgroups.  The inclusive frontier advances one look-back window per status
 // round trip across the XCDs, and every waiting workgroup keeps its registers: 0.43 -> 0.54 ms with
 // a 64-wide window, 0.60 ms with a 256-wide one.)
-template <int SH, int COV, bool NT = false>
+// SelArg: empty, or one SelIO — the instantiation of selection frames: a hidden Gaussian is culled, a
+// tinted one has its colour mixed, a fully hidden block is left like a block-culled one.
+template <int SH, int COV, bool NT = false, typename... SelArg>
 __global__ __launch_bounds__(PP_THREADS) void k_preprocess(const uint4 *__restrict__ planar, uint32_t n,
-                                                           FrameConsts fc, PreOut io) {
+                                                           FrameConsts fc, PreOut io, SelArg... sel_arg) {
+    static_assert(sizeof...(SelArg) <= 1u, "at most one SelIO");
+    constexpr bool SEL = sizeof...(SelArg) != 0u;
     __shared__ uint32_t s_red[8];
     __shared__ uint32_t s_dhist[PRE_HIST_BINS];
     __shared__ float s_ln[256];
     pre_begin(io);
+    if constexpr (SEL) {
+        if ((sel_block_hidden(sel_arg, blockIdx.x) || ...)) {
+            pre_finish_culled(io);
+            return;
+        }
+    }
     if (fc.cull_gain > 0.0f && block_is_culled(io.block_bounds + (uint64_t)blockIdx.x * 8u, fc)) {
         pre_finish_culled(io);
         return;
@@ -1088,7 +1135,11 @@ __global__ __launch_bounds__(PP_THREADS) void k_preprocess(const uint4 *__restri
             }
             uint4 rec[3];
             uint32_t rows;
-            const uint32_t cnt = project_one<SH, COV>(w, fc, rec, s_ln, rows);
+            uint32_t cnt = project_one<SH, COV>(w, fc, rec, s_ln, rows);
+            if constexpr (SEL) {
+                ((cnt = sel_hide(sel_arg, i, cnt, rec, rows)), ...);
+                (sel_tint(sel_arg, i, rec), ...);
+            }
             uint32_t *o = io.recs + (uint64_t)i * REC_WORDS;
             store16(o, rec[0], fc.wt_records);
             store16(o + 4, rec[1], fc.wt_records);
@@ -1110,14 +1161,23 @@ __global__ __launch_bounds__(PP_THREADS) void k_preprocess(const uint4 *__restri
 // (EXEC-masked loads: a 128-byte line none of whose lanes survived is not fetched).  With the
 // mirror in spatial order the Gaussians a view (or a rank's tile-row band) culls fill whole lines.
 // Same arithmetic, same outputs as k_preprocess.
-template <int SH, int COV, bool PIPELINED = true, bool NT = false>
+template <int SH, int COV, bool PIPELINED = true, bool NT = false, typename... SelArg>
 __global__ __launch_bounds__(PP_THREADS) void k_preprocess_banded(const uint4 *__restrict__ planar, uint32_t n,
-                                                                  FrameConsts fc, PreOut io) {
+                                                                  FrameConsts fc, PreOut io, SelArg... sel_arg) {
+    static_assert(sizeof...(SelArg) <= 1u, "at most one SelIO");
+    constexpr bool SEL = sizeof...(SelArg) != 0u;
     __shared__ uint32_t s_red[8];
     __shared__ uint32_t s_dhist[PRE_HIST_BINS];
     __shared__ float s_ln[256];
     pre_begin(io);
     uint32_t block = blockIdx.x;
+    if constexpr (SEL) {
+        // (a list frame never sees such a block: k_block_cull dropped it)
+        if (!io.block_list && (sel_block_hidden(sel_arg, blockIdx.x) || ...)) {
+            pre_finish_culled(io);
+            return;
+        }
+    }
     if (io.block_list) {
         // block list (k_block_cull): the surviving blocks are taken by the FIRST *block_count workgroups,
         // back to back; the rest of the grid leaves without a single vector instruction.  (With the test
@@ -1201,7 +1261,8 @@ __global__ __launch_bounds__(PP_THREADS) void k_preprocess_banded(const uint4 *_
             uint4 rec[3];
             float d[3];
             uint32_t rows;
-            const uint32_t cnt = project_geom<SH, COV>(w, fc, rec, d, s_ln, rows);
+            uint32_t cnt = project_geom<SH, COV>(w, fc, rec, d, s_ln, rows);
+            if constexpr (SEL) ((cnt = sel_hide(sel_arg, i, cnt, rec, rows)), ...);
             if (cnt) {
                 constexpr int S0 = 1, S1 = G0 - 1;   // SH-only chunks (G0.. were loaded above)
                 if constexpr (S1 >= S0) {
@@ -1218,6 +1279,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_preprocess_banded(const uint4 *_
                     }
                 }
                 shade_one<SH>(w, fc, d, rec);
+                if constexpr (SEL) (sel_tint(sel_arg, i, rec), ...);
             }
             const uint32_t oi = obase + (i - base);
             if (cnt || !fc.mask_culled_records) {
@@ -1252,9 +1314,14 @@ __global__ __launch_bounds__(PP_THREADS) void k_preprocess_banded(const uint4 *_
 // resets the ticket for the next frame; the one that owns the last group publishes the list length.
 // Ascending matters because the preprocess kernel writes its outputs in LIST order (PreOut::block_list):
 // list order must be mirror order for the depth sort's ties to break as they do without the list.
+// Hidden: empty, or one `const uint32_t *` — the per-block "every Gaussian is hidden" flags of a selection frame
+// (SelIO::block_hidden); such a block is dropped like a culled one.
+template <typename... Hidden>
 __global__ __launch_bounds__(256) void k_block_cull(const float *__restrict__ bb, uint32_t nblocks, FrameConsts fc,
                                                     uint32_t *__restrict__ list, FrameState *state,
-                                                    uint32_t *__restrict__ status, uint32_t tag, uint32_t groups) {
+                                                    uint32_t *__restrict__ status, uint32_t tag, uint32_t groups,
+                                                    Hidden... hidden) {
+    static_assert(sizeof...(Hidden) <= 1u, "at most one flag array");
     __shared__ uint32_t s_group, s_cnt[4], s_sum[4];
     const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
     if (threadIdx.x == 0u) {
@@ -1265,7 +1332,8 @@ __global__ __launch_bounds__(256) void k_block_cull(const float *__restrict__ bb
     __syncthreads();
     const uint32_t g = s_group;
     const uint32_t i = g * 256u + threadIdx.x;
-    const bool alive = i < nblocks && !block_is_culled(bb + (uint64_t)i * 8u, fc);
+    bool alive = i < nblocks && !block_is_culled(bb + (uint64_t)i * 8u, fc);
+    if constexpr (sizeof...(Hidden) != 0u) alive = alive && !((hidden[i] != 0u) || ...);
     const uint64_t m = __ballot(alive);
     if (lane == 0u) s_cnt[wid] = (uint32_t)__popcll(m);
     __syncthreads();
