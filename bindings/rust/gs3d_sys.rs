@@ -65,6 +65,11 @@ pub const GS_SEL_AND: u32 = 2;
 pub const GS_SEL_ANDNOT: u32 = 3;
 pub const GS_SEL_XOR: u32 = 4;
 
+pub const GS_EDIT_TRANSFORM: u32 = 1;
+pub const GS_EDIT_ROTATE_SH: u32 = 2;
+pub const GS_EDIT_COLOR: u32 = 4;
+pub const GS_EDIT_OPACITY: u32 = 8;
+
 #[repr(C)] pub struct gs_device { _private: [u8; 0] }
 #[repr(C)] pub struct gs_stream { _private: [u8; 0] }
 #[repr(C)] pub struct gs_buffer { _private: [u8; 0] }
@@ -282,6 +287,16 @@ pub struct gs_frame_selection {
     pub reserved: [u32; 2],
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_edit {
+    pub flags: u32,
+    pub transform: gs_model_transform_pod,
+    pub color: [f32; 12],
+    pub opacity: [f32; 2],
+    pub reserved: [u32; 4],
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -412,6 +427,9 @@ extern "C" {
     pub fn gs_select_box(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, model_transform: *const gs_model_transform_pod, world_to_box: *const f32, op: u32) -> gs_status;
     pub fn gs_renderer_select_visible(r: *mut gs_renderer, s: *mut gs_stream, sel: *mut gs_selection, x0: f32, y0: f32, x1: f32, y1: f32, mask_plane_device: *const u8, op: u32) -> gs_status;
     pub fn gs_render_frame_sel(r: *mut gs_renderer, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, gaussian_transform: *const gs_gaussian_transform_pod, model_transform: *const gs_model_transform_pod, camera: *const gs_camera, band_ty0: u32, band_ty1: u32, rgba_out_device: *mut f32, aux: *const gs_aux_targets, fs: *const gs_frame_selection) -> gs_status;
+    pub fn gs_gaussians_buffer_edit(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, e: *const gs_edit) -> gs_status;
+    pub fn gs_gaussians_buffer_create_from_selection(src: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
+    pub fn gs_sh_rotation_matrices(rot_xyzw: *const f32, d1: *mut f32, d2: *mut f32, d3: *mut f32) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

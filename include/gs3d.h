@@ -790,6 +790,45 @@ gs_status gs_render_frame_sel(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
                               uint32_t band_ty0, uint32_t band_ty1, float *rgba_out_device,
                               const gs_aux_targets *aux, const gs_frame_selection *fs);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Edits of the selected Gaussians, extraction (no reference item in the core     */
+/* crate: the reference's editor moves, recolours and removes Gaussians with compute passes)     */
+/* ------------------------------------------------------------------------------------------ */
+
+/* gs_edit.flags; the stages run in this order (no reference item) */
+enum { GS_EDIT_TRANSFORM = 1, GS_EDIT_ROTATE_SH = 2, GS_EDIT_COLOR = 4, GS_EDIT_OPACITY = 8 };
+/* One edit (no reference item).  Only the fields whose flag is set are looked at. */
+typedef struct gs_edit {
+    uint32_t flags;
+    gs_model_transform_pod transform;  /* pos, rot (xyzw), scale: scale.x == scale.y == scale.z > 0 */
+    float color[12];                   /* column-major 3 x 4: rgb' = C (rgb, 1) */
+    float opacity[2];                  /* a' = opacity[0] a + opacity[1] */
+    uint32_t reserved[4];              /* 0 */
+} gs_edit;
+
+/* Applies `e` to every Gaussian of `sel` (NULL: all) in place on the device, for all 12 layouts (DESIGN.md 3.8;
+ * no reference item).  Only ENQUEUES on `s` (NULL: the device's internal stream): the next frame of any renderer on any stream is
+ * ordered behind it and sees the edited records; downloads and select ops on OTHER streams are the caller's to order, as
+ * with any buffer.  A Gaussian outside the selection and a field whose flag is not set keep every byte.  GS_EDIT_ROTATE_SH
+ * on an SH-less layout is ignored; flags == 0 launches nothing and dirties nothing.  GS_ERR_INVALID_ARGUMENT, before
+ * anything is enqueued, for a null buffer or edit, unknown flag bits, nonzero `reserved`, ROTATE_SH without TRANSFORM, a
+ * non-finite field that the flags use, a zero rotation with ROTATE_SH, a scale that is not uniform, not positive or NaN,
+ * a selection whose length differs from the buffer's or that belongs to another device. */
+gs_status gs_gaussians_buffer_edit(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, const gs_edit *e);
+/* New buffer of the same layout (and spatial-order setting) holding the records of `sel` (invert != 0: of its complement;
+ * NULL: all / none), caller order kept, bytes unchanged: a stable compaction on the device (DESIGN.md 3.8;
+ * no reference item).  Blocking, like gs_selection_count: sizing the new buffer needs the count on the host; *count_out (optional) = its
+ * length.  A result of length 0 is what gs_gaussians_buffer_create gives for length 0: GS_OK and a valid buffer whose
+ * length is 0 (it owns a 16-byte allocation).  GS_ERR_INVALID_ARGUMENT for a null argument or a selection whose length
+ * differs from the buffer's or that belongs to another device; *out is then NULL. */
+gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel,
+                                                    int32_t invert, gs_gaussians_buffer **out, uint64_t *count_out);
+/* Host only: the SH band matrices of a rotation (row-major 3x3, 5x5, 7x7), as the edit uses them: sh'_k = sum_j D[k][j] sh_j
+ * per channel and band, defined by sum_k Y_k(d) c'_k = sum_k Y_k(R^T d) c_k for every unit d, R the rotation of the
+ * NORMALISED quaternion; computed in double, rounded to binary32 (no reference item).
+ * GS_ERR_INVALID_ARGUMENT for a null pointer or a non-finite or zero quaternion. */
+gs_status gs_sh_rotation_matrices(const float rot_xyzw[4], float d1[9], float d2[25], float d3[49]);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

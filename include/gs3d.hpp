@@ -296,6 +296,8 @@ class Buffer {   // wgpu::Buffer + BufferWrapper (src/buffer/mod.rs:17-102); Clo
     gs_buffer *h_ = nullptr;
 };
 
+class Selection;
+
 template <class G>
 class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
   public:
@@ -325,6 +327,11 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     bool spatial_order() const { return gs_gaussians_buffer_spatial_order(h_) != 0; }
     std::vector<uint32_t> download_order(Stream &s) const { std::vector<uint32_t> out(len()); check(gs_gaussians_buffer_download_order(h_, s.raw(), out.data(), out.size())); return out; }
     void mark_dirty() { gs_gaussians_buffer_mark_dirty(h_); }
+    // edits of the selected Gaussians on the device (gs3d.h gs_gaussians_buffer_edit; no reference item):
+    // sel == nullptr means every Gaussian; only enqueues on the stream
+    void edit(Stream &s, const Selection *sel, const gs_edit &e);
+    // a new buffer with the records of sel (invert: of its complement), caller order kept; blocking
+    GaussiansBuffer extract(Stream &s, const Selection *sel, bool invert = false) const;
     gs_gaussians_buffer *raw() const { return h_; }
   private:
     GaussiansBuffer() = default;
@@ -359,6 +366,24 @@ class Selection {
   private:
     gs_selection *h_ = nullptr;
 };
+
+template <class G>
+inline void GaussiansBuffer<G>::edit(Stream &s, const Selection *sel, const gs_edit &e) {
+    check(gs_gaussians_buffer_edit(h_, s.raw(), sel ? sel->raw() : nullptr, &e));
+}
+template <class G>
+inline GaussiansBuffer<G> GaussiansBuffer<G>::extract(Stream &s, const Selection *sel, bool invert) const {
+    GaussiansBuffer b;
+    check(gs_gaussians_buffer_create_from_selection(h_, s.raw(), sel ? sel->raw() : nullptr, invert ? 1 : 0, &b.h_, nullptr));
+    return b;
+}
+// the SH band matrices of a rotation (xyzw), row-major 3x3, 5x5, 7x7 (gs3d.h gs_sh_rotation_matrices; no reference item)
+struct ShRotation { float d1[9], d2[25], d3[49]; };
+inline ShRotation sh_rotation_matrices(const float rot_xyzw[4]) {
+    ShRotation r;
+    check(gs_sh_rotation_matrices(rot_xyzw, r.d1, r.d2, r.d3));
+    return r;
+}
 
 // GaussianTransformPod helpers (src/buffer/gaussian_transform.rs)
 inline std::optional<gs_gaussian_transform_pod> gaussian_transform_pod(float size, gs_display_mode mode, uint8_t sh_deg, bool no_sh0, float max_std_dev) {

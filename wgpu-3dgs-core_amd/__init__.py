@@ -20,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import AuxTargets, Camera, FrameResult, FrameSelection, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
+from ._capi import AuxTargets, Camera, Edit, FrameResult, FrameSelection, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
 
 _L = _capi.load()
 
@@ -840,6 +840,30 @@ class GaussiansBuffer:
                                                       _ptr(out), self.len()))
         return out
 
+    def edit(self, stream, selection, edit):
+        """gs_gaussians_buffer_edit: applies `edit` (see edit()) to the Gaussians of `selection` (None:
+        all) in place on the device.  Only enqueues on the stream; the next frame of any renderer sees the result."""
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        if not isinstance(edit, Edit):
+            raise TypeError("edit must be an Edit (see edit()), not %s" % type(edit).__name__)
+        _check(_L.gs_gaussians_buffer_edit(self._h, stream._h if stream is not None else None,
+                                           selection._h if selection is not None else None, C.byref(edit)))
+
+    def extract(self, stream, selection, invert=False):
+        """gs_gaussians_buffer_create_from_selection: a new GaussiansBuffer of the same layout with the records of
+        `selection` (invert: of its complement) in caller order, bytes unchanged.  Blocking.  `extract(sel, invert=True)`
+        deletes the selection, the pair (extract(sel), extract(sel, invert=True)) splits the buffer."""
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        h, count = C.c_void_p(), C.c_uint64()
+        _check(_L.gs_gaussians_buffer_create_from_selection(self._h, stream._h if stream is not None else None,
+                                                            selection._h if selection is not None else None,
+                                                            int(bool(invert)), C.byref(h), C.byref(count)))
+        out = GaussiansBuffer(self.device, self.pod, h)
+        assert out.len() == count.value
+        return out
+
     def destroy(self):
         if self._h:
             _L.gs_gaussians_buffer_destroy(self._h)
@@ -1281,6 +1305,106 @@ def box_from_bounds(lo, hi):
     b[0, 0], b[1, 1], b[2, 2] = 1.0 / half
     b[3] = -mid / half
     return b.reshape(-1).astype(np.float32)
+
+
+# gs_edit.flags
+EDIT_TRANSFORM, EDIT_ROTATE_SH, EDIT_COLOR, EDIT_OPACITY = 1, 2, 4, 8
+
+
+def sh_rotation_matrices(rot):
+    """gs_sh_rotation_matrices: the SH band matrices (3 x 3, 5 x 5, 7 x 7, float32) of the rotation `rot` (xyzw), as the
+    edit applies them: sh'_k = sum_j D[k][j] sh_j per channel and band."""
+    q = (C.c_float * 4)(*[float(v) for v in rot])
+    d1, d2, d3 = np.zeros((3, 3), np.float32), np.zeros((5, 5), np.float32), np.zeros((7, 7), np.float32)
+    _check(_L.gs_sh_rotation_matrices(q, _ptr(d1), _ptr(d2), _ptr(d3)))
+    return d1, d2, d3
+
+
+def _color_matrix(m):
+    """12 floats, column-major 3 x 4, from 12 numbers in that order or from a 3 x 4 array (rows = output channels)"""
+    a = np.asarray(m, dtype=np.float64)
+    if a.shape == (3, 4):
+        a = a.T
+    if a.size != 12 or a.ndim > 2 or (a.ndim == 2 and a.shape != (4, 3)):
+        raise ValueError("a colour matrix takes 12 numbers (3 x 4, column-major) or a 3 x 4 array")
+    return a.reshape(-1).astype(np.float32)
+
+
+def _color_affine(linear, offset):
+    m = np.zeros((3, 4))
+    m[:, :3] = linear
+    m[:, 3] = offset
+    return _color_matrix(m)
+
+
+def color_override(rgb):
+    """every selected Gaussian gets the colour `rgb` (0..1); the linear part is 0, so the SH rest coefficients are
+    flattened with it"""
+    return _color_affine(np.zeros((3, 3)), np.asarray(rgb, np.float64).reshape(3))
+
+
+def color_exposure(stops):
+    """rgb' = 2^stops rgb"""
+    return _color_affine(np.eye(3) * 2.0 ** float(stops), 0.0)
+
+
+def color_contrast(contrast, pivot=0.5):
+    """rgb' = (rgb - pivot) contrast + pivot"""
+    k = float(contrast)
+    return _color_affine(np.eye(3) * k, float(pivot) * (1.0 - k))
+
+
+_LUMA = np.array([0.2126, 0.7152, 0.0722])      # Rec. 709
+
+
+def color_saturation(saturation):
+    """rgb' = luma + saturation (rgb - luma), Rec. 709 luma: 0 is grey, 1 the identity"""
+    s = float(saturation)
+    return _color_affine(s * np.eye(3) + (1.0 - s) * np.outer(np.ones(3), _LUMA), 0.0)
+
+
+def color_hue(degrees):
+    """the rotation of rgb about the grey axis (1, 1, 1) by `degrees`"""
+    a = np.deg2rad(float(degrees))
+    c, s = np.cos(a), np.sin(a)
+    k = np.ones(3) / np.sqrt(3.0)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return _color_affine(c * np.eye(3) + s * K + (1.0 - c) * np.outer(k, k), 0.0)
+
+
+def edit(transform=None, rotate_sh=True, color=None, opacity=None, pivot=None):
+    """The gs_edit of GaussiansBuffer.edit.  transform: a ModelTransformPod (uniform positive scale)
+    applied to position, rotation / covariance and scale, and — with rotate_sh — to the SH rest coefficients.  pivot: the
+    point that the transform's rotation and scale leave in place (p' = s R (p - pivot) + pivot + pos); it is folded into
+    transform.pos here, on the host.  color: 12 numbers (3 x 4, column-major: rgb' = C (rgb, 1)), a 3 x 4 array, or the
+    result of a color_* helper.  opacity: (o0, o1) for a' = o0 a + o1, or one number o0.  Arguments left None are not
+    touched by the edit; the library checks the values."""
+    e = Edit()
+    if pivot is not None and transform is None:
+        raise ValueError("a pivot goes with a transform")
+    if transform is not None:
+        if not isinstance(transform, ModelTransformPod):
+            raise TypeError("transform must be a ModelTransformPod (model_transform_pod())")
+        e.flags |= EDIT_TRANSFORM | (EDIT_ROTATE_SH if rotate_sh else 0)
+        e.transform = model_transform_pod(tuple(transform.pos), tuple(transform.rot), tuple(transform.scale))
+        if pivot is not None:
+            c = np.asarray(pivot, np.float64).reshape(3)
+            x, y, z, w = [float(v) for v in transform.rot]
+            R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                          [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                          [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+            sr = R * np.asarray(tuple(transform.scale), np.float64)[None, :]
+            e.transform.pos[:] = [float(v) for v in np.asarray(tuple(transform.pos), np.float64) + c - sr @ c]
+    if color is not None:
+        e.flags |= EDIT_COLOR
+        e.color[:] = [float(v) for v in _color_matrix(color)]
+    if opacity is not None:
+        o = np.atleast_1d(np.asarray(opacity, np.float64))
+        if o.shape not in ((1,), (2,)):
+            raise ValueError("opacity takes (o0, o1) or one number")
+        e.flags |= EDIT_OPACITY
+        e.opacity[:] = [float(o[0]), float(o[1]) if o.size == 2 else 0.0]
+    return e
 
 
 class Renderer:

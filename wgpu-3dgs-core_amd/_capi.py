@@ -57,6 +57,12 @@ class FrameSelection(C.Structure):
     _fields_ = [("hide", vp), ("tint", vp), ("tint_rgba", f32 * 4), ("reserved", u32 * 2)]
 
 
+class Edit(C.Structure):
+    """gs_edit: one edit of the selected Gaussians (gs_gaussians_buffer_edit)"""
+    _fields_ = [("flags", u32), ("transform", ModelTransformPod), ("color", f32 * 12), ("opacity", f32 * 2),
+                ("reserved", u32 * 4)]
+
+
 class SortInfo(C.Structure):
     _fields_ = [("depth_msd", u32), ("depth_bucket_max", u32), ("bucket_capacity", u32), ("tile_msd", u32),
                 ("tile_bucket_max", u32), ("tile_masks", u32), ("rounds", u32), ("round1", u32), ("tiles_done", u32), ("partitioned", u32)]
@@ -217,6 +223,9 @@ SIGNATURES = {
     "gs_select_box": (i32, [vp, vp, vp, vp, vp, i32]),
     "gs_renderer_select_visible": (i32, [vp, vp, vp, f32, f32, f32, f32, vp, i32]),
     "gs_render_frame_sel": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]),
+    "gs_gaussians_buffer_edit": (i32, [vp, vp, vp, vp]),
+    "gs_gaussians_buffer_create_from_selection": (i32, [vp, vp, vp, i32, vp, vp]),
+    "gs_sh_rotation_matrices": (i32, [vp, vp, vp, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

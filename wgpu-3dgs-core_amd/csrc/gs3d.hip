@@ -23,6 +23,7 @@
 #include "gs_bundle_kernels.h"
 #include "gs_render_kernels.h"
 #include "gs_select_kernels.h"
+#include "gs_edit_kernels.h"
 #include "gs_pack_kernels.h"
 #include "_gen_kernel_lib_src.h"
 
@@ -680,6 +681,12 @@ struct gs_gaussians_buffer {
     // (several renderers keeping frames in flight on one buffer) wait for this event before reading it.
     hipEvent_t mirror_ready = nullptr;
     hipStream_t mirror_stream = nullptr;
+    // gs_gaussians_buffer_edit only ENQUEUES its kernel: a mirror rebuild on another stream waits for
+    // this event before it reads the AoS records.  keep_order: the whole buffer is dirty but no position changed (a
+    // colour / opacity edit), so the rebuild repacks through the order it has instead of sorting again.
+    hipEvent_t edit_done = nullptr;
+    hipStream_t edit_stream = nullptr;
+    bool keep_order = false;
     // what a renderer's slot-ordered selection masks were gathered through: this buffer (ids are never
     // reused, addresses are) and this build of its mirror order
     uint64_t uid = next_object_id();
@@ -691,7 +698,7 @@ struct gs_gaussians_buffer {
         if (lo < dirty_lo) dirty_lo = lo;
         if (hi > dirty_hi) dirty_hi = hi;
     }
-    void mark_all() { dirty_lo = 0; dirty_hi = (size_t)-1; }
+    void mark_all() { dirty_lo = 0; dirty_hi = (size_t)-1; keep_order = false; }
 };
 
 static size_t pod_stride(const gs_gaussians_buffer *g) { return (size_t)gs::pod_bytes(g->sh, g->cov); }
@@ -950,6 +957,7 @@ extern "C" void gs_gaussians_buffer_destroy(gs_gaussians_buffer *g) {
     if (g->inv) (void)hipFree(g->inv);
     if (g->block_bounds) (void)hipFree(g->block_bounds);
     if (g->mirror_ready) (void)hipEventDestroy(g->mirror_ready);
+    if (g->edit_done) (void)hipEventDestroy(g->edit_done);
     if (g->order) gs_buffer_release(g->order);
     gs_buffer_release(g->buf);
     delete g;
@@ -2540,9 +2548,12 @@ static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
     if (g->spatial && g->order && lo < hi && g->partial_since_order > len / 4) {
         lo = 0;
         hi = len;
+        g->keep_order = false;
     }
     if (lo < hi) {
-        const bool whole = lo == 0 && hi == len;
+        // the records may have been edited on another stream (gs_gaussians_buffer_edit only enqueues)
+        if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
+        const bool whole = lo == 0 && hi == len && !g->keep_order;
         if (whole) g->partial_since_order = 0;
         const bool want_order = g->spatial && len > 1;
         if (whole || want_order != (g->order != nullptr)) {
@@ -2592,6 +2603,7 @@ static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
         GS_HIP(hipStreamWaitEvent(st, g->mirror_ready, 0));
     }
     g->dirty_lo = g->dirty_hi = 0;
+    g->keep_order = false;
     return GS_OK;
 }
 
@@ -4073,4 +4085,253 @@ extern "C" gs_status gs_exclusive_scan_u32(gs_device *dev, gs_stream *s, const u
     if (total_out) *total_out = total;
     for (DevArray *a : {&din, &dout, &sums, &offs, &tot}) dev_free(*a);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// edits of the selected Gaussians, extraction
+// ------------------------------------------------------------------------------------------------
+
+// the basis of DESIGN.md §3.2 for one band (l = 1, 2, 3: 3, 5, 7 functions), in double
+static void sh_band_basis(int l, const double d[3], double *Y) {
+    const double x = d[0], y = d[1], z = d[2], xx = x * x, yy = y * y, zz = z * z;
+    if (l == 1) {
+        const double C1 = 0.4886025119029199;
+        Y[0] = -C1 * y;
+        Y[1] = C1 * z;
+        Y[2] = -C1 * x;
+    } else if (l == 2) {
+        Y[0] = 1.0925484305920792 * x * y;
+        Y[1] = -1.0925484305920792 * y * z;
+        Y[2] = 0.31539156525252005 * (2.0 * zz - xx - yy);
+        Y[3] = -1.0925484305920792 * x * z;
+        Y[4] = 0.5462742152960396 * (xx - yy);
+    } else {
+        Y[0] = -0.5900435899266435 * y * (3.0 * xx - yy);
+        Y[1] = 2.890611442640554 * x * y * z;
+        Y[2] = -0.4570457994644658 * y * (4.0 * zz - xx - yy);
+        Y[3] = 0.3731763325901154 * z * (2.0 * zz - 3.0 * xx - 3.0 * yy);
+        Y[4] = -0.4570457994644658 * x * (4.0 * zz - xx - yy);
+        Y[5] = 1.445305721320277 * z * (xx - yy);
+        Y[6] = -0.5900435899266435 * x * (xx - 3.0 * yy);
+    }
+}
+
+// D of one band from its defining property: B D = B' over sample directions d_i, B[i][k] = Y_k(d_i),
+// B'[i][k] = Y_k(R^T d_i); solved as the normal equations (B^T B) D = B^T B' by Gaussian elimination with partial
+// pivoting.  The band's functions span a rotation-invariant space, so the system is consistent and D is exact up to
+// double rounding.
+static bool sh_band_rotation(int l, const double R[3][3], float *out) {
+    const int nb = 2 * l + 1, NS = 64;
+    double N[7][14] = {};      // [B^T B | B^T B']
+    for (int i = 0; i < NS; i++) {
+        // Fibonacci sphere: well spread, no symmetry that a band could hide in
+        const double z = 1.0 - (2.0 * i + 1.0) / NS, r = std::sqrt(1.0 - z * z), phi = i * 2.399963229728653;
+        const double d[3] = {r * std::cos(phi), r * std::sin(phi), z};
+        double dr[3];
+        for (int a = 0; a < 3; a++) dr[a] = (R[0][a] * d[0] + R[1][a] * d[1]) + R[2][a] * d[2];     // R^T d
+        double Y[7], Yr[7];
+        sh_band_basis(l, d, Y);
+        sh_band_basis(l, dr, Yr);
+        for (int k = 0; k < nb; k++)
+            for (int j = 0; j < nb; j++) {
+                N[k][j] += Y[k] * Y[j];
+                N[k][nb + j] += Y[k] * Yr[j];
+            }
+    }
+    for (int c = 0; c < nb; c++) {
+        int p = c;
+        for (int r = c + 1; r < nb; r++)
+            if (std::fabs(N[r][c]) > std::fabs(N[p][c])) p = r;
+        if (!(std::fabs(N[p][c]) > 1e-12)) return false;
+        if (p != c)
+            for (int j = 0; j < 2 * nb; j++) std::swap(N[p][j], N[c][j]);
+        for (int r = 0; r < nb; r++) {
+            if (r == c) continue;
+            const double f = N[r][c] / N[c][c];
+            for (int j = c; j < 2 * nb; j++) N[r][j] -= f * N[c][j];
+        }
+    }
+    // the entries are polynomials in R of magnitude <= 1; what the solve leaves below 1e-14 is its own rounding noise
+    // (the identity must give the identity)
+    for (int k = 0; k < nb; k++)
+        for (int j = 0; j < nb; j++) {
+            const double v = N[k][nb + j] / N[k][k];
+            out[k * nb + j] = std::fabs(v) < 1e-14 ? 0.0f : (float)v;
+        }
+    return true;
+}
+
+extern "C" gs_status gs_sh_rotation_matrices(const float rot_xyzw[4], float d1[9], float d2[25], float d3[49]) {
+    if (!rot_xyzw || !d1 || !d2 || !d3) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    double q[4], len2 = 0.0;
+    for (int k = 0; k < 4; k++) {
+        q[k] = (double)rot_xyzw[k];
+        len2 += q[k] * q[k];
+    }
+    if (!std::isfinite(len2) || !(len2 > 0.0)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the rotation must be finite and nonzero");
+    const double inv = 1.0 / std::sqrt(len2);
+    const double x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;
+    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)},
+                            {2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)},
+                            {2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)}};
+    if (!sh_band_rotation(1, R, d1) || !sh_band_rotation(2, R, d2) || !sh_band_rotation(3, R, d3))
+        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the rotation is degenerate");
+    return GS_OK;
+}
+
+static bool all_finite(const float *v, int n) {
+    for (int k = 0; k < n; k++)
+        if (!std::isfinite(v[k])) return false;
+    return true;
+}
+
+// the selection argument of an edit / extraction: NULL (all), or n bits on the buffer's device
+static gs_status check_buffer_selection(const gs_gaussians_buffer *g, const gs_stream *s, const gs_selection *sel) {
+    if (s && s->dev != g->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (!sel) return GS_OK;
+    if (sel->dev != g->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    const size_t len = gs_gaussians_buffer_len(g);
+    if (sel->n != len) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
+    return GS_OK;
+}
+
+typedef void (*edit_fn)(uint4 *, uint32_t, const uint32_t *, gs::EditArgs);
+static edit_fn k_tbl_edit[4][3] = GS_CFG_TABLE(gs::k_edit);
+
+extern "C" gs_status gs_gaussians_buffer_edit(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, const gs_edit *e) {
+    if (!g || !e) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    const uint32_t known = GS_EDIT_TRANSFORM | GS_EDIT_ROTATE_SH | GS_EDIT_COLOR | GS_EDIT_OPACITY;
+    if (e->flags & ~known) return fail(GS_ERR_INVALID_ARGUMENT, e->flags, 0, 0, "unknown gs_edit flags 0x%x", (unsigned)e->flags);
+    for (uint32_t r : e->reserved)
+        if (r) return fail(GS_ERR_INVALID_ARGUMENT, r, 0, 0, "gs_edit.reserved must be 0");
+    if ((e->flags & GS_EDIT_ROTATE_SH) && !(e->flags & GS_EDIT_TRANSFORM))
+        return fail(GS_ERR_INVALID_ARGUMENT, e->flags, 0, 0, "GS_EDIT_ROTATE_SH goes with GS_EDIT_TRANSFORM");
+    gs::EditArgs a{};
+    a.flags = e->flags;
+    if (e->flags & GS_EDIT_TRANSFORM) {
+        const gs_model_transform_pod &t = e->transform;
+        if (!all_finite(t.pos, 3) || !all_finite(t.rot, 4) || !all_finite(t.scale, 3))
+            return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the transform of an edit must be finite");
+        if (!(t.scale[0] > 0.0f) || t.scale[1] != t.scale[0] || t.scale[2] != t.scale[0])
+            return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the scale of an edit must be uniform and positive");
+        gs::ModelTransform m;
+        std::memcpy(&m, &t, sizeof(m));
+        gs::model_transform_mat(m, a.M);
+        gs::model_scale_rot_mat(m, a.A);
+        std::memcpy(a.q, t.rot, sizeof(a.q));
+        a.s = t.scale[0];
+        if (e->flags & GS_EDIT_ROTATE_SH) GS_TRY(gs_sh_rotation_matrices(t.rot, a.D1, a.D2, a.D3));
+    }
+    if (e->flags & GS_EDIT_COLOR) {
+        if (!all_finite(e->color, 12)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the colour matrix of an edit must be finite");
+        std::memcpy(a.C, e->color, sizeof(a.C));
+    }
+    if (e->flags & GS_EDIT_OPACITY) {
+        if (!all_finite(e->opacity, 2)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the opacity terms of an edit must be finite");
+        std::memcpy(a.o, e->opacity, sizeof(a.o));
+    }
+    GS_TRY(check_buffer_selection(g, s, sel));
+    const size_t len = gs_gaussians_buffer_len(g);
+    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
+    if (g->sh == GS_SH_NONE) a.flags &= ~(uint32_t)GS_EDIT_ROTATE_SH;
+    if (!a.flags || !len) return GS_OK;
+    gs_device *dev = g->buf->dev;
+    GS_TRY(use_device(dev));
+    hipStream_t st = stream_of(dev, s);
+    // a mirror rebuild in flight on another stream still reads the records
+    if (g->mirror_ready && st != g->mirror_stream) GS_HIP(hipStreamWaitEvent(st, g->mirror_ready, 0));
+    const uint32_t n = (uint32_t)len;
+    hipLaunchKernelGGL(k_tbl_edit[g->sh][g->cov], dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, n,
+                       sel ? (const uint32_t *)sel->words : nullptr, a);
+    GS_HIP(hipGetLastError());
+    if (!g->edit_done) GS_HIP(hipEventCreateWithFlags(&g->edit_done, hipEventDisableTiming));
+    GS_HIP(hipEventRecord(g->edit_done, st));
+    g->edit_stream = st;
+    // The host does not know which Gaussians the selection names: the whole mirror is stale.  A transform moves them,
+    // so the next frame sorts the spatial order again, exactly as after an upload of the edited records; a colour /
+    // opacity edit keeps every position, and with it the order (only the repack and the block bounds run again).
+    if (a.flags & GS_EDIT_TRANSFORM) {
+        g->mark_all();
+    } else if (!(g->dirty_lo == 0 && g->dirty_hi >= len)) {
+        g->dirty_lo = 0;
+        g->dirty_hi = len;
+        g->keep_order = true;
+    }
+    return GS_OK;
+}
+
+extern "C" gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel,
+                                                               int32_t invert, gs_gaussians_buffer **out, uint64_t *count_out) {
+    if (!src || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    *out = nullptr;
+    if (count_out) *count_out = 0;
+    GS_TRY(check_buffer_selection(src, s, sel));
+    const size_t len = gs_gaussians_buffer_len(src);
+    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
+    gs_device *dev = src->buf->dev;
+    GS_TRY(use_device(dev));
+    hipStream_t st = stream_of(dev, s);
+    // an edit enqueued on another stream still writes the records
+    if (src->edit_done && st != src->edit_stream) GS_HIP(hipStreamWaitEvent(st, src->edit_done, 0));
+    const uint32_t n = (uint32_t)len, inv = invert ? 1u : 0u;
+    const uint32_t nblocks = (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK, nc = (uint32_t)(pod_stride(src) / 16);
+    const uint32_t *words = sel ? (const uint32_t *)sel->words : nullptr;
+    DevArray counts, offsets, total_dev;
+    uint32_t total = 0;
+    gs_status rc = GS_OK;
+    if (n) {
+        rc = dev_reserve(counts, (size_t)nblocks * 4);
+        if (rc == GS_OK) rc = dev_reserve(offsets, (size_t)nblocks * 4);
+        if (rc == GS_OK) rc = dev_reserve(total_dev, 16);
+        if (rc == GS_OK) {
+            hipLaunchKernelGGL(gs::k_extract_block_counts, dim3((nblocks * 32u + 255u) / 256u), dim3(256), 0, st, words, n, inv, nblocks,
+                               (uint32_t *)counts.ptr);
+            gs::ScanJob job{(const uint32_t *)counts.ptr, (uint32_t *)offsets.ptr, (uint32_t *)total_dev.ptr, nblocks};
+            hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
+            hipError_t e = hipGetLastError();
+            // sizing the new buffer needs the total on the host
+            if (e == hipSuccess) e = hipMemcpyAsync(&total, total_dev.ptr, 4, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
+            else if (total > n) rc = fail(GS_ERR_HIP, total, n, 0, "selection scan returned %u of %u Gaussians", total, n);
+        }
+    }
+    gs_gaussians_buffer *dst = nullptr;
+    if (rc == GS_OK && total) {
+        // The copy below writes every byte of the new buffer, so it is allocated WITHOUT the zero fill of gs_buffer_create:
+        // that hipMemset runs on the null stream, which `st` is not ordered behind, and would race with the copy.
+        void *p = nullptr;
+        const size_t bytes = (size_t)total * pod_stride(src);
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            rc = fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, bytes, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+        } else {
+            gs_buffer *b = new gs_buffer();
+            b->dev = dev;
+            b->ptr = p;
+            b->bytes = bytes;
+            b->owned = true;
+            b->refs.store(1);
+            rc = gs_gaussians_buffer_from_buffer(b, (gs_sh_config)src->sh, (gs_cov3d_config)src->cov, &dst);
+            gs_buffer_release(b);
+        }
+    } else if (rc == GS_OK) {
+        rc = gs_gaussians_buffer_create(dev, (gs_sh_config)src->sh, (gs_cov3d_config)src->cov, nullptr, 0, &dst);
+    }
+    if (rc == GS_OK && total) {
+        hipLaunchKernelGGL(gs::k_extract_copy, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)src->buf->ptr,
+                           (uint4 *)dst->buf->ptr, words, n, inv, (const uint32_t *)offsets.ptr, nc, total);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);      // `offsets` is freed below; the call is blocking anyway
+        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "extraction failed: %s", hipGetErrorString(e));
+    }
+    for (DevArray *a : {&counts, &offsets, &total_dev}) dev_free(*a);
+    if (rc != GS_OK) {
+        if (dst) gs_gaussians_buffer_destroy(dst);
+        return rc;
+    }
+    dst->spatial = src->spatial;
+    *out = dst;
+    if (count_out) *count_out = total;
+    return GS_OK;
 }
