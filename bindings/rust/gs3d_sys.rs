@@ -78,6 +78,7 @@ pub const GS_EDIT_OPACITY: u32 = 8;
 #[repr(C)] pub struct gs_bundle { _private: [u8; 0] }
 #[repr(C)] pub struct gs_renderer { _private: [u8; 0] }
 #[repr(C)] pub struct gs_selection { _private: [u8; 0] }
+#[repr(C)] pub struct gs_snapshot { _private: [u8; 0] }
 
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -425,11 +426,20 @@ extern "C" {
     pub fn gs_selection_count(sel: *mut gs_selection, s: *mut gs_stream, out: *mut u64) -> gs_status;
     pub fn gs_select_sphere(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, model_transform: *const gs_model_transform_pod, center: *const f32, radius: f32, op: u32) -> gs_status;
     pub fn gs_select_box(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, model_transform: *const gs_model_transform_pod, world_to_box: *const f32, op: u32) -> gs_status;
+    pub fn gs_select_range(sel: *mut gs_selection, s: *mut gs_stream, start: usize, count: usize, op: u32) -> gs_status;
     pub fn gs_renderer_select_visible(r: *mut gs_renderer, s: *mut gs_stream, sel: *mut gs_selection, x0: f32, y0: f32, x1: f32, y1: f32, mask_plane_device: *const u8, op: u32) -> gs_status;
     pub fn gs_render_frame_sel(r: *mut gs_renderer, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, gaussian_transform: *const gs_gaussian_transform_pod, model_transform: *const gs_model_transform_pod, camera: *const gs_camera, band_ty0: u32, band_ty1: u32, rgba_out_device: *mut f32, aux: *const gs_aux_targets, fs: *const gs_frame_selection) -> gs_status;
     pub fn gs_gaussians_buffer_edit(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, e: *const gs_edit) -> gs_status;
     pub fn gs_gaussians_buffer_create_from_selection(src: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
     pub fn gs_sh_rotation_matrices(rot_xyzw: *const f32, d1: *mut f32, d2: *mut f32, d3: *mut f32) -> gs_status;
+    pub fn gs_gaussians_buffer_snapshot(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, out: *mut *mut gs_snapshot) -> gs_status;
+    pub fn gs_snapshot_destroy(snap: *mut gs_snapshot);
+    pub fn gs_snapshot_len(snap: *const gs_snapshot) -> usize;
+    pub fn gs_snapshot_count(snap: *const gs_snapshot) -> u64;
+    pub fn gs_snapshot_bytes(snap: *const gs_snapshot) -> usize;
+    pub fn gs_snapshot_selection(snap: *const gs_snapshot, s: *mut gs_stream, sel: *mut gs_selection, op: u32) -> gs_status;
+    pub fn gs_gaussians_buffer_restore(g: *mut gs_gaussians_buffer, s: *mut gs_stream, snap: *mut gs_snapshot, exchange: i32) -> gs_status;
+    pub fn gs_gaussians_buffer_create_concat(s: *mut gs_stream, srcs: *const *mut gs_gaussians_buffer, sels: *const *const gs_selection, count: u32, out: *mut *mut gs_gaussians_buffer, counts_out: *mut u64) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

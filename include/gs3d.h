@@ -756,6 +756,10 @@ gs_status gs_select_sphere(gs_selection *sel, gs_stream *s, gs_gaussians_buffer 
  * sum order (no reference item) */
 gs_status gs_select_box(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *gaussians,
                         const gs_model_transform_pod *model_transform, const float world_to_box[12], gs_select_op op);
+/* sel = sel op {i : start <= i < start + count}, word-wise (no reference item).  Only enqueues.  Bits at
+ * positions >= n of the last word stay 0 for every op.  After gs_gaussians_buffer_create_concat this is how the pasted part
+ * becomes the selection.  GS_ERR_INVALID_ARGUMENT, with the selection unchanged, when start + count > n or the sum overflows. */
+gs_status gs_select_range(gs_selection *sel, gs_stream *s, size_t start, size_t count, gs_select_op op);
 /* sel = sel op {i : the LAST FRAME of r kept Gaussian i (>= 1 tile: the tiles_touched of gs_renderer_download_projected) and
  * its mean satisfies x0 <= mx < x1, y0 <= my < y1 and — with a plane — mask[floor(my) W + floor(mx)] != 0 (a mean outside
  * the image is then never selected)}.  mask_plane_device: H x W bytes on the device, or NULL.  Gaussians hidden in that
@@ -828,6 +832,60 @@ gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buffer *src, gs
  * NORMALISED quaternion; computed in double, rounded to binary32 (no reference item).
  * GS_ERR_INVALID_ARGUMENT for a null pointer or a non-finite or zero quaternion. */
 gs_status gs_sh_rotation_matrices(const float rot_xyzw[4], float d1[9], float d2[25], float d3[49]);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Snapshots of the selected records, concatenation (no reference item in the     */
+/* core crate: undo and merging are the reference editor's, done there with whole-buffer copies) */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The records of one selection of one buffer, kept on the device with the snapshot's OWN copy of the mask and one u32 per
+ * 1024 Gaussians (the first snapshot rank of each block): the undo entry of an edit (no reference item).
+ * An inverse edit is no substitute: colour and opacity quantise and clamp, SH re-encodes, rotations are not renormalised. */
+typedef struct gs_snapshot gs_snapshot;
+
+/* Captures the records of the Gaussians of `sel` (NULL: all), bytes unchanged, in caller order (DESIGN.md 3.9;
+ * no reference item).  BLOCKING, like gs_gaussians_buffer_create_from_selection: the host sizes the allocation from the
+ * count.  Ordered behind an edit or restore enqueued on another stream.  The snapshot keeps its own mask: later changes to
+ * `sel` do not affect it.  Device memory: count x pod size + 4 ceil(n / 32) + 4 ceil(n / 1024) + 4 bytes, never a
+ * whole-buffer copy for a sparse selection.  An empty selection or a buffer of length 0 gives a valid snapshot of count 0.
+ * GS_ERR_INVALID_ARGUMENT (*out = NULL) for a null argument or a selection whose length differs from the buffer's or that
+ * belongs to another device. */
+gs_status gs_gaussians_buffer_snapshot(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, gs_snapshot **out);
+/* Frees the snapshot; synchronises the device, so a restore still in flight finishes first (DESIGN.md 3.9;
+ * no reference item) */
+void gs_snapshot_destroy(gs_snapshot *snap);
+/* n of the buffer it was taken from (no reference item) */
+size_t gs_snapshot_len(const gs_snapshot *snap);
+/* records it holds (no reference item) */
+uint64_t gs_snapshot_count(const gs_snapshot *snap);
+/* device memory it owns, in bytes (no reference item) */
+size_t gs_snapshot_bytes(const gs_snapshot *snap);
+/* sel = sel op (the snapshot's mask), so that an undo can also restore what was selected (DESIGN.md 3.9;
+ * no reference item).  Only enqueues, like gs_selection_combine.  GS_ERR_INVALID_ARGUMENT when the lengths differ. */
+gs_status gs_snapshot_selection(const gs_snapshot *snap, gs_stream *s, gs_selection *sel, gs_select_op op);
+/* Writes the snapshot's records back to the indices they came from, in one launch (no reference item).
+ * Only ENQUEUES on `s` (NULL: the device's internal stream) and is ordered exactly like gs_gaussians_buffer_edit: behind a
+ * mirror rebuild or an earlier edit / restore on another stream; the next frame of any renderer on any stream sees the
+ * restored records (the whole mirror is stale, as after a TRANSFORM edit).  A Gaussian outside the snapshot's mask keeps
+ * every byte.  The target may be ANY buffer of the same device, layout and length ("paste these records in place");
+ * otherwise GS_ERR_INVALID_ARGUMENT before anything is enqueued.  A snapshot of count 0 launches nothing and dirties
+ * nothing.  exchange != 0: the same launch swaps — the buffer gets the snapshot's records, the snapshot what the buffer
+ * held — so one snapshot is the undo entry and then the redo entry (undo = exchange, redo = exchange again).  The snapshot
+ * must stay alive, and must not be used on OTHER streams, until `s` has passed the launch, as with any buffer. */
+gs_status gs_gaussians_buffer_restore(gs_gaussians_buffer *g, gs_stream *s, gs_snapshot *snap, int32_t exchange);
+/* New buffer holding, for each source in order, the records of sels[i] of srcs[i] (sels == NULL or sels[i] == NULL: all of
+ * that source), caller order kept inside each source, bytes unchanged (no reference item).  A source may
+ * appear more than once: {g, g} with {NULL, sel} duplicates a selection, {a, b} merges two models (bake a model's transform
+ * first with gs_gaussians_buffer_edit).  All sources on one device and of one layout, 1 <= count <= 64, at most 2^32 - 16
+ * records in all: otherwise GS_ERR_INVALID_ARGUMENT and *out = NULL.  counts_out (optional, `count` entries) = the records
+ * taken per source, so the host knows where each part starts.  BLOCKING, exactly once: the counts of all sources come back
+ * in one copy; the copies themselves are only enqueued on `s` (NULL: the device's internal stream) when the call returns.
+ * The new buffer is ordered like an edited one (frames, snapshots and extractions on any stream wait for the copies); the
+ * sources and selections must not be modified on OTHER streams until `s` has passed the copies.  Ordered behind an edit or
+ * restore of a source enqueued on another stream.  The new buffer takes the spatial-order setting of srcs[0]; a total of 0
+ * gives the valid length-0 buffer of gs_gaussians_buffer_create. */
+gs_status gs_gaussians_buffer_create_concat(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
+                                            uint32_t count, gs_gaussians_buffer **out, uint64_t *counts_out);
 
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,

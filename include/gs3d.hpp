@@ -298,6 +298,27 @@ class Buffer {   // wgpu::Buffer + BufferWrapper (src/buffer/mod.rs:17-102); Clo
 
 class Selection;
 
+// ---- snapshots (gs3d.h gs_snapshot; no reference item) --------------------------------
+// The records of one selection of a buffer on the device, with its own copy of the mask: made by
+// GaussiansBuffer::snapshot, written back by GaussiansBuffer::restore.  Move-only; the destructor synchronises the device.
+class Snapshot {
+  public:
+    explicit Snapshot(gs_snapshot *h) : h_(h) {}
+    Snapshot(Snapshot &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Snapshot &operator=(Snapshot &&o) noexcept { std::swap(h_, o.h_); return *this; }
+    Snapshot(const Snapshot &) = delete;
+    Snapshot &operator=(const Snapshot &) = delete;
+    ~Snapshot() { gs_snapshot_destroy(h_); }
+    size_t len() const { return gs_snapshot_len(h_); }          // n of the buffer it was taken from
+    uint64_t count() const { return gs_snapshot_count(h_); }    // records it holds
+    size_t bytes() const { return gs_snapshot_bytes(h_); }      // device memory it owns
+    // sel = sel op (the snapshot's mask); only enqueues
+    void selection(Stream &s, Selection &sel, gs_select_op op = GS_SEL_SET) const;
+    gs_snapshot *raw() const { return h_; }
+  private:
+    gs_snapshot *h_ = nullptr;
+};
+
 template <class G>
 class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
   public:
@@ -332,6 +353,14 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     void edit(Stream &s, const Selection *sel, const gs_edit &e);
     // a new buffer with the records of sel (invert: of its complement), caller order kept; blocking
     GaussiansBuffer extract(Stream &s, const Selection *sel, bool invert = false) const;
+    // snapshots and concatenation (gs3d.h; no reference item).  snapshot: the records of sel (nullptr: all),
+    // blocking.  restore: writes them back, only enqueues; exchange swaps instead (undo, then redo with the same snapshot).
+    Snapshot snapshot(Stream &s, const Selection *sel = nullptr);
+    void restore(Stream &s, Snapshot &snap, bool exchange = false) { check(gs_gaussians_buffer_restore(h_, s.raw(), snap.raw(), exchange ? 1 : 0)); }
+    // a new buffer with the records of sels[i] of srcs[i] (sels empty, or a nullptr entry: all of that source), one source
+    // after the other; counts (optional) receives the records taken per source.  Blocks once, for the counts.
+    static GaussiansBuffer concat(Stream &s, const std::vector<const GaussiansBuffer *> &srcs, const std::vector<const Selection *> &sels = {},
+                                  std::vector<uint64_t> *counts = nullptr);
     gs_gaussians_buffer *raw() const { return h_; }
   private:
     GaussiansBuffer() = default;
@@ -362,10 +391,34 @@ class Selection {
     template <class G>
     void select_box(Stream &s, GaussiansBuffer<G> &g, const gs_model_transform_pod &mt, const float world_to_box[12],
                     gs_select_op op = GS_SEL_SET) { check(gs_select_box(h_, s.raw(), g.raw(), &mt, world_to_box, op)); }
+    // sel = sel op {i : start <= i < start + count}; only enqueues
+    void select_range(Stream &s, size_t start, size_t count, gs_select_op op = GS_SEL_SET) { check(gs_select_range(h_, s.raw(), start, count, op)); }
     gs_selection *raw() const { return h_; }
   private:
     gs_selection *h_ = nullptr;
 };
+
+inline void Snapshot::selection(Stream &s, Selection &sel, gs_select_op op) const { check(gs_snapshot_selection(h_, s.raw(), sel.raw(), op)); }
+template <class G>
+inline Snapshot GaussiansBuffer<G>::snapshot(Stream &s, const Selection *sel) {
+    gs_snapshot *h = nullptr;
+    check(gs_gaussians_buffer_snapshot(h_, s.raw(), sel ? sel->raw() : nullptr, &h));
+    return Snapshot(h);
+}
+template <class G>
+inline GaussiansBuffer<G> GaussiansBuffer<G>::concat(Stream &s, const std::vector<const GaussiansBuffer *> &srcs,
+                                                     const std::vector<const Selection *> &sels, std::vector<uint64_t> *counts) {
+    if (!sels.empty() && sels.size() != srcs.size()) throw std::invalid_argument("concat: one selection per source, or none");
+    std::vector<gs_gaussians_buffer *> g;
+    std::vector<const gs_selection *> m;
+    for (auto *b : srcs) g.push_back(b ? b->raw() : nullptr);
+    for (auto *x : sels) m.push_back(x ? x->raw() : nullptr);
+    if (counts) counts->assign(srcs.size(), 0);
+    GaussiansBuffer b;
+    check(gs_gaussians_buffer_create_concat(s.raw(), g.data(), m.empty() ? nullptr : m.data(), (uint32_t)g.size(), &b.h_,
+                                            counts ? counts->data() : nullptr));
+    return b;
+}
 
 template <class G>
 inline void GaussiansBuffer<G>::edit(Stream &s, const Selection *sel, const gs_edit &e) {

@@ -5,9 +5,16 @@ colour edit (the mirror keeps its spatial order: repack + block bounds) and a tr
 order again).  Wall time per iteration with the stream synchronised behind every frame, median over the iterations; the
 edit alone (kernel only, synchronised) is listed too.  One JSON line per workload.
 
-    python tools/edit_bench.py [--iters 15] [--workloads 1m,10m]
+The history rows at the same scene sizes and shares: `snapshot` of the selection (blocking: scan, allocation
+and gather), `restore` and `exchange` of that snapshot (one launch, synchronised), `concat` of the selection into a new
+buffer (blocking scan, allocation, copy, synchronised), each as ms and as GB/s of the bytes it must move — the selected
+records read and written once, twice for an exchange — next to a device-to-device hipMemcpyAsync of the same records
+(count x pod size read and written) as the yardstick.
+
+    python tools/edit_bench.py [--iters 15] [--workloads 1m,10m] [--rows edit,history]
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -27,7 +34,57 @@ WORKLOADS = {
 SHARES = [0.001, 0.1, 1.0]
 
 
-def run(gs, wl, name, iters, W=1920, H=1080):
+def _median_ms(fn, iters, after=None):
+    ts = []
+    for _ in range(iters + 2):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+        if after is not None:
+            after(out)
+    return float(np.median(ts[2:]))
+
+
+def history_rows(gs, dev, stream, buf, sel, share, iters):
+    """snapshot / restore / exchange / concat of `sel` and the device-to-device copy of the same bytes"""
+    lib = gs._capi.load()
+    memcpy = lib.hipMemcpyAsync          # the runtime the library is linked to
+    memcpy.argtypes, memcpy.restype = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p], C.c_int
+    D2D = 3                              # hipMemcpyDeviceToDevice
+    stream.synchronize()
+    snap = buf.snapshot(stream, sel)
+    count, nbytes = snap.count, snap.count * buf.pod.size
+    a, b = gs.Buffer(dev, size=max(nbytes, 16)), gs.Buffer(dev, size=max(nbytes, 16))
+    dev.synchronize()
+
+    def copy():
+        assert memcpy(b.device_ptr(), a.device_ptr(), nbytes, D2D, stream.native()) == 0
+        stream.synchronize()
+
+    def restore(exchange):
+        buf.restore(stream, snap, exchange=exchange)
+        stream.synchronize()
+
+    def concat():
+        out, _ = gs.GaussiansBuffer.concat(stream, [buf], [sel])
+        stream.synchronize()
+        return out
+
+    ms = dict(copy=_median_ms(copy, iters),
+              snapshot=_median_ms(lambda: buf.snapshot(stream, sel), iters, after=lambda o: o.destroy()),
+              restore=_median_ms(lambda: restore(False), iters),
+              exchange=_median_ms(lambda: restore(True), iters),
+              concat=_median_ms(concat, iters, after=lambda o: o.destroy()))
+    moved = dict(copy=2 * nbytes, snapshot=2 * nbytes, restore=2 * nbytes, exchange=4 * nbytes, concat=2 * nbytes)
+    row = dict(share=share, count=count, record_bytes=nbytes, snapshot_bytes=snap.nbytes)
+    for k, v in ms.items():
+        row[k + "_ms"] = v
+        row[k + "_gbps"] = moved[k] / (v * 1e-3) / 1e9
+    snap.destroy(); a.release(); b.release()
+    return row
+
+
+def run(gs, wl, name, iters, rows, W=1920, H=1080):
     import synth
     dev = gs.Device(0)
     stream = dev.create_stream()
@@ -57,11 +114,13 @@ def run(gs, wl, name, iters, W=1920, H=1080):
         t0 = time.perf_counter()
         frame()
         ts.append((time.perf_counter() - t0) * 1e3)
-    out = dict(workload=name, n=n, width=W, height=H, iters=iters, frame_ms=float(np.median(ts)), cases=[])
+    out = dict(workload=name, n=n, width=W, height=H, iters=iters, frame_ms=float(np.median(ts)), cases=[], history=[])
     rng = np.random.default_rng(1)
     for share in SHARES:
         sel.upload(stream, rng.random(n) < share if share < 1.0 else np.ones(n, bool))
-        for kind, pair in edits.items():
+        if "history" in rows:
+            out["history"].append(history_rows(gs, dev, stream, buf, sel, share, iters))
+        for kind, pair in edits.items() if "edit" in rows else ():
             both, alone = [], []
             for k in range(iters + 2):
                 stream.synchronize()
@@ -87,10 +146,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=15)
     ap.add_argument("--workloads", default="1m,10m")
+    ap.add_argument("--rows", default="edit,history", help="edit: the edit cases; history: snapshot / restore / exchange / concat")
     a = ap.parse_args()
     import wgpu_3dgs_core_amd as gs
     for name in a.workloads.split(","):
-        print(json.dumps(run(gs, WORKLOADS[name], name, a.iters)), flush=True)
+        print(json.dumps(run(gs, WORKLOADS[name], name, a.iters, a.rows.split(","))), flush=True)
 
 
 if __name__ == "__main__":

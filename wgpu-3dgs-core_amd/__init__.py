@@ -864,6 +864,50 @@ class GaussiansBuffer:
         assert out.len() == count.value
         return out
 
+    def snapshot(self, stream, selection=None):
+        """gs_gaussians_buffer_snapshot: a Snapshot of the records of `selection` (None: all), the undo
+        entry of an edit.  Blocking (the host sizes the allocation from the count); the snapshot keeps its own mask."""
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        h = C.c_void_p()
+        _check(_L.gs_gaussians_buffer_snapshot(self._h, stream._h if stream is not None else None,
+                                               selection._h if selection is not None else None, C.byref(h)))
+        return Snapshot(self.device, self.pod, h)
+
+    def restore(self, stream, snapshot, exchange=False):
+        """gs_gaussians_buffer_restore: writes the snapshot's records back to the indices they came from (this buffer, or
+        any buffer of the same layout and length).  Only enqueues, like edit().  exchange=True swaps instead: the snapshot
+        then holds what the buffer held — undo is an exchange, redo the same exchange again."""
+        if not isinstance(snapshot, Snapshot):
+            raise TypeError("snapshot must be a Snapshot, not %s" % type(snapshot).__name__)
+        if snapshot._h is None:
+            raise ValueError("the snapshot was destroyed")
+        _check(_L.gs_gaussians_buffer_restore(self._h, stream._h if stream is not None else None, snapshot._h,
+                                              int(bool(exchange))))
+
+    @staticmethod
+    def concat(stream, buffers, selections=None):
+        """gs_gaussians_buffer_create_concat: (a new GaussiansBuffer with the records of selections[i] of buffers[i], one
+        source after the other in caller order, counts per source).  selections=None, or None for a source: all of it.
+        The same buffer may be given more than once.  Blocks once, for the counts; the copies are enqueued on the stream."""
+        buffers = list(buffers)
+        for b in buffers:
+            if not isinstance(b, GaussiansBuffer):
+                raise TypeError("buffers must be GaussiansBuffers, not %s" % type(b).__name__)
+        sels = [None] * len(buffers) if selections is None else list(selections)
+        if len(sels) != len(buffers):
+            raise ValueError("%d selections for %d buffers" % (len(sels), len(buffers)))
+        for sel in sels:
+            if sel is not None and not isinstance(sel, Selection):
+                raise TypeError("selections must be Selections or None, not %s" % type(sel).__name__)
+        k = len(buffers)
+        src = (C.c_void_p * k)(*[b._h for b in buffers])
+        sel = (C.c_void_p * k)(*[x._h if x is not None else None for x in sels])
+        counts, h = (C.c_uint64 * k)(), C.c_void_p()
+        _check(_L.gs_gaussians_buffer_create_concat(stream._h if stream is not None else None, src, sel, k, C.byref(h), counts))
+        # (no buffer, more than 64, or two layouts: the library's GS_ERR_INVALID_ARGUMENT above)
+        return GaussiansBuffer(buffers[0].device, buffers[0].pod, h), [int(c) for c in counts]
+
     def destroy(self):
         if self._h:
             _L.gs_gaussians_buffer_destroy(self._h)
@@ -1291,9 +1335,55 @@ class Selection:
             raise ValueError("world_to_box takes 12 numbers (3 x 4, column-major)")
         _check(_L.gs_select_box(self._h, stream._h, gaussians._h, C.byref(model_transform), _ptr(b), select_op(op)))
 
+    def select_range(self, stream, start, count, op=SEL_SET):
+        """self = self op {i : start <= i < start + count} (gs_select_range); only enqueues.  After GaussiansBuffer.concat
+        this is how the pasted part becomes the selection."""
+        for name, v in (("start", start), ("count", count)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an integer, not %s" % (name, type(v).__name__))
+            if int(v) < 0:
+                raise ValueError("%s must be >= 0, not %d" % (name, v))
+        op = select_op(op)
+        _check(_L.gs_select_range(self._h, stream._h, int(start), int(count), op))
+
     def destroy(self):
         if self._h:
             _L.gs_selection_destroy(self._h)
+            self._h = None
+
+
+class Snapshot:
+    """gs_snapshot: the records of one selection of a GaussiansBuffer on the device, with its own copy of the mask
+    (DESIGN.md §3.9).  Made by GaussiansBuffer.snapshot, written back by GaussiansBuffer.restore."""
+
+    def __init__(self, device, pod, _handle):
+        self.device, self.pod, self._h = device, pod, _handle
+
+    @property
+    def len(self):
+        """n of the buffer it was taken from"""
+        return _L.gs_snapshot_len(self._h)
+
+    @property
+    def count(self):
+        """records it holds"""
+        return _L.gs_snapshot_count(self._h)
+
+    @property
+    def nbytes(self):
+        """device memory it owns"""
+        return _L.gs_snapshot_bytes(self._h)
+
+    def selection(self, stream, sel, op=SEL_SET):
+        """sel = sel op (the snapshot's mask) (gs_snapshot_selection); only enqueues"""
+        if not isinstance(sel, Selection):
+            raise TypeError("sel must be a Selection, not %s" % type(sel).__name__)
+        op = select_op(op)
+        _check(_L.gs_snapshot_selection(self._h, stream._h, sel._h, op))
+
+    def destroy(self):
+        if self._h:
+            _L.gs_snapshot_destroy(self._h)
             self._h = None
 
 

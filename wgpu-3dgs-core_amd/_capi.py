@@ -221,11 +221,20 @@ SIGNATURES = {
     "gs_selection_count": (i32, [vp, vp, vp]),
     "gs_select_sphere": (i32, [vp, vp, vp, vp, vp, f32, i32]),
     "gs_select_box": (i32, [vp, vp, vp, vp, vp, i32]),
+    "gs_select_range": (i32, [vp, vp, sz, sz, i32]),
     "gs_renderer_select_visible": (i32, [vp, vp, vp, f32, f32, f32, f32, vp, i32]),
     "gs_render_frame_sel": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]),
     "gs_gaussians_buffer_edit": (i32, [vp, vp, vp, vp]),
     "gs_gaussians_buffer_create_from_selection": (i32, [vp, vp, vp, i32, vp, vp]),
     "gs_sh_rotation_matrices": (i32, [vp, vp, vp, vp]),
+    "gs_gaussians_buffer_snapshot": (i32, [vp, vp, vp, vp]),
+    "gs_snapshot_destroy": (None, [vp]),
+    "gs_snapshot_len": (sz, [vp]),
+    "gs_snapshot_count": (u64, [vp]),
+    "gs_snapshot_bytes": (sz, [vp]),
+    "gs_snapshot_selection": (i32, [vp, vp, vp, i32]),
+    "gs_gaussians_buffer_restore": (i32, [vp, vp, vp, i32]),
+    "gs_gaussians_buffer_create_concat": (i32, [vp, vp, vp, u32, vp, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

@@ -691,6 +691,9 @@ struct gs_gaussians_buffer {
     // reused, addresses are) and this build of its mirror order
     uint64_t uid = next_object_id();
     uint64_t order_epoch = 0;
+    // gs_gaussians_buffer_create_concat: the per-block offsets its copies read; they are only enqueued
+    // when the call returns, so the new buffer owns the array
+    void *concat_offsets = nullptr;
     void mark(size_t lo, size_t hi) {
         if (lo >= hi) return;
         partial_since_order += hi - lo;
@@ -956,6 +959,7 @@ extern "C" void gs_gaussians_buffer_destroy(gs_gaussians_buffer *g) {
     if (g->planar) (void)hipFree(g->planar);
     if (g->inv) (void)hipFree(g->inv);
     if (g->block_bounds) (void)hipFree(g->block_bounds);
+    if (g->concat_offsets) (void)hipFree(g->concat_offsets);
     if (g->mirror_ready) (void)hipEventDestroy(g->mirror_ready);
     if (g->edit_done) (void)hipEventDestroy(g->edit_done);
     if (g->order) gs_buffer_release(g->order);
@@ -3924,6 +3928,19 @@ extern "C" gs_status gs_select_box(gs_selection *sel, gs_stream *s, gs_gaussians
     return select_shape(sel, s, g, mt, true, world_to_box, op);
 }
 
+extern "C" gs_status gs_select_range(gs_selection *sel, gs_stream *s, size_t start, size_t count, gs_select_op op) {
+    GS_TRY(check_selection(sel, s));
+    GS_TRY(check_select_op(op));
+    if (start + count < start || start + count > sel->n)
+        return fail(GS_ERR_INVALID_ARGUMENT, start, count, sel->n, "the range [%zu, %zu + %zu) leaves a selection of %zu bits", start, start, count, sel->n);
+    sel->generation = next_object_id();
+    if (!sel->nwords) return GS_OK;
+    hipLaunchKernelGGL(gs::k_sel_range, dim3(sel->grid()), dim3(256), 0, s->s, sel->words, (uint32_t)sel->nwords, (uint32_t)start,
+                       (uint32_t)(start + count), (uint32_t)op);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
 extern "C" gs_status gs_renderer_select_visible(gs_renderer *r, gs_stream *s, gs_selection *sel, float x0, float y0, float x1, float y1,
                                                 const uint8_t *mask, gs_select_op op) {
     if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
@@ -4260,6 +4277,26 @@ extern "C" gs_status gs_gaussians_buffer_edit(gs_gaussians_buffer *g, gs_stream 
     return GS_OK;
 }
 
+// A buffer of `len` > 0 records for a copy that writes every byte of it: allocated WITHOUT the zero fill of
+// gs_buffer_create: that hipMemset runs on the null stream, which the copy's stream is not ordered behind, and would race
+// with the copy.
+static gs_status gaussians_buffer_create_unfilled(gs_device *dev, int sh, int cov, size_t len, gs_gaussians_buffer **out) {
+    void *p = nullptr;
+    const size_t bytes = len * (size_t)gs::pod_bytes(sh, cov);
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, bytes, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+    gs_buffer *b = new gs_buffer();
+    b->dev = dev;
+    b->ptr = p;
+    b->bytes = bytes;
+    b->owned = true;
+    b->refs.store(1);
+    gs_status rc = gs_gaussians_buffer_from_buffer(b, (gs_sh_config)sh, (gs_cov3d_config)cov, out);
+    gs_buffer_release(b);
+    return rc;
+}
+
 extern "C" gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel,
                                                                int32_t invert, gs_gaussians_buffer **out, uint64_t *count_out) {
     if (!src || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
@@ -4298,23 +4335,7 @@ extern "C" gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buff
     }
     gs_gaussians_buffer *dst = nullptr;
     if (rc == GS_OK && total) {
-        // The copy below writes every byte of the new buffer, so it is allocated WITHOUT the zero fill of gs_buffer_create:
-        // that hipMemset runs on the null stream, which `st` is not ordered behind, and would race with the copy.
-        void *p = nullptr;
-        const size_t bytes = (size_t)total * pod_stride(src);
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            rc = fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, bytes, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-        } else {
-            gs_buffer *b = new gs_buffer();
-            b->dev = dev;
-            b->ptr = p;
-            b->bytes = bytes;
-            b->owned = true;
-            b->refs.store(1);
-            rc = gs_gaussians_buffer_from_buffer(b, (gs_sh_config)src->sh, (gs_cov3d_config)src->cov, &dst);
-            gs_buffer_release(b);
-        }
+        rc = gaussians_buffer_create_unfilled(dev, src->sh, src->cov, total, &dst);
     } else if (rc == GS_OK) {
         rc = gs_gaussians_buffer_create(dev, (gs_sh_config)src->sh, (gs_cov3d_config)src->cov, nullptr, 0, &dst);
     }
@@ -4333,5 +4354,251 @@ extern "C" gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buff
     dst->spatial = src->spatial;
     *out = dst;
     if (count_out) *count_out = total;
+    return GS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// snapshots of the selected records, concatenation
+// ------------------------------------------------------------------------------------------------
+
+// The records of one selection of one buffer, with what restoring them needs: its own copy of the mask and the first
+// snapshot rank of every 1024-block (the exclusive scan of the per-block counts).
+struct gs_snapshot {
+    gs_device *dev;
+    int sh, cov;
+    size_t n, nwords, nblocks;
+    uint64_t count;
+    uint32_t *meta;          // device: nwords mask words, nblocks offsets, the scan's total (one allocation)
+    size_t meta_bytes;
+    void *records;           // device: count records; null while count == 0
+    const uint32_t *words() const { return meta; }
+    uint32_t *offsets() const { return meta + nwords; }
+    uint32_t *total() const { return meta + nwords + nblocks; }
+};
+
+extern "C" void gs_snapshot_destroy(gs_snapshot *snap) {
+    if (!snap) return;
+    (void)hipSetDevice(snap->dev->ordinal);
+    if (snap->records) (void)hipFree(snap->records);      // (synchronises the device: a restore in flight finishes first)
+    if (snap->meta) (void)hipFree(snap->meta);
+    delete snap;
+}
+
+extern "C" size_t gs_snapshot_len(const gs_snapshot *snap) { return snap ? snap->n : 0; }
+extern "C" uint64_t gs_snapshot_count(const gs_snapshot *snap) { return snap ? snap->count : 0; }
+extern "C" size_t gs_snapshot_bytes(const gs_snapshot *snap) {
+    return snap ? (size_t)snap->count * (size_t)gs::pod_bytes(snap->sh, snap->cov) + snap->meta_bytes : 0;
+}
+
+extern "C" gs_status gs_gaussians_buffer_snapshot(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, gs_snapshot **out) {
+    if (out) *out = nullptr;
+    if (!g || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    GS_TRY(check_buffer_selection(g, s, sel));
+    const size_t len = gs_gaussians_buffer_len(g);
+    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
+    gs_device *dev = g->buf->dev;
+    GS_TRY(use_device(dev));
+    hipStream_t st = stream_of(dev, s);
+    // an edit enqueued on another stream still writes the records
+    if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
+    gs_snapshot *snap = new gs_snapshot();
+    snap->dev = dev;
+    snap->sh = g->sh;
+    snap->cov = g->cov;
+    snap->n = len;
+    snap->nwords = (len + 31) / 32;
+    snap->nblocks = (len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK;
+    snap->count = 0;
+    snap->records = nullptr;
+    snap->meta_bytes = (snap->nwords + snap->nblocks + 1) * 4;
+    hipError_t e = hipMalloc((void **)&snap->meta, snap->meta_bytes);
+    if (e != hipSuccess) {
+        delete snap;
+        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "snapshot allocation failed: %s",
+                    hipGetErrorString(e));
+    }
+    const uint32_t n = (uint32_t)len, nwords = (uint32_t)snap->nwords, nblocks = (uint32_t)snap->nblocks;
+    const uint32_t nc = (uint32_t)(pod_stride(g) / 16);
+    uint32_t total = 0;
+    gs_status rc = GS_OK;
+    if (n) {
+        // the mask is copied first and everything below reads the copy: the snapshot does not depend on `sel` afterwards
+        hipLaunchKernelGGL(gs::k_snapshot_mask, dim3((nwords + 255u) / 256u), dim3(256), 0, st, snap->meta,
+                           sel ? (const uint32_t *)sel->words : nullptr, nwords, n);
+        // the per-block counts land where their exclusive scan goes (k_scan_chunks reads a value before it writes its slot)
+        hipLaunchKernelGGL(gs::k_extract_block_counts, dim3((nblocks * 32u + 255u) / 256u), dim3(256), 0, st, snap->words(), n, 0u, nblocks,
+                           snap->offsets());
+        gs::ScanJob job{snap->offsets(), snap->offsets(), snap->total(), nblocks};
+        hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
+        e = hipGetLastError();
+        // sizing the records needs the count on the host
+        if (e == hipSuccess) e = hipMemcpyAsync(&total, snap->total(), 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
+        else if (total > n) rc = fail(GS_ERR_HIP, total, n, 0, "selection scan returned %u of %u Gaussians", total, n);
+    }
+    if (rc == GS_OK && total) {
+        const size_t bytes = (size_t)total * pod_stride(g);
+        e = hipMalloc(&snap->records, bytes);
+        if (e != hipSuccess) {
+            snap->records = nullptr;
+            rc = fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, bytes, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+        } else {
+            hipLaunchKernelGGL(gs::k_extract_copy, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)g->buf->ptr,
+                               (uint4 *)snap->records, snap->words(), n, 0u, (const uint32_t *)snap->offsets(), nc, total);
+            e = hipGetLastError();
+            // the call is blocking anyway; a restore on any stream may follow at once
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "snapshot failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (rc != GS_OK) {
+        gs_snapshot_destroy(snap);
+        return rc;
+    }
+    snap->count = total;
+    *out = snap;
+    return GS_OK;
+}
+
+extern "C" gs_status gs_snapshot_selection(const gs_snapshot *snap, gs_stream *s, gs_selection *sel, gs_select_op op) {
+    if (!snap) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    GS_TRY(check_selection(sel, s));
+    GS_TRY(check_select_op(op));
+    if (snap->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (snap->n != sel->n) return fail(GS_ERR_INVALID_ARGUMENT, snap->n, sel->n, 0, "the snapshot covers %zu Gaussians, the selection has %zu bits", snap->n, sel->n);
+    return selection_combine_words(sel, s->s, op, snap->words());
+}
+
+extern "C" gs_status gs_gaussians_buffer_restore(gs_gaussians_buffer *g, gs_stream *s, gs_snapshot *snap, int32_t exchange) {
+    if (!g || !snap) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    gs_device *dev = g->buf->dev;
+    if (snap->dev != dev || (s && s->dev != dev)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (snap->sh != g->sh || snap->cov != g->cov)
+        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the snapshot was taken from a buffer of another layout");
+    const size_t len = gs_gaussians_buffer_len(g);
+    if (snap->n != len) return fail(GS_ERR_INVALID_ARGUMENT, snap->n, len, 0, "the snapshot covers %zu Gaussians, the buffer has %zu", snap->n, len);
+    if (!snap->count) return GS_OK;
+    GS_TRY(use_device(dev));
+    hipStream_t st = stream_of(dev, s);
+    // a mirror rebuild in flight on another stream still reads the records; an earlier edit or restore on another stream
+    // still writes them
+    if (g->mirror_ready && st != g->mirror_stream) GS_HIP(hipStreamWaitEvent(st, g->mirror_ready, 0));
+    if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
+    const uint32_t n = (uint32_t)len, nc = (uint32_t)(pod_stride(g) / 16), count = (uint32_t)snap->count;
+    if (exchange)
+        hipLaunchKernelGGL(gs::k_restore<true>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records,
+                           snap->words(), n, (const uint32_t *)snap->offsets(), nc, count);
+    else
+        hipLaunchKernelGGL(gs::k_restore<false>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records,
+                           snap->words(), n, (const uint32_t *)snap->offsets(), nc, count);
+    GS_HIP(hipGetLastError());
+    if (!g->edit_done) GS_HIP(hipEventCreateWithFlags(&g->edit_done, hipEventDisableTiming));
+    GS_HIP(hipEventRecord(g->edit_done, st));
+    g->edit_stream = st;
+    // the host does not know whether the restored records moved: the whole mirror is stale, as after a TRANSFORM edit
+    g->mark_all();
+    return GS_OK;
+}
+
+extern "C" gs_status gs_gaussians_buffer_create_concat(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
+                                                       uint32_t count, gs_gaussians_buffer **out, uint64_t *counts_out) {
+    if (out) *out = nullptr;
+    if (!srcs || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (count < 1u || count > 64u) return fail(GS_ERR_INVALID_ARGUMENT, count, 0, 0, "a concatenation takes 1 to 64 sources, not %u", (unsigned)count);
+    if (counts_out) std::memset(counts_out, 0, (size_t)count * sizeof(uint64_t));
+    size_t nblocks_all = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        const gs_gaussians_buffer *g = srcs[i];
+        if (!g) return fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "source %u is null", (unsigned)i);
+        if (g->buf->dev != srcs[0]->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "objects belong to different devices");
+        if (g->sh != srcs[0]->sh || g->cov != srcs[0]->cov)
+            return fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "source %u has another layout than source 0", (unsigned)i);
+        GS_TRY(check_buffer_selection(g, s, sels ? sels[i] : nullptr));
+        const size_t len = gs_gaussians_buffer_len(g);
+        if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
+        nblocks_all += (len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK;
+    }
+    gs_device *dev = srcs[0]->buf->dev;
+    const int sh = srcs[0]->sh, cov = srcs[0]->cov;
+    GS_TRY(use_device(dev));
+    hipStream_t st = stream_of(dev, s);
+    // one array for all sources: the per-block offsets of source i from block0[i] on, then one total per source
+    uint32_t *scan = nullptr;
+    hipError_t e = hipMalloc((void **)&scan, (nblocks_all + 64) * 4);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+    uint32_t *totals_dev = scan + nblocks_all;
+    uint32_t totals[64] = {};
+    size_t block0[64];
+    e = hipMemsetAsync(totals_dev, 0, 64 * 4, st);
+    size_t b0 = 0;
+    for (uint32_t i = 0; i < count && e == hipSuccess; i++) {
+        gs_gaussians_buffer *g = srcs[i];
+        const uint32_t n = (uint32_t)gs_gaussians_buffer_len(g), nblocks = (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
+        block0[i] = b0;
+        b0 += nblocks;
+        if (!n) continue;
+        // an edit enqueued on another stream still writes the records
+        if (g->edit_done && st != g->edit_stream) e = hipStreamWaitEvent(st, g->edit_done, 0);
+        if (e != hipSuccess) break;
+        const uint32_t *words = sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr;
+        uint32_t *offsets = scan + block0[i];
+        hipLaunchKernelGGL(gs::k_extract_block_counts, dim3((nblocks * 32u + 255u) / 256u), dim3(256), 0, st, words, n, 0u, nblocks, offsets);
+        gs::ScanJob job{offsets, offsets, totals_dev + i, nblocks};       // in place, as in the snapshot
+        hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
+        e = hipGetLastError();
+    }
+    // sizing the new buffer needs the totals on the host: the one round trip of the call
+    if (e == hipSuccess) e = hipMemcpyAsync(totals, totals_dev, (size_t)count * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    gs_status rc = GS_OK;
+    uint64_t total = 0;
+    if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
+    for (uint32_t i = 0; i < count && rc == GS_OK; i++) {
+        const size_t len = gs_gaussians_buffer_len(srcs[i]);
+        if (totals[i] > len) rc = fail(GS_ERR_HIP, totals[i], len, 0, "selection scan returned %u of %zu Gaussians", totals[i], len);
+        total += totals[i];
+    }
+    if (rc == GS_OK && total > 0xfffffff0ull)
+        rc = fail(GS_ERR_INVALID_ARGUMENT, total, 0, 0, "the concatenation would hold %llu Gaussians", (unsigned long long)total);
+    gs_gaussians_buffer *dst = nullptr;
+    if (rc == GS_OK && total) rc = gaussians_buffer_create_unfilled(dev, sh, cov, (size_t)total, &dst);
+    else if (rc == GS_OK) rc = gs_gaussians_buffer_create(dev, (gs_sh_config)sh, (gs_cov3d_config)cov, nullptr, 0, &dst);
+    if (rc == GS_OK && total) {
+        const uint32_t nc = (uint32_t)(pod_stride(dst) / 16);
+        uint64_t first = 0;      // where the part of source i starts in the new buffer
+        for (uint32_t i = 0; i < count; i++) {
+            if (!totals[i]) continue;
+            const uint32_t n = (uint32_t)gs_gaussians_buffer_len(srcs[i]);
+            const uint32_t *words = sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr;
+            // k_extract_copy stays inside `total` records from its destination pointer: the part of this source
+            hipLaunchKernelGGL(gs::k_extract_copy, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)srcs[i]->buf->ptr,
+                               (uint4 *)dst->buf->ptr + first * nc, words, n, 0u, (const uint32_t *)(scan + block0[i]), nc, totals[i]);
+            first += totals[i];
+        }
+        // The copies are only enqueued: the call has blocked once, for the totals.  The new buffer is ordered like an edited
+        // one (frames, snapshots and extractions on other streams wait for the copies) and keeps the offsets they read.
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&dst->edit_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventRecord(dst->edit_done, st);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "concatenation failed: %s", hipGetErrorString(e));
+        } else {
+            dst->edit_stream = st;
+            dst->concat_offsets = scan;
+            scan = nullptr;
+        }
+    }
+    if (scan) (void)hipFree(scan);
+    if (rc != GS_OK) {
+        if (dst) gs_gaussians_buffer_destroy(dst);
+        return rc;
+    }
+    dst->spatial = srcs[0]->spatial;
+    *out = dst;
+    if (counts_out)
+        for (uint32_t i = 0; i < count; i++) counts_out[i] = totals[i];
     return GS_OK;
 }

@@ -1,5 +1,5 @@
-// gs_edit_kernels.h — edits of the selected Gaussians in place and their extraction into a new buffer (include/gs3d.h
-// gs_gaussians_buffer_edit / _create_from_selection).  No reference item: the reference's editor does
+// gs_edit_kernels.h — edits of the selected Gaussians in place, their extraction into a new buffer (include/gs3d.h
+// gs_gaussians_buffer_edit / _create_from_selection) and snapshots of them (_snapshot / _restore; §3.9).  No reference item: the reference's editor does
 // this with compute passes over the Gaussian buffer; the core crate has none.
 //
 // The codecs are the library's own: records are decoded with gs_kernel_lib.h (gaussian_unpack_sh / _cov3d, unorm8) and
@@ -225,6 +225,53 @@ __global__ __launch_bounds__(256) void k_extract_copy(const uint4 *__restrict__ 
         if (!((mask >> r) & 1ull)) continue;
         const uint32_t rank = (uint32_t)__popcll(mask & ((1ull << r) - 1ull));
         if (base + rank < total) dst[(base + rank) * nc + c] = s[q];
+    }
+}
+
+// ---- snapshots of the selected records (gs_gaussians_buffer_snapshot / _restore) -------------------
+
+// the mask a snapshot keeps: the selection's words (null: all), bits >= n cleared
+__global__ __launch_bounds__(256) void k_snapshot_mask(uint32_t *__restrict__ dst, const uint32_t *__restrict__ words,
+                                                       uint32_t nwords, uint32_t n) {
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w < nwords) dst[w] = extract_word(words, w, n, 0u);
+}
+
+// The reverse of k_extract_copy: one wave per 64 target Gaussians.  Lanes 0..31 hold the 32 words of the SNAPSHOT'S mask
+// for the wave's 1024-block; their popcount prefix plus offsets[block] (kept from the snapshot's scan) is the rank of the
+// wave's first record in the snapshot.  The records of the wave's selected Gaussians are contiguous on both sides: lane
+// after lane takes chunk after chunk.  EXCHANGE: the buffer gets the snapshot's chunk and the snapshot what the buffer
+// held; a lane loads both before it stores either.  A wave without a selected Gaussian returns after reading its words.
+// `count` is the snapshot's length: nothing past it is read or written.
+template <bool EXCHANGE>
+__global__ __launch_bounds__(256) void k_restore(uint4 *__restrict__ aos, uint4 *__restrict__ snap,
+                                                 const uint32_t *__restrict__ words, uint32_t n,
+                                                 const uint32_t *__restrict__ offsets, uint32_t nc, uint32_t count) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t i0 = blockIdx.x * 256u + (threadIdx.x - lane);      // first Gaussian of the wave
+    if (i0 >= n) return;
+    const uint32_t block = i0 / PLANAR_BLOCK, wsel = (i0 % PLANAR_BLOCK) >> 5;
+    const uint32_t word = lane < 32u ? extract_word(words, block * 32u + lane, n, 0u) : 0u;
+    const uint32_t pc = (uint32_t)__popc(word);
+    const uint32_t inc = wave_inclusive_scan(pc, lane);
+    const uint32_t lo = (uint32_t)__shfl((int)word, (int)wsel), hi = (uint32_t)__shfl((int)word, (int)wsel + 1);
+    const uint32_t before = (uint32_t)__shfl((int)(inc - pc), (int)wsel);
+    const uint64_t mask = (uint64_t)lo | ((uint64_t)hi << 32);
+    if (mask == 0ull) return;
+    const uint64_t base = (uint64_t)offsets[block] + before;
+    uint4 *t = aos + (uint64_t)i0 * nc;
+    for (uint32_t q = lane; q < 64u * nc; q += 64u) {
+        const uint32_t r = q / nc, c = q - r * nc;
+        if (!((mask >> r) & 1ull)) continue;
+        const uint64_t rank = base + (uint32_t)__popcll(mask & ((1ull << r) - 1ull));
+        if (rank >= count) continue;
+        uint4 *sp = snap + rank * nc + c;
+        const uint4 v = *sp;
+        if constexpr (EXCHANGE) {
+            const uint4 old = t[q];
+            *sp = old;
+        }
+        t[q] = v;
     }
 }
 

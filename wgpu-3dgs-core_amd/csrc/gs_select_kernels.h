@@ -31,6 +31,18 @@ __global__ __launch_bounds__(256) void k_sel_combine(uint32_t *__restrict__ dst,
         dst[w] = sel_apply(dst[w], src[w], op);
 }
 
+// dst = dst op {i : start <= i < end} over whole words; end <= n, so no bit at a position >= n is ever set
+__global__ __launch_bounds__(256) void k_sel_range(uint32_t *__restrict__ words, uint32_t nwords, uint32_t start, uint32_t end,
+                                                   uint32_t op) {
+    for (uint32_t w = blockIdx.x * 256u + threadIdx.x; w < nwords; w += gridDim.x * 256u) {
+        const uint64_t w0 = (uint64_t)w * 32u;
+        const uint64_t a = start > w0 ? start - w0 : 0u, b = end > w0 ? end - w0 : 0u;      // the range inside the word: [a, min(b, 32))
+        uint32_t bits = 0u;
+        if (a < 32u && b > a) bits = (b >= 32u ? 0xffffffffu : (1u << b) - 1u) & ~((1u << a) - 1u);
+        words[w] = sel_apply(words[w], bits, op);
+    }
+}
+
 // popcount of the whole mask, added to *total (cleared by the host in stream order)
 __global__ __launch_bounds__(256) void k_sel_count(const uint32_t *__restrict__ words, uint32_t nwords,
                                                    unsigned long long *__restrict__ total) {
