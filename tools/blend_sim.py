@@ -77,3 +77,26 @@ for hy in range(2):
             lists.append(grp_sum(m))
     new82+=np.maximum.reduce(lists).sum(); ideal82+=sum(l.sum() for l in lists)/8
 print('8x2 eighth-waves (max of 8 lists):',new82,'ratio',new82/cur,' ideal:',ideal82/cur)
+# --- G = 8 (GS3D_BLEND_GROUPS=8) beside G = 4: wave-steps against the staging batch, and what a quadrant pre-test would see ---
+def grp(mask,g):
+    u,inv=np.unique(g,return_inverse=True); return np.bincount(inv,weights=mask,minlength=len(u))
+for name,bw,bh,nx,ny in (('8x4 (G=4)',8,4,2,2),('4x4 (G=8)',4,4,4,2)):
+    masks={}
+    for hy in range(2):
+        for by in range(ny):
+            for bx in range(nx):
+                masks[(hy,by,bx)]=touches(x0+bw*bx,x0+bw*bx+bw-1,y0+8*hy+bh*by,y0+8*hy+bh*by+bh-1)
+    tot=sum(m.sum() for m in masks.values())
+    print(name,'block entries',tot,'per pair',tot/D,' ideal wave-steps (entries / lists per wave)',tot/(nx*ny))
+    for B in (128,256,512,10**9):
+        gb=tile*100000+pos//B
+        s=0
+        for hy in range(2):
+            s+=np.maximum.reduce([grp(masks[(hy,by,bx)],gb) for by in range(ny) for bx in range(nx)]).sum()
+        print('  batch',B if B<10**9 else 'whole tile','wave-steps (max of the lists)',s,' / ideal',s/(tot/(nx*ny)))
+# quadrant pre-test (8x8): pass rate per pair, and how often a staging wave (64 consecutive pairs of a tile) has an EMPTY quadrant ballot
+wv=tile*100000+pos//64
+for qy in range(2):
+    for qx in range(2):
+        m=q[(qy,qx)]; per_wave=grp(m,wv)
+        print('quadrant',(qy,qx),'pass rate %.3f'%m.mean(),' staging waves with an empty ballot %.3f'%(per_wave==0).mean())

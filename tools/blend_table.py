@@ -46,13 +46,13 @@ CLASSES = OrderedDict([
 ])
 
 
-def kernel_isa():
+def kernel_isa(groups=4):
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "gs3d.s")
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-o", out, SRC], check=True, stderr=subprocess.DEVNULL)
         lines = open(out).read().split("\n")
-    # the plain single-round instantiation <0, 4, false, false> (the AUX ones share the prefix)
-    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN2gs15k_blend_groupedILi0ELi4ELb0ELb0EJEE"))
+    # the plain single-round instantiation <0, G, false, false> (the AUX ones share the prefix)
+    start = next(i for i, l in enumerate(lines) if l.startswith("_ZN2gs15k_blend_groupedILi0ELi%dELb0ELb0EJEE" % groups))
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith(".Lfunc_end"))
     return lines[start:end]
 
@@ -108,9 +108,14 @@ def main():
     ap.add_argument("--valu-log", required=True, help="output of tools/mb/mb_valu on the GPU box")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--waves", default="7w")
+    ap.add_argument("--groups", type=int, default=4, choices=[2, 4, 8],
+                    help="lane groups of the instantiation to price (8: write its summary elsewhere with --json-out; "
+                         "profiles/blend_issue.json is the G = 4 loop's, which bench.py reads)")
     ap.add_argument("--json-out", default=os.path.join(ROOT, "profiles", "blend_issue.json"),
                     help="machine-readable summary for bench.py's `blend` object")
     args = ap.parse_args()
+    if args.groups != 4 and args.json_out == ap.get_default("json_out"):
+        args.json_out = None
 
     cost = {}
     for line in open(args.valu_log):
@@ -120,7 +125,7 @@ def main():
         name = m.group(1).strip()
         per = dict((k, float(v)) for k, v in re.findall(r"(\dw):\s+([0-9.]+) ns/inst", line))
         cost[name] = per
-    body = kernel_isa()
+    body = kernel_isa(args.groups)
     label, blocks = inner_loop(body)
     rare = [n for n, b in blocks if any(x.startswith("s_bcnt1") for x in b)]
     counts, cal_of = Counter(), {}
@@ -135,7 +140,7 @@ def main():
     steps_per_trip = 2.0
     pmc = json.load(open(args.pmc)).get("blend_1m", {}) if os.path.exists(args.pmc) else {}
     clock_ghz = None
-    print("# k_blend_grouped<Splat, 4>: issue cost of the blend loop, class by class\n")
+    print("# k_blend_grouped<Splat, %d>: issue cost of the blend loop, class by class\n" % args.groups)
     print("Inner loop `%s` of the ISA hipcc emits for gfx950 (two blend steps per trip; the blocks that only run when a "
           "pixel reaches T < 1e-4 in that step are left out: %s).  Cost = ns per wave-instruction per SIMD of an "
           "independent stream of THAT class at %s per SIMD (tools/mb/mb_valu.hip, `%s`).\n" % (
@@ -168,7 +173,7 @@ def main():
     if missing:
         print("(no calibration stream found for: %s)\n" % sorted(set(missing)))
     if args.json_out:
-        json.dump(dict(kernel="k_blend_grouped<Splat,4>", valu_insts_per_step=valu_per_step, priced_ns_per_step=total_ns,
+        json.dump(dict(kernel="k_blend_grouped<Splat,%d>" % args.groups, valu_insts_per_step=valu_per_step, priced_ns_per_step=total_ns,
                        ns_per_valu_inst_loop_mix=total_ns / valu_per_step, waves_per_simd=args.waves,
                        classes={k: v / steps_per_trip for k, v in counts.items()},
                        source="tools/blend_table.py: loop ISA counted by class, each class priced with its own stream of "

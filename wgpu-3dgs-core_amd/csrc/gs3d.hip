@@ -2895,30 +2895,33 @@ static gs_status arm_rank_watchdog(Frame &F) {
 static gs_status stage_blend(Frame &F, uint32_t round) {
     gs_renderer *r = F.r;
     if (!F.nums.band_tiles) return GS_OK;
-    const int groups = switches().blend_groups;
+    const int groups = gsp::plan_blend_groups(switches(), round);
     const uint32_t mode = F.mode;
     typedef void (*blend_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
                              const gs::FrameState *, gs::TileKeys);
-    static const blend_fn tbl[3][3] = {
-        {gs::k_blend<0>, gs::k_blend_grouped<0, 2>, gs::k_blend_grouped<0, 4>},
-        {gs::k_blend<1>, gs::k_blend_grouped<1, 2>, gs::k_blend_grouped<1, 4>},
-        {gs::k_blend<2>, gs::k_blend_grouped<2, 2>, gs::k_blend_grouped<2, 4>}};
-    static const blend_fn tbl_rounds[3][2] = {{gs::k_blend_grouped<0, 2, true>, gs::k_blend_grouped<0, 4, true>},
-                                              {gs::k_blend_grouped<1, 2, true>, gs::k_blend_grouped<1, 4, true>},
-                                              {gs::k_blend_grouped<2, 2, true>, gs::k_blend_grouped<2, 4, true>}};
+    static const blend_fn tbl[3][4] = {
+        {gs::k_blend<0>, gs::k_blend_grouped<0, 2>, gs::k_blend_grouped<0, 4>, gs::k_blend_grouped<0, 8>},
+        {gs::k_blend<1>, gs::k_blend_grouped<1, 2>, gs::k_blend_grouped<1, 4>, gs::k_blend_grouped<1, 8>},
+        {gs::k_blend<2>, gs::k_blend_grouped<2, 2>, gs::k_blend_grouped<2, 4>, gs::k_blend_grouped<2, 8>}};
+    static const blend_fn tbl_rounds[3][3] = {
+        {gs::k_blend_grouped<0, 2, true>, gs::k_blend_grouped<0, 4, true>, gs::k_blend_grouped<0, 8, true>},
+        {gs::k_blend_grouped<1, 2, true>, gs::k_blend_grouped<1, 4, true>, gs::k_blend_grouped<1, 8, true>},
+        {gs::k_blend_grouped<2, 2, true>, gs::k_blend_grouped<2, 4, true>, gs::k_blend_grouped<2, 8, true>}};
+    // column of the grouped tables: 2 -> 8x8 blocks, 8 -> 4x4 blocks, anything else -> 8x4 blocks (an aux frame: also for 1)
+    const int gcol = groups == 2 ? 0 : groups == 8 ? 2 : 1;
     if (round != 0u && groups == 1) return fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
     F.tile_keys.round = round;
     if (F.aux) {
         // the depth / pick planes ride in the grouped blend (G = 4 where the plain frame would take k_blend)
         typedef void (*aux_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
                                const gs::FrameState *, gs::TileKeys, gs::AuxIO);
-        static const aux_fn tbl_aux[2][3][2] = {
-            {{gs::k_blend_grouped<0, 2, false, true>, gs::k_blend_grouped<0, 4, false, true>},
-             {gs::k_blend_grouped<1, 2, false, true>, gs::k_blend_grouped<1, 4, false, true>},
-             {gs::k_blend_grouped<2, 2, false, true>, gs::k_blend_grouped<2, 4, false, true>}},
-            {{gs::k_blend_grouped<0, 2, true, true>, gs::k_blend_grouped<0, 4, true, true>},
-             {gs::k_blend_grouped<1, 2, true, true>, gs::k_blend_grouped<1, 4, true, true>},
-             {gs::k_blend_grouped<2, 2, true, true>, gs::k_blend_grouped<2, 4, true, true>}}};
+        static const aux_fn tbl_aux[2][3][3] = {
+            {{gs::k_blend_grouped<0, 2, false, true>, gs::k_blend_grouped<0, 4, false, true>, gs::k_blend_grouped<0, 8, false, true>},
+             {gs::k_blend_grouped<1, 2, false, true>, gs::k_blend_grouped<1, 4, false, true>, gs::k_blend_grouped<1, 8, false, true>},
+             {gs::k_blend_grouped<2, 2, false, true>, gs::k_blend_grouped<2, 4, false, true>, gs::k_blend_grouped<2, 8, false, true>}},
+            {{gs::k_blend_grouped<0, 2, true, true>, gs::k_blend_grouped<0, 4, true, true>, gs::k_blend_grouped<0, 8, true, true>},
+             {gs::k_blend_grouped<1, 2, true, true>, gs::k_blend_grouped<1, 4, true, true>, gs::k_blend_grouped<1, 8, true, true>},
+             {gs::k_blend_grouped<2, 2, true, true>, gs::k_blend_grouped<2, 4, true, true>, gs::k_blend_grouped<2, 8, true, true>}}};
         gs::AuxIO aio;
         aio.depth = F.aux->depth;
         aio.pick = F.aux->pick;
@@ -2927,12 +2930,12 @@ static gs_status stage_blend(Frame &F, uint32_t round) {
         aio.depth_keys = (const uint32_t *)r->depth.ptr;
         aio.block_list = r->list_mode ? (const uint32_t *)r->block_list.ptr : nullptr;
         aio.order = r->last_order ? (const uint32_t *)r->last_order->ptr : nullptr;
-        hipLaunchKernelGGL(tbl_aux[round != 0u ? 1 : 0][mode][groups == 2 ? 0 : 1], dim3(F.nums.band_tiles), dim3(gs::BLEND_THREADS), 0, F.st,
+        hipLaunchKernelGGL(tbl_aux[round != 0u ? 1 : 0][mode][gcol], dim3(F.nums.band_tiles), dim3(gs::BLEND_THREADS), 0, F.st,
                            (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
                            (const uint32_t *)r->recs.ptr, F.fc, (float4 *)F.rgba, (const gs::FrameState *)r->state.ptr, F.tile_keys,
                            aio);
     } else {
-        const blend_fn blend = round != 0u ? tbl_rounds[mode][groups == 2 ? 0 : 1] : tbl[mode][groups == 1 ? 0 : groups == 2 ? 1 : 2];
+        const blend_fn blend = round != 0u ? tbl_rounds[mode][gcol] : tbl[mode][groups == 1 ? 0 : 1 + gcol];
         hipLaunchKernelGGL(blend, dim3(F.nums.band_tiles), dim3(gs::BLEND_THREADS), 0, F.st,
                            (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
                            (const uint32_t *)r->recs.ptr, F.fc, (float4 *)F.rgba, (const gs::FrameState *)r->state.ptr, F.tile_keys);

@@ -34,7 +34,7 @@ struct Switches {
     int tile_sort_large = -1;       // GS3D_TILE_SORT_LARGE=0/1: 4096- / 8192-key tiles for the 16-bit tile keys
     int tile_masks = -1;            // GS3D_TILE_MASKS=0/1: tile rect version 3 / 4
     int depth_msd = -1;             // GS3D_DEPTH_MSD=0/1: LSD / MSD-first depth sort
-    int blend_groups = 4;           // GS3D_BLEND_GROUPS = 1 (half-tile lists), 2 (8x8 blocks) or 4 (8x4 blocks, default)
+    int blend_groups = 0;           // GS3D_BLEND_GROUPS = 1 (half-tile lists), 2 (8x8 blocks), 4 (8x4 blocks) or 8 (4x4 blocks); 0: plan_blend_groups
     int rounds = -1;                // GS3D_ROUNDS=0/1: one round / two
     long round1 = 0;                // GS3D_ROUND1=<k>: Gaussians of round 1
     int round_partition = -1;       // GS3D_ROUND_PARTITION=0/1: two-round frames sort each round on its own
@@ -434,6 +434,18 @@ inline void plan_pairs(const History &h, const FrameNums &f, uint64_t pair_capac
 // 1 M and 10 M, +10 us at 4K, +12 us at 50 M against 6.8 / 10.5 / 35 / 19 us of range kernel saved: frames
 // +1.5 % at 1 M, +-0 at 10 M, -0.5 % at 50 M, -2.3 % at 4K.  It is taken where it pays: images of more than
 // 16384 tiles, where neither stand-alone kernel is cheap (GS3D_RANGES_IN_BLEND=0/1 forces).
+// Lane groups per wave of the grouped blend (k_blend_grouped<MODE, G>), unless GS3D_BLEND_GROUPS pins them.  4x4 blocks (G = 8)
+// walk 15 % fewer wave-steps than 8x4 blocks (G = 4) and test every staged splat against 16 blocks instead of 8.  Measured,
+// same box, alternating processes.  Single-round frames, 1 M at 1080p, 3 frames in flight, 5 pairs: 0.2508-0.2550 ms against
+// 0.2623-0.2654; one stream: blend 185.8 against 197.3 us, SQ_INSTS_VALU 0.977e8 against 1.02e8.  Two-round frames, whose deep
+// tiles skip most steps with finished pixels, so that the staging weighs more (blend stage, G = 4 / G = 8): 10 M 0.2122 / 0.2125,
+// 10 M at 4K 0.5131 / 0.5245, 50 M 0.2316 / 0.2438 ms.  So: 8 on single-round frames, 4 on the rounds of a two-round frame.
+// round: 0 the frame's only one, else 1 or 2
+inline int plan_blend_groups(const Switches &sw, uint32_t round) {
+    if (sw.blend_groups != 0) return sw.blend_groups;
+    return round != 0u ? 4 : 8;
+}
+
 // round: 0 the frame's only one, else 1 or 2
 inline RangeMode plan_ranges(const FrameNums &f, const Switches &sw, uint32_t capacity, bool tile_msd, uint32_t round) {
     // (a two-round frame: always — the range array is cleared once per frame, and a launch per round is saved)

@@ -3924,11 +3924,12 @@ __device__ __forceinline__ AuxIO aux_io(AuxIO a) { return a; }
 
 // One workgroup (2 waves) = one 16x16 tile, wave h = pixel rows 8h..8h+7, two pixels per lane on
 // packed f32 — as k_blend — but the wave's 64 lanes are split into G lane groups that own
-// different sub-blocks of the half-tile (G = 2: two 8x8 blocks, G = 4: four 8x4 blocks) and walk
-// DIFFERENT splat lists in lock step: one wave instruction stream serves G (splat, block) pairs.
-// A splat of a few pixels radius touches far fewer 8x4 blocks x 32 pixels than 16x8 half-tiles x
-// 128 pixels, so the number of loop iterations drops (1 M scene: x0.65 for G = 4, x0.77 for
-// G = 2, tools/blend_sim.py) at an unchanged instruction count per iteration.  The staged splat
+// different sub-blocks of the half-tile (G = 2: two 8x8 blocks, G = 4: four 8x4 blocks, G = 8: eight 4x4
+// blocks) and walk DIFFERENT splat lists in lock step: one wave instruction stream serves G (splat, block)
+// pairs.  A splat of a few pixels radius touches far fewer 8x4 blocks x 32 pixels than 16x8 half-tiles x
+// 128 pixels, so the number of loop iterations drops (1 M scene: x0.54 for G = 8, x0.65 for G = 4, x0.77
+// for G = 2, tools/blend_sim.py) at an unchanged instruction count per iteration.  What G = 8 pays is the
+// staging phase: every staged splat is tested against 16 blocks (4 column + 4 row set-ups, then 8 VALU per block).  The staged splat
 // records are stored once per batch; the per-block lists hold 16-bit byte offsets of them, padded
 // with the index of a null record whose exponent test never passes, so lanes whose list is shorter
 // than the wave's longest simply idle.  Results are bit-identical to k_blend: culling only removes
@@ -3945,11 +3946,15 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                                                                  const FrameState *__restrict__ state, TileKeys tk,
                                                                  AuxArg... aux_arg) {
     static_assert(sizeof...(AuxArg) == (AUX ? 1u : 0u), "the AUX blend takes one AuxIO, the plain one none");
-    static_assert(G == 2 || G == 4, "lane groups per wave");
+    static_assert(G == 2 || G == 4 || G == 8, "lane groups per wave");
     if (state->overflow) return;              // frame skipped: see k_blend
     constexpr int GL = WAVE / G;              // lanes per group
-    constexpr int BH = 16 / G;                // block height: G = 2 -> 8, G = 4 -> 4 (block width is 8; GL lanes x 2 pixels)
-    constexpr int NL = 2 * G;                 // lists per tile
+    constexpr int BW = G == 8 ? 4 : 8;        // block width
+    constexpr int BH = 2 * GL / BW;           // block height: G = 2 -> 8, G = 4 / 8 -> 4 (BW x BH = GL lanes x 2 pixels)
+    constexpr int NCOL = 16 / BW;             // block columns of the tile
+    constexpr int NROW = 16 / BH;             // block rows of the tile; rows 0..NROW/2-1 belong to wave 0
+    constexpr int NL = 2 * G;                 // lists per tile (= NCOL * NROW)
+    static_assert(NCOL * NROW == NL && G == NCOL * (NROW / 2), "one list per block, G blocks per wave");
     constexpr uint32_t NULL_REC = BLEND_BATCH;
     // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, pmin, opacity, r | g, b, -, -} (AUX: {.. | g, b, z', slot}).  The
     // lists hold the records' BYTE OFFSETS (16 bits each), so a step's three LDS reads share one address
@@ -3957,16 +3962,19 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     constexpr uint32_t RS = 48;
     __shared__ __attribute__((aligned(16))) float s_rec[(BLEND_BATCH + 1) * (RS / 4)];
     __shared__ __attribute__((aligned(16))) uint16_t s_list[NL][BLEND_BATCH];
-    __shared__ uint32_t s_cnt[2][NL];         // [staging wave][list]
+    // [staging wave][list]; G = 8 packs the counts (<= 64 each) in 16 bits: a wave's 16 counts are two 16-byte reads
+    typedef typename std::conditional<G == 8, uint16_t, uint32_t>::type cnt_t;
+    __shared__ __attribute__((aligned(16))) cnt_t s_cnt[2][NL];
     __shared__ uint32_t s_alive[2];
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
     const uint32_t tile = fc.band_ty0 * fc.tiles_x + blockIdx.x;
     const uint32_t ty = tile / fc.tiles_x, tx = tile % fc.tiles_x;
     const uint32_t gi = lane / GL, lg = lane % GL;
-    const uint32_t bx = gi & 1u, by = G == 4 ? gi >> 1 : 0u;
-    const uint32_t px = tx * 16u + bx * 8u + (lg & 7u);
-    const uint32_t py0 = ty * 16u + wid * 8u + by * BH + (lg >> 3), py1 = py0 + BH / 2;
+    // group gi owns block (column gi % NCOL, row gi / NCOL) of the half-tile; a lane holds (x, y) and (x, y + BH / 2)
+    const uint32_t bx = gi % (uint32_t)NCOL, by = gi / (uint32_t)NCOL;
+    const uint32_t px = tx * 16u + bx * (uint32_t)BW + lg % (uint32_t)BW;
+    const uint32_t py0 = ty * 16u + wid * 8u + by * BH + lg / (uint32_t)BW, py1 = py0 + BH / 2;
     const float pxf = (float)px + 0.5f;
     const uint32_t my_list = wid * G + gi;
     const float tx0 = (float)(tx * 16u) + 0.5f, ty0 = (float)(ty * 16u) + 0.5f;   // tile origin, pixel centres
@@ -4024,7 +4032,12 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         if ((s_alive[0] | s_alive[1]) == 0u) break;
 
         // lists start out as all-null (the previous batch's loops ended before the barrier above)
-        {
+        if constexpr (G == 8) {   // 4 KB: two 16-byte stores per thread
+            uint4 *l128 = (uint4 *)&s_list[0][0];
+            constexpr uint32_t fill = (NULL_REC * RS) * 0x00010001u;
+#pragma unroll
+            for (uint32_t q = 0; q < NL * BLEND_BATCH / 8; q += BLEND_THREADS) l128[q + tid] = make_uint4(fill, fill, fill, fill);
+        } else {
             uint32_t *l32 = (uint32_t *)&s_list[0][0];
             constexpr uint32_t fill = (NULL_REC * RS) * 0x00010001u;
             for (uint32_t q = tid; q < NL * BLEND_BATCH / 2; q += BLEND_THREADS) l32[q] = fill;
@@ -4054,32 +4067,35 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             else
                 *(float2 *)(s_rec + tid * (RS / 4) + 8) = make_float2(u2f(r1.w), u2f(r2x));
         }
-        // The tile's 2G blocks form a grid of 2 columns x G rows (8 wide, BH high).  The exact
+        // The tile's 2G blocks form a grid of NCOL columns x NROW rows (BW wide, BH high).  The exact
         // maximum of the concave exponent over a block comes from the block's two edges facing the
         // splat centre (splat_touches_rect2): the facing vertical edge depends only on the column,
         // the facing horizontal edge only on the row, so the parabola coefficients and their
         // unconstrained optima are set up once per column / row and a block costs two clamps
         // (v_med3), four fmas and a compare.  (fma is fine here: the cull is conservative, not part
         // of the bit-exact result.)
-        constexpr int NROW = G;                            // block rows of the tile (2 columns each)
         uint64_t m[NL];
+        // G = 8: the block edges (tile origin + 4 c, + 4 c + 3) are rebuilt from the origin in every batch: hoisted out of
+        // the batch loop, the sixteen of them stay in vector registers through the blend loop (84 registers, 5 waves per SIMD)
+        float bx0 = tx0, by0 = ty0;
+        if constexpr (G == 8) asm volatile("" : "+v"(bx0), "+v"(by0));
         if constexpr (MODE == 2) {
 #pragma unroll
             for (int l = 0; l < NL; l++) {
                 const int lw = l / G, lgi = l % G;
-                const float rx0 = tx0 + 8.0f * (float)(lgi & 1);
-                const float ry0 = ty0 + 8.0f * (float)lw + (G == 4 ? (float)BH * (float)(lgi >> 1) : 0.0f);
-                const float ex = mx - clampf(mx, rx0, rx0 + 7.0f), ey = my - clampf(my, ry0, ry0 + (float)(BH - 1));
+                const float rx0 = bx0 + (float)BW * (float)(lgi % NCOL);
+                const float ry0 = by0 + 8.0f * (float)lw + (float)BH * (float)(lgi / NCOL);
+                const float ex = mx - clampf(mx, rx0, rx0 + (float)(BW - 1)), ey = my - clampf(my, ry0, ry0 + (float)(BH - 1));
                 m[l] = __builtin_amdgcn_ballot_w64(have && ex * ex + ey * ey <= 2.26f);
             }
         } else {
             const float rcc = __builtin_amdgcn_rcpf(cc), rca = __builtin_amdgcn_rcpf(ca);
-            float c_lo[2], c_hi[2], c_q1[2], c_q0[2], c_t[2];
-            bool c_in[2];
+            float c_lo[NCOL], c_hi[NCOL], c_q1[NCOL], c_q0[NCOL], c_t[NCOL];
+            bool c_in[NCOL];
 #pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const float x0c = tx0 + 8.0f * (float)c;
-                c_lo[c] = mx - (x0c + 7.0f);
+            for (int c = 0; c < NCOL; c++) {
+                const float x0c = bx0 + (float)BW * (float)c;
+                c_lo[c] = mx - (x0c + (float)(BW - 1));
                 c_hi[c] = mx - x0c;
                 c_in[c] = c_lo[c] <= 0.0f && c_hi[c] >= 0.0f;
                 const float dn = fabsf(c_lo[c]) < fabsf(c_hi[c]) ? c_lo[c] : c_hi[c];   // nearer vertical edge
@@ -4089,31 +4105,56 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             }
 #pragma unroll
             for (int r = 0; r < NROW; r++) {
-                const float y0r = ty0 + (float)(BH * r);
+                const float y0r = by0 + (float)(BH * r);
                 const float r_lo = my - (y0r + (float)(BH - 1)), r_hi = my - y0r;
                 const bool r_in = r_lo <= 0.0f && r_hi >= 0.0f;
                 const float dn = fabsf(r_lo) < fabsf(r_hi) ? r_lo : r_hi;               // nearer horizontal edge
                 const float r_q1 = cb * dn, r_q0 = cc * dn * dn;
                 const float r_t = -0.5f * r_q1 * rca;
 #pragma unroll
-                for (int c = 0; c < 2; c++) {
+                for (int c = 0; c < NCOL; c++) {
                     const float tv = __builtin_amdgcn_fmed3f(c_t[c], r_lo, r_hi);
                     const float mv = __builtin_fmaf(__builtin_fmaf(cc, tv, c_q1[c]), tv, c_q0[c]);
                     const float th = __builtin_amdgcn_fmed3f(r_t, c_lo[c], c_hi[c]);
                     const float mh = __builtin_fmaf(__builtin_fmaf(ca, th, r_q1), th, r_q0);
+                    // (hipcc turns the short circuit into an exec-mask branch around every test; with "|" and "&" the G = 8
+                    // tests are branch-free, but the kernel then takes 75 vector registers instead of 71)
                     const bool keep = (c_in[c] && r_in) || !(fmaxf(mv, mh) < thr);
-                    // list of block (column c, row r): rows 0..G/2-1 belong to wave 0
-                    const int l = (r / (NROW / 2)) * G + (r % (NROW / 2)) * 2 + c;
+                    // list of block (column c, row r): rows 0..NROW/2-1 belong to wave 0
+                    const int l = (r / (NROW / 2)) * G + (r % (NROW / 2)) * NCOL + c;
                     m[l] = __builtin_amdgcn_ballot_w64(have && keep);
                 }
+                if constexpr (G == 8) __builtin_amdgcn_sched_barrier(0);   // one row's set-up and four tests at a time
             }
         }
         if (lane == 0) {
+            if constexpr (G == 8) {
+                uint32_t *c32 = (uint32_t *)&s_cnt[wid][0];
 #pragma unroll
-            for (int l = 0; l < NL; l++) s_cnt[wid][l] = (uint32_t)__popcll(m[l]);
+                for (int l = 0; l < NL; l += 2) c32[l / 2] = (uint32_t)__popcll(m[l]) | ((uint32_t)__popcll(m[l + 1]) << 16);
+            } else {
+#pragma unroll
+                for (int l = 0; l < NL; l++) s_cnt[wid][l] = (uint32_t)__popcll(m[l]);
+            }
         }
         __syncthreads();
-        {   // (the other wave's counts are read as one batch: behind a branch per list hipcc emitted eight
+        if constexpr (G == 8) {
+            // wave 0's counts, packed, in scalar registers (sixteen per-lane copies cost 12 vector registers and
+            // two waves per SIMD); a list's base rides in v_mbcnt's addend
+            const uint4 *c128 = (const uint4 *)&s_cnt[0][0];
+            const uint4 ca4 = c128[0], cb4 = c128[1];
+            const uint32_t wv[8] = {ca4.x, ca4.y, ca4.z, ca4.w, cb4.x, cb4.y, cb4.z, cb4.w};
+            uint32_t w[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) w[q] = (uint32_t)__builtin_amdgcn_readfirstlane(wv[q]);
+            const uint32_t swid = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
+#pragma unroll
+            for (int l = 0; l < NL; l++) {
+                const uint32_t base = swid ? (w[l / 2] >> (16 * (l & 1))) & 0xffffu : 0u;
+                const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[l] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[l], base));
+                if ((m[l] >> lane) & 1ull) s_list[l][pos] = (uint16_t)(tid * RS);
+            }
+        } else {   // (the other wave's counts are read as one batch: behind a branch per list hipcc emitted eight
             // ds_read + s_waitcnt pairs in a row)
             uint32_t lbase[NL];
 #pragma unroll
@@ -4125,10 +4166,21 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         }
         // trip count of MY wave: its longest list (wave-uniform)
         uint32_t trip = 0;
+        if constexpr (G == 8) {   // (two counts per word: a sum is at most 128, no carry between the halves)
+            const uint4 c0 = *(const uint4 *)&s_cnt[0][wid * G], c1 = *(const uint4 *)&s_cnt[1][wid * G];
+            const uint32_t sum[4] = {c0.x + c1.x, c0.y + c1.y, c0.z + c1.z, c0.w + c1.w};
 #pragma unroll
-        for (int g = 0; g < G; g++) {
-            const uint32_t c = s_cnt[0][wid * G + g] + s_cnt[1][wid * G + g];
-            trip = c > trip ? c : trip;
+            for (int q = 0; q < 4; q++) {
+                const uint32_t lo = sum[q] & 0xffffu, hi = sum[q] >> 16;
+                trip = lo > trip ? lo : trip;
+                trip = hi > trip ? hi : trip;
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+                const uint32_t c = s_cnt[0][wid * G + g] + s_cnt[1][wid * G + g];
+                trip = c > trip ? c : trip;
+            }
         }
         trip = __builtin_amdgcn_readfirstlane(trip);
         __syncthreads();
