@@ -70,6 +70,17 @@ pub const GS_EDIT_ROTATE_SH: u32 = 2;
 pub const GS_EDIT_COLOR: u32 = 4;
 pub const GS_EDIT_OPACITY: u32 = 8;
 
+pub const GS_ATTR_X: u32 = 0;
+pub const GS_ATTR_Y: u32 = 1;
+pub const GS_ATTR_Z: u32 = 2;
+pub const GS_ATTR_RED: u32 = 3;
+pub const GS_ATTR_GREEN: u32 = 4;
+pub const GS_ATTR_BLUE: u32 = 5;
+pub const GS_ATTR_OPACITY: u32 = 6;
+pub const GS_ATTR_SIZE2: u32 = 7;
+pub const GS_ATTR_DIST2: u32 = 8;
+pub const GS_ATTR_COUNT: u32 = 9;
+
 #[repr(C)] pub struct gs_device { _private: [u8; 0] }
 #[repr(C)] pub struct gs_stream { _private: [u8; 0] }
 #[repr(C)] pub struct gs_buffer { _private: [u8; 0] }
@@ -298,6 +309,31 @@ pub struct gs_edit {
     pub reserved: [u32; 4],
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_attribute_desc {
+    pub attr: u32,
+    pub model_transform: *const gs_model_transform_pod,
+    pub r#ref: [f32; 3],
+    pub reserved: [u32; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_attribute_stats {
+    pub finite: u64,
+    pub min: f32,
+    pub max: f32,
+    pub sum: f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_stats {
+    pub count: u64,
+    pub attr: [gs_attribute_stats; 9],
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -440,6 +476,9 @@ extern "C" {
     pub fn gs_snapshot_selection(snap: *const gs_snapshot, s: *mut gs_stream, sel: *mut gs_selection, op: u32) -> gs_status;
     pub fn gs_gaussians_buffer_restore(g: *mut gs_gaussians_buffer, s: *mut gs_stream, snap: *mut gs_snapshot, exchange: i32) -> gs_status;
     pub fn gs_gaussians_buffer_create_concat(s: *mut gs_stream, srcs: *const *mut gs_gaussians_buffer, sels: *const *const gs_selection, count: u32, out: *mut *mut gs_gaussians_buffer, counts_out: *mut u64) -> gs_status;
+    pub fn gs_gaussians_buffer_stats(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, model_transform: *const gs_model_transform_pod, r#ref: *const f32, out: *mut gs_stats) -> gs_status;
+    pub fn gs_gaussians_buffer_histogram(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, a: *const gs_attribute_desc, lo: f32, hi: f32, bins: u32, counts_out: *mut u64) -> gs_status;
+    pub fn gs_select_attribute(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, a: *const gs_attribute_desc, lo: f32, hi: f32, op: u32) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

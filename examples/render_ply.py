@@ -3,7 +3,8 @@
 reference's examples/read_ply.rs / read_spz.rs followed by one frame of the viewer.
 usage: python examples/render_ply.py tests/golden/model.ply out.ppm [--size 960x540] [--eye 0,0,4]
        [--mode splat|ellipse|point] [--pod ShHalf/Cov3dHalf]          (needs a GPU: there is no CPU fallback)
-       [--depth depth.pgm] [--pick X,Y]   the frame's depth plane (expected depth, 16-bit PGM) / the Gaussian under a pixel"""
+       [--depth depth.pgm] [--pick X,Y]   the frame's depth plane (expected depth, 16-bit PGM) / the Gaussian under a pixel
+       [--stats]                          count, bounds and centroid from gs_gaussians_buffer_stats"""
 import argparse
 import os
 import sys
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--pick", help="X,Y: print the index and record of the Gaussian picked at that pixel (median contributor)")
     ap.add_argument("--crop", nargs=6, type=float, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                     help="hide what lies outside this axis-aligned box (a device selection: the data is left alone)")
+    ap.add_argument("--stats", action="store_true",
+                    help="print count, bounds and centroid of the Gaussians (of those the crop keeps), computed on the device")
     args = ap.parse_args()
     sh, cov = args.pod.split("/")
     pod = getattr(gs, "GaussianPodWith%s%sConfigs" % (sh, cov))
@@ -53,6 +56,16 @@ def main():
         hide.select_box(stream, buf, gs.model_transform_pod(), gs.box_from_bounds(args.crop[:3], args.crop[3:]))
         hide.invert(stream)
         print("crop: %d of %d Gaussians hidden" % (hide.count(stream), len(buf)))
+    if args.stats:
+        kept = None
+        if hide is not None:
+            kept = gs.Selection(dev, len(buf))
+            kept.combine(stream, "set", hide)
+            kept.invert(stream)
+        s = buf.stats(stream, kept)
+        lo, hi = s.bounds
+        print("stats: %d Gaussians, bounds (%.4g, %.4g, %.4g) .. (%.4g, %.4g, %.4g), centroid (%.4g, %.4g, %.4g)"
+              % ((s.count,) + tuple(lo) + tuple(hi) + tuple(s.centroid)))
     r.render(stream, buf, gs.gaussian_transform_pod(1.0, mode, 3, False, 3.0), gs.model_transform_pod(), cam,
              img.device_ptr(), depth_device_ptr=depth.device_ptr() if aux else None,
              pick_device_ptr=pick.device_ptr() if aux else None, hide=hide)

@@ -887,6 +887,75 @@ gs_status gs_gaussians_buffer_restore(gs_gaussians_buffer *g, gs_stream *s, gs_s
 gs_status gs_gaussians_buffer_create_concat(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
                                             uint32_t count, gs_gaussians_buffer **out, uint64_t *counts_out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Attribute statistics, histograms and select by attribute range (no reference  */
+/* item in the core crate: the reference's editor computes these on the host from its own copy)  */
+/* ------------------------------------------------------------------------------------------ */
+
+/* An attribute maps one record to one binary32 value, the same for all 12 layouts (no reference item).
+ * X / Y / Z: pw = M (p, 1), M = model_transform_mat, sum order ((c0 + c1) + c2) + c3 — the arithmetic of gs_select_sphere.
+ * RED / GREEN / BLUE / OPACITY: byte j of word 3 divided by 255.  SIZE2: (S00 + S11) + S22 of the layout's decoded 3D
+ * covariance, the sum of the squared axis lengths as the renderer sees them (the model transform is not applied).
+ * DIST2: d = pw - ref, (d.x d.x + d.y d.y) + d.z d.z.  Every operation is rounded, nothing is fused. */
+enum {
+    GS_ATTR_X = 0, GS_ATTR_Y = 1, GS_ATTR_Z = 2, GS_ATTR_RED = 3, GS_ATTR_GREEN = 4, GS_ATTR_BLUE = 5,
+    GS_ATTR_OPACITY = 6, GS_ATTR_SIZE2 = 7, GS_ATTR_DIST2 = 8, GS_ATTR_COUNT = 9
+};
+/* One attribute (no reference item).  model_transform == NULL: gs_model_transform_pod_default pushed
+ * through the same arithmetic (an infinite coordinate becomes NaN either way). */
+typedef struct gs_attribute_desc {
+    uint32_t attr;                                   /* GS_ATTR_* */
+    const gs_model_transform_pod *model_transform;   /* or NULL */
+    float ref[3];                                    /* looked at only for GS_ATTR_DIST2; finite then */
+    uint32_t reserved[2];                            /* 0 */
+} gs_attribute_desc;
+
+/* One attribute over the selected records (no reference item).  Only finite values enter min, max and
+ * sum.  min / max: by the total order on the bit patterns (-0 < +0), so they are bit-defined; +inf / -inf when finite == 0.
+ * sum: the values widened to binary64 and added in a fixed shape (no floating-point atomics): the same bits from run to
+ * run on the same input; 0 when finite == 0. */
+typedef struct gs_attribute_stats {
+    uint64_t finite;
+    float min, max;
+    double sum;
+} gs_attribute_stats;
+/* count = the selected Gaussians; attr[GS_ATTR_*].  The centroid is sum / finite of X, Y, Z, the bounds their min and max
+ * (no reference item). */
+typedef struct gs_stats {
+    uint64_t count;
+    gs_attribute_stats attr[9];
+} gs_stats;
+
+/* Statistics of all nine attributes over the records of `sel` (NULL: all) in one pass over the caller-order buffer
+ * (no reference item).  BLOCKING, like gs_selection_count.  model_transform == NULL: the default transform;
+ * ref == NULL: the origin (ref is GS_ATTR_DIST2's reference point and must be finite).  s == NULL: the device's internal
+ * stream.  Ordered behind an edit or restore enqueued on another stream, as gs_gaussians_buffer_snapshot is.  A buffer of
+ * length 0 is valid: counts 0, min +inf, max -inf.  The buffer keeps the scratch of the call: calls on ONE buffer from
+ * several host threads at once are the caller's to order.  GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with
+ * *out untouched, for a null buffer or out, a non-finite ref, a selection whose length differs from the buffer's or that
+ * belongs to another device. */
+gs_status gs_gaussians_buffer_stats(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel,
+                                    const gs_model_transform_pod *model_transform, const float ref[3], gs_stats *out);
+/* Histogram of one attribute in one pass (no reference item).  counts_out holds 2 x (bins + 3) values: row 0
+ * = the Gaussians of `sel`, row 1 = the others (sel == NULL: everything in row 0).  scale = (float)bins / (hi - lo) in
+ * binary32 on the host; the slot of a value v, tested in this order: NaN -> bins + 2; v < lo -> bins; v >= hi -> bins + 1;
+ * else (uint32_t)((v - lo) scale), truncated, clamped to bins - 1.  BLOCKING; stream, ordering, scratch and the empty buffer
+ * as gs_gaussians_buffer_stats.  GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with counts_out untouched, for a
+ * null buffer, descriptor or counts_out, an unknown attribute, nonzero `reserved`, a non-finite ref with GS_ATTR_DIST2,
+ * bins outside 1..4096, lo, hi or hi - lo not finite, hi <= lo, a scale that is not finite, a selection whose length
+ * differs from the buffer's or that belongs to another device. */
+gs_status gs_gaussians_buffer_histogram(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel,
+                                        const gs_attribute_desc *a, float lo, float hi, uint32_t bins, uint64_t *counts_out);
+/* sel = sel op {i : lo <= v_i && v_i <= hi}, v = the attribute of record i of `gaussians` (DESIGN.md 3.10;
+ * no reference item).  Only ENQUEUES; the mask is written word-wise as by gs_select_sphere; ordered behind an edit or restore
+ * enqueued on another stream.  A NaN value is never selected, lo > hi selects nothing, infinite bounds are allowed.
+ * GS_ATTR_DIST2 with lo = 0, hi = r r is gs_select_sphere(ref, r) bit for bit.  GS_ERR_INVALID_ARGUMENT, before anything is
+ * enqueued and with the selection unchanged, for a null argument, an unknown attribute or op, nonzero `reserved`, a
+ * non-finite ref with GS_ATTR_DIST2, a NaN bound, a selection whose length differs from the buffer's or that belongs to
+ * another device. */
+gs_status gs_select_attribute(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *gaussians, const gs_attribute_desc *a,
+                              float lo, float hi, gs_select_op op);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

@@ -361,6 +361,11 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // after the other; counts (optional) receives the records taken per source.  Blocks once, for the counts.
     static GaussiansBuffer concat(Stream &s, const std::vector<const GaussiansBuffer *> &srcs, const std::vector<const Selection *> &sels = {},
                                   std::vector<uint64_t> *counts = nullptr);
+    // attribute statistics and histograms over the records of sel (nullptr: all) in one pass on the device (gs3d.h
+    // gs_gaussians_buffer_stats / _histogram; no reference item); blocking.  mt == nullptr: the default
+    // transform; ref == nullptr: the origin.  histogram: 2 x (bins + 3) counts, row 0 = the selection, row 1 = the others.
+    gs_stats stats(Stream &s, const Selection *sel = nullptr, const gs_model_transform_pod *mt = nullptr, const float *ref = nullptr) const;
+    std::vector<uint64_t> histogram(Stream &s, const gs_attribute_desc &a, float lo, float hi, uint32_t bins, const Selection *sel = nullptr) const;
     gs_gaussians_buffer *raw() const { return h_; }
   private:
     GaussiansBuffer() = default;
@@ -393,6 +398,10 @@ class Selection {
                     gs_select_op op = GS_SEL_SET) { check(gs_select_box(h_, s.raw(), g.raw(), &mt, world_to_box, op)); }
     // sel = sel op {i : start <= i < start + count}; only enqueues
     void select_range(Stream &s, size_t start, size_t count, gs_select_op op = GS_SEL_SET) { check(gs_select_range(h_, s.raw(), start, count, op)); }
+    // sel = sel op {i : lo <= attribute_i <= hi} (gs_select_attribute); only enqueues
+    template <class G>
+    void select_attribute(Stream &s, GaussiansBuffer<G> &g, const gs_attribute_desc &a, float lo, float hi,
+                          gs_select_op op = GS_SEL_SET) { check(gs_select_attribute(h_, s.raw(), g.raw(), &a, lo, hi, op)); }
     gs_selection *raw() const { return h_; }
   private:
     gs_selection *h_ = nullptr;
@@ -418,6 +427,20 @@ inline GaussiansBuffer<G> GaussiansBuffer<G>::concat(Stream &s, const std::vecto
     check(gs_gaussians_buffer_create_concat(s.raw(), g.data(), m.empty() ? nullptr : m.data(), (uint32_t)g.size(), &b.h_,
                                             counts ? counts->data() : nullptr));
     return b;
+}
+
+template <class G>
+inline gs_stats GaussiansBuffer<G>::stats(Stream &s, const Selection *sel, const gs_model_transform_pod *mt, const float *ref) const {
+    gs_stats out;
+    check(gs_gaussians_buffer_stats(h_, s.raw(), sel ? sel->raw() : nullptr, mt, ref, &out));
+    return out;
+}
+template <class G>
+inline std::vector<uint64_t> GaussiansBuffer<G>::histogram(Stream &s, const gs_attribute_desc &a, float lo, float hi, uint32_t bins,
+                                                           const Selection *sel) const {
+    std::vector<uint64_t> counts(2 * ((size_t)bins + 3));
+    check(gs_gaussians_buffer_histogram(h_, s.raw(), sel ? sel->raw() : nullptr, &a, lo, hi, bins, counts.data()));
+    return counts;
 }
 
 template <class G>

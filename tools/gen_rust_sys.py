@@ -16,6 +16,7 @@ OUT = os.path.join(ROOT, "bindings", "rust", "gs3d_sys.rs")
 SCALARS = {"int32_t": "i32", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "uint16_t": "u16",
            "uint8_t": "u8", "int8_t": "i8", "size_t": "usize", "float": "f32", "double": "f64", "char": "c_char",
            "void": "c_void", "gs_status": "gs_status", "int": "i32"}
+RUST_KEYWORDS = ("in", "type", "fn", "ref", "box", "mod", "use")
 ENUMS = {"gs_sh_config", "gs_cov3d_config", "gs_display_mode", "gs_kernel_id", "gs_select_op"}
 
 
@@ -122,11 +123,11 @@ def generate():
     for name, fields in structs:
         o.append("#[repr(C)]\n#[derive(Clone, Copy)]\npub struct %s {" % name)
         for fn, ft in fields:
-            o.append("    pub %s: %s," % (fn, ft))
+            o.append("    pub %s: %s," % (("r#" + fn) if fn in RUST_KEYWORDS else fn, ft))
         o.append("}\n")
     o.append('#[link(name = "gs3d_hip")]\nextern "C" {')
     for name, params, ret in funcs:
-        ps = ", ".join("%s: %s" % (("r#" + n) if n in ("in", "type", "fn", "ref", "box", "mod", "use") else n, t)
+        ps = ", ".join("%s: %s" % (("r#" + n) if n in RUST_KEYWORDS else n, t)
                        for n, t in params)
         o.append("    pub fn %s(%s)%s;" % (name, ps, (" -> " + ret) if ret else ""))
     o.append("}\n")

@@ -16,11 +16,12 @@ There is no CPU implementation behind any device call: constructing a Device wit
 raises NoDeviceError, and importing the package without libgs3d_hip.so raises ImportError.
 """
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
 from . import _capi
-from ._capi import AuxTargets, Camera, Edit, FrameResult, FrameSelection, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
+from ._capi import AttributeDesc, AuxTargets, Camera, Edit, FrameResult, FrameSelection, FrameStats, GaussianTransformPod, Limits, ModelTransformPod, SortInfo
 
 _L = _capi.load()
 
@@ -908,6 +909,44 @@ class GaussiansBuffer:
         # (no buffer, more than 64, or two layouts: the library's GS_ERR_INVALID_ARGUMENT above)
         return GaussiansBuffer(buffers[0].device, buffers[0].pod, h), [int(c) for c in counts]
 
+    def stats(self, stream, selection=None, model_transform=None, ref=(0.0, 0.0, 0.0)):
+        """gs_gaussians_buffer_stats: a GaussianStats — count and, for each of the nine ATTR_*, the number
+        of finite values, their bit-defined min and max and their binary64 sum — over the records of `selection` (None:
+        all), in one pass on the device.  Blocking.  model_transform=None: the default transform; `ref` is the reference
+        point of ATTR_DIST2."""
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        if model_transform is not None and not isinstance(model_transform, ModelTransformPod):
+            raise TypeError("model_transform must be a ModelTransformPod or None, not %s" % type(model_transform).__name__)
+        r = (C.c_float * 3)(*_ref_point(ref))
+        out = _capi.Stats()
+        _check(_L.gs_gaussians_buffer_stats(self._h, stream._h if stream is not None else None,
+                                            selection._h if selection is not None else None,
+                                            C.byref(model_transform) if model_transform is not None else None, r, C.byref(out)))
+        a = out.attr
+        return GaussianStats(count=int(out.count),
+                             finite=np.array([a[k].finite for k in range(ATTR_COUNT)], np.uint64),
+                             min=np.array([a[k].min for k in range(ATTR_COUNT)], np.float32),
+                             max=np.array([a[k].max for k in range(ATTR_COUNT)], np.float32),
+                             sum=np.array([a[k].sum for k in range(ATTR_COUNT)], np.float64))
+
+    def histogram(self, stream, attr, lo, hi, bins, selection=None, model_transform=None, ref=(0.0, 0.0, 0.0)):
+        """gs_gaussians_buffer_histogram: np.uint64[2, bins + 3] — row 0 the Gaussians of `selection`
+        (None: all of them), row 1 the others; columns 0..bins-1 the bins of [lo, hi), then below, above and NaN.
+        Blocking.  `attr`: an ATTR_* number or its name."""
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        d = attribute_desc(attr, model_transform, ref)
+        if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)):
+            raise TypeError("bins must be an integer, not %s" % type(bins).__name__)
+        if not 1 <= int(bins) <= 4096:
+            raise ValueError("a histogram takes 1 to 4096 bins, not %d" % bins)
+        out = np.zeros((2, int(bins) + 3), dtype=np.uint64)
+        _check(_L.gs_gaussians_buffer_histogram(self._h, stream._h if stream is not None else None,
+                                                selection._h if selection is not None else None, C.byref(d), float(lo), float(hi),
+                                                int(bins), _ptr(out)))
+        return out
+
     def destroy(self):
         if self._h:
             _L.gs_gaussians_buffer_destroy(self._h)
@@ -1218,6 +1257,68 @@ STAGE_NAMES = ["repack", "preprocess", "scan", "depth_sort", "expand", "tile_sor
 
 
 SEL_SET, SEL_OR, SEL_AND, SEL_ANDNOT, SEL_XOR = 0, 1, 2, 3, 4      # gs_select_op: dst = dst op src
+
+# GS_ATTR_*: one binary32 value per record
+ATTR_X, ATTR_Y, ATTR_Z, ATTR_RED, ATTR_GREEN, ATTR_BLUE, ATTR_OPACITY, ATTR_SIZE2, ATTR_DIST2 = range(9)
+ATTR_COUNT = 9
+ATTR_NAMES = ["x", "y", "z", "red", "green", "blue", "opacity", "size2", "dist2"]
+
+
+def attribute(attr):
+    """GS_ATTR_* from its number or name (ATTR_NAMES); ValueError for anything else."""
+    if isinstance(attr, str):
+        if attr.lower() not in ATTR_NAMES:
+            raise ValueError("unknown attribute %r (one of %s)" % (attr, ", ".join(ATTR_NAMES)))
+        return ATTR_NAMES.index(attr.lower())
+    if isinstance(attr, (int, np.integer)) and not isinstance(attr, bool) and 0 <= int(attr) < ATTR_COUNT:
+        return int(attr)
+    raise ValueError("unknown attribute %r" % (attr,))
+
+
+def _ref_point(ref):
+    r = tuple(float(v) for v in ref)
+    if len(r) != 3:
+        raise ValueError("ref takes three numbers, got %d" % len(r))
+    return r
+
+
+def attribute_desc(attr, model_transform=None, ref=(0.0, 0.0, 0.0)):
+    """The gs_attribute_desc of histogram() / select_attribute(), checked before any device call: a known attribute, a
+    ModelTransformPod or None (the default transform), a finite `ref` for ATTR_DIST2."""
+    d = AttributeDesc()
+    d.attr = attribute(attr)
+    if model_transform is not None:
+        if not isinstance(model_transform, ModelTransformPod):
+            raise TypeError("model_transform must be a ModelTransformPod or None, not %s" % type(model_transform).__name__)
+        d.model_transform = C.pointer(model_transform)
+        d._keep = model_transform      # the pod stays alive as long as the struct
+    r = _ref_point(ref)
+    if d.attr == ATTR_DIST2 and not all(np.isfinite(v) for v in r):
+        raise ValueError("the reference point of ATTR_DIST2 must be finite")
+    d.ref[:] = r
+    return d
+
+
+@dataclasses.dataclass
+class GaussianStats:
+    """gs_stats: `count` selected Gaussians and, indexed by ATTR_*, the finite values of each attribute, their min and max
+    (+inf / -inf without a finite value) and their binary64 sum."""
+    count: int
+    finite: np.ndarray       # uint64[9]
+    min: np.ndarray          # float32[9]
+    max: np.ndarray          # float32[9]
+    sum: np.ndarray          # float64[9]
+
+    @property
+    def centroid(self):
+        """sum / finite of X, Y, Z (NaN where no value is finite)"""
+        with np.errstate(all="ignore"):
+            return self.sum[:3] / self.finite[:3].astype(np.float64)
+
+    @property
+    def bounds(self):
+        """(min, max) of X, Y, Z"""
+        return self.min[:3].copy(), self.max[:3].copy()
 _SELECT_OPS = {"set": SEL_SET, "or": SEL_OR, "and": SEL_AND, "andnot": SEL_ANDNOT, "xor": SEL_XOR}
 
 
@@ -1345,6 +1446,19 @@ class Selection:
                 raise ValueError("%s must be >= 0, not %d" % (name, v))
         op = select_op(op)
         _check(_L.gs_select_range(self._h, stream._h, int(start), int(count), op))
+
+    def select_attribute(self, stream, gaussians, attr, lo, hi, op=SEL_SET, model_transform=None, ref=(0.0, 0.0, 0.0)):
+        """self = self op {i : lo <= v_i <= hi}, v = the attribute `attr` (an ATTR_* number or name) of record i of
+        `gaussians` (gs_select_attribute); only enqueues.  NaN values are never selected; infinite
+        bounds are allowed, NaN bounds are not."""
+        if not isinstance(gaussians, GaussiansBuffer):
+            raise TypeError("gaussians must be a GaussiansBuffer, not %s" % type(gaussians).__name__)
+        d = attribute_desc(attr, model_transform, ref)
+        lo, hi = float(lo), float(hi)
+        if lo != lo or hi != hi:
+            raise ValueError("a bound of the range is NaN")
+        op = select_op(op)
+        _check(_L.gs_select_attribute(self._h, stream._h, gaussians._h, C.byref(d), lo, hi, op))
 
     def destroy(self):
         if self._h:

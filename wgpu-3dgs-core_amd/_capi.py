@@ -63,6 +63,21 @@ class Edit(C.Structure):
                 ("reserved", u32 * 4)]
 
 
+class AttributeDesc(C.Structure):
+    """gs_attribute_desc: one attribute of a record (gs_gaussians_buffer_histogram, gs_select_attribute)"""
+    _fields_ = [("attr", u32), ("model_transform", C.POINTER(ModelTransformPod)), ("ref", f32 * 3), ("reserved", u32 * 2)]
+
+
+class AttributeStats(C.Structure):
+    """gs_attribute_stats: one attribute over the selected records"""
+    _fields_ = [("finite", u64), ("min", f32), ("max", f32), ("sum", C.c_double)]
+
+
+class Stats(C.Structure):
+    """gs_stats: what gs_gaussians_buffer_stats fills"""
+    _fields_ = [("count", u64), ("attr", AttributeStats * 9)]
+
+
 class SortInfo(C.Structure):
     _fields_ = [("depth_msd", u32), ("depth_bucket_max", u32), ("bucket_capacity", u32), ("tile_msd", u32),
                 ("tile_bucket_max", u32), ("tile_masks", u32), ("rounds", u32), ("round1", u32), ("tiles_done", u32), ("partitioned", u32)]
@@ -235,6 +250,9 @@ SIGNATURES = {
     "gs_snapshot_selection": (i32, [vp, vp, vp, i32]),
     "gs_gaussians_buffer_restore": (i32, [vp, vp, vp, i32]),
     "gs_gaussians_buffer_create_concat": (i32, [vp, vp, vp, u32, vp, vp]),
+    "gs_gaussians_buffer_stats": (i32, [vp, vp, vp, vp, vp, vp]),
+    "gs_gaussians_buffer_histogram": (i32, [vp, vp, vp, vp, f32, f32, u32, vp]),
+    "gs_select_attribute": (i32, [vp, vp, vp, vp, f32, f32, i32]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }
