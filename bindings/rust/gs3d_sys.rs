@@ -479,6 +479,8 @@ extern "C" {
     pub fn gs_gaussians_buffer_stats(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, model_transform: *const gs_model_transform_pod, r#ref: *const f32, out: *mut gs_stats) -> gs_status;
     pub fn gs_gaussians_buffer_histogram(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, a: *const gs_attribute_desc, lo: f32, hi: f32, bins: u32, counts_out: *mut u64) -> gs_status;
     pub fn gs_select_attribute(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, a: *const gs_attribute_desc, lo: f32, hi: f32, op: u32) -> gs_status;
+    pub fn gs_gaussians_buffer_neighbor_counts(g: *mut gs_gaussians_buffer, s: *mut gs_stream, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, cap: u32, counts_out: *mut gs_buffer) -> gs_status;
+    pub fn gs_select_neighbors(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, min_count: u32, max_count: u32, op: u32) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

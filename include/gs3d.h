@@ -956,6 +956,48 @@ gs_status gs_gaussians_buffer_histogram(gs_gaussians_buffer *g, gs_stream *s, co
 gs_status gs_select_attribute(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *gaussians, const gs_attribute_desc *a,
                               float lo, float hi, gs_select_op op);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Neighbour counts and select by neighbourhood (no reference item in the core  */
+/* crate: the reference's editor removes floaters on the host from its own copy)                 */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  pw_i = M (p_i, 1), the arithmetic of gs_select_sphere and
+ * GS_ATTR_X / Y / Z; model_transform == NULL: the default transform through the same arithmetic.  Gaussian i is a POINT iff
+ * it belongs to `among` (NULL: all) and the three components of pw_i are finite.  For points i != j, d = pw_i - pw_j: j is a
+ * neighbour of i iff (d.x d.x + d.y d.y) + d.z d.z <= r r in binary32, every operation rounded, nothing fused, r r rounded
+ * once on the host.  The relation is symmetric; a distance of exactly r counts; r = 0 finds exact duplicates.  c_i = the
+ * number of neighbours of i if i is a point, else 0: an integer that does not depend on the traversal, so it is bit-defined.
+ *
+ * Cost: a 64-bit device sort of n keys (cells of side about r, 21 bits per axis over the bounding box of the points — a far
+ * outlier grows the box, not the cells), then for every point the occupancy of the 27 cells around it, cut short by the cap.
+ * A radius that puts most of the scene inside one ball, with a large cap, is quadratic by definition: that choice is the
+ * caller's.  Both calls only ENQUEUE (the bounding box stays on the device; all 64 key bits are sorted).  The buffer keeps
+ * the scratch of the call, 28 bytes per Gaussian, until it is destroyed; a call on another stream waits for the previous one
+ * on the device.  Calls on ONE buffer from several host threads at once are the caller's to order. */
+
+/* counts_out[i] = min(c_i, cap), one uint32_t per Gaussian in caller order (no reference item): the input of
+ * a density histogram, a heat-map tint or the caller's own threshold; read it back with gs_buffer_download.  counts_out holds
+ * at least 4 n bytes on the buffer's device; cap >= 1 (counting for i may stop once it has reached cap).  Only ENQUEUES on `s`
+ * (NULL: the device's internal stream), ordered behind an edit or restore enqueued on another stream, as
+ * gs_gaussians_buffer_snapshot is.  A buffer of length 0 is valid and launches nothing.  GS_ERR_INVALID_ARGUMENT, before
+ * anything is enqueued and with the plane untouched, for a null buffer or plane, a radius that is negative, NaN or infinite or
+ * whose square is not finite in binary32, cap == 0, a plane that is too small or on another device, a selection whose length
+ * differs from the buffer's or that belongs to another device, a buffer of more than 0xfffffff0 Gaussians. */
+gs_status gs_gaussians_buffer_neighbor_counts(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *among,
+                                              const gs_model_transform_pod *model_transform, float radius, uint32_t cap,
+                                              gs_buffer *counts_out);
+/* sel = sel op {i : i is a point and min_count <= c_i <= max_count}, with the true counts (no reference item):
+ * max_count = k - 1 selects the floaters with fewer than k others within `radius`.  A Gaussian that is not a point is never
+ * selected, not even with min_count = 0; min_count > max_count selects nothing; max_count = UINT32_MAX is "no upper limit".
+ * Only ENQUEUES on `s` (NULL: the device's internal stream); the mask is written word-wise as by gs_select_sphere; ordered
+ * behind an edit or restore enqueued on another stream.  GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with the
+ * selection unchanged, for a null selection or buffer, an unknown op, a radius that is negative, NaN or infinite or whose
+ * square is not finite in binary32, a selection (`sel` or `among`) whose length differs from the buffer's or that belongs to
+ * another device, a buffer of more than 0xfffffff0 Gaussians. */
+gs_status gs_select_neighbors(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *gaussians, const gs_selection *among,
+                              const gs_model_transform_pod *model_transform, float radius, uint32_t min_count, uint32_t max_count,
+                              gs_select_op op);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

@@ -366,6 +366,11 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // transform; ref == nullptr: the origin.  histogram: 2 x (bins + 3) counts, row 0 = the selection, row 1 = the others.
     gs_stats stats(Stream &s, const Selection *sel = nullptr, const gs_model_transform_pod *mt = nullptr, const float *ref = nullptr) const;
     std::vector<uint64_t> histogram(Stream &s, const gs_attribute_desc &a, float lo, float hi, uint32_t bins, const Selection *sel = nullptr) const;
+    // counts[i] = min(c_i, cap), one uint32_t per Gaussian: the Gaussians of among (nullptr: all) with a finite world position
+    // within radius of Gaussian i (gs3d.h gs_gaussians_buffer_neighbor_counts; no reference item); only
+    // enqueues.  counts holds at least 4 len() bytes; read it back with Buffer::download.
+    void neighbor_counts(Stream &s, float radius, uint32_t cap, Buffer &counts, const Selection *among = nullptr,
+                         const gs_model_transform_pod *mt = nullptr);
     gs_gaussians_buffer *raw() const { return h_; }
   private:
     GaussiansBuffer() = default;
@@ -402,6 +407,13 @@ class Selection {
     template <class G>
     void select_attribute(Stream &s, GaussiansBuffer<G> &g, const gs_attribute_desc &a, float lo, float hi,
                           gs_select_op op = GS_SEL_SET) { check(gs_select_attribute(h_, s.raw(), g.raw(), &a, lo, hi, op)); }
+    // sel = sel op {i : min_count <= c_i <= max_count}, c_i as GaussiansBuffer::neighbor_counts without a cap
+    // (gs_select_neighbors); only enqueues.  max_count = k - 1: the floaters with fewer than k others around
+    template <class G>
+    void select_neighbors(Stream &s, GaussiansBuffer<G> &g, float radius, uint32_t min_count = 0, uint32_t max_count = UINT32_MAX,
+                          const Selection *among = nullptr, const gs_model_transform_pod *mt = nullptr, gs_select_op op = GS_SEL_SET) {
+        check(gs_select_neighbors(h_, s.raw(), g.raw(), among ? among->raw() : nullptr, mt, radius, min_count, max_count, op));
+    }
     gs_selection *raw() const { return h_; }
   private:
     gs_selection *h_ = nullptr;
@@ -441,6 +453,12 @@ inline std::vector<uint64_t> GaussiansBuffer<G>::histogram(Stream &s, const gs_a
     std::vector<uint64_t> counts(2 * ((size_t)bins + 3));
     check(gs_gaussians_buffer_histogram(h_, s.raw(), sel ? sel->raw() : nullptr, &a, lo, hi, bins, counts.data()));
     return counts;
+}
+
+template <class G>
+inline void GaussiansBuffer<G>::neighbor_counts(Stream &s, float radius, uint32_t cap, Buffer &counts, const Selection *among,
+                                                const gs_model_transform_pod *mt) {
+    check(gs_gaussians_buffer_neighbor_counts(h_, s.raw(), among ? among->raw() : nullptr, mt, radius, cap, counts.raw()));
 }
 
 template <class G>

@@ -720,6 +720,26 @@ def pack_device(device, stream, pod, gaussians_buffer, count, pods_buffer):
                              C.c_void_p(gaussians_buffer.device_ptr()), count, C.c_void_p(pods_buffer.device_ptr())))
 
 
+NEIGHBOR_COUNT_MAX = 0xFFFFFFFF      # UINT32_MAX: no cap / no upper limit
+
+
+def _neighbor_args(radius, among, model_transform):
+    """(radius, among handle or None, transform reference or None) of the neighbour calls, checked before any library
+    call: a finite radius >= 0 whose binary32 square is finite, a Selection or None, a ModelTransformPod or None."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise TypeError("radius must be a number, not %s" % type(radius).__name__)
+    r = np.float32(radius)
+    with np.errstate(over="ignore"):
+        if not (np.isfinite(r) and r >= 0 and np.isfinite(r * r)):
+            raise ValueError("radius must be finite and >= 0, with a finite square in binary32, not %r" % (radius,))
+    if among is not None and not isinstance(among, Selection):
+        raise TypeError("among must be a Selection or None, not %s" % type(among).__name__)
+    if model_transform is not None and not isinstance(model_transform, ModelTransformPod):
+        raise TypeError("model_transform must be a ModelTransformPod or None, not %s" % type(model_transform).__name__)
+    return (float(r), among._h if among is not None else None,
+            C.byref(model_transform) if model_transform is not None else None)
+
+
 class GaussiansBuffer:
     """GaussiansBuffer<G> — src/buffer/gaussian.rs:17-229."""
 
@@ -945,6 +965,31 @@ class GaussiansBuffer:
         _check(_L.gs_gaussians_buffer_histogram(self._h, stream._h if stream is not None else None,
                                                 selection._h if selection is not None else None, C.byref(d), float(lo), float(hi),
                                                 int(bins), _ptr(out)))
+        return out
+
+    def neighbor_counts(self, stream, radius, cap=NEIGHBOR_COUNT_MAX, among=None, model_transform=None, out=None):
+        """gs_gaussians_buffer_neighbor_counts: a Buffer of one uint32 per Gaussian in caller order,
+        min(c_i, cap), c_i = the Gaussians of `among` (None: all) with a finite world position within `radius` of Gaussian i,
+        itself not counted; 0 where i is not in `among` or has no finite position.  Only enqueues; read the plane with
+        Buffer.download(stream, np.uint32).  `out`: a Buffer of at least 4 len() bytes to write into instead of a new one.
+        A small `cap` bounds the cost where the scene is dense."""
+        radius, among, mt = _neighbor_args(radius, among, model_transform)
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)):
+            raise TypeError("cap must be an integer, not %s" % type(cap).__name__)
+        if not 1 <= int(cap) <= NEIGHBOR_COUNT_MAX:
+            raise ValueError("cap must be between 1 and 2^32 - 1, not %d" % cap)
+        if out is not None and not isinstance(out, Buffer):
+            raise TypeError("out must be a Buffer or None, not %s" % type(out).__name__)
+        own = out is None
+        if own:
+            out = Buffer(self.device, size=max(4 * self.len(), 4))
+        try:
+            _check(_L.gs_gaussians_buffer_neighbor_counts(self._h, stream._h if stream is not None else None, among, mt, radius,
+                                                          int(cap), out._h))
+        except Exception:
+            if own:
+                out.release()
+            raise
         return out
 
     def destroy(self):
@@ -1459,6 +1504,24 @@ class Selection:
             raise ValueError("a bound of the range is NaN")
         op = select_op(op)
         _check(_L.gs_select_attribute(self._h, stream._h, gaussians._h, C.byref(d), lo, hi, op))
+
+    def select_neighbors(self, stream, gaussians, radius, min_count=0, max_count=NEIGHBOR_COUNT_MAX, among=None,
+                         model_transform=None, op=SEL_SET):
+        """self = self op {i : min_count <= c_i <= max_count}, c_i = the neighbour count of Gaussian i of `gaussians` within
+        `radius` (gs_select_neighbors; see GaussiansBuffer.neighbor_counts); only enqueues.
+        max_count = k - 1 selects the floaters with fewer than k others around them.  A Gaussian outside `among` or without
+        a finite world position is never selected; min_count > max_count selects nothing."""
+        if not isinstance(gaussians, GaussiansBuffer):
+            raise TypeError("gaussians must be a GaussiansBuffer, not %s" % type(gaussians).__name__)
+        radius, among, mt = _neighbor_args(radius, among, model_transform)
+        for name, v in (("min_count", min_count), ("max_count", max_count)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an integer, not %s" % (name, type(v).__name__))
+            if not 0 <= int(v) <= NEIGHBOR_COUNT_MAX:
+                raise ValueError("%s must be between 0 and 2^32 - 1, not %d" % (name, v))
+        op = select_op(op)
+        _check(_L.gs_select_neighbors(self._h, stream._h if stream is not None else None, gaussians._h, among, mt, radius,
+                                      int(min_count), int(max_count), op))
 
     def destroy(self):
         if self._h:

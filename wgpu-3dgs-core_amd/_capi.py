@@ -253,6 +253,8 @@ SIGNATURES = {
     "gs_gaussians_buffer_stats": (i32, [vp, vp, vp, vp, vp, vp]),
     "gs_gaussians_buffer_histogram": (i32, [vp, vp, vp, vp, f32, f32, u32, vp]),
     "gs_select_attribute": (i32, [vp, vp, vp, vp, f32, f32, i32]),
+    "gs_gaussians_buffer_neighbor_counts": (i32, [vp, vp, vp, vp, f32, u32, vp]),
+    "gs_select_neighbors": (i32, [vp, vp, vp, vp, vp, f32, u32, u32, i32]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

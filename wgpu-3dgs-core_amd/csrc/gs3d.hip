@@ -25,6 +25,7 @@
 #include "gs_select_kernels.h"
 #include "gs_edit_kernels.h"
 #include "gs_stats_kernels.h"
+#include "gs_neighbor_kernels.h"
 #include "gs_pack_kernels.h"
 #include "_gen_kernel_lib_src.h"
 
@@ -654,6 +655,29 @@ extern "C" void gs_download_release(gs_download *d) {
 // GaussiansBuffer<G>
 // ------------------------------------------------------------------------------------------------
 
+// a device array that grows and never shrinks (hipFree synchronises the device)
+struct DevArray {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
+
+static gs_status dev_reserve(DevArray &a, size_t bytes) {
+    if (a.bytes >= bytes && a.ptr) return GS_OK;
+    if (a.ptr) GS_HIP(hipFree(a.ptr));
+    a.ptr = nullptr;
+    a.bytes = 0;
+    size_t want = bytes + bytes / 8 + 256;
+    GS_HIP(hipMalloc(&a.ptr, want));
+    a.bytes = want;
+    return GS_OK;
+}
+
+static void dev_free(DevArray &a) {
+    if (a.ptr) (void)hipFree(a.ptr);
+    a.ptr = nullptr;
+    a.bytes = 0;
+}
+
 // ids of buffers and generations of selections: unique in the process, never 0
 static uint64_t next_object_id() {
     static std::atomic<uint64_t> next{0};
@@ -698,6 +722,11 @@ struct gs_gaussians_buffer {
     // gs_gaussians_buffer_stats / _histogram: the partial rows and the device result of the last call
     void *stats_scratch = nullptr;
     size_t stats_scratch_bytes = 0;
+    // gs_gaussians_buffer_neighbor_counts / gs_select_neighbors: keys, order, sorted positions and the
+    // sort's histograms of the last call; a call on another stream waits for nb_done before it reuses them
+    DevArray nb_scratch, nb_ghist, nb_digit_totals;
+    hipEvent_t nb_done = nullptr;
+    hipStream_t nb_stream = nullptr;
     void mark(size_t lo, size_t hi) {
         if (lo >= hi) return;
         partial_since_order += hi - lo;
@@ -965,6 +994,8 @@ extern "C" void gs_gaussians_buffer_destroy(gs_gaussians_buffer *g) {
     if (g->block_bounds) (void)hipFree(g->block_bounds);
     if (g->concat_offsets) (void)hipFree(g->concat_offsets);
     if (g->stats_scratch) (void)hipFree(g->stats_scratch);
+    for (DevArray *a : {&g->nb_scratch, &g->nb_ghist, &g->nb_digit_totals}) dev_free(*a);
+    if (g->nb_done) (void)hipEventDestroy(g->nb_done);
     if (g->mirror_ready) (void)hipEventDestroy(g->mirror_ready);
     if (g->edit_done) (void)hipEventDestroy(g->edit_done);
     if (g->order) gs_buffer_release(g->order);
@@ -1538,28 +1569,6 @@ extern "C" void gs_camera_look_at(const float eye[3], const float target[3], con
     out->width = width;
     out->height = height;
     out->background[0] = out->background[1] = out->background[2] = 0.0f;
-}
-
-struct DevArray {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-
-static gs_status dev_reserve(DevArray &a, size_t bytes) {
-    if (a.bytes >= bytes && a.ptr) return GS_OK;
-    if (a.ptr) GS_HIP(hipFree(a.ptr));
-    a.ptr = nullptr;
-    a.bytes = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    GS_HIP(hipMalloc(&a.ptr, want));
-    a.bytes = want;
-    return GS_OK;
-}
-
-static void dev_free(DevArray &a) {
-    if (a.ptr) (void)hipFree(a.ptr);
-    a.ptr = nullptr;
-    a.bytes = 0;
 }
 
 // Gaussian selection: n bits in caller index order.  `generation` changes with every call that may
@@ -4783,4 +4792,141 @@ extern "C" gs_status gs_select_attribute(gs_selection *sel, gs_stream *s, gs_gau
                        (uint32_t)(pod_stride(g) / 4), n, a, lo, hi, sel->words, (uint32_t)op);
     GS_HIP(hipGetLastError());
     return GS_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// neighbour counts, select by neighbourhood
+// ------------------------------------------------------------------------------------------------
+
+static gs_status check_neighbor_radius(float radius) {
+    if (!(radius >= 0.0f) || !std::isfinite(radius) || !std::isfinite(radius * radius))
+        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the radius must be finite and not negative, with a finite square");
+    return GS_OK;
+}
+
+// counts[i] = min(c_i, cap) in caller order on `st` (mark: gs::NB_NOT_A_POINT where i is no point); counts == nullptr: the
+// plane of the buffer's scratch, returned in *plane_out.  n > 0, arguments checked.
+static gs_status neighbor_counts_enqueue(gs_gaussians_buffer *g, hipStream_t st, const gs_selection *among,
+                                         const gs_model_transform_pod *mt, float radius, uint32_t cap, bool mark, uint32_t *counts,
+                                         uint32_t **plane_out) {
+    gs_device *dev = g->buf->dev;
+    const uint32_t n = (uint32_t)gs_gaussians_buffer_len(g), pod_words = (uint32_t)(pod_stride(g) / 4);
+    const uint32_t nblocks = (n + 255u) / 256u, pgrid = nblocks < 1024u ? nblocks : 1024u;
+    // [keys 0][vals 0][keys 1][vals 1][count plane][bbox partials][bbox]; the sorted positions (3 planes of n floats) take the
+    // key / value pair the sort did not leave its result in
+    const size_t a8 = ((size_t)n * 8 + 255) & ~(size_t)255, a4 = ((size_t)n * 4 + 255) & ~(size_t)255;
+    const size_t part = ((size_t)pgrid * 24 + 255) & ~(size_t)255;
+    GS_TRY(dev_reserve(g->nb_scratch, 2 * (a8 + a4) + a4 + part + 256));
+    char *base = (char *)g->nb_scratch.ptr;
+    void *k2[2] = {base, base + a8 + a4};
+    void *v2[2] = {base + a8, base + 2 * a8 + a4};
+    uint32_t *plane = (uint32_t *)(base + 2 * (a8 + a4));
+    float *partial = (float *)(base + 2 * (a8 + a4) + a4), *bbox = (float *)(base + 2 * (a8 + a4) + a4 + part);
+    // an edit enqueued on another stream still writes the records; a call on another stream still reads the scratch
+    if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
+    if (g->nb_done && st != g->nb_stream) GS_HIP(hipStreamWaitEvent(st, g->nb_done, 0));
+    gs::SelectShape sh{};
+    gs_model_transform_pod def;
+    if (!mt) {
+        gs_model_transform_pod_default(&def);
+        mt = &def;
+    }
+    gs::ModelTransform m;
+    std::memcpy(&m, mt, sizeof(m));
+    gs::model_transform_mat(m, sh.M);
+    const uint32_t *aos = (const uint32_t *)g->buf->ptr, *words = among ? (const uint32_t *)among->words : nullptr;
+    hipLaunchKernelGGL(gs::k_nb_bbox_partial, dim3(pgrid), dim3(256), 0, st, aos, pod_words, n, words, sh, partial);
+    hipLaunchKernelGGL(gs::k_bbox_final, dim3(1), dim3(256), 0, st, (const float *)partial, pgrid, bbox);
+    hipLaunchKernelGGL(gs::k_nb_keys, dim3(nblocks), dim3(256), 0, st, aos, pod_words, n, words, sh, (const float *)bbox, radius,
+                       (uint64_t *)k2[0], (uint32_t *)v2[0]);
+    GS_HIP(hipGetLastError());
+    int side = 0;
+    uint32_t passes = 0;
+    GS_TRY(sort_pairs_device<uint64_t>(dev, k2, v2, g->nb_ghist, g->nb_digit_totals, n, 64, st, side, passes));
+    const uint64_t *skeys = (const uint64_t *)k2[side];
+    const uint32_t *svals = (const uint32_t *)v2[side];
+    float *sx = (float *)k2[side ^ 1], *sy = sx + n, *sz = sy + n;      // 12 n bytes <= a8 + a4, the pair is contiguous
+    hipLaunchKernelGGL(gs::k_nb_gather, dim3(nblocks), dim3(256), 0, st, aos, pod_words, n, sh, skeys, svals, sx, sy, sz);
+    if (!counts) counts = plane;
+    const float rr = radius * radius;
+    if (mark)
+        hipLaunchKernelGGL(gs::k_nb_count<true>, dim3(nblocks), dim3(256), 0, st, skeys, svals, (const float *)sx, (const float *)sy,
+                           (const float *)sz, n, rr, cap, counts);
+    else
+        hipLaunchKernelGGL(gs::k_nb_count<false>, dim3(nblocks), dim3(256), 0, st, skeys, svals, (const float *)sx, (const float *)sy,
+                           (const float *)sz, n, rr, cap, counts);
+    GS_HIP(hipGetLastError());
+    if (plane_out) *plane_out = plane;
+    return GS_OK;
+}
+
+// the next call on another stream waits until this one has left the scratch
+static gs_status neighbor_scratch_release(gs_gaussians_buffer *g, hipStream_t st) {
+    if (!g->nb_done) GS_HIP(hipEventCreateWithFlags(&g->nb_done, hipEventDisableTiming));
+    GS_HIP(hipEventRecord(g->nb_done, st));
+    g->nb_stream = st;
+    return GS_OK;
+}
+
+extern "C" gs_status gs_gaussians_buffer_neighbor_counts(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *among,
+                                                         const gs_model_transform_pod *mt, float radius, uint32_t cap,
+                                                         gs_buffer *counts_out) {
+    if (!g || !counts_out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    GS_TRY(check_neighbor_radius(radius));
+    if (!cap) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "cap must be at least 1");
+    GS_TRY(check_buffer_selection(g, s, among));
+    const size_t len = gs_gaussians_buffer_len(g);
+    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
+    if (counts_out->dev != g->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (counts_out->bytes < len * 4)
+        return fail(GS_ERR_INVALID_ARGUMENT, counts_out->bytes, len * 4, 0, "the count plane has %zu bytes, %zu Gaussians need %zu",
+                    counts_out->bytes, len, len * 4);
+    if (!len) return GS_OK;
+    gs_device *dev = g->buf->dev;
+    GS_TRY(use_device(dev));
+    hipStream_t st = stream_of(dev, s);
+    // the event on every path: an enqueue that failed half-way has still left kernels on the scratch
+    const gs_status rc = neighbor_counts_enqueue(g, st, among, mt, radius, cap, false, (uint32_t *)counts_out->ptr, nullptr);
+    const gs_status ev = neighbor_scratch_release(g, st);
+    return rc != GS_OK ? rc : ev;
+}
+
+extern "C" gs_status gs_select_neighbors(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_selection *among,
+                                         const gs_model_transform_pod *mt, float radius, uint32_t min_count, uint32_t max_count,
+                                         gs_select_op op) {
+    if (!sel || !g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    GS_TRY(check_select_op(op));
+    GS_TRY(check_neighbor_radius(radius));
+    if (g->buf->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    GS_TRY(check_buffer_selection(g, s, among));
+    const size_t len = gs_gaussians_buffer_len(g);
+    if (len != sel->n) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
+    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
+    gs_device *dev = sel->dev;
+    GS_TRY(use_device(dev));
+    hipStream_t st = stream_of(dev, s);
+    if (!len) {
+        sel->generation = next_object_id();
+        return GS_OK;
+    }
+    const uint32_t n = (uint32_t)len;
+    if (min_count > max_count) {      // sel = sel op {}
+        sel->generation = next_object_id();
+        hipLaunchKernelGGL(gs::k_sel_range, dim3(sel->grid()), dim3(256), 0, st, sel->words, (uint32_t)sel->nwords, 0u, 0u, (uint32_t)op);
+        GS_HIP(hipGetLastError());
+        return GS_OK;
+    }
+    // a count above max_count only has to be known as such
+    const uint32_t cap = max_count == 0xffffffffu ? max_count : max_count + 1u;
+    uint32_t *plane = nullptr;
+    gs_status rc = neighbor_counts_enqueue(g, st, among, mt, radius, cap, true, nullptr, &plane);
+    if (rc == GS_OK) {      // only now does `sel` change
+        sel->generation = next_object_id();
+        hipLaunchKernelGGL(gs::k_nb_select, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)plane, n, min_count, max_count,
+                           sel->words, (uint32_t)op);
+        if (hipGetLastError() != hipSuccess) rc = fail(GS_ERR_HIP, 0, 0, 0, "k_nb_select could not be launched");
+    }
+    // the event on every path: an enqueue that failed half-way has still left kernels on the scratch
+    const gs_status ev = neighbor_scratch_release(g, st);
+    return rc != GS_OK ? rc : ev;
 }
