@@ -24,6 +24,40 @@ def copy_camera(src, dst_cls):
     return dst
 
 
+def bits(a):
+    """the uint32 view of a float32 (or uint32) array: what "bit for bit" compares"""
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def band_rows(band, H):
+    """pixel rows [y0, y1) of a band of tile rows (None: the whole image)"""
+    return (0, H) if band is None else (band[0] * 16, min(band[1] * 16, H))
+
+
+def pair_walk(k):
+    """A sequence over range(k), k * k + 1 long, in which every ordered pair (a, b), a == b included, occurs as two
+    consecutive elements exactly once: the de Bruijn sequence B(k, 2) (concatenated Lyndon words whose length divides 2,
+    in lexicographic order), closed by repeating its first element."""
+    seq, a = [], [0, 0, 0]
+
+    def db(t, p):
+        if t > 2:
+            if 2 % p == 0:
+                seq.extend(a[1:p + 1])
+            return
+        a[t] = a[t - p]
+        db(t + 1, p)
+        for j in range(a[t - p] + 1, k):
+            a[t] = j
+            db(t + 1, t)
+    db(1, 1)
+    return seq + seq[:1]
+
+
+def consecutive_pairs(seq):
+    return set(zip(seq[:-1], seq[1:]))
+
+
 def synth_pods(ob, sh, cov, n, first=0):
     g = synth.scene(n, first=first)
     return g, ob.pack(sh, cov, g)

@@ -25,7 +25,9 @@ class Planes:
         self.depth = gs.Buffer(device, data=np.full(H * W, POISON_DEPTH, dtype=np.float32))
         self.pick = gs.Buffer(device, data=np.full(H * W, POISON_PICK, dtype=np.uint32))
 
-    def poison(self, stream):
+    def poison(self, stream, image=False):
+        if image:       # a target that one renderer fills frame after frame
+            self.img.write(stream, 0, np.full(self.H * self.W * 4, np.float32(-7.0)))
         self.depth.write(stream, 0, np.full(self.H * self.W, POISON_DEPTH, dtype=np.float32))
         self.pick.write(stream, 0, np.full(self.H * self.W, POISON_PICK, dtype=np.uint32))
         stream.synchronize()

@@ -1,0 +1,544 @@
+"""One renderer, every frame-kind transition.  A gs_renderer carries a dozen pieces of state from one
+frame into the next (the ping-pong sides, list mode, the rounds of the last frame, the slot-mask cache ...); all of it may
+change how fast a frame is, never what it contains.  Here ONE renderer renders a sequence of KINDS — a kind is the whole
+description of a frame: buffer, image size, band, camera, transform, planes, selections and every request — in which every
+ordered pair of kinds, self-pairs included, occurs as consecutive frames (helpers.pair_walk: a de Bruijn sequence B(K, 2)),
+and every frame is compared bit for bit with the ORACLE's frame of its kind, computed once per kind.  Nothing here compares
+against another renderer or an earlier device frame.
+
+The same walk runs in a child process (this file as a script) under GS3D_BLEND_GROUPS=2 — the 8x8-block instantiations of
+k_blend_grouped — and under GS3D_BLEND_GROUPS=1 with GS3D_RANGES_IN_BLEND=1 — k_blend<MODE>; the switch is read once per
+process.  The child asserts every frame itself (it ends at its first mismatch) and leaves its frames in an .npz that the
+parent compares with its own cached oracle frames.
+
+The figures in KINDS' comments (V visible Gaussians, D pairs, the longest tile list) are the oracle's, asserted below
+without a GPU; the shapes are the smallest that still reach the paths named."""
+import os
+import subprocess
+import sys
+import types
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import helpers  # noqa: E402
+from helpers import band_rows, bits  # noqa: E402
+
+gpu = pytest.mark.gpu
+
+POISON = np.float32(-7.0)            # Planes' image poison
+ROUND1 = 2048
+N = 20000
+TINT_RGBA = (1.0, 0.25, 0.0, 0.5)
+SH_SINGLE, SH_NONE, ROT_SCALE, COV_HALF = 0, 3, 0, 2      # gs.SH_* / gs.COV3D_*
+
+# buffers, created once per walk.  P' holds P's Gaussians in index order; E is new_empty(device, pod, 0)
+BUFFERS = {
+    "P": dict(sh=SH_SINGLE, cov=ROT_SCALE, n=N, first=0),
+    "P'": dict(sh=SH_SINGLE, cov=ROT_SCALE, n=N, first=0, spatial=False),
+    "Q": dict(sh=SH_NONE, cov=COV_HALF, n=N, first=777, scale=40.0),
+    "R": dict(sh=SH_NONE, cov=ROT_SCALE, n=N, first=31, opacity=250, scale=10.0),
+    "S": dict(sh=SH_NONE, cov=COV_HALF, n=3000, first=0),
+    "E": dict(sh=SH_NONE, cov=ROT_SCALE, n=0),
+}
+
+
+def _kind(buf, W=100, H=70, band=None, cam=None, mode=0, std=3.0, aux=False, sel=False, sort=(-1, -1), rounds=(0, 0),
+          masks=1, background=None):
+    """every field of a frame: nothing is inherited from the frame before (sort = set_sort_mode, rounds = set_rounds,
+    masks = set_tile_masks)"""
+    return dict(buf=buf, W=W, H=H, band=band, cam=cam or {}, mode=mode, std=std, aux=aux, sel=sel, sort=sort, rounds=rounds,
+                masks=masks, background=background, sh_deg=3 if BUFFERS[buf]["sh"] != SH_NONE else 0)
+
+
+KINDS = {
+    # V 13 993, D 18 523, longest list 1 060: banded preprocess, the block test inside the kernel, G = 8 blend; partial tiles on
+    # both edges, a last tile row of 6 pixel rows
+    "plain": _kind("P"),
+    # V 7 620, D 9 549: a band's shape; block list on a shape's first frame; rows outside the band keep the poison
+    "band": _kind("P", band=(2, 4)),
+    # V 347, D 484: V < n / 2, so the next frame, whatever its kind, starts from use_list = true (History::newest_any)
+    "corner": _kind("P", cam=dict(target=(13, 7, -3), vfov_deg=25.0)),
+    # index order: last_order null, culled records written, LSD depth sort
+    "index": _kind("P'", sort=(0, -1)),
+    # V 18 161, D 154 605, longest list 6 968: plain's shape; k_preprocess; lists of many staging batches; 8 x the pairs
+    "fat": _kind("Q", sort=(1, -1)),
+    # no rect clipping in this mode; rect version 3 pinned (the oracle follows: ob.set_rect_version)
+    "ellipse": _kind("Q", mode=1, std=1.5, masks=0),
+    "point": _kind("P", mode=2),
+    # the AUX instantiations: depth + pick planes
+    "aux": _kind("P", aux=True),
+    # the slot-mask cache: 40 % hidden, 20 % tinted
+    "hide": _kind("P", sel=True),
+    # ... and THE SAME two Selection objects on another buffer of the same length: a mask gathered through P's mirror order
+    # must not serve Q (SlotMaskKey::buffer)
+    "hide_q": _kind("Q", sel=True),
+    # V 15 209, D 35 140: two rounds; unpartitioned after a kind of another shape (a sizing frame), partitioned after any
+    # kind of 20 000 Gaussians on the full 100 x 70 image, single-round ones included
+    "rounds": _kind("R", rounds=(1, ROUND1)),
+    # V 2 027, D 2 451, 6 tiles: another n and size — a sizing frame on entry and on exit; a tile sort of one pass leaves the
+    # pairs on the other side
+    "small": _kind("S", W=48, H=32),
+    # stage_empty_frame: both sorted sides := 0, image = background
+    "empty": _kind("E", background=(0.25, 0.5, 0.75)),
+}
+NAMES = list(KINDS)
+FIGURES = {      # kind: (V, D, longest tile list or None)
+    "plain": (13993, 18523, 1060), "band": (7620, 9549, None), "corner": (347, 484, None),
+    "fat": (18161, 154605, 6968), "rounds": (15209, 35140, None), "small": (2027, 2451, None), "empty": (0, 0, 0),
+}
+SAME_SHAPE_AS_ROUNDS = [k for k, v in KINDS.items() if BUFFERS[v["buf"]]["n"] == N and (v["W"], v["H"], v["band"]) == (100, 70, None)]
+
+
+def walk_sequence():
+    return [NAMES[i] for i in helpers.pair_walk(len(NAMES))]
+
+
+def selection_masks():
+    rng = np.random.default_rng(40)
+    return rng.random(N) < 0.4, rng.random(N) < 0.2          # hidden, tinted
+
+
+# ------------------------------------------------------------------------------------------------
+# the oracle's frame of every kind (no GPU)
+# ------------------------------------------------------------------------------------------------
+
+_host_cache, _oracle_cache = {}, {}
+
+
+def host_buffer(ob, b):
+    """Gaussians, records and the mirror order of a freshly created buffer (the walk asserts that the
+    device's order IS this one before it renders anything)"""
+    if b not in _host_cache:
+        import synth
+        spec = BUFFERS[b]
+        n = spec["n"]
+        if n:
+            g = synth.scene(n, first=spec["first"])
+            if "opacity" in spec:
+                g["color"][:, 3] = spec["opacity"]
+            if "scale" in spec:
+                g["scale"] *= np.float32(spec["scale"])
+            pods = ob.pack(spec["sh"], spec["cov"], g)
+        else:
+            g, pods = np.zeros(0, dtype=ob.GAUSSIAN_DTYPE), np.zeros(0, dtype=np.uint8)
+        spatial = spec.get("spatial", True) and n > 1
+        order = ob.spatial_order(spec["sh"], spec["cov"], pods) if spatial else np.arange(n, dtype=np.uint32)
+        _host_cache[b] = dict(g=g, pods=pods, order=order)
+    return _host_cache[b]
+
+
+def _recolour(proj, tinted):
+    from test_gpu_selection import _tint32
+    for ch, t in zip("rgb", TINT_RGBA[:3]):
+        proj[ch][tinted] = _tint32(proj[ch][tinted], TINT_RGBA[3], t)
+
+
+def kind_transforms(ob, name):
+    k = KINDS[name]
+    ogt = ob.gaussian_transform(mode=k["mode"], sh_deg=k["sh_deg"], max_std_dev=k["std"])
+    omt = ob.model_transform()
+    ocam = helpers.default_camera(ob, k["W"], k["H"], **k["cam"])
+    if k["background"] is not None:
+        ocam.background[:] = list(k["background"])
+    return ogt, omt, ocam
+
+
+def oracle_frame(ob, name):
+    """built as tests/test_gpu_render.py's _oracle_frame is, order = the buffer's mirror order; a selection kind through its
+    twin (hidden: opacity byte 0) and test_tint's recolouring; the aux kind with its depth plane and the float64 pick walk"""
+    if name in _oracle_cache:
+        return _oracle_cache[name]
+    from test_gpu_render_aux import _oracle_depth, _witness
+    from test_gpu_selection import Scene
+    k = KINDS[name]
+    spec, hb = BUFFERS[k["buf"]], host_buffer(ob, k["buf"])
+    sh, cov, n, W, H = spec["sh"], spec["cov"], spec["n"], k["W"], k["H"]
+    pods = hb["pods"]
+    hidden, tinted = selection_masks()
+    if k["sel"]:
+        pods = Scene.twin_pods(types.SimpleNamespace(pods=pods, n=n), hidden)
+    ogt, omt, ocam = kind_transforms(ob, name)
+    tiles_x, tiles_y = (W + 15) // 16, (H + 15) // 16
+    version = ob.rect_version()
+    try:
+        ob.set_rect_version(4 if k["masks"] else 3)
+        proj, tiles = ob.preprocess(sh, cov, pods, ogt, omt, ocam, band=k["band"])
+        if k["sel"]:
+            _recolour(proj, tinted)
+        keys, idx = ob.build_keys(proj, tiles, tiles_x, order=hb["order"])
+    finally:
+        ob.set_rect_version(version)
+    skeys, sidx = ob.sort_pairs(keys, idx)
+    ranges = ob.tile_ranges(skeys, tiles_x * tiles_y)
+    rgba = ob.blend(proj, sidx, ranges, ocam, band=k["band"], gt=ogt)
+    tl = np.asarray(tiles)
+    o = dict(proj=proj, tiles=tl, keys=skeys, idx=sidx, ranges=ranges, rgba=rgba, V=int((tl > 0).sum()),
+             D=int(tl.astype(np.uint64).sum()), longest=int((ranges[:, 1] - ranges[:, 0]).max()), tiles_x=tiles_x,
+             num_tiles=tiles_x * tiles_y, ogt=ogt, omt=omt, ocam=ocam)
+    if k["aux"]:
+        o["depth"] = _oracle_depth(ob, proj, sidx, ranges, ocam, ogt, k["band"])
+        o["pick"], o["pick_ambiguous"] = _witness(proj, sidx, ranges, W, H, tiles_x, float(np.float32(1.0) - np.float32(0.5)))
+    if k["rounds"][0] == 1:
+        o["finished"], o["open"] = round1_coverage(o, hb["order"], W, H, k["rounds"][1])
+    _oracle_cache[name] = o
+    return o
+
+
+def round1_coverage(o, order, W, H, round1):
+    """(certainly finished, certainly open) tiles after a round 1 of the nearest `round1` visible Gaussians (an
+    unpartitioned frame's): a float64 walk of the oracle's lists restricted to them.  A pixel that meets a step with
+    T (1 - alpha) < 0.999e-4 has certainly stopped; one that never meets a step below 1.001e-4 is certainly still open
+    (f32 rounding does not cross 0.1 %); a step in between is taken as not stopping, and leaves the pixel undecided unless a
+    later step stops it for certain — which the next active step does, whichever way the kernel decided: it multiplies a T
+    of ~1e-4 by at most 1 - 1/255.  A tile is finished when every in-image pixel has stopped, open when one is open; a tile
+    with an undecided pixel and no open one is neither."""
+    proj, sidx, ranges = o["proj"], o["idx"], o["ranges"]
+    vis = order[o["tiles"][order] > 0]
+    near = vis[np.argsort(proj["depth"][vis], kind="stable")][:round1]
+    member = np.zeros(len(proj), bool)
+    member[near] = True
+    p = {f: proj[f].astype(np.float64) for f in ("mx", "my", "ca", "cb", "cc", "opacity")}
+    finished = opened = 0
+    for t in range(ranges.shape[0]):
+        tx, ty = t % o["tiles_x"], t // o["tiles_x"]
+        xs, ys = np.arange(tx * 16, min(tx * 16 + 16, W)), np.arange(ty * 16, min(ty * 16 + 16, H))
+        px, py = [a.ravel() for a in np.meshgrid(xs + 0.5, ys + 0.5)]
+        T = np.ones(px.shape)
+        stopped = np.zeros(px.shape, bool)
+        maybe = np.zeros(px.shape, bool)
+        for j in range(int(ranges[t, 0]), int(ranges[t, 1])):
+            g = int(sidx[j])
+            if not member[g]:
+                continue
+            dx, dy = p["mx"][g] - px, p["my"][g] - py
+            power = p["ca"][g] * dx * dx + p["cb"][g] * dx * dy + p["cc"][g] * dy * dy
+            alpha = np.minimum(0.99, p["opacity"][g] * np.exp(power))
+            act = ~stopped & (power <= 0.0) & (alpha >= 1.0 / 255.0)
+            Tn = T * (1.0 - alpha)
+            maybe |= act & (Tn < 1.001e-4)
+            sure = act & (Tn < 0.999e-4)
+            stopped |= sure
+            T = np.where(act & ~sure, Tn, T)
+        finished += int(stopped.all())
+        opened += int((~maybe).any())
+    return finished, opened
+
+
+def test_the_sequence_covers_every_ordered_pair():
+    for k in (1, 2, 3, 12, 13):
+        seq = helpers.pair_walk(k)
+        assert len(seq) == k * k + 1 and set(seq) == set(range(k))
+        assert helpers.consecutive_pairs(seq) == {(a, b) for a in range(k) for b in range(k)}
+    seq = walk_sequence()
+    assert len(NAMES) == 13 and len(seq) == 170
+    assert helpers.consecutive_pairs(seq) == {(a, b) for a in NAMES for b in NAMES}
+
+
+@pytest.mark.parametrize("name", list(FIGURES))
+def test_oracle_figures_of_the_kinds(ob, name):
+    """the paths a kind is there for depend on these: V < n / 2 (corner), D beyond plain's capacity (fat), lists of many
+    staging batches, one tile-sort pass (small)"""
+    o = oracle_frame(ob, name)
+    V, D, longest = FIGURES[name]
+    assert (o["V"], o["D"]) == (V, D)
+    if longest is not None:
+        assert o["longest"] == longest
+    if name == "corner":
+        assert o["V"] < N // 2
+    if name == "small":
+        assert o["num_tiles"] == 6
+    if name == "fat":
+        cap = 18523 + 18523 // 4 + 65536       # gsp::capacity_for(plain's D)
+        assert cap == 88689 and o["D"] > cap and o["longest"] > 8 * 128
+
+
+def test_rounds_kind_finishes_some_tiles_and_leaves_others_open(ob):
+    """the coverage condition of `rounds`: round 1 must finish some tiles and leave others open, or the kind exercises no
+    resumption.  Of the 35 tiles 24 come out certainly finished and 11 certainly open; a walk that ends at the first step
+    below 1e-4 and calls it undecided when it lies within 0.1 % of it leaves 11 of the 24 undecided (pixels that hover just
+    above 1e-4 and are taken below it by a small alpha) — round1_coverage walks on, and their next step decides them."""
+    o = oracle_frame(ob, "rounds")
+    print("rounds: certainly finished %d, certainly open %d of %d tiles" % (o["finished"], o["open"], o["num_tiles"]))
+    assert o["num_tiles"] == 35 and o["V"] > 2 * ROUND1
+    assert o["finished"] >= 1 and o["open"] >= 1
+    assert o["finished"] + o["open"] <= o["num_tiles"]
+
+
+# ------------------------------------------------------------------------------------------------
+# the walk
+# ------------------------------------------------------------------------------------------------
+
+class Rig:
+    """buffers, selections and image planes of a walk: created once, alive until release()"""
+
+    def __init__(self, gs, ob, device, stream):
+        from test_gpu_render_aux import Planes
+        from test_gpu_selection import Scene
+        self.gs, self.ob, self.device, self.stream = gs, ob, device, stream
+        self.scenes, self.bufs = {}, {}
+        for b, spec in BUFFERS.items():
+            hb = host_buffer(ob, b)
+            if spec["n"]:
+                sc = Scene(gs, ob, device, stream, spec["sh"], spec["cov"], spec["n"], 16, 16, spatial=spec.get("spatial", True),
+                           g=hb["g"])
+                assert np.array_equal(np.asarray(sc.pods, dtype=np.uint8).reshape(-1), hb["pods"]), "product pack != oracle pack"
+                self.scenes[b], self.bufs[b] = sc, sc.buf
+            else:
+                self.bufs[b] = gs.GaussiansBuffer.new_empty(device, gs.GaussianPod(spec["sh"], spec["cov"]), 0)
+            order = self.bufs[b].download_order(stream)
+            assert np.array_equal(order, hb["order"]), "buffer %s: the mirror order is not the oracle's spatial order" % b
+        self.planes = {(W, H): Planes(gs, device, W, H) for W, H in sorted({(k["W"], k["H"]) for k in KINDS.values()})}
+        hidden, tinted = selection_masks()
+        self.hide, self.tint = self.scenes["P"].selection(hidden), self.scenes["P"].selection(tinted)
+        self.frames = {}
+        for name in KINDS:
+            ogt, omt, ocam = kind_transforms(ob, name)
+            self.frames[name] = (gs.GaussianTransformPod.from_buffer_copy(bytes(ogt)), gs.ModelTransformPod.from_buffer_copy(bytes(omt)),
+                                 helpers.copy_camera(ocam, gs.Camera))
+
+    def render(self, r, name, check=True):
+        """one frame of a kind on renderer r: all three requests set, the target (and the aux planes) poisoned first"""
+        k = KINDS[name]
+        pl = self.planes[(k["W"], k["H"])]
+        pl.poison(self.stream, image=True)
+        r.set_rounds(*k["rounds"])
+        r.set_sort_mode(*k["sort"])
+        r.set_tile_masks(k["masks"])
+        kw = dict(band=k["band"], check=check)
+        if k["aux"]:
+            kw.update(depth_device_ptr=pl.depth.device_ptr(), pick_device_ptr=pl.pick.device_ptr(), pick_threshold=0.5)
+        if k["sel"]:
+            kw.update(hide=self.hide, tint=self.tint, tint_rgba=TINT_RGBA)
+        gt, mt, cam = self.frames[name]
+        fr = r.render(self.stream, self.bufs[k["buf"]], gt, mt, cam, pl.img.device_ptr(), **kw)
+        self.stream.synchronize()
+        return fr
+
+    def planes_of(self, name):
+        k = KINDS[name]
+        return self.planes[(k["W"], k["H"])].get(self.stream)
+
+    def release(self):
+        self.hide.destroy()
+        self.tint.destroy()
+        for pl in self.planes.values():
+            pl.release()
+        for sc in self.scenes.values():
+            sc.release()
+        self.bufs["E"].destroy()
+
+
+def check_image(name, o, rgba, ctx):
+    k = KINDS[name]
+    y0, y1 = band_rows(k["band"], k["H"])
+    bad = bits(rgba[y0:y1]) != bits(o["rgba"][y0:y1])
+    assert not bad.any(), "%s: %d words of the image differ from the oracle's frame" % (ctx, bad.sum())
+    assert (rgba[:y0] == POISON).all() and (rgba[y1:] == POISON).all(), "%s: rows outside the band were written" % ctx
+
+
+def check_aux_planes(gs_pick_none, o, rgba, depth, pick, ctx):
+    bad = bits(depth) != bits(o["depth"])
+    assert not bad.any(), "%s: %d words of the depth plane differ from the oracle's" % (ctx, bad.sum())
+    # exact: 1 - T is exact for T >= 0.5 (tests/test_gpu_render_aux.py)
+    assert np.array_equal(pick != gs_pick_none, o["rgba"][..., 3] >= 0.5), "%s: pick != NONE <=> alpha >= 0.5 broken" % ctx
+    bad = (o["pick"] != pick.astype(np.uint64)) & ~o["pick_ambiguous"]
+    assert not bad.any(), "%s: the pick plane differs from the float64 walk at %d pixels" % (ctx, bad.sum())
+
+
+def check_taps(r, fr, name, o, ctx):
+    """single-round frames: D, the sorted keys and caller indices, tiles touched and the records of the visible Gaussians"""
+    n = BUFFERS[KINDS[name]["buf"]]["n"]
+    assert fr.pairs == o["D"], "%s: %d pairs, the oracle %d" % (ctx, fr.pairs, o["D"])
+    keys, idx = r.download_sorted()
+    assert np.array_equal(keys, o["keys"]), "%s: sorted keys differ" % ctx
+    assert np.array_equal(idx, o["idx"]), "%s: sorted indices differ" % ctx
+    proj, tiles = r.download_projected(n)
+    assert np.array_equal(tiles, o["tiles"]), "%s: tiles touched differ at %d Gaussians" % (ctx, (tiles != o["tiles"]).sum())
+    keep = o["tiles"] > 0
+    assert proj[keep].tobytes() == o["proj"][keep].tobytes(), "%s: projected records of visible Gaussians differ" % ctx
+
+
+def expected_rounds(name, groups):
+    """plan_rounds refuses two rounds under GS3D_BLEND_GROUPS=1 (k_blend<MODE> cannot resume)"""
+    return 2 if KINDS[name]["rounds"][0] == 1 and groups != 1 else 1
+
+
+def walk(gs, ob, device, stream, groups=0, record=None, seq=None):
+    """groups: GS3D_BLEND_GROUPS of this process (0: unset).  record: a dict that receives every frame's planes and figures.
+    seq: a short sequence of kinds instead of the whole walk."""
+    whole = seq is None
+    if whole:
+        seq = walk_sequence()
+        assert helpers.consecutive_pairs(seq) == {(a, b) for a in NAMES for b in NAMES}, "the walk misses a transition"
+    oracle = {name: oracle_frame(ob, name) for name in dict.fromkeys(seq)}
+    if "rounds" in oracle:
+        assert oracle["rounds"]["finished"] >= 1 and oracle["rounds"]["open"] >= 1, "round 1 resumes nothing"
+    rig = Rig(gs, ob, device, stream)
+    r = gs.Renderer(device)
+    partitioned_seen = set()
+    prev = "(new renderer)"
+    for i, name in enumerate(seq):
+        ctx = "frame %d, %s -> %s" % (i, prev, name)
+        k, o = KINDS[name], oracle[name]
+        fr = rig.render(r, name)
+        rgba, depth, pick = rig.planes_of(name)
+        si = r.sort_info()
+        check_image(name, o, rgba, ctx)
+        assert fr.flags == 0 and fr.visible == o["V"], "%s: flags %#x, %d visible, the oracle %d" % (ctx, fr.flags, fr.visible, o["V"])
+        assert si.rounds == expected_rounds(name, groups), "%s: %d rounds" % (ctx, si.rounds)
+        if si.rounds == 1:
+            check_taps(r, fr, name, o, ctx)
+        else:
+            assert si.round1 == ROUND1, "%s: round 1 of %d" % (ctx, si.round1)
+            partitioned_seen.add(int(si.partitioned))
+            if prev in SAME_SHAPE_AS_ROUNDS:
+                assert si.partitioned == 1, "%s: a frame of a known shape must be partitioned" % ctx
+            elif prev != "empty":       # (an empty frame leaves the shape of the frame before it)
+                assert si.partitioned == 0, "%s: a sizing frame cannot be partitioned" % ctx
+            # a partitioned round 1 ends at a digit boundary behind the nearest ROUND1: it can only finish more tiles
+            hi = o["num_tiles"] - o["open"] if si.partitioned == 0 else o["num_tiles"]
+            assert o["finished"] <= si.tiles_done <= hi, "%s: round 1 finished %d tiles, expected %d..%d" % (
+                ctx, si.tiles_done, o["finished"], hi)
+        if k["aux"]:
+            check_aux_planes(gs.PICK_NONE, o, rgba, depth, pick, ctx)
+        if record is not None:
+            record["f%03d/rgba" % i] = rgba
+            record["f%03d/info" % i] = np.array([fr.visible, fr.pairs, si.rounds, si.round1, si.tiles_done, si.partitioned],
+                                                dtype=np.int64)
+            if k["aux"]:
+                record["f%03d/depth" % i], record["f%03d/pick" % i] = depth, pick
+        prev = name
+    if whole and groups != 1:
+        assert partitioned_seen == {0, 1}, "two-round frames were partitioned: %s (both must occur)" % sorted(partitioned_seen)
+    if record is not None:
+        record["seq"] = np.array([NAMES.index(s) for s in seq], dtype=np.int64)
+    r.destroy()
+    rig.release()
+
+
+@gpu
+def test_every_transition_on_one_renderer(gs, ob, device, stream):
+    walk(gs, ob, device, stream, groups=int(os.environ.get("GS3D_BLEND_GROUPS", "0")))
+
+
+@gpu
+def test_one_selection_pair_on_two_buffers_of_one_length(gs, ob, device, stream):
+    """the walk's hide <-> hide_q transitions on their own: the renderer's slot-ordered copies of the two masks were gathered
+    through P's mirror order; Q has the same length, the selections the same generation — only SlotMaskKey::buffer tells
+    the frames apart"""
+    walk(gs, ob, device, stream, seq=["hide", "hide_q", "hide", "hide", "hide_q"])
+
+
+@gpu
+def test_buffer_swap_overflows_an_unchanged_shape(gs, ob, device, stream):
+    """`plain` sizes the pair buffers: stage_sizing reserves max(gsp::capacity_for(D), the plan's want_capacity), and a new
+    renderer's want_capacity is 0, so the capacity is capacity_for(18 523) = 88 689.  `fat` is the same FrameShape (n, size,
+    band) with D = 154 605: no sizing frame, the pipelined frame is skipped, and the renderer recovers.  (The camera-move
+    overflow is test_pair_capacity_overflow_is_flagged_and_recovered; here the BUFFER changes under a known shape.)"""
+    o_plain, o_fat = oracle_frame(ob, "plain"), oracle_frame(ob, "fat")
+    rig = Rig(gs, ob, device, stream)
+    r = gs.Renderer(device)
+    fr = rig.render(r, "plain")
+    assert fr.flags == 0 and fr.pairs == o_plain["D"] and fr.pair_capacity == 88689
+    check_image("plain", o_plain, rig.planes_of("plain")[0], "plain (sizing frame)")
+    assert o_fat["D"] > fr.pair_capacity
+    assert rig.render(r, "fat", check=False) is None
+    with pytest.raises(gs.PairCapacityError) as e:
+        r.wait_frame()
+    assert e.value.pairs == o_fat["D"] and e.value.capacity == 88689
+    assert (rig.planes_of("fat")[0] == POISON).all(), "a skipped frame must leave the image untouched"
+    prev = "fat (skipped)"
+    for name in ("fat", "plain", "fat"):
+        ctx = "%s -> %s" % (prev, name)
+        fr = rig.render(r, name, check=True)
+        assert fr.flags == 0 and fr.visible == oracle_frame(ob, name)["V"], ctx
+        check_image(name, oracle_frame(ob, name), rig.planes_of(name)[0], ctx)
+        check_taps(r, fr, name, oracle_frame(ob, name), ctx)
+        prev = name
+    r.destroy()
+    rig.release()
+
+
+# ------------------------------------------------------------------------------------------------
+# the same walk under GS3D_BLEND_GROUPS = 2 and = 1: one child process per setting, one at a time
+# ------------------------------------------------------------------------------------------------
+
+CHILD_ENV = {2: {"GS3D_BLEND_GROUPS": "2"}, 1: {"GS3D_BLEND_GROUPS": "1", "GS3D_RANGES_IN_BLEND": "1"}}
+_child_state = {"dead": None}        # the child that ended on a signal or a timeout: nothing further is started on the GPU
+
+
+def _child(groups, out):
+    for key, val in (("GS3D_TILE_MASKS", "1"), ("GS3D_ROUNDS", "0"), ("GS3D_ROUND_PARTITION", "1")):      # tests/conftest.py's pins
+        os.environ.setdefault(key, val)
+    assert os.environ.get("GS3D_BLEND_GROUPS") == str(groups)
+    import wgpu_3dgs_core_amd as gs
+    from oracle import binding as ob
+    ob.build()
+    ob.lib()
+    dev = gs.Device(0)
+    st = dev.create_stream()
+    record = {}
+    walk(gs, ob, dev, st, groups=groups, record=record)      # an AssertionError ends the child: nonzero, the message on stdout
+    np.savez(out, **record)
+    st.close()
+    dev.close()
+
+
+@pytest.fixture(scope="module")
+def child_frames(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("renderer_walk")
+
+    def run(groups):
+        assert _child_state["dead"] is None, "not started: the GS3D_BLEND_GROUPS=%s child ended abnormally" % _child_state["dead"]
+        out = os.path.join(str(tmp), "walk_g%d.npz" % groups)
+        env = dict(os.environ)
+        env.update(CHILD_ENV[groups])
+        try:
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), str(groups), out], cwd=ROOT, env=env,
+                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+        except subprocess.TimeoutExpired:
+            _child_state["dead"] = groups
+            raise
+        if res.returncode < 0 or res.returncode >= 124:      # a signal, an abort, a time limit
+            _child_state["dead"] = groups
+        assert res.returncode == 0, res.stdout[-3000:]
+        return dict(np.load(out))
+    return run
+
+
+@gpu
+@pytest.mark.parametrize("groups", [2, 1])
+def test_every_transition_under_the_other_blend_kernels(gs, ob, child_frames, groups):
+    """GS3D_BLEND_GROUPS=2: k_blend_grouped<MODE, 2, ROUNDS, AUX>; = 1 (with the ranges searched in the blend, as
+    tests/test_gpu_switches.py pairs them): k_blend<MODE>, one round for `rounds`, and the G = 4 aux kernel for `aux`"""
+    rec = child_frames(groups)
+    seq = [NAMES[i] for i in rec["seq"]]
+    assert helpers.consecutive_pairs(seq) == {(a, b) for a in NAMES for b in NAMES}, "the child's walk misses a transition"
+    prev = "(new renderer)"
+    partitioned_seen = set()
+    for i, name in enumerate(seq):
+        ctx = "GS3D_BLEND_GROUPS=%d, frame %d, %s -> %s" % (groups, i, prev, name)
+        o = oracle_frame(ob, name)
+        rgba = rec["f%03d/rgba" % i]
+        visible, pairs, rounds, round1, tiles_done, partitioned = [int(x) for x in rec["f%03d/info" % i]]
+        check_image(name, o, rgba, ctx)
+        assert visible == o["V"] and rounds == expected_rounds(name, groups), ctx
+        if rounds == 1:
+            assert pairs == o["D"], ctx
+        else:
+            assert round1 == ROUND1 and tiles_done >= o["finished"], ctx
+            partitioned_seen.add(partitioned)
+        if KINDS[name]["aux"]:
+            check_aux_planes(gs.PICK_NONE, o, rgba, rec["f%03d/depth" % i], rec["f%03d/pick" % i], ctx)
+        prev = name
+    assert partitioned_seen == ({0, 1} if groups == 2 else set())
+
+
+if __name__ == "__main__":
+    _child(int(sys.argv[1]), sys.argv[2])
