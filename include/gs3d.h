@@ -70,7 +70,12 @@ enum {
     /* gs_renderer_wait_frame: the frame produced more (tile, Gaussian) pairs than the renderer's pair
      * buffers hold (a = pairs, b = capacity).  The frame was SKIPPED: the image was not written (it
      * keeps what it held) rather than blended without its farthest pairs.  The next frame grows the
-     * buffers: render again. */
+     * buffers: render again.
+     * A two-round frame (gs_renderer_set_rounds) bounds each ROUND on its own, usually far below the
+     * buffers' capacity; a = the true pair count of the round that outgrew the bound (round 1 if both
+     * did), b = that bound, and the message names the round.  Skipped by round 1, the image was not
+     * written; skipped by round 2, the frame's band of the image (and of the aux planes) holds round 1's
+     * intermediate pixel state — not a frame: do not present it.  The next frame has the larger bound. */
     GS_ERR_PAIR_CAPACITY = -26,
     /* gs_renderer_wait_frame: the watchdog of the radix sort's LDS-atomic rank fired in this frame (an order
      * assumption about returning LDS atomics that the hardware documents do not promise; probed at
@@ -603,6 +608,11 @@ gs_status gs_renderer_stats(gs_renderer *r, gs_frame_stats *out);
  * image with missing splats is ever written — gs_renderer_wait_frame reports GS_ERR_PAIR_CAPACITY
  * (flags bits 0 and 1) and the next gs_render_frame has the larger buffers: a viewer that presents a
  * frame only after wait_frame / flags == 0 shows the previous frame once more, never a wrong one.
+ * A two-round frame (gs_renderer_set_rounds) is skipped in the same way when one of its ROUNDS outgrows
+ * the per-round bound taken from the previous two-round frame's report, with one difference: skipped
+ * by its second round, the target is NOT untouched — its band holds the first round's intermediate
+ * pixel state (the known defect described at gs_renderer_set_rounds).  The flags, the error and the
+ * recovery in the next frame are the same, and so is the viewer's rule: present on flags == 0 only.
  *
  * Frames in flight: a renderer owns the scratch buffers of ONE frame, so consecutive frames on one
  * renderer run one after the other: in stream order on one stream, and when a frame is submitted on a
@@ -657,8 +667,9 @@ typedef struct gs_frame_result {
     uint64_t visible;         /* V */
     uint64_t pairs;           /* D (the true count, also when it exceeded the capacity) */
     uint64_t pair_capacity;   /* pairs the renderer's buffers hold */
-    uint32_t flags;           /* bit 0: pair capacity exceeded; bit 1: the frame was skipped (image not written);
-                               * bit 2: the rank watchdog fired (GS_ERR_RANK_ORDER) */
+    uint32_t flags;           /* bit 0: pair capacity exceeded; bit 1: the frame was skipped (image not written — but a
+                               * two-round frame skipped by its second round leaves the first round's pixel state in
+                               * its band: GS_ERR_PAIR_CAPACITY); bit 2: the rank watchdog fired (GS_ERR_RANK_ORDER) */
     uint32_t launches;        /* kernel launches the frame enqueued (after the repack) */
 } gs_frame_result;
 
@@ -700,8 +711,12 @@ gs_status gs_renderer_set_tile_masks(gs_renderer *r, int32_t mode);
  * rendered first; its blend marks the finished tiles and leaves the pixel state of the others in the image; the second
  * round drops every Gaussian whose rect (at most 3 x 3 tiles) lies in finished tiles and resumes the blend.  The image is
  * the single round's bit for bit; `pairs` of the frame result counts what was emitted (fewer), and the sorted / range
- * taps (gs_renderer_download_sorted, _ranges) refuse such a frame (GS_ERR_INVALID_ARGUMENT).  A frame flagged SKIPPED by its
- * second round has part of the first round's state in the image.  mode: 1 / 0 pin two rounds / one, -1 the renderer chooses
+ * taps (gs_renderer_download_sorted, _ranges) refuse such a frame (GS_ERR_INVALID_ARGUMENT).  Each round is bounded by the
+ * pairs a round of the previous two-round frame emitted (twice the larger round, with head room; the buffers' capacity
+ * without such a report), and a round that outgrows the bound skips the frame (GS_ERR_PAIR_CAPACITY).  Known defect: a
+ * frame flagged SKIPPED by its SECOND round has the first round's state in its band of the image — rgb = the first
+ * round's colour sums, alpha = a finished pixel's alpha or the raw transmittance, negated once the pixel has stopped
+ * (tests/test_gpu_round_bounds.py pins exactly this); skipped by its first round, the image is untouched.  mode: 1 / 0 pin two rounds / one, -1 the renderer chooses
  * (GS3D_ROUNDS=0/1 and GS3D_ROUND1=<count> pin it for every renderer of the process). */
 gs_status gs_renderer_set_rounds(gs_renderer *r, int32_t mode, uint32_t first_round);
 

@@ -34,6 +34,36 @@ def band_rows(band, H):
     return (0, H) if band is None else (band[0] * 16, min(band[1] * 16, H))
 
 
+POISON = np.float32(-7.0)            # what the frame tests pre-fill an image with
+
+
+def capacity_for(d):
+    """gsp::capacity_for (wgpu-3dgs-core_amd/csrc/gs_policy.h), restated: the pair capacity for a frame expected to produce
+    d pairs — 25 % head room and a floor of 65536"""
+    return d + d // 4 + 65536
+
+
+def deep_scene(n, first=4242, opacity=250, scale=3.5):
+    """layers of nearly opaque splats: most tiles are finished long before their lists end"""
+    g = synth.scene(n, first=first)
+    g["color"][:, 3] = opacity
+    g["scale"] *= np.float32(scale)
+    return g
+
+
+def round_setup(gs, ob, g, W, H, sh, cov, mode=0, **cam_kw):
+    """pods and the oracle's and the product's transforms and camera of a scene of the two-round tests"""
+    pod = gs.GaussianPod(sh, cov)
+    pods = pod.from_gaussian(g)
+    ogt = ob.gaussian_transform(sh_deg=0, mode=mode)
+    omt = ob.model_transform()
+    ocam = default_camera(ob, W, H, **cam_kw)
+    gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
+    mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
+    cam = copy_camera(ocam, gs.Camera)
+    return pod, pods, ogt, omt, ocam, gt, mt, cam
+
+
 def pair_walk(k):
     """A sequence over range(k), k * k + 1 long, in which every ordered pair (a, b), a == b included, occurs as two
     consecutive elements exactly once: the de Bruijn sequence B(k, 2) (concatenated Lyndon words whose length divides 2,

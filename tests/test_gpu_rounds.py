@@ -6,29 +6,9 @@ import numpy as np
 import pytest
 
 import helpers
+from helpers import deep_scene as _deep_scene, round_setup as _setup
 
 pytestmark = pytest.mark.gpu
-
-
-def _deep_scene(n, first=4242, opacity=250, scale=3.5):
-    """layers of nearly opaque splats: most tiles are finished long before their lists end"""
-    import synth
-    g = synth.scene(n, first=first)
-    g["color"][:, 3] = opacity
-    g["scale"] *= np.float32(scale)
-    return g
-
-
-def _setup(gs, ob, g, W, H, sh, cov, mode=0, **cam_kw):
-    pod = gs.GaussianPod(sh, cov)
-    pods = pod.from_gaussian(g)
-    ogt = ob.gaussian_transform(sh_deg=0, mode=mode)
-    omt = ob.model_transform()
-    ocam = helpers.default_camera(ob, W, H, **cam_kw)
-    gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
-    mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
-    cam = helpers.copy_camera(ocam, gs.Camera)
-    return pod, pods, ogt, omt, ocam, gt, mt, cam
 
 
 def _render(gs, device, stream, buf, gt, mt, cam, rounds, band=None, masks=None, renderer=None, frames=1):

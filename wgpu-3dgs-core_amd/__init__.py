@@ -142,7 +142,11 @@ class PairOverflowError(GsError):
 
 class PairCapacityError(GsError):
     """gs_renderer_wait_frame: the frame produced more pairs than the renderer's buffers hold and was
-    SKIPPED (its image was not written).  The next frame grows the buffers: render again."""
+    SKIPPED (its image was not written).  The next frame grows the buffers: render again.
+    A two-round frame bounds each round on its own: `pairs` is then the count of the round that outgrew
+    the bound (round 1 if both did), `capacity` that bound, and the message names the round.  Skipped by
+    round 1, the image was not written; skipped by round 2, the frame's band holds round 1's
+    intermediate pixel state (a known defect, include/gs3d.h at gs_renderer_set_rounds): not a frame."""
     code = -26
 
     def __init__(self, info):

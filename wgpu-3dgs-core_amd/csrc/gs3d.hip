@@ -1616,6 +1616,7 @@ struct gs_renderer {
     int rounds_req = -1;                  // gs_renderer_set_rounds: -1 the renderer decides, 0 one round, 1 two
     uint32_t round1_req = 0;              // ... Gaussians of round 1 (0: a quarter of the visible ones)
     uint32_t round1 = 0;                  // Gaussians the last two-round frame's first round covered
+    uint32_t frame_capacity = 0;          // the pair bound the last frame's rounds were planned with (FramePlan::capacity)
     uint8_t done_rounds[2] = {1, 1};      // the rounds of the frames behind the two result blocks, and their round-1 lengths
     uint32_t done_round_k[2] = {0, 0};
     bool wt_pairs = true;                 // k_pairs_emit stores write-through (gs::store16)
@@ -1843,11 +1844,28 @@ extern "C" gs_status gs_renderer_wait_frame(gs_renderer *r, gs_frame_result *out
                     "the LDS-atomic rank of the radix sort returned an out-of-order value in this frame: its blend order "
                     "may be wrong; the device has been switched to the ballot-based rank: render again");
     }
-    if (fr.flags & gs::FRAME_FLAG_PAIR_OVERFLOW)
+    if (fr.flags & gs::FRAME_FLAG_PAIR_OVERFLOW) {
+        if (r->two_round) {
+            // each round of a two-round frame is bounded on its own (gsp::plan_round_capacity): the round that outgrew the
+            // bound, its true count and the bound — not the frame's total against the buffers, which may well hold it
+            const uint64_t bound = r->frame_capacity, d1 = fr.pairs_round1;
+            const uint64_t d2 = fr.pairs_total > d1 ? fr.pairs_total - d1 : 0;
+            if (d1 > bound)
+                return fail(GS_ERR_PAIR_CAPACITY, d1, bound, 0,
+                            "round 1 of the two-round frame produced %llu (tile, Gaussian) pairs, a round's bound was %llu: the "
+                            "frame was skipped (the image was not written); render again (the next frame has a larger bound)",
+                            (unsigned long long)d1, (unsigned long long)bound);
+            return fail(GS_ERR_PAIR_CAPACITY, d2, bound, 0,
+                        "round 2 of the two-round frame produced %llu (tile, Gaussian) pairs, a round's bound was %llu: the "
+                        "frame was skipped (its band holds round 1's pixel state, not a frame); render again (the next frame "
+                        "has a larger bound)",
+                        (unsigned long long)d2, (unsigned long long)bound);
+        }
         return fail(GS_ERR_PAIR_CAPACITY, fr.pairs_total, r->pair_capacity, 0,
                     "the frame produced %llu (tile, Gaussian) pairs but the pair buffers hold %llu: the frame was "
                     "skipped (the image was not written); render again (the next frame grows the buffers)",
                     (unsigned long long)fr.pairs_total, (unsigned long long)r->pair_capacity);
+    }
     return GS_OK;
 }
 
@@ -3541,6 +3559,7 @@ static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
         GS_TRY(stage_preprocess(F));
         // ... and what depends on the size of the pair buffers (the sizing pass may just have set it)
         gsp::plan_pairs(F.hist, nums, r->pair_capacity, F.requests(), switches(), k_policy_params, r->sort_fb, r->rounds_fb, F.plan);
+        r->frame_capacity = F.plan.capacity;
         F.marks.mark(ST_DSORT);
         GS_TRY(stage_sort_and_rounds(F));
     }

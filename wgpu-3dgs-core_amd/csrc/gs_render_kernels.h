@@ -261,7 +261,9 @@ struct FrameResult {
     uint32_t tiles_done;         // two-round frames: tiles finished by round 1 (feeds the host's choice of round 1's length)
     uint32_t tiles_open;         // ... tiles round 1 had pairs for and did not finish
     uint32_t round_pairs_max;    // ... the larger of the two rounds' pair counts (what the next two-round frame's grids are sized for)
-    uint32_t pad[2];
+    uint32_t pairs_round1;       // ... round 1's pair count (pairs_total - pairs_round1: round 2's), so that the host can say
+                                 // which round of a skipped frame outgrew its bound (gs_renderer_wait_frame)
+    uint32_t pad;
 };
 
 // One thread publishes a frame's result to pinned host memory.  `gen` goes LAST, behind a
@@ -271,7 +273,7 @@ struct FrameResult {
 __device__ __forceinline__ void publish_result(FrameResult *r, uint32_t visible, uint64_t pairs_total, uint32_t flags,
                                                uint32_t gen, uint32_t *flags_dev = nullptr, uint32_t depth_bucket_max = 0u,
                                                uint32_t tile_bucket_max = 0u, uint32_t tiles_done = 0u, uint32_t tiles_open = 0u,
-                                               uint32_t round_pairs_max = 0u) {
+                                               uint32_t round_pairs_max = 0u, uint32_t pairs_round1 = 0u) {
     // optional copy of the flags in DEVICE memory (gs_renderer_set_frame_flags_target): a sharded frame
     // carries it inside its band's gather chunk, so every rank learns from the one all-gather whether
     // any band was skipped
@@ -284,6 +286,7 @@ __device__ __forceinline__ void publish_result(FrameResult *r, uint32_t visible,
     r->tiles_done = tiles_done;
     r->tiles_open = tiles_open;
     r->round_pairs_max = round_pairs_max;
+    r->pairs_round1 = pairs_round1;
     __hip_atomic_store(&r->gen, gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -3040,7 +3043,10 @@ struct PairCursorRec {
 
 // One thread publishes the round's pair count: FrameState::pairs (clamped to the capacity) and ::overflow for the kernels
 // behind it and — unless this is round 1 of a two-round frame — the frame result.  A two-round frame is skipped as a
-// whole when either round exceeds the capacity (round 1's blend has then left the image untouched, round 2's does too).
+// whole when either round exceeds the capacity (the frame's per-round bound, gsp::plan_round_capacity).  When round 1
+// exceeds it, round 1's blend leaves the image untouched and round 2's does too.  When only round 2 exceeds it, round 1's
+// blend has already run: the band holds round 1's intermediate pixel state (the known defect of gs3d.h,
+// gs_renderer_set_rounds), and round 2's blend adds nothing to it.
 __device__ __forceinline__ void publish_pairs(const ExpandIO &io, uint64_t d) {
     uint32_t over = d > (uint64_t)io.capacity ? 1u : 0u;
     io.state->pairs = over ? io.capacity : (uint32_t)d;
@@ -3054,7 +3060,8 @@ __device__ __forceinline__ void publish_pairs(const ExpandIO &io, uint64_t d) {
     publish_result(io.result, io.state->visible, total,
                    (over ? FRAME_FLAG_PAIR_OVERFLOW | FRAME_FLAG_SKIPPED : 0u) | (io.state->rank_fault ? FRAME_FLAG_RANK_FAULT : 0u), io.gen,
                    io.flags_dev, io.state->depth_bucket_max, io.state->tile_bucket_max, io.round == 2u ? io.state->tiles_done : 0u, io.round == 2u ? io.state->tiles_open : 0u,
-                   io.round == 2u ? (d > (uint64_t)io.state->pairs_round1 ? (d > 0xffffffffull ? 0xffffffffu : (uint32_t)d) : io.state->pairs_round1) : 0u);
+                   io.round == 2u ? (d > (uint64_t)io.state->pairs_round1 ? (d > 0xffffffffull ? 0xffffffffu : (uint32_t)d) : io.state->pairs_round1) : 0u,
+                   io.round == 2u ? io.state->pairs_round1 : 0u);
 }
 
 // Grid: sb_bound workgroups of EXP_SB threads.  Workgroup 0 also publishes D (clamped to the pair
