@@ -3968,7 +3968,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     // register and differ only in the instruction's immediate offset: no shift / mask per step.
     constexpr uint32_t RS = 48;
     __shared__ __attribute__((aligned(16))) float s_rec[(BLEND_BATCH + 1) * (RS / 4)];
-    __shared__ __attribute__((aligned(16))) uint16_t s_list[NL][BLEND_BATCH];
+    // (behind the lists, G = 8: the dump word — where the lanes that are no member of a list store, see the list build;
+    // written by non-members only, never read)
+    __shared__ __attribute__((aligned(16))) uint16_t s_list_mem[NL * BLEND_BATCH + (G == 8 ? 2 : 0)];
+    uint16_t(*const s_list)[BLEND_BATCH] = (uint16_t(*)[BLEND_BATCH])s_list_mem;
     // [staging wave][list]; G = 8 packs the counts (<= 64 each) in 16 bits: a wave's 16 counts are two 16-byte reads
     typedef typename std::conditional<G == 8, uint16_t, uint32_t>::type cnt_t;
     __shared__ __attribute__((aligned(16))) cnt_t s_cnt[2][NL];
@@ -4054,84 +4057,97 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         const uint32_t j = b0 + tid;
         float mx = 0.0f, my = 0.0f, ca = 0.0f, cb = 0.0f, cc = 0.0f, thr = 0.0f;
         const bool have = j < end;
-        if (have) {
-            const uint32_t slot = idx[j];
-            const uint32_t *rec = recs + (uint64_t)slot * REC_WORDS;
-            const u32x4_a4 r0 = *(const u32x4_a4 *)(rec);
-            const u32x4_a4 r1 = *(const u32x4_a4 *)(rec + 4);
-            const uint32_t r2x = rec[8];
-            mx = u2f(r0.x); my = u2f(r0.y); ca = u2f(r0.z); cb = u2f(r0.w); cc = u2f(r1.x);
-            float pmin;
-            if constexpr (MODE == 0) pmin = fmaxf(-__logf(255.0f * u2f(r1.y)) - 1.0e-3f, -5.6f);
-            else pmin = fc.ellipse_pmin;
-            thr = (MODE == 0 ? pmin - 0.1f : pmin - 0.1f - 1.0e-3f * fabsf(pmin)) -
-                  cull_rounding_slack(mx, my, ca, cb, cc, tx0, ty0);
-            *(float4 *)(s_rec + tid * (RS / 4)) = make_float4(mx, my, ca, cb);
-            *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(cc, pmin, u2f(r1.y), u2f(r1.z));
-            if constexpr (AUX)
-                *(float4 *)(s_rec + tid * (RS / 4) + 8) =
-                    make_float4(u2f(r1.w), u2f(r2x), u2f(aux.depth_keys[slot] + aux.key_bias), u2f(slot));
-            else
-                *(float2 *)(s_rec + tid * (RS / 4) + 8) = make_float2(u2f(r1.w), u2f(r2x));
-        }
-        // The tile's 2G blocks form a grid of NCOL columns x NROW rows (BW wide, BH high).  The exact
-        // maximum of the concave exponent over a block comes from the block's two edges facing the
-        // splat centre (splat_touches_rect2): the facing vertical edge depends only on the column,
-        // the facing horizontal edge only on the row, so the parabola coefficients and their
-        // unconstrained optima are set up once per column / row and a block costs two clamps
-        // (v_med3), four fmas and a compare.  (fma is fine here: the cull is conservative, not part
-        // of the bit-exact result.)
+        // A wave whose 64 lanes hold no splat (b0 + 64 wid >= end: wave 1 in a tile's last batch of at most 64 pairs) skips the
+        // set-ups, the block tests and the list build: all its verdicts are zero.  The branch is wave-uniform, and the
+        // barriers below stay outside of it: both waves meet at them.
+        const bool staging = __builtin_amdgcn_ballot_w64(have) != 0ull;
         uint64_t m[NL];
-        // G = 8: the block edges (tile origin + 4 c, + 4 c + 3) are rebuilt from the origin in every batch: hoisted out of
-        // the batch loop, the sixteen of them stay in vector registers through the blend loop (84 registers, 5 waves per SIMD)
-        float bx0 = tx0, by0 = ty0;
-        if constexpr (G == 8) asm volatile("" : "+v"(bx0), "+v"(by0));
-        if constexpr (MODE == 2) {
+        if (!staging) {
 #pragma unroll
-            for (int l = 0; l < NL; l++) {
-                const int lw = l / G, lgi = l % G;
-                const float rx0 = bx0 + (float)BW * (float)(lgi % NCOL);
-                const float ry0 = by0 + 8.0f * (float)lw + (float)BH * (float)(lgi / NCOL);
-                const float ex = mx - clampf(mx, rx0, rx0 + (float)(BW - 1)), ey = my - clampf(my, ry0, ry0 + (float)(BH - 1));
-                m[l] = __builtin_amdgcn_ballot_w64(have && ex * ex + ey * ey <= 2.26f);
-            }
+            for (int l = 0; l < NL; l++) m[l] = 0ull;
         } else {
-            const float rcc = __builtin_amdgcn_rcpf(cc), rca = __builtin_amdgcn_rcpf(ca);
-            float c_lo[NCOL], c_hi[NCOL], c_q1[NCOL], c_q0[NCOL], c_t[NCOL];
-            bool c_in[NCOL];
-#pragma unroll
-            for (int c = 0; c < NCOL; c++) {
-                const float x0c = bx0 + (float)BW * (float)c;
-                c_lo[c] = mx - (x0c + (float)(BW - 1));
-                c_hi[c] = mx - x0c;
-                c_in[c] = c_lo[c] <= 0.0f && c_hi[c] >= 0.0f;
-                const float dn = fabsf(c_lo[c]) < fabsf(c_hi[c]) ? c_lo[c] : c_hi[c];   // nearer vertical edge
-                c_q1[c] = cb * dn;
-                c_q0[c] = ca * dn * dn;
-                c_t[c] = -0.5f * c_q1[c] * rcc;            // optimum of cc t^2 + q1 t + q0 along the edge
+            if (have) {
+                const uint32_t slot = idx[j];
+                const uint32_t *rec = recs + (uint64_t)slot * REC_WORDS;
+                const u32x4_a4 r0 = *(const u32x4_a4 *)(rec);
+                const u32x4_a4 r1 = *(const u32x4_a4 *)(rec + 4);
+                const uint32_t r2x = rec[8];
+                mx = u2f(r0.x); my = u2f(r0.y); ca = u2f(r0.z); cb = u2f(r0.w); cc = u2f(r1.x);
+                float pmin;
+                if constexpr (MODE == 0) pmin = fmaxf(-__logf(255.0f * u2f(r1.y)) - 1.0e-3f, -5.6f);
+                else pmin = fc.ellipse_pmin;
+                thr = (MODE == 0 ? pmin - 0.1f : pmin - 0.1f - 1.0e-3f * fabsf(pmin)) -
+                      cull_rounding_slack(mx, my, ca, cb, cc, tx0, ty0);
+                *(float4 *)(s_rec + tid * (RS / 4)) = make_float4(mx, my, ca, cb);
+                *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(cc, pmin, u2f(r1.y), u2f(r1.z));
+                if constexpr (AUX)
+                    *(float4 *)(s_rec + tid * (RS / 4) + 8) =
+                        make_float4(u2f(r1.w), u2f(r2x), u2f(aux.depth_keys[slot] + aux.key_bias), u2f(slot));
+                else
+                    *(float2 *)(s_rec + tid * (RS / 4) + 8) = make_float2(u2f(r1.w), u2f(r2x));
             }
+            // The tile's 2G blocks form a grid of NCOL columns x NROW rows (BW wide, BH high).  The exact
+            // maximum of the concave exponent over a block comes from the block's two edges facing the
+            // splat centre (splat_touches_rect2): the facing vertical edge depends only on the column,
+            // the facing horizontal edge only on the row, so the parabola coefficients and their
+            // unconstrained optima are set up once per column / row and a block costs two clamps
+            // (v_med3), four fmas, a maximum and a compare.  (fma is fine here: the cull is conservative, not part
+            // of the bit-exact result.)
+            // G = 8: the block edges (tile origin + 4 c, + 4 c + 3) are rebuilt from the origin in every batch: hoisted out of
+            // the batch loop, the sixteen of them stay in vector registers through the blend loop (84 registers, 5 waves per SIMD)
+            float bx0 = tx0, by0 = ty0;
+            if constexpr (G == 8) asm volatile("" : "+v"(bx0), "+v"(by0));
+            if constexpr (MODE == 2) {
 #pragma unroll
-            for (int r = 0; r < NROW; r++) {
-                const float y0r = by0 + (float)(BH * r);
-                const float r_lo = my - (y0r + (float)(BH - 1)), r_hi = my - y0r;
-                const bool r_in = r_lo <= 0.0f && r_hi >= 0.0f;
-                const float dn = fabsf(r_lo) < fabsf(r_hi) ? r_lo : r_hi;               // nearer horizontal edge
-                const float r_q1 = cb * dn, r_q0 = cc * dn * dn;
-                const float r_t = -0.5f * r_q1 * rca;
+                for (int l = 0; l < NL; l++) {
+                    const int lw = l / G, lgi = l % G;
+                    const float rx0 = bx0 + (float)BW * (float)(lgi % NCOL);
+                    const float ry0 = by0 + 8.0f * (float)lw + (float)BH * (float)(lgi / NCOL);
+                    const float ex = mx - clampf(mx, rx0, rx0 + (float)(BW - 1)), ey = my - clampf(my, ry0, ry0 + (float)(BH - 1));
+                    m[l] = __builtin_amdgcn_ballot_w64(have && ex * ex + ey * ey <= 2.26f);
+                }
+            } else {
+                const float rcc = __builtin_amdgcn_rcpf(cc), rca = __builtin_amdgcn_rcpf(ca);
+                float c_lo[NCOL], c_hi[NCOL], c_q1[NCOL], c_q0[NCOL], c_t[NCOL];
+                uint64_t c_inb[NCOL];
+                const uint64_t have_b = __builtin_amdgcn_ballot_w64(have);
 #pragma unroll
                 for (int c = 0; c < NCOL; c++) {
-                    const float tv = __builtin_amdgcn_fmed3f(c_t[c], r_lo, r_hi);
-                    const float mv = __builtin_fmaf(__builtin_fmaf(cc, tv, c_q1[c]), tv, c_q0[c]);
-                    const float th = __builtin_amdgcn_fmed3f(r_t, c_lo[c], c_hi[c]);
-                    const float mh = __builtin_fmaf(__builtin_fmaf(ca, th, r_q1), th, r_q0);
-                    // (hipcc turns the short circuit into an exec-mask branch around every test; with "|" and "&" the G = 8
-                    // tests are branch-free, but the kernel then takes 75 vector registers instead of 71)
-                    const bool keep = (c_in[c] && r_in) || !(fmaxf(mv, mh) < thr);
-                    // list of block (column c, row r): rows 0..NROW/2-1 belong to wave 0
-                    const int l = (r / (NROW / 2)) * G + (r % (NROW / 2)) * NCOL + c;
-                    m[l] = __builtin_amdgcn_ballot_w64(have && keep);
+                    const float x0c = bx0 + (float)BW * (float)c;
+                    c_lo[c] = mx - (x0c + (float)(BW - 1));
+                    c_hi[c] = mx - x0c;
+                    c_inb[c] = __builtin_amdgcn_ballot_w64(c_lo[c] <= 0.0f) & __builtin_amdgcn_ballot_w64(c_hi[c] >= 0.0f);
+                    const float dn = fabsf(c_lo[c]) < fabsf(c_hi[c]) ? c_lo[c] : c_hi[c];   // nearer vertical edge
+                    c_q1[c] = cb * dn;
+                    c_q0[c] = ca * dn * dn;
+                    c_t[c] = -0.5f * c_q1[c] * rcc;            // optimum of cc t^2 + q1 t + q0 along the edge
                 }
-                if constexpr (G == 8) __builtin_amdgcn_sched_barrier(0);   // one row's set-up and four tests at a time
+#pragma unroll
+                for (int r = 0; r < NROW; r++) {
+                    const float y0r = by0 + (float)(BH * r);
+                    const float r_lo = my - (y0r + (float)(BH - 1)), r_hi = my - y0r;
+                    const uint64_t r_inb = __builtin_amdgcn_ballot_w64(r_lo <= 0.0f) & __builtin_amdgcn_ballot_w64(r_hi >= 0.0f);
+                    const float dn = fabsf(r_lo) < fabsf(r_hi) ? r_lo : r_hi;               // nearer horizontal edge
+                    const float r_q1 = cb * dn, r_q0 = cc * dn * dn;
+                    const float r_t = -0.5f * r_q1 * rca;
+#pragma unroll
+                    for (int c = 0; c < NCOL; c++) {
+                        const float tv = __builtin_amdgcn_fmed3f(c_t[c], r_lo, r_hi);
+                        const float mv = __builtin_fmaf(__builtin_fmaf(cc, tv, c_q1[c]), tv, c_q0[c]);
+                        const float th = __builtin_amdgcn_fmed3f(r_t, c_lo[c], c_hi[c]);
+                        const float mh = __builtin_fmaf(__builtin_fmaf(ca, th, r_q1), th, r_q0);
+                        // The verdict is put together from ballots, in scalar registers: (inside the column & inside the row)
+                        // | not below the threshold.  Written on the lanes' bools with "||" hipcc built an exec-mask region
+                        // around every test and turned the flag back into a bool (10 VALU + 7 SALU per block instead of
+                        // 8 + 3); with "|" and "&" on bools the G = 8 kernel took 75 vector registers.  The verdicts are the
+                        // same: where the short circuit skipped the test, its outcome is or-ed with a true.
+                        const uint64_t keep = (c_inb[c] & r_inb) | __builtin_amdgcn_ballot_w64(!(fmaxf(mv, mh) < thr));
+                        // list of block (column c, row r): rows 0..NROW/2-1 belong to wave 0
+                        const int l = (r / (NROW / 2)) * G + (r % (NROW / 2)) * NCOL + c;
+                        m[l] = keep & have_b;
+                    }
+                    if constexpr (G == 8) __builtin_amdgcn_sched_barrier(0);   // one row's set-up and four tests at a time
+                }
             }
         }
         if (lane == 0) {
@@ -4145,9 +4161,14 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             }
         }
         __syncthreads();
-        if constexpr (G == 8) {
+        if (!staging) {
+            // nothing to enter
+        } else if constexpr (G == 8) {
             // wave 0's counts, packed, in scalar registers (sixteen per-lane copies cost 12 vector registers and
-            // two waves per SIMD); a list's base rides in v_mbcnt's addend
+            // two waves per SIMD).  A list is written without a per-lane test of its ballot: the ballot, a scalar register
+            // pair, is the selector of one v_cndmask_b32 between the member's place in the list and the dump halfword, and
+            // the store behind it is unconditional (4 VALU per list: two v_mbcnt, v_lshl_add, the select; the per-lane
+            // bit test cost 7 and a 64-bit lane mask in two vector registers).
             const uint4 *c128 = (const uint4 *)&s_cnt[0][0];
             const uint4 ca4 = c128[0], cb4 = c128[1];
             const uint32_t wv[8] = {ca4.x, ca4.y, ca4.z, ca4.w, cb4.x, cb4.y, cb4.z, cb4.w};
@@ -4155,11 +4176,15 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
 #pragma unroll
             for (int q = 0; q < 8; q++) w[q] = (uint32_t)__builtin_amdgcn_readfirstlane(wv[q]);
             const uint32_t swid = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
+            const uint32_t dump = (uint32_t)(NL * BLEND_BATCH * sizeof(uint16_t));
 #pragma unroll
             for (int l = 0; l < NL; l++) {
                 const uint32_t base = swid ? (w[l / 2] >> (16 * (l & 1))) & 0xffffu : 0u;
-                const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[l] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[l], base));
-                if ((m[l] >> lane) & 1ull) s_list[l][pos] = (uint16_t)(tid * RS);
+                const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[l] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[l], 0u));
+                const uint32_t at = (pos << 1) + 2u * ((uint32_t)(l * BLEND_BATCH) + base);      // byte offset in s_list_mem
+                uint32_t to;
+                asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(to) : "v"(dump), "v"(at), "s"(m[l]));
+                *(uint16_t *)((char *)s_list_mem + to) = (uint16_t)(tid * RS);
             }
         } else {   // (the other wave's counts are read as one batch: behind a branch per list hipcc emitted eight
             // ds_read + s_waitcnt pairs in a row)
