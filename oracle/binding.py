@@ -283,8 +283,10 @@ def tile_ranges(keys, num_tiles):
     return r
 
 
-def blend(proj, idx, ranges, cam, band=None, gt=None):
-    """gt: the GaussianTransform whose display mode / max_std_dev apply (None = splat, 3 sigma)"""
+def blend(proj, idx, ranges, cam, band=None, gt=None, stopped=False):
+    """gt: the GaussianTransform whose display mode / max_std_dev apply (None = splat, 3 sigma).  stopped=True: returns
+    (rgba, stopped), stopped[H, W] uint8 = 1 where the pixel left its list through the transmittance test (pixels
+    outside the band stay 0)"""
     tiles_y = (cam.height + 15) // 16
     b0, b1 = band if band is not None else (0, tiles_y)
     rgba = np.zeros((cam.height, cam.width, 4), dtype=np.float32)
@@ -295,10 +297,17 @@ def blend(proj, idx, ranges, cam, band=None, gt=None):
         lib().gso_transform_max_std_dev.restype = C.c_float
         lib().gso_transform_max_std_dev.argtypes = [C.c_uint32]
         k = lib().gso_transform_max_std_dev(gt.flags_u32)
+    args = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float]
+    if stopped:
+        flags = np.zeros((cam.height, cam.width), dtype=np.uint8)
+        fn = lib().gso_blend_mode_stopped
+        fn.restype = None
+        fn.argtypes = args + [C.c_void_p]
+        fn(_p(proj), _p(idx), _p(ranges), C.byref(cam), b0, b1, _p(rgba), mode, k, _p(flags))
+        return rgba, flags
     fn = lib().gso_blend_mode
     fn.restype = None
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
-                   C.c_float]
+    fn.argtypes = args
     fn(_p(proj), _p(idx), _p(ranges), C.byref(cam), b0, b1, _p(rgba), mode, k)
     return rgba
 

@@ -1207,9 +1207,9 @@ void gso_blend(const gso_projected *proj, const uint32_t *idx, const uint32_t *r
  *   0 splat   alpha = min(0.99, opacity * exp(power)), skipped when power > 0
  *   1 ellipse alpha = min(0.99, opacity) where -k^2/2 <= power <= 0 (k = max_std_dev): the flat k-sigma ellipse
  *   2 point   alpha = min(0.99, opacity) where dx^2 + dy^2 <= 1.5^2: a fixed 1.5-pixel dot */
-void gso_blend_mode(const gso_projected *proj, const uint32_t *idx, const uint32_t *ranges,
-                    const gso_camera *cam, uint32_t band_ty0, uint32_t band_ty1, float *rgba,
-                    uint32_t display_mode, float max_std_dev) {
+static void blend_body(const gso_projected *proj, const uint32_t *idx, const uint32_t *ranges,
+                       const gso_camera *cam, uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                       uint32_t display_mode, float max_std_dev, uint8_t *stopped) {
     const float ellipse_pmin = -0.5f * (max_std_dev * max_std_dev);
     uint32_t W = cam->width, H = cam->height;
     uint32_t tiles_x = (W + 15u) / 16u, tiles_y = (H + 15u) / 16u;
@@ -1228,6 +1228,7 @@ void gso_blend_mode(const gso_projected *proj, const uint32_t *idx, const uint32
                 if (px >= W) break;
                 float pxf = (float)px + 0.5f, pyf = (float)py + 0.5f;
                 float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+                uint8_t stop = 0;
                 for (uint32_t j = s; j < e; j++) {
                     const gso_projected *g = &proj[idx[j]];
                     float dx = g->mx - pxf, dy = g->my - pyf;
@@ -1247,7 +1248,7 @@ void gso_blend_mode(const gso_projected *proj, const uint32_t *idx, const uint32
                     }
                     if (alpha < 1.0f / 255.0f) continue;
                     float test_T = T * (1.0f - alpha);
-                    if (test_T < 0.0001f) break;
+                    if (test_T < 0.0001f) { stop = 1; break; }
                     float wgt = alpha * T;
                     C0 = fmaf(g->r, wgt, C0);
                     C1 = fmaf(g->g, wgt, C1);
@@ -1259,9 +1260,24 @@ void gso_blend_mode(const gso_projected *proj, const uint32_t *idx, const uint32
                 o[1] = fmaf(T, cam->background[1], C1);
                 o[2] = fmaf(T, cam->background[2], C2);
                 o[3] = 1.0f - T;
+                if (stopped) stopped[(size_t)py * W + px] = stop;
             }
         }
     }
+}
+
+void gso_blend_mode(const gso_projected *proj, const uint32_t *idx, const uint32_t *ranges,
+                    const gso_camera *cam, uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                    uint32_t display_mode, float max_std_dev) {
+    blend_body(proj, idx, ranges, cam, band_ty0, band_ty1, rgba, display_mode, max_std_dev, NULL);
+}
+
+/* gso_blend_mode, and per pixel of the band whether it left its list through the transmittance test (1) or ran to the
+ * list's end (0): what a two-round frame's first round calls a finished pixel (DESIGN.md §4.2 "rounds") */
+void gso_blend_mode_stopped(const gso_projected *proj, const uint32_t *idx, const uint32_t *ranges,
+                            const gso_camera *cam, uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                            uint32_t display_mode, float max_std_dev, uint8_t *stopped) {
+    blend_body(proj, idx, ranges, cam, band_ty0, band_ty1, rgba, display_mode, max_std_dev, stopped);
 }
 
 static _Thread_local double g_stage[5];

@@ -183,6 +183,11 @@ void gso_blend(const gso_projected *proj, const uint32_t *idx, const uint32_t *r
 void gso_blend_mode(const gso_projected *proj, const uint32_t *idx, const uint32_t *ranges,
                     const gso_camera *cam, uint32_t band_ty0, uint32_t band_ty1, float *rgba,
                     uint32_t display_mode, float max_std_dev);
+/* same, and stopped[height*width]: 1 where the pixel left its list through the transmittance test (test_T < 1e-4), 0 where
+ * it ran to the list's end; only pixels of the band are written */
+void gso_blend_mode_stopped(const gso_projected *proj, const uint32_t *idx, const uint32_t *ranges,
+                            const gso_camera *cam, uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                            uint32_t display_mode, float max_std_dev, uint8_t *stopped);
 /* whole frame; optional outputs may be NULL. returns D. */
 uint64_t gso_render(int sh, int cov, const void *pods, size_t n, const gso_gaussian_transform *gt,
                     const gso_model_transform *mt, const gso_camera *cam, uint32_t band_ty0,

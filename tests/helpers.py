@@ -51,6 +51,24 @@ def deep_scene(n, first=4242, opacity=250, scale=3.5):
     return g
 
 
+# scenes of the two-round count tests (tests/test_gpu_round_counts.py asserts what their round 1 finishes and round 2 drops):
+# opaque splats that cover a 330 x 200 view partly after the nearest few thousand, and sparse ones that need 16 384 to
+# finish a single 16 x 16 tile
+ROUNDS_MIXED_SCENE = dict(n=40000, first=77, opacity=255, scale=5.0)
+ROUNDS_ONE_TILE_SCENE = dict(n=60000, first=123, opacity=250, scale=1.5)
+_small_image_scenes = {}
+
+
+def small_image_scene(W, H):
+    """the Gaussians tests/test_gpu_rounds.py renders at its small sizes: a scene whose round 1 finishes some tiles and leaves
+    others open — at one tile, where that cannot be, nothing at K = 2 048 and everything at 16 384"""
+    spec = ROUNDS_ONE_TILE_SCENE if (W, H) == (16, 16) else ROUNDS_MIXED_SCENE
+    key = tuple(sorted(spec.items()))
+    if key not in _small_image_scenes:
+        _small_image_scenes[key] = deep_scene(spec["n"], first=spec["first"], opacity=spec["opacity"], scale=spec["scale"])
+    return _small_image_scenes[key]
+
+
 def round_setup(gs, ob, g, W, H, sh, cov, mode=0, **cam_kw):
     """pods and the oracle's and the product's transforms and camera of a scene of the two-round tests"""
     pod = gs.GaussianPod(sh, cov)

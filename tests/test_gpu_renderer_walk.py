@@ -27,6 +27,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, _p)
 
 import helpers  # noqa: E402
+import rounds_np  # noqa: E402
 from helpers import band_rows, bits  # noqa: E402
 
 gpu = pytest.mark.gpu
@@ -178,7 +179,7 @@ def oracle_frame(ob, name):
     ranges = ob.tile_ranges(skeys, tiles_x * tiles_y)
     rgba = ob.blend(proj, sidx, ranges, ocam, band=k["band"], gt=ogt)
     tl = np.asarray(tiles)
-    o = dict(proj=proj, tiles=tl, keys=skeys, idx=sidx, ranges=ranges, rgba=rgba, V=int((tl > 0).sum()),
+    o = dict(proj=proj, tiles=tl, rows=tiles.rows, keys=skeys, idx=sidx, ranges=ranges, rgba=rgba, V=int((tl > 0).sum()),
              D=int(tl.astype(np.uint64).sum()), longest=int((ranges[:, 1] - ranges[:, 0]).max()), tiles_x=tiles_x,
              num_tiles=tiles_x * tiles_y, ogt=ogt, omt=omt, ocam=ocam)
     if k["aux"]:
@@ -186,25 +187,36 @@ def oracle_frame(ob, name):
         o["pick"], o["pick_ambiguous"] = _witness(proj, sidx, ranges, W, H, tiles_x, float(np.float32(1.0) - np.float32(0.5)))
     if k["rounds"][0] == 1:
         o["finished"], o["open"] = round1_coverage(o, hb["order"], W, H, k["rounds"][1])
+        # the exact counts of the frame, unpartitioned and partitioned (tests/rounds_np.py)
+        with_rows = tl.view(ob.TilesTouched)
+        with_rows.rows = tiles.rows
+        o["model"] = [rounds_np.frame(ob, proj, with_rows, hb["order"], ocam, ogt, k["band"], k["rounds"][1], part, n=n)
+                      for part in (0, 1)]
     _oracle_cache[name] = o
     return o
 
 
 def round1_coverage(o, order, W, H, round1):
-    """(certainly finished, certainly open) tiles after a round 1 of the nearest `round1` visible Gaussians (an
-    unpartitioned frame's): a float64 walk of the oracle's lists restricted to them.  A pixel that meets a step with
-    T (1 - alpha) < 0.999e-4 has certainly stopped; one that never meets a step below 1.001e-4 is certainly still open
-    (f32 rounding does not cross 0.1 %); a step in between is taken as not stopping, and leaves the pixel undecided unless a
-    later step stops it for certain — which the next active step does, whichever way the kernel decided: it multiplies a T
-    of ~1e-4 by at most 1 - 1/255.  A tile is finished when every in-image pixel has stopped, open when one is open; a tile
-    with an undecided pixel and no open one is neither."""
+    """the numbers of certainly finished and of certainly open tiles (round1_coverage_masks)"""
+    finished, opened = round1_coverage_masks(o, order, W, H, round1)
+    return int(finished.sum()), int(opened.sum())
+
+
+def round1_coverage_masks(o, order, W, H, round1):
+    """(certainly finished, certainly open) tiles, one bool per tile, after a round 1 of the nearest `round1` visible
+    Gaussians (an unpartitioned frame's): a float64 walk of the oracle's lists restricted to them.  A pixel that meets a
+    step with T (1 - alpha) < 0.999e-4 has certainly stopped; one that never meets a step below 1.001e-4 is certainly still
+    open (f32 rounding does not cross 0.1 %); a step in between is taken as not stopping, and leaves the pixel undecided
+    unless a later step stops it for certain — which the next active step does, whichever way the kernel decided: it
+    multiplies a T of ~1e-4 by at most 1 - 1/255.  A tile is finished when every in-image pixel has stopped, open when one
+    is open; a tile with an undecided pixel and no open one is neither."""
     proj, sidx, ranges = o["proj"], o["idx"], o["ranges"]
     vis = order[o["tiles"][order] > 0]
     near = vis[np.argsort(proj["depth"][vis], kind="stable")][:round1]
     member = np.zeros(len(proj), bool)
     member[near] = True
     p = {f: proj[f].astype(np.float64) for f in ("mx", "my", "ca", "cb", "cc", "opacity")}
-    finished = opened = 0
+    finished, opened = np.zeros(ranges.shape[0], bool), np.zeros(ranges.shape[0], bool)
     for t in range(ranges.shape[0]):
         tx, ty = t % o["tiles_x"], t // o["tiles_x"]
         xs, ys = np.arange(tx * 16, min(tx * 16 + 16, W)), np.arange(ty * 16, min(ty * 16 + 16, H))
@@ -225,8 +237,8 @@ def round1_coverage(o, order, W, H, round1):
             sure = act & (Tn < 0.999e-4)
             stopped |= sure
             T = np.where(act & ~sure, Tn, T)
-        finished += int(stopped.all())
-        opened += int((~maybe).any())
+        finished[t] = stopped.all()
+        opened[t] = (~maybe).any()
     return finished, opened
 
 
@@ -268,6 +280,10 @@ def test_rounds_kind_finishes_some_tiles_and_leaves_others_open(ob):
     assert o["num_tiles"] == 35 and o["V"] > 2 * ROUND1
     assert o["finished"] >= 1 and o["open"] >= 1
     assert o["finished"] + o["open"] <= o["num_tiles"]
+    for m in o["model"]:
+        # the model's exact counts lie inside the walk's brackets, and round 2 has something to drop
+        assert o["finished"] <= m["tiles_done"] <= o["num_tiles"] - o["open"] and not m["gated"]
+        assert m["pairs"] < m["pairs_undropped"] == o["D"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -401,10 +417,9 @@ def walk(gs, ob, device, stream, groups=0, record=None, seq=None):
                 assert si.partitioned == 1, "%s: a frame of a known shape must be partitioned" % ctx
             elif prev != "empty":       # (an empty frame leaves the shape of the frame before it)
                 assert si.partitioned == 0, "%s: a sizing frame cannot be partitioned" % ctx
-            # a partitioned round 1 ends at a digit boundary behind the nearest ROUND1: it can only finish more tiles
-            hi = o["num_tiles"] - o["open"] if si.partitioned == 0 else o["num_tiles"]
-            assert o["finished"] <= si.tiles_done <= hi, "%s: round 1 finished %d tiles, expected %d..%d" % (
-                ctx, si.tiles_done, o["finished"], hi)
+            m = o["model"][int(si.partitioned)]
+            assert si.tiles_done == m["tiles_done"], "%s: round 1 finished %d tiles, the model %d" % (ctx, si.tiles_done, m["tiles_done"])
+            assert fr.pairs == m["pairs"], "%s: %d pairs, the model %d" % (ctx, fr.pairs, m["pairs"])
         if k["aux"]:
             check_aux_planes(gs.PICK_NONE, o, rgba, depth, pick, ctx)
         if record is not None:
@@ -532,7 +547,8 @@ def test_every_transition_under_the_other_blend_kernels(gs, ob, child_frames, gr
         if rounds == 1:
             assert pairs == o["D"], ctx
         else:
-            assert round1 == ROUND1 and tiles_done >= o["finished"], ctx
+            m = o["model"][partitioned]
+            assert round1 == ROUND1 and tiles_done == m["tiles_done"] and pairs == m["pairs"], ctx
             partitioned_seen.add(partitioned)
         if KINDS[name]["aux"]:
             check_aux_planes(gs.PICK_NONE, o, rgba, rec["f%03d/depth" % i], rec["f%03d/pick" % i], ctx)

@@ -27,6 +27,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, _p)
 
 import helpers  # noqa: E402
+import rounds_np  # noqa: E402
 from helpers import POISON, band_rows, bits, capacity_for  # noqa: E402
 
 gpu = pytest.mark.gpu
@@ -107,28 +108,12 @@ def oracle_kind(ob, kind):
 
 
 def round1_members(ob, kind, K, partitioned):
-    """mask of the Gaussians round 1 renders.  Unpartitioned: the nearest K visible ones, ties in the mirror's order (the
-    depth sort is stable).  Partitioned (k_round_threshold): the depth key is bits(depth) - bits(near), of
-    bit_length(bits(far) - bits(near)) bits; round 1 takes the keys below (d + 1) << low_bits, d the smallest value of the
-    key's top 10 bits with at least K visible Gaussians at or below it (all of them when there are fewer than K)."""
+    """mask of the Gaussians round 1 renders (tests/rounds_np.py's round1_members, at this file's planes): the nearest K
+    visible ones of an unpartitioned frame, everything in front of the cut of a partitioned one"""
     key = (kind, K, bool(partitioned))
     if key not in _members_cache:
         o = oracle_kind(ob, kind)
-        order = o["order"]
-        vis = order[np.asarray(o["tiles"])[order] > 0]
-        depth = o["proj"]["depth"][vis]
-        m = np.zeros(N, bool)
-        if not partitioned:
-            m[vis[np.argsort(depth, kind="stable")][:K]] = True
-        else:
-            near_bits, far_bits = (int(np.float32(x).view(np.uint32)) for x in (NEAR, FAR))
-            low_bits = (far_bits - near_bits).bit_length() - 10
-            dkey = depth.view(np.uint32).astype(np.int64) - near_bits
-            assert (dkey >= 0).all() and (dkey >> low_bits < 1024).all()
-            upto = np.cumsum(np.bincount(dkey >> low_bits, minlength=1024))
-            tau = (int(np.searchsorted(upto, K)) + 1) << low_bits if upto[-1] >= K else 1 << 32
-            m[vis[dkey < tau]] = True
-        _members_cache[key] = m
+        _members_cache[key] = rounds_np.round1_members(o["proj"], o["tiles"], o["order"], NEAR, FAR, K, partitioned)
     return _members_cache[key]
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import helpers
+import rounds_np
 from helpers import deep_scene as _deep_scene, round_setup as _setup
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +38,20 @@ def _render(gs, device, stream, buf, gt, mt, cam, rounds, band=None, masks=None,
     return r, fr, rgba
 
 
+def _model(ob, sh, cov, pods, ogt, omt, ocam, order, k, stages, band=None, masks=1):
+    """tests/rounds_np.py's counts of the PARTITIONED frame of a scene rendered with set_rounds(1, k) — _render returns the
+    result of a renderer's last frame, and every frame after the first is partitioned (conftest's GS3D_ROUND_PARTITION=1).
+    stages: a dict of the caller's that keeps the oracle's preprocess between calls."""
+    if "proj" not in stages:
+        version = ob.rect_version()
+        try:
+            ob.set_rect_version(4 if masks else 3)
+            stages["proj"], stages["tiles"] = ob.preprocess(sh, cov, pods, ogt, omt, ocam, band=band)
+        finally:
+            ob.set_rect_version(version)
+    return rounds_np.frame(ob, stages["proj"], stages["tiles"], order, ocam, ogt, band, k, 1)
+
+
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_two_rounds_equal_one_round_and_the_oracle(gs, ob, device, stream, mode):
     g = _deep_scene(120000)
@@ -51,14 +66,19 @@ def test_two_rounds_equal_one_round_and_the_oracle(gs, ob, device, stream, mode)
     v = fr1.visible
     assert v > 20000
     seen_fewer = False
+    stages = {}
     for k in (2048, 4096, v // 4, v // 2, (v // 2048) * 2048, v + 5000):
         r2, fr2, two = _render(gs, device, stream, buf, gt, mt, cam, k)
         si = r2.sort_info()
+        m = _model(ob, gs.SH_NONE, gs.COV3D_ROT_SCALE, pods, ogt, omt, ocam, order, k, stages)
+        assert si.rounds == m["rounds"]
         if (k + 2047) // 2048 * 2048 >= len(g):
             assert si.rounds == 1                    # nothing left for a second round: one round
         else:
             assert si.rounds == 2 and si.round1 == (k + 2047) // 2048 * 2048
-            assert fr2.pairs <= fr1.pairs and fr2.visible == v
+            assert si.partitioned == 1 and fr2.visible == v == m["visible"]
+            assert (fr2.pairs, si.tiles_done) == (m["pairs"], m["tiles_done"]), "K = %d" % k
+            assert m["pairs"] <= fr1.pairs == m["D"]
             seen_fewer = seen_fewer or fr2.pairs < fr1.pairs
             with pytest.raises(gs.GsError):
                 r2.download_ranges(4)
@@ -76,11 +96,14 @@ def test_two_rounds_with_and_without_tile_masks(gs, ob, device, stream, masks, s
     pod, pods, ogt, omt, ocam, gt, mt, cam = _setup(gs, ob, g, W, H, sh, cov)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
     _, fr1, one = _render(gs, device, stream, buf, gt, mt, cam, None, masks=masks)
+    order, stages = buf.download_order(stream), {}
     for k in (16384, 40000):
         r2, fr2, two = _render(gs, device, stream, buf, gt, mt, cam, k, masks=masks)
         assert r2.sort_info().rounds == 2 and r2.sort_info().tile_masks == masks
         assert np.array_equal(two.view(np.uint32), one.view(np.uint32))
-        assert fr2.pairs < fr1.pairs
+        m = _model(ob, sh, cov, pods, ogt, omt, ocam, order, k, stages, masks=masks)
+        assert fr1.pairs == m["D"] and m["pairs"] < m["D"], "the scene drops nothing"
+        assert (fr2.visible, fr2.pairs, r2.sort_info().tiles_done) == (m["visible"], m["pairs"], m["tiles_done"]), "K = %d" % k
 
 
 @pytest.mark.parametrize("W,H", [(240, 160), (387, 144), (16, 16)])
@@ -88,7 +111,8 @@ def test_two_rounds_on_small_images(gs, ob, device, stream, W, H):
     """150 / 225 / 1 tiles: a tile sort of ONE pass (or none) leaves the sorted pairs on the other side of its ping-pong
     buffers than the two passes of the larger tests (found by tools/soak_rounds.py: round 1's blend read the side the
     PREVIOUS frame had left its pairs on)."""
-    g = _deep_scene(60000, first=123, scale=1.5)
+    # (a scene whose round 2 has something to drop at the two larger sizes: test_gpu_round_counts.py asserts it, and the counts)
+    g = helpers.small_image_scene(W, H)
     pod, pods, ogt, omt, ocam, gt, mt, cam = _setup(gs, ob, g, W, H, gs.SH_NONE, gs.COV3D_ROT_SCALE)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
     want = ob.render(gs.SH_NONE, gs.COV3D_ROT_SCALE, pods, ogt, omt, ocam, order=buf.download_order(stream))[0]
@@ -106,21 +130,20 @@ def test_round_2_is_skipped_when_round_1_finishes_every_tile(gs, ob, device, str
     W, H = 640, 360
     pod, pods, ogt, omt, ocam, gt, mt, cam = _setup(gs, ob, g, W, H, gs.SH_NONE, gs.COV3D_ROT_SCALE)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    want = ob.render(gs.SH_NONE, gs.COV3D_ROT_SCALE, pods, ogt, omt, ocam, order=buf.download_order(stream))[0]
-    seen = set()
+    order = buf.download_order(stream)
+    want = ob.render(gs.SH_NONE, gs.COV3D_ROT_SCALE, pods, ogt, omt, ocam, order=order)[0]
+    seen, stages = set(), {}
     for k in (8192, 32768, 65536):
         r2, fr2, two = _render(gs, device, stream, buf, gt, mt, cam, k, frames=3)
         si = r2.sort_info()
         assert si.rounds == 2
         assert np.array_equal(two.view(np.uint32), want.view(np.uint32)), "K = %d" % k
+        m = _model(ob, gs.SH_NONE, gs.COV3D_ROT_SCALE, pods, ogt, omt, ocam, order, k, stages)
+        assert (fr2.visible, fr2.pairs, si.tiles_done) == (m["visible"], m["pairs"], m["tiles_done"]), "K = %d" % k
         seen.add(si.tiles_done == 40 * 23)
         if si.tiles_done == 40 * 23:
-            # everything round 2 could have emitted was dropped
-            one = gs.Renderer(device)
-            one.set_rounds(0)
-            img = gs.Buffer(device, size=W * H * 16)
-            one.render(stream, buf, gt, mt, cam, img.device_ptr())
-            assert fr2.pairs < one.wait_frame().pairs
+            # everything round 2 could have emitted was dropped: the frame's pairs are round 1's
+            assert m["gated"] and fr2.pairs == m["D1"] < m["D"]
     assert seen == {False, True}, "the scene must finish every tile for the longest round 1 only: %s" % seen
 
 

@@ -508,8 +508,11 @@ extern "C" gs_status gs_buffer_create(gs_device *dev, size_t bytes, const void *
             return fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemcpy failed: %s", hipGetErrorString(e));
         }
     } else if (bytes) {
-        // wgpu zero-initialises new buffers
+        // wgpu zero-initialises new buffers.  hipMemset of device memory runs on the null stream and may return before it
+        // has run; the caller's streams are non-blocking and do not wait for that stream, so the fill is awaited here —
+        // or it may land on top of what the caller writes next
         hipError_t e = hipMemset(p, 0, bytes);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
         if (e != hipSuccess) {
             (void)hipFree(p);
             return fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemset failed: %s", hipGetErrorString(e));
@@ -3827,6 +3830,9 @@ extern "C" gs_status gs_selection_create(gs_device *dev, size_t n, gs_selection 
     const size_t bytes = (sel->nwords ? sel->nwords : 1) * 4;
     hipError_t e = hipMalloc((void **)&sel->words, bytes);
     if (e == hipSuccess) e = hipMemset(sel->words, 0, bytes);
+    // (awaited: the null stream's fill is not ordered against the non-blocking stream of the upload that follows, and a
+    // late fill clears a mask that was uploaded and already read once)
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
         if (sel->words) (void)hipFree(sel->words);
         delete sel;

@@ -1580,8 +1580,9 @@ __global__ __launch_bounds__(EXP_CHUNK) void k_expand_count(ExpandIO io) {
 }
 
 // Round 2 of a two-round frame (DESIGN.md §4.2 "rounds"): which of the visible Gaussians behind the nearest K can still
-// colour a pixel?  A Gaussian whose rect (at most 3 x 3 tiles; of a rect that lost tiles to the exact test, version 4,
-// only the kept ones) lies entirely in tiles that round 1 finished cannot, and is dropped; larger rects are few and stay.
+// colour a pixel?  A Gaussian whose rect (at most 3 x 3 tiles; a rect that lost tiles to the exact test, version 4, is
+// judged by its whole box, the lost tiles included) lies entirely in tiles that round 1 finished cannot, and is dropped;
+// larger rects are few and stay.
 // k_round2_box_table first condenses the finished-tile bits into one entry per tile: "is the w x h box at this origin
 // finished?".  k_round2_slot_bits then answers the question for EVERY output slot, in slot order — a stream over the rect
 // array instead of a gather in depth order (a first version gathered: 495 us at 50 M, a 200 MB array read by random
