@@ -18,7 +18,7 @@ open(os.path.join(csrc, "_gen_kernel_lib_src.h"), "w").write(
 PY
 mkdir -p "$root/build/ab"
 out="$root/build/ab/libgs3d_hip_$short.so"
+# every source of that revision's csrc/ (one HIP unit before the split into units, seven after it)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -Wall -Wno-unused-function \
-    -I"$tmp/include" -o "$out" "$tmp/wgpu-3dgs-core_amd/csrc/gs3d.hip" "$tmp/wgpu-3dgs-core_amd/csrc/gs_ply.cpp" \
-    "$tmp/wgpu-3dgs-core_amd/csrc/gs_spz.cpp" -lhiprtc -lz
+    -I"$tmp/include" -o "$out" "$tmp"/wgpu-3dgs-core_amd/csrc/*.hip "$tmp"/wgpu-3dgs-core_amd/csrc/*.cpp -lhiprtc -lz
 echo "$out"

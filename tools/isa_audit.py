@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per kernel of libgs3d_hip.so: the ORDER in which hipcc emitted global loads (L), stores (S), global
+"""Per kernel of the render unit of libgs3d_hip.so (csrc/gs3d.hip: the kernels of gs_render_kernels.h): the ORDER in which hipcc emitted global loads (L), stores (S), global
 atomics (A) and s_waitcnt vmcnt(n) (wn), barriers (|), plus VGPRs and LDS — no GPU needed.
 
 A run of `L w0 L w0 L w0` where the source says "issue all loads, then use them" means the loads run

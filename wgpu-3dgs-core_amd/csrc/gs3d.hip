@@ -1,1532 +1,17 @@
-// gs3d.hip — host side of libgs3d_hip.so: the C ABI of include/gs3d.h over the gfx950 kernels.
+// gs3d.hip — the render side of libgs3d_hip.so: camera, renderer, sorts, the spatial order of a buffer's mirror, the
+// stages of a frame, the parity taps, and the stand-alone sort / scan.  Kernels: gs_render_kernels.h.  The rest of the C
+// ABI of include/gs3d.h is in gs_core / gs_bundle / gs_select / gs_edit / gs_stats / gs_neighbors.hip.
 // Built by hipcc --offload-arch=gfx950 -ffp-contract=off (see build.py).  No CPU fallback: every
 // compute entry point needs a HIP device.
-#include "gs_internal.h"
+#include "gs_host.h"
 
 #include <dlfcn.h>
 
-#include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
-
-#include <atomic>
-#include <mutex>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <string>
-#include <thread>
-#include <vector>
 
-#include "gs_policy.h"
-#include "gs_bundle_kernels.h"
 #include "gs_render_kernels.h"
-#include "gs_select_kernels.h"
-#include "gs_edit_kernels.h"
-#include "gs_stats_kernels.h"
-#include "gs_neighbor_kernels.h"
-#include "gs_pack_kernels.h"
-#include "_gen_kernel_lib_src.h"
 
-// ------------------------------------------------------------------------------------------------
-// errors
-// ------------------------------------------------------------------------------------------------
-
-static thread_local gs_error_info t_err = {0, 0, 0, 0, {0}};
-
-gs_status gs_fail(gs_status code, uint64_t a, uint64_t b, uint64_t c, const char *fmt, ...) {
-    t_err.code = code;
-    t_err.a = a;
-    t_err.b = b;
-    t_err.c = c;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(t_err.message, sizeof(t_err.message), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define GS_HIP(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(e_ == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP,            \
-                        (uint64_t)e_, 0, 0, "%s failed: %s", #expr, hipGetErrorString(e_));       \
-    } while (0)
-
-#define GS_TRY(expr)                  \
-    do {                              \
-        gs_status s_ = (expr);        \
-        if (s_ != GS_OK) return s_;   \
-    } while (0)
-
-#define fail gs_fail
-
-// ------------------------------------------------------------------------------------------------
-// environment switches (gsp::Switches, gs_policy.h): read once, on the first use of any of them
-// ------------------------------------------------------------------------------------------------
-
-static bool env_on(const char *name) {      // NAME=1 switches on
-    const char *e = std::getenv(name);
-    return e && e[0] == '1';
-}
-static bool env_off(const char *name) {     // NAME=0 switches off
-    const char *e = std::getenv(name);
-    return e && e[0] == '0';
-}
-static long env_int(const char *name, long dflt) {
-    const char *e = std::getenv(name);
-    return e ? std::atol(e) : dflt;
-}
-// the three variables that are read again at every call (parallel_for, gs_device_create, buffer creation)
-static const char *env_now(const char *name) { return std::getenv(name); }
-
-static gsp::Switches read_switches() {
-    gsp::Switches s;
-    s.roctx = env_on("GS3D_ROCTX");
-    s.event_fence = env_on("GS3D_EVENT_FENCE");
-    s.frame_event = env_on("GS3D_FRAME_EVENT");
-    s.test_rank_fault = env_on("GS3D_TEST_RANK_FAULT");
-    if (const char *e = std::getenv("GS3D_TEST_RANK_WATCH")) {
-        s.test_rank_watch_set = true;
-        s.test_rank_watch = (uint32_t)std::strtoul(e, nullptr, 10);
-    }
-    s.rect_v1 = env_on("GS3D_RECT_V1");
-    s.rect32_off = env_off("GS3D_RECT32");
-    s.wt_stores = (int)env_int("GS3D_WT_STORES", s.wt_stores);
-    s.wt_records = (int)env_int("GS3D_WT_RECORDS", s.wt_records);
-    s.scan_rows_small_off = env_off("GS3D_SCAN_ROWS_SMALL");
-    s.nt_scatter = (int)env_int("GS3D_NT_SCATTER", s.nt_scatter);
-    s.chunk_hist_off = env_off("GS3D_CHUNK_HIST");
-    s.narrow_keys_off = env_off("GS3D_NARROW_KEYS");
-    s.xcd_remap_off = env_off("GS3D_XCD_REMAP");
-    s.xcd_remap_c = (int)env_int("GS3D_XCD_REMAP_C", s.xcd_remap_c);
-    s.depth_sort_large = (int)env_int("GS3D_DEPTH_SORT_LARGE", s.depth_sort_large);
-    s.tile_sort_large = (int)env_int("GS3D_TILE_SORT_LARGE", s.tile_sort_large);
-    s.tile_masks = (int)env_int("GS3D_TILE_MASKS", s.tile_masks);
-    s.depth_msd = (int)env_int("GS3D_DEPTH_MSD", s.depth_msd);
-    s.blend_groups = (int)env_int("GS3D_BLEND_GROUPS", s.blend_groups);
-    s.rounds = (int)env_int("GS3D_ROUNDS", s.rounds);
-    s.round1 = env_int("GS3D_ROUND1", s.round1);
-    s.round_partition = (int)env_int("GS3D_ROUND_PARTITION", s.round_partition);
-    s.force_banded = (int)env_int("GS3D_FORCE_BANDED", s.force_banded);
-    s.mask_rec = (int)env_int("GS3D_MASK_REC", s.mask_rec);
-    s.nt_loads = (int)env_int("GS3D_NT_LOADS", s.nt_loads);
-    s.block_cull_off = env_off("GS3D_BLOCK_CULL");
-    s.block_list = (int)env_int("GS3D_BLOCK_LIST", s.block_list);
-    s.pre_serial = env_off("GS3D_PRE_PIPELINE");
-    s.cursor_kernel = (int)env_int("GS3D_CURSOR_KERNEL", s.cursor_kernel);
-    s.expand_xcd = (int)env_int("GS3D_EXPAND_XCD", s.expand_xcd);
-    s.tile_msd = (int)env_int("GS3D_TILE_MSD", s.tile_msd);
-    s.tile_msd_auto = env_on("GS3D_TILE_MSD_AUTO");
-    s.ranges_in_blend = (int)env_int("GS3D_RANGES_IN_BLEND", s.ranges_in_blend);
-    s.ranges_search = (int)env_int("GS3D_RANGES_SEARCH", s.ranges_search);
-    return s;
-}
-
-static const gsp::Switches &switches() {
-    static const gsp::Switches s = read_switches();
-    return s;
-}
-
-extern "C" void gs_last_error(gs_error_info *out) {
-    if (out) *out = t_err;
-}
-
-extern "C" uint32_t gs_abi_version(void) { return GS3D_ABI_VERSION; }
-
-extern "C" void gs_hip_versions(int32_t *compiled, int32_t *runtime, int32_t *driver) {
-    if (compiled) *compiled = HIP_VERSION;
-    int v = 0;
-    if (runtime) *runtime = hipRuntimeGetVersion(&v) == hipSuccess ? v : 0;
-    v = 0;
-    if (driver) *driver = hipDriverGetVersion(&v) == hipSuccess ? v : 0;
-}
-
-extern "C" const char *gs_status_string(gs_status s) {
-    switch (s) {
-    case GS_OK: return "ok";
-    case GS_ERR_INVALID_ARGUMENT: return "invalid argument";
-    case GS_ERR_NO_DEVICE: return "no HIP device";
-    case GS_ERR_HIP: return "HIP runtime error";
-    case GS_ERR_OUT_OF_MEMORY: return "out of device memory";
-    case GS_ERR_COUNT_MISMATCH: return "Gaussians count mismatch";
-    case GS_ERR_RANGE_COUNT_MISMATCH: return "Gaussians range count mismatch";
-    case GS_ERR_BUFFER_SIZE_NOT_MULTIPLE: return "buffer size and expected multiple size mismatch";
-    case GS_ERR_BUFFER_SIZE_MISMATCHED: return "buffer size and expected size mismatch";
-    case GS_ERR_RESOURCE_COUNT_MISMATCH: return "resource count and bind group layout count mismatch";
-    case GS_ERR_WORKGROUP_SIZE_EXCEEDS_LIMIT: return "workgroup size exceeds device limit";
-    case GS_ERR_MISSING_BIND_GROUP_LAYOUT: return "missing bind group layout for compute bundle";
-    case GS_ERR_MISSING_RESOLVER: return "missing resolver for compute bundle";
-    case GS_ERR_MISSING_ENTRY_POINT: return "missing entry point for compute bundle";
-    case GS_ERR_MISSING_MAIN_SHADER: return "missing main shader for compute bundle";
-    case GS_ERR_KERNEL_COMPILE: return "kernel compilation failed";
-    case GS_ERR_LOSSY_CONFIG: return "configuration cannot be converted back to a Gaussian";
-    case GS_ERR_DOWNLOAD: return "buffer download failed";
-    case GS_ERR_PAIR_OVERFLOW: return "more than 2^32 (tile, Gaussian) pairs";
-    case GS_ERR_PAIR_CAPACITY: return "pair capacity exceeded; render again";
-    case GS_ERR_RANK_ORDER: return "radix rank watchdog fired; device switched to the ballot-based rank; render again";
-    case GS_ERR_PLY: return "PLY read error";
-    case GS_ERR_SPZ: return "SPZ read error";
-    default: return "unknown";
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// host-side data model: packing (G::from_gaussian) — runs on the host in the reference too
-// ------------------------------------------------------------------------------------------------
-
-static bool valid_cfg(int sh, int cov) { return sh >= 0 && sh <= 3 && cov >= 0 && cov <= 2; }
-
-extern "C" size_t gs_pod_size(gs_sh_config sh, gs_cov3d_config cov) {
-    if (!valid_cfg(sh, cov)) return 0;
-    return (size_t)gs::pod_bytes(sh, cov);
-}
-
-static const char *k_feature_names[7] = {"sh_single", "sh_half", "sh_norm8", "sh_none",
-                                         "cov3d_rot_scale", "cov3d_single", "cov3d_half"};
-
-extern "C" const char *gs_feature_name(uint32_t index) {
-    return index < 7 ? k_feature_names[index] : nullptr;
-}
-
-extern "C" gs_status gs_pod_features(gs_sh_config sh, gs_cov3d_config cov, uint8_t out[7]) {
-    if (!valid_cfg(sh, cov) || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad config");
-    for (int i = 0; i < 7; i++) out[i] = (i == (int)sh) || (i == 4 + (int)cov);
-    return GS_OK;
-}
-
-static float f16_to_f32_host(uint16_t h) {
-    union { uint32_t u; float f; } o;
-    uint32_t sign = ((uint32_t)h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
-    if (e == 0) {
-        o.f = std::ldexp((float)m, -24);
-        o.u |= sign;
-    } else if (e == 31) {
-        o.u = sign | 0x7f800000u | (m << 13);
-    } else {
-        o.u = sign | ((e + 112u) << 23) | (m << 13);
-    }
-    return o.f;
-}
-
-template <class F>
-static void parallel_for(size_t n, F fn) {
-    unsigned hw = std::thread::hardware_concurrency();
-    size_t threads = n < 65536 ? 1 : (hw ? (hw > 32 ? 32 : hw) : 4);
-    if (const char *e = env_now("GS3D_HOST_THREADS")) threads = std::atoi(e) > 0 ? (size_t)std::atoi(e) : threads;
-    if (threads <= 1) {
-        fn((size_t)0, n);
-        return;
-    }
-    std::vector<std::thread> pool;
-    size_t per = (n + threads - 1) / threads;
-    for (size_t t = 0; t < threads; t++) {
-        size_t a = t * per, b = a + per < n ? a + per : n;
-        if (a >= b) break;
-        pool.emplace_back([=] { fn(a, b); });
-    }
-    for (auto &th : pool) th.join();
-}
-
-// G::from_gaussian on the host: the same encoders the device kernel uses (gs_pack_kernels.h)
-static void pack_one(int sh, int cov, const gs_gaussian &g, uint8_t *p, size_t stride) {
-    static_assert(sizeof(gs_gaussian) == gs::GAUSSIAN_WORDS * 4, "gs_gaussian layout");
-    uint32_t gw[gs::GAUSSIAN_WORDS], pw[56];
-    std::memcpy(gw, &g, sizeof(gw));
-    gs::pack_words(sh, cov, gw, pw);
-    std::memcpy(p, pw, stride);
-}
-
-extern "C" gs_status gs_pack(gs_sh_config sh, gs_cov3d_config cov, const gs_gaussian *in, size_t n,
-                             void *out) {
-    if (!valid_cfg(sh, cov) || (n && (!in || !out)))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "gs_pack: bad argument");
-    size_t stride = gs_pod_size(sh, cov);
-    uint8_t *o = (uint8_t *)out;
-    parallel_for(n, [=](size_t a, size_t b) {
-        for (size_t i = a; i < b; i++) pack_one(sh, cov, in[i], o + i * stride, stride);
-    });
-    return GS_OK;
-}
-
-extern "C" gs_status gs_unpack_to_gaussian(gs_sh_config sh, gs_cov3d_config cov, const void *pods,
-                                           size_t n, gs_gaussian *out) {
-    if (!valid_cfg(sh, cov) || (n && (!pods || !out)))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "gs_unpack_to_gaussian: bad argument");
-    if (sh == GS_SH_NONE)
-        return fail(GS_ERR_LOSSY_CONFIG, 0, 0, 0, "Cannot convert from SH None configuration");
-    if (cov == GS_COV3D_SINGLE)
-        return fail(GS_ERR_LOSSY_CONFIG, 0, 0, 0, "Cannot convert from Cov3d Single configuration");
-    if (cov == GS_COV3D_HALF)
-        return fail(GS_ERR_LOSSY_CONFIG, 0, 0, 0, "Cannot convert from Cov3d Half configuration");
-    size_t stride = gs_pod_size(sh, cov);
-    const uint8_t *in = (const uint8_t *)pods;
-    parallel_for(n, [=](size_t a, size_t b) {
-        for (size_t i = a; i < b; i++) {
-            uint32_t pw[56], gw[gs::GAUSSIAN_WORDS];
-            std::memcpy(pw, in + i * stride, stride);
-            gs::unpack_words(sh, pw, gw);       // the same code the device kernel runs (k_unpack_pods)
-            std::memcpy(&out[i], gw, sizeof(gw));
-        }
-    });
-    return GS_OK;
-}
-
-extern "C" gs_status gs_max_std_dev_encode(float v, uint8_t *out) {
-    if (!out || !(v >= 0.0f && v <= 3.0f))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "max_std_dev must be in [0, 3]");
-    *out = (uint8_t)(v / 3.0f * 255.0f);
-    return GS_OK;
-}
-
-extern "C" float gs_max_std_dev_decode(uint8_t v) { return (float)v / 255.0f * 3.0f; }
-
-extern "C" gs_status gs_gaussian_transform_pod_new(float size, gs_display_mode mode, uint8_t sh_deg,
-                                                   uint8_t no_sh0, float max_std_dev,
-                                                   gs_gaussian_transform_pod *out) {
-    if (!out || (int)mode < 0 || (int)mode > 2)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad display mode");
-    if (sh_deg > 3) return fail(GS_ERR_INVALID_ARGUMENT, sh_deg, 0, 0, "SH degree must be in [0, 3]");
-    uint8_t sd;
-    GS_TRY(gs_max_std_dev_encode(max_std_dev, &sd));
-    out->size = size;
-    out->flags[0] = (uint8_t)mode;
-    out->flags[1] = sh_deg;
-    out->flags[2] = no_sh0 ? 1 : 0;
-    out->flags[3] = sd;
-    return GS_OK;
-}
-
-extern "C" void gs_gaussian_transform_pod_default(gs_gaussian_transform_pod *out) {
-    gs_gaussian_transform_pod_new(1.0f, GS_DISPLAY_SPLAT, 3, 0, 3.0f, out);
-}
-
-extern "C" void gs_model_transform_pod_new(const float pos[3], const float rot[4],
-                                           const float scale[3], gs_model_transform_pod *out) {
-    std::memset(out, 0, sizeof(*out));
-    std::memcpy(out->pos, pos, 12);
-    std::memcpy(out->rot, rot, 16);
-    std::memcpy(out->scale, scale, 12);
-}
-
-extern "C" void gs_model_transform_pod_default(gs_model_transform_pod *out) {
-    const float p[3] = {0, 0, 0}, r[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1};
-    gs_model_transform_pod_new(p, r, s, out);
-}
-
-// ------------------------------------------------------------------------------------------------
-// device / stream / buffer
-// ------------------------------------------------------------------------------------------------
-
-struct gs_device {
-    int ordinal;
-    gs_limits limits;
-    hipStream_t internal;  // for blocking helper work
-    // probe result: returning LDS atomics hand out lane-ordered values.  Written by any renderer of the device whose rank
-    // watchdog fired (gs_render_frame / gs_renderer_wait_frame, possibly from different host threads) and read once per
-    // frame (SortCtx::fast_rank) and by the stand-alone sorts: atomic, relaxed — it only ever goes from true to false.
-    std::atomic<bool> lds_atomic_ordered{false};
-    // renderers of this device: gs_stream_destroy records the end-of-frame event of those whose last frame sits on the
-    // stream that is going away (the event is otherwise recorded lazily, when the renderer moves to another stream)
-    std::mutex renderers_mu;
-    std::vector<struct gs_renderer *> renderers;
-};
-
-struct gs_stream {
-    gs_device *dev;
-    hipStream_t s;
-    bool owned;
-};
-
-struct gs_buffer {
-    gs_device *dev;
-    void *ptr;
-    size_t bytes;
-    bool owned;
-    std::atomic<int> refs;
-};
-
-static gs_status use_device(const gs_device *dev) {
-    if (!dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null device");
-    GS_HIP(hipSetDevice(dev->ordinal));
-    // HIP's "last error" is sticky per thread: drop whatever an earlier, already reported failure
-    // left behind so that the hipGetLastError() checks after our launches only see our launches
-    (void)hipGetLastError();
-    return GS_OK;
-}
-
-extern "C" gs_status gs_device_create(int32_t ordinal, gs_device **out) {
-    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
-    *out = nullptr;
-    int count = 0;
-    hipError_t e = hipGetDeviceCount(&count);
-    if (e != hipSuccess || count <= 0)
-        return fail(GS_ERR_NO_DEVICE, (uint64_t)e, 0, 0, "no HIP device available (%s)",
-                    e == hipSuccess ? "count = 0" : hipGetErrorString(e));
-    if (ordinal < 0 || ordinal >= count)
-        return fail(GS_ERR_NO_DEVICE, 0, 0, 0, "device ordinal %d out of range [0, %d)", ordinal, count);
-    GS_HIP(hipSetDevice(ordinal));
-    hipDeviceProp_t props;
-    GS_HIP(hipGetDeviceProperties(&props, ordinal));
-    gs_device *d = new gs_device();
-    d->ordinal = ordinal;
-    std::memset(&d->limits, 0, sizeof(d->limits));
-    d->limits.max_compute_workgroup_size_x = (uint32_t)props.maxThreadsDim[0];
-    d->limits.max_compute_invocations_per_workgroup = (uint32_t)props.maxThreadsPerBlock;
-    d->limits.compute_units = (uint32_t)props.multiProcessorCount;
-    d->limits.wavefront_size = (uint32_t)props.warpSize;
-    d->limits.total_memory_bytes = (uint64_t)props.totalGlobalMem;
-    std::snprintf(d->limits.arch_name, sizeof(d->limits.arch_name), "%s", props.gcnArchName);
-    hipError_t se = hipStreamCreateWithFlags(&d->internal, hipStreamNonBlocking);
-    if (se != hipSuccess) {
-        delete d;
-        return fail(GS_ERR_HIP, (uint64_t)se, 0, 0, "hipStreamCreate failed: %s", hipGetErrorString(se));
-    }
-    // probe the LDS-atomic ordering the fast radix ranking relies on (gs_render_kernels.h)
-    d->lds_atomic_ordered = false;
-    if (!env_now("GS3D_DISABLE_FAST_RANK")) {
-        uint32_t *bad = nullptr;
-        if (hipMalloc((void **)&bad, 4) == hipSuccess) {
-            uint32_t h = 1;
-            if (hipMemset(bad, 0, 4) == hipSuccess) {
-                // both digit widths of the sorts (256 and 512 counters per wave), the scatter's own access pattern
-                hipLaunchKernelGGL(gs::k_probe_lds_atomic_order<8>, dim3(512), dim3(gs::SORT_THREADS), 0, d->internal,
-                                   8u, 0x3D650001u, bad);
-                hipLaunchKernelGGL(gs::k_probe_lds_atomic_order<9>, dim3(512), dim3(gs::SORT_THREADS), 0, d->internal,
-                                   8u, 0x3D650002u, bad);
-                if (hipStreamSynchronize(d->internal) == hipSuccess &&
-                    hipMemcpy(&h, bad, 4, hipMemcpyDeviceToHost) == hipSuccess)
-                    d->lds_atomic_ordered = (h == 0);
-            }
-            (void)hipFree(bad);
-        }
-        (void)hipGetLastError();
-    }
-    *out = d;
-    return GS_OK;
-}
-
-extern "C" int32_t gs_device_fast_rank(const gs_device *dev) { return dev && dev->lds_atomic_ordered.load() ? 1 : 0; }
-
-extern "C" void gs_device_destroy(gs_device *dev) {
-    if (!dev) return;
-    (void)hipSetDevice(dev->ordinal);
-    (void)hipStreamDestroy(dev->internal);
-    delete dev;
-}
-
-extern "C" gs_status gs_device_limits(const gs_device *dev, gs_limits *out) {
-    if (!dev || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    *out = dev->limits;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_device_synchronize(gs_device *dev) {
-    GS_TRY(use_device(dev));
-    GS_HIP(hipDeviceSynchronize());
-    return GS_OK;
-}
-
-extern "C" gs_status gs_stream_create(gs_device *dev, gs_stream **out) {
-    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
-    GS_TRY(use_device(dev));
-    hipStream_t s;
-    GS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    *out = new gs_stream{dev, s, true};
-    return GS_OK;
-}
-
-extern "C" gs_status gs_device_stream_priority_range(gs_device *dev, int32_t *least, int32_t *greatest) {
-    GS_TRY(use_device(dev));
-    int lo = 0, hi = 0;
-    GS_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    if (least) *least = lo;
-    if (greatest) *greatest = hi;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_stream_create_with_priority(gs_device *dev, int32_t priority, gs_stream **out) {
-    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
-    GS_TRY(use_device(dev));
-    int lo = 0, hi = 0;
-    GS_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    if (priority > lo || priority < hi)
-        return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(int64_t)priority, 0, 0, "stream priority %d outside [%d (least), %d (greatest)]",
-                    priority, lo, hi);
-    hipStream_t s;
-    GS_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority));
-    *out = new gs_stream{dev, s, true};
-    return GS_OK;
-}
-
-extern "C" gs_status gs_stream_wrap(gs_device *dev, void *hip_stream, gs_stream **out) {
-    if (!dev || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    *out = new gs_stream{dev, (hipStream_t)hip_stream, false};
-    return GS_OK;
-}
-
-extern "C" void *gs_stream_native(const gs_stream *s) { return s ? (void *)s->s : nullptr; }
-
-extern "C" gs_status gs_stream_synchronize(gs_stream *s) {
-    if (!s) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null stream");
-    GS_TRY(use_device(s->dev));
-    GS_HIP(hipStreamSynchronize(s->s));
-    return GS_OK;
-}
-
-static void renderers_leave_stream(gs_device *dev, hipStream_t st);
-
-extern "C" void gs_stream_destroy(gs_stream *s) {
-    if (!s) return;
-    // A renderer whose last frame was enqueued on this stream records its end-of-frame event lazily, on the stream, when
-    // it moves elsewhere (gs_render_frame): do that now, while the handle is alive.  This holds for wrapped streams too
-    // (gs_stream_wrap): destroy the gs_stream BEFORE the hipStream_t it wraps.
-    (void)hipSetDevice(s->dev->ordinal);
-    renderers_leave_stream(s->dev, s->s);
-    if (s->owned) {
-        (void)hipSetDevice(s->dev->ordinal);
-        (void)hipStreamDestroy(s->s);
-    }
-    delete s;
-}
-
-static hipStream_t stream_of(gs_device *dev, gs_stream *s) { return s ? s->s : dev->internal; }
-
-extern "C" gs_status gs_buffer_create(gs_device *dev, size_t bytes, const void *init,
-                                      gs_buffer **out) {
-    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
-    GS_TRY(use_device(dev));
-    void *p = nullptr;
-    // a zero-sized wgpu buffer is legal; keep a 16-byte allocation so the pointer is valid
-    GS_HIP(hipMalloc(&p, bytes ? bytes : 16));
-    if (init && bytes) {
-        hipError_t e = hipMemcpy(p, init, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemcpy failed: %s", hipGetErrorString(e));
-        }
-    } else if (bytes) {
-        // wgpu zero-initialises new buffers.  hipMemset of device memory runs on the null stream and may return before it
-        // has run; the caller's streams are non-blocking and do not wait for that stream, so the fill is awaited here —
-        // or it may land on top of what the caller writes next
-        hipError_t e = hipMemset(p, 0, bytes);
-        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemset failed: %s", hipGetErrorString(e));
-        }
-    }
-    gs_buffer *b = new gs_buffer();
-    b->dev = dev;
-    b->ptr = p;
-    b->bytes = bytes;
-    b->owned = true;
-    b->refs.store(1);
-    *out = b;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_buffer_from_raw(gs_device *dev, void *device_ptr, size_t bytes,
-                                        gs_buffer **out) {
-    if (!dev || !out || (!device_ptr && bytes))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    gs_buffer *b = new gs_buffer();
-    b->dev = dev;
-    b->ptr = device_ptr;
-    b->bytes = bytes;
-    b->owned = false;
-    b->refs.store(1);
-    *out = b;
-    return GS_OK;
-}
-
-extern "C" gs_buffer *gs_buffer_retain(gs_buffer *b) {
-    if (b) b->refs.fetch_add(1);
-    return b;
-}
-
-extern "C" void gs_buffer_release(gs_buffer *b) {
-    if (!b) return;
-    if (b->refs.fetch_sub(1) == 1) {
-        if (b->owned && b->ptr) {
-            (void)hipSetDevice(b->dev->ordinal);
-            (void)hipFree(b->ptr);
-        }
-        delete b;
-    }
-}
-
-extern "C" size_t gs_buffer_size(const gs_buffer *b) { return b ? b->bytes : 0; }
-extern "C" void *gs_buffer_device_ptr(const gs_buffer *b) { return b ? b->ptr : nullptr; }
-
-extern "C" gs_status gs_buffer_write(gs_buffer *b, gs_stream *s, size_t offset, const void *src,
-                                     size_t bytes) {
-    if (!b || (bytes && !src)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (offset > b->bytes || bytes > b->bytes - offset)
-        return fail(GS_ERR_INVALID_ARGUMENT, offset, bytes, b->bytes,
-                    "write of %zu bytes at offset %zu overruns buffer of %zu bytes", bytes, offset,
-                    b->bytes);
-    if (!bytes) return GS_OK;
-    GS_TRY(use_device(b->dev));
-    hipStream_t st = stream_of(b->dev, s);
-    GS_HIP(hipMemcpyAsync((uint8_t *)b->ptr + offset, src, bytes, hipMemcpyHostToDevice, st));
-    // queue.write_buffer captures `src` at call time: do not return while the host memory may
-    // still be read by an in-flight staged copy.
-    GS_HIP(hipStreamSynchronize(st));
-    return GS_OK;
-}
-
-extern "C" gs_status gs_buffer_download(gs_buffer *b, gs_stream *s, void *dst, size_t bytes) {
-    if (!b || (bytes && !dst)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (bytes > b->bytes)
-        return fail(GS_ERR_INVALID_ARGUMENT, bytes, b->bytes, 0,
-                    "download of %zu bytes from buffer of %zu bytes", bytes, b->bytes);
-    if (!bytes) return GS_OK;
-    GS_TRY(use_device(b->dev));
-    hipStream_t st = stream_of(b->dev, s);
-    hipError_t e = hipMemcpyAsync(dst, b->ptr, bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess)
-        return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    return GS_OK;
-}
-
-// BufferWrapper::prepare_download / map_download (src/buffer/mod.rs:48-101): the copy into a
-// host-visible staging buffer is only ENQUEUED; the caller maps (waits for) it later.
-struct gs_download {
-    gs_device *dev;
-    void *pinned;
-    size_t bytes;
-    hipEvent_t done;
-};
-
-extern "C" gs_status gs_buffer_prepare_download(gs_buffer *b, gs_stream *s, gs_download **out) {
-    if (!b || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    *out = nullptr;
-    GS_TRY(use_device(b->dev));
-    gs_download *d = new gs_download();
-    d->dev = b->dev;
-    d->bytes = b->bytes;
-    d->pinned = nullptr;
-    hipError_t e = hipHostMalloc(&d->pinned, b->bytes ? b->bytes : 1, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->done, hipEventDisableTiming);
-    else d->done = nullptr;
-    hipStream_t st = stream_of(b->dev, s);
-    if (e == hipSuccess && b->bytes) e = hipMemcpyAsync(d->pinned, b->ptr, b->bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipEventRecord(d->done, st);
-    if (e != hipSuccess) {
-        if (d->pinned) (void)hipHostFree(d->pinned);
-        if (d->done) (void)hipEventDestroy(d->done);
-        delete d;
-        return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    }
-    *out = d;
-    return GS_OK;
-}
-
-extern "C" int32_t gs_download_ready(gs_download *d) {
-    if (!d) return 0;
-    (void)hipSetDevice(d->dev->ordinal);
-    const hipError_t e = hipEventQuery(d->done);
-    (void)hipGetLastError();
-    return e == hipSuccess ? 1 : 0;
-}
-
-extern "C" gs_status gs_download_map(gs_download *d, const void **data_out, size_t *bytes_out) {
-    if (!d || !data_out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(use_device(d->dev));
-    const hipError_t e = hipEventSynchronize(d->done);
-    if (e != hipSuccess)
-        return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    *data_out = d->pinned;
-    if (bytes_out) *bytes_out = d->bytes;
-    return GS_OK;
-}
-
-extern "C" void gs_download_release(gs_download *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->dev->ordinal);
-    (void)hipEventSynchronize(d->done);     // the copy may still be writing the staging memory
-    (void)hipHostFree(d->pinned);
-    (void)hipEventDestroy(d->done);
-    delete d;
-}
-
-// ------------------------------------------------------------------------------------------------
-// GaussiansBuffer<G>
-// ------------------------------------------------------------------------------------------------
-
-// a device array that grows and never shrinks (hipFree synchronises the device)
-struct DevArray {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-};
-
-static gs_status dev_reserve(DevArray &a, size_t bytes) {
-    if (a.bytes >= bytes && a.ptr) return GS_OK;
-    if (a.ptr) GS_HIP(hipFree(a.ptr));
-    a.ptr = nullptr;
-    a.bytes = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    GS_HIP(hipMalloc(&a.ptr, want));
-    a.bytes = want;
-    return GS_OK;
-}
-
-static void dev_free(DevArray &a) {
-    if (a.ptr) (void)hipFree(a.ptr);
-    a.ptr = nullptr;
-    a.bytes = 0;
-}
-
-// ids of buffers and generations of selections: unique in the process, never 0
-static uint64_t next_object_id() {
-    static std::atomic<uint64_t> next{0};
-    return ++next;
-}
-
-struct gs_gaussians_buffer {
-    gs_buffer *buf;
-    int sh, cov;
-    // block-planar mirror read by the preprocess kernel; rebuilt lazily
-    void *planar;
-    size_t planar_stride;  // capacity in Gaussians = len rounded up to whole 1024-blocks
-    // Gaussians [dirty_lo, dirty_hi) of the AoS buffer are newer than the mirror (empty when lo >= hi).
-    // update_range dirties only its own range, so an editor's per-edit update re-mirrors a few
-    // Gaussians instead of the whole scene.
-    size_t dirty_lo, dirty_hi;
-    // spatial mirror order: order[slot] = Gaussian index, inv[index] = slot; both
-    // null while the mirror is in index order.  `order` is a ref-counted gs_buffer so that the
-    // renderer's parity taps can keep the order of the frame they describe.
-    bool spatial;
-    gs_buffer *order;
-    void *inv;
-    void *block_bounds;      // 8 floats per 1024-slot block (k_block_bounds); null = not available
-    size_t partial_since_order;   // Gaussians rewritten by partial updates since the order was built
-    // The mirror is (re)built on the stream of whichever frame first needs it; frames on OTHER streams
-    // (several renderers keeping frames in flight on one buffer) wait for this event before reading it.
-    hipEvent_t mirror_ready = nullptr;
-    hipStream_t mirror_stream = nullptr;
-    // gs_gaussians_buffer_edit only ENQUEUES its kernel: a mirror rebuild on another stream waits for
-    // this event before it reads the AoS records.  keep_order: the whole buffer is dirty but no position changed (a
-    // colour / opacity edit), so the rebuild repacks through the order it has instead of sorting again.
-    hipEvent_t edit_done = nullptr;
-    hipStream_t edit_stream = nullptr;
-    bool keep_order = false;
-    // what a renderer's slot-ordered selection masks were gathered through: this buffer (ids are never
-    // reused, addresses are) and this build of its mirror order
-    uint64_t uid = next_object_id();
-    uint64_t order_epoch = 0;
-    // gs_gaussians_buffer_create_concat: the per-block offsets its copies read; they are only enqueued
-    // when the call returns, so the new buffer owns the array
-    void *concat_offsets = nullptr;
-    // gs_gaussians_buffer_stats / _histogram: the partial rows and the device result of the last call
-    void *stats_scratch = nullptr;
-    size_t stats_scratch_bytes = 0;
-    // gs_gaussians_buffer_neighbor_counts / gs_select_neighbors: keys, order, sorted positions and the
-    // sort's histograms of the last call; a call on another stream waits for nb_done before it reuses them
-    DevArray nb_scratch, nb_ghist, nb_digit_totals;
-    hipEvent_t nb_done = nullptr;
-    hipStream_t nb_stream = nullptr;
-    void mark(size_t lo, size_t hi) {
-        if (lo >= hi) return;
-        partial_since_order += hi - lo;
-        if (dirty_lo >= dirty_hi) { dirty_lo = lo; dirty_hi = hi; return; }
-        if (lo < dirty_lo) dirty_lo = lo;
-        if (hi > dirty_hi) dirty_hi = hi;
-    }
-    void mark_all() { dirty_lo = 0; dirty_hi = (size_t)-1; keep_order = false; }
-};
-
-static size_t pod_stride(const gs_gaussians_buffer *g) { return (size_t)gs::pod_bytes(g->sh, g->cov); }
-
-extern "C" size_t gs_gaussians_buffer_len(const gs_gaussians_buffer *g) {
-    return g ? g->buf->bytes / pod_stride(g) : 0;
-}
-
-extern "C" gs_status gs_gaussians_buffer_from_buffer(gs_buffer *buffer, gs_sh_config sh,
-                                                     gs_cov3d_config cov,
-                                                     gs_gaussians_buffer **out) {
-    if (!buffer || !out || !valid_cfg(sh, cov))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad argument");
-    size_t stride = gs_pod_size(sh, cov);
-    // the kernels move records as 16-byte vectors: an adopted raw pointer (gs_buffer_from_raw) must
-    // be 16-byte aligned, as every hipMalloc allocation is
-    if ((uintptr_t)buffer->ptr & 15u)
-        return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)buffer->ptr, 16, 0,
-                    "Gaussian buffer device pointer must be 16-byte aligned");
-    if (buffer->bytes % stride != 0)
-        return fail(GS_ERR_BUFFER_SIZE_NOT_MULTIPLE, buffer->bytes, stride, 0,
-                    "buffer size and expected multiple size mismatch: %zu %% %zu != 0",
-                    buffer->bytes, stride);
-    gs_gaussians_buffer *g = new gs_gaussians_buffer();
-    g->buf = gs_buffer_retain(buffer);
-    g->sh = sh;
-    g->cov = cov;
-    g->planar = nullptr;
-    g->planar_stride = 0;
-    {   // default: spatial order on; GS3D_SPATIAL_ORDER=0 keeps the mirror in index order
-        const char *e = env_now("GS3D_SPATIAL_ORDER");
-        g->spatial = !(e && e[0] == '0');
-    }
-    g->order = nullptr;
-    g->inv = nullptr;
-    g->block_bounds = nullptr;
-    g->partial_since_order = 0;
-    g->mark_all();
-    *out = g;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_gaussians_buffer_create(gs_device *dev, gs_sh_config sh, gs_cov3d_config cov,
-                                                const void *pods, size_t len,
-                                                gs_gaussians_buffer **out) {
-    if (!out || !valid_cfg(sh, cov)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad argument");
-    gs_buffer *b = nullptr;
-    GS_TRY(gs_buffer_create(dev, len * gs_pod_size(sh, cov), pods, &b));
-    gs_status st = gs_gaussians_buffer_from_buffer(b, sh, cov, out);
-    gs_buffer_release(b);
-    return st;
-}
-
-#define GS_CFG_TABLE(kernel)                                                                     \
-    {                                                                                            \
-        {kernel<0, 0>, kernel<0, 1>, kernel<0, 2>}, {kernel<1, 0>, kernel<1, 1>, kernel<1, 2>},  \
-        {kernel<2, 0>, kernel<2, 1>, kernel<2, 2>}, {kernel<3, 0>, kernel<3, 1>, kernel<3, 2>},  \
-    }
-
-typedef void (*pack_fn)(const uint32_t *, uint64_t, uint32_t *);
-static pack_fn k_tbl_pack[4][3] = GS_CFG_TABLE(gs::k_pack_pods);
-
-extern "C" gs_status gs_pack_device(gs_device *dev, gs_stream *s, gs_sh_config sh, gs_cov3d_config cov,
-                                    const gs_gaussian *gaussians_device, size_t n, void *pods_device) {
-    if (!dev || !valid_cfg(sh, cov) || (n && (!gaussians_device || !pods_device)))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "gs_pack_device: bad argument");
-    if (((uintptr_t)gaussians_device | (uintptr_t)pods_device) & 3u)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "gs_pack_device: pointers must be 4-byte aligned");
-    GS_TRY(use_device(dev));
-    if (!n) return GS_OK;
-    const uint64_t groups = ((uint64_t)n + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
-    if (groups > 0x7fffffffull) return fail(GS_ERR_INVALID_ARGUMENT, n, 0, 0, "too many Gaussians");
-    hipLaunchKernelGGL(k_tbl_pack[sh][cov], dim3((uint32_t)groups), dim3(256), 0, stream_of(dev, s),
-                       (const uint32_t *)gaussians_device, (uint64_t)n, (uint32_t *)pods_device);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-static pack_fn k_tbl_from_ply[4][3] = GS_CFG_TABLE(gs::k_from_ply_pods);
-
-extern "C" gs_status gs_pack_device_from_ply(gs_device *dev, gs_stream *s, gs_sh_config sh, gs_cov3d_config cov,
-                                             const gs_ply_gaussian_pod *ply_device, size_t n, void *pods_device) {
-    if (!dev || !valid_cfg(sh, cov) || (n && (!ply_device || !pods_device)))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "gs_pack_device_from_ply: bad argument");
-    if (((uintptr_t)ply_device | (uintptr_t)pods_device) & 3u)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "gs_pack_device_from_ply: pointers must be 4-byte aligned");
-    GS_TRY(use_device(dev));
-    if (!n) return GS_OK;
-    const uint64_t groups = ((uint64_t)n + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
-    if (groups > 0x7fffffffull) return fail(GS_ERR_INVALID_ARGUMENT, n, 0, 0, "too many Gaussians");
-    hipLaunchKernelGGL(k_tbl_from_ply[sh][cov], dim3((uint32_t)groups), dim3(256), 0, stream_of(dev, s),
-                       (const uint32_t *)ply_device, (uint64_t)n, (uint32_t *)pods_device);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-// Source records on the host (struct Gaussian, or PlyGaussianPod when `from_ply`) -> PODs in `g` at
-// [start, start + count): the records cross PCIe as they are, slice by slice through TWO staging
-// buffers (the host stages and submits slice i + 1 while the kernel of slice i runs; copies and kernels
-// share one stream, so the transfers themselves run one after the other — the link is the bound:
-// 49.7 GB/s of PLY bytes at 50 M vertices), and are converted on the device.
-// The caller's memory may be reused when this returns.
-static gs_status upload_records(gs_gaussians_buffer *g, gs_stream *s, size_t start, const void *records, size_t count,
-                                bool from_ply) {
-    constexpr size_t PACK_SLICE = 2u << 20;     // 2 Mi records: 2 x 496 MiB of staging at most
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    if (!count) return GS_OK;
-    hipStream_t st = stream_of(dev, s);
-    const size_t rec = from_ply ? sizeof(gs_ply_gaussian_pod) : sizeof(gs_gaussian);
-    const size_t slice = count < PACK_SLICE ? count : PACK_SLICE;
-    const int nbuf = count > slice ? 2 : 1;
-    void *staging[2] = {nullptr, nullptr};
-    hipEvent_t used[2] = {nullptr, nullptr};
-    gs_status rc = GS_OK;
-    for (int i = 0; i < nbuf && rc == GS_OK; i++) {
-        hipError_t e = hipMalloc(&staging[i], slice * rec);
-        if (e != hipSuccess) rc = fail(GS_ERR_OUT_OF_MEMORY, slice * rec, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-        else if ((e = hipEventCreateWithFlags(&used[i], hipEventDisableTiming)) != hipSuccess)
-            rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipEventCreate failed: %s", hipGetErrorString(e));
-    }
-    const size_t stride = pod_stride(g);
-    int k = 0;
-    for (size_t first = 0; first < count && rc == GS_OK; first += slice, k ^= (nbuf - 1)) {
-        const size_t cnt = count - first < slice ? count - first : slice;
-        // the staging buffer's previous kernel must have read it before the next copy overwrites it
-        if (first >= (size_t)nbuf * slice && hipEventSynchronize(used[k]) != hipSuccess) {
-            rc = fail(GS_ERR_HIP, 0, 0, 0, "upload failed");
-            break;
-        }
-        hipError_t e = hipMemcpyAsync(staging[k], (const uint8_t *)records + first * rec, cnt * rec, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
-            break;
-        }
-        void *dst = (uint8_t *)g->buf->ptr + (start + first) * stride;
-        rc = from_ply ? gs_pack_device_from_ply(dev, s, (gs_sh_config)g->sh, (gs_cov3d_config)g->cov,
-                                                (const gs_ply_gaussian_pod *)staging[k], cnt, dst)
-                      : gs_pack_device(dev, s, (gs_sh_config)g->sh, (gs_cov3d_config)g->cov, (const gs_gaussian *)staging[k],
-                                       cnt, dst);
-        if (rc == GS_OK && hipEventRecord(used[k], st) != hipSuccess) rc = fail(GS_ERR_HIP, 0, 0, 0, "upload failed");
-    }
-    // the staging buffers are freed below and the caller's memory may be reused: wait for everything
-    if (hipStreamSynchronize(st) != hipSuccess && rc == GS_OK) rc = fail(GS_ERR_HIP, 0, 0, 0, "pack failed");
-    for (int i = 0; i < 2; i++) {
-        if (used[i]) (void)hipEventDestroy(used[i]);
-        if (staging[i]) (void)hipFree(staging[i]);
-    }
-    return rc;
-}
-
-static gs_status upload_gaussians(gs_gaussians_buffer *g, gs_stream *s, size_t start, const gs_gaussian *gaussians,
-                                  size_t count) {
-    return upload_records(g, s, start, gaussians, count, false);
-}
-
-extern "C" gs_status gs_gaussians_buffer_create_from_ply(gs_device *dev, gs_sh_config sh, gs_cov3d_config cov,
-                                                         const gs_ply_gaussian_pod *ply, size_t len,
-                                                         gs_gaussians_buffer **out) {
-    if (!valid_cfg(sh, cov) || (len && !ply) || !out)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad argument");
-    GS_TRY(gs_gaussians_buffer_create(dev, sh, cov, nullptr, len, out));
-    gs_status rc = upload_records(*out, nullptr, 0, ply, len, true);
-    if (rc != GS_OK) {
-        gs_gaussians_buffer_destroy(*out);
-        *out = nullptr;
-    }
-    return rc;
-}
-
-// SPZ: the decompressed payload crosses PCIe once; one kernel decodes the columns (Gaussian::from_spz,
-// src/gaussian.rs:134-229) and packs (G::from_gaussian)
-typedef void (*spz_fn)(gs::SpzView, uint64_t, uint32_t *);
-static spz_fn k_tbl_from_spz[4][3] = GS_CFG_TABLE(gs::k_from_spz_pods);
-
-extern "C" gs_status gs_gaussians_buffer_create_from_spz_decompressed(gs_device *dev, gs_sh_config sh,
-                                                                      gs_cov3d_config cov, const void *bytes,
-                                                                      size_t len, gs_spz_header *header_out,
-                                                                      gs_gaussians_buffer **out) {
-    if (!valid_cfg(sh, cov) || !bytes || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad argument");
-    *out = nullptr;
-    gs_spz_header h;
-    size_t off[6];
-    uint32_t ncoef = 0;
-    GS_TRY(gs_spz_payload_layout(bytes, len, &h, off, &ncoef));
-    if (header_out) *header_out = h;
-    const size_t n = h.num_points;
-    GS_TRY(gs_gaussians_buffer_create(dev, sh, cov, nullptr, n, out));
-    if (!n) return GS_OK;
-    gs_status rc = GS_OK;
-    void *staging = nullptr;
-    const size_t used = off[5] + n * 3u * ncoef;             // the payload the header declares (len may be larger)
-    hipError_t e = hipMalloc(&staging, used);
-    if (e != hipSuccess) rc = fail(GS_ERR_OUT_OF_MEMORY, used, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-    if (rc == GS_OK && (e = hipMemcpyAsync(staging, bytes, used, hipMemcpyHostToDevice, dev->internal)) != hipSuccess)
-        rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
-    if (rc == GS_OK) {
-        const uint8_t *b = (const uint8_t *)staging;
-        gs::SpzView v{b + off[0], b + off[1], b + off[2], b + off[3], b + off[4], b + off[5], h.version, h.fractional_bits, ncoef};
-        const uint64_t groups = ((uint64_t)n + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
-        hipLaunchKernelGGL(k_tbl_from_spz[sh][cov], dim3((uint32_t)groups), dim3(256), 0, dev->internal, v, (uint64_t)n,
-                           (uint32_t *)(*out)->buf->ptr);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(dev->internal);
-        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "SPZ decode kernel failed: %s", hipGetErrorString(e));
-    }
-    if (staging) (void)hipFree(staging);
-    if (rc != GS_OK) {
-        gs_gaussians_buffer_destroy(*out);
-        *out = nullptr;
-    }
-    return rc;
-}
-
-extern "C" gs_status gs_gaussians_buffer_create_from_spz(gs_device *dev, gs_sh_config sh, gs_cov3d_config cov,
-                                                         const void *bytes, size_t len, gs_spz_header *header_out,
-                                                         gs_gaussians_buffer **out) {
-    if (!bytes || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad argument");
-    std::vector<uint8_t> raw;
-    GS_TRY(gs_spz_gunzip(bytes, len, raw));
-    return gs_gaussians_buffer_create_from_spz_decompressed(dev, sh, cov, raw.data(), raw.size(), header_out, out);
-}
-
-extern "C" gs_status gs_gaussians_buffer_update_range_ply(gs_gaussians_buffer *g, gs_stream *s, size_t start,
-                                                          const gs_ply_gaussian_pod *ply, size_t count) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    size_t len = gs_gaussians_buffer_len(g);
-    if (count > len || start > len - count)
-        return fail(GS_ERR_RANGE_COUNT_MISMATCH, count, start, len,
-                    "Gaussians count mismatch: %zu + %zu > %zu", count, start, len);
-    if (count && !ply) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null ply records");
-    g->mark(start, start + count);
-    return upload_records(g, s, start, ply, count, true);
-}
-
-extern "C" gs_status gs_gaussians_buffer_create_from_gaussians(gs_device *dev, gs_sh_config sh,
-                                                               gs_cov3d_config cov,
-                                                               const gs_gaussian *gaussians,
-                                                               size_t len,
-                                                               gs_gaussians_buffer **out) {
-    if (!valid_cfg(sh, cov) || (len && !gaussians) || !out)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad argument");
-    GS_TRY(gs_gaussians_buffer_create(dev, sh, cov, nullptr, len, out));
-    gs_status rc = upload_gaussians(*out, nullptr, 0, gaussians, len);
-    if (rc != GS_OK) {
-        gs_gaussians_buffer_destroy(*out);
-        *out = nullptr;
-    }
-    return rc;
-}
-
-extern "C" void gs_gaussians_buffer_destroy(gs_gaussians_buffer *g) {
-    if (!g) return;
-    (void)hipSetDevice(g->buf->dev->ordinal);
-    if (g->planar) (void)hipFree(g->planar);
-    if (g->inv) (void)hipFree(g->inv);
-    if (g->block_bounds) (void)hipFree(g->block_bounds);
-    if (g->concat_offsets) (void)hipFree(g->concat_offsets);
-    if (g->stats_scratch) (void)hipFree(g->stats_scratch);
-    for (DevArray *a : {&g->nb_scratch, &g->nb_ghist, &g->nb_digit_totals}) dev_free(*a);
-    if (g->nb_done) (void)hipEventDestroy(g->nb_done);
-    if (g->mirror_ready) (void)hipEventDestroy(g->mirror_ready);
-    if (g->edit_done) (void)hipEventDestroy(g->edit_done);
-    if (g->order) gs_buffer_release(g->order);
-    gs_buffer_release(g->buf);
-    delete g;
-}
-
-extern "C" gs_buffer *gs_gaussians_buffer_buffer(const gs_gaussians_buffer *g) {
-    return g ? g->buf : nullptr;
-}
-extern "C" gs_sh_config gs_gaussians_buffer_sh(const gs_gaussians_buffer *g) {
-    return (gs_sh_config)(g ? g->sh : 0);
-}
-extern "C" gs_cov3d_config gs_gaussians_buffer_cov3d(const gs_gaussians_buffer *g) {
-    return (gs_cov3d_config)(g ? g->cov : 0);
-}
-
-extern "C" gs_status gs_gaussians_buffer_update(gs_gaussians_buffer *g, gs_stream *s,
-                                                const void *pods, size_t count) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    size_t len = gs_gaussians_buffer_len(g);
-    if (count != len)
-        return fail(GS_ERR_COUNT_MISMATCH, count, len, 0, "Gaussians count mismatch: %zu != %zu",
-                    count, len);
-    g->mark_all();
-    return gs_buffer_write(g->buf, s, 0, pods, count * pod_stride(g));
-}
-
-extern "C" gs_status gs_gaussians_buffer_update_range(gs_gaussians_buffer *g, gs_stream *s,
-                                                      size_t start, const void *pods,
-                                                      size_t count) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    size_t len = gs_gaussians_buffer_len(g);
-    if (count > len || start > len - count)      // (start + count could wrap)
-        return fail(GS_ERR_RANGE_COUNT_MISMATCH, count, start, len,
-                    "Gaussians count mismatch: %zu + %zu > %zu", count, start, len);
-    g->mark(start, start + count);
-    return gs_buffer_write(g->buf, s, start * pod_stride(g), pods, count * pod_stride(g));
-}
-
-extern "C" gs_status gs_gaussians_buffer_update_gaussians(gs_gaussians_buffer *g, gs_stream *s,
-                                                          const gs_gaussian *gaussians,
-                                                          size_t count) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    size_t len = gs_gaussians_buffer_len(g);
-    if (count != len)
-        return fail(GS_ERR_COUNT_MISMATCH, count, len, 0, "Gaussians count mismatch: %zu != %zu",
-                    count, len);
-    if (count && !gaussians) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null gaussians");
-    g->mark_all();
-    return upload_gaussians(g, s, 0, gaussians, count);
-}
-
-extern "C" gs_status gs_gaussians_buffer_update_range_gaussians(gs_gaussians_buffer *g, gs_stream *s,
-                                                                size_t start,
-                                                                const gs_gaussian *gaussians,
-                                                                size_t count) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    size_t len = gs_gaussians_buffer_len(g);
-    if (count > len || start > len - count)
-        return fail(GS_ERR_RANGE_COUNT_MISMATCH, count, start, len,
-                    "Gaussians count mismatch: %zu + %zu > %zu", count, start, len);
-    if (count && !gaussians) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null gaussians");
-    g->mark(start, start + count);
-    return upload_gaussians(g, s, start, gaussians, count);
-}
-
-extern "C" gs_status gs_gaussians_buffer_download(gs_gaussians_buffer *g, gs_stream *s,
-                                                  void *pods_out, size_t count) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    if (count > gs_gaussians_buffer_len(g))
-        return fail(GS_ERR_INVALID_ARGUMENT, count, gs_gaussians_buffer_len(g), 0, "count too large");
-    return gs_buffer_download(g->buf, s, pods_out, count * pod_stride(g));
-}
-
-// GaussiansBuffer::download::<Gaussian> (src/buffer/gaussian.rs:186-196): the PODs are converted back
-// on the DEVICE (k_unpack_pods, slice by slice through a staging buffer) and the struct Gaussian
-// records come over PCIe ready to use; bit-equal to downloading the PODs and gs_unpack_to_gaussian.
-typedef void (*unpack_fn)(const uint32_t *, uint64_t, uint32_t *);
-static unpack_fn k_tbl_unpack[3] = {gs::k_unpack_pods<0>, gs::k_unpack_pods<1>, gs::k_unpack_pods<2>};
-
-extern "C" gs_status gs_gaussians_buffer_download_gaussians(gs_gaussians_buffer *g, gs_stream *s,
-                                                            gs_gaussian *out, size_t count) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    if (g->sh == GS_SH_NONE || g->cov != GS_COV3D_ROT_SCALE)
-        return gs_unpack_to_gaussian((gs_sh_config)g->sh, (gs_cov3d_config)g->cov, out, 0, out);   // the reference's error
-    if (count > gs_gaussians_buffer_len(g))
-        return fail(GS_ERR_INVALID_ARGUMENT, count, gs_gaussians_buffer_len(g), 0, "count too large");
-    if (!count) return GS_OK;
-    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    constexpr size_t SLICE = 2u << 20;
-    const size_t slice = count < SLICE ? count : SLICE;
-    void *staging = nullptr;
-    hipError_t e = hipMalloc(&staging, slice * sizeof(gs_gaussian));
-    if (e != hipSuccess)
-        return fail(GS_ERR_OUT_OF_MEMORY, slice * sizeof(gs_gaussian), 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-    gs_status rc = GS_OK;
-    const size_t stride = pod_stride(g);
-    for (size_t first = 0; first < count && rc == GS_OK; first += slice) {
-        const size_t cnt = count - first < slice ? count - first : slice;
-        const uint64_t groups = ((uint64_t)cnt + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
-        hipLaunchKernelGGL(k_tbl_unpack[g->sh], dim3((uint32_t)groups), dim3(256), 0, st,
-                           (const uint32_t *)((const uint8_t *)g->buf->ptr + first * stride), (uint64_t)cnt, (uint32_t *)staging);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out + first, staging, cnt * sizeof(gs_gaussian), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(staging);
-    return rc;
-}
-
-extern "C" void gs_gaussians_buffer_mark_dirty(gs_gaussians_buffer *g) {
-    if (g) g->mark_all();
-}
-
-// ------------------------------------------------------------------------------------------------
-// fixed-size uniform buffers
-// ------------------------------------------------------------------------------------------------
-
-static gs_status fixed_from_buffer(gs_buffer *b, size_t expected) {
-    if (!b) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
-    if (b->bytes != expected)
-        return fail(GS_ERR_BUFFER_SIZE_MISMATCHED, b->bytes, expected, 0,
-                    "buffer size and expected size mismatch: %zu != %zu", b->bytes, expected);
-    return GS_OK;
-}
-
-extern "C" gs_status gs_gaussian_transform_buffer_create(gs_device *dev, gs_buffer **out) {
-    gs_gaussian_transform_pod pod;
-    gs_gaussian_transform_pod_default(&pod);
-    return gs_buffer_create(dev, sizeof(pod), &pod, out);
-}
-extern "C" gs_status gs_gaussian_transform_buffer_update(gs_buffer *b, gs_stream *s,
-                                                         const gs_gaussian_transform_pod *pod) {
-    GS_TRY(fixed_from_buffer(b, sizeof(*pod)));
-    return gs_buffer_write(b, s, 0, pod, sizeof(*pod));
-}
-extern "C" gs_status gs_gaussian_transform_buffer_from_buffer(gs_buffer *b) {
-    return fixed_from_buffer(b, sizeof(gs_gaussian_transform_pod));
-}
-extern "C" gs_status gs_model_transform_buffer_create(gs_device *dev, gs_buffer **out) {
-    gs_model_transform_pod pod;
-    gs_model_transform_pod_default(&pod);
-    return gs_buffer_create(dev, sizeof(pod), &pod, out);
-}
-extern "C" gs_status gs_model_transform_buffer_update(gs_buffer *b, gs_stream *s,
-                                                      const gs_model_transform_pod *pod) {
-    GS_TRY(fixed_from_buffer(b, sizeof(*pod)));
-    return gs_buffer_write(b, s, 0, pod, sizeof(*pod));
-}
-extern "C" gs_status gs_model_transform_buffer_from_buffer(gs_buffer *b) {
-    return fixed_from_buffer(b, sizeof(gs_model_transform_pod));
-}
-
-// ------------------------------------------------------------------------------------------------
-// ComputeBundle
-// ------------------------------------------------------------------------------------------------
-
-typedef void (*bundle_kernel_fn)(gs::BundleArgs, uint32_t);
-
-static bundle_kernel_fn k_tbl_test_gaussian[4][3] = GS_CFG_TABLE(gs::k_test_gaussian);
-static bundle_kernel_fn k_tbl_unpack_soa[4][3] = GS_CFG_TABLE(gs::k_unpack_soa);
-
-struct gs_bundle {
-    gs_device *dev;
-    std::string label;
-    gs_kernel_id kernel;
-    int sh, cov;
-    uint32_t workgroup_size;
-    std::vector<uint32_t> layout;                     // bindings per group
-    std::vector<std::vector<gs_buffer *>> groups;     // managed bind groups (retained)
-    bool managed;
-    bool has_additional_constant;
-    uint32_t additional_constant;
-    uint32_t last_workgroups;
-    // bundles compiled from source (gs_bundle_create_from_source)
-    bool from_source = false;
-    hipModule_t module = nullptr;
-    hipFunction_t func = nullptr;
-};
-
-extern "C" gs_status gs_bundle_create(gs_device *dev, const gs_bundle_desc *desc, gs_bundle **out) {
-    if (!dev || !desc || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if ((int)desc->kernel < 0 || desc->kernel >= GS_KERNEL_COUNT_ || !valid_cfg(desc->sh, desc->cov))
-        return fail(GS_ERR_MISSING_MAIN_SHADER, 0, 0, 0, "unknown kernel id %d", (int)desc->kernel);
-    if (desc->bind_group_count == 0 || !desc->bindings_per_group)
-        return fail(GS_ERR_MISSING_BIND_GROUP_LAYOUT, 0, 0, 0,
-                    "missing bind group layout for compute bundle");
-    // compute_bundle.rs:269-281
-    uint32_t limit = dev->limits.max_compute_workgroup_size_x <
-                             dev->limits.max_compute_invocations_per_workgroup
-                         ? dev->limits.max_compute_workgroup_size_x
-                         : dev->limits.max_compute_invocations_per_workgroup;
-    uint32_t wg = desc->workgroup_size ? desc->workgroup_size : limit;
-    if (wg > limit)
-        return fail(GS_ERR_WORKGROUP_SIZE_EXCEEDS_LIMIT, wg, limit, 0,
-                    "workgroup size exceeds device limit: %u > %u", wg, limit);
-    uint32_t total = 0;
-    for (uint32_t i = 0; i < desc->bind_group_count; i++) total += desc->bindings_per_group[i];
-    if (total > (uint32_t)gs::MAX_BINDINGS)
-        return fail(GS_ERR_INVALID_ARGUMENT, total, gs::MAX_BINDINGS, 0, "too many bindings");
-    gs_bundle *b = new gs_bundle();
-    b->dev = dev;
-    b->label = desc->label ? desc->label : "";
-    b->kernel = desc->kernel;
-    b->sh = desc->sh;
-    b->cov = desc->cov;
-    b->workgroup_size = wg;
-    b->layout.assign(desc->bindings_per_group, desc->bindings_per_group + desc->bind_group_count);
-    b->managed = false;
-    b->has_additional_constant = false;
-    b->additional_constant = 0;
-    b->last_workgroups = 0;
-    for (uint32_t i = 0; i < desc->constant_count; i++) {
-        if (desc->constant_names && desc->constant_names[i] &&
-            !std::strcmp(desc->constant_names[i], "additional_constant")) {
-            b->has_additional_constant = true;
-            b->additional_constant = (uint32_t)desc->constant_values[i];
-        }
-    }
-    *out = b;
-    return GS_OK;
-}
-
-static void release_group(std::vector<gs_buffer *> &g) {
-    for (gs_buffer *x : g) gs_buffer_release(x);
-    g.clear();
-}
-
-extern "C" gs_status gs_bundle_set_bind_group(gs_bundle *b, uint32_t index, gs_buffer *const *buffers,
-                                              uint32_t count) {
-    if (!b) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null bundle");
-    if (index >= b->groups.size())
-        return fail(GS_ERR_INVALID_ARGUMENT, index, b->groups.size(), 0, "bind group index out of bounds");
-    if (count != b->layout[index])
-        return fail(GS_ERR_INVALID_ARGUMENT, count, b->layout[index], 0,
-                    "bind group %u expects %u bindings, got %u", index, b->layout[index], count);
-    std::vector<gs_buffer *> g;
-    for (uint32_t i = 0; i < count; i++) {
-        if (!buffers[i]) {
-            release_group(g);
-            return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null binding");
-        }
-        g.push_back(gs_buffer_retain(buffers[i]));
-    }
-    release_group(b->groups[index]);
-    b->groups[index] = g;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_bundle_create_with_bind_groups(gs_device *dev, const gs_bundle_desc *desc,
-                                                       gs_buffer *const *const *resources,
-                                                       const uint32_t *resource_counts,
-                                                       uint32_t resource_group_count,
-                                                       gs_bundle **out) {
-    gs_bundle *b = nullptr;
-    GS_TRY(gs_bundle_create(dev, desc, &b));
-    // compute_bundle.rs:161-168
-    if (resource_group_count != b->layout.size()) {
-        size_t layouts = b->layout.size();
-        gs_bundle_destroy(b);
-        return fail(GS_ERR_RESOURCE_COUNT_MISMATCH, resource_group_count, layouts, 0,
-                    "resource count and bind group layout count mismatch: %u != %zu",
-                    resource_group_count, layouts);
-    }
-    b->managed = true;
-    b->groups.resize(b->layout.size());
-    for (uint32_t i = 0; i < resource_group_count; i++) {
-        gs_status st = gs_bundle_set_bind_group(b, i, resources[i], resource_counts[i]);
-        if (st != GS_OK) {
-            gs_bundle_destroy(b);
-            return st;
-        }
-    }
-    *out = b;
-    return GS_OK;
-}
-
-extern "C" void gs_bundle_destroy(gs_bundle *b) {
-    if (!b) return;
-    for (auto &g : b->groups) release_group(g);
-    if (b->module) {
-        (void)hipSetDevice(b->dev->ordinal);
-        (void)hipModuleUnload(b->module);
-    }
-    delete b;
-}
-
-extern "C" gs_status gs_bundle_create_from_source(gs_device *dev, const gs_bundle_source_desc *desc,
-                                                  gs_bundle **out) {
-    if (!dev || !desc || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    // same order of checks as ComputeBundleBuilder::build (compute_bundle.rs:505-519)
-    if (desc->bind_group_count == 0 || !desc->bindings_per_group)
-        return fail(GS_ERR_MISSING_BIND_GROUP_LAYOUT, 0, 0, 0, "missing bind group layout for compute bundle");
-    if (!desc->entry_point) return fail(GS_ERR_MISSING_ENTRY_POINT, 0, 0, 0, "missing entry point for compute bundle");
-    if (!desc->source) return fail(GS_ERR_MISSING_MAIN_SHADER, 0, 0, 0, "missing main shader for compute bundle");
-    if (!valid_cfg(desc->sh, desc->cov)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad config");
-    uint32_t limit = dev->limits.max_compute_workgroup_size_x <
-                             dev->limits.max_compute_invocations_per_workgroup
-                         ? dev->limits.max_compute_workgroup_size_x
-                         : dev->limits.max_compute_invocations_per_workgroup;
-    uint32_t wg = desc->workgroup_size ? desc->workgroup_size : limit;
-    if (wg > limit)
-        return fail(GS_ERR_WORKGROUP_SIZE_EXCEEDS_LIMIT, wg, limit, 0,
-                    "workgroup size exceeds device limit: %u > %u", wg, limit);
-    uint32_t total = 0;
-    for (uint32_t i = 0; i < desc->bind_group_count; i++) total += desc->bindings_per_group[i];
-    if (total > (uint32_t)gs::MAX_BINDINGS)
-        return fail(GS_ERR_INVALID_ARGUMENT, total, gs::MAX_BINDINGS, 0, "too many bindings");
-    GS_TRY(use_device(dev));
-
-    std::vector<std::string> opts;
-    opts.push_back(std::string("--offload-arch=") + dev->limits.arch_name);
-    opts.push_back("-std=c++17");
-    opts.push_back("-ffp-contract=off");
-    opts.push_back("-DGS_SH=" + std::to_string((int)desc->sh));
-    opts.push_back("-DGS_COV=" + std::to_string((int)desc->cov));
-    opts.push_back(std::string("-D") + k_feature_names[desc->sh] + "=1");
-    opts.push_back(std::string("-D") + k_feature_names[4 + desc->cov] + "=1");
-    opts.push_back("-Dworkgroup_size=" + std::to_string(wg));
-    for (uint32_t i = 0; i < desc->define_count; i++)
-        if (desc->defines && desc->defines[i]) opts.push_back(std::string("-D") + desc->defines[i] + "=1");
-    for (uint32_t i = 0; i < desc->constant_count; i++) {
-        if (!desc->constant_names || !desc->constant_names[i]) continue;
-        double v = desc->constant_values[i];
-        char buf[64];
-        if (v == (double)(long long)v) std::snprintf(buf, sizeof(buf), "%lld", (long long)v);
-        else std::snprintf(buf, sizeof(buf), "%.17g", v);
-        opts.push_back(std::string("-D") + desc->constant_names[i] + "=" + buf);
-    }
-    std::string entry = desc->entry_point;
-    opts.push_back("-Dmain=gs_entry_main");   // `main` cannot name a kernel in C++: always renamed
-    if (entry == "main") entry = "gs_entry_main";
-    std::vector<const char *> copts;
-    for (auto &o : opts) copts.push_back(o.c_str());
-
-    hiprtcProgram prog;
-    const char *hdr_src[1] = {k_kernel_lib_src};
-    const char *hdr_names[1] = {"wgpu_3dgs_core.h"};
-    hiprtcResult rr = hiprtcCreateProgram(&prog, desc->source, "main_shader.hip", 1, hdr_src, hdr_names);
-    if (rr != HIPRTC_SUCCESS)
-        return fail(GS_ERR_KERNEL_COMPILE, (uint64_t)rr, 0, 0, "hiprtcCreateProgram: %s", hiprtcGetErrorString(rr));
-    rr = hiprtcCompileProgram(prog, (int)copts.size(), copts.data());
-    if (rr != HIPRTC_SUCCESS) {
-        size_t n = 0;
-        (void)hiprtcGetProgramLogSize(prog, &n);
-        std::string log(n ? n : 1, '\0');
-        if (n) (void)hiprtcGetProgramLog(prog, &log[0]);
-        (void)hiprtcDestroyProgram(&prog);
-        // keep the first error lines
-        size_t e = log.find("error");
-        std::string shown = e == std::string::npos ? log : log.substr(e > 80 ? e - 80 : 0);
-        return fail(GS_ERR_KERNEL_COMPILE, (uint64_t)rr, 0, 0, "kernel compilation failed: %.200s", shown.c_str());
-    }
-    size_t code_size = 0;
-    (void)hiprtcGetCodeSize(prog, &code_size);
-    std::vector<char> code(code_size);
-    (void)hiprtcGetCode(prog, code.data());
-    (void)hiprtcDestroyProgram(&prog);
-
-    gs_bundle *b = new gs_bundle();
-    b->dev = dev;
-    b->label = desc->label ? desc->label : "";
-    b->kernel = GS_KERNEL_COUNT_;
-    b->sh = desc->sh;
-    b->cov = desc->cov;
-    b->workgroup_size = wg;
-    b->layout.assign(desc->bindings_per_group, desc->bindings_per_group + desc->bind_group_count);
-    b->managed = false;
-    b->has_additional_constant = false;
-    b->additional_constant = 0;
-    b->last_workgroups = 0;
-    b->from_source = true;
-    hipError_t he = hipModuleLoadData(&b->module, code.data());
-    if (he == hipSuccess) he = hipModuleGetFunction(&b->func, b->module, entry.c_str());
-    if (he != hipSuccess) {
-        gs_bundle_destroy(b);
-        return fail(GS_ERR_MISSING_ENTRY_POINT, (uint64_t)he, 0, 0, "entry point '%s' not found in the compiled module: %s",
-                    desc->entry_point, hipGetErrorString(he));
-    }
-    *out = b;
-    return GS_OK;
-}
-
-// bind groups for a bundle created without them (gs_bundle_create / _from_source): makes it managed
-extern "C" gs_status gs_bundle_attach_bind_groups(gs_bundle *b, gs_buffer *const *const *resources,
-                                                  const uint32_t *resource_counts,
-                                                  uint32_t resource_group_count) {
-    if (!b) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null bundle");
-    if (resource_group_count != b->layout.size())
-        return fail(GS_ERR_RESOURCE_COUNT_MISMATCH, resource_group_count, b->layout.size(), 0,
-                    "resource count and bind group layout count mismatch: %u != %zu",
-                    resource_group_count, b->layout.size());
-    b->managed = true;
-    b->groups.resize(b->layout.size());
-    for (uint32_t i = 0; i < resource_group_count; i++)
-        GS_TRY(gs_bundle_set_bind_group(b, i, resources[i], resource_counts[i]));
-    return GS_OK;
-}
-
-extern "C" uint32_t gs_bundle_workgroup_size(const gs_bundle *b) { return b ? b->workgroup_size : 0; }
-extern "C" const char *gs_bundle_label(const gs_bundle *b) {
-    return (b && !b->label.empty()) ? b->label.c_str() : nullptr;
-}
-extern "C" uint32_t gs_bundle_bind_group_layout_count(const gs_bundle *b) {
-    return b ? (uint32_t)b->layout.size() : 0;
-}
-extern "C" uint32_t gs_bundle_bind_group_count(const gs_bundle *b) {
-    return b ? (uint32_t)b->groups.size() : 0;
-}
-extern "C" uint32_t gs_bundle_last_workgroup_count(const gs_bundle *b) {
-    return b ? b->last_workgroups : 0;
-}
-
-// minimum byte size each binding must have so that the kernel cannot run out of bounds
-static gs_status validate_bindings(const gs_bundle *b, const gs::BundleArgs &a, uint32_t nbind) {
-    auto need = [&](uint32_t i, uint64_t bytes) -> gs_status {
-        if (i >= nbind || a.size[i] < bytes)
-            return fail(GS_ERR_INVALID_ARGUMENT, i, i < nbind ? a.size[i] : 0, bytes,
-                        "binding %u is smaller than the %llu bytes the kernel accesses", i,
-                        (unsigned long long)bytes);
-        return GS_OK;
-    };
-    uint64_t pod = (uint64_t)gs::pod_bytes(b->sh, b->cov);
-    switch (b->kernel) {
-    case GS_KERNEL_ARRAY_MAP_ADD:
-        GS_TRY(need(0, 0));
-        if (b->layout.size() > 1) GS_TRY(need(1, 4));
-        break;
-    case GS_KERNEL_TEST_GAUSSIAN:
-        GS_TRY(need(0, pod));
-        GS_TRY(need(1, 56 * 4));
-        break;
-    case GS_KERNEL_TEST_GAUSSIAN_TRANSFORM:
-        GS_TRY(need(0, 8));
-        GS_TRY(need(1, 16));
-        break;
-    case GS_KERNEL_TEST_MODEL_TRANSFORM:
-        GS_TRY(need(0, 48));
-        GS_TRY(need(1, 12));
-        GS_TRY(need(2, 44 * 4));
-        break;
-    case GS_KERNEL_UNPACK_SOA:
-        GS_TRY(need(0, 0));
-        GS_TRY(need(1, (a.size[0] / pod) * 55 * 4));
-        break;
-    default: break;
-    }
-    return GS_OK;
-}
-
-static gs_status dispatch_groups(gs_bundle *b, gs_stream *s, uint32_t count,
-                                 const std::vector<std::vector<gs_buffer *>> &groups) {
-    if (!s) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null stream");
-    if (groups.size() != b->layout.size())
-        return fail(GS_ERR_INVALID_ARGUMENT, groups.size(), b->layout.size(), 0,
-                    "dispatch needs %zu bind groups, got %zu", b->layout.size(), groups.size());
-    gs::BundleArgs a;
-    std::memset(&a, 0, sizeof(a));
-    uint32_t n = 0;
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        if (groups[gi].size() != b->layout[gi])
-            return fail(GS_ERR_INVALID_ARGUMENT, groups[gi].size(), b->layout[gi], 0,
-                        "bind group %zu is not set or has the wrong binding count", gi);
-        for (gs_buffer *buf : groups[gi]) {
-            a.ptr[n] = buf->ptr;
-            a.size[n] = buf->bytes;
-            n++;
-        }
-    }
-    a.reg_second_group = b->layout.size() > 1 ? 1u : 0u;
-    a.reg_has_constant = b->has_additional_constant ? 1u : 0u;
-    a.reg_constant = b->additional_constant;
-    if (!b->from_source) GS_TRY(validate_bindings(b, a, n));
-    GS_TRY(use_device(b->dev));
-    // compute_bundle.rs:131 — dispatch_workgroups(count.div_ceil(workgroup_size), 1, 1)
-    uint32_t wgs = count / b->workgroup_size + (count % b->workgroup_size != 0);
-    b->last_workgroups = wgs;
-    if (wgs == 0) return GS_OK;
-    if (b->from_source) {
-        struct { gs::BundleArgs a; uint32_t count; } params{a, count};
-        size_t psize = sizeof(params);
-        void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &params, HIP_LAUNCH_PARAM_BUFFER_SIZE, &psize,
-                          HIP_LAUNCH_PARAM_END};
-        GS_HIP(hipModuleLaunchKernel(b->func, wgs, 1, 1, b->workgroup_size, 1, 1, 0, s->s, nullptr, config));
-        return GS_OK;
-    }
-    bundle_kernel_fn fn = nullptr;
-    switch (b->kernel) {
-    case GS_KERNEL_ARRAY_MAP_ADD: fn = gs::k_array_map_add; break;
-    case GS_KERNEL_TEST_GAUSSIAN: fn = k_tbl_test_gaussian[b->sh][b->cov]; break;
-    case GS_KERNEL_TEST_GAUSSIAN_TRANSFORM: fn = gs::k_test_gaussian_transform; break;
-    case GS_KERNEL_TEST_MODEL_TRANSFORM: fn = gs::k_test_model_transform; break;
-    case GS_KERNEL_UNPACK_SOA: fn = k_tbl_unpack_soa[b->sh][b->cov]; break;
-    default: return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bad kernel");
-    }
-    hipLaunchKernelGGL(fn, dim3(wgs), dim3(b->workgroup_size), 0, s->s, a, count);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" gs_status gs_bundle_dispatch(gs_bundle *b, gs_stream *s, uint32_t count) {
-    if (!b) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null bundle");
-    if (!b->managed)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0,
-                    "bundle was created without bind groups: use gs_bundle_dispatch_with_bind_groups");
-    return dispatch_groups(b, s, count, b->groups);
-}
-
-extern "C" gs_status gs_bundle_dispatch_with_bind_groups(gs_bundle *b, gs_stream *s, uint32_t count,
-                                                         gs_buffer *const *const *groups,
-                                                         const uint32_t *group_counts,
-                                                         uint32_t group_count) {
-    if (!b || (group_count && (!groups || !group_counts)))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    std::vector<std::vector<gs_buffer *>> gv(group_count);
-    for (uint32_t i = 0; i < group_count; i++) {
-        for (uint32_t k = 0; k < group_counts[i]; k++) {
-            if (!groups[i][k]) return fail(GS_ERR_INVALID_ARGUMENT, i, k, 0, "null binding");
-            gv[i].push_back(groups[i][k]);
-        }
-    }
-    return dispatch_groups(b, s, count, gv);
-}
+using namespace gsh;
 
 // ------------------------------------------------------------------------------------------------
 // renderer
@@ -1573,19 +58,6 @@ extern "C" void gs_camera_look_at(const float eye[3], const float target[3], con
     out->height = height;
     out->background[0] = out->background[1] = out->background[2] = 0.0f;
 }
-
-// Gaussian selection: n bits in caller index order.  `generation` changes with every call that may
-// modify the bits (next_object_id: unique across selections), which is how a renderer knows its slot-ordered copy is stale.
-struct gs_selection {
-    gs_device *dev;
-    size_t n, nwords;
-    uint32_t *words;            // device, nwords (at least one word is allocated)
-    DevArray scratch;           // a plane of the same size for the select ops that scatter their bits (select_visible)
-    DevArray counter;           // gs_selection_count's device total
-    uint64_t generation;
-    uint32_t tail_mask() const { return (n & 31u) ? (1u << (n & 31u)) - 1u : 0xffffffffu; }
-    uint32_t grid() const { return nwords < 256u * 1024u ? (uint32_t)((nwords + 255u) / 256u) + 1u : 1024u; }
-};
 
 // stage indices of gs_frame_stats.stage_ms
 enum { ST_REPACK = 0, ST_PRE, ST_SCAN, ST_DSORT, ST_EXPAND, ST_TSORT, ST_RANGES, ST_BLEND, ST_FRAME, ST_COUNT };
@@ -1673,7 +145,7 @@ struct gs_renderer {
 
 // gs_stream_destroy: the end-of-frame event of every renderer whose last frame is on `st` is recorded now, and the
 // renderer remembers that the stream is gone (it must not be touched again: waits go through the event).
-static void renderers_leave_stream(gs_device *dev, hipStream_t st) {
+void gsh::renderers_leave_stream(gs_device *dev, hipStream_t st) {
     std::lock_guard<std::mutex> lock(dev->renderers_mu);
     for (gs_renderer *r : dev->renderers) {
         if (!r->have_frame || r->last_stream_gone || r->last_stream != st) continue;
@@ -1681,6 +153,23 @@ static void renderers_leave_stream(gs_device *dev, hipStream_t st) {
         r->last_stream_gone = true;
     }
     (void)hipGetLastError();
+}
+
+// gs_device_create: both digit widths of the sorts (256 and 512 counters per wave), the scatter's own access pattern
+bool gsh::probe_lds_atomic_order(hipStream_t st) {
+    bool ordered = false;
+    uint32_t *bad = nullptr;
+    if (hipMalloc((void **)&bad, 4) == hipSuccess) {
+        uint32_t h = 1;
+        if (hipMemset(bad, 0, 4) == hipSuccess) {
+            hipLaunchKernelGGL(gs::k_probe_lds_atomic_order<8>, dim3(512), dim3(gs::SORT_THREADS), 0, st, 8u, 0x3D650001u, bad);
+            hipLaunchKernelGGL(gs::k_probe_lds_atomic_order<9>, dim3(512), dim3(gs::SORT_THREADS), 0, st, 8u, 0x3D650002u, bad);
+            if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(&h, bad, 4, hipMemcpyDeviceToHost) == hipSuccess) ordered = (h == 0);
+        }
+        (void)hipFree(bad);
+    }
+    (void)hipGetLastError();
+    return ordered;
 }
 
 // host wait for the renderer's last frame: its stream, or — the stream was destroyed — its end-of-frame event
@@ -1691,7 +180,7 @@ static hipError_t sync_last_frame(gs_renderer *r) {
 }
 
 extern "C" gs_status gs_renderer_create(gs_device *dev, gs_renderer **out) {
-    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
+    if (!out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
     GS_TRY(use_device(dev));
     gs_renderer *r = new gs_renderer();
     r->dev = dev;
@@ -1713,7 +202,7 @@ extern "C" gs_status gs_renderer_create(gs_device *dev, gs_renderer **out) {
         if (r->host_counters) (void)hipHostFree(r->host_counters);
         if (r->results) (void)hipHostFree(r->results);
         delete r;
-        return fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "renderer allocation failed: %s", hipGetErrorString(e));
+        return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "renderer allocation failed: %s", hipGetErrorString(e));
     }
     std::memset(r->results, 0, 2 * sizeof(gs::FrameResult));
     r->pair_capacity = 0;
@@ -1770,7 +259,7 @@ extern "C" void gs_renderer_destroy(gs_renderer *r) {
 }
 
 extern "C" gs_status gs_renderer_set_timing(gs_renderer *r, int32_t enabled) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
     GS_TRY(use_device(r->dev));
     if (enabled && !r->ev_valid) {
         for (auto &e : r->ev) GS_HIP(hipEventCreate(&e));
@@ -1781,8 +270,8 @@ extern "C" gs_status gs_renderer_set_timing(gs_renderer *r, int32_t enabled) {
 }
 
 extern "C" gs_status gs_renderer_set_frame_flags_target(gs_renderer *r, uint32_t *device_word) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
-    if ((uintptr_t)device_word & 3u) return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)device_word, 4, 0, "unaligned flags word");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if ((uintptr_t)device_word & 3u) return gs_fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)device_word, 4, 0, "unaligned flags word");
     r->flags_target = device_word;
     return GS_OK;
 }
@@ -1805,7 +294,7 @@ static gs_status collect_timing(gs_renderer *r) {
 }
 
 extern "C" gs_status gs_renderer_reset_stats(gs_renderer *r) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
     GS_TRY(use_device(r->dev));
     GS_TRY(collect_timing(r));
     for (int i = 0; i < ST_COUNT; i++) r->stage_ms[i] = 0.0;
@@ -1817,7 +306,7 @@ extern "C" gs_status gs_renderer_reset_stats(gs_renderer *r) {
 static const gs::FrameResult &last_result(const gs_renderer *r) { return r->results[r->gen & 1u]; }
 
 extern "C" gs_status gs_renderer_wait_frame(gs_renderer *r, gs_frame_result *out) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
     GS_TRY(use_device(r->dev));
     if (out) std::memset(out, 0, sizeof(*out));
     if (!r->have_frame) return GS_OK;       // no frame yet
@@ -1832,10 +321,10 @@ extern "C" gs_status gs_renderer_wait_frame(gs_renderer *r, gs_frame_result *out
         out->launches = r->launches;
     }
     if (fr.gen != r->gen)
-        return fail(GS_ERR_HIP, fr.gen, r->gen, 0, "the frame did not complete (result generation %u, expected %u)",
+        return gs_fail(GS_ERR_HIP, fr.gen, r->gen, 0, "the frame did not complete (result generation %u, expected %u)",
                     fr.gen, r->gen);
     if (fr.pairs_total > 0xfffffff0ull)
-        return fail(GS_ERR_PAIR_OVERFLOW, r->n, 0, 0,
+        return gs_fail(GS_ERR_PAIR_OVERFLOW, r->n, 0, 0,
                     "the frame needs more than 2^32 (tile, Gaussian) pairs; pair indices are 32-bit");
     if (fr.flags & gs::FRAME_FLAG_RANK_FAULT) {
         // The device drops to the ballot-based rank, and THIS renderer's watchdog word is cleared whether or not it was
@@ -1843,7 +332,7 @@ extern "C" gs_status gs_renderer_wait_frame(gs_renderer *r, gs_frame_result *out
         // second one to report used to find the switch already off, keep its word set, and flag every later frame.
         r->dev->lds_atomic_ordered.store(false);
         (void)hipMemset(&((gs::FrameState *)r->state.ptr)->rank_fault, 0, sizeof(uint32_t));   // the stream is idle here
-        return fail(GS_ERR_RANK_ORDER, 0, 0, 0,
+        return gs_fail(GS_ERR_RANK_ORDER, 0, 0, 0,
                     "the LDS-atomic rank of the radix sort returned an out-of-order value in this frame: its blend order "
                     "may be wrong; the device has been switched to the ballot-based rank: render again");
     }
@@ -1854,17 +343,17 @@ extern "C" gs_status gs_renderer_wait_frame(gs_renderer *r, gs_frame_result *out
             const uint64_t bound = r->frame_capacity, d1 = fr.pairs_round1;
             const uint64_t d2 = fr.pairs_total > d1 ? fr.pairs_total - d1 : 0;
             if (d1 > bound)
-                return fail(GS_ERR_PAIR_CAPACITY, d1, bound, 0,
+                return gs_fail(GS_ERR_PAIR_CAPACITY, d1, bound, 0,
                             "round 1 of the two-round frame produced %llu (tile, Gaussian) pairs, a round's bound was %llu: the "
                             "frame was skipped (the image was not written); render again (the next frame has a larger bound)",
                             (unsigned long long)d1, (unsigned long long)bound);
-            return fail(GS_ERR_PAIR_CAPACITY, d2, bound, 0,
+            return gs_fail(GS_ERR_PAIR_CAPACITY, d2, bound, 0,
                         "round 2 of the two-round frame produced %llu (tile, Gaussian) pairs, a round's bound was %llu: the "
                         "frame was skipped (its band holds round 1's pixel state, not a frame); render again (the next frame "
                         "has a larger bound)",
                         (unsigned long long)d2, (unsigned long long)bound);
         }
-        return fail(GS_ERR_PAIR_CAPACITY, fr.pairs_total, r->pair_capacity, 0,
+        return gs_fail(GS_ERR_PAIR_CAPACITY, fr.pairs_total, r->pair_capacity, 0,
                     "the frame produced %llu (tile, Gaussian) pairs but the pair buffers hold %llu: the frame was "
                     "skipped (the image was not written); render again (the next frame grows the buffers)",
                     (unsigned long long)fr.pairs_total, (unsigned long long)r->pair_capacity);
@@ -1873,7 +362,7 @@ extern "C" gs_status gs_renderer_wait_frame(gs_renderer *r, gs_frame_result *out
 }
 
 extern "C" gs_status gs_renderer_stats(gs_renderer *r, gs_frame_stats *out) {
-    if (!r || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (!r || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     GS_TRY(use_device(r->dev));
     GS_HIP(sync_last_frame(r));
     GS_TRY(collect_timing(r));
@@ -1892,7 +381,7 @@ extern "C" gs_status gs_renderer_stats(gs_renderer *r, gs_frame_stats *out) {
 }
 
 extern "C" gs_status gs_renderer_sort_info(gs_renderer *r, gs_sort_info *out) {
-    if (!r || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (!r || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     GS_TRY(use_device(r->dev));
     std::memset(out, 0, sizeof(*out));
     out->bucket_capacity = gs::BKT_CAP;
@@ -1913,24 +402,24 @@ extern "C" gs_status gs_renderer_sort_info(gs_renderer *r, gs_sort_info *out) {
 }
 
 extern "C" gs_status gs_renderer_set_tile_masks(gs_renderer *r, int32_t mode) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
-    if (mode < -1 || mode > 1) return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(int64_t)mode, 0, 0, "tile mask modes are -1, 0 or 1");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (mode < -1 || mode > 1) return gs_fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(int64_t)mode, 0, 0, "tile mask modes are -1, 0 or 1");
     r->tile_masks_req = mode;
     return GS_OK;
 }
 
 extern "C" gs_status gs_renderer_set_rounds(gs_renderer *r, int32_t mode, uint32_t first_round) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
-    if (mode < -1 || mode > 1) return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(int64_t)mode, 0, 0, "round modes are -1, 0 or 1");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (mode < -1 || mode > 1) return gs_fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(int64_t)mode, 0, 0, "round modes are -1, 0 or 1");
     r->rounds_req = mode;
     r->round1_req = first_round;
     return GS_OK;
 }
 
 extern "C" gs_status gs_renderer_set_sort_mode(gs_renderer *r, int32_t depth_msd, int32_t tile_msd) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
     if (depth_msd < -1 || depth_msd > 1 || tile_msd < -1 || tile_msd > 1)
-        return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(int64_t)depth_msd, (uint64_t)(int64_t)tile_msd, 0, "sort modes are -1, 0 or 1");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(int64_t)depth_msd, (uint64_t)(int64_t)tile_msd, 0, "sort modes are -1, 0 or 1");
     r->depth_msd_req = depth_msd;
     r->tile_msd_req = tile_msd;
     return GS_OK;
@@ -2499,12 +988,24 @@ static gs_status run_sort_rb(const SortCtx &c, void *const keys[2], void *const 
 
 // host-known count (spatial order build, stand-alone sort)
 template <typename K>
-static gs_status sort_pairs_device(const gs_device *dev, void *const keys[2], void *const vals[2],
-                                   DevArray &ghist, DevArray &digit_totals, uint32_t count,
-                                   uint32_t end_bit, hipStream_t st, int &result_side,
-                                   uint32_t &passes_out) {
+gs_status gsh::sort_pairs_device(const gs_device *dev, void *const keys[2], void *const vals[2],
+                                 DevArray &ghist, DevArray &digit_totals, uint32_t count,
+                                 uint32_t end_bit, hipStream_t st, int &result_side,
+                                 uint32_t &passes_out) {
     return run_sort_rb<K, gs::RADIX_BITS>(standalone_sort_ctx(dev, st, ghist, digit_totals), keys, vals, gs::SortCount{count, nullptr}, end_bit,
                                           nullptr, result_side, passes_out);
+}
+// (the neighbour counts sort 64-bit keys from their own unit)
+template gs_status gsh::sort_pairs_device<uint64_t>(const gs_device *, void *const[2], void *const[2], DevArray &, DevArray &, uint32_t, uint32_t,
+                                                    hipStream_t, int &, uint32_t &);
+
+// the two kernels of this unit that other units launch too (gs_host.h)
+void gsh::scan_chunks_enqueue(hipStream_t st, const uint32_t *in, uint32_t *out, uint32_t *total, uint32_t n) {
+    gs::ScanJob job{in, out, total, n};
+    hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
+}
+void gsh::bbox_final_enqueue(hipStream_t st, const float *partial, uint32_t count, float *bbox) {
+    hipLaunchKernelGGL(gs::k_bbox_final, dim3(1), dim3(256), 0, st, partial, count, bbox);
 }
 
 // (Re)build the block-planar mirror on `st`.  A whole-buffer rebuild in spatial mode first computes
@@ -2526,8 +1027,7 @@ static gs_status build_spatial_order(gs_gaussians_buffer *g, hipStream_t st, siz
     if (rc == GS_OK) {
         hipLaunchKernelGGL(gs::k_bbox_partial, dim3(pgrid), dim3(256), 0, st, (const uint32_t *)g->buf->ptr,
                            pod_words, n, (float *)partial.ptr);
-        hipLaunchKernelGGL(gs::k_bbox_final, dim3(1), dim3(256), 0, st, (const float *)partial.ptr, pgrid,
-                           (float *)bbox.ptr);
+        bbox_final_enqueue(st, (const float *)partial.ptr, pgrid, (float *)bbox.ptr);
         hipLaunchKernelGGL(gs::k_morton_keys, dim3((n + 255u) / 256u), dim3(256), 0, st,
                            (const uint32_t *)g->buf->ptr, pod_words, n, (const float *)bbox.ptr,
                            (uint32_t *)keys[0].ptr, (uint32_t *)vals[0].ptr);
@@ -2550,12 +1050,12 @@ static gs_status build_spatial_order(gs_gaussians_buffer *g, hipStream_t st, siz
         if (g->inv) (void)hipFree(g->inv);
         g->inv = nullptr;
         hipError_t e = hipMalloc(&g->inv, (size_t)n * 4);
-        if (e != hipSuccess) rc = fail(GS_ERR_OUT_OF_MEMORY, (size_t)n * 4, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = gs_fail(GS_ERR_OUT_OF_MEMORY, (size_t)n * 4, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
         else
             hipLaunchKernelGGL(gs::k_invert_order, dim3((n + 255u) / 256u), dim3(256), 0, st,
                                (const uint32_t *)ob->ptr, n, (uint32_t *)g->inv);
     }
-    if (rc == GS_OK && hipGetLastError() != hipSuccess) rc = fail(GS_ERR_HIP, 0, 0, 0, "spatial order launch failed");
+    if (rc == GS_OK && hipGetLastError() != hipSuccess) rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "spatial order launch failed");
     // the scratch arrays may still be in use by the queued kernels: hipFree synchronises the device
     for (int i = 0; i < 2; i++) {
         dev_free(keys[i]);
@@ -2591,7 +1091,7 @@ static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
     }
     if (lo < hi) {
         // the records may have been edited on another stream (gs_gaussians_buffer_edit only enqueues)
-        if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
+        GS_TRY(wait_for_edits(g, st));
         const bool whole = lo == 0 && hi == len && !g->keep_order;
         if (whole) g->partial_since_order = 0;
         const bool want_order = g->spatial && len > 1;
@@ -2647,7 +1147,7 @@ static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
 }
 
 extern "C" gs_status gs_gaussians_buffer_set_spatial_order(gs_gaussians_buffer *g, int32_t enabled) {
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
+    if (!g) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
     if (g->spatial != (enabled != 0)) {
         g->spatial = enabled != 0;
         g->mark_all();
@@ -2661,10 +1161,10 @@ extern "C" int32_t gs_gaussians_buffer_spatial_order(const gs_gaussians_buffer *
 
 extern "C" gs_status gs_gaussians_buffer_download_order(gs_gaussians_buffer *g, gs_stream *s,
                                                         uint32_t *order_out, size_t count) {
-    if (!g || (count && !order_out)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (!g || (count && !order_out)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     size_t len = gs_gaussians_buffer_len(g);
     if (count != len)
-        return fail(GS_ERR_COUNT_MISMATCH, count, len, 0, "Gaussians count mismatch: %zu != %zu", count, len);
+        return gs_fail(GS_ERR_COUNT_MISMATCH, count, len, 0, "Gaussians count mismatch: %zu != %zu", count, len);
     GS_TRY(use_device(g->buf->dev));
     hipStream_t st = stream_of(g->buf->dev, s);
     GS_TRY(ensure_planar(g, st));
@@ -2674,7 +1174,7 @@ extern "C" gs_status gs_gaussians_buffer_download_order(gs_gaussians_buffer *g, 
     }
     GS_HIP(hipStreamSynchronize(st));
     hipError_t e = hipMemcpy(order_out, g->order->ptr, len * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
     return GS_OK;
 }
 
@@ -2944,7 +1444,7 @@ static gs_status stage_blend(Frame &F, uint32_t round) {
         {gs::k_blend_grouped<2, 2, true>, gs::k_blend_grouped<2, 4, true>, gs::k_blend_grouped<2, 8, true>}};
     // column of the grouped tables: 2 -> 8x8 blocks, 8 -> 4x4 blocks, anything else -> 8x4 blocks (an aux frame: also for 1)
     const int gcol = groups == 2 ? 0 : groups == 8 ? 2 : 1;
-    if (round != 0u && groups == 1) return fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
+    if (round != 0u && groups == 1) return gs_fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
     F.tile_keys.round = round;
     if (F.aux) {
         // the depth / pick planes ride in the grouped blend (G = 4 where the plain frame would take k_blend)
@@ -3037,7 +1537,7 @@ static gs_status stage_sizing(Frame &F) {
     const uint32_t d = r->host_counters[0];
     if (d == 0xffffffffu) {
         r->shape = FrameShape();
-        return fail(GS_ERR_PAIR_OVERFLOW, F.n, 0, 0,
+        return gs_fail(GS_ERR_PAIR_OVERFLOW, F.n, 0, 0,
                     "the frame needs more than 2^32 (tile, Gaussian) pairs; pair indices are 32-bit");
     }
     r->rounds_fb.full_pairs = d;              // (the visible count it belongs to comes with the frame's report)
@@ -3300,7 +1800,7 @@ static gs_status stage_pairs_round(Frame &F, uint32_t round, const uint32_t *ord
     const bool tile_msd = round == 0u && F.plan.tile_msd;      // (gsp::plan_tile_msd)
     r->tile_msd = tile_msd;
     if (tile_msd) {
-        if (F.nums.tile_bits > (uint32_t)gs::MSD_TOP_BITS + 6u) return fail(GS_ERR_INVALID_ARGUMENT, F.nums.tile_bits, 0, 0, "tile id bits");
+        if (F.nums.tile_bits > (uint32_t)gs::MSD_TOP_BITS + 6u) return gs_fail(GS_ERR_INVALID_ARGUMENT, F.nums.tile_bits, 0, 0, "tile id bits");
         GS_TRY((run_tile_msd_items<gs::SortCfg<uint16_t>::ITEMS>(F.sort, r, eo, tc, F.nums.tile_bits, F.num_tiles, F.zero,
                                                                   &F.state->tile_bucket_max, tpasses)));
         tside = 0;
@@ -3444,18 +1944,18 @@ static gs_status take_over_stream(gs_renderer *r, hipStream_t st) {
 static gs_status check_frame_args(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g, const gs_gaussian_transform_pod *gt,
                                   const gs_model_transform_pod *mt, const gs_camera *cam, float *rgba) {
     if (!r || !s || !g || !gt || !mt || !cam || !rgba)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     if (g->buf->dev != r->dev || s->dev != r->dev)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
     if (cam->width == 0 || cam->height == 0 || cam->width > 65535u * 16u || cam->height > 65535u * 16u)
-        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "bad image size");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "bad image size");
     if ((uintptr_t)rgba & 15u)
-        return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)rgba, 16, 0,
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)rgba, 16, 0,
                     "the RGBA frame must be 16-byte aligned (pixels are stored as float4)");
     if (gt->flags[0] > GS_DISPLAY_POINT)
-        return fail(GS_ERR_INVALID_ARGUMENT, gt->flags[0], 0, 0, "unknown GaussianDisplayMode %u", gt->flags[0]);
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, gt->flags[0], 0, 0, "unknown GaussianDisplayMode %u", gt->flags[0]);
     if (!(cam->near_plane >= 0.0f))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the near plane must be >= 0 (depth keys are the bits of a positive float)");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the near plane must be >= 0 (depth keys are the bits of a positive float)");
     return GS_OK;
 }
 
@@ -3479,16 +1979,16 @@ static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
     fc.tile_masks = F.plan.tile_masks ? 1u : 0u;
     r->tile_masks = F.plan.tile_masks;
     r->wt_pairs = fc.wt_pairs != 0u;
-    if (n64 > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, n64, 0, 0, "too many Gaussians");
+    if (n64 > 0xfffffff0ull) return gs_fail(GS_ERR_INVALID_ARGUMENT, n64, 0, 0, "too many Gaussians");
     const uint32_t n = F.n = (uint32_t)n64;
     F.nchunks = (n + gs::PP_CHUNK - 1) / gs::PP_CHUNK;
     F.num_tiles = fc.tiles_x * fc.tiles_y;
     // one 256-Gaussian expansion chunk may touch at most 256 * num_tiles pairs: keep that inside 32 bits
     if ((uint64_t)fc.tiles_x * fc.tiles_y > (1ull << 22))
-        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 2^22 tiles");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 2^22 tiles");
     // tile rects are packed as 16-bit tile coordinates
     if (fc.tiles_x > 0xffffu || fc.tiles_y > 0xffffu)
-        return fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 65535 tiles along one axis");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, cam->width, cam->height, 0, "more than 65535 tiles along one axis");
     F.nn = n ? n : 1;
     F.nc = F.nchunks ? F.nchunks : 1;
     F.nslots = F.nc * (size_t)gs::PP_CHUNK;
@@ -3586,17 +2086,17 @@ extern "C" gs_status gs_render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_
 // gs_aux_targets as the frame takes it: null when it names no plane
 static gs_status check_aux(const gs_aux_targets *&aux) {
     if (aux) {
-        if (aux->reserved != 0u) return fail(GS_ERR_INVALID_ARGUMENT, aux->reserved, 0, 0, "gs_aux_targets.reserved must be 0");
+        if (aux->reserved != 0u) return gs_fail(GS_ERR_INVALID_ARGUMENT, aux->reserved, 0, 0, "gs_aux_targets.reserved must be 0");
         if (!aux->depth && !aux->pick) {
             aux = nullptr;      // no planes: the plain frame, whatever the threshold says
         } else {
             // tcut = 1 - t in f32 must lie in (0, 1): a t below 2^-25 rounds it to 1, which no step can cross
             const float tcut = 1.0f - aux->pick_threshold;
             if (!(aux->pick_threshold > 0.0f && aux->pick_threshold < 1.0f) || !(tcut < 1.0f))
-                return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0,
+                return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0,
                             "the pick threshold must lie in (0, 1), and 1 - threshold must be below 1 in f32 (threshold > 2^-25)");
             if (((uintptr_t)aux->depth & 3u) || ((uintptr_t)aux->pick & 3u))
-                return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)aux->depth, (uint64_t)(uintptr_t)aux->pick, 4,
+                return gs_fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)aux->depth, (uint64_t)(uintptr_t)aux->pick, 4,
                             "the depth and pick planes must be 4-byte aligned");
         }
     }
@@ -3615,23 +2115,23 @@ extern "C" gs_status gs_render_frame_aux(gs_renderer *r, gs_stream *s, gs_gaussi
 static gs_status check_frame_selection(const gs_renderer *r, const gs_gaussians_buffer *g, const gs_frame_selection *&fs) {
     if (!fs) return GS_OK;
     if (fs->reserved[0] != 0u || fs->reserved[1] != 0u)
-        return fail(GS_ERR_INVALID_ARGUMENT, fs->reserved[0], fs->reserved[1], 0, "gs_frame_selection.reserved must be 0");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, fs->reserved[0], fs->reserved[1], 0, "gs_frame_selection.reserved must be 0");
     if (!fs->hide && !fs->tint) {
         fs = nullptr;           // no selection: the plain frame, whatever the tint says
         return GS_OK;
     }
-    if (!r || !g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (!r || !g) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     const size_t len = gs_gaussians_buffer_len(g);
     for (const gs_selection *sel : {fs->hide, fs->tint}) {
         if (!sel) continue;
-        if (sel->dev != r->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the selection belongs to another device");
+        if (sel->dev != r->dev) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the selection belongs to another device");
         if (sel->n != len)
-            return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
+            return gs_fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
     }
     if (fs->tint) {
         const float *t = fs->tint_rgba;
         if (!std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2]) || !(t[3] >= 0.0f && t[3] <= 1.0f))
-            return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the tint colour must be finite and its alpha in [0, 1]");
+            return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the tint colour must be finite and its alpha in [0, 1]");
     }
     return GS_OK;
 }
@@ -3651,7 +2151,7 @@ static gs_status download_sync(gs_renderer *r, void *dst, const void *src, size_
     GS_HIP(sync_last_frame(r));
     hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess)
-        return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+        return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
     return GS_OK;
 }
 
@@ -3706,8 +2206,8 @@ static gs_status download_slot_depths(gs_renderer *r, size_t slots, std::vector<
 // plus the compacted depth keys; the 48-byte gs_projected view of DESIGN.md §3.3 is assembled here.
 extern "C" gs_status gs_renderer_download_projected(gs_renderer *r, gs_projected *proj_out,
                                                     uint32_t *tiles_out, size_t n) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
-    if (n > r->n) return fail(GS_ERR_INVALID_ARGUMENT, n, r->n, 0, "n exceeds last frame");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (n > r->n) return gs_fail(GS_ERR_INVALID_ARGUMENT, n, r->n, 0, "n exceeds last frame");
     GS_TRY(use_device(r->dev));
     static_assert(sizeof(gs_projected) == 48, "record size");
     if (!n) return GS_OK;
@@ -3767,9 +2267,9 @@ extern "C" gs_status gs_renderer_download_projected(gs_renderer *r, gs_projected
 // rebuilt here as tile << 32 | depth bits of the pair's Gaussian.
 extern "C" gs_status gs_renderer_download_sorted(gs_renderer *r, uint64_t *keys_out, uint32_t *idx_out,
                                                  uint64_t capacity, uint64_t *pairs_out) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
     if (r->have_frame && r->two_round)
-        return fail(GS_ERR_INVALID_ARGUMENT, 2, 0, 0, "the last frame took two rounds: its pair arrays hold the second round only");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, 2, 0, 0, "the last frame took two rounds: its pair arrays hold the second round only");
     GS_TRY(use_device(r->dev));
     GS_HIP(sync_last_frame(r));
     uint64_t d = r->have_frame ? last_result(r).pairs_total : 0;
@@ -3800,197 +2300,27 @@ extern "C" gs_status gs_renderer_download_sorted(gs_renderer *r, uint64_t *keys_
 
 extern "C" gs_status gs_renderer_download_ranges(gs_renderer *r, uint32_t *ranges_out,
                                                  size_t num_tiles) {
-    if (!r || !ranges_out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (!r || !ranges_out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     if (num_tiles > (size_t)r->tiles_x * r->tiles_y)
-        return fail(GS_ERR_INVALID_ARGUMENT, num_tiles, 0, 0, "too many tiles");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, num_tiles, 0, 0, "too many tiles");
     if (r->have_frame && r->two_round)
-        return fail(GS_ERR_INVALID_ARGUMENT, 2, 0, 0, "the last frame took two rounds: its tile ranges are the second round's");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, 2, 0, 0, "the last frame took two rounds: its tile ranges are the second round's");
     GS_TRY(use_device(r->dev));
     return download_sync(r, ranges_out, r->zero_region.ptr, num_tiles * 8);
 }
 
 // ------------------------------------------------------------------------------------------------
-// stand-alone primitives
+// select what the last frame shows
 // ------------------------------------------------------------------------------------------------
-
-// ------------------------------------------------------------------------------------------------
-// Gaussian selections
-// ------------------------------------------------------------------------------------------------
-
-extern "C" gs_status gs_selection_create(gs_device *dev, size_t n, gs_selection **out) {
-    if (!dev || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (n > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, n, 0, 0, "too many Gaussians");
-    GS_TRY(use_device(dev));
-    gs_selection *sel = new gs_selection();
-    sel->dev = dev;
-    sel->n = n;
-    sel->nwords = (n + 31) / 32;
-    sel->words = nullptr;
-    sel->generation = next_object_id();
-    const size_t bytes = (sel->nwords ? sel->nwords : 1) * 4;
-    hipError_t e = hipMalloc((void **)&sel->words, bytes);
-    if (e == hipSuccess) e = hipMemset(sel->words, 0, bytes);
-    // (awaited: the null stream's fill is not ordered against the non-blocking stream of the upload that follows, and a
-    // late fill clears a mask that was uploaded and already read once)
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        if (sel->words) (void)hipFree(sel->words);
-        delete sel;
-        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "selection allocation failed: %s",
-                    hipGetErrorString(e));
-    }
-    *out = sel;
-    return GS_OK;
-}
-
-extern "C" void gs_selection_destroy(gs_selection *sel) {
-    if (!sel) return;
-    (void)hipSetDevice(sel->dev->ordinal);
-    (void)hipFree(sel->words);      // (synchronises the device: kernels that still read the mask finish first)
-    dev_free(sel->scratch);
-    dev_free(sel->counter);
-    delete sel;
-}
-
-extern "C" size_t gs_selection_len(const gs_selection *sel) { return sel ? sel->n : 0; }
-
-static gs_status check_selection(const gs_selection *sel, const gs_stream *s) {
-    if (!sel || !s) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (s->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    return use_device(sel->dev);
-}
-static gs_status check_select_op(gs_select_op op) {
-    if ((uint32_t)op > (uint32_t)GS_SEL_XOR) return fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)op, 0, 0, "unknown gs_select_op %u", (unsigned)op);
-    return GS_OK;
-}
-
-static gs_status selection_unary(gs_selection *sel, gs_stream *s, uint32_t mode) {
-    GS_TRY(check_selection(sel, s));
-    sel->generation = next_object_id();
-    if (!sel->nwords) return GS_OK;
-    hipLaunchKernelGGL(gs::k_sel_unary, dim3(sel->grid()), dim3(256), 0, s->s, sel->words, (uint32_t)sel->nwords, sel->tail_mask(), mode);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-extern "C" gs_status gs_selection_clear(gs_selection *sel, gs_stream *s) { return selection_unary(sel, s, 0u); }
-extern "C" gs_status gs_selection_fill(gs_selection *sel, gs_stream *s) { return selection_unary(sel, s, 1u); }
-extern "C" gs_status gs_selection_invert(gs_selection *sel, gs_stream *s) { return selection_unary(sel, s, 2u); }
-
-// dst = dst op src over whole words on `st` (src: another selection's words, or dst's scratch plane)
-static gs_status selection_combine_words(gs_selection *dst, hipStream_t st, gs_select_op op, const uint32_t *src) {
-    dst->generation = next_object_id();
-    if (!dst->nwords) return GS_OK;
-    hipLaunchKernelGGL(gs::k_sel_combine, dim3(dst->grid()), dim3(256), 0, st, dst->words, src, (uint32_t)dst->nwords, (uint32_t)op);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" gs_status gs_selection_combine(gs_selection *dst, gs_stream *s, gs_select_op op, const gs_selection *src) {
-    GS_TRY(check_selection(dst, s));
-    GS_TRY(check_select_op(op));
-    if (!src || src->dev != dst->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the source selection is null or belongs to another device");
-    if (src->n != dst->n) return fail(GS_ERR_INVALID_ARGUMENT, src->n, dst->n, 0, "selection lengths differ: %zu != %zu", src->n, dst->n);
-    return selection_combine_words(dst, s->s, op, src->words);
-}
-
-extern "C" gs_status gs_selection_upload(gs_selection *sel, gs_stream *s, const uint32_t *words, size_t nwords) {
-    GS_TRY(check_selection(sel, s));
-    if (nwords != sel->nwords || (nwords && !words))
-        return fail(GS_ERR_INVALID_ARGUMENT, nwords, sel->nwords, 0, "a selection of %zu bits takes %zu words", sel->n, sel->nwords);
-    sel->generation = next_object_id();
-    if (!nwords) return GS_OK;
-    GS_HIP(hipMemcpyAsync(sel->words, words, nwords * 4, hipMemcpyHostToDevice, s->s));
-    return selection_unary(sel, s, 3u);      // bits past n of the last word are dropped
-}
-
-extern "C" gs_status gs_selection_download(gs_selection *sel, gs_stream *s, uint32_t *words, size_t nwords) {
-    GS_TRY(check_selection(sel, s));
-    if (nwords != sel->nwords || (nwords && !words))
-        return fail(GS_ERR_INVALID_ARGUMENT, nwords, sel->nwords, 0, "a selection of %zu bits takes %zu words", sel->n, sel->nwords);
-    if (!nwords) return GS_OK;
-    GS_HIP(hipStreamSynchronize(s->s));
-    hipError_t e = hipMemcpy(words, sel->words, nwords * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    return GS_OK;
-}
-
-extern "C" gs_status gs_selection_count(gs_selection *sel, gs_stream *s, uint64_t *out) {
-    GS_TRY(check_selection(sel, s));
-    if (!out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
-    *out = 0;
-    if (!sel->nwords) return GS_OK;
-    GS_TRY(dev_reserve(sel->counter, 8));
-    GS_HIP(hipMemsetAsync(sel->counter.ptr, 0, 8, s->s));
-    hipLaunchKernelGGL(gs::k_sel_count, dim3(sel->grid()), dim3(256), 0, s->s, (const uint32_t *)sel->words, (uint32_t)sel->nwords,
-                       (unsigned long long *)sel->counter.ptr);
-    GS_HIP(hipGetLastError());
-    GS_HIP(hipStreamSynchronize(s->s));
-    hipError_t e = hipMemcpy(out, sel->counter.ptr, 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    return GS_OK;
-}
-
-// sphere / box: one thread per Gaussian of the AoS buffer, which is always current (the mirror is not needed)
-static gs_status select_shape(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_model_transform_pod *mt, bool box,
-                              const float *params, gs_select_op op) {
-    GS_TRY(check_selection(sel, s));
-    GS_TRY(check_select_op(op));
-    if (!g || !mt || !params) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (g->buf->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len != sel->n) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
-    gs::SelectShape sh;
-    gs::ModelTransform m;
-    std::memcpy(&m, mt, sizeof(m));
-    gs::model_transform_mat(m, sh.M);
-    std::memcpy(sh.P, params, 12 * sizeof(float));
-    sel->generation = next_object_id();
-    if (!len) return GS_OK;
-    const uint32_t n = (uint32_t)len, grid = (n + 255u) / 256u, pod_words = (uint32_t)(pod_stride(g) / 4);
-    if (box)
-        hipLaunchKernelGGL(gs::k_select_shape<true>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->words,
-                           (uint32_t)op);
-    else
-        hipLaunchKernelGGL(gs::k_select_shape<false>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->words,
-                           (uint32_t)op);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-extern "C" gs_status gs_select_sphere(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_model_transform_pod *mt,
-                                      const float center[3], float radius, gs_select_op op) {
-    if (!center) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (!(radius >= 0.0f)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the radius must be >= 0");
-    float p[12] = {center[0], center[1], center[2], radius * radius};
-    return select_shape(sel, s, g, mt, false, p, op);
-}
-
-extern "C" gs_status gs_select_box(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_model_transform_pod *mt,
-                                   const float world_to_box[12], gs_select_op op) {
-    return select_shape(sel, s, g, mt, true, world_to_box, op);
-}
-
-extern "C" gs_status gs_select_range(gs_selection *sel, gs_stream *s, size_t start, size_t count, gs_select_op op) {
-    GS_TRY(check_selection(sel, s));
-    GS_TRY(check_select_op(op));
-    if (start + count < start || start + count > sel->n)
-        return fail(GS_ERR_INVALID_ARGUMENT, start, count, sel->n, "the range [%zu, %zu + %zu) leaves a selection of %zu bits", start, start, count, sel->n);
-    sel->generation = next_object_id();
-    if (!sel->nwords) return GS_OK;
-    hipLaunchKernelGGL(gs::k_sel_range, dim3(sel->grid()), dim3(256), 0, s->s, sel->words, (uint32_t)sel->nwords, (uint32_t)start,
-                       (uint32_t)(start + count), (uint32_t)op);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
 
 extern "C" gs_status gs_renderer_select_visible(gs_renderer *r, gs_stream *s, gs_selection *sel, float x0, float y0, float x1, float y1,
                                                 const uint8_t *mask, gs_select_op op) {
-    if (!r) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
+    if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
     GS_TRY(check_selection(sel, s));
     GS_TRY(check_select_op(op));
-    if (sel->dev != r->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    if (!r->have_frame) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the renderer has no last frame");
-    if (sel->n != r->n) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, r->n, 0, "the selection has %zu bits, the last frame %zu Gaussians", sel->n, (size_t)r->n);
+    if (sel->dev != r->dev) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (!r->have_frame) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the renderer has no last frame");
+    if (sel->n != r->n) return gs_fail(GS_ERR_INVALID_ARGUMENT, sel->n, r->n, 0, "the selection has %zu bits, the last frame %zu Gaussians", sel->n, (size_t)r->n);
     hipStream_t st = s->s;
     // behind the last frame; from here on the renderer's newest work is on `st`, so its next frame — on whatever stream —
     // is ordered behind this call the way it is ordered behind a frame
@@ -4029,10 +2359,14 @@ extern "C" gs_status gs_renderer_select_visible(gs_renderer *r, gs_stream *s, gs
     return GS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// stand-alone primitives
+// ------------------------------------------------------------------------------------------------
+
 extern "C" gs_status gs_sort_pairs_u64(gs_device *dev, gs_stream *s, uint64_t *keys, uint32_t *values,
                                        uint64_t count, uint32_t end_bit) {
     if (!dev || (count && (!keys || !values)) || end_bit > 64 || count > 0xfffffff0ull)
-        return fail(GS_ERR_INVALID_ARGUMENT, count, end_bit, 0, "bad argument");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, count, end_bit, 0, "bad argument");
     GS_TRY(use_device(dev));
     if (!count) return GS_OK;
     hipStream_t st = stream_of(dev, s);
@@ -4046,7 +2380,7 @@ extern "C" gs_status gs_sort_pairs_u64(gs_device *dev, gs_stream *s, uint64_t *k
         hipError_t e = hipMemcpyAsync(k[0].ptr, keys, count * 8, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipMemcpyAsync(v[0].ptr, values, count * 4, hipMemcpyHostToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
     }
     int side = 0;
     uint32_t passes = 0;
@@ -4059,7 +2393,7 @@ extern "C" gs_status gs_sort_pairs_u64(gs_device *dev, gs_stream *s, uint64_t *k
         hipError_t e = hipMemcpyAsync(keys, k[side].ptr, count * 8, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(values, v[side].ptr, count * 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
     }
     for (int i = 0; i < 2; i++) {
         dev_free(k[i]);
@@ -4110,7 +2444,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_chunk_scan_write(const uint32_t 
 extern "C" gs_status gs_exclusive_scan_u32(gs_device *dev, gs_stream *s, const uint32_t *in,
                                            uint32_t *out, uint64_t count, uint64_t *total_out) {
     if (!dev || (count && (!in || !out)) || count > 0xfffffff0ull)
-        return fail(GS_ERR_INVALID_ARGUMENT, count, 0, 0, "bad argument");
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, count, 0, 0, "bad argument");
     GS_TRY(use_device(dev));
     if (total_out) *total_out = 0;
     if (!count) return GS_OK;
@@ -4129,8 +2463,7 @@ extern "C" gs_status gs_exclusive_scan_u32(gs_device *dev, gs_stream *s, const u
         if (e == hipSuccess) {
             hipLaunchKernelGGL(gs::k_chunk_sums, dim3(nchunks), dim3(gs::PP_THREADS), 0, st,
                                (const uint32_t *)din.ptr, n, (uint32_t *)sums.ptr);
-            gs::ScanJob job{(const uint32_t *)sums.ptr, (uint32_t *)offs.ptr, (uint32_t *)tot.ptr, nchunks};
-            hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
+            scan_chunks_enqueue(st, (const uint32_t *)sums.ptr, (uint32_t *)offs.ptr, (uint32_t *)tot.ptr, nchunks);
             hipLaunchKernelGGL(gs::k_chunk_scan_write, dim3(nchunks), dim3(gs::PP_THREADS), 0, st,
                                (const uint32_t *)din.ptr, (const uint32_t *)offs.ptr, n,
                                (uint32_t *)dout.ptr);
@@ -4139,819 +2472,9 @@ extern "C" gs_status gs_exclusive_scan_u32(gs_device *dev, gs_stream *s, const u
         if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, count * 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipMemcpyAsync(&total, tot.ptr, 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "scan failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "scan failed: %s", hipGetErrorString(e));
     }
     if (total_out) *total_out = total;
     for (DevArray *a : {&din, &dout, &sums, &offs, &tot}) dev_free(*a);
     return rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// edits of the selected Gaussians, extraction
-// ------------------------------------------------------------------------------------------------
-
-// the basis of DESIGN.md §3.2 for one band (l = 1, 2, 3: 3, 5, 7 functions), in double
-static void sh_band_basis(int l, const double d[3], double *Y) {
-    const double x = d[0], y = d[1], z = d[2], xx = x * x, yy = y * y, zz = z * z;
-    if (l == 1) {
-        const double C1 = 0.4886025119029199;
-        Y[0] = -C1 * y;
-        Y[1] = C1 * z;
-        Y[2] = -C1 * x;
-    } else if (l == 2) {
-        Y[0] = 1.0925484305920792 * x * y;
-        Y[1] = -1.0925484305920792 * y * z;
-        Y[2] = 0.31539156525252005 * (2.0 * zz - xx - yy);
-        Y[3] = -1.0925484305920792 * x * z;
-        Y[4] = 0.5462742152960396 * (xx - yy);
-    } else {
-        Y[0] = -0.5900435899266435 * y * (3.0 * xx - yy);
-        Y[1] = 2.890611442640554 * x * y * z;
-        Y[2] = -0.4570457994644658 * y * (4.0 * zz - xx - yy);
-        Y[3] = 0.3731763325901154 * z * (2.0 * zz - 3.0 * xx - 3.0 * yy);
-        Y[4] = -0.4570457994644658 * x * (4.0 * zz - xx - yy);
-        Y[5] = 1.445305721320277 * z * (xx - yy);
-        Y[6] = -0.5900435899266435 * x * (xx - 3.0 * yy);
-    }
-}
-
-// D of one band from its defining property: B D = B' over sample directions d_i, B[i][k] = Y_k(d_i),
-// B'[i][k] = Y_k(R^T d_i); solved as the normal equations (B^T B) D = B^T B' by Gaussian elimination with partial
-// pivoting.  The band's functions span a rotation-invariant space, so the system is consistent and D is exact up to
-// double rounding.
-static bool sh_band_rotation(int l, const double R[3][3], float *out) {
-    const int nb = 2 * l + 1, NS = 64;
-    double N[7][14] = {};      // [B^T B | B^T B']
-    for (int i = 0; i < NS; i++) {
-        // Fibonacci sphere: well spread, no symmetry that a band could hide in
-        const double z = 1.0 - (2.0 * i + 1.0) / NS, r = std::sqrt(1.0 - z * z), phi = i * 2.399963229728653;
-        const double d[3] = {r * std::cos(phi), r * std::sin(phi), z};
-        double dr[3];
-        for (int a = 0; a < 3; a++) dr[a] = (R[0][a] * d[0] + R[1][a] * d[1]) + R[2][a] * d[2];     // R^T d
-        double Y[7], Yr[7];
-        sh_band_basis(l, d, Y);
-        sh_band_basis(l, dr, Yr);
-        for (int k = 0; k < nb; k++)
-            for (int j = 0; j < nb; j++) {
-                N[k][j] += Y[k] * Y[j];
-                N[k][nb + j] += Y[k] * Yr[j];
-            }
-    }
-    for (int c = 0; c < nb; c++) {
-        int p = c;
-        for (int r = c + 1; r < nb; r++)
-            if (std::fabs(N[r][c]) > std::fabs(N[p][c])) p = r;
-        if (!(std::fabs(N[p][c]) > 1e-12)) return false;
-        if (p != c)
-            for (int j = 0; j < 2 * nb; j++) std::swap(N[p][j], N[c][j]);
-        for (int r = 0; r < nb; r++) {
-            if (r == c) continue;
-            const double f = N[r][c] / N[c][c];
-            for (int j = c; j < 2 * nb; j++) N[r][j] -= f * N[c][j];
-        }
-    }
-    // the entries are polynomials in R of magnitude <= 1; what the solve leaves below 1e-14 is its own rounding noise
-    // (the identity must give the identity)
-    for (int k = 0; k < nb; k++)
-        for (int j = 0; j < nb; j++) {
-            const double v = N[k][nb + j] / N[k][k];
-            out[k * nb + j] = std::fabs(v) < 1e-14 ? 0.0f : (float)v;
-        }
-    return true;
-}
-
-extern "C" gs_status gs_sh_rotation_matrices(const float rot_xyzw[4], float d1[9], float d2[25], float d3[49]) {
-    if (!rot_xyzw || !d1 || !d2 || !d3) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    double q[4], len2 = 0.0;
-    for (int k = 0; k < 4; k++) {
-        q[k] = (double)rot_xyzw[k];
-        len2 += q[k] * q[k];
-    }
-    if (!std::isfinite(len2) || !(len2 > 0.0)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the rotation must be finite and nonzero");
-    const double inv = 1.0 / std::sqrt(len2);
-    const double x = q[0] * inv, y = q[1] * inv, z = q[2] * inv, w = q[3] * inv;
-    const double R[3][3] = {{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)},
-                            {2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x)},
-                            {2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)}};
-    if (!sh_band_rotation(1, R, d1) || !sh_band_rotation(2, R, d2) || !sh_band_rotation(3, R, d3))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the rotation is degenerate");
-    return GS_OK;
-}
-
-static bool all_finite(const float *v, int n) {
-    for (int k = 0; k < n; k++)
-        if (!std::isfinite(v[k])) return false;
-    return true;
-}
-
-// the selection argument of an edit / extraction: NULL (all), or n bits on the buffer's device
-static gs_status check_buffer_selection(const gs_gaussians_buffer *g, const gs_stream *s, const gs_selection *sel) {
-    if (s && s->dev != g->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    if (!sel) return GS_OK;
-    if (sel->dev != g->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (sel->n != len) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
-    return GS_OK;
-}
-
-typedef void (*edit_fn)(uint4 *, uint32_t, const uint32_t *, gs::EditArgs);
-static edit_fn k_tbl_edit[4][3] = GS_CFG_TABLE(gs::k_edit);
-
-extern "C" gs_status gs_gaussians_buffer_edit(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, const gs_edit *e) {
-    if (!g || !e) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    const uint32_t known = GS_EDIT_TRANSFORM | GS_EDIT_ROTATE_SH | GS_EDIT_COLOR | GS_EDIT_OPACITY;
-    if (e->flags & ~known) return fail(GS_ERR_INVALID_ARGUMENT, e->flags, 0, 0, "unknown gs_edit flags 0x%x", (unsigned)e->flags);
-    for (uint32_t r : e->reserved)
-        if (r) return fail(GS_ERR_INVALID_ARGUMENT, r, 0, 0, "gs_edit.reserved must be 0");
-    if ((e->flags & GS_EDIT_ROTATE_SH) && !(e->flags & GS_EDIT_TRANSFORM))
-        return fail(GS_ERR_INVALID_ARGUMENT, e->flags, 0, 0, "GS_EDIT_ROTATE_SH goes with GS_EDIT_TRANSFORM");
-    gs::EditArgs a{};
-    a.flags = e->flags;
-    if (e->flags & GS_EDIT_TRANSFORM) {
-        const gs_model_transform_pod &t = e->transform;
-        if (!all_finite(t.pos, 3) || !all_finite(t.rot, 4) || !all_finite(t.scale, 3))
-            return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the transform of an edit must be finite");
-        if (!(t.scale[0] > 0.0f) || t.scale[1] != t.scale[0] || t.scale[2] != t.scale[0])
-            return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the scale of an edit must be uniform and positive");
-        gs::ModelTransform m;
-        std::memcpy(&m, &t, sizeof(m));
-        gs::model_transform_mat(m, a.M);
-        gs::model_scale_rot_mat(m, a.A);
-        std::memcpy(a.q, t.rot, sizeof(a.q));
-        a.s = t.scale[0];
-        if (e->flags & GS_EDIT_ROTATE_SH) GS_TRY(gs_sh_rotation_matrices(t.rot, a.D1, a.D2, a.D3));
-    }
-    if (e->flags & GS_EDIT_COLOR) {
-        if (!all_finite(e->color, 12)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the colour matrix of an edit must be finite");
-        std::memcpy(a.C, e->color, sizeof(a.C));
-    }
-    if (e->flags & GS_EDIT_OPACITY) {
-        if (!all_finite(e->opacity, 2)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the opacity terms of an edit must be finite");
-        std::memcpy(a.o, e->opacity, sizeof(a.o));
-    }
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    if (g->sh == GS_SH_NONE) a.flags &= ~(uint32_t)GS_EDIT_ROTATE_SH;
-    if (!a.flags || !len) return GS_OK;
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // a mirror rebuild in flight on another stream still reads the records
-    if (g->mirror_ready && st != g->mirror_stream) GS_HIP(hipStreamWaitEvent(st, g->mirror_ready, 0));
-    const uint32_t n = (uint32_t)len;
-    hipLaunchKernelGGL(k_tbl_edit[g->sh][g->cov], dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, n,
-                       sel ? (const uint32_t *)sel->words : nullptr, a);
-    GS_HIP(hipGetLastError());
-    if (!g->edit_done) GS_HIP(hipEventCreateWithFlags(&g->edit_done, hipEventDisableTiming));
-    GS_HIP(hipEventRecord(g->edit_done, st));
-    g->edit_stream = st;
-    // The host does not know which Gaussians the selection names: the whole mirror is stale.  A transform moves them,
-    // so the next frame sorts the spatial order again, exactly as after an upload of the edited records; a colour /
-    // opacity edit keeps every position, and with it the order (only the repack and the block bounds run again).
-    if (a.flags & GS_EDIT_TRANSFORM) {
-        g->mark_all();
-    } else if (!(g->dirty_lo == 0 && g->dirty_hi >= len)) {
-        g->dirty_lo = 0;
-        g->dirty_hi = len;
-        g->keep_order = true;
-    }
-    return GS_OK;
-}
-
-// A buffer of `len` > 0 records for a copy that writes every byte of it: allocated WITHOUT the zero fill of
-// gs_buffer_create: that hipMemset runs on the null stream, which the copy's stream is not ordered behind, and would race
-// with the copy.
-static gs_status gaussians_buffer_create_unfilled(gs_device *dev, int sh, int cov, size_t len, gs_gaussians_buffer **out) {
-    void *p = nullptr;
-    const size_t bytes = len * (size_t)gs::pod_bytes(sh, cov);
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, bytes, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-    gs_buffer *b = new gs_buffer();
-    b->dev = dev;
-    b->ptr = p;
-    b->bytes = bytes;
-    b->owned = true;
-    b->refs.store(1);
-    gs_status rc = gs_gaussians_buffer_from_buffer(b, (gs_sh_config)sh, (gs_cov3d_config)cov, out);
-    gs_buffer_release(b);
-    return rc;
-}
-
-extern "C" gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel,
-                                                               int32_t invert, gs_gaussians_buffer **out, uint64_t *count_out) {
-    if (!src || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    *out = nullptr;
-    if (count_out) *count_out = 0;
-    GS_TRY(check_buffer_selection(src, s, sel));
-    const size_t len = gs_gaussians_buffer_len(src);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    gs_device *dev = src->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // an edit enqueued on another stream still writes the records
-    if (src->edit_done && st != src->edit_stream) GS_HIP(hipStreamWaitEvent(st, src->edit_done, 0));
-    const uint32_t n = (uint32_t)len, inv = invert ? 1u : 0u;
-    const uint32_t nblocks = (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK, nc = (uint32_t)(pod_stride(src) / 16);
-    const uint32_t *words = sel ? (const uint32_t *)sel->words : nullptr;
-    DevArray counts, offsets, total_dev;
-    uint32_t total = 0;
-    gs_status rc = GS_OK;
-    if (n) {
-        rc = dev_reserve(counts, (size_t)nblocks * 4);
-        if (rc == GS_OK) rc = dev_reserve(offsets, (size_t)nblocks * 4);
-        if (rc == GS_OK) rc = dev_reserve(total_dev, 16);
-        if (rc == GS_OK) {
-            hipLaunchKernelGGL(gs::k_extract_block_counts, dim3((nblocks * 32u + 255u) / 256u), dim3(256), 0, st, words, n, inv, nblocks,
-                               (uint32_t *)counts.ptr);
-            gs::ScanJob job{(const uint32_t *)counts.ptr, (uint32_t *)offsets.ptr, (uint32_t *)total_dev.ptr, nblocks};
-            hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
-            hipError_t e = hipGetLastError();
-            // sizing the new buffer needs the total on the host
-            if (e == hipSuccess) e = hipMemcpyAsync(&total, total_dev.ptr, 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
-            else if (total > n) rc = fail(GS_ERR_HIP, total, n, 0, "selection scan returned %u of %u Gaussians", total, n);
-        }
-    }
-    gs_gaussians_buffer *dst = nullptr;
-    if (rc == GS_OK && total) {
-        rc = gaussians_buffer_create_unfilled(dev, src->sh, src->cov, total, &dst);
-    } else if (rc == GS_OK) {
-        rc = gs_gaussians_buffer_create(dev, (gs_sh_config)src->sh, (gs_cov3d_config)src->cov, nullptr, 0, &dst);
-    }
-    if (rc == GS_OK && total) {
-        hipLaunchKernelGGL(gs::k_extract_copy, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)src->buf->ptr,
-                           (uint4 *)dst->buf->ptr, words, n, inv, (const uint32_t *)offsets.ptr, nc, total);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);      // `offsets` is freed below; the call is blocking anyway
-        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "extraction failed: %s", hipGetErrorString(e));
-    }
-    for (DevArray *a : {&counts, &offsets, &total_dev}) dev_free(*a);
-    if (rc != GS_OK) {
-        if (dst) gs_gaussians_buffer_destroy(dst);
-        return rc;
-    }
-    dst->spatial = src->spatial;
-    *out = dst;
-    if (count_out) *count_out = total;
-    return GS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// snapshots of the selected records, concatenation
-// ------------------------------------------------------------------------------------------------
-
-// The records of one selection of one buffer, with what restoring them needs: its own copy of the mask and the first
-// snapshot rank of every 1024-block (the exclusive scan of the per-block counts).
-struct gs_snapshot {
-    gs_device *dev;
-    int sh, cov;
-    size_t n, nwords, nblocks;
-    uint64_t count;
-    uint32_t *meta;          // device: nwords mask words, nblocks offsets, the scan's total (one allocation)
-    size_t meta_bytes;
-    void *records;           // device: count records; null while count == 0
-    const uint32_t *words() const { return meta; }
-    uint32_t *offsets() const { return meta + nwords; }
-    uint32_t *total() const { return meta + nwords + nblocks; }
-};
-
-extern "C" void gs_snapshot_destroy(gs_snapshot *snap) {
-    if (!snap) return;
-    (void)hipSetDevice(snap->dev->ordinal);
-    if (snap->records) (void)hipFree(snap->records);      // (synchronises the device: a restore in flight finishes first)
-    if (snap->meta) (void)hipFree(snap->meta);
-    delete snap;
-}
-
-extern "C" size_t gs_snapshot_len(const gs_snapshot *snap) { return snap ? snap->n : 0; }
-extern "C" uint64_t gs_snapshot_count(const gs_snapshot *snap) { return snap ? snap->count : 0; }
-extern "C" size_t gs_snapshot_bytes(const gs_snapshot *snap) {
-    return snap ? (size_t)snap->count * (size_t)gs::pod_bytes(snap->sh, snap->cov) + snap->meta_bytes : 0;
-}
-
-extern "C" gs_status gs_gaussians_buffer_snapshot(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, gs_snapshot **out) {
-    if (out) *out = nullptr;
-    if (!g || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // an edit enqueued on another stream still writes the records
-    if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
-    gs_snapshot *snap = new gs_snapshot();
-    snap->dev = dev;
-    snap->sh = g->sh;
-    snap->cov = g->cov;
-    snap->n = len;
-    snap->nwords = (len + 31) / 32;
-    snap->nblocks = (len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK;
-    snap->count = 0;
-    snap->records = nullptr;
-    snap->meta_bytes = (snap->nwords + snap->nblocks + 1) * 4;
-    hipError_t e = hipMalloc((void **)&snap->meta, snap->meta_bytes);
-    if (e != hipSuccess) {
-        delete snap;
-        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "snapshot allocation failed: %s",
-                    hipGetErrorString(e));
-    }
-    const uint32_t n = (uint32_t)len, nwords = (uint32_t)snap->nwords, nblocks = (uint32_t)snap->nblocks;
-    const uint32_t nc = (uint32_t)(pod_stride(g) / 16);
-    uint32_t total = 0;
-    gs_status rc = GS_OK;
-    if (n) {
-        // the mask is copied first and everything below reads the copy: the snapshot does not depend on `sel` afterwards
-        hipLaunchKernelGGL(gs::k_snapshot_mask, dim3((nwords + 255u) / 256u), dim3(256), 0, st, snap->meta,
-                           sel ? (const uint32_t *)sel->words : nullptr, nwords, n);
-        // the per-block counts land where their exclusive scan goes (k_scan_chunks reads a value before it writes its slot)
-        hipLaunchKernelGGL(gs::k_extract_block_counts, dim3((nblocks * 32u + 255u) / 256u), dim3(256), 0, st, snap->words(), n, 0u, nblocks,
-                           snap->offsets());
-        gs::ScanJob job{snap->offsets(), snap->offsets(), snap->total(), nblocks};
-        hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
-        e = hipGetLastError();
-        // sizing the records needs the count on the host
-        if (e == hipSuccess) e = hipMemcpyAsync(&total, snap->total(), 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
-        else if (total > n) rc = fail(GS_ERR_HIP, total, n, 0, "selection scan returned %u of %u Gaussians", total, n);
-    }
-    if (rc == GS_OK && total) {
-        const size_t bytes = (size_t)total * pod_stride(g);
-        e = hipMalloc(&snap->records, bytes);
-        if (e != hipSuccess) {
-            snap->records = nullptr;
-            rc = fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, bytes, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-        } else {
-            hipLaunchKernelGGL(gs::k_extract_copy, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)g->buf->ptr,
-                               (uint4 *)snap->records, snap->words(), n, 0u, (const uint32_t *)snap->offsets(), nc, total);
-            e = hipGetLastError();
-            // the call is blocking anyway; a restore on any stream may follow at once
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "snapshot failed: %s", hipGetErrorString(e));
-        }
-    }
-    if (rc != GS_OK) {
-        gs_snapshot_destroy(snap);
-        return rc;
-    }
-    snap->count = total;
-    *out = snap;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_snapshot_selection(const gs_snapshot *snap, gs_stream *s, gs_selection *sel, gs_select_op op) {
-    if (!snap) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(check_selection(sel, s));
-    GS_TRY(check_select_op(op));
-    if (snap->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    if (snap->n != sel->n) return fail(GS_ERR_INVALID_ARGUMENT, snap->n, sel->n, 0, "the snapshot covers %zu Gaussians, the selection has %zu bits", snap->n, sel->n);
-    return selection_combine_words(sel, s->s, op, snap->words());
-}
-
-extern "C" gs_status gs_gaussians_buffer_restore(gs_gaussians_buffer *g, gs_stream *s, gs_snapshot *snap, int32_t exchange) {
-    if (!g || !snap) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    gs_device *dev = g->buf->dev;
-    if (snap->dev != dev || (s && s->dev != dev)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    if (snap->sh != g->sh || snap->cov != g->cov)
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the snapshot was taken from a buffer of another layout");
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (snap->n != len) return fail(GS_ERR_INVALID_ARGUMENT, snap->n, len, 0, "the snapshot covers %zu Gaussians, the buffer has %zu", snap->n, len);
-    if (!snap->count) return GS_OK;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // a mirror rebuild in flight on another stream still reads the records; an earlier edit or restore on another stream
-    // still writes them
-    if (g->mirror_ready && st != g->mirror_stream) GS_HIP(hipStreamWaitEvent(st, g->mirror_ready, 0));
-    if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
-    const uint32_t n = (uint32_t)len, nc = (uint32_t)(pod_stride(g) / 16), count = (uint32_t)snap->count;
-    if (exchange)
-        hipLaunchKernelGGL(gs::k_restore<true>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records,
-                           snap->words(), n, (const uint32_t *)snap->offsets(), nc, count);
-    else
-        hipLaunchKernelGGL(gs::k_restore<false>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records,
-                           snap->words(), n, (const uint32_t *)snap->offsets(), nc, count);
-    GS_HIP(hipGetLastError());
-    if (!g->edit_done) GS_HIP(hipEventCreateWithFlags(&g->edit_done, hipEventDisableTiming));
-    GS_HIP(hipEventRecord(g->edit_done, st));
-    g->edit_stream = st;
-    // the host does not know whether the restored records moved: the whole mirror is stale, as after a TRANSFORM edit
-    g->mark_all();
-    return GS_OK;
-}
-
-extern "C" gs_status gs_gaussians_buffer_create_concat(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
-                                                       uint32_t count, gs_gaussians_buffer **out, uint64_t *counts_out) {
-    if (out) *out = nullptr;
-    if (!srcs || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (count < 1u || count > 64u) return fail(GS_ERR_INVALID_ARGUMENT, count, 0, 0, "a concatenation takes 1 to 64 sources, not %u", (unsigned)count);
-    if (counts_out) std::memset(counts_out, 0, (size_t)count * sizeof(uint64_t));
-    size_t nblocks_all = 0;
-    for (uint32_t i = 0; i < count; i++) {
-        const gs_gaussians_buffer *g = srcs[i];
-        if (!g) return fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "source %u is null", (unsigned)i);
-        if (g->buf->dev != srcs[0]->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "objects belong to different devices");
-        if (g->sh != srcs[0]->sh || g->cov != srcs[0]->cov)
-            return fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "source %u has another layout than source 0", (unsigned)i);
-        GS_TRY(check_buffer_selection(g, s, sels ? sels[i] : nullptr));
-        const size_t len = gs_gaussians_buffer_len(g);
-        if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-        nblocks_all += (len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK;
-    }
-    gs_device *dev = srcs[0]->buf->dev;
-    const int sh = srcs[0]->sh, cov = srcs[0]->cov;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // one array for all sources: the per-block offsets of source i from block0[i] on, then one total per source
-    uint32_t *scan = nullptr;
-    hipError_t e = hipMalloc((void **)&scan, (nblocks_all + 64) * 4);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-    uint32_t *totals_dev = scan + nblocks_all;
-    uint32_t totals[64] = {};
-    size_t block0[64];
-    e = hipMemsetAsync(totals_dev, 0, 64 * 4, st);
-    size_t b0 = 0;
-    for (uint32_t i = 0; i < count && e == hipSuccess; i++) {
-        gs_gaussians_buffer *g = srcs[i];
-        const uint32_t n = (uint32_t)gs_gaussians_buffer_len(g), nblocks = (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
-        block0[i] = b0;
-        b0 += nblocks;
-        if (!n) continue;
-        // an edit enqueued on another stream still writes the records
-        if (g->edit_done && st != g->edit_stream) e = hipStreamWaitEvent(st, g->edit_done, 0);
-        if (e != hipSuccess) break;
-        const uint32_t *words = sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr;
-        uint32_t *offsets = scan + block0[i];
-        hipLaunchKernelGGL(gs::k_extract_block_counts, dim3((nblocks * 32u + 255u) / 256u), dim3(256), 0, st, words, n, 0u, nblocks, offsets);
-        gs::ScanJob job{offsets, offsets, totals_dev + i, nblocks};       // in place, as in the snapshot
-        hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, st, job, job);
-        e = hipGetLastError();
-    }
-    // sizing the new buffer needs the totals on the host: the one round trip of the call
-    if (e == hipSuccess) e = hipMemcpyAsync(totals, totals_dev, (size_t)count * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    gs_status rc = GS_OK;
-    uint64_t total = 0;
-    if (e != hipSuccess) rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
-    for (uint32_t i = 0; i < count && rc == GS_OK; i++) {
-        const size_t len = gs_gaussians_buffer_len(srcs[i]);
-        if (totals[i] > len) rc = fail(GS_ERR_HIP, totals[i], len, 0, "selection scan returned %u of %zu Gaussians", totals[i], len);
-        total += totals[i];
-    }
-    if (rc == GS_OK && total > 0xfffffff0ull)
-        rc = fail(GS_ERR_INVALID_ARGUMENT, total, 0, 0, "the concatenation would hold %llu Gaussians", (unsigned long long)total);
-    gs_gaussians_buffer *dst = nullptr;
-    if (rc == GS_OK && total) rc = gaussians_buffer_create_unfilled(dev, sh, cov, (size_t)total, &dst);
-    else if (rc == GS_OK) rc = gs_gaussians_buffer_create(dev, (gs_sh_config)sh, (gs_cov3d_config)cov, nullptr, 0, &dst);
-    if (rc == GS_OK && total) {
-        const uint32_t nc = (uint32_t)(pod_stride(dst) / 16);
-        uint64_t first = 0;      // where the part of source i starts in the new buffer
-        for (uint32_t i = 0; i < count; i++) {
-            if (!totals[i]) continue;
-            const uint32_t n = (uint32_t)gs_gaussians_buffer_len(srcs[i]);
-            const uint32_t *words = sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr;
-            // k_extract_copy stays inside `total` records from its destination pointer: the part of this source
-            hipLaunchKernelGGL(gs::k_extract_copy, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)srcs[i]->buf->ptr,
-                               (uint4 *)dst->buf->ptr + first * nc, words, n, 0u, (const uint32_t *)(scan + block0[i]), nc, totals[i]);
-            first += totals[i];
-        }
-        // The copies are only enqueued: the call has blocked once, for the totals.  The new buffer is ordered like an edited
-        // one (frames, snapshots and extractions on other streams wait for the copies) and keeps the offsets they read.
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&dst->edit_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventRecord(dst->edit_done, st);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            rc = fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "concatenation failed: %s", hipGetErrorString(e));
-        } else {
-            dst->edit_stream = st;
-            dst->concat_offsets = scan;
-            scan = nullptr;
-        }
-    }
-    if (scan) (void)hipFree(scan);
-    if (rc != GS_OK) {
-        if (dst) gs_gaussians_buffer_destroy(dst);
-        return rc;
-    }
-    dst->spatial = srcs[0]->spatial;
-    *out = dst;
-    if (counts_out)
-        for (uint32_t i = 0; i < count; i++) counts_out[i] = totals[i];
-    return GS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// attribute statistics, histograms, select by attribute range
-// ------------------------------------------------------------------------------------------------
-
-#define GS_ATTR_COV_TABLE(kernel)                                                                                       \
-    {                                                                                                                   \
-        {kernel<gs::ATTR_CLASS_COV, 0, 0>, kernel<gs::ATTR_CLASS_COV, 0, 1>, kernel<gs::ATTR_CLASS_COV, 0, 2>},         \
-        {kernel<gs::ATTR_CLASS_COV, 1, 0>, kernel<gs::ATTR_CLASS_COV, 1, 1>, kernel<gs::ATTR_CLASS_COV, 1, 2>},         \
-        {kernel<gs::ATTR_CLASS_COV, 2, 0>, kernel<gs::ATTR_CLASS_COV, 2, 1>, kernel<gs::ATTR_CLASS_COV, 2, 2>},         \
-        {kernel<gs::ATTR_CLASS_COV, 3, 0>, kernel<gs::ATTR_CLASS_COV, 3, 1>, kernel<gs::ATTR_CLASS_COV, 3, 2>},         \
-    }
-
-typedef void (*select_attr_fn)(const uint32_t *, uint32_t, uint32_t, gs::AttrArgs, float, float, uint32_t *, uint32_t);
-typedef void (*histogram_fn)(const uint32_t *, uint32_t, uint32_t, const uint32_t *, gs::AttrArgs, float, float, float, uint32_t,
-                             unsigned long long *);
-typedef void (*stats_fn)(const uint32_t *, uint32_t, const uint32_t *, gs::AttrArgs, uint32_t *, double *, uint32_t);
-static select_attr_fn k_tbl_select_attr_cov[4][3] = GS_ATTR_COV_TABLE(gs::k_select_attr);
-static histogram_fn k_tbl_histogram_cov[4][3] = GS_ATTR_COV_TABLE(gs::k_histogram);
-static stats_fn k_tbl_stats[4][3] = GS_CFG_TABLE(gs::k_stats_partial);
-
-// the kernel of an attribute's class: the position and colour passes do not depend on the layout
-static select_attr_fn select_attr_kernel(const gs_gaussians_buffer *g, uint32_t attr) {
-    const int cls = gs::attr_class(attr);
-    return cls == gs::ATTR_CLASS_POS ? gs::k_select_attr<gs::ATTR_CLASS_POS, 0, 0>
-           : cls == gs::ATTR_CLASS_COLOR ? gs::k_select_attr<gs::ATTR_CLASS_COLOR, 0, 0> : k_tbl_select_attr_cov[g->sh][g->cov];
-}
-static histogram_fn histogram_kernel(const gs_gaussians_buffer *g, uint32_t attr) {
-    const int cls = gs::attr_class(attr);
-    return cls == gs::ATTR_CLASS_POS ? gs::k_histogram<gs::ATTR_CLASS_POS, 0, 0>
-           : cls == gs::ATTR_CLASS_COLOR ? gs::k_histogram<gs::ATTR_CLASS_COLOR, 0, 0> : k_tbl_histogram_cov[g->sh][g->cov];
-}
-
-// the constants of an attribute pass; NULL transform = the default one through the same arithmetic
-static void attr_args_fill(gs::AttrArgs &a, uint32_t attr, const gs_model_transform_pod *mt, const float *ref) {
-    gs_model_transform_pod def;
-    if (!mt) {
-        gs_model_transform_pod_default(&def);
-        mt = &def;
-    }
-    gs::ModelTransform m;
-    std::memcpy(&m, mt, sizeof(m));
-    gs::model_transform_mat(m, a.M);
-    for (int k = 0; k < 3; k++) a.ref[k] = ref ? ref[k] : 0.0f;
-    a.attr = attr;
-}
-
-static gs_status check_attribute_desc(const gs_attribute_desc *a) {
-    if (!a) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (a->attr >= (uint32_t)GS_ATTR_COUNT) return fail(GS_ERR_INVALID_ARGUMENT, a->attr, 0, 0, "unknown attribute %u", (unsigned)a->attr);
-    for (uint32_t r : a->reserved)
-        if (r) return fail(GS_ERR_INVALID_ARGUMENT, r, 0, 0, "gs_attribute_desc.reserved must be 0");
-    if (a->attr == (uint32_t)GS_ATTR_DIST2 && !all_finite(a->ref, 3))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the reference point of GS_ATTR_DIST2 must be finite");
-    return GS_OK;
-}
-
-// the buffer's scratch for a stats / histogram call (grown, never shrunk; hipFree synchronises the device)
-static gs_status stats_scratch_reserve(gs_gaussians_buffer *g, size_t bytes) {
-    if (g->stats_scratch && g->stats_scratch_bytes >= bytes) return GS_OK;
-    if (g->stats_scratch) GS_HIP(hipFree(g->stats_scratch));
-    g->stats_scratch = nullptr;
-    g->stats_scratch_bytes = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    GS_HIP(hipMalloc(&g->stats_scratch, want));
-    g->stats_scratch_bytes = want;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_gaussians_buffer_stats(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel,
-                                               const gs_model_transform_pod *mt, const float ref[3], gs_stats *out) {
-    if (!g || !out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (ref && !all_finite(ref, 3)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the reference point must be finite");
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    static_assert(sizeof(gs::StatsOut) == sizeof(gs_stats), "the device result is a gs_stats");
-    gs_stats res;
-    std::memset(&res, 0, sizeof(res));
-    for (gs_attribute_stats &a : res.attr) {
-        a.min = INFINITY;
-        a.max = -INFINITY;
-    }
-    if (len) {
-        gs_device *dev = g->buf->dev;
-        GS_TRY(use_device(dev));
-        hipStream_t st = stream_of(dev, s);
-        const uint32_t n = (uint32_t)len, nblocks = (n + 255u) / 256u;
-        // [the result, 256 bytes][the sums: 9 x nblocks doubles][the integer fields: 28 x nblocks words]
-        const size_t d_bytes = (size_t)gs::ATTR_COUNT * nblocks * 8, u_bytes = (size_t)gs::STATS_U_FIELDS * nblocks * 4;
-        GS_TRY(stats_scratch_reserve(g, 256 + d_bytes + u_bytes));
-        // an edit enqueued on another stream still writes the records
-        if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
-        gs::StatsOut *dout = (gs::StatsOut *)g->stats_scratch;
-        double *part_d = (double *)((char *)g->stats_scratch + 256);
-        uint32_t *part_u = (uint32_t *)((char *)g->stats_scratch + 256 + d_bytes);
-        gs::AttrArgs a;
-        attr_args_fill(a, 0u, mt, ref);
-        hipLaunchKernelGGL(k_tbl_stats[g->sh][g->cov], dim3(nblocks), dim3(256), 0, st, (const uint32_t *)g->buf->ptr, n,
-                           sel ? (const uint32_t *)sel->words : nullptr, a, part_u, part_d, nblocks);
-        hipLaunchKernelGGL(gs::k_stats_finish, dim3(1), dim3(256), 0, st, (const uint32_t *)part_u, (const double *)part_d, nblocks, dout);
-        GS_HIP(hipGetLastError());
-        GS_HIP(hipMemcpyAsync(&res, dout, sizeof(res), hipMemcpyDeviceToHost, st));
-        hipError_t e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    }
-    *out = res;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_gaussians_buffer_histogram(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel,
-                                                   const gs_attribute_desc *ad, float lo, float hi, uint32_t bins, uint64_t *counts_out) {
-    if (!g || !counts_out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(check_attribute_desc(ad));
-    if (bins < 1u || bins > 4096u) return fail(GS_ERR_INVALID_ARGUMENT, bins, 0, 0, "a histogram takes 1 to 4096 bins, not %u", (unsigned)bins);
-    const float width = hi - lo;
-    if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(width) || !(hi > lo))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the range of a histogram must be finite, with hi > lo");
-    const float scale = (float)bins / width;
-    if (!std::isfinite(scale)) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bins / (hi - lo) is not finite in binary32");
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    const size_t slots = 2 * ((size_t)bins + 3);
-    if (!len) {
-        std::memset(counts_out, 0, slots * sizeof(uint64_t));
-        return GS_OK;
-    }
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    GS_TRY(stats_scratch_reserve(g, slots * 8));
-    // an edit enqueued on another stream still writes the records
-    if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
-    GS_HIP(hipMemsetAsync(g->stats_scratch, 0, slots * 8, st));
-    gs::AttrArgs a;
-    attr_args_fill(a, ad->attr, ad->model_transform, ad->ref);
-    const uint32_t n = (uint32_t)len, nblocks = (n + 255u) / 256u, grid = nblocks < 2048u ? nblocks : 2048u;
-    hipLaunchKernelGGL(histogram_kernel(g, ad->attr), dim3(grid), dim3(256), slots * 4, st, (const uint32_t *)g->buf->ptr,
-                       (uint32_t)(pod_stride(g) / 4), n, sel ? (const uint32_t *)sel->words : nullptr, a, lo, hi, scale, bins,
-                       (unsigned long long *)g->stats_scratch);
-    GS_HIP(hipGetLastError());
-    // into a host copy first: counts_out stays untouched when the stream reports a failure
-    std::vector<uint64_t> host(slots);
-    GS_HIP(hipMemcpyAsync(host.data(), g->stats_scratch, slots * 8, hipMemcpyDeviceToHost, st));
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    std::memcpy(counts_out, host.data(), slots * 8);
-    return GS_OK;
-}
-
-extern "C" gs_status gs_select_attribute(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_attribute_desc *ad, float lo,
-                                         float hi, gs_select_op op) {
-    GS_TRY(check_selection(sel, s));
-    GS_TRY(check_select_op(op));
-    if (!g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(check_attribute_desc(ad));
-    if (lo != lo || hi != hi) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "a bound of the range is NaN");
-    if (g->buf->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len != sel->n) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    sel->generation = next_object_id();
-    if (!len) return GS_OK;
-    // an edit enqueued on another stream still writes the records
-    if (g->edit_done && s->s != g->edit_stream) GS_HIP(hipStreamWaitEvent(s->s, g->edit_done, 0));
-    gs::AttrArgs a;
-    attr_args_fill(a, ad->attr, ad->model_transform, ad->ref);
-    const uint32_t n = (uint32_t)len;
-    hipLaunchKernelGGL(select_attr_kernel(g, ad->attr), dim3((n + 255u) / 256u), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr,
-                       (uint32_t)(pod_stride(g) / 4), n, a, lo, hi, sel->words, (uint32_t)op);
-    GS_HIP(hipGetLastError());
-    return GS_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// neighbour counts, select by neighbourhood
-// ------------------------------------------------------------------------------------------------
-
-static gs_status check_neighbor_radius(float radius) {
-    if (!(radius >= 0.0f) || !std::isfinite(radius) || !std::isfinite(radius * radius))
-        return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the radius must be finite and not negative, with a finite square");
-    return GS_OK;
-}
-
-// counts[i] = min(c_i, cap) in caller order on `st` (mark: gs::NB_NOT_A_POINT where i is no point); counts == nullptr: the
-// plane of the buffer's scratch, returned in *plane_out.  n > 0, arguments checked.
-static gs_status neighbor_counts_enqueue(gs_gaussians_buffer *g, hipStream_t st, const gs_selection *among,
-                                         const gs_model_transform_pod *mt, float radius, uint32_t cap, bool mark, uint32_t *counts,
-                                         uint32_t **plane_out) {
-    gs_device *dev = g->buf->dev;
-    const uint32_t n = (uint32_t)gs_gaussians_buffer_len(g), pod_words = (uint32_t)(pod_stride(g) / 4);
-    const uint32_t nblocks = (n + 255u) / 256u, pgrid = nblocks < 1024u ? nblocks : 1024u;
-    // [keys 0][vals 0][keys 1][vals 1][count plane][bbox partials][bbox]; the sorted positions (3 planes of n floats) take the
-    // key / value pair the sort did not leave its result in
-    const size_t a8 = ((size_t)n * 8 + 255) & ~(size_t)255, a4 = ((size_t)n * 4 + 255) & ~(size_t)255;
-    const size_t part = ((size_t)pgrid * 24 + 255) & ~(size_t)255;
-    GS_TRY(dev_reserve(g->nb_scratch, 2 * (a8 + a4) + a4 + part + 256));
-    char *base = (char *)g->nb_scratch.ptr;
-    void *k2[2] = {base, base + a8 + a4};
-    void *v2[2] = {base + a8, base + 2 * a8 + a4};
-    uint32_t *plane = (uint32_t *)(base + 2 * (a8 + a4));
-    float *partial = (float *)(base + 2 * (a8 + a4) + a4), *bbox = (float *)(base + 2 * (a8 + a4) + a4 + part);
-    // an edit enqueued on another stream still writes the records; a call on another stream still reads the scratch
-    if (g->edit_done && st != g->edit_stream) GS_HIP(hipStreamWaitEvent(st, g->edit_done, 0));
-    if (g->nb_done && st != g->nb_stream) GS_HIP(hipStreamWaitEvent(st, g->nb_done, 0));
-    gs::SelectShape sh{};
-    gs_model_transform_pod def;
-    if (!mt) {
-        gs_model_transform_pod_default(&def);
-        mt = &def;
-    }
-    gs::ModelTransform m;
-    std::memcpy(&m, mt, sizeof(m));
-    gs::model_transform_mat(m, sh.M);
-    const uint32_t *aos = (const uint32_t *)g->buf->ptr, *words = among ? (const uint32_t *)among->words : nullptr;
-    hipLaunchKernelGGL(gs::k_nb_bbox_partial, dim3(pgrid), dim3(256), 0, st, aos, pod_words, n, words, sh, partial);
-    hipLaunchKernelGGL(gs::k_bbox_final, dim3(1), dim3(256), 0, st, (const float *)partial, pgrid, bbox);
-    hipLaunchKernelGGL(gs::k_nb_keys, dim3(nblocks), dim3(256), 0, st, aos, pod_words, n, words, sh, (const float *)bbox, radius,
-                       (uint64_t *)k2[0], (uint32_t *)v2[0]);
-    GS_HIP(hipGetLastError());
-    int side = 0;
-    uint32_t passes = 0;
-    GS_TRY(sort_pairs_device<uint64_t>(dev, k2, v2, g->nb_ghist, g->nb_digit_totals, n, 64, st, side, passes));
-    const uint64_t *skeys = (const uint64_t *)k2[side];
-    const uint32_t *svals = (const uint32_t *)v2[side];
-    float *sx = (float *)k2[side ^ 1], *sy = sx + n, *sz = sy + n;      // 12 n bytes <= a8 + a4, the pair is contiguous
-    hipLaunchKernelGGL(gs::k_nb_gather, dim3(nblocks), dim3(256), 0, st, aos, pod_words, n, sh, skeys, svals, sx, sy, sz);
-    if (!counts) counts = plane;
-    const float rr = radius * radius;
-    if (mark)
-        hipLaunchKernelGGL(gs::k_nb_count<true>, dim3(nblocks), dim3(256), 0, st, skeys, svals, (const float *)sx, (const float *)sy,
-                           (const float *)sz, n, rr, cap, counts);
-    else
-        hipLaunchKernelGGL(gs::k_nb_count<false>, dim3(nblocks), dim3(256), 0, st, skeys, svals, (const float *)sx, (const float *)sy,
-                           (const float *)sz, n, rr, cap, counts);
-    GS_HIP(hipGetLastError());
-    if (plane_out) *plane_out = plane;
-    return GS_OK;
-}
-
-// the next call on another stream waits until this one has left the scratch
-static gs_status neighbor_scratch_release(gs_gaussians_buffer *g, hipStream_t st) {
-    if (!g->nb_done) GS_HIP(hipEventCreateWithFlags(&g->nb_done, hipEventDisableTiming));
-    GS_HIP(hipEventRecord(g->nb_done, st));
-    g->nb_stream = st;
-    return GS_OK;
-}
-
-extern "C" gs_status gs_gaussians_buffer_neighbor_counts(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *among,
-                                                         const gs_model_transform_pod *mt, float radius, uint32_t cap,
-                                                         gs_buffer *counts_out) {
-    if (!g || !counts_out) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(check_neighbor_radius(radius));
-    if (!cap) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "cap must be at least 1");
-    GS_TRY(check_buffer_selection(g, s, among));
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    if (counts_out->dev != g->buf->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    if (counts_out->bytes < len * 4)
-        return fail(GS_ERR_INVALID_ARGUMENT, counts_out->bytes, len * 4, 0, "the count plane has %zu bytes, %zu Gaussians need %zu",
-                    counts_out->bytes, len, len * 4);
-    if (!len) return GS_OK;
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // the event on every path: an enqueue that failed half-way has still left kernels on the scratch
-    const gs_status rc = neighbor_counts_enqueue(g, st, among, mt, radius, cap, false, (uint32_t *)counts_out->ptr, nullptr);
-    const gs_status ev = neighbor_scratch_release(g, st);
-    return rc != GS_OK ? rc : ev;
-}
-
-extern "C" gs_status gs_select_neighbors(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *g, const gs_selection *among,
-                                         const gs_model_transform_pod *mt, float radius, uint32_t min_count, uint32_t max_count,
-                                         gs_select_op op) {
-    if (!sel || !g) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(check_select_op(op));
-    GS_TRY(check_neighbor_radius(radius));
-    if (g->buf->dev != sel->dev) return fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
-    GS_TRY(check_buffer_selection(g, s, among));
-    const size_t len = gs_gaussians_buffer_len(g);
-    if (len != sel->n) return fail(GS_ERR_INVALID_ARGUMENT, sel->n, len, 0, "the selection has %zu bits, the buffer %zu Gaussians", sel->n, len);
-    if (len > 0xfffffff0ull) return fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
-    gs_device *dev = sel->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    if (!len) {
-        sel->generation = next_object_id();
-        return GS_OK;
-    }
-    const uint32_t n = (uint32_t)len;
-    if (min_count > max_count) {      // sel = sel op {}
-        sel->generation = next_object_id();
-        hipLaunchKernelGGL(gs::k_sel_range, dim3(sel->grid()), dim3(256), 0, st, sel->words, (uint32_t)sel->nwords, 0u, 0u, (uint32_t)op);
-        GS_HIP(hipGetLastError());
-        return GS_OK;
-    }
-    // a count above max_count only has to be known as such
-    const uint32_t cap = max_count == 0xffffffffu ? max_count : max_count + 1u;
-    uint32_t *plane = nullptr;
-    gs_status rc = neighbor_counts_enqueue(g, st, among, mt, radius, cap, true, nullptr, &plane);
-    if (rc == GS_OK) {      // only now does `sel` change
-        sel->generation = next_object_id();
-        hipLaunchKernelGGL(gs::k_nb_select, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)plane, n, min_count, max_count,
-                           sel->words, (uint32_t)op);
-        if (hipGetLastError() != hipSuccess) rc = fail(GS_ERR_HIP, 0, 0, 0, "k_nb_select could not be launched");
-    }
-    // the event on every path: an enqueue that failed half-way has still left kernels on the scratch
-    const gs_status ev = neighbor_scratch_release(g, st);
-    return rc != GS_OK ? rc : ev;
 }

@@ -1,6 +1,6 @@
 // gs_convert.h — source-format record -> struct Gaussian conversions as ONE set of host + device
 // functions: Gaussian::from_ply (src/gaussian.rs:70-92).  The host entry point
-// (gs_gaussian_from_ply, gs_ply.cpp) and the device kernel (k_from_ply_pods, gs3d.hip) both call
+// (gs_gaussian_from_ply, gs_ply.cpp) and the device kernel (k_from_ply_pods, gs_pack_kernels.h) both call
 // ply_to_gaussian_words below, so a scene loaded on the device is bit-identical to one converted on
 // the host by construction.
 //

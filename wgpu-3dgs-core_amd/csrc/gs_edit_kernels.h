@@ -3,11 +3,11 @@
 // this with compute passes over the Gaussian buffer; the core crate has none.
 //
 // The codecs are the library's own: records are decoded with gs_kernel_lib.h (gaussian_unpack_sh / _cov3d, unorm8) and
-// re-encoded with gs_pack_kernels.h / gs_convert.h (f32_to_f16_rtne_bits, sh_norm8_byte, cv_sat_u8, cv_canon_nan_bits).
+// re-encoded with gs_device_common.h / gs_convert.h (f32_to_f16_rtne_bits, sh_norm8_byte, cv_sat_u8, cv_canon_nan_bits).
 #pragma once
 
-#include "gs_pack_kernels.h"
-#include "gs_render_kernels.h"
+#include "gs_convert.h"
+#include "gs_device_common.h"
 
 namespace gs {
 
@@ -24,16 +24,6 @@ struct EditArgs {
     float o[2];       // opacity: a' = o[0] a + o[1]
     uint32_t flags;
 };
-
-// the selection words of the 64 Gaussians starting at `i0` (a multiple of 64) as one 64-bit mask; words == null selects
-// every Gaussian below n.  A mask word never has bits at positions >= n.
-__device__ __forceinline__ uint64_t wave_selection_mask(const uint32_t *__restrict__ words, uint32_t i0, uint32_t n) {
-    if (i0 >= n) return 0ull;
-    if (!words) return n - i0 >= 64u ? ~0ull : (1ull << (n - i0)) - 1ull;
-    const uint32_t w = i0 >> 5;
-    const uint64_t lo = words[w], hi = i0 + 32u < n ? words[w + 1u] : 0u;
-    return lo | (hi << 32);
-}
 
 __device__ __forceinline__ uint32_t edit_unorm_byte(float v) { return cv_sat_u8(v * 255.0f + 0.5f); }
 

@@ -1,0 +1,213 @@
+// gs_host.h — what the HIP translation units of libgs3d_hip.so share: the error macros, the objects behind
+// the handles of include/gs3d.h that more than one unit touches, and the few host functions that cross a unit boundary
+// (namespace gsh; each says which unit defines it).  gs_internal.h stays free of HIP: gs_ply.cpp and gs_spz.cpp are also
+// built by a plain C++ compiler.
+#pragma once
+
+#include "gs_internal.h"
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "gs_kernel_lib.h"
+#include "gs_policy.h"
+
+#define GS_HIP(expr)                                                                              \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess)                                                                     \
+            return gs_fail(e_ == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP,         \
+                           (uint64_t)e_, 0, 0, "%s failed: %s", #expr, hipGetErrorString(e_));    \
+    } while (0)
+
+#define GS_TRY(expr)                  \
+    do {                              \
+        gs_status s_ = (expr);        \
+        if (s_ != GS_OK) return s_;   \
+    } while (0)
+
+// one kernel instance per POD layout: table[sh][cov]
+#define GS_CFG_TABLE(kernel)                                                                     \
+    {                                                                                            \
+        {kernel<0, 0>, kernel<0, 1>, kernel<0, 2>}, {kernel<1, 0>, kernel<1, 1>, kernel<1, 2>},  \
+        {kernel<2, 0>, kernel<2, 1>, kernel<2, 2>}, {kernel<3, 0>, kernel<3, 1>, kernel<3, 2>},  \
+    }
+
+// ------------------------------------------------------------------------------------------------
+// device / stream / buffer
+// ------------------------------------------------------------------------------------------------
+
+struct gs_device {
+    int ordinal;
+    gs_limits limits;
+    hipStream_t internal;  // for blocking helper work
+    // probe result: returning LDS atomics hand out lane-ordered values.  Written by any renderer of the device whose rank
+    // watchdog fired (gs_render_frame / gs_renderer_wait_frame, possibly from different host threads) and read once per
+    // frame (SortCtx::fast_rank) and by the stand-alone sorts: atomic, relaxed — it only ever goes from true to false.
+    std::atomic<bool> lds_atomic_ordered{false};
+    // renderers of this device: gs_stream_destroy records the end-of-frame event of those whose last frame sits on the
+    // stream that is going away (the event is otherwise recorded lazily, when the renderer moves to another stream)
+    std::mutex renderers_mu;
+    std::vector<struct gs_renderer *> renderers;
+};
+
+struct gs_stream {
+    gs_device *dev;
+    hipStream_t s;
+    bool owned;
+};
+
+struct gs_buffer {
+    gs_device *dev;
+    void *ptr;
+    size_t bytes;
+    bool owned;
+    std::atomic<int> refs;
+};
+
+// a device array that grows and never shrinks (hipFree synchronises the device)
+struct DevArray {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
+
+namespace gsh {
+
+// ---- gs_core.hip ----
+// every GS3D_* switch that is read once per process
+const gsp::Switches &switches();
+gs_status use_device(const gs_device *dev);
+gs_status dev_reserve(DevArray &a, size_t bytes);
+void dev_free(DevArray &a);
+// *out = `bytes` of device memory, or null and GS_ERR_OUT_OF_MEMORY / GS_ERR_HIP with the message "<what> failed: ..."
+// (gs_error_info: a = the HIP error, b as given: the size, or 0 at the sites that never reported one)
+gs_status dev_alloc(void **out, size_t bytes, uint64_t b, const char *what);
+// ids of buffers and generations of selections: unique in the process, never 0
+uint64_t next_object_id();
+
+}  // namespace gsh
+
+// ------------------------------------------------------------------------------------------------
+// GaussiansBuffer<G>
+// ------------------------------------------------------------------------------------------------
+
+struct gs_gaussians_buffer {
+    gs_buffer *buf;
+    int sh, cov;
+    // block-planar mirror read by the preprocess kernel; rebuilt lazily
+    void *planar;
+    size_t planar_stride;  // capacity in Gaussians = len rounded up to whole 1024-blocks
+    // Gaussians [dirty_lo, dirty_hi) of the AoS buffer are newer than the mirror (empty when lo >= hi).
+    // update_range dirties only its own range, so an editor's per-edit update re-mirrors a few
+    // Gaussians instead of the whole scene.
+    size_t dirty_lo, dirty_hi;
+    // spatial mirror order: order[slot] = Gaussian index, inv[index] = slot; both
+    // null while the mirror is in index order.  `order` is a ref-counted gs_buffer so that the
+    // renderer's parity taps can keep the order of the frame they describe.
+    bool spatial;
+    gs_buffer *order;
+    void *inv;
+    void *block_bounds;      // 8 floats per 1024-slot block (k_block_bounds); null = not available
+    size_t partial_since_order;   // Gaussians rewritten by partial updates since the order was built
+    // The mirror is (re)built on the stream of whichever frame first needs it; frames on OTHER streams
+    // (several renderers keeping frames in flight on one buffer) wait for this event before reading it.
+    hipEvent_t mirror_ready = nullptr;
+    hipStream_t mirror_stream = nullptr;
+    // gs_gaussians_buffer_edit only ENQUEUES its kernel: a mirror rebuild on another stream waits for
+    // this event before it reads the AoS records (gsh::wait_for_edits / record_edit).  keep_order: the whole buffer is
+    // dirty but no position changed (a colour / opacity edit), so the rebuild repacks through the order it has instead
+    // of sorting again.
+    hipEvent_t edit_done = nullptr;
+    hipStream_t edit_stream = nullptr;
+    bool keep_order = false;
+    // what a renderer's slot-ordered selection masks were gathered through: this buffer (ids are never
+    // reused, addresses are) and this build of its mirror order
+    uint64_t uid = gsh::next_object_id();
+    uint64_t order_epoch = 0;
+    // gs_gaussians_buffer_create_concat: the per-block offsets its copies read; they are only enqueued
+    // when the call returns, so the new buffer owns the array
+    void *concat_offsets = nullptr;
+    // gs_gaussians_buffer_stats / _histogram: the partial rows and the device result of the last call
+    DevArray stats_scratch;
+    // gs_gaussians_buffer_neighbor_counts / gs_select_neighbors: keys, order, sorted positions and the
+    // sort's histograms of the last call; a call on another stream waits for nb_done before it reuses them
+    DevArray nb_scratch, nb_ghist, nb_digit_totals;
+    hipEvent_t nb_done = nullptr;
+    hipStream_t nb_stream = nullptr;
+    void mark(size_t lo, size_t hi) {
+        if (lo >= hi) return;
+        partial_since_order += hi - lo;
+        if (dirty_lo >= dirty_hi) { dirty_lo = lo; dirty_hi = hi; return; }
+        if (lo < dirty_lo) dirty_lo = lo;
+        if (hi > dirty_hi) dirty_hi = hi;
+    }
+    void mark_all() { dirty_lo = 0; dirty_hi = (size_t)-1; keep_order = false; }
+};
+
+// Gaussian selection: n bits in caller index order.  `generation` changes with every call that may
+// modify the bits (next_object_id: unique across selections), which is how a renderer knows its slot-ordered copy is stale.
+struct gs_selection {
+    gs_device *dev;
+    size_t n, nwords;
+    uint32_t *words;            // device, nwords (at least one word is allocated)
+    DevArray scratch;           // a plane of the same size for the select ops that scatter their bits (select_visible)
+    DevArray counter;           // gs_selection_count's device total
+    uint64_t generation;
+    uint32_t tail_mask() const { return (n & 31u) ? (1u << (n & 31u)) - 1u : 0xffffffffu; }
+    uint32_t grid() const { return nwords < 256u * 1024u ? (uint32_t)((nwords + 255u) / 256u) + 1u : 1024u; }
+};
+
+namespace gsh {
+
+inline bool valid_cfg(int sh, int cov) { return sh >= 0 && sh <= 3 && cov >= 0 && cov <= 2; }
+inline hipStream_t stream_of(gs_device *dev, gs_stream *s) { return s ? s->s : dev->internal; }
+inline size_t pod_stride(const gs_gaussians_buffer *g) { return (size_t)gs::pod_bytes(g->sh, g->cov); }
+inline bool all_finite(const float *v, int n) {
+    for (int k = 0; k < n; k++)
+        if (!std::isfinite(v[k])) return false;
+    return true;
+}
+// the kernels index Gaussians with 32 bits
+inline gs_status check_len32(size_t len) {
+    if (len > 0xfffffff0ull) return gs_fail(GS_ERR_INVALID_ARGUMENT, len, 0, 0, "too many Gaussians");
+    return GS_OK;
+}
+
+// ---- gs_core.hip ----
+// `st` waits for the edit, restore or concatenation that another stream still has in flight on the records of `g`
+gs_status wait_for_edits(const gs_gaussians_buffer *g, hipStream_t st);
+// ... and `st` has just been given such work: whoever reads or writes the records on another stream waits for it
+gs_status record_edit(gs_gaussians_buffer *g, hipStream_t st);
+
+// ---- gs3d.hip ----
+// gs_device_create: do returning LDS atomics hand out lane-ordered values (the fast radix rank)?  Blocks on `st`.
+bool probe_lds_atomic_order(hipStream_t st);
+// gs_stream_destroy: the end-of-frame event of every renderer whose last frame is on `st` is recorded now
+void renderers_leave_stream(gs_device *dev, hipStream_t st);
+// stable radix sort of (key, u32 value) pairs with a host-known count; instantiated for uint32_t and uint64_t keys
+template <typename K>
+gs_status sort_pairs_device(const gs_device *dev, void *const keys[2], void *const vals[2], DevArray &ghist, DevArray &digit_totals,
+                            uint32_t count, uint32_t end_bit, hipStream_t st, int &result_side, uint32_t &passes_out);
+// k_scan_chunks, one workgroup of 1024: out = exclusive scan of in[0, n) (in place allowed), *total = the sum
+void scan_chunks_enqueue(hipStream_t st, const uint32_t *in, uint32_t *out, uint32_t *total, uint32_t n);
+// k_bbox_final, one workgroup of 256: `count` partial boxes of 6 floats -> bbox
+void bbox_final_enqueue(hipStream_t st, const float *partial, uint32_t count, float *bbox);
+
+// ---- gs_select.hip ----
+gs_status check_selection(const gs_selection *sel, const gs_stream *s);
+gs_status check_select_op(gs_select_op op);
+// the selection argument of an edit / extraction / statistic: NULL (all), or n bits on the buffer's device
+gs_status check_buffer_selection(const gs_gaussians_buffer *g, const gs_stream *s, const gs_selection *sel);
+// dst = dst op src over whole words on `st` (src: another selection's words, or dst's scratch plane)
+gs_status selection_combine_words(gs_selection *dst, hipStream_t st, gs_select_op op, const uint32_t *src);
+// k_sel_range: sel = sel op {i : start <= i < end} on `st`; sel->nwords > 0
+void sel_range_enqueue(gs_selection *sel, hipStream_t st, uint32_t start, uint32_t end, gs_select_op op);
+
+}  // namespace gsh

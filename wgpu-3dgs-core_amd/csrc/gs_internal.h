@@ -1,4 +1,5 @@
-// gs_internal.h — helpers shared by the host translation units of libgs3d_hip.so
+// gs_internal.h — helpers shared by ALL host translation units of libgs3d_hip.so; free of HIP (gs_ply.cpp and gs_spz.cpp
+// are also built by a plain C++ compiler).  What only the HIP units share is in gs_host.h.
 #pragma once
 #include "../../include/gs3d.h"
 
@@ -8,7 +9,7 @@ gs_status gs_fail(gs_status code, uint64_t a, uint64_t b, uint64_t c, const char
 
 #ifdef __cplusplus
 #include <vector>
-// gs_spz.cpp, for the device load path in gs3d.hip: validates the header of a DECOMPRESSED SPZ payload
+// gs_spz.cpp, for the device load path in gs_core.hip: validates the header of a DECOMPRESSED SPZ payload
 // and its length, returns the byte offsets of the six columns (positions, alphas, colors, scales,
 // rotations, sh) and the SH coefficients per channel; errors as gs_spz_decode_decompressed
 gs_status gs_spz_payload_layout(const void *bytes, size_t len, gs_spz_header *header_out, size_t col_offset[6],

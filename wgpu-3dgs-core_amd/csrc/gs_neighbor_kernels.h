@@ -10,7 +10,7 @@
 // Every operation is rounded (-ffp-contract=off).
 #pragma once
 
-#include "gs_stats_kernels.h"
+#include "gs_device_common.h"
 
 namespace gs {
 

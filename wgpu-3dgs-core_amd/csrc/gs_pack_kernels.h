@@ -6,7 +6,7 @@
 #pragma once
 
 #include "gs_convert.h"
-#include "gs_kernel_lib.h"
+#include "gs_device_common.h"
 
 namespace gs {
 
@@ -14,40 +14,6 @@ namespace gs {
 // rot xyzw @0, pos @4, color u8x4 @7, sh[45] @8, scale @53
 constexpr int GAUSSIAN_WORDS = 56;
 constexpr int GW_ROT = 0, GW_POS = 4, GW_COLOR = 7, GW_SH = 8, GW_SCALE = 53;
-
-// IEEE binary32 -> binary16, round to nearest even (half 2.7.1 f16::from_f32; gaussian_config.rs:59,227)
-__host__ __device__ inline uint16_t f32_to_f16_rtne_bits(uint32_t fbits) {
-    const uint32_t f32infty = 255u << 23, f16max = (127u + 16u) << 23;
-    const uint32_t magic = ((127u - 15u) + (23u - 10u) + 1u) << 23;
-    const uint32_t sign = fbits & 0x80000000u;
-    uint32_t u = fbits ^ sign;
-    uint16_t o;
-    if (u >= f16max) {
-        o = (u > f32infty) ? (uint16_t)(0x7e00u | ((u >> 13) & 0x1ffu)) : (uint16_t)0x7c00u;
-    } else if (u < (113u << 23)) {
-        // subnormal / zero result: one float add against the magic constant does the rounding
-        union { uint32_t u; float f; } a, m;
-        a.u = u;
-        m.u = magic;
-        a.f += m.f;
-        o = (uint16_t)(a.u - magic);
-    } else {
-        const uint32_t odd = (u >> 13) & 1u;
-        u += ((uint32_t)(15 - 127) << 23) + 0xfffu;
-        u += odd;
-        o = (uint16_t)(u >> 13);
-    }
-    return (uint16_t)(o | (sign >> 16));
-}
-
-// GaussianShNorm8Config: (v * 127).clamp(-127, 127) as i8 — truncation toward zero, NaN -> 0
-__host__ __device__ inline uint32_t sh_norm8_byte(float v) {
-    float x = v * 127.0f;
-    if (x != x) x = 0.0f;
-    if (x < -127.0f) x = -127.0f;
-    if (x > 127.0f) x = 127.0f;
-    return (uint32_t)(uint8_t)(int8_t)(int)x;
-}
 
 // GaussianCov3dSingleConfig: (R S)(R S)^T with glam's Mat3::from_quat formulation, upper triangle
 __host__ __device__ inline void cov3d_from_rot_scale(const float q[4], const float s[3], float out[6]) {

@@ -1,7 +1,7 @@
 // gs_policy.h — what a frame decides before and between its launches: pure arithmetic on the reports of the finished
 // frames, the frame's shape numbers, the requests of the API, the environment switches and the renderer's feedback
 // state.  No HIP header, no HIP call, no launch: tests/cpp/test_policy.cpp compiles this file with a host compiler.
-// The device-side constants the rules refer to come in through PolicyParams (gs3d.hip fills it from gs_render_kernels.h).
+// The device-side constants the rules refer to come in through PolicyParams (the render unit, gs3d.hip, fills it from gs_render_kernels.h).
 #pragma once
 
 #include <cstdint>
@@ -9,7 +9,7 @@
 namespace gsp {
 
 // ------------------------------------------------------------------------------------------------
-// switches: every GS3D_* environment variable the library reads once per process (read_switches() in gs3d.hip fills
+// switches: every GS3D_* environment variable the library reads once per process (read_switches() in gs_core.hip fills
 // the table on first use; the defaults here are the values of an empty environment).  -1 = "not set": the renderer
 // chooses.  Precedence everywhere: gs_renderer_set_* request, then the environment, then the renderer's own choice.
 // ------------------------------------------------------------------------------------------------

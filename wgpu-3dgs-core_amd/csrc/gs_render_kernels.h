@@ -20,11 +20,10 @@
 
 #include <type_traits>
 
-#include "gs_kernel_lib.h"
+#include "gs_device_common.h"
 
 namespace gs {
 
-constexpr int WAVE = 64;
 constexpr int PP_THREADS = 256;
 constexpr int PP_ITEMS = 4;                       // Gaussians per thread in preprocess / emit
 constexpr int PP_CHUNK = PP_THREADS * PP_ITEMS;   // scan chunk = one workgroup's Gaussians
@@ -111,89 +110,6 @@ __host__ __device__ inline void rect_unpack64(uint2 r, uint32_t &r0, uint32_t &r
         r1 = r.y;
         rows = 0u;
     }
-}
-
-// ---------------------------------------------------------------------------------------------
-// wave / block primitives
-// ---------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t lane_id() {
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
-// number of set bits of `mask` strictly below this lane
-__device__ __forceinline__ uint32_t mbcnt(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                     __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// Wave64 inclusive scans on the DPP cross-lane path (no LDS traffic, one VALU instruction per step):
-// row_shr 1/2/4/8 scan each 16-lane row, row_bcast15 carries the row totals into the odd rows
-// (row mask 0xa) and row_bcast31 carries the lower half's total into the upper half (row mask 0xc).
-// Lanes without a source keep `identity`.  (A __shfl_up ladder costs a ds_bpermute round trip per
-// step: ~6 dependent LDS operations per scan.)
-#define GS_DPP_STEP(OP, CTRL, ROWMASK)                                                             \
-    v = OP(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, CTRL, ROWMASK, 0xf, false))
-__device__ __forceinline__ uint32_t dpp_op_add(uint32_t a, uint32_t b) { return a + b; }
-__device__ __forceinline__ uint32_t dpp_op_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane) {
-    (void)lane;
-    const uint32_t identity = 0u;
-    GS_DPP_STEP(dpp_op_add, 0x111, 0xf);   // row_shr:1
-    GS_DPP_STEP(dpp_op_add, 0x112, 0xf);   // row_shr:2
-    GS_DPP_STEP(dpp_op_add, 0x114, 0xf);   // row_shr:4
-    GS_DPP_STEP(dpp_op_add, 0x118, 0xf);   // row_shr:8
-    GS_DPP_STEP(dpp_op_add, 0x142, 0xa);   // row_bcast:15
-    GS_DPP_STEP(dpp_op_add, 0x143, 0xc);   // row_bcast:31
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t v) {
-    const uint32_t identity = 0u;
-    GS_DPP_STEP(dpp_op_max, 0x111, 0xf);
-    GS_DPP_STEP(dpp_op_max, 0x112, 0xf);
-    GS_DPP_STEP(dpp_op_max, 0x114, 0xf);
-    GS_DPP_STEP(dpp_op_max, 0x118, 0xf);
-    GS_DPP_STEP(dpp_op_max, 0x142, 0xa);
-    GS_DPP_STEP(dpp_op_max, 0x143, 0xc);
-    return v;
-}
-#undef GS_DPP_STEP
-
-__device__ __forceinline__ uint32_t dpp_op_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
-// wave minimum / maximum, uniform in every lane (all 64 lanes must be active)
-__device__ __forceinline__ uint32_t wave_reduce_min(uint32_t v) {
-    const uint32_t identity = 0xffffffffu;
-#define GS_DPP_MIN(CTRL, ROWMASK) \
-    v = dpp_op_min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, CTRL, ROWMASK, 0xf, false))
-    GS_DPP_MIN(0x111, 0xf); GS_DPP_MIN(0x112, 0xf); GS_DPP_MIN(0x114, 0xf); GS_DPP_MIN(0x118, 0xf);
-    GS_DPP_MIN(0x142, 0xa); GS_DPP_MIN(0x143, 0xc);
-#undef GS_DPP_MIN
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t wave_reduce_max(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_max(v), 63);
-}
-
-// wave total, uniform in every lane (all 64 lanes must be active)
-__device__ __forceinline__ uint32_t wave_reduce_add(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(v, 0u), 63);
-}
-
-// Exclusive scan over a 256-thread block; `smem` holds >= 4 words; returns exclusive prefix and
-// the block total.  Ends with the LDS reusable after the caller's next barrier.
-__device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_t *smem,
-                                                             uint32_t &total) {
-    uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
-    uint32_t inc = wave_inclusive_scan(v, lane);
-    if (lane == 63u) smem[wid] = inc;
-    __syncthreads();
-    uint32_t w0 = smem[0], w1 = smem[1], w2 = smem[2], w3 = smem[3];
-    uint32_t wave_off = wid == 0 ? 0u : wid == 1 ? w0 : wid == 2 ? w0 + w1 : w0 + w1 + w2;
-    total = w0 + w1 + w2 + w3;
-    __syncthreads();
-    return wave_off + inc - v;
 }
 
 // 16-byte store, optionally WRITE-THROUGH at agent scope (`sc1`).  A kernel that leaves B bytes dirty in the L2s makes
@@ -301,13 +217,6 @@ __global__ void k_publish_result(FrameResult *r, FrameState *state, uint32_t gen
     }
 }
 
-// wave sum of a 64-bit value, uniform in every lane (all 64 lanes active)
-__device__ __forceinline__ uint64_t wave_reduce_add64(uint64_t v) {
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor((unsigned long long)v, d, WAVE);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------
 // repack: AoS (N x pod_bytes) -> block-planar mirror
 // ---------------------------------------------------------------------------------------------
@@ -317,7 +226,7 @@ __device__ __forceinline__ uint64_t wave_reduce_add64(uint64_t v) {
 // preprocess workgroup (one block) therefore streams one contiguous nc x 16 KiB span, and a wave
 // still reads 1 KiB contiguous per load instruction.  (Whole-array planes — plane stride N x 16 B —
 // measured 2 % slower at 10 M: 14 streams 160 MB apart instead of one 224 KiB span per workgroup.)
-constexpr uint32_t PLANAR_BLOCK = 1024;
+// (PLANAR_BLOCK: gs_device_common.h)
 __device__ __forceinline__ uint64_t planar_at(uint32_t c, uint64_t i, uint32_t nc) {
     return (((i / PLANAR_BLOCK) * nc + c) * PLANAR_BLOCK) | (i % PLANAR_BLOCK);
 }
@@ -4370,4 +4279,70 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// selections and the frame: the two kernels that read a frame's per-slot arrays or write the
+// slot-ordered masks its preprocess kernels read; the selection's own kernels are in gs_select_kernels.h
+// ---------------------------------------------------------------------------------------------
+
+// gs_renderer_select_visible: the per-slot outputs a frame left behind -> bits of a scratch plane in caller index order
+struct VisibleIO {
+    const uint32_t *depth;         // per-slot depth keys (0xffffffff = culled)
+    const uint32_t *chunk_vis;     // 0 = the chunk's per-slot arrays are stale (block-culled or fully hidden)
+    const uint32_t *recs;          // blend records: words 0, 1 = mx, my
+    const uint32_t *block_list;    // list frame: block of every list position; else null
+    const uint32_t *list_blocks;   // ... and the list's length (device word)
+    const uint32_t *order;         // caller index of every mirror slot; null = identity
+    uint32_t n, nslots;
+    float x0, y0, x1, y1;
+    const uint8_t *mask;           // H x W, or null
+    uint32_t width, height;
+    uint32_t *scratch;             // cleared; bits are set with atomics (the slots of one word are scattered)
+};
+
+__global__ __launch_bounds__(256) void k_select_visible(VisibleIO io) {
+    const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t limit = io.block_list ? *io.list_blocks * (uint32_t)PP_CHUNK : io.nslots;
+    if (slot >= limit || slot >= io.nslots) return;
+    if (io.chunk_vis[slot / (uint32_t)PP_CHUNK] == 0u || io.depth[slot] == 0xffffffffu) return;
+    const float mx = u2f(io.recs[(uint64_t)slot * REC_WORDS]), my = u2f(io.recs[(uint64_t)slot * REC_WORDS + 1u]);
+    if (!(io.x0 <= mx && mx < io.x1 && io.y0 <= my && my < io.y1)) return;
+    if (io.mask) {
+        if (!(mx >= 0.0f && my >= 0.0f && mx < (float)io.width && my < (float)io.height)) return;
+        const uint32_t px = (uint32_t)floorf(mx), py = (uint32_t)floorf(my);
+        if (px >= io.width || py >= io.height || io.mask[(uint64_t)py * io.width + px] == 0u) return;
+    }
+    uint32_t ms = slot;
+    if (io.block_list) ms = io.block_list[slot / (uint32_t)PP_CHUNK] * (uint32_t)PP_CHUNK + slot % (uint32_t)PP_CHUNK;
+    if (ms >= io.n) return;
+    const uint32_t i = io.order ? io.order[ms] : ms;
+    if (i >= io.n) return;
+    atomicOr(&io.scratch[i >> 5], 1u << (i & 31u));
+}
+
+// Caller-order mask -> mirror-slot order, 64 slots per word (SelIO), one workgroup per 1024-block of the mirror; with
+// `block_hidden`, also the block's "every Gaussian is hidden" flag.  out holds blocks * 16 words.
+__global__ __launch_bounds__(PP_THREADS) void k_selection_to_slots(const uint32_t *__restrict__ words,
+                                                                   const uint32_t *__restrict__ order, uint32_t n,
+                                                                   uint64_t *__restrict__ out,
+                                                                   uint32_t *__restrict__ block_hidden) {
+    __shared__ uint32_t s_all[PP_THREADS / WAVE];
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    bool all = true;
+#pragma unroll
+    for (int k = 0; k < PP_ITEMS; k++) {
+        const uint32_t slot = blockIdx.x * (uint32_t)PP_CHUNK + k * PP_THREADS + threadIdx.x;
+        bool bit = false;
+        if (slot < n) {
+            const uint32_t i = order ? order[slot] : slot;
+            bit = i < n && ((words[i >> 5] >> (i & 31u)) & 1u);
+        }
+        const uint64_t m = __ballot(bit), valid = __ballot(slot < n);
+        if (lane == 0u) out[slot >> 6] = m;
+        all = all && m == valid;
+    }
+    if (!block_hidden) return;
+    if (lane == 0u) s_all[wid] = all ? 1u : 0u;
+    __syncthreads();
+    if (threadIdx.x == 0u) block_hidden[blockIdx.x] = (s_all[0] & s_all[1]) & (s_all[2] & s_all[3]);
+}
 }  // namespace gs

@@ -7,8 +7,7 @@
 // written word-wise as in gs_select_kernels.h / gs_edit_kernels.h.  Every operation is rounded (-ffp-contract=off).
 #pragma once
 
-#include "gs_edit_kernels.h"
-#include "gs_select_kernels.h"
+#include "gs_device_common.h"
 
 namespace gs {
 
@@ -29,7 +28,6 @@ struct AttrArgs {
     uint32_t attr;
 };
 
-__device__ __forceinline__ bool attr_finite(float v) { return (f2u(v) & 0x7f800000u) != 0x7f800000u; }
 // the total order on the bit patterns as an unsigned integer: -0 < +0, every finite key lies strictly between the keys
 // of -inf and +inf
 __device__ __forceinline__ uint32_t attr_sort_key(float v) {
