@@ -1,6 +1,18 @@
-import sys, numpy as np
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tools'); sys.path.insert(0,'/root/repo/tests')
+# Wave-steps of the blend on the bench's 1 M scene and camera, from the oracle's lists (CPU only).
+#   python3 tools/blend_sim.py                      the block shapes and batch sizes, threshold slack 0.1
+#   python3 tools/blend_sim.py --slack 0.0          the same with another constant in the block threshold pmin - slack
+#   python3 tools/blend_sim.py --staging-table      only the G = 8 staging table: slack 0.1 / 0.01 / 0.0, each with and without
+#                                                   the blocks that are finished at a batch start left off that batch's lists
+#   --drop-finished                                 adds that drop to the G = 8 rows of the default run
+import argparse, os, sys, numpy as np
+_root=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (_root, os.path.join(_root,'tools'), os.path.join(_root,'tests')): sys.path.insert(0,_p)
 import synth, helpers
+_ap=argparse.ArgumentParser()
+_ap.add_argument('--slack',type=float,default=0.1)
+_ap.add_argument('--drop-finished',action='store_true')
+_ap.add_argument('--staging-table',action='store_true')
+ARGS=_ap.parse_args()
 from oracle import binding as ob
 N=1_000_000; sh,cov=3,0
 g=synth.scene(N); pods=ob.pack(sh,cov,g)
@@ -19,16 +31,55 @@ op=p['opacity'].astype(np.float64)
 pmin=np.maximum(-np.log(255*op)-1e-3,-5.6)
 def pmax(q2,q1,q0,lo,hi):
     t=np.clip(-0.5*q1/q2,lo,hi); return (q2*t+q1)*t+q0
-def touches(rx0,rx1,ry0,ry1):
+def touches(rx0,rx1,ry0,ry1,slack=None):
+    slack=ARGS.slack if slack is None else slack
     dxl=mx-rx1; dxh=mx-rx0; dyl=my-ry1; dyh=my-ry0
     inx=(dxl<=0)&(dxh>=0); iny=(dyl<=0)&(dyh>=0)
     m0=pmax(cc,cb*dxl,ca*dxl*dxl,dyl,dyh); m1=pmax(cc,cb*dxh,ca*dxh*dxh,dyl,dyh)
     m2=pmax(ca,cb*dyl,cc*dyl*dyl,dxl,dxh); m3=pmax(ca,cb*dyh,cc*dyh*dyh,dxl,dxh)
     m=np.maximum(np.maximum(m0,m1),np.maximum(m2,m3))
-    return (inx&iny)|~(m<pmin-0.1)
+    return (inx&iny)|~(m<pmin-slack)
 x0=tx*16+0.5; y0=ty*16+0.5
 # position within tile list -> batch
 start=np.searchsorted(tile,np.arange(8160)); pos=np.arange(D)-start[tile]; batch=pos//128
+# --- the G = 8 staging: 4x4 blocks, 128-splat batches; a block all of whose 16 pixels have stopped (T < 1e-4, or outside the image) when a
+# batch starts takes no entry in that batch.  The flags are the oracle's: blend(..., stopped=True) on every range cut at a multiple of 128.
+_fin={}
+def finished_at(mb):
+    if mb not in _fin:
+        nt=120*68
+        rng=np.asarray(ob.tile_ranges(keys,nt)).reshape(nt,2).astype(np.int64)
+        r=rng.copy(); r[:,1]=r[:,0]+np.minimum(rng[:,1]-rng[:,0],128*mb)
+        _,st=ob.blend(proj,idx,np.ascontiguousarray(r.astype(np.uint32)),cam,stopped=True)
+        pad=np.ones((68*16,1920),dtype=bool); pad[:1080]=st[:1080,:1920]>0      # rows outside the image count as finished
+        _fin[mb]=pad.reshape(68*4,4,480,4).all(axis=(1,3))
+    return _fin[mb]
+def staging_g8(slack,drop):
+    gb=tile*100000+batch
+    u,inv=np.unique(gb,return_inverse=True)
+    tot=0; s=0
+    for hy in range(2):
+        ls=[]
+        for by in range(2):
+            for bx in range(4):
+                m=touches(x0+4*bx,x0+4*bx+3,y0+8*hy+4*by,y0+8*hy+4*by+3,slack)
+                if drop:
+                    br=ty*4+hy*2+by; bc=tx*4+bx
+                    dead=np.zeros(D,dtype=bool)
+                    for mb in range(1,int(batch.max())+1):
+                        sel=batch==mb
+                        dead[sel]=finished_at(mb)[br[sel],bc[sel]]
+                    m=m&~dead
+                tot+=m.sum(); ls.append(np.bincount(inv,weights=m,minlength=len(u)))
+        s+=np.maximum.reduce(ls).sum()
+    return int(tot),int(s)
+if ARGS.staging_table:
+    print('| block threshold slack | finished blocks | block entries | wave-steps |')
+    for slack in (0.1,0.01,0.0):
+        for drop in (False,True):
+            e,s=staging_g8(slack,drop)
+            print('| %g | %s | %d | %d |'%(slack,'left off' if drop else 'staged',e,s),flush=True)
+    sys.exit(0)
 gid=tile*1000+batch   # (tile,batch) group id
 def grp_sum(mask):
     u,inv=np.unique(gid,return_inverse=True); return np.bincount(inv,weights=mask,minlength=len(u))
@@ -100,3 +151,6 @@ for qy in range(2):
     for qx in range(2):
         m=q[(qy,qx)]; per_wave=grp(m,wv)
         print('quadrant',(qy,qx),'pass rate %.3f'%m.mean(),' staging waves with an empty ballot %.3f'%(per_wave==0).mean())
+if ARGS.drop_finished:
+    e,s=staging_g8(ARGS.slack,True)
+    print('4x4 (G=8), batch 128, slack %g, finished blocks left off: block entries %d wave-steps %d'%(ARGS.slack,e,s))

@@ -3462,13 +3462,37 @@ __device__ __forceinline__ float gs_exp(float x) {
 // the splat centre to a pixel centre of the tile, 5 u = 3e-7; the cull's own evaluation of the block
 // maximum errs by as much again.  A constant 0.1 (rounds 1-2) is enough for ordinary splats only: an
 // 8K frame with an 800-px needle lost threshold-level pixels against the oracle (round 3).  The
-// threshold handed to the block tests is therefore  pmin - 0.1 - 2 * 3e-7 * (|ca|+|cb|+|cc|) * D^2.
+// threshold handed to k_blend's half-tile test is therefore  pmin - 0.1 - slack, slack = K (|ca|+|cb|+|cc|) D^2.
+//
+// The block tests of k_blend_grouped (Splat, Ellipse) take  pmin - slack  with no constant; K = 9e-7 = 15.1 u is what
+// the count below needs (it was 6e-7 = 10 u beside the 0.1; the count asks for 14 u).  Write u = 2^-24, B = |ca|+|cb|+|cc|,
+// everything to first order in u (the second-order terms are u times smaller: the 1.1 u left over hold them and the
+// rounding of the slack's own six operations), code compiled without contraction, an fma where one is written.
+// Offsets below 2^22 pixels: tile origins + 0.5 + 4 c + 3 are exact, and the sign of a rounded difference is exact.
+//  (a) pixel loop, GS_BLEND_STEP: dx, dy one rounding each; power = fma(ca dx, dx, fma(cc dy, dy, (cb dx) dy)).
+//      Relative roundings met by  ca dx^2: 2 (dx) + 1 (ca dx) + 1 (outer fma) = 4;  cb dx dy: 2 + 1 + 1 (product) +
+//      1 (inner fma) + 1 (outer) = 6;  cc dy^2: 2 + 1 + 1 + 1 = 5.  |power_fl - power| <= 6 u S, S = |ca| dx^2 +
+//      |cb dx dy| + |cc| dy^2 <= B D^2.
+//  (b) block test: along the facing vertical edge P(t) = cc t^2 + (cb dn) t + ca dn^2, t in [lo, hi], true maximum at
+//      t* = clamp(topt).  dn, lo, hi: one rounding each; q1 = cb dn: 2; q0 = (ca dn) dn: 4; the value is
+//      fma(fma(cc, tv, q1), tv, q0): cc tv^2 meets 2 more roundings, q1 tv 2, q0 1 -> at most 5 u S' off P(tv),
+//      S' = S at (dn, tv).  Where tv is evaluated: tv = med3(topt_fl, lo_fl, hi_fl).  Interior optimum: P' = 0 there,
+//      so the error of topt_fl (two products and the 1-ulp rcp: relative 5 u; anything below 1e-4 would do) costs
+//      |cc| topt^2 (5 u)^2: second order.  Optimum at or beyond an end: tv is that end moved by u |end|, which moves P by
+//      at most |2 cc t + cb dn| u |t| <= 2 u S'.  (An optimum within 6 u of an end may land on either side: P' is then
+//      O(u) itself.)  The same along the facing horizontal edge with ca and cc exchanged; the larger of the two values is
+//      compared.  So the test's maximum is at least the true maximum over the block - 7 u S', S' <= B D^2, and
+//      the true maximum over the rectangle of pixel centres is at least every pixel's exact power.
+//  (c) thr = fl(pmin' - slack): one rounding, <= u (|pmin'| + slack); a pixel that passes has |pmin| <= |power_fl| <=
+//      S (1 + 6 u), so this is <= 1 u B D^2 as well.  (Ellipse: pmin' = pmin - 1e-3 |pmin| only lowers it further.)
+//  A pixel of the block with power_fl >= pmin therefore gives a test maximum >= pmin - (6 + 7 + 1) u B D^2 >= thr:
+//  the block is kept.  D is the largest |offset| to a pixel centre of the TILE, so it serves every block of it.
 __device__ __forceinline__ float cull_rounding_slack(float mx, float my, float ca, float cb, float cc, float x0,
                                                      float y0) {
     const float ax = fmaxf(fabsf(mx - x0), fabsf(mx - (x0 + 15.0f)));
     const float ay = fmaxf(fabsf(my - y0), fabsf(my - (y0 + 15.0f)));
     const float d = fmaxf(ax, ay);
-    return (6.0e-7f * ((fabsf(ca) + fabsf(cb)) + fabsf(cc))) * (d * d);
+    return (9.0e-7f * ((fabsf(ca) + fabsf(cb)) + fabsf(cc))) * (d * d);
 }
 
 // Maximum over t in [lo, hi] of the concave parabola q2*t^2 + q1*t + q0 (q2 < 0).  Used only by
@@ -3986,8 +4010,8 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 float pmin;
                 if constexpr (MODE == 0) pmin = fmaxf(-__logf(255.0f * u2f(r1.y)) - 1.0e-3f, -5.6f);
                 else pmin = fc.ellipse_pmin;
-                thr = (MODE == 0 ? pmin - 0.1f : pmin - 0.1f - 1.0e-3f * fabsf(pmin)) -
-                      cull_rounding_slack(mx, my, ca, cb, cc, tx0, ty0);
+                // no constant below pmin: cull_rounding_slack is the whole rounding bound (derived there)
+                thr = (MODE == 0 ? pmin : pmin - 1.0e-3f * fabsf(pmin)) - cull_rounding_slack(mx, my, ca, cb, cc, tx0, ty0);
                 *(float4 *)(s_rec + tid * (RS / 4)) = make_float4(mx, my, ca, cb);
                 *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(cc, pmin, u2f(r1.y), u2f(r1.z));
                 if constexpr (AUX)
