@@ -481,6 +481,10 @@ extern "C" {
     pub fn gs_select_attribute(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, a: *const gs_attribute_desc, lo: f32, hi: f32, op: u32) -> gs_status;
     pub fn gs_gaussians_buffer_neighbor_counts(g: *mut gs_gaussians_buffer, s: *mut gs_stream, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, cap: u32, counts_out: *mut gs_buffer) -> gs_status;
     pub fn gs_select_neighbors(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, min_count: u32, max_count: u32, op: u32) -> gs_status;
+    pub fn gs_layout_convertible(src_sh: u32, src_cov: u32, dst_sh: u32, dst_cov: u32) -> i32;
+    pub fn gs_convert_pods(src_sh: u32, src_cov: u32, dst_sh: u32, dst_cov: u32, pods: *const c_void, n: usize, out: *mut c_void) -> gs_status;
+    pub fn gs_gaussians_buffer_create_converted(src: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, dst_sh: u32, dst_cov: u32, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
+    pub fn gs_gaussians_buffer_create_concat_as(s: *mut gs_stream, srcs: *const *mut gs_gaussians_buffer, sels: *const *const gs_selection, count: u32, dst_sh: u32, dst_cov: u32, out: *mut *mut gs_gaussians_buffer, counts_out: *mut u64) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

@@ -1013,6 +1013,48 @@ gs_status gs_select_neighbors(gs_selection *sel, gs_stream *s, gs_gaussians_buff
                               const gs_model_transform_pod *model_transform, float radius, uint32_t min_count, uint32_t max_count,
                               gs_select_op op);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Layout conversion (no reference item in the core crate: a buffer of the      */
+/* reference keeps the layout it was uploaded with)                                             */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  convert((S, C) -> (S', C')) maps one record to one record.  Words 0..3
+ * (position, colour) are copied.  SH section: S' == S copies its words verbatim, pad included; otherwise each of the 45
+ * coefficients is decoded to binary32 as gs_unpack_to_gaussian does (f32: the bits; f16: exact; snorm8: (float)(int8) / 127
+ * clamped below at -1; none: +0) and encoded as gs_pack does (f16: round to nearest even; snorm8: truncation, NaN -> 0;
+ * none: no words), padding zero.  Cov section: C' == C verbatim; rot-scale -> f32 / f16 is gs_pack's arithmetic; f32 -> f16
+ * rounds each of the six words to nearest even; f16 -> f32 is exact; f32 or f16 -> rot-scale is NOT defined
+ * (GS_ERR_LOSSY_CONFIG).  Trailing pad words are zero.  Identical layouts keep every byte.  112 of the 144 pairs are defined.
+ * For a source that gs_unpack_to_gaussian accepts and pods that gs_pack produced, the result is
+ * gs_pack(dst, gs_unpack_to_gaussian(src)) bit for bit. */
+
+/* 1 when records of layout (src_sh, src_cov) convert to (dst_sh, dst_cov), else 0; 0 for an unknown enum value
+ * (no reference item) */
+int32_t gs_layout_convertible(gs_sh_config src_sh, gs_cov3d_config src_cov, gs_sh_config dst_sh, gs_cov3d_config dst_cov);
+/* Host only: converts n records (no reference item); `out` holds n x gs_pod_size(dst_sh, dst_cov) bytes and
+ * does not overlap `pods`.  The per-record function is the one the device kernel calls.  GS_ERR_LOSSY_CONFIG for a pair
+ * that is not defined, GS_ERR_INVALID_ARGUMENT for a null pointer or an unknown config; `out` is then untouched. */
+gs_status gs_convert_pods(gs_sh_config src_sh, gs_cov3d_config src_cov, gs_sh_config dst_sh, gs_cov3d_config dst_cov,
+                          const void *pods, size_t n, void *out);
+/* New buffer of layout (dst_sh, dst_cov) holding the converted records of `sel` (invert != 0: of its complement; NULL:
+ * all / none), caller order kept: the conversion is fused with the stable compaction (no reference item).
+ * Blocking, ordered and checked exactly like gs_gaussians_buffer_create_from_selection (behind an edit or restore enqueued
+ * on another stream); the result takes the source's spatial-order setting; *count_out (optional) = its length, and a count
+ * of 0 gives the valid length-0 buffer of the destination layout.  With identical layouts it IS that call.
+ * GS_ERR_LOSSY_CONFIG for a pair that is not defined, before anything is enqueued or allocated; GS_ERR_INVALID_ARGUMENT for
+ * a null argument, an unknown config, a selection whose length differs from the buffer's or that belongs to another
+ * device; *out is then NULL. */
+gs_status gs_gaussians_buffer_create_converted(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                               gs_sh_config dst_sh, gs_cov3d_config dst_cov, gs_gaussians_buffer **out,
+                                               uint64_t *count_out);
+/* gs_gaussians_buffer_create_concat in every respect (1..64 sources on one device, one blocking round trip for the counts,
+ * the copies only enqueued, ordering, counts_out, at most 2^32 - 16 records, the spatial-order setting of srcs[0]), but the
+ * sources may have ANY layouts: each is converted to (dst_sh, dst_cov), the layout of the new buffer (DESIGN.md 3.12;
+ * no reference item).  GS_ERR_LOSSY_CONFIG when a source cannot be converted: nothing is enqueued and *out = NULL. */
+gs_status gs_gaussians_buffer_create_concat_as(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
+                                               uint32_t count, gs_sh_config dst_sh, gs_cov3d_config dst_cov,
+                                               gs_gaussians_buffer **out, uint64_t *counts_out);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

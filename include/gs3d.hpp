@@ -319,6 +319,10 @@ class Snapshot {
     gs_snapshot *h_ = nullptr;
 };
 
+// tag of the GaussiansBuffer::concat overload that converts its sources to the target layout: concat(s, converted, {...})
+struct converted_t { explicit converted_t() = default; };
+inline constexpr converted_t converted{};
+
 template <class G>
 class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
   public:
@@ -361,6 +365,15 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // after the other; counts (optional) receives the records taken per source.  Blocks once, for the counts.
     static GaussiansBuffer concat(Stream &s, const std::vector<const GaussiansBuffer *> &srcs, const std::vector<const Selection *> &sels = {},
                                   std::vector<uint64_t> *counts = nullptr);
+    // layout conversion (gs3d.h gs_gaussians_buffer_create_converted / _create_concat_as; no reference item).
+    // convert<To>: a new buffer of layout To with the converted records of sel (nullptr: all; invert: of its complement),
+    // caller order kept; blocking.  concat(s, converted, ...): concat, but the sources may have any layouts (they are given
+    // as raw handles, b.raw(), since their types differ) and each is converted to G, the target layout.  LossyConfigError
+    // where a covariance would have to become rotation and scale (gs_layout_convertible).
+    template <class To>
+    GaussiansBuffer<To> convert(Stream &s, const Selection *sel = nullptr, bool invert = false) const;
+    static GaussiansBuffer concat(Stream &s, converted_t, const std::vector<gs_gaussians_buffer *> &srcs,
+                                  const std::vector<const Selection *> &sels = {}, std::vector<uint64_t> *counts = nullptr);
     // attribute statistics and histograms over the records of sel (nullptr: all) in one pass on the device (gs3d.h
     // gs_gaussians_buffer_stats / _histogram; no reference item); blocking.  mt == nullptr: the default
     // transform; ref == nullptr: the origin.  histogram: 2 x (bins + 3) counts, row 0 = the selection, row 1 = the others.
@@ -373,6 +386,7 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
                          const gs_model_transform_pod *mt = nullptr);
     gs_gaussians_buffer *raw() const { return h_; }
   private:
+    template <class> friend class GaussiansBuffer;      // convert<To> builds a buffer of another layout
     GaussiansBuffer() = default;
     gs_gaussians_buffer *h_ = nullptr;
 };
@@ -438,6 +452,26 @@ inline GaussiansBuffer<G> GaussiansBuffer<G>::concat(Stream &s, const std::vecto
     GaussiansBuffer b;
     check(gs_gaussians_buffer_create_concat(s.raw(), g.data(), m.empty() ? nullptr : m.data(), (uint32_t)g.size(), &b.h_,
                                             counts ? counts->data() : nullptr));
+    return b;
+}
+
+template <class G>
+template <class To>
+inline GaussiansBuffer<To> GaussiansBuffer<G>::convert(Stream &s, const Selection *sel, bool invert) const {
+    GaussiansBuffer<To> b;
+    check(gs_gaussians_buffer_create_converted(h_, s.raw(), sel ? sel->raw() : nullptr, invert ? 1 : 0, To::sh, To::cov3d, &b.h_, nullptr));
+    return b;
+}
+template <class G>
+inline GaussiansBuffer<G> GaussiansBuffer<G>::concat(Stream &s, converted_t, const std::vector<gs_gaussians_buffer *> &srcs,
+                                                          const std::vector<const Selection *> &sels, std::vector<uint64_t> *counts) {
+    if (!sels.empty() && sels.size() != srcs.size()) throw std::invalid_argument("concat: one selection per source, or none");
+    std::vector<const gs_selection *> m;
+    for (auto *x : sels) m.push_back(x ? x->raw() : nullptr);
+    if (counts) counts->assign(srcs.size(), 0);
+    GaussiansBuffer b;
+    check(gs_gaussians_buffer_create_concat_as(s.raw(), srcs.data(), m.empty() ? nullptr : m.data(), (uint32_t)srcs.size(), G::sh, G::cov3d,
+                                               &b.h_, counts ? counts->data() : nullptr));
     return b;
 }
 

@@ -215,6 +215,26 @@ class GaussianPod:
         _check(_L.gs_unpack_to_gaussian(self.sh, self.cov, _ptr(pods), n, _ptr(out)))
         return out
 
+    def convertible_to(self, other):
+        """gs_layout_convertible: can records of this layout be converted to `other`?  Every pair but
+        those that would turn a covariance back into rotation and scale."""
+        if not isinstance(other, GaussianPod):
+            raise TypeError("other must be a GaussianPod, not %s" % type(other).__name__)
+        return bool(_L.gs_layout_convertible(self.sh, self.cov, other.sh, other.cov))
+
+    def convert(self, pods, to):
+        """gs_convert_pods: packed records of this layout -> packed records of layout `to`, on the host,
+        with the per-record function the device kernel calls.  Raises LossyConfigError for a pair that is not defined."""
+        if not isinstance(to, GaussianPod):
+            raise TypeError("to must be a GaussianPod, not %s" % type(to).__name__)
+        pods = np.ascontiguousarray(pods, dtype=np.uint8).reshape(-1)
+        if pods.size % self.size:
+            raise ValueError("%d bytes are no whole number of %d-byte records" % (pods.size, self.size))
+        n = pods.size // self.size
+        out = np.zeros(max(n * to.size, 1), dtype=np.uint8)
+        _check(_L.gs_convert_pods(self.sh, self.cov, to.sh, to.cov, _ptr(pods) if n else _ptr(out), n, _ptr(out)))
+        return out[:n * to.size]
+
     def __repr__(self):
         return self.name
 
@@ -889,6 +909,22 @@ class GaussiansBuffer:
         assert out.len() == count.value
         return out
 
+    def convert(self, stream, pod, selection=None, invert=False):
+        """gs_gaussians_buffer_create_converted: a new GaussiansBuffer of layout `pod` with the converted
+        records of `selection` (None: all; invert: of its complement) in caller order — extract() and the conversion in one
+        pass on the device.  Blocking.  Raises LossyConfigError where pod.convertible_to is False."""
+        if not isinstance(pod, GaussianPod):
+            raise TypeError("pod must be a GaussianPod, not %s" % type(pod).__name__)
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        h, count = C.c_void_p(), C.c_uint64()
+        _check(_L.gs_gaussians_buffer_create_converted(self._h, stream._h if stream is not None else None,
+                                                       selection._h if selection is not None else None,
+                                                       int(bool(invert)), pod.sh, pod.cov, C.byref(h), C.byref(count)))
+        out = GaussiansBuffer(self.device, pod, h)
+        assert out.len() == count.value
+        return out
+
     def snapshot(self, stream, selection=None):
         """gs_gaussians_buffer_snapshot: a Snapshot of the records of `selection` (None: all), the undo
         entry of an edit.  Blocking (the host sizes the allocation from the count); the snapshot keeps its own mask."""
@@ -911,10 +947,14 @@ class GaussiansBuffer:
                                               int(bool(exchange))))
 
     @staticmethod
-    def concat(stream, buffers, selections=None):
+    def concat(stream, buffers, selections=None, pod=None):
         """gs_gaussians_buffer_create_concat: (a new GaussiansBuffer with the records of selections[i] of buffers[i], one
         source after the other in caller order, counts per source).  selections=None, or None for a source: all of it.
-        The same buffer may be given more than once.  Blocks once, for the counts; the copies are enqueued on the stream."""
+        The same buffer may be given more than once.  Blocks once, for the counts; the copies are enqueued on the stream.
+        pod=None: the sources share one layout.  pod=a GaussianPod: gs_gaussians_buffer_create_concat_as — the sources may
+        have any layouts and each is converted to `pod`; LossyConfigError if one cannot be."""
+        if pod is not None and not isinstance(pod, GaussianPod):
+            raise TypeError("pod must be a GaussianPod or None, not %s" % type(pod).__name__)
         buffers = list(buffers)
         for b in buffers:
             if not isinstance(b, GaussiansBuffer):
@@ -929,9 +969,13 @@ class GaussiansBuffer:
         src = (C.c_void_p * k)(*[b._h for b in buffers])
         sel = (C.c_void_p * k)(*[x._h if x is not None else None for x in sels])
         counts, h = (C.c_uint64 * k)(), C.c_void_p()
-        _check(_L.gs_gaussians_buffer_create_concat(stream._h if stream is not None else None, src, sel, k, C.byref(h), counts))
+        st = stream._h if stream is not None else None
+        if pod is None:
+            _check(_L.gs_gaussians_buffer_create_concat(st, src, sel, k, C.byref(h), counts))
+        else:
+            _check(_L.gs_gaussians_buffer_create_concat_as(st, src, sel, k, pod.sh, pod.cov, C.byref(h), counts))
         # (no buffer, more than 64, or two layouts: the library's GS_ERR_INVALID_ARGUMENT above)
-        return GaussiansBuffer(buffers[0].device, buffers[0].pod, h), [int(c) for c in counts]
+        return GaussiansBuffer(buffers[0].device, buffers[0].pod if pod is None else pod, h), [int(c) for c in counts]
 
     def stats(self, stream, selection=None, model_transform=None, ref=(0.0, 0.0, 0.0)):
         """gs_gaussians_buffer_stats: a GaussianStats — count and, for each of the nine ATTR_*, the number

@@ -255,6 +255,10 @@ SIGNATURES = {
     "gs_select_attribute": (i32, [vp, vp, vp, vp, f32, f32, i32]),
     "gs_gaussians_buffer_neighbor_counts": (i32, [vp, vp, vp, vp, f32, u32, vp]),
     "gs_select_neighbors": (i32, [vp, vp, vp, vp, vp, f32, u32, u32, i32]),
+    "gs_layout_convertible": (i32, [i32, i32, i32, i32]),
+    "gs_convert_pods": (i32, [i32, i32, i32, i32, vp, sz, vp]),
+    "gs_gaussians_buffer_create_converted": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "gs_gaussians_buffer_create_concat_as": (i32, [vp, vp, vp, u32, i32, i32, vp, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

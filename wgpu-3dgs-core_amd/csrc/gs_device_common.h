@@ -1,8 +1,9 @@
-// gs_device_common.h — what the kernel headers of the render, pack, select, edit, stats and neighbour units share beyond
+// gs_device_common.h — what the kernel headers of the render, pack, select, edit, relayout, stats and neighbour units share beyond
 // gs_kernel_lib.h (gs_bundle_kernels.h needs only that one): WAVE and PLANAR_BLOCK, the wave / block primitives,
 // attr_finite, the selection-mask helpers (SEL_*, sel_apply, SelectShape, wave_selection_mask) and the two scalar encoders
 // that both the pack kernels and the edit kernel use.  It holds no kernel: every *_kernels.h is included by exactly one
-// translation unit of the library, this header by six of them.
+// translation unit of the library — but gs_pack_kernels.h, whose per-record functions the relayout unit
+// shares with gs_core.hip — this header by seven of them.
 #pragma once
 
 #include "gs_kernel_lib.h"
@@ -131,6 +132,14 @@ __device__ __forceinline__ uint64_t wave_selection_mask(const uint32_t *__restri
     const uint32_t w = i0 >> 5;
     const uint64_t lo = words[w], hi = i0 + 32u < n ? words[w + 1u] : 0u;
     return lo | (hi << 32);
+}
+
+// word `w` of the mask that an extraction copies (gs_edit_kernels.h, gs_relayout_kernels.h): the selection (null: all), inverted if asked, bits >= n cleared
+__device__ __forceinline__ uint32_t extract_word(const uint32_t *__restrict__ words, uint32_t w, uint32_t n, uint32_t invert) {
+    if (w * 32u >= n) return 0u;
+    const uint32_t valid = n - w * 32u >= 32u ? 0xffffffffu : (1u << (n - w * 32u)) - 1u;
+    const uint32_t v = words ? words[w] : 0xffffffffu;
+    return (invert ? ~v : v) & valid;
 }
 
 // ---------------------------------------------------------------------------------------------

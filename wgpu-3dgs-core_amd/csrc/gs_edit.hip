@@ -1,5 +1,5 @@
 // gs_edit.hip — the write side of the device editor: SH rotation matrices, edits of the selected Gaussians, extraction
-// (DESIGN.md §3.8), snapshots, restore and concatenation (§3.9).  Kernels: gs_edit_kernels.h.
+// (DESIGN.md §3.8), snapshots and restore (§3.9; the concatenation's body is gs_relayout.hip's).  Kernels: gs_edit_kernels.h.
 #include "gs_host.h"
 
 #include "gs_edit_kernels.h"
@@ -164,7 +164,7 @@ extern "C" gs_status gs_gaussians_buffer_edit(gs_gaussians_buffer *g, gs_stream 
 // A buffer of `len` > 0 records for a copy that writes every byte of it: allocated WITHOUT the zero fill of
 // gs_buffer_create: that hipMemset runs on the null stream, which the copy's stream is not ordered behind, and would race
 // with the copy.
-static gs_status gaussians_buffer_create_unfilled(gs_device *dev, int sh, int cov, size_t len, gs_gaussians_buffer **out) {
+gs_status gsh::gaussians_buffer_create_unfilled(gs_device *dev, int sh, int cov, size_t len, gs_gaussians_buffer **out) {
     void *p = nullptr;
     const size_t bytes = len * (size_t)gs::pod_bytes(sh, cov);
     GS_TRY(dev_alloc(&p, bytes, bytes, "hipMalloc"));
@@ -183,14 +183,14 @@ static gs_status gaussians_buffer_create_unfilled(gs_device *dev, int sh, int co
 // of n > 0 bits are counted into `offsets`, scanned there in place (k_scan_chunks reads a value before it writes its
 // slot) and summed into *total_dev.  Only enqueued: gs_gaussians_buffer_create_concat fetches the totals of all its
 // sources in one round trip.
-static void extract_scan_enqueue(hipStream_t st, const uint32_t *words, uint32_t n, uint32_t invert, uint32_t *offsets, uint32_t *total_dev) {
+void gsh::extract_scan_enqueue(hipStream_t st, const uint32_t *words, uint32_t n, uint32_t invert, uint32_t *offsets, uint32_t *total_dev) {
     const uint32_t nblocks = (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
     hipLaunchKernelGGL(gs::k_extract_block_counts, dim3((nblocks * 32u + 255u) / 256u), dim3(256), 0, st, words, n, invert, nblocks, offsets);
     scan_chunks_enqueue(st, offsets, offsets, total_dev, nblocks);
 }
 
 // ... and its total on the host, which sizing the destination needs: blocks on `st`
-static gs_status extract_scan(hipStream_t st, const uint32_t *words, uint32_t n, uint32_t invert, uint32_t *offsets, uint32_t *total_dev,
+gs_status gsh::extract_scan(hipStream_t st, const uint32_t *words, uint32_t n, uint32_t invert, uint32_t *offsets, uint32_t *total_dev,
                               uint32_t *total) {
     extract_scan_enqueue(st, words, n, invert, offsets, total_dev);
     hipError_t e = hipGetLastError();
@@ -202,7 +202,7 @@ static gs_status extract_scan(hipStream_t st, const uint32_t *words, uint32_t n,
 }
 
 // the `total` records the scan counted: src (n records of nc 16-byte chunks) -> dst, packed in index order
-static void extract_copy_enqueue(hipStream_t st, const void *src, void *dst, const uint32_t *words, uint32_t n, uint32_t invert,
+void gsh::extract_copy_enqueue(hipStream_t st, const void *src, void *dst, const uint32_t *words, uint32_t n, uint32_t invert,
                                  const uint32_t *offsets, uint32_t nc, uint32_t total) {
     hipLaunchKernelGGL(gs::k_extract_copy, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)src, (uint4 *)dst, words, n, invert,
                        offsets, nc, total);
@@ -374,94 +374,8 @@ extern "C" gs_status gs_gaussians_buffer_restore(gs_gaussians_buffer *g, gs_stre
     return GS_OK;
 }
 
+// (the body is shared with gs_gaussians_buffer_create_concat_as: gs_relayout.hip)
 extern "C" gs_status gs_gaussians_buffer_create_concat(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
                                                        uint32_t count, gs_gaussians_buffer **out, uint64_t *counts_out) {
-    if (out) *out = nullptr;
-    if (!srcs || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    if (count < 1u || count > 64u) return gs_fail(GS_ERR_INVALID_ARGUMENT, count, 0, 0, "a concatenation takes 1 to 64 sources, not %u", (unsigned)count);
-    if (counts_out) std::memset(counts_out, 0, (size_t)count * sizeof(uint64_t));
-    size_t nblocks_all = 0;
-    for (uint32_t i = 0; i < count; i++) {
-        const gs_gaussians_buffer *g = srcs[i];
-        if (!g) return gs_fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "source %u is null", (unsigned)i);
-        if (g->buf->dev != srcs[0]->buf->dev) return gs_fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "objects belong to different devices");
-        if (g->sh != srcs[0]->sh || g->cov != srcs[0]->cov)
-            return gs_fail(GS_ERR_INVALID_ARGUMENT, i, 0, 0, "source %u has another layout than source 0", (unsigned)i);
-        GS_TRY(check_buffer_selection(g, s, sels ? sels[i] : nullptr));
-        const size_t len = gs_gaussians_buffer_len(g);
-        GS_TRY(check_len32(len));
-        nblocks_all += (len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK;
-    }
-    gs_device *dev = srcs[0]->buf->dev;
-    const int sh = srcs[0]->sh, cov = srcs[0]->cov;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // one array for all sources: the per-block offsets of source i from block0[i] on, then one total per source
-    uint32_t *scan = nullptr;
-    GS_TRY(dev_alloc((void **)&scan, (nblocks_all + 64) * 4, 0, "hipMalloc"));
-    uint32_t *totals_dev = scan + nblocks_all;
-    uint32_t totals[64] = {};
-    size_t block0[64] = {};
-    gs_status rc = GS_OK;
-    hipError_t e = hipMemsetAsync(totals_dev, 0, 64 * 4, st);
-    size_t b0 = 0;
-    for (uint32_t i = 0; i < count && e == hipSuccess && rc == GS_OK; i++) {
-        gs_gaussians_buffer *g = srcs[i];
-        const uint32_t n = (uint32_t)gs_gaussians_buffer_len(g);
-        block0[i] = b0;
-        b0 += (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
-        if (!n) continue;
-        rc = wait_for_edits(g, st);
-        if (rc != GS_OK) break;
-        extract_scan_enqueue(st, sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr, n, 0u, scan + block0[i], totals_dev + i);
-        e = hipGetLastError();
-    }
-    // sizing the new buffer needs the totals on the host: the one round trip of the call
-    if (rc == GS_OK && e == hipSuccess) e = hipMemcpyAsync(totals, totals_dev, (size_t)count * 4, hipMemcpyDeviceToHost, st);
-    if (rc == GS_OK && e == hipSuccess) e = hipStreamSynchronize(st);
-    uint64_t total = 0;
-    if (rc == GS_OK && e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
-    for (uint32_t i = 0; i < count && rc == GS_OK; i++) {
-        const size_t len = gs_gaussians_buffer_len(srcs[i]);
-        if (totals[i] > len) rc = gs_fail(GS_ERR_HIP, totals[i], len, 0, "selection scan returned %u of %zu Gaussians", totals[i], len);
-        total += totals[i];
-    }
-    if (rc == GS_OK && total > 0xfffffff0ull)
-        rc = gs_fail(GS_ERR_INVALID_ARGUMENT, total, 0, 0, "the concatenation would hold %llu Gaussians", (unsigned long long)total);
-    gs_gaussians_buffer *dst = nullptr;
-    if (rc == GS_OK && total) rc = gaussians_buffer_create_unfilled(dev, sh, cov, (size_t)total, &dst);
-    else if (rc == GS_OK) rc = gs_gaussians_buffer_create(dev, (gs_sh_config)sh, (gs_cov3d_config)cov, nullptr, 0, &dst);
-    if (rc == GS_OK && total) {
-        const uint32_t nc = (uint32_t)(pod_stride(dst) / 16);
-        uint64_t first = 0;      // where the part of source i starts in the new buffer
-        for (uint32_t i = 0; i < count; i++) {
-            if (!totals[i]) continue;
-            const uint32_t n = (uint32_t)gs_gaussians_buffer_len(srcs[i]);
-            const uint32_t *words = sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr;
-            // k_extract_copy stays inside `total` records from its destination pointer: the part of this source
-            extract_copy_enqueue(st, srcs[i]->buf->ptr, (uint4 *)dst->buf->ptr + first * nc, words, n, 0u, scan + block0[i], nc, totals[i]);
-            first += totals[i];
-        }
-        // The copies are only enqueued: the call has blocked once, for the totals.  The new buffer is ordered like an edited
-        // one (frames, snapshots and extractions on other streams wait for the copies) and keeps the offsets they read.
-        e = hipGetLastError();
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "concatenation failed: %s", hipGetErrorString(e));
-        else rc = record_edit(dst, st);
-        if (rc != GS_OK) {
-            (void)hipStreamSynchronize(st);
-        } else {
-            dst->concat_offsets = scan;
-            scan = nullptr;
-        }
-    }
-    if (scan) (void)hipFree(scan);
-    if (rc != GS_OK) {
-        if (dst) gs_gaussians_buffer_destroy(dst);
-        return rc;
-    }
-    dst->spatial = srcs[0]->spatial;
-    *out = dst;
-    if (counts_out)
-        for (uint32_t i = 0; i < count; i++) counts_out[i] = totals[i];
-    return GS_OK;
+    return concat_records(s, srcs, sels, count, false, 0, 0, out, counts_out);
 }

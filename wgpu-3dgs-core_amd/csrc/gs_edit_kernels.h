@@ -169,13 +169,7 @@ __global__ __launch_bounds__(256) void k_edit(uint4 *__restrict__ aos, uint32_t 
 
 // ---- extraction: per-block counts -> k_scan_chunks -> stable copy ------------------------------------------------
 
-// word `w` of the mask that the extraction copies: the selection (null: all), inverted if asked, bits >= n cleared
-__device__ __forceinline__ uint32_t extract_word(const uint32_t *__restrict__ words, uint32_t w, uint32_t n, uint32_t invert) {
-    if (w * 32u >= n) return 0u;
-    const uint32_t valid = n - w * 32u >= 32u ? 0xffffffffu : (1u << (n - w * 32u)) - 1u;
-    const uint32_t v = words ? words[w] : 0xffffffffu;
-    return (invert ? ~v : v) & valid;
-}
+// (extract_word, the mask word that an extraction copies: gs_device_common.h — the relayout unit locates records with it too)
 
 // counts[b] = selected Gaussians of the 1024-Gaussian block b (32 mask words): one thread per word, summed over the 32
 // lanes of a wave half.  nblocks * 32 threads do work; the grid is rounded up to whole workgroups.

@@ -210,4 +210,23 @@ gs_status selection_combine_words(gs_selection *dst, hipStream_t st, gs_select_o
 // k_sel_range: sel = sel op {i : start <= i < end} on `st`; sel->nwords > 0
 void sel_range_enqueue(gs_selection *sel, hipStream_t st, uint32_t start, uint32_t end, gs_select_op op);
 
+// ---- gs_edit.hip ----
+// a buffer of `len` > 0 records for a copy that writes every byte of it: allocated without the zero fill of gs_buffer_create
+gs_status gaussians_buffer_create_unfilled(gs_device *dev, int sh, int cov, size_t len, gs_gaussians_buffer **out);
+// the prelude of every extraction, on `st`: per-1024-block counts of the mask, scanned in place, summed into *total_dev
+void extract_scan_enqueue(hipStream_t st, const uint32_t *words, uint32_t n, uint32_t invert, uint32_t *offsets, uint32_t *total_dev);
+// ... and its total on the host: blocks on `st`
+gs_status extract_scan(hipStream_t st, const uint32_t *words, uint32_t n, uint32_t invert, uint32_t *offsets, uint32_t *total_dev,
+                       uint32_t *total);
+// k_extract_copy: the `total` records the scan counted, src (n records of nc 16-byte chunks) -> dst, packed in index order
+void extract_copy_enqueue(hipStream_t st, const void *src, void *dst, const uint32_t *words, uint32_t n, uint32_t invert,
+                          const uint32_t *offsets, uint32_t nc, uint32_t total);
+
+// ---- gs_relayout.hip ----
+// gs_gaussians_buffer_create_concat (as_layout false: the sources share one layout, which the result takes) and
+// gs_gaussians_buffer_create_concat_as (as_layout true: every source is converted to (dsh, dcov))
+gs_status concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels, uint32_t count, bool as_layout,
+                         int dsh, int dcov, gs_gaussians_buffer **out, uint64_t *counts_out);
+
+
 }  // namespace gsh

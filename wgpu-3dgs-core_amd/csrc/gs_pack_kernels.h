@@ -121,6 +121,98 @@ __host__ __device__ inline void unpack_words(int sh, const uint32_t *p, uint32_t
     for (int k = 0; k < 3; k++) g[GW_SCALE + k] = c[4 + k];
 }
 
+// Layout conversion (no reference item): which (src -> dst) pairs are defined.  The SH section converts
+// between any two configs; a covariance cannot go back to rotation + scale.
+__host__ __device__ constexpr bool layout_convertible(int ssh, int scov, int dsh, int dcov) {
+    return ssh >= 0 && ssh <= 3 && dsh >= 0 && dsh <= 3 && scov >= 0 && scov <= 2 && dcov >= 0 && dcov <= 2 &&
+           (dcov != COV_ROT_SCALE || scov == COV_ROT_SCALE);
+}
+
+// coefficient k of an SH section as binary32 bits: the decode of unpack_words (none: +0)
+__host__ __device__ inline uint32_t sh_coef_bits(int sh, const uint32_t *s, int k) {
+    if (sh == SH_SINGLE) return s[k];
+    if (sh == SH_HALF) return cv_f2u(cv_f16_to_f32((s[k >> 1] >> (16 * (k & 1))) & 0xffffu));
+    if (sh == SH_NORM8) {
+        const float v = (float)(int8_t)((s[k >> 2] >> (8 * (k & 3))) & 0xffu) / 127.0f;
+        return cv_f2u(v < -1.0f ? -1.0f : v);
+    }
+    return 0u;
+}
+
+// One POD of layout (ssh, scov) -> one POD of layout (dsh, dcov), DESIGN.md §3.12: words 0..3 copied; a section whose
+// config is kept is copied verbatim (pad included), otherwise decoded as unpack_words does and encoded as pack_words
+// does; every other pad word of the destination is zero.  Only for layout_convertible pairs of two DIFFERENT layouts, which
+// the callers check (identical layouts keep every byte, the trailing pad too: a copy).
+// Shared by the host path (gs_convert_pods) and the device kernel (k_convert_extract).  Every index is a constant after
+// unrolling (a run-time cov config only predicates): with constant SH configs and register arrays nothing is indexed
+// dynamically.
+__host__ __device__ inline void convert_words(int ssh, int scov, int dsh, int dcov, const uint32_t *p, uint32_t *o) {
+    for (int k = 0; k < 4; k++) o[k] = p[k];
+    const uint32_t *s = p + 4;
+    uint32_t *d = o + 4;
+    if (dsh == ssh) {
+        const int nw = sh_bytes(ssh) / 4;
+#pragma unroll
+        for (int k = 0; k < 45; k++)
+            if (k < nw) d[k] = s[k];
+    } else if (dsh == SH_SINGLE) {
+#pragma unroll
+        for (int k = 0; k < 45; k++) d[k] = sh_coef_bits(ssh, s, k);
+    } else if (dsh == SH_HALF) {
+#pragma unroll
+        for (int k = 0; k < 22; k++)
+            d[k] = (uint32_t)f32_to_f16_rtne_bits(sh_coef_bits(ssh, s, 2 * k)) |
+                   ((uint32_t)f32_to_f16_rtne_bits(sh_coef_bits(ssh, s, 2 * k + 1)) << 16);
+        d[22] = (uint32_t)f32_to_f16_rtne_bits(sh_coef_bits(ssh, s, 44));
+    } else if (dsh == SH_NORM8) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) {
+            uint32_t w = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (4 * k + j < 45) w |= sh_norm8_byte(cv_u2f(sh_coef_bits(ssh, s, 4 * k + j))) << (8 * j);
+            d[k] = w;
+        }
+    }
+    const uint32_t *c = p + cov_word0(ssh);
+    uint32_t *e = o + cov_word0(dsh);
+    // the cov section and the trailing pad are at most 10 words (28 bytes + 12): zero first, so that the pad is zero
+    const int ntail = pod_words(dsh, dcov) - cov_word0(dsh);
+#pragma unroll
+    for (int k = 0; k < 10; k++)
+        if (k < ntail) e[k] = 0u;
+    if (dcov == scov) {
+        const int ncw = cov_bytes(scov) / 4;
+#pragma unroll
+        for (int k = 0; k < 7; k++)
+            if (k < ncw) e[k] = c[k];
+    } else {
+        uint32_t c6[6];      // the six covariance terms as binary32 bits
+        if (scov == COV_ROT_SCALE) {
+            const float q[4] = {cv_u2f(c[0]), cv_u2f(c[1]), cv_u2f(c[2]), cv_u2f(c[3])};
+            const float sc[3] = {cv_u2f(c[4]), cv_u2f(c[5]), cv_u2f(c[6])};
+            float f6[6];
+            cov3d_from_rot_scale(q, sc, f6);
+#pragma unroll
+            for (int k = 0; k < 6; k++) c6[k] = cv_canon_nan_bits(f6[k]);
+        } else if (scov == COV_SINGLE) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) c6[k] = c[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; k++) c6[k] = cv_f2u(cv_f16_to_f32((c[k >> 1] >> (16 * (k & 1))) & 0xffffu));
+        }
+        if (dcov == COV_SINGLE) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) e[k] = c6[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                e[k] = (uint32_t)f32_to_f16_rtne_bits(c6[2 * k]) | ((uint32_t)f32_to_f16_rtne_bits(c6[2 * k + 1]) << 16);
+        }
+    }
+}
+
 // Device side of GaussiansBuffer::download::<Gaussian>: PODs -> struct Gaussian records, LDS-staged on
 // both sides like k_pack_pods (COV is RotScale by construction).
 template <int SH>
