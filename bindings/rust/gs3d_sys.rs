@@ -354,6 +354,7 @@ extern "C" {
     pub fn gs_ply_property_name(index: u32) -> *const c_char;
     pub fn gs_gaussian_from_ply(r#in: *const gs_ply_gaussian_pod, n: usize, out: *mut gs_gaussian);
     pub fn gs_expf(x: f32) -> f32;
+    pub fn gs_logf(x: f32) -> f32;
     pub fn gs_gaussian_to_ply(r#in: *const gs_gaussian, n: usize, out: *mut gs_ply_gaussian_pod);
     pub fn gs_ply_read(bytes: *const c_void, len: usize, out: *mut gs_ply_gaussian_pod, capacity: usize, count_out: *mut usize, is_inria_out: *mut i32) -> gs_status;
     pub fn gs_ply_write(pods: *const gs_ply_gaussian_pod, n: usize, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
@@ -485,6 +486,10 @@ extern "C" {
     pub fn gs_convert_pods(src_sh: u32, src_cov: u32, dst_sh: u32, dst_cov: u32, pods: *const c_void, n: usize, out: *mut c_void) -> gs_status;
     pub fn gs_gaussians_buffer_create_converted(src: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, dst_sh: u32, dst_cov: u32, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
     pub fn gs_gaussians_buffer_create_concat_as(s: *mut gs_stream, srcs: *const *mut gs_gaussians_buffer, sels: *const *const gs_selection, count: u32, dst_sh: u32, dst_cov: u32, out: *mut *mut gs_gaussians_buffer, counts_out: *mut u64) -> gs_status;
+    pub fn gs_gaussians_buffer_export_ply(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, out: *mut gs_ply_gaussian_pod, capacity: usize, count_out: *mut u64) -> gs_status;
+    pub fn gs_gaussians_buffer_export_spz_decompressed(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, options: *const gs_spz_options, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
+    pub fn gs_gaussians_buffer_export_spz(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, options: *const gs_spz_options, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
+    pub fn gs_gaussians_buffer_write(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, source: gs_gaussians_source, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

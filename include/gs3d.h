@@ -192,6 +192,11 @@ void gs_gaussian_from_ply(const gs_ply_gaussian_pod *in, size_t n, gs_gaussian *
  * table algorithm glibc's expf uses, restated so that the host path above and the device path
  * (gs_pack_device_from_ply) give the same bits (csrc/gs_convert.h). */
 float gs_expf(float x);
+/* The ln of Gaussian::to_ply / to_spz (f32::ln in the reference, src/gaussian.rs:100,105,254): the double-based table
+ * algorithm glibc's logf uses, restated so that the host paths (gs_gaussian_to_ply, gs_spz_encode_decompressed) and the device
+ * path (gs_gaussians_buffer_export_*) give the same bits (csrc/gs_convert.h).  Bit-equal to glibc 2.35's logf for every
+ * binary32 input: -inf for +-0, 0xffc00000 for a negative argument, the argument quieted for a NaN. */
+float gs_logf(float x);
 void gs_gaussian_to_ply(const gs_gaussian *in, size_t n, gs_ply_gaussian_pod *out);
 /* PlyGaussians::read_from — ply.rs:292-408.  Call with out == NULL to get the vertex count, then
  * with a buffer.  Handles the Inria fast path (one memcpy) and custom property orders in ascii /
@@ -1054,6 +1059,45 @@ gs_status gs_gaussians_buffer_create_converted(gs_gaussians_buffer *src, gs_stre
 gs_status gs_gaussians_buffer_create_concat_as(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
                                                uint32_t count, gs_sh_config dst_sh, gs_cov3d_config dst_cov,
                                                gs_gaussians_buffer **out, uint64_t *counts_out);
+
+/* ------------------------------------------------------------------------------------------ */
+/* Export (no reference item in the core crate: the reference downloads a       */
+/* buffer and encodes it on the host)                                                           */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  Each call below gives, byte for byte, what the host path gives for the
+ * same records: gs_gaussians_buffer_create_from_selection(sel, invert), gs_gaussians_buffer_download_gaussians, then
+ * gs_gaussian_to_ply / gs_spz_encode_decompressed / gs_spz_encode / gs_gaussians_write.  Extraction, decoding of the records and
+ * encoding run in one kernel on the device; the host receives records that are ready to write.
+ * Common to the four calls: `sel` selects the records (invert != 0: its complement; NULL: all / none), caller order kept.
+ * Blocking on `s` (NULL: the device's internal stream), ordered behind an edit, restore or concatenation enqueued on another
+ * stream.  out == NULL: only the selection is scanned and the count / size is returned (the gzip member of
+ * gs_gaussians_buffer_export_spz has to be built to be measured).  GS_ERR_INVALID_ARGUMENT, with `out` untouched, for a null
+ * buffer or count pointer, a capacity below the count / size, a selection whose length differs from the buffer's or that
+ * belongs to another device.  Only the layouts gs_gaussians_buffer_download_gaussians accepts (SH f32 / f16 / snorm8 with
+ * rotation + scale) can be exported; the others return its error, GS_ERR_LOSSY_CONFIG with the reference's message, before
+ * anything is enqueued. */
+
+/* Gaussian::to_ply of the selected records on the device (no reference item): *count_out = their number,
+ * `out` (capacity in records) receives them.  The source is walked in slices (2 Mi records; GS3D_EXPORT_SLICE=<records, a
+ * multiple of 1024> overrides) through two device staging buffers, ordered so that the kernel of one slice can run under the copy of the
+ * previous one.  GS_ERR_OUT_OF_MEMORY when the staging buffers cannot be allocated. */
+gs_status gs_gaussians_buffer_export_ply(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                         gs_ply_gaussian_pod *out, size_t capacity, uint64_t *count_out);
+/* gs_spz_encode_decompressed of the selected records on the device (no reference item): header and six
+ * columns, built in device memory (at most 16 + 65 bytes per record) and copied once.  options == NULL: gs_spz_options_default.
+ * capacity and *bytes_out in bytes.  The options are checked as gs_spz_encode_decompressed checks them. */
+gs_status gs_gaussians_buffer_export_spz_decompressed(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                                      const gs_spz_options *options, void *out, size_t capacity, size_t *bytes_out);
+/* ... and the gzip member around that payload, as gs_spz_encode writes it (gs_spz_compress: zlib on one host thread)
+ * (no reference item) */
+gs_status gs_gaussians_buffer_export_spz(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                         const gs_spz_options *options, void *out, size_t capacity, size_t *bytes_out);
+/* The complete file image gs_gaussians_write gives for the selected records (no reference item): for
+ * GS_SOURCE_PLY the header of gs_ply_write for their count with the vertices landing directly behind it, for GS_SOURCE_SPZ
+ * gs_gaussians_buffer_export_spz with the default options.  GS_SOURCE_INTERNAL fails as gs_gaussians_write does. */
+gs_status gs_gaussians_buffer_write(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                    gs_gaussians_source source, void *out, size_t capacity, size_t *bytes_out);
 
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,

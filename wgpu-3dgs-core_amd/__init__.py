@@ -334,6 +334,11 @@ def expf(x):
     return float(_L.gs_expf(float(x)))
 
 
+def logf(x):
+    """gs_logf: the ln of Gaussian::to_ply / to_spz on host and device (csrc/gs_convert.h)"""
+    return float(_L.gs_logf(float(x)))
+
+
 def gaussian_to_ply(gaussians):
     """Gaussian::to_ply"""
     g = np.ascontiguousarray(np.atleast_1d(gaussians), dtype=GAUSSIAN_DTYPE)
@@ -924,6 +929,60 @@ class GaussiansBuffer:
         out = GaussiansBuffer(self.device, pod, h)
         assert out.len() == count.value
         return out
+
+    def _export_args(self, stream, selection):
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        return self._h, stream._h if stream is not None else None, selection._h if selection is not None else None
+
+    def export_ply(self, stream, selection=None, invert=False):
+        """gs_gaussians_buffer_export_ply: the records of `selection` (None: all; invert: of its
+        complement) as PlyGaussians in caller order — extract(), download_gaussians() and gaussian_to_ply() in one kernel on
+        the device, byte-equal to them.  Blocking."""
+        head = self._export_args(stream, selection) + (int(bool(invert)),)
+        count = C.c_uint64()
+        _check(_L.gs_gaussians_buffer_export_ply(*head, None, 0, C.byref(count)))
+        pods = np.zeros(count.value, dtype=PLY_GAUSSIAN_DTYPE)
+        if count.value:
+            _check(_L.gs_gaussians_buffer_export_ply(*head, _ptr(pods), len(pods), C.byref(count)))
+        return PlyGaussians(pods[:count.value], True)
+
+    def export_spz(self, stream, selection=None, invert=False, options=None):
+        """gs_gaussians_buffer_export_spz_decompressed: the records of `selection` as SpzGaussians (None:
+        spz_options()), the columns encoded on the device — byte-equal to
+        SpzGaussians.from_gaussians_with_options(extract().download_gaussians(), options).  Blocking."""
+        if options is not None and not isinstance(options, _capi.SpzOptions):
+            raise TypeError("options must be spz_options(...) or None, not %s" % type(options).__name__)
+        head = self._export_args(stream, selection) + (int(bool(invert)), C.byref(options) if options is not None else None)
+        return SpzGaussians(_sized_call(_L.gs_gaussians_buffer_export_spz_decompressed, *head))
+
+    def write(self, stream, source, selection=None, invert=False):
+        """gs_gaussians_buffer_write: the complete file image of the records of `selection` as bytes —
+        GaussiansSource.Ply: header + vertices; GaussiansSource.Spz: the gzip member, default options.  Blocking."""
+        if source == GaussiansSource.Internal:
+            raise ValueError("cannot write Internal Gaussians to buffer")
+        if source not in (GaussiansSource.Ply, GaussiansSource.Spz):
+            raise TypeError("source must be GaussiansSource.Ply or GaussiansSource.Spz, not %r" % (source,))
+        args = self._export_args(stream, selection) + (int(bool(invert)),)
+        head = args + (1 if source == GaussiansSource.Ply else 2,)
+        if source == GaussiansSource.Spz:
+            # A size query of the gzip member has to build it: ask for the size of the payload instead (the scan alone) and
+            # call once with room for it plus deflate's worst case; a member that is larger still goes the two-call way.
+            n = C.c_size_t()
+            _check(_L.gs_gaussians_buffer_export_spz_decompressed(*args, None, None, 0, C.byref(n)))
+            out = np.empty(n.value + n.value // 8 + 1024, dtype=np.uint8)
+            status = _L.gs_gaussians_buffer_write(*head, _ptr(out), out.size, C.byref(n))
+            if status == 0 or n.value <= out.size:
+                _check(status)
+                return out[:n.value].tobytes()
+        return _sized_call(_L.gs_gaussians_buffer_write, *head)
+
+    def write_to_file(self, path, stream=None, selection=None, invert=False):
+        """write() into a file; the format follows the suffix: .spz is SPZ, everything else PLY"""
+        source = GaussiansSource.Spz if str(path).lower().endswith(".spz") else GaussiansSource.Ply
+        data = self.write(stream, source, selection, invert)
+        with open(path, "wb") as f:
+            f.write(data)
 
     def snapshot(self, stream, selection=None):
         """gs_gaussians_buffer_snapshot: a Snapshot of the records of `selection` (None: all), the undo

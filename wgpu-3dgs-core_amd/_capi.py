@@ -129,6 +129,7 @@ SIGNATURES = {
     "gs_gaussian_from_ply": (None, [vp, sz, vp]),
     "gs_gaussian_to_ply": (None, [vp, sz, vp]),
     "gs_expf": (f32, [f32]),
+    "gs_logf": (f32, [f32]),
     "gs_ply_read": (i32, [vp, sz, vp, sz, vp, vp]),
     "gs_ply_write": (i32, [vp, sz, vp, sz, vp]),
     "gs_spz_options_default": (None, [vp]),
@@ -259,6 +260,10 @@ SIGNATURES = {
     "gs_convert_pods": (i32, [i32, i32, i32, i32, vp, sz, vp]),
     "gs_gaussians_buffer_create_converted": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     "gs_gaussians_buffer_create_concat_as": (i32, [vp, vp, vp, u32, i32, i32, vp, vp]),
+    "gs_gaussians_buffer_export_ply": (i32, [vp, vp, vp, i32, vp, sz, vp]),
+    "gs_gaussians_buffer_export_spz_decompressed": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
+    "gs_gaussians_buffer_export_spz": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
+    "gs_gaussians_buffer_write": (i32, [vp, vp, vp, i32, i32, vp, sz, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

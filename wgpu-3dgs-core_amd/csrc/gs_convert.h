@@ -23,6 +23,12 @@
 #else
 #define GS_HD
 #endif
+// loops whose indices must be constants where the arrays are a kernel's registers
+#if defined(__clang__)
+#define GS_UNROLL _Pragma("unroll")
+#else
+#define GS_UNROLL
+#endif
 
 namespace gs {
 
@@ -94,6 +100,56 @@ GS_HD inline float gs_expf(float x) {
     double y = c2 * r + 1.0;
     y = p * r2 + y;
     y = y * s;
+    return (float)y;
+}
+
+// log: the reference calls f32::ln (gaussian.rs:100,105,254), glibc's logf — Szabolcs Nagy's logf from ARM
+// optimized-routines (math/logf.c, math/logf_data.c; LOGF_TABLE_BITS = 4): x = 2^k z with z in [0x1.66p-1, 0x1.66p0),
+// c = the centre of z's sixteenth of that interval, log x = log(z / c) + log c + k ln 2 with a cubic in r = z / c - 1,
+// evaluated in DOUBLE and rounded to binary32 once.  As gs_expf: IEEE double +, * and conversions only, written without
+// contraction, so host and device agree bit for bit.
+GS_HD inline double logf_invc(uint32_t i) {
+    const double T[16] = {0x1.661ec79f8f3bep+0, 0x1.571ed4aaf883dp+0, 0x1.49539f0f010bp+0,  0x1.3c995b0b80385p+0,
+                          0x1.30d190c8864a5p+0, 0x1.25e227b0b8eap+0,  0x1.1bb4a4a1a343fp+0, 0x1.12358f08ae5bap+0,
+                          0x1.0953f419900a7p+0, 0x1p+0,               0x1.e608cfd9a47acp-1, 0x1.ca4b31f026aap-1,
+                          0x1.b2036576afce6p-1, 0x1.9c2d163a1aa2dp-1, 0x1.886e6037841edp-1, 0x1.767dcf5534862p-1};
+    return T[i & 15u];
+}
+GS_HD inline double logf_logc(uint32_t i) {
+    const double T[16] = {-0x1.57bf7808caadep-2, -0x1.2bef0a7c06ddbp-2, -0x1.01eae7f513a67p-2, -0x1.b31d8a68224e9p-3,
+                          -0x1.6574f0ac07758p-3, -0x1.1aa2bc79c81p-3,   -0x1.a4e76ce8c0e5ep-4, -0x1.1973c5a611cccp-4,
+                          -0x1.252f438e10c1ep-5, 0.0,                   0x1.aa5aa5df25984p-5,  0x1.c5e53aa362eb4p-4,
+                          0x1.526e57720db08p-3,  0x1.bc2860d22477p-3,   0x1.1058bc8a07ee1p-2,  0x1.4043057b6ee09p-2};
+    return T[i & 15u];
+}
+
+// logf for every binary32 input: +-0 -> -inf, +inf -> +inf, NaN -> the NaN quieted, negative (and -inf) -> the default
+// NaN x86 produces for 0/0 (0xffc00000: what glibc's (x - x) / (x - x) returns there), subnormals through the normal path
+GS_HD inline float gs_logf(float x) {
+    uint32_t ix = cv_f2u(x);
+    if (ix == 0x3f800000u) return 0.0f;
+    if (ix - 0x00800000u >= 0x7f000000u) {             // zero, subnormal, negative, inf, NaN
+        if ((ix << 1) == 0u) return cv_u2f(0xff800000u);
+        if (ix == 0x7f800000u) return x;
+        if ((ix << 1) > 0xff000000u) return cv_u2f(ix | 0x00400000u);
+        if (ix & 0x80000000u) return cv_u2f(0xffc00000u);
+        // bits(x * 2^23) - (23 << 23): x = ix * 2^-149 and the conversion of ix < 2^23 is exact, so this is an integer
+        // identity and does not depend on how the device treats a subnormal operand
+        ix = cv_f2u((float)ix) - (149u << 23);
+    }
+    const uint32_t tmp = ix - 0x3f330000u;
+    const uint32_t i = (tmp >> 19) & 15u;
+    const int32_t k = (int32_t)tmp >> 23;
+    const uint32_t iz = ix - (tmp & 0xff800000u);
+    const double z = (double)cv_u2f(iz);
+    const double ln2 = 0x1.62e42fefa39efp-1;
+    const double a0 = -0x1.00ea348b88334p-2, a1 = 0x1.5575b0be00b6ap-2, a2 = -0x1.ffffef20a4123p-2;
+    const double r = z * logf_invc(i) - 1.0;
+    const double y0 = logf_logc(i) + (double)k * ln2;
+    const double r2 = r * r;
+    double y = a1 * r + a2;
+    y = a0 * r2 + y;
+    y = y * r2 + (y0 + r);
     return (float)y;
 }
 
@@ -222,6 +278,173 @@ GS_HD inline void spz_to_gaussian_words(const SpzView &v, size_t i, uint32_t *g,
     for (int k = 0; k < 45; k++) g[8 + k] = 0u;
     for (uint32_t k = 0; k < v.ncoef; k++)
         for (int c = 0; c < 3; c++) g[8 + 3 * k + c] = cv_f2u(((float)v.sh[(i * v.ncoef + k) * 3 + c] - 128.0f) / 128.0f);
+}
+
+// ---- struct Gaussian -> source-format records: Gaussian::to_ply (gaussian.rs:95-125) and Gaussian::to_spz
+// (gaussian.rs:227-352), shared by the host entry points (gs_gaussian_to_ply, gs_spz_encode_decompressed) and the export
+// kernels (gs_export_kernels.h).  min / max / clamp are written as comparisons (NaN -> the lower bound, as f32::max(lo)
+// .min(hi) gives) and every value that reaches the output goes through gs_logf, a correctly rounded IEEE operation or an
+// integer: host and device produce the same bytes.
+
+// g = 56 words of one struct Gaussian, p = 62 words of one PlyGaussianPod out
+GS_HD inline void gaussian_to_ply_words(const uint32_t *g, uint32_t *p) {
+    p[0] = g[4];
+    p[1] = g[5];
+    p[2] = g[6];
+    p[3] = 0u;                       // normal (0, 0, 1)
+    p[4] = 0u;
+    p[5] = 0x3f800000u;
+    const uint32_t color = g[7];
+    GS_UNROLL
+    for (int k = 0; k < 3; k++) {
+        const float c = (float)((color >> (8 * k)) & 0xffu) / 255.0f;
+        p[6 + k] = cv_f2u((c - 0.5f) / 0.2820948f);
+    }
+    GS_UNROLL
+    for (int k = 0; k < 15; k++) {       // RGB-interleaved -> channel-planar f_rest
+        p[9 + k] = g[8 + 3 * k + 0];
+        p[9 + k + 15] = g[8 + 3 * k + 1];
+        p[9 + k + 30] = g[8 + 3 * k + 2];
+    }
+    const float a = (float)(color >> 24) / 255.0f;
+    p[54] = cv_f2u(-gs_logf(1.0f / a - 1.0f));      // the argument is >= 0 or +inf: never a NaN whose sign the negation would flip
+    GS_UNROLL
+    for (int k = 0; k < 3; k++) p[55 + k] = cv_f2u(gs_logf(cv_u2f(g[53 + k])));
+    p[58] = g[3];                    // rot wxyz
+    p[59] = g[0];
+    p[60] = g[1];
+    p[61] = g[2];
+}
+
+// half 2.x f16::from_f32 (const conversion == IEEE RNE; every NaN becomes 0x7e00 | sign)
+GS_HD inline uint32_t cv_f32_to_f16(float value) {
+    const uint32_t f32infty = 255u << 23, f16max = (127u + 16u) << 23;
+    const uint32_t magic = ((127u - 15u) + (23u - 10u) + 1u) << 23;
+    uint32_t u = cv_f2u(value);
+    const uint32_t sign = u & 0x80000000u;
+    u ^= sign;
+    uint32_t o;
+    if (u >= f16max) {
+        o = u > f32infty ? 0x7e00u : 0x7c00u;
+    } else if (u < (113u << 23)) {
+        o = cv_f2u(cv_u2f(u) + cv_u2f(magic)) - magic;
+    } else {
+        const uint32_t odd = (u >> 13) & 1u;
+        u += ((uint32_t)(15 - 127) << 23) + 0xfffu;
+        u += odd;
+        o = u >> 13;
+    }
+    return (o & 0xffffu) | (sign >> 16);
+}
+// Rust `as u32` / `as i32` of an f32: truncating, saturating, NaN -> 0
+GS_HD inline uint32_t cv_sat_u32(float v) { return !(v > 0.0f) ? 0u : v >= 4294967295.0f ? 0xffffffffu : (uint32_t)v; }
+GS_HD inline int32_t cv_sat_i32(float v) {
+    return v != v ? 0 : v >= 2147483647.0f ? 2147483647 : v <= -2147483648.0f ? (int32_t)0x80000000u : (int32_t)v;
+}
+// f32::max(lo).min(hi) for lo <= hi: NaN -> lo
+GS_HD inline float cv_clamp(float v, float lo, float hi) {
+    const float a = v > lo ? v : lo;
+    return a < hi ? a : hi;
+}
+GS_HD inline float cv_fabs(float v) { return cv_u2f(cv_f2u(v) & 0x7fffffffu); }
+// gaussian.rs:317-324: only buckets when bucket < 8
+GS_HD inline uint32_t spz_quantize_sh(float x, uint32_t bucket) {
+    uint32_t q = cv_sat_u32(roundf(x * 128.0f + 128.0f));
+    if (!(bucket >= 8u)) q = (q + bucket / 2u) / bucket * bucket;
+    return q > 255u ? 255u : q;
+}
+
+// the six columns of a decompressed SPZ payload, in file order, and their bytes per record
+enum { SPZ_COL_POS = 0, SPZ_COL_ALPHA = 1, SPZ_COL_COLOR = 2, SPZ_COL_SCALE = 3, SPZ_COL_ROT = 4, SPZ_COL_SH = 5 };
+GS_HD inline uint32_t spz_col_bytes(int col, uint32_t version, uint32_t ncoef) {
+    return col == SPZ_COL_POS ? (version == 1u ? 6u : 9u) : col == SPZ_COL_ALPHA ? 1u : col == SPZ_COL_ROT ? (version >= 3u ? 4u : 3u)
+           : col == SPZ_COL_SH ? 3u * ncoef : 3u;
+}
+
+// g = 56 words of one struct Gaussian; put(column, k, byte) receives byte k of the record's entry in each column.
+// bucket = 1 << (8 - quantize bits of the degree).  `sqrtf_cr`: a correctly rounded binary32 square root, as above.
+template <class Put, class Sqrt>
+GS_HD inline void gaussian_to_spz_bytes(const uint32_t *g, uint32_t version, uint32_t fractional_bits, uint32_t ncoef, uint32_t bucket,
+                                        Put put, Sqrt sqrtf_cr) {
+    if (version == 1u) {
+        GS_UNROLL
+        for (int c = 0; c < 3; c++) {
+            const uint32_t h = cv_f32_to_f16(cv_u2f(g[4 + c]));
+            put(SPZ_COL_POS, 2 * c, h & 0xffu);
+            put(SPZ_COL_POS, 2 * c + 1, h >> 8);
+        }
+    } else {
+        const float s = (float)(int32_t)(1u << (fractional_bits & 31u));
+        GS_UNROLL
+        for (int c = 0; c < 3; c++) {
+            const uint32_t fixed = (uint32_t)cv_sat_i32(roundf(cv_u2f(g[4 + c]) * s));
+            put(SPZ_COL_POS, 3 * c, fixed & 0xffu);
+            put(SPZ_COL_POS, 3 * c + 1, (fixed >> 8) & 0xffu);
+            put(SPZ_COL_POS, 3 * c + 2, (fixed >> 16) & 0xffu);
+        }
+    }
+    GS_UNROLL
+    for (int c = 0; c < 3; c++) {
+        const float v = roundf((gs_logf(cv_u2f(g[53 + c])) + 10.0f) * 16.0f);
+        put(SPZ_COL_SCALE, c, cv_sat_u8(cv_clamp(v, 0.0f, 255.0f)));
+    }
+    // Quat::normalize
+    float q[4];
+    {
+        const float r0 = cv_u2f(g[0]), r1 = cv_u2f(g[1]), r2 = cv_u2f(g[2]), r3 = cv_u2f(g[3]);
+        const float len = sqrtf_cr(((r0 * r0 + r1 * r1) + r2 * r2) + r3 * r3);
+        q[0] = r0 / len;
+        q[1] = r1 / len;
+        q[2] = r2 / len;
+        q[3] = r3 / len;
+    }
+    if (version >= 3u) {
+        uint32_t largest = 0;
+        GS_UNROLL
+        for (uint32_t k = 1; k < 4; k++) {       // max_by keeps the LAST maximum
+            float cur = cv_fabs(q[0]);
+            GS_UNROLL
+            for (uint32_t j = 1; j < 4; j++)
+                if (j == largest) cur = cv_fabs(q[j]);
+            if (!(cv_fabs(q[k]) < cur)) largest = k;     // ... and a NaN compares Equal (partial_cmp(..).unwrap_or(Equal))
+        }
+        const uint32_t mask = (1u << 9) - 1u;
+        float ql = q[0];
+        GS_UNROLL
+        for (uint32_t j = 1; j < 4; j++)
+            if (j == largest) ql = q[j];
+        const uint32_t negate = ql < 0.0f ? 1u : 0u;
+        uint32_t comp = largest;
+        GS_UNROLL
+        for (uint32_t k = 0; k < 4; k++) {
+            if (k == largest) continue;
+            const uint32_t neg = (q[k] < 0.0f ? 1u : 0u) ^ negate;
+            const float mv = (float)mask * (cv_fabs(q[k]) * 1.41421356237309504880f) + 0.5f;
+            const uint32_t mag = cv_sat_u32(cv_clamp(mv, 0.0f, (float)mask - 1.0f));
+            comp = (comp << 10) | (neg << 9) | mag;
+        }
+        GS_UNROLL
+        for (int b = 0; b < 4; b++) put(SPZ_COL_ROT, b, (comp >> (8 * b)) & 0xffu);
+    } else {
+        const bool flip = q[3] < 0.0f;
+        GS_UNROLL
+        for (int c = 0; c < 3; c++) {
+            const float v = roundf(((flip ? -q[c] : q[c]) + 1.0f) * 127.5f);
+            put(SPZ_COL_ROT, c, cv_sat_u8(cv_clamp(v, 0.0f, 255.0f)));
+        }
+    }
+    const uint32_t color = g[7];
+    put(SPZ_COL_ALPHA, 0, color >> 24);
+    GS_UNROLL
+    for (int c = 0; c < 3; c++) {
+        const float v = ((float)((color >> (8 * c)) & 0xffu) - spz_color_c()) / spz_color_ab();
+        put(SPZ_COL_COLOR, c, cv_sat_u8(cv_clamp(v, 0.0f, 255.0f)));
+    }
+    GS_UNROLL
+    for (uint32_t k = 0; k < 15u; k++)
+        if (k < ncoef)
+            GS_UNROLL
+            for (int c = 0; c < 3; c++) put(SPZ_COL_SH, (int)(3u * k) + c, spz_quantize_sh(cv_u2f(g[8 + 3 * k + c]), bucket));
 }
 
 }  // namespace gs

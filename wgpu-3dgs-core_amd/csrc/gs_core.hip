@@ -87,6 +87,7 @@ static gsp::Switches read_switches() {
     s.tile_msd_auto = env_on("GS3D_TILE_MSD_AUTO");
     s.ranges_in_blend = (int)env_int("GS3D_RANGES_IN_BLEND", s.ranges_in_blend);
     s.ranges_search = (int)env_int("GS3D_RANGES_SEARCH", s.ranges_search);
+    s.export_slice = env_int("GS3D_EXPORT_SLICE", s.export_slice);
     return s;
 }
 

@@ -8,7 +8,14 @@ gs_status gs_fail(gs_status code, uint64_t a, uint64_t b, uint64_t c, const char
     __attribute__((format(printf, 5, 6)));
 
 #ifdef __cplusplus
+#include <string>
 #include <vector>
+// gs_ply.cpp, for the export path in gs_export.hip: the header gs_ply_write puts in front of n records
+std::string gs_ply_header(size_t n);
+// gs_spz.cpp, for the export path: what gs_spz_encode_decompressed checks and lays out before it encodes n records — the
+// header, the byte offsets of the six columns, the SH coefficients per channel, the bucket of quantize_sh and the payload size
+gs_status gs_spz_encode_layout(size_t n, const gs_spz_options *opt, gs_spz_header *header_out, size_t col_offset[6],
+                               uint32_t *ncoef_out, uint32_t *bucket_out, size_t *bytes_out);
 // gs_spz.cpp, for the device load path in gs_core.hip: validates the header of a DECOMPRESSED SPZ payload
 // and its length, returns the byte offsets of the six columns (positions, alphas, colors, scales,
 // rotations, sh) and the SH coefficients per channel; errors as gs_spz_decode_decompressed

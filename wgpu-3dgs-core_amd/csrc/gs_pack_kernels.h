@@ -106,7 +106,8 @@ __host__ __device__ inline void unpack_words(int sh, const uint32_t *p, uint32_t
     g[GW_POS + 2] = p[2];
     g[GW_COLOR] = p[3];
     const uint32_t *s = p + 4;
-    for (int k = 0; k < 45; k++) {
+#pragma unroll
+    for (int k = 0; k < 45; k++) {       // unrolled: the export kernels keep p and g in registers
         if (sh == SH_SINGLE) {
             g[GW_SH + k] = s[k];
         } else if (sh == SH_HALF) {

@@ -68,29 +68,18 @@ extern "C" void gs_gaussian_from_ply(const gs_ply_gaussian_pod *in, size_t n, gs
 
 extern "C" float gs_expf(float x) { return gs::gs_expf(x); }
 
+extern "C" float gs_logf(float x) { return gs::gs_logf(x); }
+
+// the per-record arithmetic is gs_convert.h's gaussian_to_ply_words, shared with the export kernel (k_export_ply)
 extern "C" void gs_gaussian_to_ply(const gs_gaussian *in, size_t n, gs_ply_gaussian_pod *out) {
-    for (size_t i = 0; i < n; i++) {
-        const gs_gaussian &g = in[i];
-        gs_ply_gaussian_pod &p = out[i];
-        std::memcpy(p.pos, g.pos, 12);
-        p.rot[0] = g.rot[3];
-        p.rot[1] = g.rot[0];
-        p.rot[2] = g.rot[1];
-        p.rot[3] = g.rot[2];
-        for (int k = 0; k < 3; k++) p.scale[k] = std::log(g.scale[k]);
-        float rgba[4];
-        for (int k = 0; k < 4; k++) rgba[k] = (float)g.color[k] / 255.0f;
-        for (int k = 0; k < 3; k++) p.color[k] = (rgba[k] - 0.5f) / 0.2820948f;
-        p.alpha = -std::log(1.0f / rgba[3] - 1.0f);
-        for (int k = 0; k < 15; k++) {
-            p.sh[k] = g.sh[3 * k + 0];
-            p.sh[k + 15] = g.sh[3 * k + 1];
-            p.sh[k + 30] = g.sh[3 * k + 2];
+    ply_parallel_for(n, [=](size_t a, size_t b) {
+        for (size_t i = a; i < b; i++) {
+            uint32_t gw[gs::CV_GAUSSIAN_WORDS], pw[gs::PLY_WORDS];
+            std::memcpy(gw, &in[i], sizeof(gw));
+            gs::gaussian_to_ply_words(gw, pw);
+            std::memcpy(&out[i], pw, sizeof(pw));
         }
-        p.normal[0] = 0.0f;
-        p.normal[1] = 0.0f;
-        p.normal[2] = 1.0f;
-    }
+    });
 }
 
 // ---- header ------------------------------------------------------------------------------------
@@ -356,12 +345,17 @@ extern "C" gs_status gs_ply_read(const void *bytes, size_t len, gs_ply_gaussian_
     return GS_OK;
 }
 
-extern "C" gs_status gs_ply_write(const gs_ply_gaussian_pod *pods, size_t n, void *out,
-                                  size_t capacity, size_t *bytes_out) {
-    if (!bytes_out || (n && !pods)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+std::string gs_ply_header(size_t n) {
     std::string hdr = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) + "\n";
     for (int k = 0; k < 62; k++) hdr += std::string("property float ") + k_props[k] + "\n";
     hdr += "end_header\n";
+    return hdr;
+}
+
+extern "C" gs_status gs_ply_write(const gs_ply_gaussian_pod *pods, size_t n, void *out,
+                                  size_t capacity, size_t *bytes_out) {
+    if (!bytes_out || (n && !pods)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    const std::string hdr = gs_ply_header(n);
     size_t total = hdr.size() + n * sizeof(gs_ply_gaussian_pod);
     *bytes_out = total;
     if (!out) return GS_OK;

@@ -50,6 +50,7 @@ struct Switches {
     bool tile_msd_auto = false;     // GS3D_TILE_MSD_AUTO=1: the renderer may choose the MSD-first tile sort by itself
     int ranges_in_blend = -1;       // GS3D_RANGES_IN_BLEND=0/1: the blend workgroups search their tile's range themselves
     int ranges_search = -1;         // GS3D_RANGES_SEARCH=0/1: k_tile_ranges / k_tile_ranges_search
+    long export_slice = 0;          // GS3D_EXPORT_SLICE=<records>: source records per kernel of the PLY export, a multiple of 1024 (tests)
 };
 
 // what gs_renderer_set_sort_mode / _set_tile_masks / _set_rounds asked for (-1 / 0: the renderer chooses)

@@ -21,8 +21,6 @@
 static_assert(sizeof(gs_spz_header) == 16, "SpzGaussiansHeaderPod is 16 bytes");
 
 static const uint32_t k_magic = 0x5053474eu;   // "NGSP", spz.rs:458
-static const float k_ab = 0.2820948f / 0.15f;  // SPZ_COLOR_TO_LINEAR_FRAC_A_B, gaussian.rs:127-128
-static const float k_c = (1.0f - k_ab) * (0.5f * 255.0f);   // SPZ_COLOR_TO_LINEAR_C, :130-131
 
 static uint32_t num_coefficients(uint32_t deg) { return deg == 0 ? 0 : deg == 1 ? 3 : deg == 2 ? 8 : 15; }
 
@@ -48,19 +46,6 @@ static gs_status validate_header(const gs_spz_header &h) {
 }
 
 // ---- f16 (half crate const conversions == IEEE RNE) ---------------------------------------------
-static uint16_t f32_to_f16(float value) {
-    union { uint32_t u; float f; } f, magic;
-    f.f = value;
-    const uint32_t f32infty = 255u << 23, f16max = (127u + 16u) << 23;
-    magic.u = ((127u - 15u) + (23u - 10u) + 1u) << 23;
-    uint32_t sign = f.u & 0x80000000u;
-    f.u ^= sign;
-    uint16_t o;
-    if (f.u >= f16max) o = (f.u > f32infty) ? (uint16_t)0x7e00u : (uint16_t)0x7c00u;
-    else if (f.u < (113u << 23)) { f.f += magic.f; o = (uint16_t)(f.u - magic.u); }
-    else { uint32_t odd = (f.u >> 13) & 1u; f.u += ((uint32_t)(15 - 127) << 23) + 0xfffu; f.u += odd; o = (uint16_t)(f.u >> 13); }
-    return (uint16_t)(o | (sign >> 16));
-}
 static float f16_to_f32(uint16_t h) {
     union { uint32_t u; float f; } o;
     uint32_t sign = ((uint32_t)h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
@@ -69,10 +54,6 @@ static float f16_to_f32(uint16_t h) {
     else o.u = sign | ((e + 112u) << 23) | (m << 13);
     return o.f;
 }
-static uint8_t sat_u8(float v) { return !(v > 0.0f) ? 0 : v >= 255.0f ? 255 : (uint8_t)v; }
-static uint32_t sat_u32(float v) { return !(v > 0.0f) ? 0u : v >= 4294967295.0f ? 0xffffffffu : (uint32_t)v; }
-static int32_t sat_i32(float v) { return v != v ? 0 : v >= 2147483647.0f ? 2147483647 : v <= -2147483648.0f ? (int32_t)0x80000000 : (int32_t)v; }
-
 template <class F>
 static void spz_parallel_for(size_t n, F fn) {
     unsigned hw = std::thread::hardware_concurrency();
@@ -157,15 +138,8 @@ extern "C" gs_status gs_spz_decode_decompressed(const void *bytes, size_t len, g
 }
 
 // ---- Gaussian::to_spz (gaussian.rs:240-352) + write_decompressed (spz.rs:776-794) --------------
-static uint8_t quantize_sh(float x, uint32_t bucket) {   // gaussian.rs:317-324
-    uint32_t q = sat_u32(std::round(x * 128.0f + 128.0f));
-    if (!(bucket >= 8)) q = (q + bucket / 2) / bucket * bucket;
-    return (uint8_t)(q > 255u ? 255u : q);
-}
-
-extern "C" gs_status gs_spz_encode_decompressed(const gs_gaussian *in, size_t n, const gs_spz_options *opt,
-                                                void *out, size_t capacity, size_t *bytes_out) {
-    if (!opt || !bytes_out || (n && !in)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+gs_status gs_spz_encode_layout(size_t n, const gs_spz_options *opt, gs_spz_header *header_out, size_t col_offset[6],
+                               uint32_t *ncoef_out, uint32_t *bucket_out, size_t *bytes_out) {
     gs_spz_header h;
     h.magic = k_magic;
     h.version = opt->version;
@@ -181,82 +155,47 @@ extern "C" gs_status gs_spz_encode_decompressed(const gs_gaussian *in, size_t n,
                        "sh_quantize_bits must be in 0..=8");
     if (h.version > 1 && h.fractional_bits > 30)
         return gs_fail(GS_ERR_INVALID_ARGUMENT, h.fractional_bits, 30, 0, "fractional_bits must be below 31");
-    const size_t total = payload_bytes(h);
+    const uint32_t bits = h.sh_degree ? opt->sh_quantize_bits[h.sh_degree - 1] : 8;
+    col_offset[0] = 16;
+    col_offset[1] = col_offset[0] + n * pos_bytes(h.version);
+    col_offset[2] = col_offset[1] + n;
+    col_offset[3] = col_offset[2] + 3 * n;
+    col_offset[4] = col_offset[3] + 3 * n;
+    col_offset[5] = col_offset[4] + n * rot_bytes(h.version);
+    *header_out = h;
+    *ncoef_out = num_coefficients(h.sh_degree);
+    *bucket_out = 1u << (8 - bits);
+    *bytes_out = payload_bytes(h);
+    return GS_OK;
+}
+
+// the per-record arithmetic is gs_convert.h's gaussian_to_spz_bytes, shared with the export kernel (k_export_spz)
+extern "C" gs_status gs_spz_encode_decompressed(const gs_gaussian *in, size_t n, const gs_spz_options *opt,
+                                                void *out, size_t capacity, size_t *bytes_out) {
+    if (!opt || !bytes_out || (n && !in)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    gs_spz_header h;
+    size_t off[6], total = 0;
+    uint32_t ncoef = 0, bucket = 0;
+    gs_status rc = gs_spz_encode_layout(n, opt, &h, off, &ncoef, &bucket, &total);
+    if (rc != GS_OK) return rc;
     *bytes_out = total;
     if (!out) return GS_OK;
     if (capacity < total) return gs_fail(GS_ERR_INVALID_ARGUMENT, capacity, total, 0, "output buffer too small");
     uint8_t *b = (uint8_t *)out;
     std::memcpy(b, &h, 16);
-    uint8_t *pos = b + 16;
-    uint8_t *alpha = pos + n * pos_bytes(h.version);
-    uint8_t *color = alpha + n;
-    uint8_t *scale = color + 3 * n;
-    uint8_t *rot = scale + 3 * n;
-    uint8_t *sh = rot + n * rot_bytes(h.version);
-    const uint32_t ncoef = num_coefficients(h.sh_degree);
-    const uint32_t bits = h.sh_degree ? opt->sh_quantize_bits[h.sh_degree - 1] : 8;
-    const uint32_t bucket = 1u << (8 - bits);
-    for (size_t i = 0; i < n; i++) {
-        const gs_gaussian &g = in[i];
-        if (h.version == 1) {
-            for (int c = 0; c < 3; c++) {
-                uint16_t v = f32_to_f16(g.pos[c]);
-                std::memcpy(pos + 6 * i + 2 * c, &v, 2);
-            }
-        } else {
-            const float s = (float)(1 << h.fractional_bits);
-            for (int c = 0; c < 3; c++) {
-                int32_t fixed = sat_i32(std::round(g.pos[c] * s));
-                uint8_t *p = pos + 9 * i + 3 * c;
-                p[0] = (uint8_t)(fixed & 0xff);
-                p[1] = (uint8_t)((fixed >> 8) & 0xff);
-                p[2] = (uint8_t)((fixed >> 16) & 0xff);
-            }
+    const uint32_t version = h.version, fractional_bits = h.fractional_bits;
+    uint32_t width[6];
+    for (int c = 0; c < 6; c++) width[c] = gs::spz_col_bytes(c, version, ncoef);
+    spz_parallel_for(n, [=](size_t a, size_t e) {
+        for (size_t i = a; i < e; i++) {
+            uint32_t gw[gs::CV_GAUSSIAN_WORDS];
+            std::memcpy(gw, &in[i], sizeof(gw));
+            gs::gaussian_to_spz_bytes(
+                gw, version, fractional_bits, ncoef, bucket,
+                [=](int col, int k, uint32_t byte) { b[off[col] + i * width[col] + (size_t)k] = (uint8_t)byte; },
+                [](float x) { return std::sqrt(x); });
         }
-        for (int c = 0; c < 3; c++) {
-            float v = std::round((std::log(g.scale[c]) + 10.0f) * 16.0f);
-            scale[3 * i + c] = sat_u8(std::fmin(std::fmax(v, 0.0f), 255.0f));
-        }
-        // Quat::normalize
-        float q[4];
-        {
-            float len = std::sqrt(((g.rot[0] * g.rot[0] + g.rot[1] * g.rot[1]) + g.rot[2] * g.rot[2]) + g.rot[3] * g.rot[3]);
-            for (int c = 0; c < 4; c++) q[c] = g.rot[c] / len;
-        }
-        if (h.version >= 3) {
-            uint32_t largest = 0;
-            for (uint32_t k = 1; k < 4; k++)
-                if (std::fabs(q[k]) >= std::fabs(q[largest])) largest = k;   // max_by keeps the LAST maximum
-            const uint32_t mask = (1u << 9) - 1u;
-            uint32_t negate = q[largest] < 0.0f ? 1u : 0u;
-            uint32_t comp = largest;
-            for (uint32_t k = 0; k < 4; k++) {
-                if (k == largest) continue;
-                uint32_t neg = (q[k] < 0.0f ? 1u : 0u) ^ negate;
-                float mv = (float)mask * (std::fabs(q[k]) * 1.41421356237309504880f) + 0.5f;
-                uint32_t mag = sat_u32(std::fmin(std::fmax(mv, 0.0f), (float)mask - 1.0f));
-                comp = (comp << 10) | (neg << 9) | mag;
-            }
-            uint8_t *r = rot + 4 * i;
-            r[0] = (uint8_t)(comp & 0xff);
-            r[1] = (uint8_t)((comp >> 8) & 0xff);
-            r[2] = (uint8_t)((comp >> 16) & 0xff);
-            r[3] = (uint8_t)((comp >> 24) & 0xff);
-        } else {
-            float sgn = q[3] < 0.0f ? -1.0f : 1.0f;
-            for (int c = 0; c < 3; c++) {
-                float v = std::round(((sgn < 0.0f ? -q[c] : q[c]) + 1.0f) * 127.5f);
-                rot[3 * i + c] = sat_u8(std::fmin(std::fmax(v, 0.0f), 255.0f));
-            }
-        }
-        alpha[i] = g.color[3];
-        for (int c = 0; c < 3; c++) {
-            float v = ((float)g.color[c] - k_c) / k_ab;
-            color[3 * i + c] = sat_u8(std::fmin(std::fmax(v, 0.0f), 255.0f));
-        }
-        for (uint32_t k = 0; k < ncoef; k++)
-            for (int c = 0; c < 3; c++) sh[(i * ncoef + k) * 3 + c] = quantize_sh(g.sh[3 * k + c], bucket);
-    }
+    });
     return GS_OK;
 }
 
