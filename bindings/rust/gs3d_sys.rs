@@ -81,6 +81,10 @@ pub const GS_ATTR_SIZE2: u32 = 7;
 pub const GS_ATTR_DIST2: u32 = 8;
 pub const GS_ATTR_COUNT: u32 = 9;
 
+pub const GS_CONTRIB_SUM: u32 = 0;
+pub const GS_CONTRIB_HITS: u32 = 1;
+pub const GS_CONTRIB_MAX: u32 = 2;
+
 #[repr(C)] pub struct gs_device { _private: [u8; 0] }
 #[repr(C)] pub struct gs_stream { _private: [u8; 0] }
 #[repr(C)] pub struct gs_buffer { _private: [u8; 0] }
@@ -334,6 +338,14 @@ pub struct gs_stats {
     pub attr: [gs_attribute_stats; 9],
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_contribution {
+    pub sum: u64,
+    pub hits: u32,
+    pub wmax: f32,
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -490,6 +502,9 @@ extern "C" {
     pub fn gs_gaussians_buffer_export_spz_decompressed(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, options: *const gs_spz_options, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
     pub fn gs_gaussians_buffer_export_spz(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, options: *const gs_spz_options, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
     pub fn gs_gaussians_buffer_write(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, source: gs_gaussians_source, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
+    pub fn gs_render_frame_contrib(r: *mut gs_renderer, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, gaussian_transform: *const gs_gaussian_transform_pod, model_transform: *const gs_model_transform_pod, camera: *const gs_camera, band_ty0: u32, band_ty1: u32, rgba_out_device: *mut f32, fs: *const gs_frame_selection, contrib: *mut gs_buffer) -> gs_status;
+    pub fn gs_contributions_clear(contrib: *mut gs_buffer, s: *mut gs_stream, n: usize) -> gs_status;
+    pub fn gs_select_contribution(sel: *mut gs_selection, s: *mut gs_stream, contrib: *mut gs_buffer, kind: u32, lo: f32, hi: f32, op: u32) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

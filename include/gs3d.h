@@ -1099,6 +1099,57 @@ gs_status gs_gaussians_buffer_export_spz(gs_gaussians_buffer *g, gs_stream *s, c
 gs_status gs_gaussians_buffer_write(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
                                     gs_gaussians_source source, void *out, size_t capacity, size_t *bytes_out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Contribution scores (no reference item in the core crate: pruning and          */
+/* compression tools score a Gaussian by what it does to the images of a set of views)           */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  A contribution is a pair (pixel, Gaussian) whose blend step at that
+ * pixel is taken with alpha_eff > 0 — a step the pick plane would consider.  The step that finishes a pixel
+ * (T (1 - alpha) < 1e-4) is not blended and contributes nothing; neither do culled or hidden Gaussians.  Its weight is
+ * w = alpha_eff * T, the binary32 product the blend forms; w > 0 always (T >= 1e-4, alpha >= 1/255).  One record per Gaussian
+ * in CALLER index order; every field is an integer reduction, so the result does not depend on traversal order, lane
+ * grouping, bands or streams: it is defined bit for bit. */
+typedef struct gs_contribution {
+    uint64_t sum;   /* += (uint32_t)(w * 16777216.0f) per contribution: units of 2^-24, truncated; exact integer adds */
+    uint32_t hits;  /* += 1 per contribution (wraps mod 2^32; documented, not checked) */
+    float    wmax;  /* max over contributions; all w > 0, so the max of the bit patterns */
+} gs_contribution;
+
+/* gs_select_contribution kinds: the value v of a record (no reference item) */
+enum {
+    GS_CONTRIB_SUM = 0,   /* (float)sum * 0x1p-24f: u64 -> f32 round-to-nearest-even, then the exact scale */
+    GS_CONTRIB_HITS = 1,  /* (float)hits */
+    GS_CONTRIB_MAX = 2    /* wmax */
+};
+
+/* gs_render_frame_sel without aux planes, which also ACCUMULATES the frame's contributions into `contrib`: n records of 16
+ * bytes in a caller-owned buffer of at least 16 n bytes (no reference item).  A frame never clears the
+ * records: gs_contributions_clear does.  contrib == NULL: exactly gs_render_frame_sel(..., NULL, fs).  With `contrib` the
+ * image is bit for bit the plain frame's and so is `launches`: the accumulation rides in the blend launch (the grouped
+ * blend, 8x4 blocks where the plain frame would take the ungrouped kernel).  GS_ERR_INVALID_ARGUMENT, before anything is
+ * enqueued, for a buffer smaller than 16 n bytes, one that is not 16-byte aligned or one of another device.
+ * A contribution frame is planned as ONE round — exactly as a frame under gs_renderer_set_rounds(r, 0, 0), without changing
+ * the renderer's pin — because a frame skipped for pair capacity (GS_ERR_PAIR_CAPACITY) must leave the records untouched,
+ * always: a two-round frame skipped in its second round could not undo the adds of its first.
+ * Frames of several renderers on several streams may accumulate into one buffer concurrently (the adds are atomic); clears
+ * and reads are the caller's to order, as with any buffer. */
+gs_status gs_render_frame_contrib(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *gaussians,
+                                  const gs_gaussian_transform_pod *gaussian_transform,
+                                  const gs_model_transform_pod *model_transform, const gs_camera *camera,
+                                  uint32_t band_ty0, uint32_t band_ty1, float *rgba_out_device,
+                                  const gs_frame_selection *fs, gs_buffer *contrib);
+/* Zeroes the first 16 n bytes of `contrib` (no reference item).  Only enqueues on `s`.  GS_ERR_INVALID_ARGUMENT for a null
+ * argument, a buffer smaller than 16 n bytes or a stream of another device. */
+gs_status gs_contributions_clear(gs_buffer *contrib, gs_stream *s, size_t n);
+/* sel = sel op {i : lo <= v_i && v_i <= hi}, v the `kind` value of record i of `contrib` (n = the selection's length;
+ * DESIGN.md 3.5c; no reference item).  The argument rules of gs_select_attribute: a NaN bound is refused, lo > hi selects
+ * nothing, infinite bounds are allowed; the mask is written word-wise, bits past n stay 0.  Only enqueues.
+ * GS_ERR_INVALID_ARGUMENT for an unknown kind or op, a buffer smaller than 16 n bytes, a misaligned one, or objects of
+ * different devices. */
+gs_status gs_select_contribution(gs_selection *sel, gs_stream *s, gs_buffer *contrib, uint32_t kind, float lo, float hi,
+                                 gs_select_op op);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

@@ -428,10 +428,18 @@ class Selection {
                           const Selection *among = nullptr, const gs_model_transform_pod *mt = nullptr, gs_select_op op = GS_SEL_SET) {
         check(gs_select_neighbors(h_, s.raw(), g.raw(), among ? among->raw() : nullptr, mt, radius, min_count, max_count, op));
     }
+    // sel = sel op {i : lo <= v_i <= hi}, v the GS_CONTRIB_* value of record i of `contrib` (gs_select_contribution,
+    // DESIGN.md 3.5c); only enqueues
+    void select_contribution(Stream &s, Buffer &contrib, uint32_t kind, float lo, float hi, gs_select_op op = GS_SEL_SET) {
+        check(gs_select_contribution(h_, s.raw(), contrib.raw(), kind, lo, hi, op));
+    }
     gs_selection *raw() const { return h_; }
   private:
     gs_selection *h_ = nullptr;
 };
+
+// gs_contributions_clear: zeroes the n contribution records (16 n bytes) of `contrib`; only enqueues
+inline void contributions_clear(Buffer &contrib, Stream &s, size_t n) { check(gs_contributions_clear(contrib.raw(), s.raw(), n)); }
 
 inline void Snapshot::selection(Stream &s, Selection &sel, gs_select_op op) const { check(gs_snapshot_selection(h_, s.raw(), sel.raw(), op)); }
 template <class G>
@@ -658,6 +666,20 @@ class Renderer {
         fs.tint = tint ? tint->raw() : nullptr;
         for (int c = 0; c < 4; c++) fs.tint_rgba[c] = tint_rgba ? tint_rgba[c] : 0.0f;
         check(gs_render_frame_sel(h_, s.raw(), g.raw(), &gt, &mt, &cam, band_ty0, band_ty1, rgba_device, aux, &fs));
+    }
+    // the plain or selection frame (hide / tint may be nullptr) that also ACCUMULATES its per-Gaussian contribution scores
+    // into the gs_contribution records of `contrib`, at least 16 len() bytes (gs_render_frame_contrib):
+    // one round, no planes; a frame never clears the records (contributions_clear)
+    template <class G>
+    void render_contrib(Stream &s, GaussiansBuffer<G> &g, const gs_gaussian_transform_pod &gt, const gs_model_transform_pod &mt,
+                        const gs_camera &cam, float *rgba_device, Buffer &contrib, uint32_t band_ty0 = 0,
+                        uint32_t band_ty1 = 0xffffffffu, const Selection *hide = nullptr, const Selection *tint = nullptr,
+                        const float tint_rgba[4] = nullptr) {
+        gs_frame_selection fs{};
+        fs.hide = hide ? hide->raw() : nullptr;
+        fs.tint = tint ? tint->raw() : nullptr;
+        for (int c = 0; c < 4; c++) fs.tint_rgba[c] = tint_rgba ? tint_rgba[c] : 0.0f;
+        check(gs_render_frame_contrib(h_, s.raw(), g.raw(), &gt, &mt, &cam, band_ty0, band_ty1, rgba_device, &fs, contrib.raw()));
     }
     // the Gaussians the last frame kept whose mean lies in [x0, x1) x [y0, y1) (and on a nonzero byte of the H x W device
     // plane `mask`, if given): sel = sel op that set.  Enqueued behind the frame; does not block.

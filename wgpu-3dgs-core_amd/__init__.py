@@ -1636,6 +1636,52 @@ class Selection:
             self._h = None
 
 
+# GS_CONTRIB_*: the value gs_select_contribution compares
+CONTRIB_SUM, CONTRIB_HITS, CONTRIB_MAX = 0, 1, 2
+# gs_contribution: one record per Gaussian in caller order; sum in units of 2^-24
+CONTRIBUTION_DTYPE = np.dtype([("sum", "<u8"), ("hits", "<u4"), ("wmax", "<f4")])
+
+
+class Contributions:
+    """Per-Gaussian contribution scores (gs_contribution): n 16-byte records in a device Buffer that
+    Renderer.render(..., contributions=...) accumulates into.  Frames never clear it: clear() does."""
+
+    def __init__(self, device, n, buffer=None):
+        self.device = device
+        self.n = int(n)
+        self.buffer = buffer if buffer is not None else Buffer(device, size=max(self.n, 1) * CONTRIBUTION_DTYPE.itemsize)
+
+    @staticmethod
+    def new(device, stream, n):
+        """n zeroed records"""
+        c = Contributions(device, n)
+        c.clear(stream)
+        return c
+
+    def __len__(self):
+        return self.n
+
+    def clear(self, stream):
+        """gs_contributions_clear: zeroes the n records; only enqueues"""
+        _check(_L.gs_contributions_clear(self.buffer._h, stream._h, self.n))
+
+    def download(self, stream):
+        """the n records as a CONTRIBUTION_DTYPE array; blocking"""
+        return self.buffer.download(stream, np.uint8)[:self.n * CONTRIBUTION_DTYPE.itemsize].view(CONTRIBUTION_DTYPE)
+
+    def select(self, stream, selection, kind, lo, hi, op=SEL_SET):
+        """gs_select_contribution: selection = selection op {i : lo <= v_i <= hi}, v the CONTRIB_* value of record i
+        (SUM: sum * 2^-24, HITS: hits, MAX: wmax, each as binary32); only enqueues"""
+        if not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection")
+        if len(selection) != self.n:
+            raise ValueError("the selection has %d bits, the contributions %d records" % (len(selection), self.n))
+        _check(_L.gs_select_contribution(selection._h, stream._h, self.buffer._h, int(kind), float(lo), float(hi), select_op(op)))
+
+    def release(self):
+        self.buffer.release()
+
+
 class Snapshot:
     """gs_snapshot: the records of one selection of a GaussiansBuffer on the device, with its own copy of the mask
     (DESIGN.md §3.9).  Made by GaussiansBuffer.snapshot, written back by GaussiansBuffer.restore."""
@@ -1826,7 +1872,7 @@ class Renderer:
 
     def render(self, stream, gaussians, gaussian_transform, model_transform, camera,
                rgba_device_ptr, band=None, check=True, depth_device_ptr=None, pick_device_ptr=None,
-               pick_threshold=0.5, hide=None, tint=None, tint_rgba=None):
+               pick_threshold=0.5, hide=None, tint=None, tint_rgba=None, contributions=None):
         """gs_render_frame.  check=True (the validated use: tests, one-off renders) waits for the
         frame and, if it exceeded the pair capacity sized from earlier frames, renders it again
         with the grown buffers; check=False only enqueues (the pipelined use: a viewer's frame
@@ -1835,15 +1881,26 @@ class Renderer:
         (gs_render_frame_aux): the depth sum (expected depth = depth / alpha) and the
         caller's index of the Gaussian that takes the pixel's alpha to pick_threshold (PICK_NONE).
         hide / tint: Selections of the buffer's length (gs_render_frame_sel): the frame culls the
-        Gaussians of `hide` and mixes tint_rgba = (r, g, b, a) into the colour of those of `tint`."""
+        Gaussians of `hide` and mixes tint_rgba = (r, g, b, a) into the colour of those of `tint`.
+        contributions: a Contributions (or a Buffer of at least 16 n bytes) that the frame's blend ACCUMULATES the
+        per-Gaussian scores into (gs_render_frame_contrib); one round, no aux planes."""
         b0, b1 = band if band is not None else (0, 0xFFFFFFFF)
         fs = frame_selection(hide, tint, tint_rgba)
+        if contributions is not None and (depth_device_ptr is not None or pick_device_ptr is not None):
+            raise ValueError("a contribution frame takes no depth / pick planes")
+        cbuf = contributions.buffer if isinstance(contributions, Contributions) else contributions
         aux = None
         if depth_device_ptr is not None or pick_device_ptr is not None:
             aux = AuxTargets(C.c_void_p(depth_device_ptr or 0), C.c_void_p(pick_device_ptr or 0),
                              float(pick_threshold), 0)
         for attempt in range(4):
-            if fs is not None:
+            if cbuf is not None:
+                # (a frame skipped for pair capacity left the records untouched: the retry adds once)
+                _check(_L.gs_render_frame_contrib(self._h, stream._h, gaussians._h, C.byref(gaussian_transform),
+                                                  C.byref(model_transform), C.byref(camera), b0, b1,
+                                                  C.c_void_p(rgba_device_ptr), C.byref(fs) if fs is not None else None,
+                                                  cbuf._h))
+            elif fs is not None:
                 _check(_L.gs_render_frame_sel(self._h, stream._h, gaussians._h, C.byref(gaussian_transform),
                                               C.byref(model_transform), C.byref(camera), b0, b1,
                                               C.c_void_p(rgba_device_ptr), C.byref(aux) if aux is not None else None,
@@ -1928,17 +1985,19 @@ class FrameRing:
         return len(self.renderers)
 
     def render(self, gaussians, gaussian_transform, model_transform, camera, rgba_device_ptr, band=None, check=False,
-               depth_device_ptr=None, pick_device_ptr=None, pick_threshold=0.5, hide=None, tint=None, tint_rgba=None):
+               depth_device_ptr=None, pick_device_ptr=None, pick_threshold=0.5, hide=None, tint=None, tint_rgba=None,
+               contributions=None):
         """enqueues one frame on the next lane; returns the lane's index (its stream: `streams[lane]`).  The
         depth / pick planes as in Renderer.render: a lane writes them while later lanes run, so each lane needs its own.
         hide / tint / tint_rgba as in Renderer.render; the selections must have been filled on a stream the lane's stream is
-        ordered behind (or be synchronised) before the frame is enqueued."""
+        ordered behind (or be synchronised) before the frame is enqueued.  contributions as in Renderer.render: the lanes
+        may share one buffer (the adds are atomic)."""
         lane = self._next % len(self.renderers)
         self._next += 1
         self.renderers[lane].render(self.streams[lane], gaussians, gaussian_transform, model_transform, camera,
                                     rgba_device_ptr, band=band, check=check, depth_device_ptr=depth_device_ptr,
                                     pick_device_ptr=pick_device_ptr, pick_threshold=pick_threshold, hide=hide, tint=tint,
-                                    tint_rgba=tint_rgba)
+                                    tint_rgba=tint_rgba, contributions=contributions)
         return lane
 
     def wait(self):

@@ -264,6 +264,9 @@ SIGNATURES = {
     "gs_gaussians_buffer_export_spz_decompressed": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
     "gs_gaussians_buffer_export_spz": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
     "gs_gaussians_buffer_write": (i32, [vp, vp, vp, i32, i32, vp, sz, vp]),
+    "gs_render_frame_contrib": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]),
+    "gs_contributions_clear": (i32, [vp, vp, sz]),
+    "gs_select_contribution": (i32, [vp, vp, vp, u32, f32, f32, i32]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

@@ -1353,6 +1353,7 @@ struct Frame {
     uint32_t *zero = nullptr, *esb = nullptr, *esb2 = nullptr, *done_bits = nullptr, *open_bits = nullptr;
     gs::TileKeys tile_keys{nullptr, nullptr, 0u, 0u, 0u, nullptr, nullptr};   // null keys: the blend reads its ranges from the range array
     gs::SelIO sel{};                  // selection frames: what the preprocess kernels read (stage_selection)
+    gs_buffer *contrib = nullptr;     // contribution frames (gs_render_frame_contrib, checked there): the records the blend adds to, or null
     gsp::Requests requests() const {
         gsp::Requests q;
         q.depth_msd = r->depth_msd_req;
@@ -1360,6 +1361,7 @@ struct Frame {
         q.tile_masks = r->tile_masks_req;
         q.rounds = r->rounds_req;
         q.round1 = r->round1_req;
+        q.single_round = contrib != nullptr;
         return q;
     }
 };
@@ -1446,7 +1448,24 @@ static gs_status stage_blend(Frame &F, uint32_t round) {
     const int gcol = groups == 2 ? 0 : groups == 8 ? 2 : 1;
     if (round != 0u && groups == 1) return gs_fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
     F.tile_keys.round = round;
-    if (F.aux) {
+    if (F.contrib) {
+        // the accumulation rides in the grouped blend of the frame's only round (G = 4 where the plain frame would take k_blend)
+        typedef void (*contrib_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
+                                   const gs::FrameState *, gs::TileKeys, gs::ContribIO);
+        static const contrib_fn tbl_contrib[3][3] = {
+            {gs::k_blend_grouped<0, 2, false, false>, gs::k_blend_grouped<0, 4, false, false>, gs::k_blend_grouped<0, 8, false, false>},
+            {gs::k_blend_grouped<1, 2, false, false>, gs::k_blend_grouped<1, 4, false, false>, gs::k_blend_grouped<1, 8, false, false>},
+            {gs::k_blend_grouped<2, 2, false, false>, gs::k_blend_grouped<2, 4, false, false>, gs::k_blend_grouped<2, 8, false, false>}};
+        if (round != 0u || F.aux) return gs_fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "contribution frames take one round and no planes");
+        gs::ContribIO cio;
+        cio.rec = (uint4 *)F.contrib->ptr;
+        cio.block_list = r->list_mode ? (const uint32_t *)r->block_list.ptr : nullptr;
+        cio.order = r->last_order ? (const uint32_t *)r->last_order->ptr : nullptr;
+        hipLaunchKernelGGL(tbl_contrib[mode][gcol], dim3(F.nums.band_tiles), dim3(gs::BLEND_THREADS), 0, F.st,
+                           (uint32_t *)r->zero_region.ptr, (const uint32_t *)r->tvals[r->tsorted_side].ptr,
+                           (const uint32_t *)r->recs.ptr, F.fc, (float4 *)F.rgba, (const gs::FrameState *)r->state.ptr, F.tile_keys,
+                           cio);
+    } else if (F.aux) {
         // the depth / pick planes ride in the grouped blend (G = 4 where the plain frame would take k_blend)
         typedef void (*aux_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,
                                const gs::FrameState *, gs::TileKeys, gs::AuxIO);
@@ -1961,14 +1980,17 @@ static gs_status check_frame_args(gs_renderer *r, gs_stream *s, gs_gaussians_buf
 
 static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g, const gs_gaussian_transform_pod *gt,
                               const gs_model_transform_pod *mt, const gs_camera *cam, uint32_t band_ty0,
-                              uint32_t band_ty1, float *rgba, const gs_aux_targets *aux, const gs_frame_selection *fs = nullptr) {
+                              uint32_t band_ty1, float *rgba, const gs_aux_targets *aux, const gs_frame_selection *fs = nullptr,
+                              gs_buffer *contrib = nullptr) {
     GS_TRY(check_frame_args(r, s, g, gt, mt, cam, rgba));
+    if (contrib) GS_TRY(check_contrib_buffer(contrib, r->dev, gs_gaussians_buffer_len(g)));
     GS_TRY(use_device(r->dev));
     hipStream_t st = s->s;
     GS_TRY(collect_timing(r));
     GS_TRY(take_over_stream(r, st));
     Frame F{r, st, g, aux, rgba, fs, StageMarks{r, st, r->timing && r->ev_valid}};
     F.mode = gt->flags[0];
+    F.contrib = contrib;
     gs::FrameConsts &fc = F.fc;
     make_frame_consts(gt, mt, cam, band_ty0, band_ty1, fc);
     const size_t n64 = gs_gaussians_buffer_len(g);
@@ -2144,6 +2166,15 @@ extern "C" gs_status gs_render_frame_sel(gs_renderer *r, gs_stream *s, gs_gaussi
     GS_TRY(check_aux(aux));
     GS_TRY(check_frame_selection(r, g, fs));
     return render_frame(r, s, g, gt, mt, cam, band_ty0, band_ty1, rgba, aux, fs);
+}
+
+extern "C" gs_status gs_render_frame_contrib(gs_renderer *r, gs_stream *s, gs_gaussians_buffer *g,
+                                             const gs_gaussian_transform_pod *gt,
+                                             const gs_model_transform_pod *mt, const gs_camera *cam,
+                                             uint32_t band_ty0, uint32_t band_ty1, float *rgba,
+                                             const gs_frame_selection *fs, gs_buffer *contrib) {
+    GS_TRY(check_frame_selection(r, g, fs));
+    return render_frame(r, s, g, gt, mt, cam, band_ty0, band_ty1, rgba, nullptr, fs, contrib);
 }
 
 static gs_status download_sync(gs_renderer *r, void *dst, const void *src, size_t bytes) {

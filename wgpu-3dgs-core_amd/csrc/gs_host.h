@@ -203,6 +203,8 @@ void bbox_final_enqueue(hipStream_t st, const float *partial, uint32_t count, fl
 // ---- gs_select.hip ----
 gs_status check_selection(const gs_selection *sel, const gs_stream *s);
 gs_status check_select_op(gs_select_op op);
+// the contribution records of gs_render_frame_contrib / gs_select_contribution: n x 16 bytes, aligned, on `dev`
+gs_status check_contrib_buffer(const gs_buffer *contrib, const gs_device *dev, size_t n);
 // the selection argument of an edit / extraction / statistic: NULL (all), or n bits on the buffer's device
 gs_status check_buffer_selection(const gs_gaussians_buffer *g, const gs_stream *s, const gs_selection *sel);
 // dst = dst op src over whole words on `st` (src: another selection's words, or dst's scratch plane)

@@ -57,6 +57,9 @@ struct Switches {
 struct Requests {
     int depth_msd = -1, tile_msd = -1, tile_masks = -1, rounds = -1;
     uint32_t round1 = 0;
+    // a contribution frame (gs_render_frame_contrib): one round, whatever the pin — planned as under rounds = 0, round1 = 0.
+    // A frame skipped for pair capacity must leave the accumulators untouched, and round 1's adds could not be undone.
+    bool single_round = false;
 };
 
 // constants of the kernels the rules compare against
@@ -292,9 +295,11 @@ inline bool plan_rounds(const History &h, const FrameNums &f, const Requests &re
         }
         fb.auto_deep = deep;
         fb.auto_k = (uint64_t)k_auto;
-        const int pinned = req.rounds >= 0 ? req.rounds : sw.rounds;
+        const int req_rounds = req.single_round ? 0 : req.rounds;
+        const uint32_t req_round1 = req.single_round ? 0u : req.round1;
+        const int pinned = req_rounds >= 0 ? req_rounds : sw.rounds;
         two_round = pinned >= 0 ? pinned != 0 : deep;
-        const uint64_t k = req.round1 ? req.round1 : sw.round1 > 0 ? (uint64_t)sw.round1 : pinned > 0 && !deep ? v_est / 4u : (uint64_t)k_auto;
+        const uint64_t k = req_round1 ? req_round1 : sw.round1 > 0 ? (uint64_t)sw.round1 : pinned > 0 && !deep ? v_est / 4u : (uint64_t)k_auto;
         round_k = (uint32_t)((k + 2047u) / 2048u * 2048u < f.n ? (k + 2047u) / 2048u * 2048u : 0u);
         if (round_k == 0u) two_round = false;
     }

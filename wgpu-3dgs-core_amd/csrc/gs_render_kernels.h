@@ -3863,6 +3863,77 @@ __device__ __forceinline__ void aux_store(const AuxIO &aux, uint64_t pix, uint32
 __device__ __forceinline__ AuxIO aux_io() { return AuxIO{}; }
 __device__ __forceinline__ AuxIO aux_io(AuxIO a) { return a; }
 
+// Per-Gaussian contribution scores of a contribution frame (gs_render_frame_contrib): one 16-byte record
+// {u64 sum, u32 hits, f32 wmax} per Gaussian in CALLER index order, accumulated (never cleared) by the blend.
+struct ContribIO {
+    uint4 *rec;                    // the caller's records
+    const uint32_t *block_list;    // list frame: block of every list position; else null (as AuxIO)
+    const uint32_t *order;         // caller index of every mirror slot; null = identity
+};
+__device__ __forceinline__ AuxIO aux_io(ContribIO) { return AuxIO{}; }
+__device__ __forceinline__ ContribIO contrib_io() { return ContribIO{}; }
+__device__ __forceinline__ ContribIO contrib_io(AuxIO) { return ContribIO{}; }
+__device__ __forceinline__ ContribIO contrib_io(ContribIO c) { return c; }
+template <typename... A> struct is_contrib_pack : std::false_type {};
+template <> struct is_contrib_pack<ContribIO> : std::true_type {};
+__device__ __forceinline__ uint32_t contrib_caller_index(const ContribIO &c, uint32_t slot) {
+    if (c.block_list) slot = c.block_list[slot / (uint32_t)PP_CHUNK] * (uint32_t)PP_CHUNK + slot % (uint32_t)PP_CHUNK;
+    return c.order ? c.order[slot] : slot;
+}
+// the value of lane (l ^ OFF) for OFF = 1, 2 (quad permutes) and, on values that are already uniform over aligned groups of
+// OFF lanes, OFF = 4, 8 (the mirrors of 8 and 16 lanes land in the other half) and 16 (swizzle inside 32 lanes)
+template <int OFF> __device__ __forceinline__ uint32_t contrib_other_half(uint32_t v) {
+    static_assert(OFF == 1 || OFF == 2 || OFF == 4 || OFF == 8 || OFF == 16, "inside a group of at most 32 lanes");
+    if constexpr (OFF == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);        // quad_perm [1,0,3,2]
+    else if constexpr (OFF == 2) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
+    else if constexpr (OFF == 4) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true);  // row_half_mirror
+    else if constexpr (OFF == 8) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true);  // row_mirror
+    else return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);                                            // lane ^ 16
+}
+// One lock step of a contribution frame: the lane group of GL lanes has blended ONE staged splat (accumulator `acc`: the
+// byte offset of its word in s_max, the same in every lane of the group) into its 2 GL pixels with the weights w0, w1 (0: no
+// contribution).  The three integer reductions over the group — add the truncated weights in units of 2^-24, count the
+// positive ones, max of the bit patterns — then two no-return LDS atomics of the group's first lane into the splat's
+// accumulators of this batch: one 64-bit add of (hits << 32 | sum) — a tile has 256 pixels and a weight is below 2^24 units,
+// so a batch's sum stays below 2^32 and never carries into the count — and one max.  Every lane of the wave calls it (the
+// cross-lane reads need their sources).
+template <int GL>
+__device__ __forceinline__ void contrib_add(unsigned long long *s_qh, uint32_t *s_max, uint32_t acc, float w0, float w1, uint32_t lg) {
+    uint32_t q = (uint32_t)(w0 * 16777216.0f) + (uint32_t)(w1 * 16777216.0f);
+    uint32_t h = (w0 > 0.0f ? 1u : 0u) + (w1 > 0.0f ? 1u : 0u);
+    uint32_t m = f2u(w0) > f2u(w1) ? f2u(w0) : f2u(w1);
+#define GS_CONTRIB_FOLD(OFF)                                  \
+    if constexpr (GL > OFF) {                                 \
+        const uint32_t oq = contrib_other_half<OFF>(q);       \
+        const uint32_t oh = contrib_other_half<OFF>(h);       \
+        const uint32_t om = contrib_other_half<OFF>(m);       \
+        q += oq;                                              \
+        h += oh;                                              \
+        m = om > m ? om : m;                                  \
+    }
+    GS_CONTRIB_FOLD(1)
+    GS_CONTRIB_FOLD(2)
+    GS_CONTRIB_FOLD(4)
+    GS_CONTRIB_FOLD(8)
+    GS_CONTRIB_FOLD(16)
+#undef GS_CONTRIB_FOLD
+    if (lg == 0u && h != 0u) {
+        (void)__hip_atomic_fetch_add((unsigned long long *)((char *)s_qh + 2u * acc), ((unsigned long long)h << 32) | q, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+        (void)__hip_atomic_fetch_max((uint32_t *)((char *)s_max + acc), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+// Once per batch and thread: what the tile's pixels added to the splat this thread staged goes to the Gaussian's record with
+// three no-return atomics (one 64-byte line).  Called behind a barrier that follows the batch's blend loops.
+__device__ __forceinline__ void contrib_flush(const ContribIO &c, uint32_t index, unsigned long long qh, uint32_t m) {
+    if ((uint32_t)(qh >> 32) != 0u) {
+        uint4 *p = c.rec + index;
+        (void)__hip_atomic_fetch_add((unsigned long long *)p, qh & 0xffffffffull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_add((uint32_t *)p + 2, (uint32_t)(qh >> 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_max((uint32_t *)p + 3, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // One workgroup (2 waves) = one 16x16 tile, wave h = pixel rows 8h..8h+7, two pixels per lane on
 // packed f32 — as k_blend — but the wave's 64 lanes are split into G lane groups that own
 // different sub-blocks of the half-tile (G = 2: two 8x8 blocks, G = 4: four 8x4 blocks, G = 8: eight 4x4
@@ -3879,6 +3950,10 @@ __device__ __forceinline__ AuxIO aux_io(AuxIO a) { return a; }
 // AUX: the instantiation that also writes the depth and pick planes; its one extra argument, the
 // AuxIO, is a parameter pack that is empty in the plain instantiations, so that they keep the launch signature they share
 // with k_blend and the kernel-argument layout (and code) they had before the planes existed.
+// CONTRIB (the pack holds one ContribIO instead): the instantiation of contribution frames, which also adds
+// every blend weight to its Gaussian's record.  A lock step blends G different splats, so the weights are reduced per lane
+// group (contrib_add) into LDS accumulators of the batch's staged records, and each thread flushes its record's once per
+// batch with global atomics (contrib_flush).  Measured against atomics straight from every group step: NOTES.md.
 template <int MODE, int G, bool ROUNDS = false, bool AUX = false, typename... AuxArg>
 __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__restrict__ ranges,
                                                                  const uint32_t *__restrict__ idx,
@@ -3886,7 +3961,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                                                                  FrameConsts fc, float4 *__restrict__ rgba,
                                                                  const FrameState *__restrict__ state, TileKeys tk,
                                                                  AuxArg... aux_arg) {
-    static_assert(sizeof...(AuxArg) == (AUX ? 1u : 0u), "the AUX blend takes one AuxIO, the plain one none");
+    // CONTRIB: the instantiation of contribution frames: its one extra argument is a ContribIO in the same pack
+    // (so the plain, ROUNDS and AUX instantiations keep their names, argument layouts and code); single-round, no planes
+    constexpr bool CONTRIB = is_contrib_pack<AuxArg...>::value;
+    static_assert(sizeof...(AuxArg) == (AUX || CONTRIB ? 1u : 0u), "the AUX blend takes one AuxIO, the CONTRIB one one ContribIO, the plain one none");
+    static_assert(!CONTRIB || (!AUX && !ROUNDS), "contribution frames take one round and no planes");
     static_assert(G == 2 || G == 4 || G == 8, "lane groups per wave");
     if (state->overflow) return;              // frame skipped: see k_blend
     constexpr int GL = WAVE / G;              // lanes per group
@@ -3897,7 +3976,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     constexpr int NL = 2 * G;                 // lists per tile (= NCOL * NROW)
     static_assert(NCOL * NROW == NL && G == NCOL * (NROW / 2), "one list per block, G blocks per wave");
     constexpr uint32_t NULL_REC = BLEND_BATCH;
-    // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, pmin, opacity, r | g, b, -, -} (AUX: {.. | g, b, z', slot}).  The
+    // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, pmin, opacity, r | g, b, -, -} (AUX: {.. | g, b, z', slot}; CONTRIB: {.. | g, b, -, accumulator offset}).  The
     // lists hold the records' BYTE OFFSETS (16 bits each), so a step's three LDS reads share one address
     // register and differ only in the instruction's immediate offset: no shift / mask per step.
     constexpr uint32_t RS = 48;
@@ -3949,6 +4028,20 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     f32x2 D = {0.0f, 0.0f};
     uint32_t pk0 = PICK_NONE, pk1 = PICK_NONE;
     const AuxIO aux = aux_io(aux_arg...);
+    const ContribIO cio = contrib_io(aux_arg...);
+    // CONTRIB: one accumulator pair per staged record, (hits << 32 | sum) and max, zeroed by the record's staging thread and
+    // flushed by it to the Gaussian's record (caller index my_index) behind the barrier that follows the batch's blend loops:
+    // at the top of the next batch, before the all-pixels-finished break, or behind the loop
+    unsigned long long *s_qh = nullptr;
+    uint32_t *s_max = nullptr;
+    uint32_t my_index = 0u;
+    bool flush_pending = false;     // workgroup-uniform: the loop's control flow is
+    if constexpr (CONTRIB) {
+        __shared__ __attribute__((aligned(8))) unsigned long long s_contrib_qh[BLEND_BATCH];
+        __shared__ uint32_t s_contrib_max[BLEND_BATCH];
+        s_qh = s_contrib_qh;
+        s_max = s_contrib_max;
+    }
     if (AUX && ROUNDS && tk.round == 2u) {
         if (in0) {
             if (aux.depth) D.x = aux.depth[(uint64_t)py0 * fc.width + px];
@@ -3965,7 +4058,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     if (tid == 0) {   // the null record: power = 0 everywhere, pmin = 1 -> "power >= pmin" never holds
         *(float4 *)(s_rec + NULL_REC * (RS / 4)) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         *(float4 *)(s_rec + NULL_REC * (RS / 4) + 4) = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
-        if constexpr (AUX) *(float4 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if constexpr (AUX || CONTRIB) *(float4 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         else *(float2 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float2(0.0f, 0.0f);
     }
 
@@ -3973,6 +4066,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         // stop fetching once every pixel of the tile is finished
         if (lane == 0) s_alive[wid] = remaining;
         __syncthreads();
+        if constexpr (CONTRIB) {
+            if (flush_pending) contrib_flush(cio, my_index, s_qh[tid], s_max[tid]);
+            flush_pending = false;
+        }
         if ((s_alive[0] | s_alive[1]) == 0u) break;
 
         // lists start out as all-null (the previous batch's loops ended before the barrier above)
@@ -3995,6 +4092,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         // set-ups, the block tests and the list build: all its verdicts are zero.  The branch is wave-uniform, and the
         // barriers below stay outside of it: both waves meet at them.
         const bool staging = __builtin_amdgcn_ballot_w64(have) != 0ull;
+        if constexpr (CONTRIB) {   // (its own slot, read by this thread just above; the batch's adds lie behind two barriers)
+            s_qh[tid] = 0ull;
+            s_max[tid] = 0u;
+        }
         uint64_t m[NL];
         if (!staging) {
 #pragma unroll
@@ -4017,6 +4118,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 if constexpr (AUX)
                     *(float4 *)(s_rec + tid * (RS / 4) + 8) =
                         make_float4(u2f(r1.w), u2f(r2x), u2f(aux.depth_keys[slot] + aux.key_bias), u2f(slot));
+                else if constexpr (CONTRIB) {
+                    *(float4 *)(s_rec + tid * (RS / 4) + 8) = make_float4(u2f(r1.w), u2f(r2x), 0.0f, u2f(tid * 4u));
+                    my_index = contrib_caller_index(cio, slot);
+                }
                 else
                     *(float2 *)(s_rec + tid * (RS / 4) + 8) = make_float2(u2f(r1.w), u2f(r2x));
             }
@@ -4189,9 +4294,9 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         }                                                                                                     \
         if (__builtin_amdgcn_ballot_w64(p0 || p1) != 0ull) {                                                  \
             float2 cq; /* g, b */                                                                             \
-            float zq = 0.0f; /* AUX: depth, slot */                                                           \
+            float zq = 0.0f; /* AUX: depth, slot; CONTRIB: -, accumulator */                                  \
             uint32_t sq = 0u;                                                                                 \
-            if constexpr (AUX) {                                                                              \
+            if constexpr (AUX || CONTRIB) {                                                                   \
                 const float4 c4 = *(const float4 *)(rbase + ID + 32);                                         \
                 cq = make_float2(c4.x, c4.y);                                                                 \
                 zq = c4.z;                                                                                    \
@@ -4243,6 +4348,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 pk0 = alpha_eff.x > 0.0f && T.x > aux.tcut ? sq : pk0;                                        \
                 pk1 = alpha_eff.y > 0.0f && T.y > aux.tcut ? sq : pk1;                                        \
             }                                                                                                 \
+            if constexpr (CONTRIB) { /* wgt = 0 exactly where the step is no contribution (alpha_eff = 0) */  \
+                if (__builtin_amdgcn_ballot_w64(wgt.x > 0.0f || wgt.y > 0.0f) != 0ull)                        \
+                    contrib_add<GL>(s_qh, s_max, sq, wgt.x, wgt.y, lg);                                       \
+            }                                                                                                 \
             T = test_T;                                                                                       \
         }                                                                                                     \
     }
@@ -4257,6 +4366,13 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 GS_BLEND_STEP(a_B, b_B, id_B)
             }
 #undef GS_BLEND_STEP
+        }
+        if constexpr (CONTRIB) flush_pending = true;
+    }
+    if constexpr (CONTRIB) {
+        if (flush_pending) {   // the range's last batch
+            __syncthreads();
+            contrib_flush(cio, my_index, s_qh[tid], s_max[tid]);
         }
     }
     if (ROUNDS && tk.round == 1u) {

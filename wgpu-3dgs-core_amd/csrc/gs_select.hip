@@ -174,6 +174,44 @@ extern "C" gs_status gs_select_box(gs_selection *sel, gs_stream *s, gs_gaussians
     return select_shape(sel, s, g, mt, true, world_to_box, op);
 }
 
+// the caller's contribution records: n x 16 bytes, 16-byte aligned, on `dev`
+gs_status gsh::check_contrib_buffer(const gs_buffer *contrib, const gs_device *dev, size_t n) {
+    if (!contrib || !contrib->ptr) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (contrib->dev != dev) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
+    if (n > contrib->bytes / sizeof(gs_contribution))
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, contrib->bytes, n, 0, "the contribution buffer holds %zu bytes, %zu records need %zu", contrib->bytes, n,
+                       n * sizeof(gs_contribution));
+    if ((uintptr_t)contrib->ptr & 15u)
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, (uint64_t)(uintptr_t)contrib->ptr, 16, 0, "the contribution records must be 16-byte aligned");
+    return GS_OK;
+}
+
+extern "C" gs_status gs_contributions_clear(gs_buffer *contrib, gs_stream *s, size_t n) {
+    if (!contrib || !s) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    GS_TRY(check_contrib_buffer(contrib, s->dev, n));
+    GS_TRY(use_device(s->dev));
+    if (!n) return GS_OK;
+    GS_HIP(hipMemsetAsync(contrib->ptr, 0, n * sizeof(gs_contribution), s->s));
+    return GS_OK;
+}
+
+extern "C" gs_status gs_select_contribution(gs_selection *sel, gs_stream *s, gs_buffer *contrib, uint32_t kind, float lo, float hi,
+                                            gs_select_op op) {
+    GS_TRY(check_selection(sel, s));
+    GS_TRY(check_select_op(op));
+    if (kind > (uint32_t)GS_CONTRIB_MAX) return gs_fail(GS_ERR_INVALID_ARGUMENT, kind, 0, 0, "unknown contribution kind %u", (unsigned)kind);
+    if (lo != lo || hi != hi) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "a bound of the range is NaN");
+    GS_TRY(check_len32(sel->n));
+    GS_TRY(check_contrib_buffer(contrib, sel->dev, sel->n));
+    sel->generation = next_object_id();
+    if (!sel->n) return GS_OK;
+    const uint32_t n = (uint32_t)sel->n;
+    hipLaunchKernelGGL(gs::k_select_contrib, dim3((n + 255u) / 256u), dim3(256), 0, s->s, (const uint4 *)contrib->ptr, n, kind, lo, hi, sel->words,
+                       (uint32_t)op);
+    GS_HIP(hipGetLastError());
+    return GS_OK;
+}
+
 void gsh::sel_range_enqueue(gs_selection *sel, hipStream_t st, uint32_t start, uint32_t end, gs_select_op op) {
     hipLaunchKernelGGL(gs::k_sel_range, dim3(sel->grid()), dim3(256), 0, st, sel->words, (uint32_t)sel->nwords, start, end, (uint32_t)op);
 }

@@ -76,4 +76,24 @@ __global__ __launch_bounds__(256) void k_select_shape(const uint32_t *__restrict
     if ((lane & 31u) == 0u && i < n) words[word] = sel_apply(words[word], (uint32_t)(m >> lane), op);
 }
 
+// gs_select_contribution: one thread per 16-byte record {u64 sum, u32 hits, f32 wmax}, one 16-byte load;
+// kind 0: (float)sum * 2^-24 (u64 -> f32 to nearest even, the scale exact), 1: (float)hits, 2: wmax.  The mask is written as
+// by k_select_shape.
+__global__ __launch_bounds__(256) void k_select_contrib(const uint4 *__restrict__ recs, uint32_t n, uint32_t kind, float lo, float hi,
+                                                        uint32_t *__restrict__ words, uint32_t op) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool hit = false;
+    if (i < n) {
+        const uint4 r = recs[i];
+        float v;
+        if (kind == 0u) v = __ull2float_rn(((unsigned long long)r.y << 32) | r.x) * 0x1p-24f;
+        else if (kind == 1u) v = __uint2float_rn(r.z);
+        else v = u2f(r.w);
+        hit = lo <= v && v <= hi;
+    }
+    const uint64_t m = __ballot(hit);
+    const uint32_t lane = threadIdx.x & 63u, word = i >> 5;
+    if ((lane & 31u) == 0u && i < n) words[word] = sel_apply(words[word], (uint32_t)(m >> lane), op);
+}
+
 }  // namespace gs
