@@ -85,6 +85,8 @@ pub const GS_CONTRIB_SUM: u32 = 0;
 pub const GS_CONTRIB_HITS: u32 = 1;
 pub const GS_CONTRIB_MAX: u32 = 2;
 
+pub const GS_COMPARE_SSIM: u32 = 1;
+
 #[repr(C)] pub struct gs_device { _private: [u8; 0] }
 #[repr(C)] pub struct gs_stream { _private: [u8; 0] }
 #[repr(C)] pub struct gs_buffer { _private: [u8; 0] }
@@ -346,6 +348,31 @@ pub struct gs_contribution {
     pub wmax: f32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_image_compare_desc {
+    pub flags: u32,
+    pub data_range: f32,
+    pub err_plane: *mut f32,
+    pub ssim_plane: *mut f32,
+    pub reserved: [u32; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_image_metrics {
+    pub pixels: u64,
+    pub finite: u64,
+    pub differing: u64,
+    pub bit_differing: u64,
+    pub sum_sq: [f64; 4],
+    pub sum_abs: [f64; 4],
+    pub max_abs: [f32; 4],
+    pub max_abs_at: [u32; 4],
+    pub ssim_sum: [f64; 3],
+    pub ssim_finite: [u64; 3],
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -505,6 +532,7 @@ extern "C" {
     pub fn gs_render_frame_contrib(r: *mut gs_renderer, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, gaussian_transform: *const gs_gaussian_transform_pod, model_transform: *const gs_model_transform_pod, camera: *const gs_camera, band_ty0: u32, band_ty1: u32, rgba_out_device: *mut f32, fs: *const gs_frame_selection, contrib: *mut gs_buffer) -> gs_status;
     pub fn gs_contributions_clear(contrib: *mut gs_buffer, s: *mut gs_stream, n: usize) -> gs_status;
     pub fn gs_select_contribution(sel: *mut gs_selection, s: *mut gs_stream, contrib: *mut gs_buffer, kind: u32, lo: f32, hi: f32, op: u32) -> gs_status;
+    pub fn gs_image_compare(dev: *mut gs_device, s: *mut gs_stream, a: *const f32, b: *const f32, width: u32, height: u32, desc: *const gs_image_compare_desc, out: *mut gs_image_metrics) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

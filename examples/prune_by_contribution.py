@@ -4,9 +4,12 @@
 stays below a threshold, extract the others and write them — all on the device; the scene is downloaded once, as the
 pruned file.
 usage: python examples/prune_by_contribution.py tests/golden/model.ply pruned.ply [--views 24] [--radius 4] [--height 0.5]
-       [--size 640x360] [--threshold 0.5] [--pod ShSingle/Cov3dRotScale]          (needs a GPU: there is no CPU fallback)
+       [--size 640x360] [--threshold 0.5] [--pod ShSingle/Cov3dRotScale] [--report-quality]
+                                                                                   (needs a GPU: there is no CPU fallback)
        threshold: in units of "fully covered pixels", summed over all views (1.0 = the weight of one opaque pixel in one view);
-       0 removes exactly the Gaussians no view blended."""
+       0 removes exactly the Gaussians no view blended.
+       --report-quality: renders the orbit's views again from the original and from the pruned buffer and prints PSNR and
+       SSIM per view and their means (gs_image_compare); no image is downloaded."""
 import argparse
 import os
 import sys
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--size", default="640x360")
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--pod", default="ShSingle/Cov3dRotScale")
+    ap.add_argument("--report-quality", action="store_true")
     args = ap.parse_args()
     sh, cov = args.pod.split("/")
     pod = getattr(gs, "GaussianPodWith%s%sConfigs" % (sh, cov))
@@ -44,11 +48,14 @@ def main():
     scores = gs.Contributions.new(dev, stream, n)
     r = gs.Renderer(dev)
     gt, mt = gs.gaussian_transform_pod(sh_deg=3), gs.model_transform_pod()
-    for k in range(args.views):
+
+    def camera(k):
         a = 2.0 * np.pi * k / args.views
         eye = (target[0] + args.radius * np.sin(a), target[1] + args.height, target[2] + args.radius * np.cos(a))
-        cam = gs.camera_look_at(eye, target, (0, 1, 0), float(np.deg2rad(60.0)), W, H)
-        r.render(stream, buf, gt, mt, cam, img.device_ptr(), contributions=scores)      # accumulates; never clears
+        return gs.camera_look_at(eye, target, (0, 1, 0), float(np.deg2rad(60.0)), W, H)
+
+    for k in range(args.views):
+        r.render(stream, buf, gt, mt, camera(k), img.device_ptr(), contributions=scores)      # accumulates; never clears
     low = gs.Selection(dev, n)
     if args.threshold > 0.0:
         scores.select(stream, low, gs.CONTRIB_SUM, 0.0, args.threshold)
@@ -60,6 +67,22 @@ def main():
     rec = scores.download(stream)
     print("%d Gaussians, %d views: %d never blended, %d below %g -> %d kept -> %s" % (
         n, args.views, int((rec["hits"] == 0).sum()), removed, args.threshold, len(kept), args.out))
+    if args.report_quality:
+        # what the pruning cost: every view of the orbit from both buffers, compared where the images are (gs_image_compare,
+        # DESIGN.md §3.14); only the 176-byte record of each view comes back
+        img2 = gs.Buffer(dev, size=W * H * 16)
+        psnr, ssim = [], []
+        for k in range(args.views):
+            r.render(stream, buf, gt, mt, camera(k), img.device_ptr())
+            r.render(stream, kept, gt, mt, camera(k), img2.device_ptr())
+            m = gs.image_compare(dev, stream, img.device_ptr(), img2.device_ptr(), W, H, ssim=True)
+            psnr.append(m.psnr())
+            ssim.append(m.ssim)
+            print("view %2d: PSNR %s dB  SSIM %.6f  %d of %d pixels differ, max |d| %.4g" % (
+                k, "inf" if m.identical or np.isinf(psnr[-1]) else "%.2f" % psnr[-1], ssim[-1], m.differing, m.pixels, float(m.max_abs[:3].max())))
+        finite = [p for p in psnr if np.isfinite(p)]
+        print("mean over %d views: PSNR %s dB (%d views unchanged)  SSIM %.6f" % (
+            args.views, "%.2f" % np.mean(finite) if finite else "inf", len(psnr) - len(finite), float(np.mean(ssim))))
 
 
 if __name__ == "__main__":

@@ -1150,6 +1150,61 @@ gs_status gs_contributions_clear(gs_buffer *contrib, gs_stream *s, size_t n);
 gs_status gs_select_contribution(gs_selection *sel, gs_stream *s, gs_buffer *contrib, uint32_t kind, float lo, float hi,
                                  gs_select_op op);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Image metrics (no reference item): what a change of the scene did to the    */
+/* rendered picture, measured where the pictures are                                            */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  Two images of H x W pixels, four binary32 channels r g b a each, in the
+ * layout of rgba_out_device.  d_c = a_c - b_c, one binary32 subtraction.  A pixel is FINITE when its eight values are; only
+ * finite pixels enter the sums, maxima and `differing`.  The sums are binary64, added in a fixed shape (no floating-point
+ * atomics): two calls on the same inputs return the same bytes.
+ * SSIM (flag GS_COMPARE_SSIM) is the usual 3DGS metric per colour channel: an 11 x 11 Gaussian window, sigma 1.5, zero padding,
+ * every pixel counted.  It is defined operation by operation in binary32, every operation rounded, nothing fused, the
+ * division correctly rounded: the weights g[0..10] (binary32 of exp(-(k-5)^2 / 4.5) / sum); the five planes a, b, a a, a b, b b
+ * (products rounded per pixel) filtered horizontally, then vertically, each as acc = +0, acc = acc + g[k] v for k = 0..10
+ * ascending, samples outside the image +0; C1 = (0.01f L)^2, C2 = (0.03f L)^2; and with ma, mb, eaa, eab, ebb the filtered planes
+ *   maa = ma ma, mbb = mb mb, mab = ma mb, saa = eaa - maa, sbb = ebb - mbb, sab = eab - mab,
+ *   s = ((2 mab + C1) (2 sab + C2)) / (((maa + mbb) + C1) ((saa + sbb) + C2)).
+ * Identical images give s = 1.0f exactly.  A non-finite input makes exactly the windows that contain it non-finite; those
+ * values are left out of ssim_sum and ssim_finite.  Against a binary64 evaluation a value is off by about 1e-5 on ordinary
+ * images and by up to a few 1e-4 where an image is nearly constant over the window (eaa - maa cancels). */
+enum { GS_COMPARE_SSIM = 1 };
+/* What gs_image_compare computes besides the error fields (no reference item).  err_plane[p] =
+ * fmaxf(fmaxf(fmaxf(|d_r|, |d_g|), |d_b|), |d_a|) of a finite pixel, the quiet NaN 0x7FC00000 of any other;
+ * ssim_plane[p] = ((s_r + s_g) + s_b) / 3.0f.  A plane that overlaps an image (or the other plane) is the caller's error. */
+typedef struct gs_image_compare_desc {
+    uint32_t flags;          /* GS_COMPARE_SSIM or 0 */
+    float data_range;        /* L: finite, > 0 (1 for the renderer's images) */
+    float *err_plane;        /* device H x W f32, or NULL */
+    float *ssim_plane;       /* device H x W f32, or NULL; needs GS_COMPARE_SSIM */
+    uint32_t reserved[4];    /* 0 */
+} gs_image_compare_desc;
+/* The result of gs_image_compare (no reference item).  MSE of channel c = sum_sq[c] / finite; the mean SSIM
+ * of channel c = ssim_sum[c] / ssim_finite[c]. */
+typedef struct gs_image_metrics {
+    uint64_t pixels;         /* W * H */
+    uint64_t finite;         /* pixels whose 8 values (4 of a, 4 of b) are all finite */
+    uint64_t differing;      /* finite pixels with some d_c != 0 */
+    uint64_t bit_differing;  /* pixels (finite or not) where any of the four 32-bit words differs */
+    double sum_sq[4];        /* over finite pixels, per channel r g b a: sum of (double)d_c * (double)d_c */
+    double sum_abs[4];       /* sum of (double)|d_c| */
+    float max_abs[4];        /* max |d_c| over finite pixels; 0 when there is none */
+    uint32_t max_abs_at[4];  /* smallest y * W + x that attains it; 0xFFFFFFFF when finite == 0 */
+    double ssim_sum[3];      /* r g b: sum of the FINITE per-pixel SSIM values; 0 without the flag */
+    uint64_t ssim_finite[3]; /* how many were finite */
+} gs_image_metrics;
+/* Compares two device images in one pass (no reference item).  `a` and `b` are device pointers to H x W x 4
+ * binary32 values, 16-byte aligned; they may be equal.  desc == NULL: flags 0, L = 1, no planes.  BLOCKING, like
+ * gs_gaussians_buffer_stats (`out` is host memory); s == NULL: the device's internal stream.  The device keeps the scratch of
+ * the call (144 bytes per workgroup, at most 2048 of them); calls on one device from several host threads take
+ * turns.  Without GS_COMPARE_SSIM each image is read exactly once.  GS_ERR_INVALID_ARGUMENT, before anything is enqueued and
+ * with *out untouched, for a null device, image or out, a zero dimension, W * H > 2^32 - 2, an image that is not 16-byte
+ * aligned or a plane that is not 4-byte aligned, unknown flags, nonzero `reserved`, a data_range that is not finite or not
+ * positive, ssim_plane without GS_COMPARE_SSIM, a stream of another device. */
+gs_status gs_image_compare(gs_device *dev, gs_stream *s, const float *a, const float *b, uint32_t width, uint32_t height,
+                           const gs_image_compare_desc *desc, gs_image_metrics *out);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

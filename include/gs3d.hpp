@@ -5,9 +5,11 @@
 // carrying the variant fields of src/error.rs.  Citations are relative to the reference.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -766,6 +768,25 @@ template <class G>
 inline void pack_device(Device &d, Stream &s, const Buffer &gaussians, size_t count, Buffer &pods) {
     check(gs_pack_device(d.raw(), s.raw(), G::sh, G::cov3d, static_cast<const gs_gaussian *>(gaussians.device_ptr()), count,
                          pods.device_ptr()));
+}
+
+// Two device images (H x W x 4 float each, 16-byte aligned; e.g. two rgba_out_device targets) compared on the device
+// (gs3d.h gs_image_compare; no reference item): error sums, maxima and counts per channel and, with
+// desc.flags = GS_COMPARE_SSIM, the sums of the per-pixel SSIM.  desc == nullptr: no SSIM, L = 1, no planes.  Blocking.
+inline gs_image_metrics image_compare(Device &d, Stream &s, const float *a, const float *b, uint32_t width, uint32_t height,
+                                      const gs_image_compare_desc *desc = nullptr) {
+    gs_image_metrics out;
+    check(gs_image_compare(d.raw(), s.raw(), a, b, width, height, desc, &out));
+    return out;
+}
+// what a caller derives from the record: the mean squared error over r g b, its PSNR (infinity at 0), the mean SSIM
+inline double image_mse_rgb(const gs_image_metrics &m) { return ((m.sum_sq[0] + m.sum_sq[1]) + m.sum_sq[2]) / (3.0 * (double)m.finite); }
+inline double image_psnr(const gs_image_metrics &m, double data_range = 1.0) {
+    const double e = image_mse_rgb(m);
+    return e == 0.0 ? std::numeric_limits<double>::infinity() : 10.0 * std::log10(data_range * data_range / e);
+}
+inline double image_ssim(const gs_image_metrics &m) {
+    return ((m.ssim_sum[0] / (double)m.ssim_finite[0] + m.ssim_sum[1] / (double)m.ssim_finite[1]) + m.ssim_sum[2] / (double)m.ssim_finite[2]) / 3.0;
 }
 
 }  // namespace gs3d

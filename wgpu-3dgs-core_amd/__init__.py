@@ -2016,6 +2016,104 @@ class FrameRing:
         self.renderers, self.streams = [], []
 
 
+COMPARE_SSIM = 1      # GS_COMPARE_SSIM
+
+
+@dataclasses.dataclass
+class ImageMetrics:
+    """gs_image_metrics: the raw fields of gs_image_compare, channels r g b a (SSIM: r g b), and what a
+    caller derives from them on the host."""
+    pixels: int
+    finite: int
+    differing: int
+    bit_differing: int
+    sum_sq: np.ndarray        # float64[4]
+    sum_abs: np.ndarray       # float64[4]
+    max_abs: np.ndarray       # float32[4]
+    max_abs_at: np.ndarray    # uint32[4]
+    ssim_sum: np.ndarray      # float64[3]
+    ssim_finite: np.ndarray   # uint64[3]
+    raw: bytes = b""          # the 176 bytes of the record as the library wrote it
+
+    @property
+    def mse(self):
+        """sum_sq / finite per channel (NaN without a finite pixel)"""
+        with np.errstate(all="ignore"):
+            return self.sum_sq / np.float64(self.finite)
+
+    @property
+    def mse_rgb(self):
+        """the mean squared error over the three colour channels of the finite pixels"""
+        with np.errstate(all="ignore"):
+            return float(((self.sum_sq[0] + self.sum_sq[1]) + self.sum_sq[2]) / np.float64(3 * self.finite))
+
+    def psnr(self, data_range=1.0):
+        """10 log10(L^2 / mse_rgb); inf when the colour channels are equal"""
+        m = self.mse_rgb
+        if m == 0.0:
+            return float("inf")
+        return float(10.0 * np.log10(float(data_range) ** 2 / m))
+
+    @property
+    def ssim_channels(self):
+        """ssim_sum / ssim_finite per colour channel (NaN without the SSIM flag)"""
+        with np.errstate(all="ignore"):
+            return self.ssim_sum / self.ssim_finite.astype(np.float64)
+
+    @property
+    def ssim(self):
+        """the mean of the three channel means"""
+        c = self.ssim_channels
+        return float(((c[0] + c[1]) + c[2]) / 3.0)
+
+    @property
+    def identical(self):
+        return self.bit_differing == 0
+
+
+def _device_address(p, what):
+    if isinstance(p, bool) or not isinstance(p, (int, np.integer)):
+        raise TypeError("%s must be a device address (an integer), not %s" % (what, type(p).__name__))
+    return int(p)
+
+
+def image_compare(device, stream, a_ptr, b_ptr, width, height, ssim=False, data_range=1.0, err_plane_ptr=None, ssim_plane_ptr=None):
+    """gs_image_compare: an ImageMetrics of the two device images a, b (H x W x 4 float32 each, 16-byte
+    aligned, e.g. Buffer.device_ptr() of two frames) — error sums, maxima and counts per channel and, with ssim=True, the
+    sums of the 11 x 11-window SSIM of the colour channels.  err_plane_ptr / ssim_plane_ptr: device H x W float32 planes
+    that receive the per-pixel largest |difference| / mean SSIM.  Blocking; stream None: the device's internal stream."""
+    if not isinstance(device, Device):
+        raise TypeError("device must be a Device, not %s" % type(device).__name__)
+    if stream is not None and not isinstance(stream, Stream):
+        raise TypeError("stream must be a Stream or None, not %s" % type(stream).__name__)
+    a, b = _device_address(a_ptr, "a_ptr"), _device_address(b_ptr, "b_ptr")
+    for name, v in (("width", width), ("height", height)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s must be an integer, not %s" % (name, type(v).__name__))
+    if not (0 < int(width) <= 0xFFFFFFFF and 0 < int(height) <= 0xFFFFFFFF) or int(width) * int(height) > 0xFFFFFFFE:
+        raise ValueError("an image of %d x %d pixels cannot be compared" % (width, height))
+    L = float(data_range)
+    with np.errstate(over="ignore"):
+        L32 = np.float32(L)
+    if not (np.isfinite(L32) and L32 > 0):
+        raise ValueError("data_range must be finite and positive, not %r" % (data_range,))
+    if ssim_plane_ptr is not None and not ssim:
+        raise ValueError("ssim_plane_ptr needs ssim=True")
+    d = _capi.ImageCompareDesc()
+    d.flags = COMPARE_SSIM if ssim else 0
+    d.data_range = L
+    d.err_plane = _device_address(err_plane_ptr, "err_plane_ptr") if err_plane_ptr is not None else None
+    d.ssim_plane = _device_address(ssim_plane_ptr, "ssim_plane_ptr") if ssim_plane_ptr is not None else None
+    out = _capi.ImageMetricsRecord()
+    _check(_L.gs_image_compare(device._h, stream._h if stream is not None else None, C.c_void_p(a), C.c_void_p(b), int(width),
+                               int(height), C.byref(d), C.byref(out)))
+    return ImageMetrics(pixels=int(out.pixels), finite=int(out.finite), differing=int(out.differing),
+                        bit_differing=int(out.bit_differing), sum_sq=np.array(out.sum_sq[:], np.float64),
+                        sum_abs=np.array(out.sum_abs[:], np.float64), max_abs=np.array(out.max_abs[:], np.float32),
+                        max_abs_at=np.array(out.max_abs_at[:], np.uint32), ssim_sum=np.array(out.ssim_sum[:], np.float64),
+                        ssim_finite=np.array(out.ssim_finite[:], np.uint64), raw=bytes(out))
+
+
 def sort_pairs_u64(device, stream, keys, values, end_bit=64):
     """Device radix sort of host arrays (stable LSD on key bits [0, end_bit)); returns copies."""
     k = np.ascontiguousarray(keys, dtype=np.uint64).copy()

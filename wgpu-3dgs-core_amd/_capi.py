@@ -78,6 +78,18 @@ class Stats(C.Structure):
     _fields_ = [("count", u64), ("attr", AttributeStats * 9)]
 
 
+class ImageCompareDesc(C.Structure):
+    """gs_image_compare_desc: flags, data range and the optional device planes of gs_image_compare"""
+    _fields_ = [("flags", u32), ("data_range", f32), ("err_plane", vp), ("ssim_plane", vp), ("reserved", u32 * 4)]
+
+
+class ImageMetricsRecord(C.Structure):
+    """gs_image_metrics: what gs_image_compare fills"""
+    _fields_ = [("pixels", u64), ("finite", u64), ("differing", u64), ("bit_differing", u64), ("sum_sq", C.c_double * 4),
+                ("sum_abs", C.c_double * 4), ("max_abs", f32 * 4), ("max_abs_at", u32 * 4), ("ssim_sum", C.c_double * 3),
+                ("ssim_finite", u64 * 3)]
+
+
 class SortInfo(C.Structure):
     _fields_ = [("depth_msd", u32), ("depth_bucket_max", u32), ("bucket_capacity", u32), ("tile_msd", u32),
                 ("tile_bucket_max", u32), ("tile_masks", u32), ("rounds", u32), ("round1", u32), ("tiles_done", u32), ("partitioned", u32)]
@@ -267,6 +279,7 @@ SIGNATURES = {
     "gs_render_frame_contrib": (i32, [vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp]),
     "gs_contributions_clear": (i32, [vp, vp, sz]),
     "gs_select_contribution": (i32, [vp, vp, vp, u32, f32, f32, i32]),
+    "gs_image_compare": (i32, [vp, vp, vp, vp, u32, u32, vp, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

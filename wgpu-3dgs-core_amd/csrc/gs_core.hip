@@ -318,6 +318,7 @@ extern "C" void gs_device_destroy(gs_device *dev) {
     if (!dev) return;
     (void)hipSetDevice(dev->ordinal);
     (void)hipStreamDestroy(dev->internal);
+    dev_free(dev->metrics_scratch);
     delete dev;
 }
 

@@ -44,6 +44,12 @@
 // device / stream / buffer
 // ------------------------------------------------------------------------------------------------
 
+// a device array that grows and never shrinks (hipFree synchronises the device)
+struct DevArray {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
+
 struct gs_device {
     int ordinal;
     gs_limits limits;
@@ -56,6 +62,9 @@ struct gs_device {
     // stream that is going away (the event is otherwise recorded lazily, when the renderer moves to another stream)
     std::mutex renderers_mu;
     std::vector<struct gs_renderer *> renderers;
+    // gs_image_compare: the partial rows and the device result of the last call; the call holds the mutex
+    std::mutex metrics_mu;
+    DevArray metrics_scratch;
 };
 
 struct gs_stream {
@@ -70,12 +79,6 @@ struct gs_buffer {
     size_t bytes;
     bool owned;
     std::atomic<int> refs;
-};
-
-// a device array that grows and never shrinks (hipFree synchronises the device)
-struct DevArray {
-    void *ptr = nullptr;
-    size_t bytes = 0;
 };
 
 namespace gsh {
