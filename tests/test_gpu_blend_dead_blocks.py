@@ -29,7 +29,6 @@ ranges and `stopped` flags are asserted to say what the scene was built for befo
                 splat whose block maximum is within 0.1 above pmin reaches alpha >= 1/255 on a pixel of the block whose
                 final alpha is far from saturation — what a threshold that is too tight would lose."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -40,6 +39,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import gpu_child  # noqa: E402
 import helpers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -235,46 +235,42 @@ def _gaussians(name, case):
 
 def _child(out):
     """renders every case under this process's switches"""
-    import wgpu_3dgs_core_amd as gs
-    from test_gpu_render_aux import Planes
-    dev = gs.Device(0)
-    st = dev.create_stream()
-    res = {}
-    cases = dict(CASES)
-    cases["rounds"] = ROUNDS_CASE
-    for name, case in cases.items():
-        kind, W, H, mode, band, vfov = case
-        pod = gs.GaussianPod(SH, COV)
-        pods = pod.from_gaussian(_gaussians(name, case))
-        gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
-        mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
-        cam = helpers.default_camera(gs, W, H, vfov_deg=vfov)
-        buf = gs.GaussiansBuffer.new_with_pods(dev, pod, pods)
-        r = gs.Renderer(dev)
-        if kind != "rounds":
-            img = gs.Buffer(dev, data=np.full(H * W * 4, helpers.POISON))
-            r.render(st, buf, gt, mt, cam, img.device_ptr(), band=band)
-            st.synchronize()
-            res[name + "/rgba"] = img.download(st, np.float32).reshape(H, W, 4).copy()
-            img.release()
-        else:
-            r.set_rounds(1, ROUND1)
-            pl = Planes(gs, dev, W, H)
-            for frame in range(2):       # the second frame of a two-round renderer is partitioned
-                pl.poison(st)
-                pl.render(r, st, buf, gt, mt, cam, band=band)
-                si = r.sort_info()
-                rgba, depth, pick = pl.get(st)
-                res["%s/f%d/rgba" % (name, frame)] = rgba
-                res["%s/f%d/depth" % (name, frame)] = depth
-                res["%s/f%d/pick" % (name, frame)] = pick
-                res["%s/f%d/info" % (name, frame)] = np.array([si.rounds, si.round1, si.tiles_done], dtype=np.int64)
-            pl.release()
-        r.destroy()
-        buf.destroy()
-    np.savez(out, **res)
-    st.close()
-    dev.close()
+    with gpu_child.child_rig() as (gs, _, dev, st):
+        from test_gpu_render_aux import Planes
+        res = {}
+        cases = dict(CASES)
+        cases["rounds"] = ROUNDS_CASE
+        for name, case in cases.items():
+            kind, W, H, mode, band, vfov = case
+            pod = gs.GaussianPod(SH, COV)
+            pods = pod.from_gaussian(_gaussians(name, case))
+            gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
+            mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
+            cam = helpers.default_camera(gs, W, H, vfov_deg=vfov)
+            buf = gs.GaussiansBuffer.new_with_pods(dev, pod, pods)
+            r = gs.Renderer(dev)
+            if kind != "rounds":
+                img = gs.Buffer(dev, data=np.full(H * W * 4, helpers.POISON))
+                r.render(st, buf, gt, mt, cam, img.device_ptr(), band=band)
+                st.synchronize()
+                res[name + "/rgba"] = img.download(st, np.float32).reshape(H, W, 4).copy()
+                img.release()
+            else:
+                r.set_rounds(1, ROUND1)
+                pl = Planes(gs, dev, W, H)
+                for frame in range(2):       # the second frame of a two-round renderer is partitioned
+                    pl.poison(st)
+                    pl.render(r, st, buf, gt, mt, cam, band=band)
+                    si = r.sort_info()
+                    rgba, depth, pick = pl.get(st)
+                    res["%s/f%d/rgba" % (name, frame)] = rgba
+                    res["%s/f%d/depth" % (name, frame)] = depth
+                    res["%s/f%d/pick" % (name, frame)] = pick
+                    res["%s/f%d/info" % (name, frame)] = np.array([si.rounds, si.round1, si.tiles_done], dtype=np.int64)
+                pl.release()
+            r.destroy()
+            buf.destroy()
+        np.savez(out, **res)
 
 
 @pytest.fixture(scope="module")
@@ -286,12 +282,9 @@ def frames(tmp_path_factory):
     def get(groups):
         if groups not in cache:
             out = os.path.join(str(tmp), "g%d.npz" % groups)
-            env = dict(os.environ)
-            env["GS3D_BLEND_GROUPS"] = str(groups)
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), out], cwd=ROOT, env=env,
-                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-            assert res.returncode == 0, res.stdout[-3000:]
-            cache[groups] = dict(np.load(out))
+            gpu_child.run([os.path.abspath(__file__), out], env={"GS3D_BLEND_GROUPS": str(groups)}, timeout=300,
+                          label="GS3D_BLEND_GROUPS=%d" % groups)
+            cache[groups] = gpu_child.load_npz(out)
         return cache[groups]
     return get
 

@@ -18,7 +18,6 @@ no final T is below 1e-4; what the dense case asserts on the oracle's side is th
 own sorted lists finds a step with T (1 - alpha) < 0.9e-4, a margin f32 rounding cannot cross, at a pixel whose final T
 in the oracle's image is the T before that step."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -29,6 +28,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import gpu_child  # noqa: E402
 import helpers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -61,55 +61,47 @@ def _gaussians(case):
 
 def _child(set_name, out):
     """renders every case of the set under this process's switches"""
-    import wgpu_3dgs_core_amd as gs
-    from test_gpu_render_aux import Planes
-    cases = SETS[set_name][0]
-    dev = gs.Device(0)
-    st = dev.create_stream()
-    res = {}
-    for name, case in cases.items():
-        W, H, n, first, mode, band, dense = case
-        pod = gs.GaussianPod(SH, COV)
-        pods = pod.from_gaussian(_gaussians(case))
-        gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
-        mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
-        cam = helpers.default_camera(gs, W, H, **CAMERA.get(name, {}))
-        buf = gs.GaussiansBuffer.new_with_pods(dev, pod, pods)
-        r = gs.Renderer(dev)
-        if set_name == "plain":
-            img = gs.Buffer(dev, data=np.full(H * W * 4, np.float32(-7.0)))
-            r.render(st, buf, gt, mt, cam, img.device_ptr(), band=band)
-            st.synchronize()
-            res[name + "/rgba"] = img.download(st, np.float32).reshape(H, W, 4).copy()
-            img.release()
-        else:
-            pl = Planes(gs, dev, W, H)
-            for frame in range(2):       # the second frame of a two-round renderer is partitioned
-                pl.poison(st)
-                pl.render(r, st, buf, gt, mt, cam, band=band)
-                si = r.sort_info()
-                rgba, depth, pick = pl.get(st)
-                res["%s/f%d/rgba" % (name, frame)] = rgba
-                res["%s/f%d/depth" % (name, frame)] = depth
-                res["%s/f%d/pick" % (name, frame)] = pick
-                res["%s/f%d/info" % (name, frame)] = np.array([si.rounds, si.round1, si.tiles_done], dtype=np.int64)
-            pl.release()
-        r.destroy()
-        buf.destroy()
-    np.savez(out, **res)
-    st.close()
-    dev.close()
+    with gpu_child.child_rig() as (gs, _, dev, st):
+        from test_gpu_render_aux import Planes
+        cases = SETS[set_name][0]
+        res = {}
+        for name, case in cases.items():
+            W, H, n, first, mode, band, dense = case
+            pod = gs.GaussianPod(SH, COV)
+            pods = pod.from_gaussian(_gaussians(case))
+            gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
+            mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
+            cam = helpers.default_camera(gs, W, H, **CAMERA.get(name, {}))
+            buf = gs.GaussiansBuffer.new_with_pods(dev, pod, pods)
+            r = gs.Renderer(dev)
+            if set_name == "plain":
+                img = gs.Buffer(dev, data=np.full(H * W * 4, np.float32(-7.0)))
+                r.render(st, buf, gt, mt, cam, img.device_ptr(), band=band)
+                st.synchronize()
+                res[name + "/rgba"] = img.download(st, np.float32).reshape(H, W, 4).copy()
+                img.release()
+            else:
+                pl = Planes(gs, dev, W, H)
+                for frame in range(2):       # the second frame of a two-round renderer is partitioned
+                    pl.poison(st)
+                    pl.render(r, st, buf, gt, mt, cam, band=band)
+                    si = r.sort_info()
+                    rgba, depth, pick = pl.get(st)
+                    res["%s/f%d/rgba" % (name, frame)] = rgba
+                    res["%s/f%d/depth" % (name, frame)] = depth
+                    res["%s/f%d/pick" % (name, frame)] = pick
+                    res["%s/f%d/info" % (name, frame)] = np.array([si.rounds, si.round1, si.tiles_done], dtype=np.int64)
+                pl.release()
+            r.destroy()
+            buf.destroy()
+        np.savez(out, **res)
 
 
 def _run_child(tmp, groups, set_name):
     out = os.path.join(str(tmp), "g%d_%s.npz" % (groups, set_name))
-    env = dict(os.environ)
-    env.update(SETS[set_name][1])
-    env["GS3D_BLEND_GROUPS"] = str(groups)
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), set_name, out], cwd=ROOT, env=env,
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout[-3000:]
-    return dict(np.load(out))
+    gpu_child.run([os.path.abspath(__file__), set_name, out], env=dict(SETS[set_name][1], GS3D_BLEND_GROUPS=str(groups)),
+                  timeout=300, label="GS3D_BLEND_GROUPS=%d %s" % (groups, set_name))
+    return gpu_child.load_npz(out)
 
 
 @pytest.fixture(scope="module")

@@ -28,7 +28,6 @@ the splats of `full` 1182 small ones in tile 5, which fill round 1 up to 2048; b
 `counts`, which are round 2 — every resumed tile stages a list of one of the lengths above; and 4096 Gaussians behind
 the camera, which add no pair."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -39,6 +38,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import gpu_child  # noqa: E402
 import helpers  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -133,53 +133,46 @@ def _gaussians(scene, W, H):
 
 def _child(set_name, out):
     """renders every case of the set under this process's switches"""
-    import wgpu_3dgs_core_amd as gs
-    from test_gpu_render_aux import Planes
-    dev = gs.Device(0)
-    st = dev.create_stream()
-    res = {}
-    for name, (scene, W, H, mode, band) in SETS[set_name].items():
-        pod = gs.GaussianPod(SH, COV)
-        pods = pod.from_gaussian(_gaussians(scene, W, H))
-        gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
-        mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
-        cam = helpers.default_camera(gs, W, H)
-        buf = gs.GaussiansBuffer.new_with_pods(dev, pod, pods)
-        r = gs.Renderer(dev)
-        if set_name == "plain":
-            img = gs.Buffer(dev, data=np.full(H * W * 4, helpers.POISON))
-            r.render(st, buf, gt, mt, cam, img.device_ptr(), band=band)
-            st.synchronize()
-            res[name + "/rgba"] = img.download(st, np.float32).reshape(H, W, 4).copy()
-            img.release()
-        else:
-            r.set_rounds(1, ROUND1)
-            pl = Planes(gs, dev, W, H)
-            for frame in range(2):       # the second frame of a two-round renderer is partitioned
-                pl.poison(st)
-                pl.render(r, st, buf, gt, mt, cam, band=band)
-                si = r.sort_info()
-                rgba, depth, pick = pl.get(st)
-                res["%s/f%d/rgba" % (name, frame)] = rgba
-                res["%s/f%d/depth" % (name, frame)] = depth
-                res["%s/f%d/pick" % (name, frame)] = pick
-                res["%s/f%d/info" % (name, frame)] = np.array([si.rounds, si.round1, si.tiles_done], dtype=np.int64)
-            pl.release()
-        r.destroy()
-        buf.destroy()
-    np.savez(out, **res)
-    st.close()
-    dev.close()
+    with gpu_child.child_rig() as (gs, _, dev, st):
+        from test_gpu_render_aux import Planes
+        res = {}
+        for name, (scene, W, H, mode, band) in SETS[set_name].items():
+            pod = gs.GaussianPod(SH, COV)
+            pods = pod.from_gaussian(_gaussians(scene, W, H))
+            gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
+            mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
+            cam = helpers.default_camera(gs, W, H)
+            buf = gs.GaussiansBuffer.new_with_pods(dev, pod, pods)
+            r = gs.Renderer(dev)
+            if set_name == "plain":
+                img = gs.Buffer(dev, data=np.full(H * W * 4, helpers.POISON))
+                r.render(st, buf, gt, mt, cam, img.device_ptr(), band=band)
+                st.synchronize()
+                res[name + "/rgba"] = img.download(st, np.float32).reshape(H, W, 4).copy()
+                img.release()
+            else:
+                r.set_rounds(1, ROUND1)
+                pl = Planes(gs, dev, W, H)
+                for frame in range(2):       # the second frame of a two-round renderer is partitioned
+                    pl.poison(st)
+                    pl.render(r, st, buf, gt, mt, cam, band=band)
+                    si = r.sort_info()
+                    rgba, depth, pick = pl.get(st)
+                    res["%s/f%d/rgba" % (name, frame)] = rgba
+                    res["%s/f%d/depth" % (name, frame)] = depth
+                    res["%s/f%d/pick" % (name, frame)] = pick
+                    res["%s/f%d/info" % (name, frame)] = np.array([si.rounds, si.round1, si.tiles_done], dtype=np.int64)
+                pl.release()
+            r.destroy()
+            buf.destroy()
+        np.savez(out, **res)
 
 
 def _run_child(tmp, groups, set_name):
     out = os.path.join(str(tmp), "g%d_%s.npz" % (groups, set_name))
-    env = dict(os.environ)
-    env["GS3D_BLEND_GROUPS"] = str(groups)
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), set_name, out], cwd=ROOT, env=env,
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout[-3000:]
-    return dict(np.load(out))
+    gpu_child.run([os.path.abspath(__file__), set_name, out], env={"GS3D_BLEND_GROUPS": str(groups)}, timeout=300,
+                  label="GS3D_BLEND_GROUPS=%d %s" % (groups, set_name))
+    return gpu_child.load_npz(out)
 
 
 @pytest.fixture(scope="module")

@@ -3,13 +3,12 @@
 Every field of a record is an integer reduction, so the records are defined bit for bit: they are compared, as raw 16-byte
 rows, with the expectation that tests/contrib_np.py derives from the frozen oracle's blend."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import contrib_np as cn
+import gpu_child
 import helpers
 
 pytestmark = pytest.mark.gpu
@@ -243,11 +242,8 @@ def test_blend_groups_switch(gs, ob, device, stream, groups, tmp_path):
         want.append(sc.oracle()[1])
         sc.release()
     out = str(tmp_path / "records.npy")
-    env = dict(os.environ)
-    env["GS3D_BLEND_GROUPS"] = str(groups)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "contrib_child.py"), out], cwd=ROOT, env=env,
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    assert res.returncode == 0 and "contrib_child OK" in res.stdout, res.stdout[-3000:]
+    gpu_child.run([os.path.join(ROOT, "tests", "contrib_child.py"), out], env={"GS3D_BLEND_GROUPS": str(groups)}, timeout=300,
+                  label="GS3D_BLEND_GROUPS=%d" % groups, expect="contrib_child OK")
     got = np.load(out)
     for mode in (0, 1, 2):
         _same(got[mode], want[mode], "GS3D_BLEND_GROUPS=%d mode %d" % (groups, mode))

@@ -6,11 +6,11 @@ refused layouts, a short capacity, and the ordering behind an edit on another st
 import ctypes as C
 import importlib.util
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import gpu_child
 
 pytestmark = pytest.mark.gpu
 
@@ -145,10 +145,8 @@ print("slices OK")
 def test_export_ply_across_slice_boundaries():
     """n = 3000 with GS3D_EXPORT_SLICE=1024: three slices, two boundaries, both staging buffers (the switch is read once per
     process, hence the child)"""
-    env = dict(os.environ, GS3D_EXPORT_SLICE="1024")
-    res = subprocess.run([sys.executable, "-c", _SLICE_CHILD % (ROOT, ROOT)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                         text=True, timeout=120)
-    assert res.returncode == 0 and "slices OK" in res.stdout, res.stdout
+    gpu_child.run(["-c", _SLICE_CHILD % (ROOT, ROOT)], env={"GS3D_EXPORT_SLICE": "1024"}, timeout=120,
+                  label="GS3D_EXPORT_SLICE=1024", expect="slices OK")
 
 
 # ---- SPZ -------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,6 @@ The same cases run in a child process under GS3D_NT_LOADS=1 (the non-temporal ha
 renderer picks by itself only above 512 MB of records) and in one under GS3D_PRE_PIPELINE=0 (the serial two-phase
 kernels); the switches are read once per process."""
 import os
-import subprocess
 import sys
 import types
 
@@ -32,6 +31,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import gpu_child  # noqa: E402
 import helpers  # noqa: E402
 import test_gpu_renderer_walk as walk  # noqa: E402
 from helpers import POISON, band_rows, bits  # noqa: E402
@@ -433,9 +433,6 @@ def test_enlarged_gaussians_reach_in_from_blocks_outside_the_view(gs, ob, device
 # the same cases under GS3D_NT_LOADS=1 and under GS3D_PRE_PIPELINE=0: one child process per switch, one at a time
 # ------------------------------------------------------------------------------------------------
 
-_child_state = {"dead": None}        # the child that ended on a signal or a timeout: nothing further is started on the GPU
-
-
 @gpu
 @pytest.mark.parametrize("env", [{"GS3D_NT_LOADS": "1"}, {"GS3D_PRE_PIPELINE": "0"}],
                          ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
@@ -445,17 +442,7 @@ def test_every_path_of_every_layout_under_switch(env):
     false>, with and without SelIO."""
     if any(os.environ.get(k) == v for k, v in env.items()):
         pytest.skip("already running under this switch")
-    assert _child_state["dead"] is None, "not started: the %s child ended abnormally" % _child_state["dead"]
-    child_env = dict(os.environ)
-    child_env.update(env)
-    try:
-        res = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu",
-                              "-k", "test_every_path_of_a_layout or test_enlarged_gaussians", "-p", "no:cacheprovider"],
-                             cwd=ROOT, env=child_env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-    except subprocess.TimeoutExpired:
-        _child_state["dead"] = env
-        raise
-    if res.returncode < 0 or res.returncode >= 124:      # a signal, an abort, a time limit
-        _child_state["dead"] = env
-    assert res.returncode == 0, res.stdout[-3000:]
+    res = gpu_child.run(["-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu",
+                         "-k", "test_every_path_of_a_layout or test_enlarged_gaussians", "-p", "no:cacheprovider"],
+                        env=env, timeout=300, label=",".join("%s=%s" % kv for kv in env.items()))
     assert "%d passed" % (2 * len(LAYOUTS)) in res.stdout and "deselected" in res.stdout, res.stdout[-1000:]

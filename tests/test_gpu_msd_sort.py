@@ -6,6 +6,7 @@ sorts, which follows the bucket sizes the frames report."""
 import numpy as np
 import pytest
 
+import gpu_child
 import helpers
 from test_gpu_render import _compare_frame, _mirror_order, _oracle_frame
 
@@ -181,8 +182,6 @@ def test_tile_masks_follow_the_scene_size_unless_pinned(gs, device, stream):
     kernel is instruction-bound and the tile test would cost more than the pairs it saves — and a scene beyond 512 MB of
     records with version 4; both pins override."""
     import os
-    import subprocess
-    import sys
     code = (
         "import sys; sys.path[:0] = [%r, %r]\n"
         "import numpy as np, synth, wgpu_3dgs_core_amd as gs\n"
@@ -201,10 +200,7 @@ def test_tile_masks_follow_the_scene_size_unless_pinned(gs, device, stream):
         "        out.append((n, mode, r.sort_info().tile_masks, r.stats().pairs)); r.destroy()\n"
         "    buf.destroy()\n"
         "print('RESULT', out)\n" % (ROOT_DIR, os.path.join(ROOT_DIR, 'tools')))
-    env = dict(os.environ)
-    env.pop("GS3D_TILE_MASKS", None)
-    res = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert res.returncode == 0 and "RESULT" in res.stdout, res.stdout[-3000:]
+    res = gpu_child.run(["-c", code], unset=("GS3D_TILE_MASKS",), timeout=600, label="unpinned tile masks", expect="RESULT")
     out = eval(res.stdout.split("RESULT", 1)[1].strip())
     by = {(n, mode): (masks, pairs) for n, mode, masks, pairs in out}
     assert by[(20000, -1)][0] == 0 and by[(2500000, -1)][0] == 1, by          # the renderer's own choice

@@ -9,17 +9,15 @@ The hardware does not fail on demand: GS3D_TEST_RANK_FAULT=1 (read once per proc
 watchdog's expectation by one, so that it fires in the first frame of a renderer.  Each case therefore
 runs in a child process — one at a time."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import gpu_child
 import helpers
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARMED = os.environ.get("GS3D_TEST_RANK_FAULT") == "1"
 
 
@@ -165,12 +163,10 @@ def test_watchdog_children(extra):
     tile 1 of every pass, never tile 0), pinned to an arbitrary tile / round (GS3D_TEST_RANK_WATCH: tile = n mod live
     tiles, round = (n / live tiles) mod keys per lane — round 4 only ever looked at tile 0, round 0), and with the depth
     sort's LSD passes instead of the MSD-first sort (whose bucket kernel carries its own check)."""
-    env = dict(os.environ, GS3D_TEST_RANK_FAULT="1", **extra)
-    res = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu",
-                          "-k", "child", "-p", "no:cacheprovider"], cwd=ROOT, env=env, stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:]
-    assert "4 passed" in res.stdout, res.stdout[-1000:]       # (a child that skipped its cases is a failure)
+    env = dict(extra, GS3D_TEST_RANK_FAULT="1")
+    gpu_child.run(["-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu", "-k", "child", "-p", "no:cacheprovider"],
+                  env=env, timeout=600, label=",".join("%s=%s" % kv for kv in env.items()),
+                  expect="4 passed")       # (a child that skipped its cases is a failure)
 
 
 @pytest.mark.skipif(ARMED, reason="this is the child")

@@ -6,27 +6,20 @@ first (wgpu-3dgs-core_amd/_hiprt.py; round 2 died with "No HIP GPUs are availabl
 product-first order).  One child at a time; a child never re-execs."""
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 
+import gpu_child
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _child(order, env=None, timeout=600):
-    e = dict(os.environ)
-    e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    e.update(env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "tests", "rccl_child.py"), order], cwd=ROOT, env=e,
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("order", ["product-first", "torch-first"])
 def test_rccl_world1_frame_pipeline_on_dedicated_stream(order):
-    res = _child(order)
-    assert res.returncode == 0, res.stdout[-4000:]
+    res = gpu_child.run([os.path.join(ROOT, "tests", "rccl_child.py"), order], timeout=600, label="rccl " + order,
+                        env={"HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")})
     line = [x for x in res.stdout.splitlines() if x.startswith("{")][-1]
     j = json.loads(line)
     assert j["ok"] and j["backend"] == "nccl" and j["world_size"] == 1
@@ -61,9 +54,7 @@ def test_import_orders_share_one_hip_runtime_cpu():
             "print(json.dumps(import_module('wgpu_3dgs_core_amd._hiprt').check()))\n")
     seen = []
     for imports in ("import wgpu_3dgs_core_amd\nimport torch", "import torch\nimport wgpu_3dgs_core_amd"):
-        res = subprocess.run([sys.executable, "-c", code % (ROOT, imports)], stdout=subprocess.PIPE,
-                             stderr=subprocess.STDOUT, text=True, timeout=600)
-        assert res.returncode == 0, res.stdout[-3000:]
+        res = gpu_child.run(["-c", code % (ROOT, imports)], timeout=600, label="import order")
         m = json.loads(res.stdout.strip().splitlines()[-1])
         assert all(len(v) == 1 for v in m.values()), m
         seen.append(m)
@@ -78,9 +69,7 @@ def test_forced_system_runtime_then_torch_is_refused_cpu():
             "import wgpu_3dgs_core_amd, torch\n"
             "from importlib import import_module\n"
             "import_module('wgpu_3dgs_core_amd._hiprt').check('torch')\n") % ROOT
-    env = dict(os.environ, GS3D_HIP_RUNTIME="system")
-    res = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                         text=True, timeout=600)
+    res = gpu_child.run(["-c", code], env={"GS3D_HIP_RUNTIME": "system"}, timeout=600, label="system runtime, then torch", check=False)
     assert res.returncode != 0 and "two HIP runtimes" in res.stdout, res.stdout[-2000:]
     assert "GS3D_HIP_RUNTIME=system" in res.stdout           # the message names the ways out
 
@@ -96,10 +85,7 @@ def test_forced_system_runtime_without_torch_imports_fine_cpu():
             "assert h.info()['source'] == 'system' and len(m['libamdhip64']) == 1 and 'torch' not in m['libamdhip64'][0]\n"
             "c, r, d = gs.hip_versions(); assert c > 0 and r > 0\n"
             "print('ok', c, r)\n") % ROOT
-    env = dict(os.environ, GS3D_HIP_RUNTIME="system")
-    res = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                         text=True, timeout=600)
-    assert res.returncode == 0 and "ok" in res.stdout, res.stdout[-2000:]
+    gpu_child.run(["-c", code], env={"GS3D_HIP_RUNTIME": "system"}, timeout=600, label="system runtime, no torch", expect="ok")
 
 
 @needs_bundled_torch
@@ -123,8 +109,6 @@ def test_soname_mismatch_falls_back_to_the_system_runtime_cpu():
             "    assert h.prepare() == 'system' and not h.info()['preloaded'] and 'libamdhip64.so.99' in h.info()['note']\n"
             "    assert not h.mapped()['libamdhip64']\n"
             "    print('fell back')\n") % ROOT
-    res = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert res.returncode == 0 and "fell back" in res.stdout, res.stdout[-2000:]
-    res = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, GS3D_HIP_RUNTIME="torch"), stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert res.returncode == 0 and "refused:" in res.stdout and "libamdhip64.so.99" in res.stdout, res.stdout[-2000:]
+    gpu_child.run(["-c", code], timeout=600, label="SONAME mismatch, auto", expect="fell back")
+    res = gpu_child.run(["-c", code], env={"GS3D_HIP_RUNTIME": "torch"}, timeout=600, label="SONAME mismatch, torch", expect="refused:")
+    assert "libamdhip64.so.99" in res.stdout, res.stdout[-2000:]

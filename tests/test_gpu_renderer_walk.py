@@ -14,7 +14,6 @@ parent compares with its own cached oracle frames.
 The figures in KINDS' comments (V visible Gaussians, D pairs, the longest tile list) are the oracle's, asserted below
 without a GPU; the shapes are the smallest that still reach the paths named."""
 import os
-import subprocess
 import sys
 import types
 
@@ -26,6 +25,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import gpu_child  # noqa: E402
 import helpers  # noqa: E402
 import rounds_np  # noqa: E402
 from helpers import band_rows, bits  # noqa: E402
@@ -485,24 +485,14 @@ def test_buffer_swap_overflows_an_unchanged_shape(gs, ob, device, stream):
 # ------------------------------------------------------------------------------------------------
 
 CHILD_ENV = {2: {"GS3D_BLEND_GROUPS": "2"}, 1: {"GS3D_BLEND_GROUPS": "1", "GS3D_RANGES_IN_BLEND": "1"}}
-_child_state = {"dead": None}        # the child that ended on a signal or a timeout: nothing further is started on the GPU
 
 
 def _child(groups, out):
-    for key, val in (("GS3D_TILE_MASKS", "1"), ("GS3D_ROUNDS", "0"), ("GS3D_ROUND_PARTITION", "1")):      # tests/conftest.py's pins
-        os.environ.setdefault(key, val)
     assert os.environ.get("GS3D_BLEND_GROUPS") == str(groups)
-    import wgpu_3dgs_core_amd as gs
-    from oracle import binding as ob
-    ob.build()
-    ob.lib()
-    dev = gs.Device(0)
-    st = dev.create_stream()
-    record = {}
-    walk(gs, ob, dev, st, groups=groups, record=record)      # an AssertionError ends the child: nonzero, the message on stdout
-    np.savez(out, **record)
-    st.close()
-    dev.close()
+    with gpu_child.child_rig() as (gs, ob, dev, st):
+        record = {}
+        walk(gs, ob, dev, st, groups=groups, record=record)      # an AssertionError ends the child: nonzero, the message on stdout
+        np.savez(out, **record)
 
 
 @pytest.fixture(scope="module")
@@ -510,20 +500,10 @@ def child_frames(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("renderer_walk")
 
     def run(groups):
-        assert _child_state["dead"] is None, "not started: the GS3D_BLEND_GROUPS=%s child ended abnormally" % _child_state["dead"]
         out = os.path.join(str(tmp), "walk_g%d.npz" % groups)
-        env = dict(os.environ)
-        env.update(CHILD_ENV[groups])
-        try:
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), str(groups), out], cwd=ROOT, env=env,
-                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-        except subprocess.TimeoutExpired:
-            _child_state["dead"] = groups
-            raise
-        if res.returncode < 0 or res.returncode >= 124:      # a signal, an abort, a time limit
-            _child_state["dead"] = groups
-        assert res.returncode == 0, res.stdout[-3000:]
-        return dict(np.load(out))
+        gpu_child.run([os.path.abspath(__file__), str(groups), out], env=CHILD_ENV[groups], timeout=300,
+                      label="GS3D_BLEND_GROUPS=%d" % groups)
+        return gpu_child.load_npz(out)
     return run
 
 

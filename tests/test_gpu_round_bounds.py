@@ -15,7 +15,6 @@ boundary of the depth key's top 10 bits with at least K Gaussians in front of it
 both.  tests/conftest.py pins GS3D_ROUND_PARTITION=1; one child process (this file as a script) runs three of the sequences
 under GS3D_ROUND_PARTITION=0 and hands its frames back in an .npz that the parent compares with the same oracle frames."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -26,6 +25,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import gpu_child  # noqa: E402
 import helpers  # noqa: E402
 import rounds_np  # noqa: E402
 from helpers import POISON, band_rows, bits, capacity_for  # noqa: E402
@@ -483,24 +483,15 @@ def test_planes_and_the_flags_word_over_a_skipped_frame(gs, ob, rig):
 # ------------------------------------------------------------------------------------------------
 
 def _child(out):
-    for key, val in (("GS3D_TILE_MASKS", "1"), ("GS3D_ROUNDS", "0")):      # tests/conftest.py's other pins
-        os.environ.setdefault(key, val)
     assert os.environ.get("GS3D_ROUND_PARTITION") == "0"
-    import wgpu_3dgs_core_amd as gs
-    from oracle import binding as ob
-    ob.build()
-    ob.lib()
-    dev = gs.Device(0)
-    st = dev.create_stream()
-    rg = Rig(gs, ob, dev, st)
-    record = {}
-    for name in CHILD_SEQUENCES:
-        for k, v in run_sequence(rg, name).items():
-            record["%s/%s" % (name, k)] = v
-    np.savez(out, **record)
-    rg.release()
-    st.close()
-    dev.close()
+    with gpu_child.child_rig() as (gs, ob, dev, st):
+        rg = Rig(gs, ob, dev, st)
+        record = {}
+        for name in CHILD_SEQUENCES:
+            for k, v in run_sequence(rg, name).items():
+                record["%s/%s" % (name, k)] = v
+        np.savez(out, **record)
+        rg.release()
 
 
 @gpu
@@ -511,12 +502,8 @@ def test_the_sequences_with_round_2_compacted_out_of_the_full_order(ob, runs, tm
     for i in range(1, len(SEQUENCES["round2"]["frames"])):
         assert int(runs("round2")["f%d/info" % i][INFO.index("partitioned")]) == _partition() == 1
     out = os.path.join(str(tmp_path), "bounds_p0.npz")
-    env = dict(os.environ)
-    env["GS3D_ROUND_PARTITION"] = "0"
-    res = subprocess.run([sys.executable, os.path.abspath(__file__), out], cwd=ROOT, env=env, stdout=subprocess.PIPE,
-                         stderr=subprocess.STDOUT, text=True, timeout=120)
-    assert res.returncode == 0, res.stdout[-3000:]
-    rec = dict(np.load(out))
+    gpu_child.run([os.path.abspath(__file__), out], env={"GS3D_ROUND_PARTITION": "0"}, timeout=120, label="GS3D_ROUND_PARTITION=0")
+    rec = gpu_child.load_npz(out)
     for name in CHILD_SEQUENCES:
         sub = {k[len(name) + 1:]: v for k, v in rec.items() if k.startswith(name + "/")}
         for i in range(len(SEQUENCES[name]["frames"])):

@@ -24,7 +24,6 @@ The mixed and the band case also run in one child process (this file as a script
 kernel has a ROUNDS instantiation other than the default's (k_blend_grouped<MODE, 4, true>): 2 and 8.  The child hands its
 frames back in an .npz that the parent checks against the same model."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -35,6 +34,7 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import gpu_child  # noqa: E402
 import helpers  # noqa: E402
 import rounds_np  # noqa: E402
 from helpers import POISON, band_rows, bits  # noqa: E402
@@ -556,48 +556,26 @@ def test_depth_planes_and_distributions_under_two_rounds(ob, rig, pi, dc):
 # the other blend kernels with a ROUNDS instantiation: one child process per GS3D_BLEND_GROUPS, one at a time
 # ------------------------------------------------------------------------------------------------
 
-_child_state = {"dead": None}        # the child that ended on a signal or a timeout: nothing further is started on the GPU
-
-
 def _child(groups, out):
-    for key, val in (("GS3D_TILE_MASKS", "1"), ("GS3D_ROUNDS", "0"), ("GS3D_ROUND_PARTITION", "1")):      # tests/conftest.py's pins
-        os.environ.setdefault(key, val)
     assert os.environ.get("GS3D_BLEND_GROUPS") == str(groups)
-    import wgpu_3dgs_core_amd as gs
-    from oracle import binding as ob
-    ob.build()
-    ob.lib()
-    dev = gs.Device(0)
-    st = dev.create_stream()
-    rg = Rig(gs, ob, dev, st)
-    record = {}
-    for name in CHILD_CASES:
-        for k, v in run_case(rg, name).items():
-            record["%s/%s" % (name, k)] = v
-    np.savez(out, **record)
-    rg.release()
-    st.close()
-    dev.close()
+    with gpu_child.child_rig() as (gs, ob, dev, st):
+        rg = Rig(gs, ob, dev, st)
+        record = {}
+        for name in CHILD_CASES:
+            for k, v in run_case(rg, name).items():
+                record["%s/%s" % (name, k)] = v
+        np.savez(out, **record)
+        rg.release()
 
 
 @gpu
 @pytest.mark.parametrize("groups", CHILD_GROUPS)
 def test_the_counts_under_the_other_blend_kernels(ob, tmp_path, groups):
     """GS3D_BLEND_GROUPS=2 / 8: k_blend_grouped<MODE, 2, true> / <MODE, 8, true> set the done and open bits"""
-    assert _child_state["dead"] is None, "not started: the GS3D_BLEND_GROUPS=%s child ended abnormally" % _child_state["dead"]
     out = os.path.join(str(tmp_path), "counts_g%d.npz" % groups)
-    env = dict(os.environ)
-    env["GS3D_BLEND_GROUPS"] = str(groups)
-    try:
-        res = subprocess.run([sys.executable, os.path.abspath(__file__), str(groups), out], cwd=ROOT, env=env,
-                             stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=90)
-    except subprocess.TimeoutExpired:
-        _child_state["dead"] = groups
-        raise
-    if res.returncode < 0 or res.returncode >= 124:      # a signal, an abort, a time limit
-        _child_state["dead"] = groups
-    assert res.returncode == 0, res.stdout[-3000:]
-    rec = dict(np.load(out))
+    gpu_child.run([os.path.abspath(__file__), str(groups), out], env={"GS3D_BLEND_GROUPS": str(groups)}, timeout=90,
+                  label="GS3D_BLEND_GROUPS=%d" % groups)
+    rec = gpu_child.load_npz(out)
     for name in CHILD_CASES:
         sub = {k[len(name) + 1:]: v for k, v in rec.items() if k.startswith(name + "/")}
         check_case(ob, name, sub, ctx="GS3D_BLEND_GROUPS=%d, " % groups)

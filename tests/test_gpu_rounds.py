@@ -5,6 +5,7 @@ and the oracle's — bit for bit, whatever K is."""
 import numpy as np
 import pytest
 
+import gpu_child
 import helpers
 import rounds_np
 from helpers import deep_scene as _deep_scene, round_setup as _setup
@@ -227,8 +228,6 @@ def test_renderer_chooses_two_rounds_for_deep_scenes_only():
     second frame on — and a scene that finishes no tile (sparse, translucent) goes back to one round after the feedback
     has lengthened round 1 three times — and tries again 512 frames later.  All frames equal their single-round frame."""
     import os
-    import subprocess
-    import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = (
         "import sys; sys.path[:0] = [%r, %r]\n"
@@ -259,12 +258,8 @@ def test_renderer_chooses_two_rounds_for_deep_scenes_only():
         "        assert hashlib.sha256(img.download(st, np.float32).tobytes()).hexdigest() == want, name\n"
         "    out.append((name, rounds)); print(name, r.stats().pairs, r.stats().visible, rounds[:12], flush=True); r.destroy(); buf.destroy()\n"
         "print('RESULT', out)\n" % (root, os.path.join(root, 'tools')))
-    env = dict(os.environ)
-    env.pop("GS3D_ROUNDS", None)
-    env.pop("GS3D_ROUND1", None)
-    env.pop("GS3D_ROUND_PARTITION", None)
-    res = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    assert res.returncode == 0 and "RESULT" in res.stdout, res.stdout[-3000:]
+    res = gpu_child.run(["-c", code], unset=("GS3D_ROUNDS", "GS3D_ROUND1", "GS3D_ROUND_PARTITION"), timeout=900,
+                        label="unpinned rounds", expect="RESULT")
     by = dict(eval(res.stdout.split("RESULT", 1)[1].strip()))
     assert by["1m"] == [1] * 12, by["1m"]
     assert by["10m"][0] == 1 and by["10m"][1:] == [2] * 11, by["10m"]

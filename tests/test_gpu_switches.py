@@ -5,10 +5,10 @@ LSD sorts, the unpacked rect format, the store policies) are
 exercised by running a subset of the parity tests in a child process per setting — one child at a
 time."""
 import os
-import subprocess
-import sys
 
 import pytest
+
+import gpu_child
 
 pytestmark = pytest.mark.gpu
 
@@ -29,12 +29,9 @@ SUBSET = "synthetic_small or emission or capacity_overflow or edge_cases or wide
 def test_parity_subset_under_switch(env):
     if any(os.environ.get(k) == v for k, v in env.items()):
         pytest.skip("already running under this switch")
-    child_env = dict(os.environ)
-    child_env.update(env)
     # the block-culling views only where the switch set moves the block test (GS3D_BLOCK_LIST)
     subset = SUBSET + (" or block_culling" if "GS3D_BLOCK_LIST" in env else "")
-    res = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_render.py"), "-x", "-q",
-                          "-m", "gpu", "-k", subset, "-p", "no:cacheprovider"],
-                         cwd=ROOT, env=child_env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert res.returncode == 0, res.stdout[-3000:]
+    res = gpu_child.run(["-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_render.py"), "-x", "-q",
+                         "-m", "gpu", "-k", subset, "-p", "no:cacheprovider"],
+                        env=env, timeout=600, label=",".join("%s=%s" % kv for kv in env.items()))
     assert " passed" in res.stdout and "deselected" in res.stdout, res.stdout[-1000:]
