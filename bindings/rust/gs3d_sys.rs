@@ -533,6 +533,10 @@ extern "C" {
     pub fn gs_contributions_clear(contrib: *mut gs_buffer, s: *mut gs_stream, n: usize) -> gs_status;
     pub fn gs_select_contribution(sel: *mut gs_selection, s: *mut gs_stream, contrib: *mut gs_buffer, kind: u32, lo: f32, hi: f32, op: u32) -> gs_status;
     pub fn gs_image_compare(dev: *mut gs_device, s: *mut gs_stream, a: *const f32, b: *const f32, width: u32, height: u32, desc: *const gs_image_compare_desc, out: *mut gs_image_metrics) -> gs_status;
+    pub fn gs_gzip_fast_bound(len: usize) -> usize;
+    pub fn gs_gzip_fast(bytes: *const c_void, len: usize, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
+    pub fn gs_buffer_gzip_fast(b: *mut gs_buffer, s: *mut gs_stream, offset: usize, len: usize, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
+    pub fn gs_gaussians_buffer_export_spz_fast(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, options: *const gs_spz_options, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

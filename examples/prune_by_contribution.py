@@ -4,12 +4,14 @@
 stays below a threshold, extract the others and write them — all on the device; the scene is downloaded once, as the
 pruned file.
 usage: python examples/prune_by_contribution.py tests/golden/model.ply pruned.ply [--views 24] [--radius 4] [--height 0.5]
-       [--size 640x360] [--threshold 0.5] [--pod ShSingle/Cov3dRotScale] [--report-quality]
+       [--size 640x360] [--threshold 0.5] [--pod ShSingle/Cov3dRotScale] [--report-quality] [--fast-save]
                                                                                    (needs a GPU: there is no CPU fallback)
        threshold: in units of "fully covered pixels", summed over all views (1.0 = the weight of one opaque pixel in one view);
        0 removes exactly the Gaussians no view blended.
        --report-quality: renders the orbit's views again from the original and from the pruned buffer and prints PSNR and
-       SSIM per view and their means (gs_image_compare); no image is downloaded."""
+       SSIM per view and their means (gs_image_compare); no image is downloaded.
+       --fast-save: an .spz result is deflated on the device (Huffman only, no zlib; every .spz reader opens
+       it); a .ply result is the same either way."""
 import argparse
 import os
 import sys
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--pod", default="ShSingle/Cov3dRotScale")
     ap.add_argument("--report-quality", action="store_true")
+    ap.add_argument("--fast-save", action="store_true")
     args = ap.parse_args()
     sh, cov = args.pod.split("/")
     pod = getattr(gs, "GaussianPodWith%s%sConfigs" % (sh, cov))
@@ -63,7 +66,7 @@ def main():
         scores.select(stream, low, gs.CONTRIB_HITS, 0.0, 0.0)
     removed = low.count(stream)
     kept = buf.extract(stream, low, invert=True)
-    kept.write_to_file(args.out, stream)
+    kept.write_to_file(args.out, stream, fast=args.fast_save)
     rec = scores.download(stream)
     print("%d Gaussians, %d views: %d never blended, %d below %g -> %d kept -> %s" % (
         n, args.views, int((rec["hits"] == 0).sum()), removed, args.threshold, len(kept), args.out))

@@ -1205,6 +1205,38 @@ typedef struct gs_image_metrics {
 gs_status gs_image_compare(gs_device *dev, gs_stream *s, const float *a, const float *b, uint32_t width, uint32_t height,
                            const gs_image_compare_desc *desc, gs_image_metrics *out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Fast gzip members (no reference item): SPZ saved without zlib, the member    */
+/* deflated on the device from the payload that is already there                               */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  A gzip member (header 1f 8b 08 00 00 00 00 00 00 03, a DEFLATE stream,
+ * CRC-32 and length mod 2^32) whose stream holds one block per 32768 input bytes, each starting on a byte boundary: a
+ * fixed-Huffman run block for a chunk of >= 4 equal bytes, else a dynamic block of literals only, else a stored block, by the
+ * size rule of 3.15; an empty input is the block 03 00.  No string matching: the quantised byte-planar columns of an SPZ
+ * payload gain almost nothing from it.  Every inflater reads the member (gs_spz_decompress, zlib, the reference's GzDecoder);
+ * it is NOT the bytes gs_spz_compress gives.  The host and the device encoder give the same bytes, whatever the thread count. */
+
+/* The largest member of `len` input bytes: 18 + len + 5 max(1, ceil(len / 32768)) (no reference item) */
+size_t gs_gzip_fast_bound(size_t len);
+/* The member of `len` host bytes, encoded on the host (no reference item) by up to 32 threads
+ * (GS3D_HOST_THREADS overrides).  out == NULL: *bytes_out = its exact size.  GS_ERR_INVALID_ARGUMENT, with nothing written,
+ * for a null pointer or a capacity below the size (*bytes_out is still the size). */
+gs_status gs_gzip_fast(const void *bytes, size_t len, void *out, size_t capacity, size_t *bytes_out);
+/* The member of the `len` DEVICE bytes of `b` from `offset` (any alignment), encoded on the device; `out` is host memory and
+ * only the compressed bytes cross the link (no reference item).  Byte-equal to gs_gzip_fast of the same bytes.
+ * BLOCKING on `s` (NULL: the device's internal stream).  out == NULL: the exact size (the kernels run, nothing is gathered or
+ * copied).  Device memory of the call: 32784 bytes per chunk of 32768 plus the member, freed before it returns.
+ * GS_ERR_INVALID_ARGUMENT, with nothing written, for a null buffer or size pointer, a range past the end of the buffer, a
+ * capacity below the size, a stream of another device. */
+gs_status gs_buffer_gzip_fast(gs_buffer *b, gs_stream *s, size_t offset, size_t len, void *out, size_t capacity, size_t *bytes_out);
+/* gs_gaussians_buffer_export_spz with the member of gs_gzip_fast around the same payload (no reference item):
+ * the scan and the payload kernel of the export, the payload (16-byte header included) stays on the device and is deflated
+ * there.  The arguments, the refused layouts and the errors are those of gs_gaussians_buffer_export_spz; out == NULL returns
+ * the exact size.  The member inflates to the bytes of gs_gaussians_buffer_export_spz_decompressed. */
+gs_status gs_gaussians_buffer_export_spz_fast(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                              const gs_spz_options *options, void *out, size_t capacity, size_t *bytes_out);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

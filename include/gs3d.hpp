@@ -293,6 +293,9 @@ class Buffer {   // wgpu::Buffer + BufferWrapper (src/buffer/mod.rs:17-102); Clo
         gs_download *d_;
     };
     Download prepare_download(Stream &s) const { gs_download *d = nullptr; check(gs_buffer_prepare_download(h_, s.raw(), &d)); return Download(d); }
+    // the bytes [offset, offset + len) as a Huffman-only gzip member deflated on the device (gs3d.h gs_buffer_gzip_fast,
+    // DESIGN.md 3.15; no reference item): byte-equal to gs3d::gzip_fast of the same bytes; blocking
+    std::vector<uint8_t> gzip_fast(Stream &s, size_t offset, size_t len) const;
     gs_buffer *raw() const { return h_; }
   private:
     gs_buffer *h_ = nullptr;
@@ -386,6 +389,10 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // enqueues.  counts holds at least 4 len() bytes; read it back with Buffer::download.
     void neighbor_counts(Stream &s, float radius, uint32_t cap, Buffer &counts, const Selection *among = nullptr,
                          const gs_model_transform_pod *mt = nullptr);
+    // the .spz file image of the records of sel (nullptr: all; invert: of its complement), the payload deflated on the device
+    // (gs3d.h gs_gaussians_buffer_export_spz_fast; no reference item); options == nullptr: the defaults.
+    // Inflates to what gs_gaussians_buffer_export_spz_decompressed gives; blocking.
+    std::vector<uint8_t> export_spz_fast(Stream &s, const Selection *sel = nullptr, bool invert = false, const gs_spz_options *options = nullptr) const;
     gs_gaussians_buffer *raw() const { return h_; }
   private:
     template <class> friend class GaussiansBuffer;      // convert<To> builds a buffer of another layout
@@ -787,6 +794,30 @@ inline double image_psnr(const gs_image_metrics &m, double data_range = 1.0) {
 }
 inline double image_ssim(const gs_image_metrics &m) {
     return ((m.ssim_sum[0] / (double)m.ssim_finite[0] + m.ssim_sum[1] / (double)m.ssim_finite[1]) + m.ssim_sum[2] / (double)m.ssim_finite[2]) / 3.0;
+}
+
+// ---- fast gzip members (gs3d.h gs_gzip_fast ...; no reference item) ------------------------------------
+// A Huffman-only gzip member, one DEFLATE block per 32768 bytes: the host encoder, the device encoder over the bytes of a
+// Buffer (Buffer::gzip_fast) and the .spz image of a GaussiansBuffer deflated where its payload is built
+// (GaussiansBuffer::export_spz_fast) give the same bytes for the same input.  Each is one call into a vector of
+// gs_gzip_fast_bound bytes: a size query would encode twice.  Blocking.
+template <class F, class... A>
+inline std::vector<uint8_t> gzip_fast_bounded(size_t input_bytes, F fn, A... head) {
+    std::vector<uint8_t> out(gs_gzip_fast_bound(input_bytes));
+    size_t n = 0;
+    check(fn(head..., out.data(), out.size(), &n));
+    out.resize(n);
+    return out;
+}
+inline std::vector<uint8_t> gzip_fast(const void *bytes, size_t len) { return gzip_fast_bounded(len, gs_gzip_fast, bytes, len); }
+inline std::vector<uint8_t> Buffer::gzip_fast(Stream &s, size_t offset, size_t len) const {
+    return gzip_fast_bounded(len < size() ? len : size(), gs_buffer_gzip_fast, h_, s.raw(), offset, len);
+}
+template <class G>
+inline std::vector<uint8_t> GaussiansBuffer<G>::export_spz_fast(Stream &s, const Selection *sel, bool invert, const gs_spz_options *options) const {
+    size_t payload = 0;      // from the scan alone
+    check(gs_gaussians_buffer_export_spz_decompressed(h_, s.raw(), sel ? sel->raw() : nullptr, invert ? 1 : 0, options, nullptr, 0, &payload));
+    return gzip_fast_bounded(payload, gs_gaussians_buffer_export_spz_fast, h_, s.raw(), sel ? sel->raw() : nullptr, (int32_t)(invert ? 1 : 0), options);
 }
 
 }  // namespace gs3d

@@ -11,7 +11,13 @@ host memory (gs_buffer_download) is measured in the same run, and the PLY rows r
 to it.  The gzip member (gs_gaussians_buffer_export_spz: zlib on one host thread) is timed with `--gzip-iters` repeats and
 reported as a share of the call.  One JSON line per workload and a table.
 
-    python tools/export_bench.py [--iters 15] [--warmup 2] [--gzip-iters 3] [--workloads 1m,10m]
+--rows deflate (or all) adds the fast gzip member of DESIGN.md §3.15: write(SPZ, fast), Buffer.gzip_fast of the payload
+resident on the device and the host encoder gs_gzip_fast, next to write(SPZ) — zlib, this build's untouched path — of the
+same run, with the speed-up, the member's size over zlib's and the call's time over a plain device-to-host copy of as many
+bytes as the member has.  The kernel times come from a run of their own:
+    rocprofv3 --kernel-trace --stats -- python tools/export_bench.py --rows deflate --workloads 10m --iters 3 --gzip-iters 0
+
+    python tools/export_bench.py [--iters 15] [--warmup 2] [--gzip-iters 3] [--workloads 1m,10m] [--rows export|deflate|all]
 """
 import argparse
 import ctypes as C
@@ -38,7 +44,52 @@ def _timed(fn, stream):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-def run(gs, name, n, iters, warmup, gzip_iters):
+def deflate_rows(gs, dev, stream, buf, mask_name, s, count, payload, iters, warmup, gzip_iters):
+    """The fast gzip member next to zlib's in the same run: write(SPZ, fast), Buffer.gzip_fast of the payload
+    resident on the device and the host encoder gs_gzip_fast, alternating inside every repeat; write(SPZ) — zlib on one host
+    thread, this build's untouched path — is the baseline (`gzip_iters` repeats); the yardstick is a plain device-to-host
+    copy of as many bytes as the fast member has."""
+    resident = gs.Buffer(dev, data=np.frombuffer(payload, np.uint8))
+    calls = [("write(SPZ, fast): payload + member on the device", lambda: buf.write(stream, gs.GaussiansSource.Spz, s, fast=True)),
+             ("Buffer.gzip_fast of the resident payload", lambda: resident.gzip_fast(stream)),
+             ("host gs_gzip_fast of the payload", lambda: gs.gzip_fast(payload))]
+    ts = {label: [] for label, _ in calls}
+    sizes = {}
+    for _ in range(warmup + iters):
+        for label, fn in calls:
+            ms, out = _timed(fn, stream)
+            ts[label].append(ms)
+            sizes[label] = len(out)
+            del out
+    assert len(set(sizes.values())) == 1, sizes
+    member = sizes[calls[0][0]]
+    resident.release()
+    raw = gs.Buffer(dev, size=member)
+    copy_ms = [_timed(lambda: raw.download(stream, np.uint8), stream)[0] for _ in range(warmup + iters)]
+    raw.release()
+    copy = float(np.median(copy_ms[warmup:]))
+    zl, zl_bytes = [], 0
+    for _ in range(gzip_iters):
+        ms, out = _timed(lambda: buf.write(stream, gs.GaussiansSource.Spz, s), stream)
+        zl.append(ms)
+        zl_bytes = len(out)
+        del out
+    rows = []
+    if zl:
+        rows.append(dict(mask=mask_name, call="write(SPZ): payload + zlib member (baseline)", count=int(count), bytes=int(zl_bytes),
+                         ms=float(np.median(zl)), ms_min=float(min(zl)), ms_max=float(max(zl)), payload_bytes=len(payload)))
+    for label, _ in calls:
+        t = np.array(ts[label][warmup:])
+        row = dict(mask=mask_name, call=label, count=int(count), bytes=int(member), ms=float(np.median(t)), ms_min=float(t.min()),
+                   ms_max=float(t.max()), payload_bytes=len(payload), copy_ms=copy, over_copy=float(np.median(t)) / copy)
+        if zl:
+            row["speedup_over_zlib"] = float(np.median(zl)) / row["ms"]
+            row["size_over_zlib"] = member / zl_bytes
+        rows.append(row)
+    return rows
+
+
+def run(gs, name, n, iters, warmup, gzip_iters, which="all"):
     import synth
     dev = gs.Device(0)
     stream = dev.create_stream()
@@ -51,6 +102,14 @@ def run(gs, name, n, iters, warmup, gzip_iters):
     sel.upload(stream, np.random.default_rng(1).random(n) < 0.3)
     count30 = sel.count(stream)
     opt = gs.spz_options()
+    if which == "deflate":
+        rows = []
+        for mask_name, s, count in (("all", None, n), ("30 %", sel, count30)):
+            payload = gs._sized_call(gs._L.gs_gaussians_buffer_export_spz_decompressed, buf._h, stream._h, s._h if s is not None else None, 0,
+                                     C.byref(opt))
+            rows += deflate_rows(gs, dev, stream, buf, mask_name, s, count, payload, iters, warmup, gzip_iters)
+        sel.destroy(); buf.destroy(); stream.close()
+        return dict(workload=name, n=n, iters=iters, warmup=warmup, gzip_iters=gzip_iters, rows=rows)
 
     def host_pods(s):
         part = buf.extract(stream, s)
@@ -110,6 +169,8 @@ def run(gs, name, n, iters, warmup, gzip_iters):
             payload_ms = float(np.median(ts[calls[4][0]][warmup:]))
             rows.append(dict(mask=mask_name, call="write(SPZ): payload + gzip member", count=int(count), ms=float(np.median(t)),
                              ms_min=float(t.min()), ms_max=float(t.max()), gzip_share=1.0 - payload_ms / float(np.median(t))))
+        if which == "all":
+            rows += deflate_rows(gs, dev, stream, buf, mask_name, s, count, device_spz(s), iters, warmup, gzip_iters)
     sel.destroy(); buf.destroy(); stream.close()
     return dict(workload=name, n=n, iters=iters, warmup=warmup, gzip_iters=gzip_iters, rows=rows)
 
@@ -120,16 +181,33 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--gzip-iters", type=int, default=3)
     ap.add_argument("--workloads", default="1m,10m")
+    ap.add_argument("--rows", default="export", choices=("export", "deflate", "all"),
+                    help="export: the rows of DESIGN.md 3.13; deflate: the fast gzip member of 3.15 next to zlib's; all: both")
     a = ap.parse_args()
     import wgpu_3dgs_core_amd as gs
     results = []
     for name in a.workloads.split(","):
-        results.append(run(gs, name, WORKLOADS[name], a.iters, a.warmup, a.gzip_iters))
+        results.append(run(gs, name, WORKLOADS[name], a.iters, a.warmup, a.gzip_iters, a.rows))
         print(json.dumps(results[-1]), flush=True)
+    if a.rows != "export":
+        print("| scene | mask | call | records | member bytes (of payload) | ms (min .. max) | x zlib time | size / zlib | time / plain copy of the member |")
+        print("|---|---|---|---|---|---|---|---|---|")
+        for res in results:
+            for r in res["rows"]:
+                if "payload_bytes" not in r:
+                    continue
+                print("| %s | %s | %s | %d | %d (%.4f) | %.1f (%.1f .. %.1f) | %s | %s | %s |" % (
+                    res["workload"], r["mask"], r["call"], r["count"], r["bytes"], r["bytes"] / r["payload_bytes"], r["ms"], r["ms_min"], r["ms_max"],
+                    "%.0f" % r["speedup_over_zlib"] if "speedup_over_zlib" in r else "", "%.4f" % r["size_over_zlib"] if "size_over_zlib" in r else "",
+                    "%.2f (copy %.1f ms)" % (r["over_copy"], r["copy_ms"]) if "over_copy" in r else ""))
+        if a.rows == "deflate":
+            return
     print("| scene | mask | call | records | ms (min .. max) | PLY GB/s delivered (plain copy) | gzip share |")
     print("|---|---|---|---|---|---|---|")
     for res in results:
         for r in res["rows"]:
+            if "payload_bytes" in r:
+                continue
             rate = "%.1f (%.1f)" % (r["delivered_gbps"], r["copy_gbps"]) if "delivered_gbps" in r else ""
             share = "%.0f %%" % (100 * r["gzip_share"]) if "gzip_share" in r else ""
             print("| %s | %s | %s | %d | %.1f (%.1f .. %.1f) | %s | %s |" % (res["workload"], r["mask"], r["call"], r["count"], r["ms"],

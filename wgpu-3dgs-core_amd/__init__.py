@@ -423,6 +423,39 @@ def _sized_call(fn, *head):
     return out[:n.value].tobytes()
 
 
+_new_bytearray = C.pythonapi.PyByteArray_FromStringAndSize      # (NULL, n): n bytes, contents not initialised
+_new_bytearray.restype = C.py_object
+_new_bytearray.argtypes = [C.c_char_p, C.c_ssize_t]
+
+
+def _bounded_call(fn, bound, *head):
+    """One call with room for the largest result (a size query of the fast gzip member would encode twice).  Returns a
+    bytearray cut to the result in place: copying half a gigabyte into a bytes object costs more than encoding it."""
+    n = C.c_size_t()
+    # uninitialised: bytearray(n) would write n zeroes, and at half a gigabyte touching the pages costs more than the call
+    out = _new_bytearray(None, max(int(bound), 1))
+    view = np.frombuffer(out, dtype=np.uint8)
+    try:
+        _check(fn(*head, _ptr(view), view.size, C.byref(n)))
+    finally:
+        del view                             # a bytearray with an exported buffer cannot be resized
+    del out[n.value:]
+    return out
+
+
+def gzip_fast_bound(n):
+    """gs_gzip_fast_bound: the largest member of n input bytes"""
+    return _L.gs_gzip_fast_bound(int(n))
+
+
+def gzip_fast(data):
+    """gs_gzip_fast: `data` as a Huffman-only gzip member, encoded on the host — what Buffer.gzip_fast
+    gives for the same bytes on the device.  Any inflater reads it; it is not the bytes of zlib's encoder.  Returns a
+    bytearray (bytes-like: compare it, write it to a file, inflate it)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    return _bounded_call(_L.gs_gzip_fast, gzip_fast_bound(buf.size), _ptr(buf) if buf.size else None, buf.size)
+
+
 class SpzGaussians:
     """SpzGaussians — spz.rs:514-959.  Holds the decompressed payload (header + columns) exactly as
     read or encoded, so write_to reproduces the same columns; `gaussians` is Gaussian::from_spz of
@@ -709,6 +742,20 @@ class Buffer:
         _check(_L.gs_buffer_download(self._h, stream._h, _ptr(out), out.nbytes))
         return out.view(dtype)
 
+    def gzip_fast(self, stream, offset=0, length=None):
+        """gs_buffer_gzip_fast: the bytes [offset, offset + length) of the buffer (None: to its end) as a
+        Huffman-only gzip member, deflated on the device; only the member crosses the link.  Byte-equal to
+        gzip_fast(those bytes), and a bytearray like it.  Blocking."""
+        if stream is not None and not isinstance(stream, Stream):
+            raise TypeError("stream must be a Stream or None, not %s" % type(stream).__name__)
+        offset = int(offset)
+        length = self.size() - offset if length is None else int(length)
+        if offset < 0 or length < 0:
+            raise ValueError("offset and length must not be negative")
+        # a range past the buffer is the library's to refuse: no room is made for it
+        return _bounded_call(_L.gs_buffer_gzip_fast, gzip_fast_bound(min(length, self.size())), self._h, stream._h if stream is not None else None,
+                             offset, length)
+
     def prepare_download(self, stream):
         """BufferWrapper::prepare_download: enqueue the copy into a staging buffer; returns a Download"""
         h = C.c_void_p()
@@ -956,13 +1003,33 @@ class GaussiansBuffer:
         head = self._export_args(stream, selection) + (int(bool(invert)), C.byref(options) if options is not None else None)
         return SpzGaussians(_sized_call(_L.gs_gaussians_buffer_export_spz_decompressed, *head))
 
-    def write(self, stream, source, selection=None, invert=False):
+    def export_spz_file(self, stream, selection=None, invert=False, options=None, fast=True):
+        """The .spz file image of the records of `selection` as bytes.  fast=True: gs_gaussians_buffer_export_spz_fast
+         — the payload stays on the device and is deflated there, Huffman only; fast=False:
+        gs_gaussians_buffer_export_spz, zlib on one host thread.  Both inflate to export_spz(...).payload.  Blocking.  The fast
+        image comes as a bytearray, zlib's as bytes."""
+        if options is not None and not isinstance(options, _capi.SpzOptions):
+            raise TypeError("options must be spz_options(...) or None, not %s" % type(options).__name__)
+        args = self._export_args(stream, selection) + (int(bool(invert)),)
+        head = args + (C.byref(options) if options is not None else None,)
+        if not fast:
+            return _sized_call(_L.gs_gaussians_buffer_export_spz, *head)
+        # the payload's size comes from the scan alone; the member is bounded by it
+        n = C.c_size_t()
+        _check(_L.gs_gaussians_buffer_export_spz_decompressed(*head, None, 0, C.byref(n)))
+        return _bounded_call(_L.gs_gaussians_buffer_export_spz_fast, gzip_fast_bound(n.value), *head)
+
+    def write(self, stream, source, selection=None, invert=False, fast=False):
         """gs_gaussians_buffer_write: the complete file image of the records of `selection` as bytes —
-        GaussiansSource.Ply: header + vertices; GaussiansSource.Spz: the gzip member, default options.  Blocking."""
+        GaussiansSource.Ply: header + vertices; GaussiansSource.Spz: the gzip member, default options.  Blocking.
+        fast=True makes the SPZ member export_spz_file's (deflated on the device, not zlib's bytes); a PLY
+        image has nothing to compress and is the same either way."""
         if source == GaussiansSource.Internal:
             raise ValueError("cannot write Internal Gaussians to buffer")
         if source not in (GaussiansSource.Ply, GaussiansSource.Spz):
             raise TypeError("source must be GaussiansSource.Ply or GaussiansSource.Spz, not %r" % (source,))
+        if fast and source == GaussiansSource.Spz:
+            return self.export_spz_file(stream, selection, invert, None, fast=True)
         args = self._export_args(stream, selection) + (int(bool(invert)),)
         head = args + (1 if source == GaussiansSource.Ply else 2,)
         if source == GaussiansSource.Spz:
@@ -977,10 +1044,10 @@ class GaussiansBuffer:
                 return out[:n.value].tobytes()
         return _sized_call(_L.gs_gaussians_buffer_write, *head)
 
-    def write_to_file(self, path, stream=None, selection=None, invert=False):
+    def write_to_file(self, path, stream=None, selection=None, invert=False, fast=False):
         """write() into a file; the format follows the suffix: .spz is SPZ, everything else PLY"""
         source = GaussiansSource.Spz if str(path).lower().endswith(".spz") else GaussiansSource.Ply
-        data = self.write(stream, source, selection, invert)
+        data = self.write(stream, source, selection, invert, fast=fast)
         with open(path, "wb") as f:
             f.write(data)
 

@@ -280,6 +280,10 @@ SIGNATURES = {
     "gs_contributions_clear": (i32, [vp, vp, sz]),
     "gs_select_contribution": (i32, [vp, vp, vp, u32, f32, f32, i32]),
     "gs_image_compare": (i32, [vp, vp, vp, vp, u32, u32, vp, vp]),
+    "gs_gzip_fast_bound": (sz, [sz]),
+    "gs_gzip_fast": (i32, [vp, sz, vp, sz, vp]),
+    "gs_buffer_gzip_fast": (i32, [vp, vp, sz, sz, vp, sz, vp]),
+    "gs_gaussians_buffer_export_spz_fast": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

@@ -163,12 +163,10 @@ extern "C" gs_status gs_gaussians_buffer_export_ply(gs_gaussians_buffer *g, gs_s
 
 // The x.total records of the scan as a decompressed SPZ payload in `payload` (host, `bytes` long: gs_spz_encode_layout's size
 // for x.total records).  The whole payload is built on the device (at most 16 + 65 bytes per record) and comes over in one copy.
-static gs_status export_spz_payload(gs_gaussians_buffer *g, ExportScan &x, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
-                                    uint32_t bucket, uint8_t *payload, size_t bytes) {
-    std::memcpy(payload, &h, 16);
-    if (!x.total) return GS_OK;
-    uint8_t *dev_payload = nullptr;
-    GS_TRY(dev_alloc((void **)&dev_payload, bytes, bytes, "hipMalloc"));
+// the six columns of the x.total > 0 records into dev_payload (device, `bytes` long; its first 16 bytes are the header's and
+// are left alone).  Only enqueues.
+static hipError_t export_spz_columns(gs_gaussians_buffer *g, ExportScan &x, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
+                                     uint32_t bucket, uint8_t *dev_payload) {
     gs::SpzOut o;
     for (int c = 0; c < 6; c++) {
         o.col[c] = dev_payload + off[c];
@@ -180,7 +178,16 @@ static gs_status export_spz_payload(gs_gaussians_buffer *g, ExportScan &x, const
     o.bucket = bucket;
     hipLaunchKernelGGL(k_tbl_export_spz[g->sh], dim3((x.n + gs::EXPORT_GROUP - 1u) / gs::EXPORT_GROUP), dim3(gs::EXPORT_GROUP), 0, x.st,
                        (const uint4 *)g->buf->ptr, o, x.words, x.n, x.inv, (const uint32_t *)x.scan.ptr, (uint64_t)x.total);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+static gs_status export_spz_payload(gs_gaussians_buffer *g, ExportScan &x, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
+                                    uint32_t bucket, uint8_t *payload, size_t bytes) {
+    std::memcpy(payload, &h, 16);
+    if (!x.total) return GS_OK;
+    uint8_t *dev_payload = nullptr;
+    GS_TRY(dev_alloc((void **)&dev_payload, bytes, bytes, "hipMalloc"));
+    hipError_t e = export_spz_columns(g, x, h, off, ncoef, bucket, dev_payload);
     if (e == hipSuccess) e = hipMemcpyAsync(payload + 16, dev_payload + 16, bytes - 16, hipMemcpyDeviceToHost, x.st);
     const hipError_t e2 = hipStreamSynchronize(x.st);
     if (e == hipSuccess) e = e2;
@@ -228,6 +235,32 @@ extern "C" gs_status gs_gaussians_buffer_export_spz_decompressed(gs_gaussians_bu
 extern "C" gs_status gs_gaussians_buffer_export_spz(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
                                                     const gs_spz_options *options, void *out, size_t capacity, size_t *bytes_out) {
     return export_spz(g, s, sel, invert, options, true, out, capacity, bytes_out);
+}
+
+// The member of gs_gzip_fast around the payload of export_spz: the payload never leaves the device.
+extern "C" gs_status gs_gaussians_buffer_export_spz_fast(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                                         const gs_spz_options *options, void *out, size_t capacity, size_t *bytes_out) {
+    if (!g || !bytes_out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    *bytes_out = 0;
+    gs_spz_options dflt;
+    gs_spz_options_default(&dflt);
+    const gs_spz_options *opt = options ? options : &dflt;
+    ExportScan x;
+    GS_TRY(export_begin(g, s, sel, invert, x));
+    gs_spz_header h;
+    size_t off[6], bytes = 0;
+    uint32_t ncoef = 0, bucket = 0;
+    GS_TRY(gs_spz_encode_layout(x.total, opt, &h, off, &ncoef, &bucket, &bytes));
+    if (!x.total) return gs_gzip_fast(&h, 16, out, out ? capacity : 0, bytes_out);      // the header alone: the same bytes from the host
+    uint8_t *dev_payload = nullptr;
+    GS_TRY(dev_alloc((void **)&dev_payload, bytes, bytes, "hipMalloc"));
+    hipError_t e = hipMemcpyAsync(dev_payload, &h, 16, hipMemcpyHostToDevice, x.st);
+    if (e == hipSuccess) e = export_spz_columns(g, x, h, off, ncoef, bucket, dev_payload);
+    gs_status rc = e == hipSuccess ? gzip_fast_device(x.st, dev_payload, bytes, out, out ? capacity : 0, bytes_out)
+                                   : gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) (void)hipStreamSynchronize(x.st);
+    (void)hipFree(dev_payload);
+    return rc;
 }
 
 extern "C" gs_status gs_gaussians_buffer_write(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,

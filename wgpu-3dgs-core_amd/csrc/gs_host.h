@@ -233,5 +233,9 @@ void extract_copy_enqueue(hipStream_t st, const void *src, void *dst, const uint
 gs_status concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels, uint32_t count, bool as_layout,
                          int dsh, int dcov, gs_gaussians_buffer **out, uint64_t *counts_out);
 
+// ---- gs_deflate.hip ----
+// gs_buffer_gzip_fast without its checks: the gzip member of the `len` device bytes at `bytes` (any
+// alignment, on the current device) into the host memory `out`; out == NULL: only *bytes_out.  Blocks on `st`.
+gs_status gzip_fast_device(hipStream_t st, const uint8_t *bytes, size_t len, void *out, size_t capacity, size_t *bytes_out);
 
 }  // namespace gsh

@@ -21,6 +21,11 @@ gs_status gs_spz_encode_layout(size_t n, const gs_spz_options *opt, gs_spz_heade
 // rotations, sh) and the SH coefficients per channel; errors as gs_spz_decode_decompressed
 gs_status gs_spz_payload_layout(const void *bytes, size_t len, gs_spz_header *header_out, size_t col_offset[6],
                                 uint32_t *ncoef_out);
+// gs_deflate.cpp, for the device encoder in gs_deflate.hip: the 10 header bytes in front of `body` DEFLATE bytes at out + 10
+// and the trailer (CRC-32 and length of the `len` input bytes) behind them
+void gs_gzip_fast_frame(uint8_t *out, size_t body, uint32_t crc, size_t len);
+// ... and the CRC-32 of `len` input bytes from the CRCs of its chunks of 32768 (the last one shorter)
+uint32_t gs_gzip_fast_fold_crcs(const uint32_t *crcs, size_t chunks, size_t len);
 // the bounded gunzip of gs_spz_decode
 gs_status gs_spz_gunzip(const void *bytes, size_t len, std::vector<uint8_t> &out);
 #endif
