@@ -395,6 +395,16 @@ extern "C" void gs_stream_destroy(gs_stream *s) {
     delete s;
 }
 
+gs_buffer *gsh::make_buffer(gs_device *dev, void *ptr, size_t bytes, bool owned) {
+    gs_buffer *b = new gs_buffer();
+    b->dev = dev;
+    b->ptr = ptr;
+    b->bytes = bytes;
+    b->owned = owned;
+    b->refs.store(1);
+    return b;
+}
+
 extern "C" gs_status gs_buffer_create(gs_device *dev, size_t bytes, const void *init,
                                       gs_buffer **out) {
     if (!out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
@@ -419,13 +429,7 @@ extern "C" gs_status gs_buffer_create(gs_device *dev, size_t bytes, const void *
             return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemset failed: %s", hipGetErrorString(e));
         }
     }
-    gs_buffer *b = new gs_buffer();
-    b->dev = dev;
-    b->ptr = p;
-    b->bytes = bytes;
-    b->owned = true;
-    b->refs.store(1);
-    *out = b;
+    *out = make_buffer(dev, p, bytes, true);
     return GS_OK;
 }
 
@@ -433,13 +437,7 @@ extern "C" gs_status gs_buffer_from_raw(gs_device *dev, void *device_ptr, size_t
                                         gs_buffer **out) {
     if (!dev || !out || (!device_ptr && bytes))
         return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    gs_buffer *b = new gs_buffer();
-    b->dev = dev;
-    b->ptr = device_ptr;
-    b->bytes = bytes;
-    b->owned = false;
-    b->refs.store(1);
-    *out = b;
+    *out = make_buffer(dev, device_ptr, bytes, false);
     return GS_OK;
 }
 
@@ -479,6 +477,11 @@ extern "C" gs_status gs_buffer_write(gs_buffer *b, gs_stream *s, size_t offset, 
     return GS_OK;
 }
 
+hipError_t gsh::fetch(hipStream_t st, void *dst, const void *src, size_t bytes) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+}
+
 extern "C" gs_status gs_buffer_download(gs_buffer *b, gs_stream *s, void *dst, size_t bytes) {
     if (!b || (bytes && !dst)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     if (bytes > b->bytes)
@@ -486,9 +489,7 @@ extern "C" gs_status gs_buffer_download(gs_buffer *b, gs_stream *s, void *dst, s
                     "download of %zu bytes from buffer of %zu bytes", bytes, b->bytes);
     if (!bytes) return GS_OK;
     GS_TRY(use_device(b->dev));
-    hipStream_t st = stream_of(b->dev, s);
-    hipError_t e = hipMemcpyAsync(dst, b->ptr, bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    const hipError_t e = fetch(stream_of(b->dev, s), dst, b->ptr, bytes);
     if (e != hipSuccess)
         return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
     return GS_OK;
@@ -594,6 +595,25 @@ gs_status gsh::record_edit(gs_gaussians_buffer *g, hipStream_t st) {
     GS_HIP(hipEventRecord(g->edit_done, st));
     g->edit_stream = st;
     return GS_OK;
+}
+
+gs_status gsh::records_check(const gs_gaussians_buffer *g, const gs_stream *s, const gs_selection *sel, int32_t invert, RecordsAccess &a) {
+    GS_TRY(check_buffer_selection(g, s, sel));
+    a.len = gs_gaussians_buffer_len(g);
+    GS_TRY(check_len32(a.len));
+    a.dev = g->buf->dev;
+    a.n = (uint32_t)a.len;
+    a.nblocks = (a.n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
+    a.words = sel ? (const uint32_t *)sel->words : nullptr;
+    a.inv = invert ? 1u : 0u;
+    return GS_OK;
+}
+
+gs_status gsh::records_access(const gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert, RecordsAccess &a) {
+    GS_TRY(records_check(g, s, sel, invert, a));
+    GS_TRY(use_device(a.dev));
+    a.st = stream_of(a.dev, s);
+    return wait_for_edits(g, a.st);
 }
 
 uint64_t gsh::next_object_id() {
@@ -703,13 +723,15 @@ static gs_status upload_records(gs_gaussians_buffer *g, gs_stream *s, size_t sta
     const size_t rec = from_ply ? sizeof(gs_ply_gaussian_pod) : sizeof(gs_gaussian);
     const size_t slice = count < PACK_SLICE ? count : PACK_SLICE;
     const int nbuf = count > slice ? 2 : 1;
-    void *staging[2] = {nullptr, nullptr};
-    hipEvent_t used[2] = {nullptr, nullptr};
+    DevMem staging[2];
+    Event used[2];
+    // (no early return: the stream is synchronised before anything is freed, as it always was, also when the second
+    // allocation fails)
     gs_status rc = GS_OK;
     for (int i = 0; i < nbuf && rc == GS_OK; i++) {
-        hipError_t e = hipMalloc(&staging[i], slice * rec);
+        hipError_t e = staging[i].alloc_raw(slice * rec);
         if (e != hipSuccess) rc = gs_fail(GS_ERR_OUT_OF_MEMORY, slice * rec, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-        else if ((e = hipEventCreateWithFlags(&used[i], hipEventDisableTiming)) != hipSuccess)
+        else if ((e = used[i].create()) != hipSuccess)
             rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipEventCreate failed: %s", hipGetErrorString(e));
     }
     const size_t stride = pod_stride(g);
@@ -717,28 +739,24 @@ static gs_status upload_records(gs_gaussians_buffer *g, gs_stream *s, size_t sta
     for (size_t first = 0; first < count && rc == GS_OK; first += slice, k ^= (nbuf - 1)) {
         const size_t cnt = count - first < slice ? count - first : slice;
         // the staging buffer's previous kernel must have read it before the next copy overwrites it
-        if (first >= (size_t)nbuf * slice && hipEventSynchronize(used[k]) != hipSuccess) {
+        if (first >= (size_t)nbuf * slice && hipEventSynchronize(used[k].e) != hipSuccess) {
             rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "upload failed");
             break;
         }
-        hipError_t e = hipMemcpyAsync(staging[k], (const uint8_t *)records + first * rec, cnt * rec, hipMemcpyHostToDevice, st);
+        hipError_t e = hipMemcpyAsync(staging[k].ptr, (const uint8_t *)records + first * rec, cnt * rec, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) {
             rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
             break;
         }
         void *dst = (uint8_t *)g->buf->ptr + (start + first) * stride;
         rc = from_ply ? gs_pack_device_from_ply(dev, s, (gs_sh_config)g->sh, (gs_cov3d_config)g->cov,
-                                                (const gs_ply_gaussian_pod *)staging[k], cnt, dst)
-                      : gs_pack_device(dev, s, (gs_sh_config)g->sh, (gs_cov3d_config)g->cov, (const gs_gaussian *)staging[k],
+                                                (const gs_ply_gaussian_pod *)staging[k].ptr, cnt, dst)
+                      : gs_pack_device(dev, s, (gs_sh_config)g->sh, (gs_cov3d_config)g->cov, (const gs_gaussian *)staging[k].ptr,
                                        cnt, dst);
-        if (rc == GS_OK && hipEventRecord(used[k], st) != hipSuccess) rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "upload failed");
+        if (rc == GS_OK && hipEventRecord(used[k].e, st) != hipSuccess) rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "upload failed");
     }
-    // the staging buffers are freed below and the caller's memory may be reused: wait for everything
+    // the staging buffers are freed at the return and the caller's memory may be reused: wait for everything
     if (hipStreamSynchronize(st) != hipSuccess && rc == GS_OK) rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "pack failed");
-    for (int i = 0; i < 2; i++) {
-        if (used[i]) (void)hipEventDestroy(used[i]);
-        if (staging[i]) (void)hipFree(staging[i]);
-    }
     return rc;
 }
 
@@ -766,6 +784,27 @@ extern "C" gs_status gs_gaussians_buffer_create_from_ply(gs_device *dev, gs_sh_c
 typedef void (*spz_fn)(gs::SpzView, uint64_t, uint32_t *);
 static spz_fn k_tbl_from_spz[4][3] = GS_CFG_TABLE(gs::k_from_spz_pods);
 
+// the n > 0 records of a checked payload -> dst, on the device's own stream; blocks
+static gs_status decode_spz_payload(gs_device *dev, const void *bytes, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
+                                    gs_gaussians_buffer *dst) {
+    const size_t n = h.num_points;
+    const size_t used = off[5] + n * 3u * ncoef;             // the payload the header declares (len may be larger)
+    DevMem staging;
+    hipError_t e = staging.alloc_raw(used);
+    if (e != hipSuccess) return gs_fail(GS_ERR_OUT_OF_MEMORY, used, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+    if ((e = hipMemcpyAsync(staging.ptr, bytes, used, hipMemcpyHostToDevice, dev->internal)) != hipSuccess)
+        return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
+    const uint8_t *b = (const uint8_t *)staging.ptr;
+    gs::SpzView v{b + off[0], b + off[1], b + off[2], b + off[3], b + off[4], b + off[5], h.version, h.fractional_bits, ncoef};
+    const uint64_t groups = ((uint64_t)n + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
+    hipLaunchKernelGGL(k_tbl_from_spz[dst->sh][dst->cov], dim3((uint32_t)groups), dim3(256), 0, dev->internal, v, (uint64_t)n,
+                       (uint32_t *)dst->buf->ptr);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->internal);      // (the staging memory is freed at the return)
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "SPZ decode kernel failed: %s", hipGetErrorString(e));
+    return GS_OK;
+}
+
 extern "C" gs_status gs_gaussians_buffer_create_from_spz_decompressed(gs_device *dev, gs_sh_config sh,
                                                                       gs_cov3d_config cov, const void *bytes,
                                                                       size_t len, gs_spz_header *header_out,
@@ -777,27 +816,9 @@ extern "C" gs_status gs_gaussians_buffer_create_from_spz_decompressed(gs_device 
     uint32_t ncoef = 0;
     GS_TRY(gs_spz_payload_layout(bytes, len, &h, off, &ncoef));
     if (header_out) *header_out = h;
-    const size_t n = h.num_points;
-    GS_TRY(gs_gaussians_buffer_create(dev, sh, cov, nullptr, n, out));
-    if (!n) return GS_OK;
-    gs_status rc = GS_OK;
-    void *staging = nullptr;
-    const size_t used = off[5] + n * 3u * ncoef;             // the payload the header declares (len may be larger)
-    hipError_t e = hipMalloc(&staging, used);
-    if (e != hipSuccess) rc = gs_fail(GS_ERR_OUT_OF_MEMORY, used, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-    if (rc == GS_OK && (e = hipMemcpyAsync(staging, bytes, used, hipMemcpyHostToDevice, dev->internal)) != hipSuccess)
-        rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
-    if (rc == GS_OK) {
-        const uint8_t *b = (const uint8_t *)staging;
-        gs::SpzView v{b + off[0], b + off[1], b + off[2], b + off[3], b + off[4], b + off[5], h.version, h.fractional_bits, ncoef};
-        const uint64_t groups = ((uint64_t)n + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
-        hipLaunchKernelGGL(k_tbl_from_spz[sh][cov], dim3((uint32_t)groups), dim3(256), 0, dev->internal, v, (uint64_t)n,
-                           (uint32_t *)(*out)->buf->ptr);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(dev->internal);
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "SPZ decode kernel failed: %s", hipGetErrorString(e));
-    }
-    if (staging) (void)hipFree(staging);
+    GS_TRY(gs_gaussians_buffer_create(dev, sh, cov, nullptr, h.num_points, out));
+    if (!h.num_points) return GS_OK;
+    const gs_status rc = decode_spz_payload(dev, bytes, h, off, ncoef, *out);
     if (rc != GS_OK) {
         gs_gaussians_buffer_destroy(*out);
         *out = nullptr;
@@ -946,24 +967,22 @@ extern "C" gs_status gs_gaussians_buffer_download_gaussians(gs_gaussians_buffer 
     hipStream_t st = stream_of(dev, s);
     constexpr size_t SLICE = 2u << 20;
     const size_t slice = count < SLICE ? count : SLICE;
-    void *staging = nullptr;
-    hipError_t e = hipMalloc(&staging, slice * sizeof(gs_gaussian));
+    DevMem staging;
+    hipError_t e = staging.alloc_raw(slice * sizeof(gs_gaussian));
     if (e != hipSuccess)
         return gs_fail(GS_ERR_OUT_OF_MEMORY, slice * sizeof(gs_gaussian), 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-    gs_status rc = GS_OK;
     const size_t stride = pod_stride(g);
-    for (size_t first = 0; first < count && rc == GS_OK; first += slice) {
+    for (size_t first = 0; first < count; first += slice) {
         const size_t cnt = count - first < slice ? count - first : slice;
         const uint64_t groups = ((uint64_t)cnt + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
         hipLaunchKernelGGL(k_tbl_unpack[g->sh], dim3((uint32_t)groups), dim3(256), 0, st,
-                           (const uint32_t *)((const uint8_t *)g->buf->ptr + first * stride), (uint64_t)cnt, (uint32_t *)staging);
+                           (const uint32_t *)((const uint8_t *)g->buf->ptr + first * stride), (uint64_t)cnt, (uint32_t *)staging.ptr);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out + first, staging, cnt * sizeof(gs_gaussian), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+        // every slice is awaited before the next one, and the last one before the staging memory is freed at the return
+        if (e == hipSuccess) e = fetch(st, out + first, staging.ptr, cnt * sizeof(gs_gaussian));
+        if (e != hipSuccess) return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
     }
-    (void)hipFree(staging);
-    return rc;
+    return GS_OK;
 }
 
 extern "C" void gs_gaussians_buffer_mark_dirty(gs_gaussians_buffer *g) {

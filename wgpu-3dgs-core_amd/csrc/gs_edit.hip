@@ -133,19 +133,17 @@ extern "C" gs_status gs_gaussians_buffer_edit(gs_gaussians_buffer *g, gs_stream 
         if (!all_finite(e->opacity, 2)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the opacity terms of an edit must be finite");
         std::memcpy(a.o, e->opacity, sizeof(a.o));
     }
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    GS_TRY(check_len32(len));
+    RecordsAccess r;
+    GS_TRY(records_check(g, s, sel, 0, r));
+    const size_t len = r.len;
     if (g->sh == GS_SH_NONE) a.flags &= ~(uint32_t)GS_EDIT_ROTATE_SH;
     if (!a.flags || !len) return GS_OK;
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    // a mirror rebuild in flight on another stream still reads the records
+    GS_TRY(use_device(r.dev));
+    hipStream_t st = stream_of(r.dev, s);
+    // a mirror rebuild in flight on another stream still reads the records (the one wait of this call: it takes the
+    // checks of records_access, not its wait for edits)
     if (g->mirror_ready && st != g->mirror_stream) GS_HIP(hipStreamWaitEvent(st, g->mirror_ready, 0));
-    const uint32_t n = (uint32_t)len;
-    hipLaunchKernelGGL(k_tbl_edit[g->sh][g->cov], dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, n,
-                       sel ? (const uint32_t *)sel->words : nullptr, a);
+    hipLaunchKernelGGL(k_tbl_edit[g->sh][g->cov], dim3((r.n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, r.n, r.words, a);
     GS_HIP(hipGetLastError());
     GS_TRY(record_edit(g, st));
     // The host does not know which Gaussians the selection names: the whole mirror is stale.  A transform moves them,
@@ -165,15 +163,10 @@ extern "C" gs_status gs_gaussians_buffer_edit(gs_gaussians_buffer *g, gs_stream 
 // gs_buffer_create: that hipMemset runs on the null stream, which the copy's stream is not ordered behind, and would race
 // with the copy.
 gs_status gsh::gaussians_buffer_create_unfilled(gs_device *dev, int sh, int cov, size_t len, gs_gaussians_buffer **out) {
-    void *p = nullptr;
+    DevMem p;
     const size_t bytes = len * (size_t)gs::pod_bytes(sh, cov);
-    GS_TRY(dev_alloc(&p, bytes, bytes, "hipMalloc"));
-    gs_buffer *b = new gs_buffer();
-    b->dev = dev;
-    b->ptr = p;
-    b->bytes = bytes;
-    b->owned = true;
-    b->refs.store(1);
+    GS_TRY(p.alloc(bytes, bytes, "hipMalloc"));
+    gs_buffer *b = make_buffer(dev, p.release(), bytes, true);
     gs_status rc = gs_gaussians_buffer_from_buffer(b, (gs_sh_config)sh, (gs_cov3d_config)cov, out);
     gs_buffer_release(b);
     return rc;
@@ -194,11 +187,19 @@ gs_status gsh::extract_scan(hipStream_t st, const uint32_t *words, uint32_t n, u
                               uint32_t *total) {
     extract_scan_enqueue(st, words, n, invert, offsets, total_dev);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(total, total_dev, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = fetch(st, total, total_dev, 4);
     if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
     if (*total > n) return gs_fail(GS_ERR_HIP, *total, n, 0, "selection scan returned %u of %u Gaussians", *total, n);
     return GS_OK;
+}
+
+// what extraction, conversion and the exports start with: the prelude, the scan into an array of the call (freed with `x`,
+// after whatever the caller enqueues on it has been awaited) and its total.  An empty buffer is scanned by nobody.
+gs_status gsh::extract_begin(const gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert, ExtractScan &x) {
+    GS_TRY(records_access(g, s, sel, invert, x));
+    if (!x.n) return GS_OK;
+    GS_TRY(dev_reserve(x.scan, ((size_t)x.nblocks + 1) * 4));
+    return extract_scan(x.st, x.words, x.n, x.inv, (uint32_t *)x.scan.ptr, (uint32_t *)x.scan.ptr + x.nblocks, &x.total);
 }
 
 // the `total` records the scan counted: src (n records of nc 16-byte chunks) -> dst, packed in index order
@@ -213,44 +214,11 @@ extern "C" gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buff
     if (!src || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     *out = nullptr;
     if (count_out) *count_out = 0;
-    GS_TRY(check_buffer_selection(src, s, sel));
-    const size_t len = gs_gaussians_buffer_len(src);
-    GS_TRY(check_len32(len));
-    gs_device *dev = src->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    GS_TRY(wait_for_edits(src, st));
-    const uint32_t n = (uint32_t)len, inv = invert ? 1u : 0u;
-    const uint32_t nblocks = (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK, nc = (uint32_t)(pod_stride(src) / 16);
-    const uint32_t *words = sel ? (const uint32_t *)sel->words : nullptr;
-    DevArray scan;      // the per-block offsets, then the total
-    uint32_t total = 0;
-    gs_status rc = GS_OK;
-    if (n) {
-        rc = dev_reserve(scan, ((size_t)nblocks + 1) * 4);
-        if (rc == GS_OK) rc = extract_scan(st, words, n, inv, (uint32_t *)scan.ptr, (uint32_t *)scan.ptr + nblocks, &total);
-    }
-    gs_gaussians_buffer *dst = nullptr;
-    if (rc == GS_OK && total) {
-        rc = gaussians_buffer_create_unfilled(dev, src->sh, src->cov, total, &dst);
-    } else if (rc == GS_OK) {
-        rc = gs_gaussians_buffer_create(dev, (gs_sh_config)src->sh, (gs_cov3d_config)src->cov, nullptr, 0, &dst);
-    }
-    if (rc == GS_OK && total) {
-        extract_copy_enqueue(st, src->buf->ptr, dst->buf->ptr, words, n, inv, (const uint32_t *)scan.ptr, nc, total);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);      // the offsets are freed below; the call is blocking anyway
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "extraction failed: %s", hipGetErrorString(e));
-    }
-    dev_free(scan);
-    if (rc != GS_OK) {
-        if (dst) gs_gaussians_buffer_destroy(dst);
-        return rc;
-    }
-    dst->spatial = src->spatial;
-    *out = dst;
-    if (count_out) *count_out = total;
-    return GS_OK;
+    // (the body is shared with gs_gaussians_buffer_create_converted: gs_relayout.hip)
+    hipError_t e = hipSuccess;
+    const gs_status rc = extract_records(src, s, sel, invert, src->sh, src->cov, out, count_out, &e);
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "extraction failed: %s", hipGetErrorString(e));
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -286,52 +254,49 @@ extern "C" size_t gs_snapshot_bytes(const gs_snapshot *snap) {
     return snap ? (size_t)snap->count * (size_t)gs::pod_bytes(snap->sh, snap->cov) + snap->meta_bytes : 0;
 }
 
+// the mask, the scan and the selected records of `g` into an empty snapshot; blocks on r.st.  What it allocates is the
+// snapshot's: the caller destroys that when this fails.
+static gs_status snapshot_fill(const gs_gaussians_buffer *g, const RecordsAccess &r, gs_snapshot *snap) {
+    GS_TRY(dev_alloc((void **)&snap->meta, snap->meta_bytes, 0, "snapshot allocation"));
+    if (!r.n) return GS_OK;
+    const uint32_t nwords = (uint32_t)snap->nwords;
+    // the mask is copied first and everything below reads the copy: the snapshot does not depend on the selection afterwards
+    hipLaunchKernelGGL(gs::k_snapshot_mask, dim3((nwords + 255u) / 256u), dim3(256), 0, r.st, snap->meta, r.words, nwords, r.n);
+    uint32_t total = 0;
+    GS_TRY(extract_scan(r.st, snap->words(), r.n, 0u, snap->offsets(), snap->total(), &total));
+    if (!total) return GS_OK;
+    const size_t bytes = (size_t)total * pod_stride(g);
+    GS_TRY(dev_alloc(&snap->records, bytes, bytes, "hipMalloc"));
+    extract_copy_enqueue(r.st, g->buf->ptr, snap->records, snap->words(), r.n, 0u, snap->offsets(), (uint32_t)(pod_stride(g) / 16), total);
+    hipError_t e = hipGetLastError();
+    // the call is blocking anyway; a restore on any stream may follow at once
+    if (e == hipSuccess) e = hipStreamSynchronize(r.st);
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "snapshot failed: %s", hipGetErrorString(e));
+    snap->count = total;
+    return GS_OK;
+}
+
 extern "C" gs_status gs_gaussians_buffer_snapshot(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, gs_snapshot **out) {
     if (out) *out = nullptr;
     if (!g || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    GS_TRY(check_len32(len));
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    GS_TRY(wait_for_edits(g, st));
+    RecordsAccess r;
+    GS_TRY(records_access(g, s, sel, 0, r));
     gs_snapshot *snap = new gs_snapshot();
-    snap->dev = dev;
+    snap->dev = r.dev;
     snap->sh = g->sh;
     snap->cov = g->cov;
-    snap->n = len;
-    snap->nwords = (len + 31) / 32;
-    snap->nblocks = (len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK;
+    snap->n = r.len;
+    snap->nwords = (r.len + 31) / 32;
+    snap->nblocks = r.nblocks;
     snap->count = 0;
+    snap->meta = nullptr;
     snap->records = nullptr;
     snap->meta_bytes = (snap->nwords + snap->nblocks + 1) * 4;
-    gs_status rc = dev_alloc((void **)&snap->meta, snap->meta_bytes, 0, "snapshot allocation");
-    const uint32_t n = (uint32_t)len, nwords = (uint32_t)snap->nwords;
-    const uint32_t nc = (uint32_t)(pod_stride(g) / 16);
-    uint32_t total = 0;
-    if (rc == GS_OK && n) {
-        // the mask is copied first and everything below reads the copy: the snapshot does not depend on `sel` afterwards
-        hipLaunchKernelGGL(gs::k_snapshot_mask, dim3((nwords + 255u) / 256u), dim3(256), 0, st, snap->meta,
-                           sel ? (const uint32_t *)sel->words : nullptr, nwords, n);
-        rc = extract_scan(st, snap->words(), n, 0u, snap->offsets(), snap->total(), &total);
-    }
-    if (rc == GS_OK && total) {
-        const size_t bytes = (size_t)total * pod_stride(g);
-        rc = dev_alloc(&snap->records, bytes, bytes, "hipMalloc");
-        if (rc == GS_OK) {
-            extract_copy_enqueue(st, g->buf->ptr, snap->records, snap->words(), n, 0u, snap->offsets(), nc, total);
-            hipError_t e = hipGetLastError();
-            // the call is blocking anyway; a restore on any stream may follow at once
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "snapshot failed: %s", hipGetErrorString(e));
-        }
-    }
+    const gs_status rc = snapshot_fill(g, r, snap);
     if (rc != GS_OK) {
         gs_snapshot_destroy(snap);
         return rc;
     }
-    snap->count = total;
     *out = snap;
     return GS_OK;
 }

@@ -11,37 +11,13 @@ typedef void (*export_spz_fn)(const uint4 *, gs::SpzOut, const uint32_t *, uint3
 static export_ply_fn k_tbl_export_ply[3] = {gs::k_export_ply<0>, gs::k_export_ply<1>, gs::k_export_ply<2>};
 static export_spz_fn k_tbl_export_spz[3] = {gs::k_export_spz<0>, gs::k_export_spz<1>, gs::k_export_spz<2>};
 
-// what every export starts with: the checks of an extraction and its scan
-struct ExportScan {
-    gs_device *dev = nullptr;
-    hipStream_t st = nullptr;
-    const uint32_t *words = nullptr;
-    uint32_t n = 0, inv = 0, nblocks = 0, total = 0;
-    DevArray scan;      // the per-1024-block offsets, then the total
-    ~ExportScan() { dev_free(scan); }
-};
-
-static gs_status export_begin(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert, ExportScan &x) {
+// what every export starts with: the layouts that can be exported, then the prelude and the scan of an extraction
+static gs_status export_begin(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert, ExtractScan &x) {
     if (!g) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null buffer");
     // the layouts gs_gaussians_buffer_download_gaussians accepts, and its error for the others
     if (g->sh == GS_SH_NONE || g->cov != GS_COV3D_ROT_SCALE)
         return gs_unpack_to_gaussian((gs_sh_config)g->sh, (gs_cov3d_config)g->cov, nullptr, 0, nullptr);
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    GS_TRY(check_len32(len));
-    x.dev = g->buf->dev;
-    GS_TRY(use_device(x.dev));
-    x.st = stream_of(x.dev, s);
-    GS_TRY(wait_for_edits(g, x.st));
-    x.n = (uint32_t)len;
-    x.inv = invert ? 1u : 0u;
-    x.nblocks = (x.n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
-    x.words = sel ? (const uint32_t *)sel->words : nullptr;
-    if (!x.n) return GS_OK;
-    GS_TRY(dev_reserve(x.scan, ((size_t)x.nblocks + 1) * 4));
-    GS_TRY(extract_scan(x.st, x.words, x.n, x.inv, (uint32_t *)x.scan.ptr, (uint32_t *)x.scan.ptr + x.nblocks, &x.total));
-    if (x.total > x.n) return gs_fail(GS_ERR_HIP, x.total, x.n, 0, "selection scan returned %u of %u Gaussians", x.total, x.n);
-    return GS_OK;
+    return extract_begin(g, s, sel, invert, x);
 }
 
 // GS3D_EXPORT_SLICE (records, a multiple of 1024; tests cross slice boundaries with it): the source records one kernel of the
@@ -57,14 +33,13 @@ static size_t export_slice() {
 // copy of slice k is issued on a stream of its own (a copy into pageable memory may hold the host until it is done), so the
 // kernel can run under that copy; events order a staging buffer's kernel, its copy and the next kernel that overwrites it.
 // That the two overlap on the device was not measured; at 0.2 ms of kernel per 30 ms of copy the total does not depend on it.
-static gs_status export_ply_records(gs_gaussians_buffer *g, ExportScan &x, uint8_t *out) {
+static gs_status export_ply_records(gs_gaussians_buffer *g, ExtractScan &x, uint8_t *out) {
     if (!x.total) return GS_OK;
     const size_t slice = export_slice();
     const uint32_t slices = (uint32_t)(((size_t)x.n + slice - 1) / slice);
     const int nbuf = slices > 1 ? 2 : 1;
     std::vector<uint32_t> offsets((size_t)x.nblocks + 1);
-    hipError_t e = hipMemcpyAsync(offsets.data(), x.scan.ptr, offsets.size() * 4, hipMemcpyDeviceToHost, x.st);
-    if (e == hipSuccess) e = hipStreamSynchronize(x.st);
+    hipError_t e = fetch(x.st, offsets.data(), x.scan.ptr, offsets.size() * 4);
     if (e != hipSuccess) return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
     const size_t blocks_per_slice = slice / gs::PLANAR_BLOCK;
     // a staging buffer holds the most vertices any slice selects
@@ -76,21 +51,22 @@ static gs_status export_ply_records(gs_gaussians_buffer *g, ExportScan &x, uint8
         if (offsets[b1] - offsets[b0] > most) most = offsets[b1] - offsets[b0];
     }
     if (offsets[x.nblocks] != x.total) return gs_fail(GS_ERR_HIP, offsets[x.nblocks], x.total, 0, "selection scan returned offsets out of order");
-    void *staging[2] = {nullptr, nullptr};
-    hipEvent_t encoded[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-    hipStream_t copy_st = nullptr;
-    gs_status rc = GS_OK;
+    // Declared in the order the return has to undo: the copy stream goes first, then the events, then the memory.  Nothing is
+    // enqueued while they are made (the fetch above has just drained x.st), so a failure here returns at once.
     const size_t rec = sizeof(gs_ply_gaussian_pod);
-    for (int i = 0; i < nbuf && rc == GS_OK; i++) {
-        e = hipMalloc(&staging[i], most * rec);
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_OUT_OF_MEMORY, most * rec, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-        else if ((e = hipEventCreateWithFlags(&encoded[i], hipEventDisableTiming)) != hipSuccess ||
-                 (e = hipEventCreateWithFlags(&copied[i], hipEventDisableTiming)) != hipSuccess)
-            rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipEventCreate failed: %s", hipGetErrorString(e));
+    DevMem staging[2];
+    Event encoded[2], copied[2];
+    Stream copy;
+    for (int i = 0; i < nbuf; i++) {
+        if ((e = staging[i].alloc_raw(most * rec)) != hipSuccess)
+            return gs_fail(GS_ERR_OUT_OF_MEMORY, most * rec, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+        if ((e = encoded[i].create()) != hipSuccess || (e = copied[i].create()) != hipSuccess)
+            return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipEventCreate failed: %s", hipGetErrorString(e));
     }
-    if (rc == GS_OK && nbuf > 1 && (e = hipStreamCreateWithFlags(&copy_st, hipStreamNonBlocking)) != hipSuccess)
-        rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    hipStream_t cst = copy_st ? copy_st : x.st;
+    if (nbuf > 1 && (e = copy.create()) != hipSuccess)
+        return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipStreamCreate failed: %s", hipGetErrorString(e));
+    const hipStream_t copy_st = copy.s, cst = copy_st ? copy_st : x.st;
+    gs_status rc = GS_OK;
     bool used[2] = {false, false};
     int b = 0;
     // the copy of the slice encoded last, issued once the next slice's kernel has been enqueued
@@ -98,10 +74,10 @@ static gs_status export_ply_records(gs_gaussians_buffer *g, ExportScan &x, uint8
     uint64_t pending_rank0 = 0, pending_count = 0;
     auto issue_copy = [&]() -> hipError_t {
         if (pending < 0) return hipSuccess;
-        hipError_t ce = copy_st ? hipStreamWaitEvent(copy_st, encoded[pending], 0) : hipSuccess;
+        hipError_t ce = copy_st ? hipStreamWaitEvent(copy_st, encoded[pending].e, 0) : hipSuccess;
         if (ce == hipSuccess)
-            ce = hipMemcpyAsync(out + pending_rank0 * rec, staging[pending], (size_t)pending_count * rec, hipMemcpyDeviceToHost, cst);
-        if (ce == hipSuccess && copy_st) ce = hipEventRecord(copied[pending], copy_st);
+            ce = hipMemcpyAsync(out + pending_rank0 * rec, staging[pending].ptr, (size_t)pending_count * rec, hipMemcpyDeviceToHost, cst);
+        if (ce == hipSuccess && copy_st) ce = hipEventRecord(copied[pending].e, copy_st);
         pending = -1;
         return ce;
     };
@@ -112,14 +88,14 @@ static gs_status export_ply_records(gs_gaussians_buffer *g, ExportScan &x, uint8
         const uint32_t first = (uint32_t)(b0 * gs::PLANAR_BLOCK);
         const uint32_t end = b1 * gs::PLANAR_BLOCK < x.n ? (uint32_t)(b1 * gs::PLANAR_BLOCK) : x.n;
         // the kernel overwrites staging[b]: its previous copy (issued two slices ago) must have left
-        e = used[b] && copy_st ? hipStreamWaitEvent(x.st, copied[b], 0) : hipSuccess;
+        e = used[b] && copy_st ? hipStreamWaitEvent(x.st, copied[b].e, 0) : hipSuccess;
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_tbl_export_ply[g->sh], dim3((end - first + gs::EXPORT_GROUP - 1u) / gs::EXPORT_GROUP), dim3(gs::EXPORT_GROUP),
-                               0, x.st, (const uint4 *)g->buf->ptr, (uint2 *)staging[b], x.words, x.n, x.inv, (const uint32_t *)x.scan.ptr,
+                               0, x.st, (const uint4 *)g->buf->ptr, (uint2 *)staging[b].ptr, x.words, x.n, x.inv, x.offsets(),
                                first, rank0, rank_end);
             e = hipGetLastError();
         }
-        if (e == hipSuccess && copy_st) e = hipEventRecord(encoded[b], x.st);
+        if (e == hipSuccess && copy_st) e = hipEventRecord(encoded[b].e, x.st);
         if (e == hipSuccess) e = issue_copy();      // the previous slice's, into the other staging buffer
         if (e != hipSuccess) {
             rc = gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
@@ -132,19 +108,13 @@ static gs_status export_ply_records(gs_gaussians_buffer *g, ExportScan &x, uint8
         b ^= nbuf - 1;
     }
     if (rc == GS_OK && (e = issue_copy()) != hipSuccess) rc = gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
-    // the staging buffers are freed below and the caller reads `out`: wait for everything
+    // the staging buffers are freed at the return and the caller reads `out`: wait for everything, on every path from the loop
     e = hipStreamSynchronize(x.st);
     if (copy_st) {
         const hipError_t e2 = hipStreamSynchronize(copy_st);
         if (e == hipSuccess) e = e2;
-        (void)hipStreamDestroy(copy_st);
     }
     if (e != hipSuccess && rc == GS_OK) rc = gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
-    for (int i = 0; i < 2; i++) {
-        if (encoded[i]) (void)hipEventDestroy(encoded[i]);
-        if (copied[i]) (void)hipEventDestroy(copied[i]);
-        if (staging[i]) (void)hipFree(staging[i]);
-    }
     return rc;
 }
 
@@ -152,7 +122,7 @@ extern "C" gs_status gs_gaussians_buffer_export_ply(gs_gaussians_buffer *g, gs_s
                                                     gs_ply_gaussian_pod *out, size_t capacity, uint64_t *count_out) {
     if (!g || !count_out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     *count_out = 0;
-    ExportScan x;
+    ExtractScan x;
     GS_TRY(export_begin(g, s, sel, invert, x));
     *count_out = x.total;
     if (!out) return GS_OK;
@@ -165,7 +135,7 @@ extern "C" gs_status gs_gaussians_buffer_export_ply(gs_gaussians_buffer *g, gs_s
 // for x.total records).  The whole payload is built on the device (at most 16 + 65 bytes per record) and comes over in one copy.
 // the six columns of the x.total > 0 records into dev_payload (device, `bytes` long; its first 16 bytes are the header's and
 // are left alone).  Only enqueues.
-static hipError_t export_spz_columns(gs_gaussians_buffer *g, ExportScan &x, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
+static hipError_t export_spz_columns(gs_gaussians_buffer *g, ExtractScan &x, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
                                      uint32_t bucket, uint8_t *dev_payload) {
     gs::SpzOut o;
     for (int c = 0; c < 6; c++) {
@@ -177,21 +147,21 @@ static hipError_t export_spz_columns(gs_gaussians_buffer *g, ExportScan &x, cons
     o.ncoef = ncoef;
     o.bucket = bucket;
     hipLaunchKernelGGL(k_tbl_export_spz[g->sh], dim3((x.n + gs::EXPORT_GROUP - 1u) / gs::EXPORT_GROUP), dim3(gs::EXPORT_GROUP), 0, x.st,
-                       (const uint4 *)g->buf->ptr, o, x.words, x.n, x.inv, (const uint32_t *)x.scan.ptr, (uint64_t)x.total);
+                       (const uint4 *)g->buf->ptr, o, x.words, x.n, x.inv, x.offsets(), (uint64_t)x.total);
     return hipGetLastError();
 }
 
-static gs_status export_spz_payload(gs_gaussians_buffer *g, ExportScan &x, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
+static gs_status export_spz_payload(gs_gaussians_buffer *g, ExtractScan &x, const gs_spz_header &h, const size_t off[6], uint32_t ncoef,
                                     uint32_t bucket, uint8_t *payload, size_t bytes) {
     std::memcpy(payload, &h, 16);
     if (!x.total) return GS_OK;
-    uint8_t *dev_payload = nullptr;
-    GS_TRY(dev_alloc((void **)&dev_payload, bytes, bytes, "hipMalloc"));
+    DevMem mem;
+    GS_TRY(mem.alloc(bytes, bytes, "hipMalloc"));
+    uint8_t *dev_payload = (uint8_t *)mem.ptr;
     hipError_t e = export_spz_columns(g, x, h, off, ncoef, bucket, dev_payload);
     if (e == hipSuccess) e = hipMemcpyAsync(payload + 16, dev_payload + 16, bytes - 16, hipMemcpyDeviceToHost, x.st);
-    const hipError_t e2 = hipStreamSynchronize(x.st);
+    const hipError_t e2 = hipStreamSynchronize(x.st);      // whatever was enqueued: the payload is freed at the return
     if (e == hipSuccess) e = e2;
-    (void)hipFree(dev_payload);
     if (e != hipSuccess) return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
     return GS_OK;
 }
@@ -204,7 +174,7 @@ static gs_status export_spz(gs_gaussians_buffer *g, gs_stream *s, const gs_selec
     gs_spz_options dflt;
     gs_spz_options_default(&dflt);
     const gs_spz_options *opt = options ? options : &dflt;
-    ExportScan x;
+    ExtractScan x;
     GS_TRY(export_begin(g, s, sel, invert, x));
     gs_spz_header h;
     size_t off[6], bytes = 0;
@@ -245,22 +215,24 @@ extern "C" gs_status gs_gaussians_buffer_export_spz_fast(gs_gaussians_buffer *g,
     gs_spz_options dflt;
     gs_spz_options_default(&dflt);
     const gs_spz_options *opt = options ? options : &dflt;
-    ExportScan x;
+    ExtractScan x;
     GS_TRY(export_begin(g, s, sel, invert, x));
     gs_spz_header h;
     size_t off[6], bytes = 0;
     uint32_t ncoef = 0, bucket = 0;
     GS_TRY(gs_spz_encode_layout(x.total, opt, &h, off, &ncoef, &bucket, &bytes));
     if (!x.total) return gs_gzip_fast(&h, 16, out, out ? capacity : 0, bytes_out);      // the header alone: the same bytes from the host
-    uint8_t *dev_payload = nullptr;
-    GS_TRY(dev_alloc((void **)&dev_payload, bytes, bytes, "hipMalloc"));
+    DevMem mem;
+    GS_TRY(mem.alloc(bytes, bytes, "hipMalloc"));
+    uint8_t *dev_payload = (uint8_t *)mem.ptr;
     hipError_t e = hipMemcpyAsync(dev_payload, &h, 16, hipMemcpyHostToDevice, x.st);
     if (e == hipSuccess) e = export_spz_columns(g, x, h, off, ncoef, bucket, dev_payload);
-    gs_status rc = e == hipSuccess ? gzip_fast_device(x.st, dev_payload, bytes, out, out ? capacity : 0, bytes_out)
-                                   : gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
-    if (e != hipSuccess) (void)hipStreamSynchronize(x.st);
-    (void)hipFree(dev_payload);
-    return rc;
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(x.st);      // the header's copy may be in flight, and the payload is freed at the return
+        return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "export failed: %s", hipGetErrorString(e));
+    }
+    // (a member that fails after its kernels returns without a wait: the frees of its scratch and of the payload wait)
+    return gzip_fast_device(x.st, dev_payload, bytes, out, out ? capacity : 0, bytes_out);
 }
 
 extern "C" gs_status gs_gaussians_buffer_write(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
@@ -269,7 +241,7 @@ extern "C" gs_status gs_gaussians_buffer_write(gs_gaussians_buffer *g, gs_stream
     *bytes_out = 0;
     switch (source) {
     case GS_SOURCE_PLY: {
-        ExportScan x;
+        ExtractScan x;
         GS_TRY(export_begin(g, s, sel, invert, x));
         const std::string hdr = gs_ply_header(x.total);
         const size_t bytes = hdr.size() + (size_t)x.total * sizeof(gs_ply_gaussian_pod);

@@ -94,6 +94,42 @@ void dev_free(DevArray &a);
 gs_status dev_alloc(void **out, size_t bytes, uint64_t b, const char *what);
 // ids of buffers and generations of selections: unique in the process, never 0
 uint64_t next_object_id();
+// a gs_buffer of one reference over `ptr`: owned (released with hipFree) or borrowed
+gs_buffer *make_buffer(gs_device *dev, void *ptr, size_t bytes, bool owned);
+// `bytes` of device memory into host memory on `st`, awaited; the caller words the failure
+hipError_t fetch(hipStream_t st, void *dst, const void *src, size_t bytes);
+
+// ---- scoped owners of what ONE call holds across its blocking part ----
+// Each frees in its destructor, with the device of use_device() current.  hipFree waits for the device, but the functions
+// do not lean on that: whoever has enqueued work on an owner's memory synchronises the stream(s) before it returns, on every
+// path (the few returns that rely on the wait instead say so).  An enqueue-only call hands its memory on: release().
+struct NoCopy {
+    NoCopy() noexcept = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+struct DevMem : NoCopy {
+    ~DevMem() noexcept { if (ptr) (void)hipFree(ptr); }
+    // through dev_alloc, with its error (once per owner) ... and for the sites that word the failure themselves
+    gs_status alloc(size_t bytes, uint64_t b, const char *what) noexcept { return dev_alloc(&ptr, bytes, b, what); }
+    hipError_t alloc_raw(size_t bytes) noexcept { return hipMalloc(&ptr, bytes); }
+    void *release() noexcept { void *p = ptr; ptr = nullptr; return p; }
+    void *ptr = nullptr;
+};
+struct Event : NoCopy {      // hipEventDisableTiming
+    ~Event() noexcept { if (e) (void)hipEventDestroy(e); }
+    hipError_t create() noexcept { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+    hipEvent_t e = nullptr;
+};
+struct Stream : NoCopy {     // hipStreamNonBlocking
+    ~Stream() noexcept { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() noexcept { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    hipStream_t s = nullptr;
+};
+// a DevArray that lives for one call (dev_reserve grows it as any other)
+struct ScopedDevArray : DevArray, NoCopy {
+    ~ScopedDevArray() noexcept { dev_free(*this); }
+};
 
 }  // namespace gsh
 
@@ -188,6 +224,20 @@ inline gs_status check_len32(size_t len) {
 gs_status wait_for_edits(const gs_gaussians_buffer *g, hipStream_t st);
 // ... and `st` has just been given such work: whoever reads or writes the records on another stream waits for it
 gs_status record_edit(gs_gaussians_buffer *g, hipStream_t st);
+// What a call that reads the records of `g` under a selection (NULL: all; invert: the unselected) starts with.
+// records_check: the selection fits the buffer and the kernels can index it -> len, n, nblocks, words, inv, dev; touches
+// no device.  records_access: ... then dev is current, st is the stream of the call and waits for edits in flight.
+// An entry point with checks of its own between the two halves calls records_check and goes on by hand.
+struct RecordsAccess {
+    gs_device *dev = nullptr;
+    hipStream_t st = nullptr;
+    size_t len = 0;
+    uint32_t n = 0, nblocks = 0;      // nblocks: whole and partial 1024-blocks
+    const uint32_t *words = nullptr;
+    uint32_t inv = 0;
+};
+gs_status records_check(const gs_gaussians_buffer *g, const gs_stream *s, const gs_selection *sel, int32_t invert, RecordsAccess &a);
+gs_status records_access(const gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert, RecordsAccess &a);
 
 // ---- gs3d.hip ----
 // gs_device_create: do returning LDS atomics hand out lane-ordered values (the fast radix rank)?  Blocks on `st`.
@@ -226,8 +276,21 @@ gs_status extract_scan(hipStream_t st, const uint32_t *words, uint32_t n, uint32
 // k_extract_copy: the `total` records the scan counted, src (n records of nc 16-byte chunks) -> dst, packed in index order
 void extract_copy_enqueue(hipStream_t st, const void *src, void *dst, const uint32_t *words, uint32_t n, uint32_t invert,
                           const uint32_t *offsets, uint32_t nc, uint32_t total);
+// what extraction, conversion and the exports start with: records_access, the scan into an array of the call, its total on
+// the host (n == 0: no array, total 0).  Blocks on x.st.
+struct ExtractScan : RecordsAccess {
+    ScopedDevArray scan;      // the per-1024-block offsets, then the total
+    uint32_t total = 0;
+    const uint32_t *offsets() const { return (const uint32_t *)scan.ptr; }
+};
+gs_status extract_begin(const gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert, ExtractScan &x);
 
 // ---- gs_relayout.hip ----
+// The body of gs_gaussians_buffer_create_from_selection ((dsh, dcov) = the layout of src) and _create_converted: the
+// selected records as a new buffer of layout (dsh, dcov).  Blocks.  A copy that fails leaves the HIP error in *copy_error
+// and returns GS_ERR_HIP without a message: the entry point words it.
+gs_status extract_records(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel, int32_t invert, int dsh, int dcov,
+                          gs_gaussians_buffer **out, uint64_t *count_out, hipError_t *copy_error);
 // gs_gaussians_buffer_create_concat (as_layout false: the sources share one layout, which the result takes) and
 // gs_gaussians_buffer_create_concat_as (as_layout true: every source is converted to (dsh, dcov))
 gs_status concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels, uint32_t count, bool as_layout,

@@ -86,17 +86,16 @@ extern "C" gs_status gs_gaussians_buffer_neighbor_counts(gs_gaussians_buffer *g,
     if (!g || !counts_out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     GS_TRY(check_neighbor_radius(radius));
     if (!cap) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "cap must be at least 1");
-    GS_TRY(check_buffer_selection(g, s, among));
-    const size_t len = gs_gaussians_buffer_len(g);
-    GS_TRY(check_len32(len));
+    RecordsAccess r;
+    GS_TRY(records_check(g, s, among, 0, r));
+    const size_t len = r.len;
     if (counts_out->dev != g->buf->dev) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "objects belong to different devices");
     if (counts_out->bytes < len * 4)
         return gs_fail(GS_ERR_INVALID_ARGUMENT, counts_out->bytes, len * 4, 0, "the count plane has %zu bytes, %zu Gaussians need %zu",
                     counts_out->bytes, len, len * 4);
     if (!len) return GS_OK;
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
+    GS_TRY(use_device(r.dev));
+    hipStream_t st = stream_of(r.dev, s);
     // the event on every path: an enqueue that failed half-way has still left kernels on the scratch
     const gs_status rc = neighbor_counts_enqueue(g, st, among, mt, radius, cap, false, (uint32_t *)counts_out->ptr, nullptr);
     const gs_status ev = neighbor_scratch_release(g, st);

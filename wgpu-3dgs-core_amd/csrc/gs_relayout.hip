@@ -59,6 +59,30 @@ static void convert_extract_enqueue(hipStream_t st, const gs_gaussians_buffer *s
                        words, n, invert, offsets, src->cov, dcov, dst_base, total);
 }
 
+gs_status gsh::extract_records(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel, int32_t invert, int dsh, int dcov,
+                               gs_gaussians_buffer **out, uint64_t *count_out, hipError_t *copy_error) {
+    ExtractScan x;
+    GS_TRY(extract_begin(src, s, sel, invert, x));
+    gs_gaussians_buffer *dst = nullptr;
+    if (x.total) {
+        GS_TRY(gaussians_buffer_create_unfilled(x.dev, dsh, dcov, x.total, &dst));
+        convert_extract_enqueue(x.st, src, dsh, dcov, dst->buf->ptr, 0, x.words, x.n, x.inv, x.offsets(), x.total);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(x.st);      // the offsets are freed with `x`; the call is blocking anyway
+        if (e != hipSuccess) {
+            gs_gaussians_buffer_destroy(dst);
+            *copy_error = e;
+            return GS_ERR_HIP;
+        }
+    } else {
+        GS_TRY(gs_gaussians_buffer_create(x.dev, (gs_sh_config)dsh, (gs_cov3d_config)dcov, nullptr, 0, &dst));
+    }
+    dst->spatial = src->spatial;
+    *out = dst;
+    if (count_out) *count_out = x.total;
+    return GS_OK;
+}
+
 extern "C" gs_status gs_gaussians_buffer_create_converted(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel, int32_t invert,
                                                           gs_sh_config dst_sh, gs_cov3d_config dst_cov, gs_gaussians_buffer **out,
                                                           uint64_t *count_out) {
@@ -67,44 +91,10 @@ extern "C" gs_status gs_gaussians_buffer_create_converted(gs_gaussians_buffer *s
     if (count_out) *count_out = 0;
     GS_TRY(check_pair(src->sh, src->cov, dst_sh, dst_cov));
     if (src->sh == (int)dst_sh && src->cov == (int)dst_cov) return gs_gaussians_buffer_create_from_selection(src, s, sel, invert, out, count_out);
-    GS_TRY(check_buffer_selection(src, s, sel));
-    const size_t len = gs_gaussians_buffer_len(src);
-    GS_TRY(check_len32(len));
-    gs_device *dev = src->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
-    GS_TRY(wait_for_edits(src, st));
-    const uint32_t n = (uint32_t)len, inv = invert ? 1u : 0u;
-    const uint32_t nblocks = (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
-    const uint32_t *words = sel ? (const uint32_t *)sel->words : nullptr;
-    DevArray scan;      // the per-block offsets, then the total
-    uint32_t total = 0;
-    gs_status rc = GS_OK;
-    if (n) {
-        rc = dev_reserve(scan, ((size_t)nblocks + 1) * 4);
-        if (rc == GS_OK) rc = extract_scan(st, words, n, inv, (uint32_t *)scan.ptr, (uint32_t *)scan.ptr + nblocks, &total);
-    }
-    gs_gaussians_buffer *dst = nullptr;
-    if (rc == GS_OK && total) {
-        rc = gaussians_buffer_create_unfilled(dev, dst_sh, dst_cov, total, &dst);
-    } else if (rc == GS_OK) {
-        rc = gs_gaussians_buffer_create(dev, dst_sh, dst_cov, nullptr, 0, &dst);
-    }
-    if (rc == GS_OK && total) {
-        convert_extract_enqueue(st, src, dst_sh, dst_cov, dst->buf->ptr, 0, words, n, inv, (const uint32_t *)scan.ptr, total);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(st);      // the offsets are freed below; the call is blocking anyway
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "conversion failed: %s", hipGetErrorString(e));
-    }
-    dev_free(scan);
-    if (rc != GS_OK) {
-        if (dst) gs_gaussians_buffer_destroy(dst);
-        return rc;
-    }
-    dst->spatial = src->spatial;
-    *out = dst;
-    if (count_out) *count_out = total;
-    return GS_OK;
+    hipError_t e = hipSuccess;
+    const gs_status rc = extract_records(src, s, sel, invert, dst_sh, dst_cov, out, count_out, &e);
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "conversion failed: %s", hipGetErrorString(e));
+    return rc;
 }
 
 extern "C" gs_status gs_gaussians_buffer_create_concat_as(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
@@ -141,41 +131,37 @@ gs_status gsh::concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, co
     GS_TRY(use_device(dev));
     hipStream_t st = stream_of(dev, s);
     // one array for all sources: the per-block offsets of source i from block0[i] on, then one total per source
-    uint32_t *scan = nullptr;
-    GS_TRY(dev_alloc((void **)&scan, (nblocks_all + 64) * 4, 0, "hipMalloc"));
-    uint32_t *totals_dev = scan + nblocks_all;
+    DevMem scan_mem;
+    GS_TRY(scan_mem.alloc((nblocks_all + 64) * 4, 0, "hipMalloc"));
+    uint32_t *scan = (uint32_t *)scan_mem.ptr, *totals_dev = scan + nblocks_all;
     uint32_t totals[64] = {};
     size_t block0[64] = {};
-    gs_status rc = GS_OK;
     hipError_t e = hipMemsetAsync(totals_dev, 0, 64 * 4, st);
     size_t b0 = 0;
-    for (uint32_t i = 0; i < count && e == hipSuccess && rc == GS_OK; i++) {
+    for (uint32_t i = 0; i < count && e == hipSuccess; i++) {
         gs_gaussians_buffer *g = srcs[i];
         const uint32_t n = (uint32_t)gs_gaussians_buffer_len(g);
         block0[i] = b0;
         b0 += (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
         if (!n) continue;
-        rc = wait_for_edits(g, st);
-        if (rc != GS_OK) break;
+        GS_TRY(wait_for_edits(g, st));      // (scans of earlier sources may be in flight: the array's hipFree waits for them)
         extract_scan_enqueue(st, sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr, n, 0u, scan + block0[i], totals_dev + i);
         e = hipGetLastError();
     }
     // sizing the new buffer needs the totals on the host: the one round trip of the call
-    if (rc == GS_OK && e == hipSuccess) e = hipMemcpyAsync(totals, totals_dev, (size_t)count * 4, hipMemcpyDeviceToHost, st);
-    if (rc == GS_OK && e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = fetch(st, totals, totals_dev, (size_t)count * 4);
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
     uint64_t total = 0;
-    if (rc == GS_OK && e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "selection scan failed: %s", hipGetErrorString(e));
-    for (uint32_t i = 0; i < count && rc == GS_OK; i++) {
+    for (uint32_t i = 0; i < count; i++) {
         const size_t len = gs_gaussians_buffer_len(srcs[i]);
-        if (totals[i] > len) rc = gs_fail(GS_ERR_HIP, totals[i], len, 0, "selection scan returned %u of %zu Gaussians", totals[i], len);
+        if (totals[i] > len) return gs_fail(GS_ERR_HIP, totals[i], len, 0, "selection scan returned %u of %zu Gaussians", totals[i], len);
         total += totals[i];
     }
-    if (rc == GS_OK && total > 0xfffffff0ull)
-        rc = gs_fail(GS_ERR_INVALID_ARGUMENT, total, 0, 0, "the concatenation would hold %llu Gaussians", (unsigned long long)total);
+    if (total > 0xfffffff0ull)
+        return gs_fail(GS_ERR_INVALID_ARGUMENT, total, 0, 0, "the concatenation would hold %llu Gaussians", (unsigned long long)total);
     gs_gaussians_buffer *dst = nullptr;
-    if (rc == GS_OK && total) rc = gaussians_buffer_create_unfilled(dev, sh, cov, (size_t)total, &dst);
-    else if (rc == GS_OK) rc = gs_gaussians_buffer_create(dev, (gs_sh_config)sh, (gs_cov3d_config)cov, nullptr, 0, &dst);
-    if (rc == GS_OK && total) {
+    if (total) {
+        GS_TRY(gaussians_buffer_create_unfilled(dev, sh, cov, (size_t)total, &dst));
         uint64_t first = 0;      // where the part of source i starts in the new buffer
         for (uint32_t i = 0; i < count; i++) {
             if (!totals[i]) continue;
@@ -188,19 +174,16 @@ gs_status gsh::concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, co
         // The copies are only enqueued: the call has blocked once, for the totals.  The new buffer is ordered like an edited
         // one (frames, snapshots and extractions on other streams wait for the copies) and keeps the offsets they read.
         e = hipGetLastError();
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "concatenation failed: %s", hipGetErrorString(e));
-        else rc = record_edit(dst, st);
+        const gs_status rc = e != hipSuccess ? gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "concatenation failed: %s", hipGetErrorString(e))
+                                             : record_edit(dst, st);
         if (rc != GS_OK) {
-            (void)hipStreamSynchronize(st);
-        } else {
-            dst->concat_offsets = scan;
-            scan = nullptr;
+            (void)hipStreamSynchronize(st);      // the copies read the offsets, which are freed at the return
+            gs_gaussians_buffer_destroy(dst);
+            return rc;
         }
-    }
-    if (scan) (void)hipFree(scan);
-    if (rc != GS_OK) {
-        if (dst) gs_gaussians_buffer_destroy(dst);
-        return rc;
+        dst->concat_offsets = scan_mem.release();
+    } else {
+        GS_TRY(gs_gaussians_buffer_create(dev, (gs_sh_config)sh, (gs_cov3d_config)cov, nullptr, 0, &dst));
     }
     dst->spatial = srcs[0]->spatial;
     *out = dst;

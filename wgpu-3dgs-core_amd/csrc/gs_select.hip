@@ -14,27 +14,22 @@ extern "C" gs_status gs_selection_create(gs_device *dev, size_t n, gs_selection 
     if (!dev || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     GS_TRY(check_len32(n));
     GS_TRY(use_device(dev));
-    gs_selection *sel = new gs_selection();
-    sel->dev = dev;
-    sel->n = n;
-    sel->nwords = (n + 31) / 32;
-    sel->words = nullptr;
-    sel->generation = next_object_id();
-    const size_t bytes = (sel->nwords ? sel->nwords : 1) * 4;
-    if (gs_status rc = dev_alloc((void **)&sel->words, bytes, 0, "selection allocation")) {
-        delete sel;
-        return rc;
-    }
-    hipError_t e = hipMemset(sel->words, 0, bytes);
+    const size_t nwords = (n + 31) / 32, bytes = (nwords ? nwords : 1) * 4;
+    DevMem words;
+    GS_TRY(words.alloc(bytes, 0, "selection allocation"));
+    hipError_t e = hipMemset(words.ptr, 0, bytes);
     // (awaited: the null stream's fill is not ordered against the non-blocking stream of the upload that follows, and a
     // late fill clears a mask that was uploaded and already read once)
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipFree(sel->words);
-        delete sel;
+    if (e != hipSuccess)
         return gs_fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "selection allocation failed: %s",
                     hipGetErrorString(e));
-    }
+    gs_selection *sel = new gs_selection();
+    sel->dev = dev;
+    sel->n = n;
+    sel->nwords = nwords;
+    sel->words = (uint32_t *)words.release();
+    sel->generation = next_object_id();
     *out = sel;
     return GS_OK;
 }

@@ -66,9 +66,9 @@ extern "C" gs_status gs_gaussians_buffer_stats(gs_gaussians_buffer *g, gs_stream
                                                const gs_model_transform_pod *mt, const float ref[3], gs_stats *out) {
     if (!g || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     if (ref && !all_finite(ref, 3)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the reference point must be finite");
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    GS_TRY(check_len32(len));
+    RecordsAccess r;
+    GS_TRY(records_check(g, s, sel, 0, r));
+    const size_t len = r.len;
     static_assert(sizeof(gs::StatsOut) == sizeof(gs_stats), "the device result is a gs_stats");
     gs_stats res;
     std::memset(&res, 0, sizeof(res));
@@ -77,10 +77,10 @@ extern "C" gs_status gs_gaussians_buffer_stats(gs_gaussians_buffer *g, gs_stream
         a.max = -INFINITY;
     }
     if (len) {
-        gs_device *dev = g->buf->dev;
-        GS_TRY(use_device(dev));
-        hipStream_t st = stream_of(dev, s);
-        const uint32_t n = (uint32_t)len, nblocks = (n + 255u) / 256u;
+        // (the scratch grows before the wait for edits, as it always did: the second half of records_access by hand)
+        GS_TRY(use_device(r.dev));
+        hipStream_t st = stream_of(r.dev, s);
+        const uint32_t n = r.n, nblocks = (n + 255u) / 256u;
         // [the result, 256 bytes][the sums: 9 x nblocks doubles][the integer fields: 28 x nblocks words]
         const size_t d_bytes = (size_t)gs::ATTR_COUNT * nblocks * 8, u_bytes = (size_t)gs::STATS_U_FIELDS * nblocks * 4;
         GS_TRY(dev_reserve(g->stats_scratch, 256 + d_bytes + u_bytes));
@@ -92,7 +92,7 @@ extern "C" gs_status gs_gaussians_buffer_stats(gs_gaussians_buffer *g, gs_stream
         gs::AttrArgs a;
         attr_args_fill(a, 0u, mt, ref);
         hipLaunchKernelGGL(k_tbl_stats[g->sh][g->cov], dim3(nblocks), dim3(256), 0, st, (const uint32_t *)g->buf->ptr, n,
-                           sel ? (const uint32_t *)sel->words : nullptr, a, part_u, part_d, nblocks);
+                           r.words, a, part_u, part_d, nblocks);
         hipLaunchKernelGGL(gs::k_stats_finish, dim3(1), dim3(256), 0, st, (const uint32_t *)part_u, (const double *)part_d, nblocks, dout);
         GS_HIP(hipGetLastError());
         GS_HIP(hipMemcpyAsync(&res, dout, sizeof(res), hipMemcpyDeviceToHost, st));
@@ -113,26 +113,25 @@ extern "C" gs_status gs_gaussians_buffer_histogram(gs_gaussians_buffer *g, gs_st
         return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the range of a histogram must be finite, with hi > lo");
     const float scale = (float)bins / width;
     if (!std::isfinite(scale)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "bins / (hi - lo) is not finite in binary32");
-    GS_TRY(check_buffer_selection(g, s, sel));
-    const size_t len = gs_gaussians_buffer_len(g);
-    GS_TRY(check_len32(len));
+    RecordsAccess r;
+    GS_TRY(records_check(g, s, sel, 0, r));
+    const size_t len = r.len;
     const size_t slots = 2 * ((size_t)bins + 3);
     if (!len) {
         std::memset(counts_out, 0, slots * sizeof(uint64_t));
         return GS_OK;
     }
-    gs_device *dev = g->buf->dev;
-    GS_TRY(use_device(dev));
-    hipStream_t st = stream_of(dev, s);
+    GS_TRY(use_device(r.dev));
+    hipStream_t st = stream_of(r.dev, s);
     GS_TRY(dev_reserve(g->stats_scratch, slots * 8));
     // an edit enqueued on another stream still writes the records
     GS_TRY(wait_for_edits(g, st));
     GS_HIP(hipMemsetAsync(g->stats_scratch.ptr, 0, slots * 8, st));
     gs::AttrArgs a;
     attr_args_fill(a, ad->attr, ad->model_transform, ad->ref);
-    const uint32_t n = (uint32_t)len, nblocks = (n + 255u) / 256u, grid = nblocks < 2048u ? nblocks : 2048u;
+    const uint32_t n = r.n, nblocks = (n + 255u) / 256u, grid = nblocks < 2048u ? nblocks : 2048u;
     hipLaunchKernelGGL(histogram_kernel(g, ad->attr), dim3(grid), dim3(256), slots * 4, st, (const uint32_t *)g->buf->ptr,
-                       (uint32_t)(pod_stride(g) / 4), n, sel ? (const uint32_t *)sel->words : nullptr, a, lo, hi, scale, bins,
+                       (uint32_t)(pod_stride(g) / 4), n, r.words, a, lo, hi, scale, bins,
                        (unsigned long long *)g->stats_scratch.ptr);
     GS_HIP(hipGetLastError());
     // into a host copy first: counts_out stays untouched when the stream reports a failure
