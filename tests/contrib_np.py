@@ -8,7 +8,6 @@ import hashlib
 
 import numpy as np
 
-import helpers
 import synth
 
 CONTRIBUTION_DTYPE = np.dtype([("sum", "<u8"), ("hits", "<u4"), ("wmax", "<f4")])
@@ -99,11 +98,6 @@ def scene_a():
 
 
 SCENE_A_SIZE = (90, 58)
-
-
-def scene_a_setup(gs, ob, sh, cov, mode=0, **cam_kw):
-    W, H = SCENE_A_SIZE
-    return helpers.round_setup(gs, ob, scene_a(), W, H, sh, cov, mode=mode, **cam_kw)
 
 
 def assert_scene_a_conditions(ob, tiles, skeys, sidx, ranges, ocam, ogt, proj, order, exp):

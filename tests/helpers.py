@@ -29,6 +29,10 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def same_bits(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
 def band_rows(band, H):
     """pixel rows [y0, y1) of a band of tile rows (None: the whole image)"""
     return (0, H) if band is None else (band[0] * 16, min(band[1] * 16, H))
@@ -67,19 +71,6 @@ def small_image_scene(W, H):
     if key not in _small_image_scenes:
         _small_image_scenes[key] = deep_scene(spec["n"], first=spec["first"], opacity=spec["opacity"], scale=spec["scale"])
     return _small_image_scenes[key]
-
-
-def round_setup(gs, ob, g, W, H, sh, cov, mode=0, **cam_kw):
-    """pods and the oracle's and the product's transforms and camera of a scene of the two-round tests"""
-    pod = gs.GaussianPod(sh, cov)
-    pods = pod.from_gaussian(g)
-    ogt = ob.gaussian_transform(sh_deg=0, mode=mode)
-    omt = ob.model_transform()
-    ocam = default_camera(ob, W, H, **cam_kw)
-    gt = gs.gaussian_transform_pod(1.0, mode, 0, False, 3.0)
-    mt = gs.model_transform_pod((0, 0, 0), (0, 0, 0, 1), (1, 1, 1))
-    cam = copy_camera(ocam, gs.Camera)
-    return pod, pods, ogt, omt, ocam, gt, mt, cam
 
 
 def pair_walk(k):

@@ -13,50 +13,27 @@ import pytest
 
 import convert_np
 import edit_np
+from records import diff
+from scenes import ALL_LAYOUTS, hostile_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TITLE = "Layout conversion"
 ENTRIES = ["gs_layout_convertible", "gs_convert_pods", "gs_gaussians_buffer_create_converted", "gs_gaussians_buffer_create_concat_as"]
-LAYOUTS = [(s, c) for s in range(4) for c in range(3)]
-PAIRS = [(a, b) for a in LAYOUTS for b in LAYOUTS]
+PAIRS = [(a, b) for a in ALL_LAYOUTS for b in ALL_LAYOUTS]
 VALID = [(a, b) for a, b in PAIRS if convert_np.convertible(*a, *b)]
 f32 = np.float32
 N = 257
 
 
-def _scene(n, seed=3):
-    """the scene of tests/test_gpu_edit.py: SH beyond [-1, 1], NaN and Inf in SH, position and scale"""
-    import synth
-    g = synth.scene(n, first=seed)
-    rng = np.random.default_rng(seed)
-    g["color"] = rng.integers(0, 256, (n, 4), dtype=np.uint8)
-    g["sh"] = rng.uniform(-1.2, 1.2, (n, 45)).astype(f32)
-    g["pos"][5] = np.nan
-    g["pos"][6, 1] = np.inf
-    g["pos"][7] = (-np.inf, 1.0, np.nan)
-    g["sh"][8, 3] = np.nan
-    g["sh"][9, 4] = np.inf
-    g["scale"][10] = (np.inf, 1.0, 0.0)
-    return g
-
-
 @pytest.fixture(scope="module")
 def packed(gs):
     """{(sh, cov): the N records of the scene packed by gs_pack}, computed once and left unchanged"""
-    g = _scene(N)
+    g = hostile_scene(N)
     out = {}
-    for sh, cov in LAYOUTS:
+    for sh, cov in ALL_LAYOUTS:
         out[(sh, cov)] = gs.GaussianPod(sh, cov).from_gaussian(g)
         out[(sh, cov)].setflags(write=False)
     return out, g
-
-
-def _diff(got, want, nb):
-    got, want = got.reshape(-1, nb), want.reshape(-1, nb)
-    bad = np.flatnonzero((got != want).any(axis=1))
-    if len(bad) == 0:
-        return ""
-    return "%d records differ; first %d at bytes %s" % (len(bad), bad[0], np.flatnonzero(got[bad[0]] != want[bad[0]])[:12].tolist())
 
 
 # ---- header and bindings ---------------------------------------------------------------------------------------------
@@ -167,19 +144,19 @@ def test_pair_table(gs):
 
 # ---- bytes -----------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("src", LAYOUTS)
+@pytest.mark.parametrize("src", ALL_LAYOUTS)
 def test_bytes_equal_the_restatement(gs, packed, src):
     pods, _ = packed
     spod = gs.GaussianPod(*src)
     done = 0
-    for dst in LAYOUTS:
+    for dst in ALL_LAYOUTS:
         if (src, dst) not in VALID:
             continue
         dpod = gs.GaussianPod(*dst)
         got = spod.convert(pods[src], dpod)
         assert got.size == N * dpod.size == N * edit_np.pod_bytes(*dst)
         want = convert_np.convert(*src, *dst, pods[src])
-        assert np.array_equal(got, want), (src, dst, _diff(got, want, dpod.size))
+        assert np.array_equal(got, want), (src, dst, diff(got, want, dpod.size))
         done += 1
     assert done == (12 if src[1] == 0 else 8)
 
@@ -190,10 +167,10 @@ def test_bytes_equal_unpack_then_pack(gs, packed, src):
     pods, _ = packed
     spod = gs.GaussianPod(*src)
     g = spod.into_gaussian(pods[src])
-    for dst in LAYOUTS:
+    for dst in ALL_LAYOUTS:
         dpod = gs.GaussianPod(*dst)
         got, want = spod.convert(pods[src], dpod), dpod.from_gaussian(g)
-        assert np.array_equal(got, want), (src, dst, _diff(got, want, dpod.size))
+        assert np.array_equal(got, want), (src, dst, diff(got, want, dpod.size))
         if src == (0, 0):       # the f32 / rot-scale layout holds the Gaussians themselves
             assert np.array_equal(got, pods[dst]), (src, dst)
 
@@ -249,7 +226,7 @@ def test_a_kept_section_is_copied_verbatim(gs):
     back = gs.GaussianPod(0, 0).convert(gs.GaussianPod(1, 0).convert(src.reshape(-1), gs.GaussianPod(0, 0)), gs.GaussianPod(1, 0))
     assert back.reshape(len(src), -1)[:, 16:108].view(np.uint16)[0, 7] == 0x7F01
     # identical layouts keep every byte
-    for sh, cov in LAYOUTS:
+    for sh, cov in ALL_LAYOUTS:
         src, _ = _raw_records(sh, cov)
         pod = gs.GaussianPod(sh, cov)
         assert np.array_equal(pod.convert(src.reshape(-1), pod), src.reshape(-1)), (sh, cov)

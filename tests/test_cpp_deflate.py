@@ -2,30 +2,16 @@
 against the C ABI on the CPU; on the GPU the compiled test compares the device member with the host member, inflates both and
 reads a saved scene back."""
 import os
-import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _build():
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    import wgpu_3dgs_core_amd  # noqa: F401  (builds the library if needed)
-    return ge.build_cpp_deflate_test()
+import cpp_test
 
 
 def test_cpp_deflate_compiles():
-    assert os.path.exists(_build())
+    assert os.path.exists(cpp_test.build("deflate"))
 
 
 @pytest.mark.gpu
 def test_cpp_deflate_on_gpu():
-    exe = os.path.join(ROOT, "build", "test_deflate")
-    if not os.path.exists(exe):
-        exe = _build()
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-    assert res.returncode == 0, res.stdout
-    assert "cpp deflate OK" in res.stdout
+    cpp_test.run("deflate", "cpp deflate OK")

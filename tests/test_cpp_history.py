@@ -2,30 +2,16 @@
 compiles against the C ABI on the CPU; on the GPU the compiled test takes a snapshot, edits, exchanges twice, concatenates
 and range-selects, and compares the bytes it downloads."""
 import os
-import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _build():
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    import wgpu_3dgs_core_amd  # noqa: F401  (builds the library if needed)
-    return ge.build_cpp_history_test()
+import cpp_test
 
 
 def test_cpp_history_compiles():
-    assert os.path.exists(_build())
+    assert os.path.exists(cpp_test.build("history"))
 
 
 @pytest.mark.gpu
 def test_cpp_history_on_gpu():
-    exe = os.path.join(ROOT, "build", "test_history")
-    if not os.path.exists(exe):
-        exe = _build()
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-    assert res.returncode == 0, res.stdout
-    assert "cpp history OK" in res.stdout
+    cpp_test.run("history", "cpp history OK")

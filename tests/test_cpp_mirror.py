@@ -2,23 +2,17 @@
 compiled test mirrors the reference's buffer / compute-bundle tests end to end."""
 import os
 import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_test
 
-
-def _build():
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    import wgpu_3dgs_core_amd  # noqa: F401  (builds the library if needed)
-    return ge.build_cpp_mirror_test()
+ROOT = cpp_test.ROOT
 
 
 def test_cpp_mirror_compiles_and_fails_loudly_without_gpu():
     import torch
-    exe = _build()
+    exe = cpp_test.build("mirror")
     if torch.cuda.is_available():
         pytest.skip("a GPU is present")
     res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -28,19 +22,12 @@ def test_cpp_mirror_compiles_and_fails_loudly_without_gpu():
 
 @pytest.mark.gpu
 def test_cpp_mirror_on_gpu():
-    exe = os.path.join(ROOT, "build", "test_mirror")
-    if not os.path.exists(exe):
-        exe = _build()
-    res = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
-    assert res.returncode == 0, res.stdout
-    assert "cpp mirror OK" in res.stdout
+    cpp_test.run("mirror", "cpp mirror OK")
 
 
 def test_cpp_fullsize_compiles_and_fails_loudly_without_gpu():
     import torch
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    exe = ge.build_cpp_fullsize_test()
+    exe = cpp_test.build("fullsize")
     if torch.cuda.is_available():
         pytest.skip("a GPU is present")
     res = subprocess.run([exe] + ["1000", "3", "0", "0", "64", "64", "x", "y", "z"], stdout=subprocess.PIPE,
@@ -58,11 +45,7 @@ def test_cpp_fullsize_on_the_runtime_the_library_is_built_for(name):
     spatial and the index mirror order."""
     import json
     g = json.load(open(os.path.join(ROOT, "tests", "golden", "fullsize_v3.json")))[name]
-    exe = os.path.join(ROOT, "build", "test_fullsize")
-    if not os.path.exists(exe):
-        sys.path.insert(0, ROOT)
-        import __graft_entry__ as ge
-        exe = ge.build_cpp_fullsize_test()
+    exe = cpp_test.exe("fullsize") if os.path.exists(cpp_test.exe("fullsize")) else cpp_test.build("fullsize")
     env = dict(os.environ)
     env.pop("LD_PRELOAD", None)
     env.pop("GS3D_ROUNDS", None)          # the renderer's own choice: the 10 M frames take two rounds from the second frame on

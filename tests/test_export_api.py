@@ -3,7 +3,6 @@ gs_convert.h's gaussian_to_ply_words / gaussian_to_spz_bytes, the functions the 
 Gaussian::to_ply / to_spz and against tests/golden/export_v1.npz; the declarations of the new entry points; what they check
 before they need a device."""
 import ctypes as C
-import importlib.util
 import os
 import re
 import subprocess
@@ -11,6 +10,8 @@ import sys
 
 import numpy as np
 import pytest
+
+import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ["gs_gaussians_buffer_export_ply", "gs_gaussians_buffer_export_spz_decompressed", "gs_gaussians_buffer_export_spz",
@@ -20,23 +21,14 @@ N = 20000
 CONFIGS = [(v, d, b) for v in (1, 2, 3) for d in (0, 1, 2, 3) for b in (8, 5, 4, 0)]
 
 
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "golden", name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
 @pytest.fixture(scope="module")
 def mk():
-    return _load("make_golden_export")
+    return scenes.golden_export()
 
 
 @pytest.fixture(scope="module")
-def scene(gs, mk):
-    g = mk.scene(N)
-    g.setflags(write=False)
-    return g
+def scene(gs):
+    return scenes.export_scene(N)
 
 
 def _is_nan(bits):

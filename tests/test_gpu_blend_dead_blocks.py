@@ -236,7 +236,7 @@ def _gaussians(name, case):
 def _child(out):
     """renders every case under this process's switches"""
     with gpu_child.child_rig() as (gs, _, dev, st):
-        from test_gpu_render_aux import Planes
+        from planes import Planes
         res = {}
         cases = dict(CASES)
         cases["rounds"] = ROUNDS_CASE
@@ -296,7 +296,7 @@ def _oracle(ob, name, case):
     """the oracle's planes of a case and its lists; computed once per case"""
     if name in _ORACLE:
         return _ORACLE[name]
-    from test_gpu_render_aux import _oracle_depth
+    from planes import oracle_depth
     kind, W, H, mode, band, vfov = case
     pods = ob.pack(SH, COV, _gaussians(name, case))
     ogt, omt = ob.gaussian_transform(sh_deg=0, mode=mode), ob.model_transform()
@@ -309,7 +309,7 @@ def _oracle(ob, name, case):
     ranges = ob.tile_ranges(skeys, tiles_x * tiles_y)
     rgba = ob.blend(proj, sidx, ranges, ocam, band=band, gt=ogt)
     _ORACLE[name] = dict(rgba=rgba, proj=proj, sidx=sidx, ranges=ranges, tiles_x=tiles_x, tiles_y=tiles_y, ocam=ocam, ogt=ogt,
-                         depth=lambda: _oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band))
+                         depth=lambda: oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band))
     return _ORACLE[name]
 
 
@@ -405,13 +405,13 @@ def test_dead_blocks_equal_the_oracle(ob, frames, name):
 
 
 def test_round_two_resumes_with_dead_blocks(ob, gs, frames):
-    from test_gpu_render_aux import _witness
+    from planes import pick_witness
     name, case = "rounds", ROUNDS_CASE
     kind, W, H, mode, band, vfov = case
     o = _oracle(ob, name, case)
     _check_scene(ob, name, case, o)
     o_depth = o["depth"]()
-    w_pick, amb = _witness(o["proj"], o["sidx"], o["ranges"], W, H, o["tiles_x"], 0.5)
+    w_pick, amb = pick_witness(o["proj"], o["sidx"], o["ranges"], W, H, o["tiles_x"], 0.5)
     assert amb.mean() <= 1e-2
     for frame in range(2):
         k = "%s/f%d/" % (name, frame)

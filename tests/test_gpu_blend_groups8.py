@@ -62,7 +62,7 @@ def _gaussians(case):
 def _child(set_name, out):
     """renders every case of the set under this process's switches"""
     with gpu_child.child_rig() as (gs, _, dev, st):
-        from test_gpu_render_aux import Planes
+        from planes import Planes
         cases = SETS[set_name][0]
         res = {}
         for name, case in cases.items():
@@ -123,12 +123,12 @@ def _bits(a):
 
 def _oracle(ob, case, name=None):
     """the oracle's colour and depth planes of a case, and what its lists looked like"""
-    from test_gpu_render_aux import _oracle_depth
+    from planes import oracle_depth
     W, H, n, first, mode, band, dense = case
     pods = ob.pack(SH, COV, _gaussians(case))
     ogt, omt = ob.gaussian_transform(sh_deg=0, mode=mode), ob.model_transform()
     ocam = helpers.default_camera(ob, W, H, **CAMERA.get(name, {}))
-    order = ob.spatial_order(SH, COV, pods)      # a fresh buffer's mirror order (tests/test_gpu_render.py: _mirror_order)
+    order = ob.spatial_order(SH, COV, pods)      # a fresh buffer's mirror order (tests/frames.py: mirror_order)
     proj, tiles = ob.preprocess(SH, COV, pods, ogt, omt, ocam, band=band)
     tiles_x, tiles_y = (W + 15) // 16, (H + 15) // 16
     keys, idx = ob.build_keys(proj, tiles, tiles_x, order=order)
@@ -136,7 +136,7 @@ def _oracle(ob, case, name=None):
     ranges = ob.tile_ranges(skeys, tiles_x * tiles_y)
     rgba = ob.blend(proj, sidx, ranges, ocam, band=band, gt=ogt)
     return dict(rgba=rgba, proj=proj, sidx=sidx, ranges=ranges, ocam=ocam, ogt=ogt, tiles_x=tiles_x,
-                depth=lambda: _oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band))
+                depth=lambda: oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band))
 
 
 def _pixels_finishing_mid_list(o, W, H):

@@ -134,7 +134,7 @@ def _gaussians(scene, W, H):
 def _child(set_name, out):
     """renders every case of the set under this process's switches"""
     with gpu_child.child_rig() as (gs, _, dev, st):
-        from test_gpu_render_aux import Planes
+        from planes import Planes
         res = {}
         for name, (scene, W, H, mode, band) in SETS[set_name].items():
             pod = gs.GaussianPod(SH, COV)
@@ -195,12 +195,12 @@ def _oracle(ob, name, case):
     """the oracle's planes of a case and what its lists look like; computed once per case"""
     if name in _ORACLE:
         return _ORACLE[name]
-    from test_gpu_render_aux import _oracle_depth
+    from planes import oracle_depth
     scene, W, H, mode, band = case
     pods = ob.pack(SH, COV, _gaussians(scene, W, H))
     ogt, omt = ob.gaussian_transform(sh_deg=0, mode=mode), ob.model_transform()
     ocam = helpers.default_camera(ob, W, H)
-    order = ob.spatial_order(SH, COV, pods)      # a fresh buffer's mirror order (tests/test_gpu_render.py: _mirror_order)
+    order = ob.spatial_order(SH, COV, pods)      # a fresh buffer's mirror order (tests/frames.py: mirror_order)
     proj, tiles = ob.preprocess(SH, COV, pods, ogt, omt, ocam, band=band)
     tiles_x, tiles_y = (W + 15) // 16, (H + 15) // 16
     keys, idx = ob.build_keys(proj, tiles, tiles_x, order=order)
@@ -208,7 +208,7 @@ def _oracle(ob, name, case):
     ranges = ob.tile_ranges(skeys, tiles_x * tiles_y)
     rgba = ob.blend(proj, sidx, ranges, ocam, band=band, gt=ogt)
     _ORACLE[name] = dict(rgba=rgba, proj=proj, sidx=sidx, ranges=ranges, tiles_x=tiles_x, tiles_y=tiles_y,
-                         depth=lambda: _oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band))
+                         depth=lambda: oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band))
     return _ORACLE[name]
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import helpers
+from scenes import synthetic_ply
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -143,10 +144,9 @@ def test_device_from_ply_equals_host_path(gs, ob, device, stream, pod_idx):
     gs_pack (same gs_convert.h arithmetic on both sides, incl. the specified exp): the reference's
     data file, 300 k synthetic vertices with hostile values (inf / NaN / overflowing and subnormal exp
     results / zero quaternions), and a ranged update."""
-    from test_ply import _synthetic_ply
     pod = gs.ALL_PODS[pod_idx]
     for name, ply in (("model.ply", gs.PlyGaussians.read_from_file(os.path.join(GOLD, "model.ply")).pods),
-                      ("synthetic", _synthetic_ply(300_000, seed=pod_idx))):
+                      ("synthetic", synthetic_ply(300_000, seed=pod_idx))):
         want = pod.from_gaussian(gs.gaussian_from_ply(ply))
         buf = gs.GaussiansBuffer.new_from_ply(device, pod, ply)
         assert len(buf) == len(ply)
@@ -162,7 +162,7 @@ def test_device_from_ply_equals_host_path(gs, ob, device, stream, pod_idx):
             raise AssertionError("\n".join(msg))
         # a ranged update through the same kernel
         if len(ply) > 1000:
-            part = _synthetic_ply(777, seed=100 + pod_idx)
+            part = synthetic_ply(777, seed=100 + pod_idx)
             buf.update_range_from_ply(stream, 123, part)
             w2 = want.reshape(len(ply), -1).copy()
             w2[123:123 + 777] = pod.from_gaussian(gs.gaussian_from_ply(part)).reshape(777, -1)
@@ -180,9 +180,8 @@ def test_device_from_ply_frame_and_load_time(gs, ob, device, stream):
     from_ply (libm), on a 1 M-vertex PLY written by the product's writer; also records the load time
     split (host from_ply vs device path) for DESIGN.md §7."""
     import time
-    from test_ply import _synthetic_ply
     n = 1_000_000
-    ply = _synthetic_ply(n, seed=77)
+    ply = synthetic_ply(n, seed=77)
     ply["pos"][:, 2] = -np.abs(ply["pos"][:, 2]) - 2.0
     ply["scale"] = np.clip(ply["scale"], -7.0, -2.5)
     ply["rot"][25:28] = (1.0, 0.1, 0.2, 0.3)

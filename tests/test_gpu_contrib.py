@@ -10,6 +10,7 @@ import pytest
 import contrib_np as cn
 import gpu_child
 import helpers
+from frames import frame_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,8 @@ class SceneA:
 
     def __init__(self, gs, ob, device, stream, sh, cov, mode=0, **cam_kw):
         self.gs, self.ob, self.device, self.sh, self.cov = gs, ob, device, sh, cov
-        self.pod, self.pods, self.ogt, self.omt, self.ocam, self.gt, self.mt, self.cam = cn.scene_a_setup(gs, ob, sh, cov, mode, **cam_kw)
+        self.pod, self.pods, self.ogt, self.omt, self.ocam, self.gt, self.mt, self.cam = frame_setup(
+            gs, ob, cn.scene_a(), *cn.SCENE_A_SIZE, sh, cov, mode=mode, **cam_kw)
         self.buf = gs.GaussiansBuffer.new_with_pods(device, self.pod, self.pods)
         self.order = self.buf.download_order(stream)
         self.img = gs.Buffer(device, data=np.full(H * W * 4, helpers.POISON))

@@ -5,10 +5,15 @@ another stream, and the frame of a converted buffer against the frame of a direc
 import numpy as np
 import pytest
 
+from frames import render_image
+from helpers import same_bits
+from records import diff, selection_from_mask
+from records import rows as _rows
+from scenes import ALL_LAYOUTS, packed_pods
+
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-LAYOUTS = [(s, c) for s in range(4) for c in range(3)]
 THREE_PAIRS = [((0, 0), (1, 2)), ((2, 1), (3, 2)), ((1, 2), (0, 1))]
 
 
@@ -16,75 +21,23 @@ def _ok(src, dst):
     return dst[1] != 0 or src[1] == 0
 
 
-def _scene(n, seed=3):
-    """the scene of tests/test_gpu_edit.py: SH beyond [-1, 1], NaN and Inf in SH, position and scale"""
-    import synth
-    g = synth.scene(n, first=seed)
-    rng = np.random.default_rng(seed)
-    g["color"] = rng.integers(0, 256, (n, 4), dtype=np.uint8)
-    g["sh"] = rng.uniform(-1.2, 1.2, (n, 45)).astype(f32)
-    if n > 10:
-        g["pos"][5] = np.nan
-        g["pos"][6, 1] = np.inf
-        g["pos"][7] = (-np.inf, 1.0, np.nan)
-        g["sh"][8, 3] = np.nan
-        g["sh"][9, 4] = np.inf
-        g["scale"][10] = (np.inf, 1.0, 0.0)
-    return g
-
-
-_SCENES = {}
-
-
-def _pods(gs, layout, n, seed=3):
-    """the scene packed for one layout: computed once per (layout, n, seed), read-only"""
-    key = (layout, n, seed)
-    if key not in _SCENES:
-        if ("g", n, seed) not in _SCENES:
-            _SCENES[("g", n, seed)] = _scene(n, seed)
-        p = gs.GaussianPod(*layout).from_gaussian(_SCENES[("g", n, seed)]) if n else np.zeros(0, np.uint8)
-        p.setflags(write=False)
-        _SCENES[key] = p
-    return _SCENES[key]
-
-
-def _rows(a, nb):
-    return np.asarray(a).reshape(-1, nb)
-
-
-def _diff(got, want, nb):
-    if got.size != want.size:
-        return "%d bytes, want %d" % (got.size, want.size)
-    got, want = _rows(got, nb), _rows(want, nb)
-    bad = np.flatnonzero((got != want).any(axis=1))
-    if len(bad) == 0:
-        return ""
-    return "%d records differ; first %d at bytes %s" % (len(bad), bad[0], np.flatnonzero(got[bad[0]] != want[bad[0]])[:12].tolist())
-
-
-def _selection(gs, device, stream, mask):
-    sel = gs.Selection(device, len(mask))
-    sel.upload(stream, mask)
-    return sel
-
-
 # ---- bytes -----------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("src", LAYOUTS)
+@pytest.mark.parametrize("src", ALL_LAYOUTS)
 def test_device_bytes_equal_the_host_conversion(gs, device, stream, src):
     n = 5003
     spod = gs.GaussianPod(*src)
-    pods = _pods(gs, src, n)
+    pods = packed_pods(gs, *src, n)
     buf = gs.GaussiansBuffer.new_with_pods(device, spod, pods)
     done = 0
-    for dst in LAYOUTS:
+    for dst in ALL_LAYOUTS:
         if not _ok(src, dst):
             continue
         dpod = gs.GaussianPod(*dst)
         out = buf.convert(stream, dpod)
         assert out.pod == dpod and out.len() == n
         got, want = out.download(stream), spod.convert(pods, dpod)
-        assert np.array_equal(got, want), (src, dst, _diff(got, want, dpod.size))
+        assert np.array_equal(got, want), (src, dst, diff(got, want, dpod.size))
         out.destroy()
         done += 1
     assert done == (12 if src[1] == 0 else 8)
@@ -109,16 +62,16 @@ def _masks(n):
 @pytest.mark.parametrize("src,dst", THREE_PAIRS)
 def test_conversion_is_fused_with_the_stable_compaction(gs, device, stream, src, dst, n):
     spod, dpod = gs.GaussianPod(*src), gs.GaussianPod(*dst)
-    pods = _pods(gs, src, n)
+    pods = packed_pods(gs, *src, n)
     buf = gs.GaussiansBuffer.new_with_pods(device, spod, pods)
     for name, mask, invert in _masks(n):
-        sel = _selection(gs, device, stream, mask)
+        sel = selection_from_mask(gs, device, stream, mask)
         out = buf.convert(stream, dpod, sel, invert=invert)
         keep = ~mask if invert else mask
         want = spod.convert(np.ascontiguousarray(_rows(pods, spod.size)[keep]).reshape(-1), dpod)
         assert out.len() == int(keep.sum()) and out.pod == dpod, (name, n)          # (convert() itself asserts len == count_out)
         got = out.download(stream)
-        assert np.array_equal(got, want), (name, n, _diff(got, want, dpod.size))
+        assert np.array_equal(got, want), (name, n, diff(got, want, dpod.size))
         if not keep.any():
             assert out.is_empty() and got.size == 0                                 # the valid length-0 buffer
             assert (gs._capi.load().gs_gaussians_buffer_sh(out._h), gs._capi.load().gs_gaussians_buffer_cov3d(out._h)) == dst
@@ -141,13 +94,13 @@ def test_a_source_of_length_zero(gs, device, stream):
 def test_identical_layouts_equal_extract(gs, device, stream, layout):
     n = 5003
     pod = gs.GaussianPod(*layout)
-    pods = np.array(_pods(gs, layout, n))
+    pods = np.array(packed_pods(gs, *layout, n))
     # nonzero trailing pad bytes, where the layout has any: identical layouts keep every byte
     used = 16 + [180, 92, 48, 0][layout[0]] + [28, 24, 12][layout[1]]
     _rows(pods, pod.size)[:, used:] = 0xCD
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
     mask = np.random.default_rng(9).random(n) < 0.3
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     for s, inv in ((None, False), (sel, False), (sel, True)):
         a, b = buf.convert(stream, pod, s, invert=inv), buf.extract(stream, s, invert=inv)
         got = a.download(stream)
@@ -165,7 +118,7 @@ def test_lossy_pairs_raise_and_create_nothing(gs, device, stream):
     n = 63
     lib = gs._capi.load()
     for src in [(s, c) for s in range(4) for c in (1, 2)]:
-        pods = _pods(gs, src, n)
+        pods = packed_pods(gs, *src, n)
         buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(*src), pods)
         for dsh in range(4):
             with pytest.raises(gs.LossyConfigError):
@@ -176,7 +129,7 @@ def test_lossy_pairs_raise_and_create_nothing(gs, device, stream):
         assert np.array_equal(buf.download(stream), pods)
         buf.destroy()
     # an unknown config and a selection of another length are argument errors
-    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(0, 0), _pods(gs, (0, 0), n))
+    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(0, 0), packed_pods(gs, 0, 0, n))
     h = C.c_void_p(1)
     assert lib.gs_gaussians_buffer_create_converted(buf._h, stream._h, None, 0, 4, 0, C.byref(h), None) == gs.InvalidArgumentError.code
     assert h.value is None
@@ -191,12 +144,12 @@ def test_lossy_pairs_raise_and_create_nothing(gs, device, stream):
 def test_concat_as(gs, device, stream):
     dst = gs.GaussianPod(1, 2)
     layouts, lens = [(0, 0), (1, 2), (3, 1)], [5003, 1025, 2049]
-    rows = [_pods(gs, l, n, seed=10 + k) for k, (l, n) in enumerate(zip(layouts, lens))]
+    rows = [packed_pods(gs, *l, n, seed=10 + k) for k, (l, n) in enumerate(zip(layouts, lens))]
     bufs = [gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(*l), r) for l, r in zip(layouts, rows)]
     rng = np.random.default_rng(12)
     order = [0, 1, 2, 0]
     masks = [None, rng.random(1025) < 0.5, None, rng.random(5003) < 0.3]
-    sels = [_selection(gs, device, stream, m) if m is not None else None for m in masks]
+    sels = [selection_from_mask(gs, device, stream, m) for m in masks]
     out, counts = gs.GaussiansBuffer.concat(stream, [bufs[k] for k in order], sels, pod=dst)
     parts = []
     for k, m in zip(order, masks):
@@ -206,7 +159,7 @@ def test_concat_as(gs, device, stream):
     assert counts == [len(p) // dst.size for p in parts]
     assert out.pod == dst and out.len() == sum(counts)
     got, want = out.download(stream), np.concatenate(parts)
-    assert np.array_equal(got, want), _diff(got, want, dst.size)
+    assert np.array_equal(got, want), diff(got, want, dst.size)
     for b, r in zip(bufs, rows):
         assert np.array_equal(b.download(stream), r), "the sources are untouched"
     # pod=None is today's call: one layout, bytes unchanged
@@ -240,7 +193,7 @@ def test_concat_as(gs, device, stream):
 def test_convert_is_ordered_behind_an_edit_on_another_stream(gs, device, stream):
     n = 5003
     spod, dpod = gs.GaussianPod(0, 0), gs.GaussianPod(1, 2)
-    pods = _pods(gs, (0, 0), n)
+    pods = packed_pods(gs, 0, 0, n)
     s1, s2 = stream, device.create_stream()
     buf = gs.GaussiansBuffer.new_with_pods(device, spod, pods)
     s1.synchronize()
@@ -251,26 +204,13 @@ def test_convert_is_ordered_behind_an_edit_on_another_stream(gs, device, stream)
     edited = buf.download(s1)
     assert (_rows(edited, 224) != _rows(pods, 224)).any(axis=1).mean() > 0.9
     got, want = out.download(s2), spod.convert(edited, dpod)
-    assert np.array_equal(got, want), _diff(got, want, dpod.size)
+    assert np.array_equal(got, want), diff(got, want, dpod.size)
     s2.synchronize()
     out.destroy(); buf.destroy()
     s2.close()
 
 
 # ---- renderable ------------------------------------------------------------------------------------------------------
-
-def _frame(gs, device, stream, r, buf, gt, mt, cam, W, H):
-    img = gs.Buffer(device, data=np.full(H * W * 4, f32(np.nan)))
-    fr = r.render(stream, buf, gt, mt, cam, img.device_ptr())
-    stream.synchronize()
-    out = img.download(stream, f32).reshape(H, W, 4).copy()
-    img.release()
-    return out, fr
-
-
-def _same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
 
 def test_a_converted_buffer_renders_like_a_direct_upload(gs, device, stream):
     import synth
@@ -282,16 +222,16 @@ def test_a_converted_buffer_renders_like_a_direct_upload(gs, device, stream):
     src = gs.GaussiansBuffer.new_with_pods(device, spod, spod.from_gaussian(g))
     direct = gs.GaussiansBuffer.new_with_pods(device, dpod, dpod.from_gaussian(g))
     r_src, r_conv, r_direct = gs.Renderer(device), gs.Renderer(device), gs.Renderer(device)
-    before, _ = _frame(gs, device, stream, r_src, src, gt, mt, cam, W, H)
+    before, _ = render_image(gs, device, stream, r_src, src, gt, mt, cam, W, H)
     conv = src.convert(stream, dpod)
     assert np.array_equal(conv.download(stream), direct.download(stream))
     assert conv.spatial_order() == src.spatial_order()
-    got, fr_c = _frame(gs, device, stream, r_conv, conv, gt, mt, cam, W, H)
-    want, fr_d = _frame(gs, device, stream, r_direct, direct, gt, mt, cam, W, H)
+    got, fr_c = render_image(gs, device, stream, r_conv, conv, gt, mt, cam, W, H)
+    want, fr_d = render_image(gs, device, stream, r_direct, direct, gt, mt, cam, W, H)
     assert fr_d.visible > 1000 and (fr_c.visible, fr_c.pairs) == (fr_d.visible, fr_d.pairs)
     assert np.array_equal(conv.download_order(stream), direct.download_order(stream))
-    assert _same(got, want)
-    after, _ = _frame(gs, device, stream, r_src, src, gt, mt, cam, W, H)
-    assert _same(after, before), "the source renders as before"
+    assert same_bits(got, want)
+    after, _ = render_image(gs, device, stream, r_src, src, gt, mt, cam, W, H)
+    assert same_bits(after, before), "the source renders as before"
     for o in (r_src, r_conv, r_direct, conv, direct, src):
         o.destroy()

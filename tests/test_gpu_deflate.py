@@ -5,47 +5,20 @@ every selection shape, the three layouts that can be exported and two option set
 a range past the buffer."""
 import ctypes as C
 import gzip
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
 import deflate_np
+from records import first_difference, selection_from_mask
+from scenes import deflate_selections, export_scene
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTABLE = [(0, 0), (1, 0), (2, 0)]
 REFUSED = [(s, c) for s in range(4) for c in range(3) if (s, c) not in EXPORTABLE]
 SIZES = [1, 64, 1025, 3000]
 NAMES = [name for name, _ in deflate_np.inputs()]
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "golden", name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-_MK = _load("make_golden_export")
-_SCENES = {}
-
-
-def _scene(n):
-    if n not in _SCENES:
-        g = _MK.scene(n)
-        g.setflags(write=False)
-        _SCENES[n] = g
-    return _SCENES[n]
-
-
-def _first_difference(got, want):
-    a, b = np.frombuffer(got, np.uint8), np.frombuffer(want, np.uint8)
-    m = min(len(a), len(b))
-    bad = np.flatnonzero(a[:m] != b[:m])
-    return "%d bytes, want %d; first difference at byte %s" % (len(a), len(b), bad[0] if len(bad) else ("none" if len(a) == len(b) else m))
 
 
 @pytest.fixture(scope="module")
@@ -59,7 +32,7 @@ def test_device_member_equals_the_host_member(gs, device, stream, host_members, 
     data, want = host_members[name]
     buf = gs.Buffer(device, data=np.frombuffer(data + b"\xa5", np.uint8))      # one byte behind the range: never read into the member
     got = buf.gzip_fast(stream, 0, len(data))
-    assert got == want, (name, _first_difference(got, want))
+    assert got == want, (name, first_difference(got, want))
     # the size query runs the same kernels without the gather
     n = C.c_size_t()
     assert gs._capi.load().gs_buffer_gzip_fast(buf._h, stream._h, 0, len(data), None, 0, C.byref(n)) == 0
@@ -73,7 +46,7 @@ def test_unaligned_offsets(gs, device, stream, host_members, offset):
         data, want = host_members[name]
         buf = gs.Buffer(device, data=np.frombuffer(bytes(range(1, offset + 1)) + data + b"\x77\x77", np.uint8))
         got = buf.gzip_fast(stream, offset, len(data))
-        assert got == want, (name, offset, _first_difference(got, want))
+        assert got == want, (name, offset, first_difference(got, want))
         buf.release()
 
 
@@ -98,7 +71,7 @@ def test_forty_one_chunks(gs, device, stream):
     assert gzip.decompress(want) == data
     buf = gs.Buffer(device, data=np.frombuffer(data, np.uint8))
     got = buf.gzip_fast(stream)
-    assert got == want, _first_difference(got, want)
+    assert got == want, first_difference(got, want)
     buf.release()
 
 
@@ -120,23 +93,14 @@ def test_range_and_capacity_errors(gs, device, stream, host_members):
     buf.release()
 
 
-def _selections(n):
-    rng = np.random.default_rng(2000 + n)
-    random30 = rng.random(n) < 0.3
-    return [("none", None, False), ("empty", np.zeros(n, bool), False), ("random30", random30, False), ("inverted", random30, True)]
-
-
 @pytest.mark.parametrize("layout", EXPORTABLE)
 def test_export_round_trip(gs, device, stream, layout):
     pod = gs.GaussianPod(*layout)
     done = 0
     for n in SIZES:
-        buf = gs.GaussiansBuffer.new(device, pod, _scene(n))
-        for name, mask, invert in _selections(n):
-            sel = None
-            if mask is not None:
-                sel = gs.Selection(device, n)
-                sel.upload(stream, mask)
+        buf = gs.GaussiansBuffer.new(device, pod, export_scene(n))
+        for name, mask, invert in deflate_selections(n):
+            sel = selection_from_mask(gs, device, stream, mask)
             keep = n if mask is None else int((~mask if invert else mask).sum())
             for version, degree in ((3, 3), (1, 0)):
                 opt = gs.spz_options(version=version, sh_degree=degree)
@@ -144,7 +108,7 @@ def test_export_round_trip(gs, device, stream, layout):
                 payload = buf.export_spz(stream, sel, invert, opt).payload
                 got = buf.export_spz_file(stream, sel, invert, opt, fast=True)
                 assert gzip.decompress(got) == payload, what
-                assert got == gs.gzip_fast(payload), (what, _first_difference(got, gs.gzip_fast(payload)))
+                assert got == gs.gzip_fast(payload), (what, first_difference(got, gs.gzip_fast(payload)))
                 hdr, back = gs.SpzGaussians.decode(got)
                 assert len(back) == keep == hdr.num_points and hdr.version == version and hdr.sh_degree == degree, what
                 assert back.tobytes() == gs.SpzGaussians(payload).gaussians.tobytes(), what
@@ -162,7 +126,7 @@ def test_export_round_trip(gs, device, stream, layout):
 
 def test_export_errors_are_those_of_the_zlib_export(gs, device, stream):
     lib = gs._capi.load()
-    g = _scene(64)
+    g = export_scene(64)
     out = np.full(1 << 16, 0xee, np.uint8)
     n = C.c_size_t()
     info = gs._capi.ErrorInfo()

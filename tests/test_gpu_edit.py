@@ -9,64 +9,25 @@ import pytest
 
 import edit_np
 import helpers
+import records
+import scenes
+from frames import render_image
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-ALL_LAYOUTS = [(s, c) for s in range(4) for c in range(3)]
-Q = np.array([0.3, -0.5, 0.2, 0.7])
-Q = tuple((Q / np.linalg.norm(Q)).astype(f32))
-POS, SCALE = (0.5, -0.25, 1.5), 1.25
-# a non-trivial colour matrix (column-major 3 x 4): mixes the channels, pushes some results below 0 and above 1
-COLOR = np.array([1.3, 0.1, -0.2, -0.4, 0.9, 0.3, 0.2, -0.1, 1.6, -0.15, 0.05, 0.1], f32)
-OPACITY = (1.7, -0.2)
-
-
-def _scene(n, seed=3):
-    import synth
-    g = synth.scene(n, first=seed)
-    rng = np.random.default_rng(seed)
-    g["color"] = rng.integers(0, 256, (n, 4), dtype=np.uint8)
-    g["sh"] = rng.uniform(-1.2, 1.2, (n, 45)).astype(f32)      # beyond the snorm8 range too
-    g["pos"][5] = np.nan
-    g["pos"][6, 1] = np.inf
-    g["pos"][7] = (-np.inf, 1.0, np.nan)
-    g["sh"][8, 3] = np.nan
-    g["sh"][9, 4] = np.inf
-    g["scale"][10] = (np.inf, 1.0, 0.0)
-    return g
-
-
-def _edit(gs, flags):
-    e = gs.edit(transform=gs.model_transform_pod(pos=POS, rot=Q, scale=(SCALE,) * 3), color=COLOR, opacity=OPACITY)
-    e.flags = flags
-    return e
-
-
-def _want(gs, sh, cov, pods, mask, flags):
-    return edit_np.apply_edit(sh, cov, pods, mask, flags, pos=POS, rot=Q, scale=(SCALE,) * 3, color=COLOR, opacity=OPACITY,
-                              D=gs.sh_rotation_matrices(Q))
-
-
-def _diff(got, want, nb):
-    bad = np.flatnonzero((got.reshape(-1, nb) != want.reshape(-1, nb)).any(axis=1))
-    if len(bad) == 0:
-        return ""
-    k = bad[0]
-    cols = np.flatnonzero(got.reshape(-1, nb)[k] != want.reshape(-1, nb)[k])
-    return "%d records differ; first %d at bytes %s" % (len(bad), k, cols[:12].tolist())
 
 
 # ------------------------------------------------------------------------------------------------
 # 1. byte equality with the restatement
 # ------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("sh,cov", ALL_LAYOUTS)
+@pytest.mark.parametrize("sh,cov", scenes.ALL_LAYOUTS)
 def test_edit_bytes_equal_the_restatement(gs, device, stream, sh, cov):
     n = 5003
     pod = gs.GaussianPod(sh, cov)
     assert pod.size == edit_np.pod_bytes(sh, cov)
-    pods = pod.from_gaussian(_scene(n))
+    pods = pod.from_gaussian(scenes.hostile_scene(n))
     mask = np.random.default_rng(1).random(n) < 0.3
     sel = gs.Selection(device, n)
     sel.upload(stream, mask)
@@ -74,10 +35,10 @@ def test_edit_bytes_equal_the_restatement(gs, device, stream, sh, cov):
     cases = [(T | R | Cf | O, mask), (T, mask), (T | R, mask), (Cf, mask), (O, mask), (T | R | Cf | O, None), (Cf | O, None)]
     for flags, m in cases:
         buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-        buf.edit(stream, sel if m is not None else None, _edit(gs, flags))
+        buf.edit(stream, sel if m is not None else None, records.sample_edit(gs, flags))
         got = buf.download(stream)
-        want = _want(gs, sh, cov, pods, m, flags)
-        assert np.array_equal(got, want), (flags, m is not None, _diff(got, want, pod.size))
+        want = records.edited_pods(gs, sh, cov, pods, m, flags)
+        assert np.array_equal(got, want), (flags, m is not None, records.diff(got, want, pod.size))
         if m is not None:       # outside the selection every byte stays
             assert np.array_equal(got.reshape(n, -1)[~m], np.asarray(pods).reshape(n, -1)[~m])
         changed = (got.reshape(n, -1) != np.asarray(pods).reshape(n, -1)).any(axis=0)
@@ -108,14 +69,14 @@ def test_rotated_sh_on_quantised_layouts(gs, device, stream, sh):
     on the stored bytes in units of the step (|b - 127 clamp(v, -1, 1)| <= 1, exact in float64) so that the decode's own
     division does not enter."""
     n = 4000
-    g = _scene(n)
+    g = scenes.hostile_scene(n)
     g["sh"] = np.random.default_rng(4).uniform(-1, 1, (n, 45)).astype(f32)
     podq, pod32 = gs.GaussianPod(sh, 0), gs.GaussianPod(0, 0)
     pq = podq.from_gaussian(g)
     dec = edit_np.decode_sh(sh, np.asarray(pq).reshape(n, -1)[:, 16:16 + edit_np.SH_BYTES[sh]])
     g["sh"] = dec
     p32 = pod32.from_gaussian(g)
-    e = _edit(gs, gs.EDIT_TRANSFORM | gs.EDIT_ROTATE_SH)
+    e = records.sample_edit(gs, gs.EDIT_TRANSFORM | gs.EDIT_ROTATE_SH)
     out = []
     for pod, p in ((podq, pq), (pod32, p32)):
         buf = gs.GaussiansBuffer.new_with_pods(device, pod, p)
@@ -139,19 +100,6 @@ def test_rotated_sh_on_quantised_layouts(gs, device, stream, sh):
 # 3. frames after an edit
 # ------------------------------------------------------------------------------------------------
 
-def _frame(gs, device, stream, r, buf, gt, mt, cam, W, H, **kw):
-    img = gs.Buffer(device, data=np.full(H * W * 4, f32(np.nan)))
-    fr = r.render(stream, buf, gt, mt, cam, img.device_ptr(), **kw)
-    stream.synchronize()
-    out = img.download(stream, f32).reshape(H, W, 4).copy()
-    img.release()
-    return out, fr
-
-
-def _same(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
 @pytest.mark.parametrize("spatial", [False, True])
 @pytest.mark.parametrize("flags", [15, 12])       # everything; colour + opacity (the mirror keeps its order)
 def test_frames_after_an_edit(gs, ob, device, stream, spatial, flags):
@@ -167,7 +115,7 @@ def test_frames_after_an_edit(gs, ob, device, stream, spatial, flags):
     cam = helpers.copy_camera(ocam, gs.Camera)
     if spatial:
         # the mirror order is observable only where two Gaussians have bit-identical view depths (§3.4a): none here
-        proj, tiles = ob.preprocess(sh, cov, _want(gs, sh, cov, pods, mask, flags), ogt, omt, ocam)
+        proj, tiles = ob.preprocess(sh, cov, records.edited_pods(gs, sh, cov, pods, mask, flags), ogt, omt, ocam)
         depth = proj["depth"][np.asarray(tiles) > 0]
         assert len(depth) > 100 and len(np.unique(depth.view(np.uint32))) == len(depth)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
@@ -176,23 +124,23 @@ def test_frames_after_an_edit(gs, ob, device, stream, spatial, flags):
     sel.upload(stream, mask)
     r1, r2 = gs.Renderer(device), gs.Renderer(device)
     stream2 = device.create_stream()
-    before, _ = _frame(gs, device, stream, r1, buf, gt, mt, cam, W, H)         # r1 has rendered the buffer; the mirror is current
-    buf.edit(stream, sel, _edit(gs, flags))
+    before, _ = render_image(gs, device, stream, r1, buf, gt, mt, cam, W, H)         # r1 has rendered the buffer; the mirror is current
+    buf.edit(stream, sel, records.sample_edit(gs, flags))
     # a second renderer on ANOTHER stream right behind the edit, with no host synchronisation in between
-    after2, _ = _frame(gs, device, stream2, r2, buf, gt, mt, cam, W, H)
-    after1, fr1 = _frame(gs, device, stream, r1, buf, gt, mt, cam, W, H)
+    after2, _ = render_image(gs, device, stream2, r2, buf, gt, mt, cam, W, H)
+    after1, fr1 = render_image(gs, device, stream, r1, buf, gt, mt, cam, W, H)
     edited = buf.download(stream)
-    assert np.array_equal(edited, _want(gs, sh, cov, pods, mask, flags))
+    assert np.array_equal(edited, records.edited_pods(gs, sh, cov, pods, mask, flags))
     fresh = gs.GaussiansBuffer.new_with_pods(device, pod, edited)
     fresh.set_spatial_order(spatial)
     r3 = gs.Renderer(device)
-    want, fr3 = _frame(gs, device, stream, r3, fresh, gt, mt, cam, W, H)
-    assert not _same(before, want), "the edit must change the frame"
-    assert _same(after1, want) and _same(after2, want)
+    want, fr3 = render_image(gs, device, stream, r3, fresh, gt, mt, cam, W, H)
+    assert not helpers.same_bits(before, want), "the edit must change the frame"
+    assert helpers.same_bits(after1, want) and helpers.same_bits(after2, want)
     assert (fr1.visible, fr1.pairs) == (fr3.visible, fr3.pairs)
     assert np.array_equal(buf.download_order(stream), fresh.download_order(stream))
     ref, d, vis, _ = ob.render(sh, cov, edited, ogt, omt, ocam, order=fresh.download_order(stream))
-    assert _same(want, ref) and (fr3.visible, fr3.pairs) == (vis, d)
+    assert helpers.same_bits(want, ref) and (fr3.visible, fr3.pairs) == (vis, d)
     stream2.synchronize(); stream2.close()
     for o in (r1, r2, r3, sel, buf, fresh):
         o.destroy()
@@ -262,7 +210,7 @@ def test_bake_equals_model_transform(gs, ob, device, stream, cov):
     by 3.6e-7 at most; without ROTATE_SH the pair differs by up to 0.64, beyond the allowance on 54 % of the pixels."""
     n, W, H, sh = 4000, 320, 192, 0
     g = _bake_scene(n)
-    q, pos, s = Q, (0.3, -0.2, -0.4), 1.2
+    q, pos, s = records.Q, (0.3, -0.2, -0.4), 1.2
     pod = gs.GaussianPod(sh, cov)
     ogt, oid = ob.gaussian_transform(sh_deg=3), ob.model_transform()
     omt = ob.model_transform(pos=pos, rot=q, scale=(s, s, s))
@@ -282,11 +230,11 @@ def test_bake_equals_model_transform(gs, ob, device, stream, cov):
     # the GPU pair
     r = gs.Renderer(device)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    a, _ = _frame(gs, device, stream, r, buf, gt, mt, cam, W, H)
+    a, _ = render_image(gs, device, stream, r, buf, gt, mt, cam, W, H)
     e = gs.edit(transform=gs.model_transform_pod(pos=pos, rot=q, scale=(s, s, s)))
     assert e.flags == gs.EDIT_TRANSFORM | gs.EDIT_ROTATE_SH
     buf.edit(stream, None, e)
-    b, _ = _frame(gs, device, stream, r, buf, gt, ident, cam, W, H)
+    b, _ = render_image(gs, device, stream, r, buf, gt, ident, cam, W, H)
     diff = np.abs(a - b).max(axis=2)
     over = float((diff > allow).mean())
     print("gpu pair max %.3g, pixels beyond the allowance %.4f %%" % (float(diff.max()), 100 * over))
@@ -294,7 +242,7 @@ def test_bake_equals_model_transform(gs, ob, device, stream, cov):
     # without the SH rotation the view dependence points the wrong way: far beyond the allowance
     buf2 = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
     buf2.edit(stream, None, gs.edit(transform=gs.model_transform_pod(pos=pos, rot=q, scale=(s, s, s)), rotate_sh=False))
-    c, _ = _frame(gs, device, stream, r, buf2, gt, ident, cam, W, H)
+    c, _ = render_image(gs, device, stream, r, buf2, gt, ident, cam, W, H)
     diff2 = np.abs(a - c).max(axis=2)
     print("without ROTATE_SH: max %.3g, pixels beyond the allowance %.2f %%" % (float(diff2.max()), 100 * float((diff2 > allow).mean())))
     assert (diff2 > allow).mean() > 1e-3
@@ -351,7 +299,7 @@ def test_extract_sizes(gs, device, stream, n):
     _check_extract(gs, device, stream, 0, 0, n, n)
 
 
-@pytest.mark.parametrize("sh,cov", ALL_LAYOUTS)
+@pytest.mark.parametrize("sh,cov", scenes.ALL_LAYOUTS)
 def test_extract_all_layouts(gs, device, stream, sh, cov):
     _check_extract(gs, device, stream, sh, cov, 5003, sh * 3 + cov)
 
@@ -371,11 +319,11 @@ def test_delete_equals_hide(gs, device, stream):
     gt, mt = gs.gaussian_transform_pod(sh_deg=3), gs.model_transform_pod()
     cam = gs.camera_look_at((0, 0, 0), (0, 0, -1), (0, 1, 0), float(np.deg2rad(60.0)), W, H)
     r1, r2 = gs.Renderer(device), gs.Renderer(device)
-    hidden, fh = _frame(gs, device, stream, r1, buf, gt, mt, cam, W, H, hide=sel)
+    hidden, fh = render_image(gs, device, stream, r1, buf, gt, mt, cam, W, H, hide=sel)
     kept = buf.extract(stream, sel, invert=True)
     assert not kept.spatial_order() and kept.len() == int((~mask).sum())
-    deleted, fd = _frame(gs, device, stream, r2, kept, gt, mt, cam, W, H)
-    assert _same(hidden, deleted) and (fh.visible, fh.pairs) == (fd.visible, fd.pairs) and fh.visible > 0
+    deleted, fd = render_image(gs, device, stream, r2, kept, gt, mt, cam, W, H)
+    assert helpers.same_bits(hidden, deleted) and (fh.visible, fh.pairs) == (fd.visible, fd.pairs) and fh.visible > 0
     for o in (r1, r2, sel, kept, buf):
         o.destroy()
 
@@ -387,12 +335,12 @@ def test_delete_equals_hide(gs, device, stream):
 def test_argument_errors_leave_the_bytes(gs, device, stream):
     n = 777
     pod = gs.GaussianPod(0, 0)
-    pods = pod.from_gaussian(_scene(n))
+    pods = pod.from_gaussian(scenes.hostile_scene(n))
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
     sel = gs.Selection(device, n)
     sel.fill(stream)
     short = gs.Selection(device, n - 1)
-    good = _edit(gs, 15)
+    good = records.sample_edit(gs, 15)
 
     def variant(**kw):
         e = gs.Edit.from_buffer_copy(bytes(good))
@@ -422,5 +370,5 @@ def test_argument_errors_leave_the_bytes(gs, device, stream):
     # a field that the flags do not use may hold anything
     e = variant(flags=gs.EDIT_OPACITY, pos_0=np.nan, color_0=np.inf, scale_1=7.0)
     buf.edit(stream, sel, e)
-    assert np.array_equal(buf.download(stream), _want(gs, 0, 0, pods, None, gs.EDIT_OPACITY))
+    assert np.array_equal(buf.download(stream), records.edited_pods(gs, 0, 0, pods, None, gs.EDIT_OPACITY))
     short.destroy(); sel.destroy(); buf.destroy()

@@ -4,13 +4,14 @@ byte, at the wave (64), workgroup (128, 256) and 1024-block edges, for every sel
 exported; against tests/golden/export_v1.npz (the oracle's bytes, recorded on glibc 2.35); through a PLY file and back; the
 refused layouts, a short capacity, and the ordering behind an edit on another stream."""
 import ctypes as C
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
 import gpu_child
+from records import first_difference, selection_from_mask
+from scenes import export_scene, export_selections, golden_export
 
 pytestmark = pytest.mark.gpu
 
@@ -20,55 +21,6 @@ EXPORTABLE = [(0, 0), (1, 0), (2, 0)]
 REFUSED = [(s, c) for s in range(4) for c in range(3) if (s, c) not in EXPORTABLE]
 SPZ_CONFIGS = [(v, d, b) for v in (1, 2, 3) for d in (0, 3) for b in (8, 4)]
 INVALID_ARGUMENT = -1
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "golden", name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-_MK = _load("make_golden_export")
-_CACHE = {}
-
-
-def _scene(n):
-    """the scene of tests/golden/make_golden_export.py (hostile records at the wave, workgroup and block edges): once per n"""
-    if n not in _CACHE:
-        g = _MK.scene(n)
-        g.setflags(write=False)
-        _CACHE[n] = g
-    return _CACHE[n]
-
-
-def _selections(n):
-    """(name, mask or None, invert)"""
-    rng = np.random.default_rng(1000 + n)
-    per_wave = np.zeros(n, bool)
-    per_wave[(np.arange(0, n, 64) + rng.integers(0, 64, len(range(0, n, 64)))).clip(max=n - 1)] = True
-    last = np.zeros(n, bool)
-    last[-1] = True
-    random30 = rng.random(n) < 0.3
-    return [("none", None, False), ("empty", np.zeros(n, bool), False), ("full", np.ones(n, bool), False),
-            ("inverted", random30, True), ("one-per-wave", per_wave, False), ("every-second", np.arange(n) % 2 == 0, False),
-            ("random30", random30, False), ("last", last, False)]
-
-
-def _selection(gs, device, stream, mask):
-    if mask is None:
-        return None
-    sel = gs.Selection(device, len(mask))
-    sel.upload(stream, mask)
-    return sel
-
-
-def _first_difference(got, want, rec):
-    got, want = np.frombuffer(got, np.uint8), np.frombuffer(want, np.uint8)
-    if got.size != want.size:
-        return "%d bytes, want %d" % (got.size, want.size)
-    bad = np.flatnonzero(got != want)
-    return "" if len(bad) == 0 else "%d bytes differ; first at byte %d (record %d, byte %d)" % (len(bad), bad[0], bad[0] // rec, bad[0] % rec)
 
 
 def _spz_options(gs, cfg):
@@ -83,15 +35,15 @@ def test_export_ply_equals_the_host_path(gs, device, stream, layout):
     pod = gs.GaussianPod(*layout)
     done = 0
     for n in SIZES:
-        buf = gs.GaussiansBuffer.new(device, pod, _scene(n))
-        for name, mask, invert in _selections(n):
-            sel = _selection(gs, device, stream, mask)
+        buf = gs.GaussiansBuffer.new(device, pod, export_scene(n))
+        for name, mask, invert in export_selections(n):
+            sel = selection_from_mask(gs, device, stream, mask)
             picked = buf.extract(stream, sel, invert)
             want = gs.gaussian_to_ply(picked.download_gaussians(stream))
             got = buf.export_ply(stream, sel, invert)
             keep = np.ones(n, bool) if mask is None else (~mask if invert else mask)
             assert len(got) == len(want) == int(keep.sum()), (n, name)
-            assert np.array_equal(got.pods.view(np.uint32), want.view(np.uint32)), (n, name, _first_difference(got.pods.tobytes(), want.tobytes(), 248))
+            assert np.array_equal(got.pods.view(np.uint32), want.view(np.uint32)), (n, name, first_difference(got.pods.tobytes(), want.tobytes(), 248))
             picked.destroy()
             if sel is not None:
                 sel.destroy()
@@ -103,10 +55,10 @@ def test_export_ply_equals_the_host_path(gs, device, stream, layout):
 def test_export_ply_decodes_the_records_of_the_buffer(gs, device, stream):
     """... and the host path itself starts from the records the caller uploaded: to_ply of the scene, selected with numpy"""
     n = 3000
-    g = _scene(n)
+    g = export_scene(n)
     buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), g)
     mask = np.random.default_rng(5).random(n) < 0.3
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     assert buf.export_ply(stream, sel).pods.tobytes() == gs.gaussian_to_ply(g[mask]).tobytes()
     assert buf.export_ply(stream, sel, invert=True).pods.tobytes() == gs.gaussian_to_ply(g[~mask]).tobytes()
     sel.destroy(); buf.destroy()
@@ -155,17 +107,17 @@ def test_export_ply_across_slice_boundaries():
 def test_export_spz_equals_the_host_encoder(gs, device, stream, layout):
     pod = gs.GaussianPod(*layout)
     for n in SIZES:
-        buf = gs.GaussiansBuffer.new(device, pod, _scene(n))
+        buf = gs.GaussiansBuffer.new(device, pod, export_scene(n))
         src = buf.download_gaussians(stream)
-        for name, mask, invert in _selections(n):
-            sel = _selection(gs, device, stream, mask)
+        for name, mask, invert in export_selections(n):
+            sel = selection_from_mask(gs, device, stream, mask)
             picked = src if mask is None else src[~mask if invert else mask]
             for cfg in SPZ_CONFIGS:
                 opt = _spz_options(gs, cfg)
                 want = gs.SpzGaussians.write_gaussians_decompressed(picked, opt)
                 got = buf.export_spz(stream, sel, invert, opt)
                 assert len(got) == len(picked)
-                assert got.payload == want, (n, name, cfg, _first_difference(got.payload, want, 1))
+                assert got.payload == want, (n, name, cfg, first_difference(got.payload, want, 1))
             if sel is not None:
                 sel.destroy()
         buf.destroy()
@@ -173,10 +125,10 @@ def test_export_spz_equals_the_host_encoder(gs, device, stream, layout):
 
 def test_export_spz_default_options_and_gzip_member(gs, device, stream):
     n = 1025
-    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), _scene(n))
+    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), export_scene(n))
     src = buf.download_gaussians(stream)
     mask = np.arange(n) % 3 != 0
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     assert buf.export_spz(stream, sel).payload == gs.SpzGaussians.write_gaussians_decompressed(src[mask])
     assert buf.write(stream, gs.GaussiansSource.Spz, sel) == gs.SpzGaussians.write_gaussians(src[mask])
     assert buf.write(stream, gs.GaussiansSource.Spz) == gs.Gaussians.from_gaussians_iter(src, gs.GaussiansSource.Spz).write_to()
@@ -189,7 +141,7 @@ def test_export_spz_default_options_and_gzip_member(gs, device, stream):
 
 def test_write_to_file_picks_the_format_by_suffix(gs, device, stream, tmp_path):
     n = 257
-    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(1, 0), _scene(n))
+    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(1, 0), export_scene(n))
     src = buf.download_gaussians(stream)
     buf.write_to_file(str(tmp_path / "a.ply"), stream)
     buf.write_to_file(str(tmp_path / "a.spz"), stream)
@@ -208,7 +160,7 @@ def test_device_export_equals_the_golden_bytes(gs, device, stream, layout):
     g = np.ascontiguousarray(gold["gaussians"]).view(gs.GAUSSIAN_DTYPE).reshape(-1)
     buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(*layout), g)
     assert buf.export_ply(stream).pods.tobytes() == gold["ply"].tobytes()
-    for cfg in _MK.GOLDEN_CONFIGS:
+    for cfg in golden_export().GOLDEN_CONFIGS:
         assert buf.export_spz(stream, options=_spz_options(gs, cfg)).payload == gold["spz_v%d_d%d_b%d" % cfg].tobytes(), cfg
     buf.destroy()
 
@@ -223,7 +175,7 @@ def _round_trip_scene(gs, n):
     below is exact: the quaternions are normalised a few more times, and the few that keep moving between two neighbours
     (16 of 1500) take the quaternion of a record that has settled."""
     rng = np.random.default_rng(23)
-    g = np.array(_MK.scene(n + 2000)[1100:1100 + n])          # a stretch without hostile records
+    g = np.array(golden_export().scene(n + 2000)[1100:1100 + n])          # a stretch without hostile records
     assert np.isfinite(g["scale"]).all() and (g["scale"] > 0).all() and np.isfinite(g["rot"]).all()
     g["color"][:, 3] = rng.integers(0, 256, n)
     g["color"][:4, 3] = (0, 255, 1, 254)
@@ -272,7 +224,7 @@ def test_ply_file_round_trip_of_quaternions_normalised_once(gs, device, stream):
     less than 2^-21 of its value, and an ulp is at least 2^-24 of the value — 8 ulp.  Everything else as above."""
     n = 1500
     pod = gs.GaussianPod(0, 0)
-    g = np.array(_MK.scene(n + 2000)[1100:1100 + n])
+    g = np.array(golden_export().scene(n + 2000)[1100:1100 + n])
     assert np.isfinite(g["rot"]).all()
     buf = gs.GaussiansBuffer.new(device, pod, g)
     before = buf.download(stream).view(np.uint32).reshape(n, 56)
@@ -303,7 +255,7 @@ def test_refused_layouts_return_the_error_of_download_gaussians(gs, device, stre
     lib = gs._capi.load()
     n = 65
     pod = gs.GaussianPod(*layout)
-    buf = gs.GaussiansBuffer.new(device, pod, _scene(n))
+    buf = gs.GaussiansBuffer.new(device, pod, export_scene(n))
     g_out = np.zeros(n, dtype=gs.GAUSSIAN_DTYPE)
     want = _status_and_message(gs, lib.gs_gaussians_buffer_download_gaussians(buf._h, stream._h, g_out.ctypes.data, n))
     assert want[0] == gs.LossyConfigError.code
@@ -326,9 +278,9 @@ def test_refused_layouts_return_the_error_of_download_gaussians(gs, device, stre
 def test_short_capacity_is_an_invalid_argument_and_writes_nothing(gs, device, stream):
     lib = gs._capi.load()
     n = 300
-    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), _scene(n))
+    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), export_scene(n))
     mask = np.arange(n) % 2 == 0
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     k = int(mask.sum())
     out = np.full(n * 248 + 4096, 0xAB, dtype=np.uint8)
     count, size = C.c_uint64(), C.c_size_t()
@@ -367,7 +319,7 @@ def test_empty_buffer_exports_empty_files(gs, device, stream):
 def test_export_is_ordered_behind_an_edit_on_another_stream(gs, device, stream):
     n = 3000
     s1, s2 = stream, device.create_stream()
-    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), _scene(n))
+    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), export_scene(n))
     before = buf.download_gaussians(s1)
     e = gs.edit(transform=gs.model_transform_pod(pos=(0.5, -0.25, 1.5), rot=(0, 0, 0, 1), scale=(1.25,) * 3), opacity=(0.5, 0.1))
     buf.edit(s1, None, e)

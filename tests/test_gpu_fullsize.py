@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 import helpers
+from frames import render_image
+from scenes import upload_synth
 
 pytestmark = pytest.mark.gpu
 
@@ -27,29 +29,6 @@ if os.environ.get("GS3D_RECT_V1") == "1":
 elif os.environ.get("GS3D_TILE_MASKS") == "0":
     for _g in GOLD.values():
         _g["visible"], _g["pairs"] = _g["visible_rect_v3"], _g["pairs_rect_v3"]
-
-
-def _upload(gs, device, stream, g, step=1_000_000):
-    import synth
-    pod = gs.GaussianPod(g["sh"], g["cov"])
-    buf = gs.GaussiansBuffer.new_empty(device, pod, g["n"])
-    h = hashlib.sha256()
-    for first in range(0, g["n"], step):
-        cnt = min(step, g["n"] - first)
-        pods = pod.from_gaussian(synth.scene(cnt, first=first))
-        h.update(pods.tobytes())
-        buf.update_range_with_pod(stream, first, pods)
-    stream.synchronize()
-    return pod, buf, h.hexdigest()
-
-
-def _frame(gs, device, stream, r, buf, gt, mt, cam, band=None):
-    img = gs.Buffer(device, size=cam.height * cam.width * 16)
-    r.render(stream, buf, gt, mt, cam, img.device_ptr(), band=band)
-    stream.synchronize()
-    rgba = img.download(stream, np.float32).reshape(cam.height, cam.width, 4)
-    img.release()
-    return rgba
 
 
 def _check_intermediates(gs, r, g, cam, order):
@@ -103,7 +82,7 @@ def _check_intermediates(gs, r, g, cam, order):
 @pytest.mark.parametrize("name", ["1m", "10m", "50m"])
 def test_fullsize_frame_matches_oracle_hash(gs, device, stream, name):
     g = GOLD[name]
-    pod, buf, scene_hash = _upload(gs, device, stream, g)
+    pod, buf, scene_hash = upload_synth(gs, device, stream, g)
     assert scene_hash == g["scene_sha256"], "synthetic scene generator differs from the golden run (not a renderer issue)"
     spatial = buf.spatial_order()     # off only under GS3D_SPATIAL_ORDER=0
     if spatial:
@@ -113,7 +92,7 @@ def test_fullsize_frame_matches_oracle_hash(gs, device, stream, name):
     cam = helpers.default_camera(gs, g["width"], g["height"])
     gt, mt = gs.gaussian_transform_pod(sh_deg=g["sh_deg"]), gs.model_transform_pod()
     r = gs.Renderer(device)
-    rgba = _frame(gs, device, stream, r, buf, gt, mt, cam)
+    rgba = render_image(gs, device, stream, r, buf, gt, mt, cam, cam.width, cam.height, poison=None)[0]
     st = r.stats()
     assert (st.visible, st.pairs) == (g["visible"], g["pairs"])
     assert np.isfinite(rgba).all()
@@ -123,7 +102,7 @@ def test_fullsize_frame_matches_oracle_hash(gs, device, stream, name):
     if g["n"] <= 10_000_000:   # at 50 M the taps would move 175 M pairs through numpy: hashes, V, D and bands only
         _check_intermediates(gs, r, g, cam, buf.download_order(stream))
     # idempotence: same inputs, same bits (the pipeline has no order-dependent atomics in its results)
-    again = _frame(gs, device, stream, r, buf, gt, mt, cam)
+    again = render_image(gs, device, stream, r, buf, gt, mt, cam, cam.width, cam.height, poison=None)[0]
     assert np.array_equal(again.view(np.uint32), rgba.view(np.uint32))
     # band stitching at full size: 8 tile-row bands (the 8-GPU decomposition) == the full frame
     tiles_y = (g["height"] + 15) // 16
@@ -131,7 +110,7 @@ def test_fullsize_frame_matches_oracle_hash(gs, device, stream, name):
     stitched = np.zeros_like(rgba)
     vis_sum = 0
     for b0, b1 in zip(edges[:-1], edges[1:]):
-        part = _frame(gs, device, stream, r, buf, gt, mt, cam, band=(b0, b1))
+        part = render_image(gs, device, stream, r, buf, gt, mt, cam, cam.width, cam.height, poison=None, band=(b0, b1))[0]
         stitched[b0 * 16:min(b1 * 16, g["height"])] = part[b0 * 16:min(b1 * 16, g["height"])]
         vis_sum += r.stats().pairs
     assert hashlib.sha256(stitched.tobytes()).hexdigest() == g[frame_key]
@@ -144,7 +123,7 @@ def test_fullsize_frame_matches_oracle_hash(gs, device, stream, name):
         assert abs(vis_sum - g["pairs"]) <= 0.01 * g["pairs"], (vis_sum, g["pairs"])
     # the same buffer with the spatial order switched off: plain index order, the oracle's other hash
     buf.set_spatial_order(False)
-    plain = _frame(gs, device, stream, r, buf, gt, mt, cam)
+    plain = render_image(gs, device, stream, r, buf, gt, mt, cam, cam.width, cam.height, poison=None)[0]
     assert np.array_equal(buf.download_order(stream), np.arange(g["n"], dtype=np.uint32))
     assert hashlib.sha256(plain.tobytes()).hexdigest() == g["frame_sha256_index_order"]
     r.destroy()
@@ -153,12 +132,12 @@ def test_fullsize_frame_matches_oracle_hash(gs, device, stream, name):
 
 def test_fullsize_4k_frame_matches_oracle_hash(gs, device, stream):
     g = GOLD["10m-4k"]
-    pod, buf, scene_hash = _upload(gs, device, stream, g)
+    pod, buf, scene_hash = upload_synth(gs, device, stream, g)
     assert scene_hash == g["scene_sha256"]
     cam = helpers.default_camera(gs, g["width"], g["height"])
     gt, mt = gs.gaussian_transform_pod(sh_deg=g["sh_deg"]), gs.model_transform_pod()
     r = gs.Renderer(device)
-    rgba = _frame(gs, device, stream, r, buf, gt, mt, cam)
+    rgba = render_image(gs, device, stream, r, buf, gt, mt, cam, cam.width, cam.height, poison=None)[0]
     st = r.stats()
     assert (st.visible, st.pairs) == (g["visible"], g["pairs"])
     assert hashlib.sha256(rgba.tobytes()).hexdigest() == g["frame_sha256" if buf.spatial_order() else
@@ -200,7 +179,7 @@ def test_sharded_path_single_gpu_4k(gs, device, stream):
     from importlib import import_module
     par = import_module("wgpu_3dgs_core_amd.parallel")
     g = GOLD["10m-4k"]
-    pod, buf, scene_hash = _upload(gs, device, stream, g)
+    pod, buf, scene_hash = upload_synth(gs, device, stream, g)
     assert scene_hash == g["scene_sha256"]
     W, H = g["width"], g["height"]
     cam = helpers.default_camera(gs, W, H)
@@ -242,14 +221,14 @@ def test_sharded_path_single_gpu_4k(gs, device, stream):
 def test_fullsize_background_identity(gs, device, stream):
     """out(bg).rgb = out(0).rgb + (1 - alpha) * bg, alpha independent of bg — at 1 M / 1080p."""
     g = GOLD["1m"]
-    pod, buf, _ = _upload(gs, device, stream, g)
+    pod, buf, _ = upload_synth(gs, device, stream, g)
     gt, mt = gs.gaussian_transform_pod(sh_deg=g["sh_deg"]), gs.model_transform_pod()
     r = gs.Renderer(device)
     cam0 = helpers.default_camera(gs, g["width"], g["height"])
     cam1 = helpers.default_camera(gs, g["width"], g["height"])
     cam1.background[:] = [0.25, 0.5, 1.0]
-    a = _frame(gs, device, stream, r, buf, gt, mt, cam0)
-    b = _frame(gs, device, stream, r, buf, gt, mt, cam1)
+    a = render_image(gs, device, stream, r, buf, gt, mt, cam0, cam0.width, cam0.height, poison=None)[0]
+    b = render_image(gs, device, stream, r, buf, gt, mt, cam1, cam1.width, cam1.height, poison=None)[0]
     assert np.array_equal(a[..., 3].view(np.uint32), b[..., 3].view(np.uint32))
     t = 1.0 - a[..., 3].astype(np.float64)
     exp = a[..., :3].astype(np.float64) + t[..., None] * np.array([0.25, 0.5, 1.0])
@@ -289,7 +268,7 @@ def test_largest_scene_one_gpu(gs, ob, device, stream):
     assert pairs < 0xfffffff0, "pick a smaller scene: pair indices are 32-bit"
     r = gs.Renderer(device)
     t0 = time.perf_counter()
-    rgba = _frame(gs, device, stream, r, buf, gt, mt, cam)      # includes the mirror / spatial-order build
+    rgba = render_image(gs, device, stream, r, buf, gt, mt, cam, cam.width, cam.height, poison=None)[0]      # includes the mirror / spatial-order build
     t_first = time.perf_counter() - t0
     st = r.stats()
     assert (st.visible, st.pairs) == (vis, pairs), (st.visible, vis, st.pairs, pairs)
@@ -309,7 +288,7 @@ def test_largest_scene_one_gpu(gs, ob, device, stream):
     stitched = np.zeros_like(rgba)
     d_sum = 0
     for b0, b1 in ((0, tiles_y // 2), (tiles_y // 2, tiles_y)):
-        part = _frame(gs, device, stream, r, buf, gt, mt, cam, band=(b0, b1))
+        part = render_image(gs, device, stream, r, buf, gt, mt, cam, cam.width, cam.height, poison=None, band=(b0, b1))[0]
         stitched[b0 * 16:min(b1 * 16, H)] = part[b0 * 16:min(b1 * 16, H)]
         d_sum += r.stats().pairs
     assert d_sum == pairs

@@ -4,54 +4,13 @@ test uploaded itself, and every comparison is on bytes (frames: on the bits of t
 import numpy as np
 import pytest
 
-from test_gpu_edit import ALL_LAYOUTS, _edit, _scene
+from records import buffer_rows, np_op, sample_edit, selection_from_mask
+from scenes import ALL_LAYOUTS, FOUR_LAYOUTS, N, history_masks, pod_rows
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-N = 5003          # no multiple of 32, 64 or 1024: four full 1024-blocks and a partial one
 ALL_FLAGS = 15
-# f32 SH + rot-scale, f16 SH + f16 cov, snorm8 + f32 cov, no SH + rot-scale
-FOUR_LAYOUTS = [(0, 0), (1, 2), (2, 1), (3, 0)]
-
-_PODS = {}
-
-
-def _pods(gs, sh, cov, n=N, seed=3):
-    """the records of _scene(n, seed) in one layout, as n rows of bytes; computed once and never written to"""
-    key = (sh, cov, n, seed)
-    if key not in _PODS:
-        pod = gs.GaussianPod(sh, cov)
-        # _scene plants its NaN and inf rows at 5..10: a shorter scene is the tail of an 11-row one, so it keeps some
-        scene = _scene(n, seed) if n >= 11 else _scene(11, seed)[11 - n:]
-        rows = np.asarray(pod.from_gaussian(scene)).reshape(n, pod.size).copy()
-        rows.setflags(write=False)
-        _PODS[key] = rows
-    return _PODS[key]
-
-
-def _masks(n=N):
-    rng = np.random.default_rng(1)
-    last = np.zeros(n, bool)
-    last[n - 1] = True
-    tail = np.zeros(n, bool)
-    tail[4992:n] = True
-    but_block = np.ones(n, bool)
-    but_block[1024:2048] = False
-    first = np.zeros(n, bool)
-    first[0] = True
-    return [("random30", rng.random(n) < 0.3), ("none", np.zeros(n, bool)), ("all", None), ("last", last), ("tail", tail),
-            ("all-but-block-1", but_block), ("first", first)]
-
-
-def _rows(buf, stream):
-    return np.asarray(buf.download(stream)).reshape(buf.len(), buf.pod.size)
-
-
-def _selection(gs, device, stream, mask):
-    sel = gs.Selection(device, len(mask))
-    sel.upload(stream, mask)
-    return sel
 
 
 # ------------------------------------------------------------------------------------------------
@@ -61,21 +20,21 @@ def _selection(gs, device, stream, mask):
 @pytest.mark.parametrize("sh,cov", ALL_LAYOUTS)
 def test_restore_gives_the_bytes_back(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
-    orig = _pods(gs, sh, cov)
-    for name, mask in _masks():
+    orig = pod_rows(gs, sh, cov)
+    for name, mask in history_masks():
         m = np.ones(N, bool) if mask is None else mask
         buf = gs.GaussiansBuffer.new_with_pods(device, pod, orig)
-        sel = _selection(gs, device, stream, mask) if mask is not None else None
+        sel = selection_from_mask(gs, device, stream, mask)
         snap = buf.snapshot(stream, sel)
         assert (snap.len, snap.count) == (N, int(m.sum())), name
-        buf.edit(stream, sel, _edit(gs, ALL_FLAGS))
-        edited = _rows(buf, stream)
+        buf.edit(stream, sel, sample_edit(gs, ALL_FLAGS))
+        edited = buffer_rows(buf, stream)
         changed = (edited != orig).any(axis=1)
         assert changed.any() == m.any() and not changed[~m].any(), name
         if m.any():
             assert changed[m].mean() > 0.9, name          # (a NaN row may re-encode to itself)
         buf.restore(stream, snap)
-        got = _rows(buf, stream)
+        got = buffer_rows(buf, stream)
         assert np.array_equal(got, orig), (name, int((got != orig).any(axis=1).sum()))
         snap.destroy()
         if sel is not None:
@@ -90,20 +49,20 @@ def test_restore_gives_the_bytes_back(gs, device, stream, sh, cov):
 def test_snapshot_is_independent_of_the_selection(gs, device, stream):
     sh, cov = 0, 0
     pod = gs.GaussianPod(sh, cov)
-    orig = _pods(gs, sh, cov)
+    orig = pod_rows(gs, sh, cov)
     mask = np.random.default_rng(5).random(N) < 0.3
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, orig)
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     snap = buf.snapshot(stream, sel)
     count = int(mask.sum())
     assert snap.count == count and snap.len == N
     print("snapshot of %d of %d records: %d bytes, records alone %d" % (count, N, snap.nbytes, count * pod.size))
     assert count * pod.size <= snap.nbytes <= count * pod.size + 8 * ((N + 31) // 32) + 4096
-    buf.edit(stream, sel, _edit(gs, ALL_FLAGS))
+    buf.edit(stream, sel, sample_edit(gs, ALL_FLAGS))
     sel.clear(stream)                       # the snapshot has its own mask
     assert sel.count(stream) == 0
     buf.restore(stream, snap)
-    assert np.array_equal(_rows(buf, stream), orig)
+    assert np.array_equal(buffer_rows(buf, stream), orig)
     # the mask comes back, alone and folded into another selection
     snap.selection(stream, sel, gs.SEL_SET)
     assert np.array_equal(sel.download(stream), mask)
@@ -126,7 +85,7 @@ def test_snapshot_is_independent_of_the_selection(gs, device, stream):
     assert (empty.len, empty.count) == (N, 0) and empty.nbytes <= 8 * ((N + 31) // 32) + 4096
     buf.restore(stream, empty)
     buf.restore(stream, empty, exchange=True)
-    assert np.array_equal(_rows(buf, stream), orig)
+    assert np.array_equal(buffer_rows(buf, stream), orig)
     nothing = gs.GaussiansBuffer.new_empty(device, pod, 0)
     zero = nothing.snapshot(stream)
     assert (zero.len, zero.count) == (0, 0)
@@ -144,23 +103,23 @@ def test_snapshot_is_independent_of_the_selection(gs, device, stream):
 @pytest.mark.parametrize("sh,cov", FOUR_LAYOUTS)
 def test_exchange_is_undo_then_redo(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
-    O = _pods(gs, sh, cov)
+    O = pod_rows(gs, sh, cov)
     mask = np.random.default_rng(2).random(N) < 0.3
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, O)
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     snap = buf.snapshot(stream, sel)
-    buf.edit(stream, sel, _edit(gs, ALL_FLAGS))
-    E = _rows(buf, stream)
+    buf.edit(stream, sel, sample_edit(gs, ALL_FLAGS))
+    E = buffer_rows(buf, stream)
     assert (E != O).any(axis=1)[mask].mean() > 0.9 and np.array_equal(E[~mask], O[~mask])
     for step, want in enumerate([O, E, O]):
         buf.restore(stream, snap, exchange=True)
-        got = _rows(buf, stream)
+        got = buffer_rows(buf, stream)
         assert np.array_equal(got[~mask], O[~mask]), step
         assert np.array_equal(got, want), step
     # the snapshot now holds E: a plain restore pastes it and leaves the snapshot alone
     buf.restore(stream, snap)
     buf.restore(stream, snap)
-    assert np.array_equal(_rows(buf, stream), E)
+    assert np.array_equal(buffer_rows(buf, stream), E)
     for o in (snap, sel, buf):
         o.destroy()
 
@@ -172,28 +131,28 @@ def test_exchange_is_undo_then_redo(gs, device, stream, sh, cov):
 def test_restore_into_another_buffer(gs, device, stream):
     sh, cov = 1, 1
     pod = gs.GaussianPod(sh, cov)
-    A, B = _pods(gs, sh, cov), _pods(gs, sh, cov, seed=8)
+    A, B = pod_rows(gs, sh, cov), pod_rows(gs, sh, cov, seed=8)
     assert (A != B).any(axis=1).mean() > 0.9
     mask = np.random.default_rng(3).random(N) < 0.3
     a = gs.GaussiansBuffer.new_with_pods(device, pod, A)
     b = gs.GaussiansBuffer.new_with_pods(device, pod, B)
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     snap = a.snapshot(stream, sel)
     b.restore(stream, snap)
-    assert np.array_equal(_rows(b, stream), np.where(mask[:, None], A, B))
-    assert np.array_equal(_rows(a, stream), A)
+    assert np.array_equal(buffer_rows(b, stream), np.where(mask[:, None], A, B))
+    assert np.array_equal(buffer_rows(a, stream), A)
     # another length, another layout: refused, nothing written
     b.update_with_pod(stream, B)
-    longer = gs.GaussiansBuffer.new_with_pods(device, pod, _pods(gs, sh, cov, n=N + 1, seed=8))
+    longer = gs.GaussiansBuffer.new_with_pods(device, pod, pod_rows(gs, sh, cov, n=N + 1, seed=8))
     other_pod = gs.GaussianPod(sh, 2)
-    other = gs.GaussiansBuffer.new_with_pods(device, other_pod, _pods(gs, sh, 2, seed=8))
+    other = gs.GaussiansBuffer.new_with_pods(device, other_pod, pod_rows(gs, sh, 2, seed=8))
     for target in (longer, other):
-        before = _rows(target, stream)
+        before = buffer_rows(target, stream)
         for exchange in (False, True):
             with pytest.raises(gs.InvalidArgumentError):
                 target.restore(stream, snap, exchange=exchange)
-        assert np.array_equal(_rows(target, stream), before)
-    assert np.array_equal(_rows(b, stream), B)
+        assert np.array_equal(buffer_rows(target, stream), before)
+    assert np.array_equal(buffer_rows(b, stream), B)
     for o in (snap, sel, other, longer, b, a):
         o.destroy()
 
@@ -236,11 +195,11 @@ def test_frames_after_a_restore(gs, device, stream, sh, cov, aux):
     pods = np.asarray(pod.from_gaussian(synth.scene(n, first=21)))
     mask = np.random.default_rng(2).random(n) < 0.3
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    sel = _selection(gs, device, stream, mask)
+    sel = selection_from_mask(gs, device, stream, mask)
     r, r2 = gs.Renderer(device), gs.Renderer(device)
     A = _frame(gs, device, stream, r, buf, aux)
     snap = buf.snapshot(stream, sel)
-    buf.edit(stream, sel, _edit(gs, gs.EDIT_TRANSFORM | gs.EDIT_ROTATE_SH))
+    buf.edit(stream, sel, sample_edit(gs, gs.EDIT_TRANSFORM | gs.EDIT_ROTATE_SH))
     B = _frame(gs, device, stream, r, buf, aux)
     buf.restore(stream, snap)
     C = _frame(gs, device, stream, r, buf, aux)
@@ -262,26 +221,26 @@ def test_frames_after_a_restore(gs, device, stream, sh, cov, aux):
 def test_restore_and_snapshot_are_ordered_behind_an_edit_on_another_stream(gs, device, stream):
     sh, cov = 0, 0
     pod = gs.GaussianPod(sh, cov)
-    orig = _pods(gs, sh, cov)
+    orig = pod_rows(gs, sh, cov)
     mask = np.random.default_rng(4).random(N) < 0.3
     s1, s2 = stream, device.create_stream()
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, orig)
-    sel = _selection(gs, device, s1, mask)
+    sel = selection_from_mask(gs, device, s1, mask)
     s1.synchronize()
     snap = buf.snapshot(s1, sel)
     # edit on stream 1, restore on stream 2, no host synchronisation in between
-    buf.edit(s1, sel, _edit(gs, ALL_FLAGS))
+    buf.edit(s1, sel, sample_edit(gs, ALL_FLAGS))
     buf.restore(s2, snap)
-    assert np.array_equal(_rows(buf, s2), orig)
+    assert np.array_equal(buffer_rows(buf, s2), orig)
     # a snapshot on stream 2 right behind an edit on stream 1 holds the edited records
-    buf.edit(s1, sel, _edit(gs, ALL_FLAGS))
+    buf.edit(s1, sel, sample_edit(gs, ALL_FLAGS))
     late = buf.snapshot(s2, sel)
     s1.synchronize()
-    edited = _rows(buf, s1)
+    edited = buffer_rows(buf, s1)
     assert (edited != orig).any(axis=1)[mask].mean() > 0.9
     fresh = gs.GaussiansBuffer.new_with_pods(device, pod, orig)
     fresh.restore(s2, late)
-    assert np.array_equal(_rows(fresh, s2), edited)
+    assert np.array_equal(buffer_rows(fresh, s2), edited)
     s2.synchronize()
     for o in (late, snap, sel, fresh, buf):
         o.destroy()
@@ -296,27 +255,27 @@ def test_restore_and_snapshot_are_ordered_behind_an_edit_on_another_stream(gs, d
 def test_concat(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
     lens = [N, 0, 1, 2049]
-    rows = [_pods(gs, sh, cov, n=n, seed=10 + k) if n else np.zeros((0, pod.size), np.uint8) for k, n in enumerate(lens)]
+    rows = [pod_rows(gs, sh, cov, n=n, seed=10 + k) if n else np.zeros((0, pod.size), np.uint8) for k, n in enumerate(lens)]
     bufs = [gs.GaussiansBuffer.new_with_pods(device, pod, r) for r in rows]
     rng = np.random.default_rng(12)
     # sources 0, 1, 2, 3 and source 0 once more: all, all (of nothing), all by a filled selection, 50 %, 30 %
     order = [0, 1, 2, 3, 0]
     masks = [None, None, np.ones(1, bool), rng.random(2049) < 0.5, rng.random(N) < 0.3]
-    sels = [_selection(gs, device, stream, m) if m is not None else None for m in masks]
+    sels = [selection_from_mask(gs, device, stream, m) for m in masks]
     out, counts = gs.GaussiansBuffer.concat(stream, [bufs[k] for k in order], sels)
     parts = [rows[k] if m is None else rows[k][m] for k, m in zip(order, masks)]
     assert counts == [len(p) for p in parts] and counts[1] == 0
     assert out.len() == sum(counts) and out.pod == pod
-    got = _rows(out, stream)
+    got = buffer_rows(out, stream)
     want = np.concatenate(parts)
     assert np.array_equal(got, want), int((got != want).any(axis=1).sum())
     for k, b in enumerate(bufs):
-        assert np.array_equal(_rows(b, stream), rows[k]), "the sources are untouched"
+        assert np.array_equal(buffer_rows(b, stream), rows[k]), "the sources are untouched"
     # selections=None: everything of every source; a single source is a copy
     every, c2 = gs.GaussiansBuffer.concat(stream, bufs)
-    assert c2 == lens and np.array_equal(_rows(every, stream), np.concatenate(rows))
+    assert c2 == lens and np.array_equal(buffer_rows(every, stream), np.concatenate(rows))
     one, c1 = gs.GaussiansBuffer.concat(stream, [bufs[3]], [sels[3]])
-    assert c1 == [int(masks[3].sum())] and np.array_equal(_rows(one, stream), rows[3][masks[3]])
+    assert c1 == [int(masks[3].sum())] and np.array_equal(buffer_rows(one, stream), rows[3][masks[3]])
     for o in [out, every, one] + [s for s in sels if s is not None] + bufs:
         o.destroy()
 
@@ -324,8 +283,8 @@ def test_concat(gs, device, stream, sh, cov):
 def test_concat_of_nothing_and_errors(gs, device, stream):
     sh, cov = 0, 0
     pod = gs.GaussianPod(sh, cov)
-    a = gs.GaussiansBuffer.new_with_pods(device, pod, _pods(gs, sh, cov))
-    b = gs.GaussiansBuffer.new_with_pods(device, pod, _pods(gs, sh, cov, n=2049, seed=13))
+    a = gs.GaussiansBuffer.new_with_pods(device, pod, pod_rows(gs, sh, cov))
+    b = gs.GaussiansBuffer.new_with_pods(device, pod, pod_rows(gs, sh, cov, n=2049, seed=13))
     none_a, none_b = gs.Selection(device, N), gs.Selection(device, 2049)
     out, counts = gs.GaussiansBuffer.concat(stream, [a, b], [none_a, none_b])
     assert counts == [0, 0] and out.len() == 0 and out.is_empty() and out.download(stream).size == 0
@@ -333,7 +292,7 @@ def test_concat_of_nothing_and_errors(gs, device, stream):
     frame = _frame(gs, device, stream, r, out)[0].view(f32).reshape(H, W, 4)
     assert np.array_equal(frame, np.zeros_like(frame))           # the camera's background, alpha 0
     # errors: two layouts, no source, a selection of another length; nothing is created
-    c = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(1, 0), _pods(gs, 1, 0))
+    c = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(1, 0), pod_rows(gs, 1, 0))
     with pytest.raises(gs.InvalidArgumentError):
         gs.GaussiansBuffer.concat(stream, [a, c])
     with pytest.raises(gs.InvalidArgumentError):
@@ -342,7 +301,7 @@ def test_concat_of_nothing_and_errors(gs, device, stream):
         gs.GaussiansBuffer.concat(stream, [a, b], [none_b, none_b])
     with pytest.raises(gs.InvalidArgumentError):
         gs.GaussiansBuffer.concat(stream, [a] * 65)
-    assert np.array_equal(_rows(a, stream), _pods(gs, sh, cov))
+    assert np.array_equal(buffer_rows(a, stream), pod_rows(gs, sh, cov))
     for o in (r, out, none_a, none_b, c, b, a):
         o.destroy()
 
@@ -371,10 +330,6 @@ def test_frame_of_a_concat(gs, device, stream):
 # 8. select_range
 # ------------------------------------------------------------------------------------------------
 
-def _apply(op, d, s):
-    return [s, d | s, d & s, d & ~s, d ^ s][op]
-
-
 def test_select_range(gs, device, stream):
     n = N
     start_mask = np.random.default_rng(7).random(n) < 0.5
@@ -388,8 +343,8 @@ def test_select_range(gs, device, stream):
             rng_mask[start:start + count] = True
             words = sel.download_words(stream)
             assert (int(words[-1]) >> (n & 31)) == 0, (op, start, count)
-            assert np.array_equal(sel.download(stream), _apply(op, start_mask, rng_mask)), (op, start, count)
-            assert sel.count(stream) == int(_apply(op, start_mask, rng_mask).sum())
+            assert np.array_equal(sel.download(stream), np_op(start_mask, rng_mask, op)), (op, start, count)
+            assert sel.count(stream) == int(np_op(start_mask, rng_mask, op).sum())
     # out of range: refused, the selection stays
     sel.upload(stream, start_mask)
     for start, count in [(n, 1), (1, n), (2 ** 64 - 1, 2), (0, n + 1)]:

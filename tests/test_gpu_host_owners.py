@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_export import _scene, _selection
+from records import selection_from_mask
+from scenes import export_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -26,8 +27,8 @@ def case(gs, device):
     """the buffer, its selection and what every export of the selected records must give: computed once, read-only"""
     st = device.create_stream()
     mask = np.arange(N) % 3 == 0
-    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), _scene(N))
-    sel = _selection(gs, device, st, mask)
+    buf = gs.GaussiansBuffer.new(device, gs.GaussianPod(0, 0), export_scene(N))
+    sel = selection_from_mask(gs, device, st, mask)
     picked = buf.download_gaussians(st)[mask]
     ply = gs.gaussian_to_ply(picked)
     payload = gs.SpzGaussians.write_gaussians_decompressed(picked)
@@ -88,11 +89,11 @@ def test_restore_of_another_layout_then_one_that_fits(gs, device, stream, case):
     lib = gs._capi.load()
     _, sel, mask, _ = case
     pod, other_pod = gs.GaussianPod(0, 0), gs.GaussianPod(0, 2)
-    A = np.asarray(pod.from_gaussian(_scene(N))).reshape(N, pod.size)
+    A = np.asarray(pod.from_gaussian(export_scene(N))).reshape(N, pod.size)
     B = A[::-1].copy()
     a = gs.GaussiansBuffer.new_with_pods(device, pod, A)
     b = gs.GaussiansBuffer.new_with_pods(device, pod, B)
-    other = gs.GaussiansBuffer.new(device, other_pod, _scene(N))
+    other = gs.GaussiansBuffer.new(device, other_pod, export_scene(N))
     before = other.download(stream).copy()
     snap = C.c_void_p()
     assert lib.gs_gaussians_buffer_snapshot(a._h, stream._h, sel._h, C.byref(snap)) == 0 and lib.gs_snapshot_count(snap) == int(mask.sum())
@@ -115,7 +116,7 @@ def test_empty_selection_then_a_selection(gs, device, stream, case, dst):
     buf, sel, mask, _ = case
     spod, dpod = gs.GaussianPod(0, 0), gs.GaussianPod(*dst)
     rows = np.asarray(buf.download(stream)).reshape(N, spod.size)
-    empty = _selection(gs, device, stream, np.zeros(N, bool))
+    empty = selection_from_mask(gs, device, stream, np.zeros(N, bool))
 
     def create(selection):
         h, count = C.c_void_p(), C.c_uint64(77)

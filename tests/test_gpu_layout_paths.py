@@ -8,7 +8,7 @@ bounds recomputed after a partial update — and every frame is compared with th
 tiles touched, the projected records of the visible Gaussians byte for byte, the sorted keys and indices, the tile ranges
 and the image bit for bit.
 
-The scene is the renderer walk's buffer P (tests/test_gpu_renderer_walk.py) with the layout swapped: 20 000 Gaussians in
+The scene is the renderer walk's buffer P (tests/walk_kinds.py) with the layout swapped: 20 000 Gaussians in
 spatial order, 20 mirror blocks, a partial last block of 544, an image of 7 x 5 tiles with partial tiles on both edges and
 the walk's corner view, which culls 18 of the 20 blocks.  The figures the paths depend on are the oracle's and are asserted
 below without a GPU, for all 12 layouts.
@@ -33,7 +33,8 @@ for _p in (ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")):
 
 import gpu_child  # noqa: E402
 import helpers  # noqa: E402
-import test_gpu_renderer_walk as walk  # noqa: E402
+import walk_kinds as walk  # noqa: E402
+from frames import Scene  # noqa: E402
 from helpers import POISON, band_rows, bits  # noqa: E402
 
 gpu = pytest.mark.gpu
@@ -163,7 +164,6 @@ def frame_transforms(ob, sh, f):
 def oracle_preprocess(ob, sh, cov, f):
     """(proj, tiles) of a frame: a selection frame through its twin records (hidden: opacity byte 0) and the tint
     recolouring, as tests/test_gpu_selection.py and the walk build them"""
-    from test_gpu_selection import Scene
     sc = scene(ob)
     pods = layout_pods(ob, sh, cov, f["moved"])
     if f["sel"]:
@@ -171,7 +171,7 @@ def oracle_preprocess(ob, sh, cov, f):
     ogt, omt, ocam = frame_transforms(ob, sh, f)
     proj, tiles = ob.preprocess(sh, cov, pods, ogt, omt, ocam, band=f["band"])
     if f["sel"]:
-        walk._recolour(proj, sc["tinted"])
+        walk.recolour(proj, sc["tinted"])
     return proj, tiles, (ogt, omt, ocam)
 
 

@@ -8,7 +8,7 @@ import pytest
 
 import gpu_child
 import helpers
-from test_gpu_render import _compare_frame, _mirror_order, _oracle_frame
+from frames import compare_frame, mirror_order, oracle_stages
 
 pytestmark = pytest.mark.gpu
 
@@ -39,8 +39,8 @@ def test_depth_sort_modes_match_the_oracle(gs, ob, device, stream, depth, msd):
     g = _scene(60000, depth)
     g["scale"] *= 0.5          # keeps the pair count of the walls moderate
     info = []
-    st = _compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1280, 720, gt_kw=dict(sh_deg=0),
-                        sort_mode=(msd, 0), info=info)
+    st = compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1280, 720, gt_kw=dict(sh_deg=0),
+                       sort_mode=(msd, 0), info=info)
     si = info[0]
     assert si.depth_msd == msd and si.bucket_capacity >= 16384
     if depth == "spread":
@@ -72,8 +72,8 @@ def test_bucket_sizes_across_the_register_path_variants(gs, ob, device, stream):
     g["pos"][:, :2] *= (z[perm, None] / 14.0)
     g["scale"] *= 0.2
     info = []
-    _compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1280, 720, gt_kw=dict(sh_deg=0),
-                   sort_mode=(1, 0), info=info)
+    compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1280, 720, gt_kw=dict(sh_deg=0),
+                  sort_mode=(1, 0), info=info)
     assert info[0].depth_msd == 1 and info[0].bucket_capacity < info[0].depth_bucket_max <= 40000
 
 
@@ -100,7 +100,7 @@ def test_renderer_chooses_from_the_reported_buckets(gs, ob, device, stream):
             r.render(stream, buf, gt, mt, cam, img.device_ptr())
             seq.append(r.sort_info().depth_msd)
         rgba = img.download(stream, np.float32).reshape(cam.height, cam.width, 4)
-        o_rgba = _oracle_frame(ob, pod.sh, pod.cov, pods, ogt, omt, ocam, order=_mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))[-1]
+        o_rgba = oracle_stages(ob, pod.sh, pod.cov, pods, ogt, omt, ocam, order=mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))[-1]
         assert np.array_equal(rgba.view(np.uint32), o_rgba.view(np.uint32)), phase
         modes.setdefault(phase, []).append(seq)
         buf.destroy()
@@ -124,8 +124,8 @@ def test_tile_sort_modes_match_the_oracle(gs, ob, device, stream, size, expect, 
     g = synth.scene(20000, first=808)
     g["scale"] *= 2.0
     info = []
-    st = _compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, size[0], size[1], gt_kw=dict(sh_deg=0),
-                        sort_mode=(-1, tile_msd), info=info)
+    st = compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, size[0], size[1], gt_kw=dict(sh_deg=0),
+                       sort_mode=(-1, tile_msd), info=info)
     assert info[0].tile_msd == (tile_msd and expect)
     if info[0].tile_msd:
         assert 0 < info[0].tile_bucket_max <= st.pairs
@@ -139,8 +139,8 @@ def test_tile_buckets_beyond_the_register_path(gs, ob, device, stream):
     g["pos"][:, 0] *= 0.03
     g["pos"][:, 1] *= 0.03
     info = []
-    st = _compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1920, 1080, gt_kw=dict(sh_deg=0),
-                        sort_mode=(-1, 1), info=info)
+    st = compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1920, 1080, gt_kw=dict(sh_deg=0),
+                       sort_mode=(-1, 1), info=info)
     assert info[0].tile_msd == 1 and info[0].tile_bucket_max > info[0].bucket_capacity, (info[0].tile_bucket_max, st.pairs)
 
 
@@ -162,8 +162,8 @@ def test_renderer_leaves_the_msd_tile_sort_when_buckets_overflow(gs, ob, device,
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
     img = gs.Buffer(device, size=cam.height * cam.width * 16)
     r = gs.Renderer(device)
-    o_rgba = _oracle_frame(ob, pod.sh, pod.cov, pods, ob.gaussian_transform(sh_deg=0), ob.model_transform(),
-                           helpers.copy_camera(cam, ob.Camera), order=_mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))[-1]
+    o_rgba = oracle_stages(ob, pod.sh, pod.cov, pods, ob.gaussian_transform(sh_deg=0), ob.model_transform(),
+                                 helpers.copy_camera(cam, ob.Camera), order=mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))[-1]
     seq = []
     for i in range(6):
         r.render(stream, buf, gt, mt, cam, img.device_ptr())

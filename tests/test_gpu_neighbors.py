@@ -8,23 +8,18 @@ import pytest
 
 import neighbors_np
 import stats_np
-from test_gpu_edit import ALL_LAYOUTS, _edit, _want
-from test_gpu_history import FOUR_LAYOUTS, N, _masks, _pods, _rows, _selection
+from records import SELECT_OPS, buffer_rows, edited_pods, np_op, sample_edit, selection_from_mask
+from scenes import ALL_LAYOUTS, FOUR_LAYOUTS, N, history_masks, pod_rows
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-OPS = ["set", "or", "and", "andnot", "xor"]
 UMAX = 0xFFFFFFFF
 # rotation + translation + non-uniform scale
 Q = np.array([0.3, -0.5, 0.2, 0.7])
 MT = dict(pos=(0.5, -0.25, 1.5), rot=tuple((Q / np.linalg.norm(Q)).astype(f32)), scale=(1.25, 0.75, 2.0))
 
 _REF = {}
-
-
-def _np_op(d, s, op):
-    return {"set": s, "or": d | s, "and": d & s, "andnot": d & ~s, "xor": d ^ s}[op]
 
 
 def _kth_distance(pw, k):
@@ -41,7 +36,7 @@ def _scene_ref(gs):
     """pw of the N-scene under MT, three radii (median count 0, about 8, more than half of n) and the restatement's counts
     for each; computed once, never written to"""
     if not _REF:
-        pw = neighbors_np.positions(_pods(gs, 3, 0), **MT)
+        pw = neighbors_np.positions(pod_rows(gs, 3, 0), **MT)
         radii = [0.5 * _kth_distance(pw, 1), _kth_distance(pw, 8), _kth_distance(pw, (6 * N) // 10)]
         counts = [neighbors_np.counts(pw, r) for r in radii]
         med = [float(np.median(c[neighbors_np.points(pw)])) for c in counts]
@@ -76,7 +71,7 @@ def _buffer_at(gs, device, positions):
 @pytest.mark.parametrize("sh,cov", ALL_LAYOUTS)
 def test_counts_equal_the_restatement(gs, device, stream, sh, cov):
     ref = _scene_ref(gs)
-    rows = _pods(gs, sh, cov)
+    rows = pod_rows(gs, sh, cov)
     assert np.array_equal(neighbors_np.positions(rows, **MT).view(np.uint32), ref["pw"].view(np.uint32))
     buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), rows)
     mt = gs.model_transform_pod(**MT)
@@ -86,7 +81,7 @@ def test_counts_equal_the_restatement(gs, device, stream, sh, cov):
             got = _plane(buf, stream, r, cap, None, mt)
             assert got.dtype == np.uint32 and np.array_equal(got, neighbors_np.capped(want, cap)), (r, cap)
     assert not got[5:8].any()                     # the planted NaN / inf rows
-    assert np.array_equal(_rows(buf, stream), rows)
+    assert np.array_equal(buffer_rows(buf, stream), rows)
     buf.destroy()
 
 
@@ -98,7 +93,7 @@ def test_counts_equal_the_restatement(gs, device, stream, sh, cov):
 def test_small_buffers(gs, device, stream, n):
     sh, cov = 1, 2
     pod = gs.GaussianPod(sh, cov)
-    rows = _pods(gs, sh, cov, n) if n else np.zeros((0, pod.size), np.uint8)
+    rows = pod_rows(gs, sh, cov, n) if n else np.zeros((0, pod.size), np.uint8)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, rows)
     pw = neighbors_np.positions(rows) if n else np.zeros((0, 3), f32)
     r = 2.0 * _kth_distance(pw, 1) if n > 12 else 1.0
@@ -158,7 +153,7 @@ def test_lattice_of_spacing_r(gs, device, stream):
 def test_far_outlier(gs, device, stream):
     ref = _scene_ref(gs)
     sh, cov = 3, 0
-    rows = _pods(gs, sh, cov)
+    rows = pod_rows(gs, sh, cov)
     far = rows[11:12].copy()
     far[0, :12] = np.array([1e6, 1e6, 1e6], f32).view(np.uint8)
     mt = gs.model_transform_pod(**MT)
@@ -206,12 +201,12 @@ def test_duplicates(gs, device, stream):
 def test_non_points(gs, device, stream):
     ref = _scene_ref(gs)
     sh, cov = 0, 0
-    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), pod_rows(gs, sh, cov))
     mt = gs.model_transform_pod(**MT)
     r = ref["radii"][1]
     out = gs.Selection(device, N)
-    for name, mask in _masks():
-        among = _selection(gs, device, stream, mask) if mask is not None else None
+    for name, mask in history_masks():
+        among = selection_from_mask(gs, device, stream, mask)
         pt = neighbors_np.points(ref["pw"], mask)
         want = neighbors_np.counts(ref["pw"], r, mask)
         got = _plane(buf, stream, r, UMAX, among, mt)
@@ -223,7 +218,7 @@ def test_non_points(gs, device, stream):
         if among is not None:
             among.destroy()
     # nobody's neighbour: the counts among a subset are those of the subset alone
-    mask = _masks()[0][1]
+    mask = history_masks()[0][1]
     sub = ref["pw"][mask]
     assert np.array_equal(neighbors_np.counts(ref["pw"], r, mask)[mask], neighbors_np.counts(sub, r))
     out.destroy(); buf.destroy()
@@ -236,27 +231,27 @@ def test_non_points(gs, device, stream):
 def test_select_ops(gs, device, stream):
     ref = _scene_ref(gs)
     sh, cov = 2, 1
-    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), pod_rows(gs, sh, cov))
     mt = gs.model_transform_pod(**MT)
     r, c = ref["radii"][1], ref["counts"][1]
     pt = neighbors_np.points(ref["pw"])
     prior = np.random.default_rng(7).random(N) < 0.5
     sel = gs.Selection(device, N)
-    for op in OPS:
+    for op in SELECT_OPS:
         for lo, hi in ((0, 3), (4, 12), (9, UMAX), (0, UMAX), (0, 0), (5, 4), (UMAX, UMAX)):
             sel.upload(stream, prior)
             sel.select_neighbors(stream, buf, r, lo, hi, None, mt, op)
-            want = _np_op(prior, neighbors_np.in_count_range(c, pt, lo, hi), op)
+            want = np_op(prior, neighbors_np.in_count_range(c, pt, lo, hi), op)
             assert np.array_equal(sel.download_words(stream), stats_np.pack_bits(want)), (op, lo, hi)
     assert 0 < neighbors_np.in_count_range(c, pt, 0, 3).sum() < N and neighbors_np.in_count_range(c, pt, 9, UMAX).any()
     sel.destroy(); buf.destroy()
 
 
-@pytest.mark.parametrize("op", OPS)
+@pytest.mark.parametrize("op", SELECT_OPS)
 def test_select_keeps_the_tail_clear(gs, device, stream, op):
     n = 65
     sh, cov = 0, 0
-    rows = _pods(gs, sh, cov, n)
+    rows = pod_rows(gs, sh, cov, n)
     buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), rows)
     pw = neighbors_np.positions(rows)
     r = 2.0 * _kth_distance(pw, 1)
@@ -266,13 +261,13 @@ def test_select_keeps_the_tail_clear(gs, device, stream, op):
     sel.select_neighbors(stream, buf, r, 0, UMAX, op=op)
     words = sel.download_words(stream)
     assert len(words) == 3 and words[2] >> 1 == 0
-    assert np.array_equal(words, stats_np.pack_bits(_np_op(np.ones(n, bool), pt, op)))
+    assert np.array_equal(words, stats_np.pack_bits(np_op(np.ones(n, bool), pt, op)))
     sel.fill(stream)
     sel.select_neighbors(stream, buf, r, 1, 0, op=op)                   # min_count > max_count: T is empty
-    assert np.array_equal(sel.download_words(stream), stats_np.pack_bits(_np_op(np.ones(n, bool), np.zeros(n, bool), op)))
+    assert np.array_equal(sel.download_words(stream), stats_np.pack_bits(np_op(np.ones(n, bool), np.zeros(n, bool), op)))
     sel.clear(stream)
     sel.select_neighbors(stream, buf, r, 1, UMAX, op=op)
-    assert np.array_equal(sel.download_words(stream), stats_np.pack_bits(_np_op(np.zeros(n, bool), pt & (c >= 1), op)))
+    assert np.array_equal(sel.download_words(stream), stats_np.pack_bits(np_op(np.zeros(n, bool), pt & (c >= 1), op)))
     assert sel.count(stream) <= n
     sel.destroy(); buf.destroy()
 
@@ -284,7 +279,7 @@ def test_select_keeps_the_tail_clear(gs, device, stream, op):
 @pytest.mark.parametrize("sh,cov", FOUR_LAYOUTS)
 def test_delete_the_floaters(gs, device, stream, sh, cov):
     ref = _scene_ref(gs)
-    rows = _pods(gs, sh, cov)
+    rows = pod_rows(gs, sh, cov)
     buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), rows)
     mt = gs.model_transform_pod(**MT)
     k = 4
@@ -295,8 +290,8 @@ def test_delete_the_floaters(gs, device, stream, sh, cov):
     assert sel.count(stream) == int(isolated.sum())
     kept = buf.extract(stream, sel, invert=True)
     assert kept.len() == N - int(isolated.sum())
-    assert np.array_equal(_rows(kept, stream), rows[~isolated])
-    assert np.array_equal(_rows(buf, stream), rows)
+    assert np.array_equal(buffer_rows(kept, stream), rows[~isolated])
+    assert np.array_equal(buffer_rows(buf, stream), rows)
     kept.destroy(); sel.destroy(); buf.destroy()
 
 
@@ -307,19 +302,19 @@ def test_delete_the_floaters(gs, device, stream, sh, cov):
 def test_ordered_behind_an_edit_on_another_stream(gs, device, stream):
     sh, cov = 0, 0
     pod = gs.GaussianPod(sh, cov)
-    orig = _pods(gs, sh, cov)
+    orig = pod_rows(gs, sh, cov)
     mask = np.random.default_rng(4).random(N) < 0.3
     s1, s2 = stream, device.create_stream()
-    sel, out = _selection(gs, device, s1, mask), gs.Selection(device, N)
+    sel, out = selection_from_mask(gs, device, s1, mask), gs.Selection(device, N)
     s1.synchronize()
-    edited = _want(gs, sh, cov, orig.reshape(-1), mask, 15).reshape(N, pod.size)
+    edited = edited_pods(gs, sh, cov, orig.reshape(-1), mask, 15).reshape(N, pod.size)
     pw, before = neighbors_np.positions(edited), neighbors_np.positions(orig)
     r = _kth_distance(before, 8)
     c, c0 = neighbors_np.counts(pw, r), neighbors_np.counts(before, r)
     assert not np.array_equal(c, c0), "the edit changes the counts"
     for what in ("counts", "select"):
         buf = gs.GaussiansBuffer.new_with_pods(device, pod, orig)
-        buf.edit(s1, sel, _edit(gs, 15))
+        buf.edit(s1, sel, sample_edit(gs, 15))
         # on stream 2 right behind the edit on stream 1, no host synchronisation in between
         if what == "counts":
             assert np.array_equal(_plane(buf, s2, r), c.astype(np.uint32))
@@ -327,7 +322,7 @@ def test_ordered_behind_an_edit_on_another_stream(gs, device, stream):
             out.select_neighbors(s2, buf, r, 0, 3)
             assert np.array_equal(out.download_words(s2), stats_np.pack_bits(neighbors_np.in_count_range(c, neighbors_np.points(pw), 0, 3)))
         s1.synchronize()
-        assert np.array_equal(_rows(buf, s1), edited)
+        assert np.array_equal(buffer_rows(buf, s1), edited)
         buf.destroy()
     s2.synchronize()
     sel.destroy(); out.destroy()
@@ -341,7 +336,7 @@ def test_ordered_behind_an_edit_on_another_stream(gs, device, stream):
 def test_runs_are_identical(gs, device, stream):
     ref = _scene_ref(gs)
     sh, cov = 1, 2
-    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), pod_rows(gs, sh, cov))
     mt = gs.model_transform_pod(**MT)
     s2 = device.create_stream()
     for r, want in zip(ref["radii"], ref["counts"]):
@@ -365,9 +360,9 @@ def test_runs_are_identical(gs, device, stream):
 
 def test_argument_errors_change_nothing(gs, device, stream):
     sh, cov = 0, 0
-    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, gs.GaussianPod(sh, cov), pod_rows(gs, sh, cov))
     mask = np.random.default_rng(9).random(N) < 0.3
-    sel, short = _selection(gs, device, stream, mask), gs.Selection(device, N - 1)
+    sel, short = selection_from_mask(gs, device, stream, mask), gs.Selection(device, N - 1)
     other = gs.Device(0)          # a second device object: its objects belong to another device
     foreign, foreign_plane = gs.Selection(other, N), gs.Buffer(other, size=4 * N)
     words = sel.download_words(stream)

@@ -15,6 +15,7 @@ import pytest
 
 import gpu_child
 import helpers
+from frames import oracle_stages
 
 pytestmark = pytest.mark.gpu
 
@@ -35,9 +36,8 @@ def _scene(gs, ob, n=20000, W=800, H=600):
 
 
 def _oracle_image(gs, ob, buf, stream, pods, o):
-    from test_gpu_render import _oracle_frame
     order = buf.download_order(stream)
-    return _oracle_frame(ob, gs.SH_NONE, gs.COV3D_ROT_SCALE, pods, o[0], o[1], o[2], None, order=order)[-1]
+    return oracle_stages(ob, gs.SH_NONE, gs.COV3D_ROT_SCALE, pods, o[0], o[1], o[2], None, order=order)[-1]
 
 
 @pytest.mark.skipif(not ARMED, reason="runs in the child process of test_watchdog_children (GS3D_TEST_RANK_FAULT=1)")

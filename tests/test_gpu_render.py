@@ -11,116 +11,15 @@ import numpy as np
 import pytest
 
 import helpers
+from frames import compare_frame, mirror_order, oracle_stages, render_gpu
 
 pytestmark = pytest.mark.gpu
-
-RGBA_TOL = 1e-4  # BASELINE.json north_star: <= 1e-4 per channel
-
-
-def _render_gpu(gs, device, stream, pod, pods, gt, mt, cam, band=None, renderer=None, sort_mode=None):
-    buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    img = gs.Buffer(device, size=cam.height * cam.width * 16)
-    r = renderer or gs.Renderer(device)
-    if sort_mode is not None:
-        r.set_sort_mode(*sort_mode)        # (depth, tile): 1 MSD-first, 0 LSD passes, -1 the renderer chooses
-    r.render(stream, buf, gt, mt, cam, img.device_ptr(), band=band)
-    stream.synchronize()
-    rgba = img.download(stream, np.float32).reshape(cam.height, cam.width, 4)
-    return r, buf, img, rgba
-
-
-def _mirror_order(ob, buf, stream, sh, cov, pods, fresh=True):
-    """The buffer's mirror order, which the oracle needs for exact-depth ties.  For
-    a freshly created buffer it must equal the oracle's own restatement of the spatial order."""
-    order = buf.download_order(stream)
-    assert np.array_equal(np.sort(order), np.arange(len(order), dtype=np.uint32)), "order is not a permutation"
-    if fresh:
-        exp = ob.spatial_order(sh, cov, pods) if buf.spatial_order() and len(order) > 1 else np.arange(
-            len(order), dtype=np.uint32)
-        assert np.array_equal(order, exp), "mirror order differs from the oracle's spatial order"
-    return order
-
-
-def _oracle_frame(ob, sh, cov, pods, ogt, omt, ocam, band=None, order=None):
-    proj, tiles = ob.preprocess(sh, cov, pods, ogt, omt, ocam, band=band)
-    tiles_x = (ocam.width + 15) // 16
-    tiles_y = (ocam.height + 15) // 16
-    keys, idx = ob.build_keys(proj, tiles, tiles_x, order=order)
-    skeys, sidx = ob.sort_pairs(keys, idx)
-    ranges = ob.tile_ranges(skeys, tiles_x * tiles_y)
-    rgba = ob.blend(proj, sidx, ranges, ocam, band=band, gt=ogt)
-    return proj, tiles, keys, idx, skeys, sidx, ranges, rgba
-
-
-def _compare_frame(gs, ob, device, stream, sh, cov, gaussians, W, H, gt_kw=None, mt_kw=None,
-                   cam_kw=None, band=None, check_image_exact=True, sort_mode=None, info=None):
-    gt_kw, mt_kw, cam_kw = gt_kw or {}, mt_kw or {}, cam_kw or {}
-    pod = gs.GaussianPod(sh, cov)
-    pods = pod.from_gaussian(gaussians)
-    assert np.array_equal(pods, ob.pack(sh, cov, gaussians)), "product pack != oracle pack"
-    ogt = ob.gaussian_transform(**gt_kw)
-    omt = ob.model_transform(**mt_kw)
-    ocam = helpers.default_camera(ob, W, H, **cam_kw)
-    gt = gs.gaussian_transform_pod(gt_kw.get("size", 1.0), gt_kw.get("mode", 0), gt_kw.get("sh_deg", 3),
-                                   gt_kw.get("no_sh0", False), gt_kw.get("max_std_dev", 3.0))
-    mt = gs.model_transform_pod(mt_kw.get("pos", (0, 0, 0)), mt_kw.get("rot", (0, 0, 0, 1)),
-                                mt_kw.get("scale", (1, 1, 1)))
-    cam = helpers.copy_camera(ocam, gs.Camera)
-    assert bytes(gt) == bytes(ogt) and bytes(mt) == bytes(omt)
-
-    r, buf, img, rgba = _render_gpu(gs, device, stream, pod, pods, gt, mt, cam, band, sort_mode=sort_mode)
-    if info is not None:
-        info.append(r.sort_info())
-    order = _mirror_order(ob, buf, stream, sh, cov, pods)
-    o_proj, o_tiles, o_keys, o_idx, o_skeys, o_sidx, o_ranges, o_rgba = _oracle_frame(
-        ob, sh, cov, pods, ogt, omt, ocam, band, order=order)
-    n = len(gaussians)
-    st = r.stats()
-    g_proj, g_tiles = r.download_projected(n)
-    # --- preprocess ---
-    bad = np.nonzero(g_tiles != o_tiles)[0]
-    assert bad.size == 0, "tiles_touched differs at %d Gaussians, first %s: gpu %s oracle %s" % (
-        bad.size, bad[:5], g_tiles[bad[:5]], o_tiles[bad[:5]])
-    vis = o_tiles > 0
-    gb = g_proj[vis].view(np.uint8).reshape(-1, 48)
-    obb = o_proj[vis].view(np.uint8).reshape(-1, 48)
-    badrec = np.nonzero((gb != obb).any(axis=1))[0]
-    if badrec.size:
-        i = badrec[0]
-        raise AssertionError("projected record differs for %d of %d visible; first:\n gpu    %s\n oracle %s"
-                             % (badrec.size, vis.sum(), g_proj[vis][i], o_proj[vis][i]))
-    assert st.visible == int(vis.sum())
-    assert st.pairs == len(o_keys)
-    # --- keys + sort ---
-    g_skeys, g_sidx = r.download_sorted()
-    assert np.array_equal(g_skeys, o_skeys), "sorted keys differ"
-    assert np.array_equal(g_sidx, o_sidx), "sorted indices differ"
-    # --- ranges ---
-    tiles_x, tiles_y = (W + 15) // 16, (H + 15) // 16
-    g_ranges = r.download_ranges(tiles_x * tiles_y)
-    assert np.array_equal(g_ranges, o_ranges), "tile ranges differ"
-    # --- image ---
-    b0, b1 = band if band is not None else (0, tiles_y)
-    y0, y1 = b0 * 16, min(b1 * 16, H)
-    diff = np.abs(rgba[y0:y1] - o_rgba[y0:y1])
-    assert np.isfinite(rgba[y0:y1]).all()
-    assert diff.max(initial=0.0) <= RGBA_TOL, "RGBA L-inf %g > %g (at %s)" % (
-        diff.max(), RGBA_TOL, np.unravel_index(diff.argmax(), diff.shape))
-    if check_image_exact:
-        neq = (rgba[y0:y1].view(np.uint32) != o_rgba[y0:y1].view(np.uint32)).sum()
-        assert neq == 0, "%d channel values differ in the last bits (max abs diff %g)" % (neq, diff.max())
-    for h in (buf,):
-        h.destroy()
-    img.release()
-    r.destroy()
-    return st
-
 
 def test_synthetic_small_sh0(gs, ob, device, stream):
     import synth
     g = synth.scene(30000)
-    st = _compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1920, 1080,
-                        gt_kw=dict(sh_deg=0))
+    st = compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 1920, 1080,
+                       gt_kw=dict(sh_deg=0))
     assert st.pairs > 30000
 
 
@@ -129,25 +28,25 @@ def test_synthetic_small_sh0(gs, ob, device, stream):
 def test_all_twelve_pods_sh3(gs, ob, device, stream, sh, cov):
     import synth
     g = synth.scene(6000, first=1000)
-    _compare_frame(gs, ob, device, stream, sh, cov, g, 640, 360, gt_kw=dict(sh_deg=3))
+    compare_frame(gs, ob, device, stream, sh, cov, g, 640, 360, gt_kw=dict(sh_deg=3))
 
 
 @pytest.mark.parametrize("deg,no_sh0", [(0, False), (1, False), (2, True), (3, True)])
 def test_sh_degrees(gs, ob, device, stream, deg, no_sh0):
     import synth
     g = synth.scene(5000, first=77)
-    _compare_frame(gs, ob, device, stream, gs.SH_SINGLE, gs.COV3D_ROT_SCALE, g, 800, 600,
-                   gt_kw=dict(sh_deg=deg, no_sh0=no_sh0))
+    compare_frame(gs, ob, device, stream, gs.SH_SINGLE, gs.COV3D_ROT_SCALE, g, 800, 600,
+                  gt_kw=dict(sh_deg=deg, no_sh0=no_sh0))
 
 
 def test_model_transform_size_and_std_dev(gs, ob, device, stream):
     import synth
     g = synth.scene(8000, first=5)
     q = np.array([0.239118, 0.369644, -0.099046, 0.892399], dtype=np.float32)
-    _compare_frame(gs, ob, device, stream, gs.SH_HALF, gs.COV3D_ROT_SCALE, g, 1000, 700,
-                   gt_kw=dict(sh_deg=2, size=1.7, max_std_dev=2.0),
-                   mt_kw=dict(pos=(0.5, -0.25, -3.0), rot=tuple(q / np.linalg.norm(q)), scale=(1.5, 0.75, 1.25)),
-                   cam_kw=dict(eye=(1.0, 2.0, 6.0), target=(0.0, 0.0, -10.0), vfov_deg=50.0))
+    compare_frame(gs, ob, device, stream, gs.SH_HALF, gs.COV3D_ROT_SCALE, g, 1000, 700,
+                  gt_kw=dict(sh_deg=2, size=1.7, max_std_dev=2.0),
+                  mt_kw=dict(pos=(0.5, -0.25, -3.0), rot=tuple(q / np.linalg.norm(q)), scale=(1.5, 0.75, 1.25)),
+                  cam_kw=dict(eye=(1.0, 2.0, 6.0), target=(0.0, 0.0, -10.0), vfov_deg=50.0))
 
 
 def test_odd_image_size_and_background(gs, ob, device, stream):
@@ -160,10 +59,10 @@ def test_odd_image_size_and_background(gs, ob, device, stream):
     ocam = helpers.default_camera(ob, 333, 211)
     ocam.background[:] = [0.25, 0.5, 0.75]
     cam = helpers.copy_camera(ocam, gs.Camera)
-    r, buf, img, rgba = _render_gpu(gs, device, stream, pod, pods, gs.gaussian_transform_pod(sh_deg=1),
-                                    gs.model_transform_pod(), cam)
-    _, _, _, _, _, _, _, o_rgba = _oracle_frame(ob, pod.sh, pod.cov, pods, ogt, omt, ocam,
-                                                order=_mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))
+    r, buf, img, rgba = render_gpu(gs, device, stream, pod, pods, gs.gaussian_transform_pod(sh_deg=1),
+                                   gs.model_transform_pod(), cam)
+    _, _, _, _, _, _, _, o_rgba = oracle_stages(ob, pod.sh, pod.cov, pods, ogt, omt, ocam,
+                                                order=mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))
     assert np.array_equal(rgba.view(np.uint32), o_rgba.view(np.uint32))
 
 
@@ -174,7 +73,7 @@ def test_more_than_65536_tiles_uses_wide_tile_keys(gs, ob, device, stream):
     import synth
     g = synth.scene(6000, first=4242)
     g["scale"] *= 3.0   # cover more tiles
-    st = _compare_frame(gs, ob, device, stream, gs.SH_HALF, gs.COV3D_SINGLE, g, 4112, 4100, gt_kw=dict(sh_deg=2))
+    st = compare_frame(gs, ob, device, stream, gs.SH_HALF, gs.COV3D_SINGLE, g, 4112, 4100, gt_kw=dict(sh_deg=2))
     assert st.tiles_x * st.tiles_y == 257 * 257 and st.pairs > 0
     pod = gs.GaussianPod(gs.SH_HALF, gs.COV3D_SINGLE)
     pods = pod.from_gaussian(g)
@@ -183,10 +82,10 @@ def test_more_than_65536_tiles_uses_wide_tile_keys(gs, ob, device, stream):
     frames = []
     for (w, h) in ((4112, 4100), (640, 480), (4112, 4100)):
         cam = helpers.default_camera(gs, w, h)
-        _, buf, img, rgba = _render_gpu(gs, device, stream, pod, pods, gt, mt, cam, renderer=r)
+        _, buf, img, rgba = render_gpu(gs, device, stream, pod, pods, gt, mt, cam, renderer=r)
         ocam = helpers.copy_camera(cam, ob.Camera)
         o = ob.render(pod.sh, pod.cov, pods, ob.gaussian_transform(sh_deg=2), ob.model_transform(), ocam,
-                      order=_mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))[0]
+                      order=mirror_order(ob, buf, stream, pod.sh, pod.cov, pods))[0]
         assert np.array_equal(rgba.view(np.uint32), o.view(np.uint32)), (w, h)
         buf.destroy(); img.release()
     r.destroy()
@@ -229,8 +128,8 @@ def test_depth_key_ranges(gs, ob, device, stream, case, planes, msd):
         g["pos"][:, 2] = (-mid * (1.0 - rng.random(len(g)) * 1e-4)).astype(np.float32)
         g["pos"][:, :2] *= mid / 14.0
     info = []
-    st = _compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 640, 360,
-                        gt_kw=dict(sh_deg=0), cam_kw=dict(near=near, far=far), sort_mode=(msd, 0), info=info)
+    st = compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 640, 360,
+                       gt_kw=dict(sh_deg=0), cam_kw=dict(near=near, far=far), sort_mode=(msd, 0), info=info)
     assert st.visible > 100
     tile_passes = 2   # 40 x 23 = 920 tiles -> 10 bits -> 5 + 5
     bits = _depth_bits(near, far)
@@ -263,7 +162,7 @@ def test_block_culling_is_conservative_over_random_views(gs, ob, device, stream,
     pod = gs.GaussianPod(sh, cov)
     pods = pod.from_gaussian(g)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    order = _mirror_order(ob, buf, stream, sh, cov, pods)
+    order = mirror_order(ob, buf, stream, sh, cov, pods)
     W, H = 480, 272
     img = gs.Buffer(device, size=W * H * 16)
     r = gs.Renderer(device)
@@ -318,7 +217,7 @@ def test_block_culling_with_cancelling_translations(gs, ob, device, stream):
     pod = gs.GaussianPod(sh, cov)
     pods = pod.from_gaussian(g)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    order = _mirror_order(ob, buf, stream, sh, cov, pods)
+    order = mirror_order(ob, buf, stream, sh, cov, pods)
     W, H = 400, 240
     img = gs.Buffer(device, size=W * H * 16)
     r = gs.Renderer(device)
@@ -356,7 +255,7 @@ def test_block_list_mode_follows_the_view(gs, ob, device, stream):
     pod = gs.GaussianPod(sh, cov)
     pods = pod.from_gaussian(g)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    order = _mirror_order(ob, buf, stream, sh, cov, pods)
+    order = mirror_order(ob, buf, stream, sh, cov, pods)
     W, H = 320, 192
     img = gs.Buffer(device, size=W * H * 16)
     r = gs.Renderer(device)
@@ -377,7 +276,7 @@ def test_block_list_mode_follows_the_view(gs, ob, device, stream):
         assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), (k, name)
         # the taps of EVERY frame — list frames keep their per-slot arrays in list space, the
         # translation back to Gaussian indices goes through the block list and the mirror order
-        o_proj, o_tiles, _, _, o_skeys, o_sidx, o_ranges, _ = _oracle_frame(ob, sh, cov, pods, ogt, omt, ocam, order=order)
+        o_proj, o_tiles, _, _, o_skeys, o_sidx, o_ranges, _ = oracle_stages(ob, sh, cov, pods, ogt, omt, ocam, order=order)
         g_proj, g_tiles = r.download_projected(n)
         assert np.array_equal(g_tiles, o_tiles), (k, name)
         seen = o_tiles > 0
@@ -412,7 +311,7 @@ def test_list_frames_with_a_partial_last_block(gs, ob, device, stream, n):
     pod = gs.GaussianPod(sh, cov)
     pods = pod.from_gaussian(g)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, pods)
-    order = _mirror_order(ob, buf, stream, sh, cov, pods)
+    order = mirror_order(ob, buf, stream, sh, cov, pods)
     W, H = 640, 368
     tiles_y = H // 16
     img = gs.Buffer(device, size=W * H * 16)
@@ -428,7 +327,7 @@ def test_list_frames_with_a_partial_last_block(gs, ob, device, stream, n):
             fr = r.render(stream, buf, gt, mt, cam, img.device_ptr(), band=band)
         if n >= 1024:
             assert fr.launches == r.render(stream, buf, gt, mt, cam, img.device_ptr(), band=band).launches
-        o_proj, o_tiles, _, _, o_skeys, o_sidx, o_ranges, o_rgba = _oracle_frame(ob, sh, cov, pods, ogt, omt, ocam, band, order=order)
+        o_proj, o_tiles, _, _, o_skeys, o_sidx, o_ranges, o_rgba = oracle_stages(ob, sh, cov, pods, ogt, omt, ocam, band, order=order)
         st = r.stats()
         assert (st.visible, st.pairs) == (int((o_tiles > 0).sum()), len(o_skeys)), (n, band)
         g_proj, g_tiles = r.download_projected(n)
@@ -476,7 +375,7 @@ def test_pathological_gaussians_do_not_derail_the_frame(gs, ob, device, stream):
             gt, mt = gs.gaussian_transform_pod(sh_deg=3), gs.model_transform_pod()
             r.render(stream, buf, gt, mt, cam, img.device_ptr())
             got = img.download(stream, np.float32).reshape(cam.height, cam.width, 4)
-            order = _mirror_order(ob, buf, stream, sh, cov, pods)
+            order = mirror_order(ob, buf, stream, sh, cov, pods)
             exp, d, vis, _ = ob.render(sh, cov, pods, ob.gaussian_transform(sh_deg=3), ob.model_transform(), ocam,
                                        order=order)
             st = r.stats()
@@ -494,15 +393,15 @@ def test_display_modes_ellipse_and_point(gs, ob, device, stream, mode, std):
     import synth
     g = synth.scene(15000, first=77 + mode)
     g["scale"] *= 2.5
-    st = _compare_frame(gs, ob, device, stream, gs.SH_NORM8, gs.COV3D_ROT_SCALE, g, 512, 300,
-                        gt_kw=dict(mode=mode, sh_deg=2, max_std_dev=std))
+    st = compare_frame(gs, ob, device, stream, gs.SH_NORM8, gs.COV3D_ROT_SCALE, g, 512, 300,
+                       gt_kw=dict(mode=mode, sh_deg=2, max_std_dev=std))
     assert st.pairs > 0
     # and the three modes really differ
     pod = gs.GaussianPod(gs.SH_NORM8, gs.COV3D_ROT_SCALE)
     pods = pod.from_gaussian(g)
     cam = helpers.default_camera(gs, 512, 300)
-    frames = [_render_gpu(gs, device, stream, pod, pods, gs.gaussian_transform_pod(1.0, m, 2, False, std),
-                          gs.model_transform_pod(), cam)[3] for m in (0, mode)]
+    frames = [render_gpu(gs, device, stream, pod, pods, gs.gaussian_transform_pod(1.0, m, 2, False, std),
+                         gs.model_transform_pod(), cam)[3] for m in (0, mode)]
     assert not np.array_equal(frames[0], frames[1])
 
 
@@ -512,23 +411,23 @@ def test_edge_cases(gs, ob, device, stream):
     pod = gs.GaussianPod(gs.SH_SINGLE, gs.COV3D_ROT_SCALE)
     # empty
     g0 = np.zeros(0, dtype=gs.GAUSSIAN_DTYPE)
-    st = _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g0, 320, 200)
+    st = compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g0, 320, 200)
     assert st.pairs == 0 and st.visible == 0
     # single
     g1 = synth.scene(1, first=3)
     g1["pos"][0] = (0.1, -0.2, -5.0)
-    _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g1, 320, 200)
+    compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g1, 320, 200)
     # all behind the camera
     gb = synth.scene(3000)
     gb["pos"][:, 2] *= -1.0
-    st = _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, gb, 320, 200)
+    st = compare_frame(gs, ob, device, stream, pod.sh, pod.cov, gb, 320, 200)
     assert st.pairs == 0
     # huge splat close to the camera + many small ones (rect = whole screen; deep tile lists)
     gh = synth.scene(2000, first=9)
     gh["pos"][0] = (0.0, 0.0, -0.5)
     gh["scale"][0] = (0.6, 0.5, 0.4)
     gh["color"][0] = (10, 200, 90, 40)
-    st = _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, gh, 640, 480)
+    st = compare_frame(gs, ob, device, stream, pod.sh, pod.cov, gh, 640, 480)
     assert st.pairs >= 40 * 30
 
 
@@ -543,7 +442,7 @@ def test_pair_emission_regimes(gs, ob, device, stream, case):
     pod = gs.GaussianPod(gs.SH_NONE, gs.COV3D_ROT_SCALE)
     if case == "one_tile":
         g = synth.scene(500, first=77)
-        st = _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 16, 16, gt_kw=dict(sh_deg=0))
+        st = compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 16, 16, gt_kw=dict(sh_deg=0))
         assert st.tiles_x * st.tiles_y == 1 and st.pairs == st.visible > 0
     elif case == "screen_fillers":
         g = synth.scene(300, first=5)
@@ -551,18 +450,18 @@ def test_pair_emission_regimes(gs, ob, device, stream, case):
             g["pos"][7 * k] = (0.05 * k, -0.03 * k, -0.4 - 0.1 * k)
             g["scale"][7 * k] = (2.0, 1.5, 1.0)
             g["color"][7 * k, 3] = 30
-        st = _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 1920, 1080, gt_kw=dict(sh_deg=0))
+        st = compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 1920, 1080, gt_kw=dict(sh_deg=0))
         assert st.pairs >= 5 * 120 * 68
     elif case == "single_tile_splats":
         g = synth.scene(30000, first=1234)
         g["scale"] *= 0.02
-        st = _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 640, 480, gt_kw=dict(sh_deg=0))
+        st = compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 640, 480, gt_kw=dict(sh_deg=0))
         assert st.pairs < 2 * st.visible
     else:
         for n in (255, 257, 1021, 4099):
             g = synth.scene(n, first=n)
             g["pos"][:, 2] = -np.abs(g["pos"][:, 2]) - 3.0       # all in front: V is close to n
-            _compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 333, 211, gt_kw=dict(sh_deg=0))
+            compare_frame(gs, ob, device, stream, pod.sh, pod.cov, g, 333, 211, gt_kw=dict(sh_deg=0))
 
 
 def test_two_renderers_keep_frames_in_flight_on_one_buffer(gs, ob, device, stream):
@@ -584,7 +483,7 @@ def test_two_renderers_keep_frames_in_flight_on_one_buffer(gs, ob, device, strea
         rs[k].render(streams[k], buf, gt, mt, cams[k], imgs[k].device_ptr(), check=False)
     for s in streams:
         s.synchronize()
-    order = _mirror_order(ob, buf, stream, pod.sh, pod.cov, pods)
+    order = mirror_order(ob, buf, stream, pod.sh, pod.cov, pods)
     for k in range(2):
         rgba = imgs[k].download(streams[k], np.float32).reshape(480, 640, 4)
         ocam = helpers.copy_camera(cams[k], ob.Camera)
@@ -630,7 +529,7 @@ def test_one_renderer_alternating_streams_is_ordered(gs, ob, device, stream):
     r.wait_frame()
     for s in streams:
         s.synchronize()
-    order = _mirror_order(ob, buf, stream, pod.sh, pod.cov, pods)
+    order = mirror_order(ob, buf, stream, pod.sh, pod.cov, pods)
     want = [ob.render(pod.sh, pod.cov, pods, ob.gaussian_transform(sh_deg=2), ob.model_transform(),
                       helpers.copy_camera(c, ob.Camera), order=order)[0] for c in cams]
     for i in range(8):
@@ -694,8 +593,8 @@ def test_deep_tiles_early_termination(gs, ob, device, stream):
     g["pos"][:, 0] *= 0.02
     g["pos"][:, 1] *= 0.02
     g["color"][:, 3] = 250
-    _compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 256, 256,
-                   gt_kw=dict(sh_deg=0))
+    compare_frame(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, g, 256, 256,
+                  gt_kw=dict(sh_deg=0))
 
 
 def test_model_ply_config(gs, ob, device, stream):
@@ -708,8 +607,8 @@ def test_model_ply_config(gs, ob, device, stream):
     g = np.zeros(n, dtype=ob.GAUSSIAN_DTYPE)
     for i in range(n):
         ob.lib().gso_gaussian_from_ply(ply[i:i + 1].ctypes.data, g[i:i + 1].ctypes.data)
-    st = _compare_frame(gs, ob, device, stream, gs.SH_HALF, gs.COV3D_HALF, g, 640, 480,
-                        cam_kw=dict(eye=(4.0, 4.0, 22.0), target=(4.0, 4.0, 4.0)))
+    st = compare_frame(gs, ob, device, stream, gs.SH_HALF, gs.COV3D_HALF, g, 640, 480,
+                       cam_kw=dict(eye=(4.0, 4.0, 22.0), target=(4.0, 4.0, 4.0)))
     assert st.visible == 9
 
 
@@ -722,19 +621,19 @@ def test_tile_row_bands_stitch_bit_exact(gs, ob, device, stream):
     pods = pod.from_gaussian(g)
     gt, mt = gs.gaussian_transform_pod(sh_deg=3), gs.model_transform_pod()
     cam = helpers.default_camera(gs, 1280, 720)
-    r, buf, img, full = _render_gpu(gs, device, stream, pod, pods, gt, mt, cam)
+    r, buf, img, full = render_gpu(gs, device, stream, pod, pods, gt, mt, cam)
     tiles_y = (720 + 15) // 16
     stitched = np.zeros_like(full)
     bands = [(0, 11), (11, 23), (23, 40), (40, tiles_y)]
     for b in bands:
-        r2, buf2, img2, part = _render_gpu(gs, device, stream, pod, pods, gt, mt, cam, band=b)
+        r2, buf2, img2, part = render_gpu(gs, device, stream, pod, pods, gt, mt, cam, band=b)
         y0, y1 = b[0] * 16, min(b[1] * 16, 720)
         stitched[y0:y1] = part[y0:y1]
         # per-band parity against the oracle too
         ocam = helpers.copy_camera(cam, ob.Camera)
-        o = _oracle_frame(ob, pod.sh, pod.cov, pods, ob.gaussian_transform(sh_deg=3),
+        o = oracle_stages(ob, pod.sh, pod.cov, pods, ob.gaussian_transform(sh_deg=3),
                           ob.model_transform(), ocam, band=b,
-                          order=_mirror_order(ob, buf2, stream, pod.sh, pod.cov, pods))
+                          order=mirror_order(ob, buf2, stream, pod.sh, pod.cov, pods))
         assert np.array_equal(part[y0:y1].view(np.uint32), o[-1][y0:y1].view(np.uint32))
         buf2.destroy(); img2.release(); r2.destroy()
     assert np.array_equal(stitched.view(np.uint32), full.view(np.uint32))
@@ -761,8 +660,8 @@ def test_update_then_rerender_uses_new_data(gs, ob, device, stream):
     ocam = helpers.copy_camera(cam, ob.Camera)
     # update_range keeps the order computed at creation (from the OLD positions, which are unchanged here)
     o = ob.render(pod.sh, pod.cov, ob.pack(pod.sh, pod.cov, g2), ob.gaussian_transform(sh_deg=0),
-                  ob.model_transform(), ocam, order=_mirror_order(ob, buf, stream, pod.sh, pod.cov,
-                                                                  ob.pack(pod.sh, pod.cov, g)))[0]
+                  ob.model_transform(), ocam, order=mirror_order(ob, buf, stream, pod.sh, pod.cov,
+                                                                 ob.pack(pod.sh, pod.cov, g)))[0]
     assert np.array_equal(b.view(np.uint32).reshape(-1), o.view(np.uint32).reshape(-1))
 
 
@@ -789,7 +688,7 @@ def test_partial_updates_remirror_only_their_range_correctly(gs, ob, device, str
         r.render(stream, buf, gt, mt, cam, img.device_ptr())
         got = img.download(stream, np.float32)
         # positions move between updates: a whole-buffer update re-sorts, a partial one keeps the slots
-        order = _mirror_order(ob, buf, stream, sh, cov, None, fresh=False)
+        order = mirror_order(ob, buf, stream, sh, cov, None, fresh=False)
         if (start, count) == (0, 4500) and buf.spatial_order():
             assert np.array_equal(order, ob.spatial_order(sh, cov, ob.pack(sh, cov, g)))
         exp = ob.render(sh, cov, ob.pack(sh, cov, g), ob.gaussian_transform(sh_deg=3), ob.model_transform(), ocam,
@@ -955,7 +854,7 @@ def test_adversarial_needles_match_the_unclipped_frame(gs, ob, device, stream, c
     pods = pod.from_gaussian(g)
     cam = helpers.copy_camera(ocam, gs.Camera)
     gt, mt = gs.gaussian_transform_pod(sh_deg=0), gs.model_transform_pod()
-    r, buf, img, rgba = _render_gpu(gs, device, stream, pod, pods, gt, mt, cam)
+    r, buf, img, rgba = render_gpu(gs, device, stream, pod, pods, gt, mt, cam)
     st = r.stats()
     old = ob.rect_version()
     try:
@@ -1059,7 +958,7 @@ def test_renderer_survives_the_stream_of_its_last_frame(gs, ob, device):
     b.synchronize()
     rgba = img.download(b, np.float32).reshape(cam.height, cam.width, 4)
     o = ob.render(pod.sh, pod.cov, pods, ob.gaussian_transform(sh_deg=0), ob.model_transform(), helpers.copy_camera(cam, ob.Camera),
-                  order=_mirror_order(ob, buf, b, pod.sh, pod.cov, pods))[0]
+                  order=mirror_order(ob, buf, b, pod.sh, pod.cov, pods))[0]
     assert np.array_equal(rgba.view(np.uint32), o.view(np.uint32))
     r.destroy()
     buf.destroy()

@@ -8,70 +8,18 @@ import numpy as np
 import pytest
 
 import helpers
+import synth
+from frames import frame_setup
+from helpers import band_rows, bits, deep_scene
+from planes import POISON_PICK, Planes, oracle_depth, pick_witness
 
 pytestmark = pytest.mark.gpu
 
-POISON_DEPTH = np.float32(np.nan)
-POISON_PICK = np.uint32(0xDEADBEEF)
 PODS = [(0, 0), (3, 0)]          # (sh, cov): SH3 f32 + rot-scale, SH-none + rot-scale
 
 
-class Planes:
-    """an RGBA target and the two aux planes of one image, poisoned"""
-
-    def __init__(self, gs, device, W, H):
-        self.W, self.H = W, H
-        self.img = gs.Buffer(device, data=np.full(H * W * 4, np.float32(-7.0)))
-        self.depth = gs.Buffer(device, data=np.full(H * W, POISON_DEPTH, dtype=np.float32))
-        self.pick = gs.Buffer(device, data=np.full(H * W, POISON_PICK, dtype=np.uint32))
-
-    def poison(self, stream, image=False):
-        if image:       # a target that one renderer fills frame after frame
-            self.img.write(stream, 0, np.full(self.H * self.W * 4, np.float32(-7.0)))
-        self.depth.write(stream, 0, np.full(self.H * self.W, POISON_DEPTH, dtype=np.float32))
-        self.pick.write(stream, 0, np.full(self.H * self.W, POISON_PICK, dtype=np.uint32))
-        stream.synchronize()
-
-    def render(self, r, stream, buf, gt, mt, cam, band=None, threshold=0.5, check=True):
-        fr = r.render(stream, buf, gt, mt, cam, self.img.device_ptr(), band=band, check=check,
-                      depth_device_ptr=self.depth.device_ptr(), pick_device_ptr=self.pick.device_ptr(),
-                      pick_threshold=threshold)
-        stream.synchronize()
-        return fr
-
-    def get(self, stream):
-        return (self.img.download(stream, np.float32).reshape(self.H, self.W, 4).copy(),
-                self.depth.download(stream, np.float32).reshape(self.H, self.W).copy(),
-                self.pick.download(stream, np.uint32).reshape(self.H, self.W).copy())
-
-    def release(self):
-        for b in (self.img, self.depth, self.pick):
-            b.release()
-
-
 def _scene(gs, ob, sh, cov, n, W, H, mode=0, first=7, **cam_kw):
-    import synth
-    g = synth.scene(n, first=first)
-    pod = gs.GaussianPod(sh, cov)
-    pods = pod.from_gaussian(g)
-    ogt = ob.gaussian_transform(sh_deg=3 if sh != gs.SH_NONE else 0, mode=mode)
-    omt = ob.model_transform()
-    ocam = helpers.default_camera(ob, W, H, **cam_kw)
-    gt = gs.GaussianTransformPod.from_buffer_copy(bytes(ogt))
-    mt = gs.ModelTransformPod.from_buffer_copy(bytes(omt))
-    cam = helpers.copy_camera(ocam, gs.Camera)
-    return pod, pods, ogt, omt, ocam, gt, mt, cam
-
-
-def _oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band=None):
-    """the depth plane's definition: the oracle blend's R channel with r := z', g = b = 0, background 0"""
-    p = proj.copy()
-    p["r"] = p["depth"]
-    p["g"] = 0.0
-    p["b"] = 0.0
-    cam0 = ob.Camera.from_buffer_copy(bytes(ocam))
-    cam0.background[:] = [0.0, 0.0, 0.0]
-    return ob.blend(p, sidx, ranges, cam0, band=band, gt=ogt)[..., 0]
+    return frame_setup(gs, ob, synth.scene(n, first=first), W, H, sh, cov, mode, sh_deg=3 if sh != gs.SH_NONE else 0, **cam_kw)
 
 
 def _oracle(ob, sh, cov, pods, ogt, omt, ocam, order, band=None):
@@ -81,15 +29,7 @@ def _oracle(ob, sh, cov, pods, ogt, omt, ocam, order, band=None):
     skeys, sidx = ob.sort_pairs(keys, idx)
     ranges = ob.tile_ranges(skeys, tiles_x * tiles_y)
     rgba = ob.blend(proj, sidx, ranges, ocam, band=band, gt=ogt)
-    return rgba, _oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band)
-
-
-def _rows(band, H):
-    return (0, H) if band is None else (band[0] * 16, min(band[1] * 16, H))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+    return rgba, oracle_depth(ob, proj, sidx, ranges, ocam, ogt, band)
 
 
 @pytest.mark.parametrize("sh,cov", PODS)
@@ -101,7 +41,7 @@ def test_aux_colour_unchanged_and_depth_exact(gs, ob, device, stream, mode, sh, 
     order = buf.download_order(stream)
     for band in (None, (3, 9)):
         o_rgba, o_depth = _oracle(ob, sh, cov, pods, ogt, omt, ocam, order, band)
-        y0, y1 = _rows(band, H)
+        y0, y1 = band_rows(band, H)
         plain = gs.Buffer(device, size=W * H * 16)
         r_plain, r_aux = gs.Renderer(device), gs.Renderer(device)
         fr_plain = r_plain.render(stream, buf, gt, mt, cam, plain.device_ptr(), band=band)
@@ -110,9 +50,9 @@ def test_aux_colour_unchanged_and_depth_exact(gs, ob, device, stream, mode, sh, 
         fr_aux = pl.render(r_aux, stream, buf, gt, mt, cam, band=band)
         rgba, depth, pick = pl.get(stream)
         assert fr_aux.launches == fr_plain.launches, "the planes ride in the blend launch"
-        assert np.array_equal(_bits(rgba[y0:y1]), _bits(rgba_plain[y0:y1])), "aux frame colour != plain frame colour"
-        assert np.array_equal(_bits(rgba[y0:y1]), _bits(o_rgba[y0:y1])), "aux frame colour != oracle"
-        bad = _bits(depth[y0:y1]) != _bits(o_depth[y0:y1])
+        assert np.array_equal(bits(rgba[y0:y1]), bits(rgba_plain[y0:y1])), "aux frame colour != plain frame colour"
+        assert np.array_equal(bits(rgba[y0:y1]), bits(o_rgba[y0:y1])), "aux frame colour != oracle"
+        bad = bits(depth[y0:y1]) != bits(o_depth[y0:y1])
         assert not bad.any(), "depth differs from the oracle at %d pixels, first %s: %s vs %s" % (
             bad.sum(), np.argwhere(bad)[0], depth[y0:y1][bad][:3], o_depth[y0:y1][bad][:3])
         # rows outside the band keep the poison
@@ -125,52 +65,6 @@ def test_aux_colour_unchanged_and_depth_exact(gs, ob, device, stream, mode, sh, 
         assert (depth[y0:y1][rgba[y0:y1, :, 3] == 0.0] == 0.0).all()
         pl.release(); plain.release(); r_plain.destroy(); r_aux.destroy()
     buf.destroy()
-
-
-def _witness(proj, sidx, ranges, W, H, tiles_x, tcut64, rel=1e-5):
-    """float64 walk of every pixel's tile list (splat mode): the first splat whose step takes T to <= tcut; also
-    whether any decision up to there lies within `rel` of its boundary.  Returns (pick, ambiguous)."""
-    NONE = 0xFFFFFFFF
-    pick = np.full((H, W), NONE, dtype=np.uint64)
-    amb = np.zeros((H, W), bool)
-    p = {k: proj[k].astype(np.float64) for k in ("mx", "my", "ca", "cb", "cc", "opacity")}
-    for t in range(ranges.shape[0]):
-        s, e = int(ranges[t, 0]), int(ranges[t, 1])
-        if e <= s:
-            continue
-        tx, ty = t % tiles_x, t // tiles_x
-        xs = np.arange(tx * 16, min(tx * 16 + 16, W))
-        ys = np.arange(ty * 16, min(ty * 16 + 16, H))
-        if not len(xs) or not len(ys):
-            continue
-        px, py = np.meshgrid(xs + 0.5, ys + 0.5)
-        px, py = px.ravel(), py.ravel()
-        T = np.ones(px.shape)
-        live = np.ones(px.shape, bool)
-        got = np.full(px.shape, NONE, dtype=np.uint64)
-        am = np.zeros(px.shape, bool)
-        for j in range(s, e):
-            g = int(sidx[j])
-            dx, dy = p["mx"][g] - px, p["my"][g] - py
-            a, b, c = p["ca"][g] * dx * dx, p["cb"][g] * dx * dy, p["cc"][g] * dy * dy
-            power = a + b + c
-            scale = np.abs(a) + np.abs(b) + np.abs(c)
-            alpha = np.minimum(0.99, p["opacity"][g] * np.exp(power))
-            act = live & (power <= 0.0) & (alpha >= 1.0 / 255.0)
-            am |= live & ((np.abs(power) <= rel * scale) | (np.abs(alpha - 1.0 / 255.0) <= rel / 255.0))
-            Tn = T * (1.0 - alpha)
-            am |= act & ((np.abs(Tn - 1e-4) <= rel * 1e-4) | (np.abs(Tn - tcut64) <= rel * tcut64))
-            fin = act & (Tn < 1e-4)
-            blend = act & ~fin
-            hit = blend & (Tn <= tcut64) & (got == NONE)
-            got[hit] = g
-            T = np.where(blend, Tn, T)
-            live &= ~fin & (got == NONE)
-            if not live.any():
-                break
-        pick[py.astype(int), px.astype(int)] = got
-        amb[py.astype(int), px.astype(int)] = am
-    return pick, amb
 
 
 def _check_pick_pairs(gs, r, pick, W, H, n):
@@ -207,7 +101,7 @@ def test_aux_pick_matches_a_float64_walk(gs, ob, device, stream, threshold):
     picked = pick != gs.PICK_NONE
     # the float64 walk agrees wherever it is unambiguous
     tcut = np.float32(1.0) - np.float32(threshold)
-    w_pick, amb = _witness(proj, sidx, ranges, W, H, tiles_x, float(tcut))
+    w_pick, amb = pick_witness(proj, sidx, ranges, W, H, tiles_x, float(tcut))
     assert amb.mean() <= 1e-3, "%.4f %% ambiguous pixels" % (100 * amb.mean())
     bad = (w_pick != pick.astype(np.uint64)) & ~amb
     assert not bad.any(), "pick differs from the float64 walk at %d pixels, first %s: %s vs %s" % (
@@ -245,7 +139,7 @@ def test_aux_invalid_arguments(gs, ob, device, stream):
     pl2 = Planes(gs, device, W, H)
     r2.render(stream, buf, gt, mt, cam, pl2.img.device_ptr(), pick_device_ptr=pl2.pick.device_ptr())
     rgba2, depth2, pick2 = pl2.get(stream)
-    assert np.array_equal(pick2, pick) and np.isnan(depth2).all() and np.array_equal(_bits(rgba2), _bits(rgba))
+    assert np.array_equal(pick2, pick) and np.isnan(depth2).all() and np.array_equal(bits(rgba2), bits(rgba))
     # the smallest thresholds that are accepted pick the first contributor, as 1/255 does
     firsts = []
     for t in (1.0 / 255.0, 2.0 ** -24, float(np.nextafter(np.float32(2.0 ** -25), np.float32(1.0)))):
@@ -261,13 +155,12 @@ def test_aux_invalid_arguments(gs, ob, device, stream):
                                                   0, 0xFFFFFFFF, pl2.img.device_ptr(), gs.C.byref(gs.AuxTargets())))
     assert r2.wait_frame().flags == 0
     rgba2, depth2, pick2 = pl2.get(stream)
-    assert np.array_equal(_bits(rgba2), _bits(rgba)) and np.isnan(depth2).all() and (pick2 == POISON_PICK).all()
+    assert np.array_equal(bits(rgba2), bits(rgba)) and np.isnan(depth2).all() and (pick2 == POISON_PICK).all()
     pl.release(); pl2.release(); r.destroy(); r2.destroy(); buf.destroy()
 
 
 def test_aux_pick_is_a_caller_index(gs, ob, device, stream):
     """spatial order on / off, and a renderer in block-list mode (its per-slot arrays in list space): the same planes"""
-    import synth
     n, W, H = 90_000, 320, 192
     g = synth.scene(n, first=4242)
     pod = gs.GaussianPod(1, 0)
@@ -294,22 +187,14 @@ def test_aux_pick_is_a_caller_index(gs, ob, device, stream):
     for key in res:
         ref = res[(True, 0 if key[1] == 0 else 1)][1]
         for a, b in zip(res[key][1], ref):
-            assert np.array_equal(_bits(a), _bits(b)), key
+            assert np.array_equal(bits(a), bits(b)), key
     assert (res[(True, 1)][1][2] != gs.PICK_NONE).any() and (res[(True, 0)][1][2] != gs.PICK_NONE).any()
-
-
-def _deep_scene(n, first=4242, opacity=250, scale=3.5):
-    import synth
-    g = synth.scene(n, first=first)
-    g["color"][:, 3] = opacity
-    g["scale"] *= np.float32(scale)
-    return g
 
 
 def test_aux_two_rounds_equal_one_round(gs, ob, device, stream):
     W, H = 640, 360
     sh, cov = gs.SH_NONE, gs.COV3D_ROT_SCALE
-    g = _deep_scene(200_000)
+    g = deep_scene(200_000)
     pod = gs.GaussianPod(sh, cov)
     pods = pod.from_gaussian(g)
     gt = gs.gaussian_transform_pod(1.0, 0, 0, False, 3.0)
@@ -323,7 +208,7 @@ def test_aux_two_rounds_equal_one_round(gs, ob, device, stream):
     ref = pl.get(stream)
     assert r.sort_info().rounds == 1
     for band in (None, (4, 17)):
-        y0, y1 = _rows(band, H)
+        y0, y1 = band_rows(band, H)
         for k in (5_000, 30_000, 120_000):
             r2 = gs.Renderer(device)
             r2.set_rounds(1, k)
@@ -333,8 +218,8 @@ def test_aux_two_rounds_equal_one_round(gs, ob, device, stream):
                 assert r2.sort_info().rounds == 2
                 rgba, depth, pick = pl.get(stream)
                 ctx = (band, k, frame)
-                assert np.array_equal(_bits(rgba[y0:y1]), _bits(ref[0][y0:y1])), ctx
-                assert np.array_equal(_bits(depth[y0:y1]), _bits(ref[1][y0:y1])), ctx
+                assert np.array_equal(bits(rgba[y0:y1]), bits(ref[0][y0:y1])), ctx
+                assert np.array_equal(bits(depth[y0:y1]), bits(ref[1][y0:y1])), ctx
                 assert np.array_equal(pick[y0:y1], ref[2][y0:y1]), ctx
                 if band is not None:
                     assert np.isnan(depth[:y0]).all() and (pick[y1:] == POISON_PICK).all(), ctx
@@ -344,7 +229,6 @@ def test_aux_two_rounds_equal_one_round(gs, ob, device, stream):
 
 def test_aux_skipped_frame_leaves_the_planes(gs, ob, device, stream):
     """far-then-near: the near frame outgrows the pair capacity and is skipped; its planes stay untouched"""
-    import synth
     g = synth.scene(60000, first=5)
     pod = gs.GaussianPod(gs.SH_NONE, gs.COV3D_ROT_SCALE)
     pods = pod.from_gaussian(g)
@@ -367,18 +251,17 @@ def test_aux_skipped_frame_leaves_the_planes(gs, ob, device, stream):
         r.wait_frame()
     got = pl.get(stream)
     for a, b in zip(got, far):
-        assert np.array_equal(_bits(a), _bits(b)), "a skipped frame must leave the planes untouched"
+        assert np.array_equal(bits(a), bits(b)), "a skipped frame must leave the planes untouched"
     pl.render(r, stream, buf, gt_big, mt, near_cam, check=False)
     assert r.wait_frame().flags == 0
     got = pl.get(stream)
     for a, b in zip(got, want):
-        assert np.array_equal(_bits(a), _bits(b))
+        assert np.array_equal(bits(a), bits(b))
     pl.release(); ref.release(); r.destroy(); ref_r.destroy(); buf.destroy()
 
 
 def test_aux_frame_ring(gs, ob, device, stream):
     """three frames in flight, each lane with its own planes: every lane's planes are the lone renderer's"""
-    import synth
     W, H = 480, 270
     g = synth.scene(200_000, first=11)
     pod = gs.GaussianPod(gs.SH_NONE, gs.COV3D_ROT_SCALE)
@@ -410,7 +293,7 @@ def test_aux_frame_ring(gs, ob, device, stream):
         ring.wait()
         for k, (a, b) in enumerate(zip(got, want)):
             for x, y in zip(a, b):
-                assert np.array_equal(_bits(x), _bits(y)), (rep, k)
+                assert np.array_equal(bits(x), bits(y)), (rep, k)
     for pl in lanes:
         pl.release()
     ring.close(); buf.destroy()
@@ -418,7 +301,6 @@ def test_aux_frame_ring(gs, ob, device, stream):
 
 def test_aux_at_scale(gs, ob, device, stream):
     """1 M Gaussians at 1080p under the renderer's own policy: the aux colour is the plain frame's, the depth the oracle's"""
-    import synth
     n, W, H = 1_000_000, 1920, 1080
     sh, cov = gs.SH_NONE, gs.COV3D_ROT_SCALE
     g = synth.scene(n)
@@ -441,7 +323,7 @@ def test_aux_at_scale(gs, ob, device, stream):
     _, depth, pick = pl.get(stream)
     o_rgba, o_depth = _oracle(ob, sh, cov, pods, ogt, omt, ocam, order)
     rgba = plain.download(stream, np.float32).reshape(H, W, 4)
-    assert np.array_equal(_bits(rgba), _bits(o_rgba))
-    assert np.array_equal(_bits(depth), _bits(o_depth))
+    assert np.array_equal(bits(rgba), bits(o_rgba))
+    assert np.array_equal(bits(depth), bits(o_depth))
     assert np.array_equal(pick != gs.PICK_NONE, rgba[..., 3] >= 0.5)
     pl.release(); plain.release(); r_plain.destroy(); r_aux.destroy(); buf.destroy()

@@ -205,7 +205,7 @@ def describe(name, part, m):
 def test_the_model_reproduces_the_figures_of_the_round_bound_sequences(ob):
     """tests/test_gpu_round_bounds.py asserts on the device: the translucent kinds finish no tile and emit D = D1 + D2, `cover`
     finishes all 360 tiles of the band with a round 1 of 2 048 and emits round 1's 63 555 pairs alone"""
-    import test_gpu_round_bounds as rb
+    import round_kinds as rb
     want = {"small": (23501, 55345, {2048: 10613, 16384: 42774}), "big": (28468, 309085, {2048: 76478, 16384: 237078}),
             "cover": (27773, 258918, {2048: 63555})}
     for kind, (V, D, d1) in want.items():
@@ -227,9 +227,9 @@ def test_the_model_reproduces_the_figures_of_the_round_bound_sequences(ob):
 
 @pytest.mark.parametrize("which", ["walk_rounds", "mixed4k"])
 def test_the_model_agrees_with_the_float64_walk(ob, which):
-    """an independent computation of round 1's coverage (tests/test_gpu_renderer_walk.py's round1_coverage: float64, its own
+    """an independent computation of round 1's coverage (tests/walk_kinds.py's round1_coverage: float64, its own
     arithmetic, a 0.1 % undecided margin): every tile it calls certainly finished is done, no done tile is certainly open"""
-    import test_gpu_renderer_walk as tw
+    import walk_kinds as tw
     if which == "walk_rounds":
         o = tw.oracle_frame(ob, "rounds")
         W, H, order = 100, 70, tw.host_buffer(ob, "R")["order"]

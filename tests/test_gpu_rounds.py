@@ -8,7 +8,8 @@ import pytest
 import gpu_child
 import helpers
 import rounds_np
-from helpers import deep_scene as _deep_scene, round_setup as _setup
+from frames import frame_setup as _setup
+from helpers import deep_scene as _deep_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -199,10 +200,10 @@ def test_two_rounds_at_full_size_match_the_golden_frame(gs, device, stream):
     import hashlib
     import json
     import os
-    from test_gpu_fullsize import _upload
+    from scenes import upload_synth
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     g = json.load(open(os.path.join(root, "tests", "golden", "fullsize_v3.json")))["10m"]
-    pod, buf, scene_sha = _upload(gs, device, stream, g)
+    pod, buf, scene_sha = upload_synth(gs, device, stream, g)
     assert scene_sha == g["scene_sha256"]
     cam = gs.camera_look_at((0, 0, 0), (0, 0, -1), (0, 1, 0), float(np.deg2rad(60)), g["width"], g["height"], 0.1, 100.0)
     gt, mt = gs.gaussian_transform_pod(sh_deg=g["sh_deg"]), gs.model_transform_pod()

@@ -6,19 +6,13 @@ import numpy as np
 import pytest
 
 import helpers
+from frames import Scene, tint32
+from helpers import band_rows, bits, deep_scene
+from records import SELECT_OPS, np_op
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-OPS = ["set", "or", "and", "andnot", "xor"]
-
-
-def _np_op(d, s, op):
-    return {"set": s, "or": d | s, "and": d & s, "andnot": d & ~s, "xor": d ^ s}[op]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _tail_mask(n):
@@ -60,10 +54,10 @@ def test_bit_operations(gs, device, stream, n):
     a.upload(stream, fl)
     assert np.array_equal(a.download(stream), fl) and a.count(stream) == int(fl.sum())
     a.upload(stream, wa)
-    for op in OPS:
+    for op in SELECT_OPS:
         a.upload(stream, wa)
         a.combine(stream, op, b)
-        want = _np_op(wa, wb, op)
+        want = np_op(wa, wb, op)
         got = a.download_words(stream)
         assert np.array_equal(got, want), op
         assert got[-1] & ~_tail_mask(n) == 0
@@ -165,14 +159,14 @@ def test_sphere_and_box_exact(gs, device, stream, sh, cov):
         # a sheared box, and every op on top of a random selection
         b = rng.uniform(-0.2, 0.2, 12).astype(f32)
         want_box = _box32(pw, b)
-        for op in OPS:
+        for op in SELECT_OPS:
             base = rng.random(n) < 0.5
             sel.upload(stream, base)
             sel.select_box(stream, buf, mt, b, op=op)
-            assert np.array_equal(sel.download(stream), _np_op(base, want_box, op)), op
+            assert np.array_equal(sel.download(stream), np_op(base, want_box, op)), op
             sel.upload(stream, base)
             sel.select_sphere(stream, buf, mt, (1.0, 1.0, 1.0), 6.0, op=op)
-            assert np.array_equal(sel.download(stream), _np_op(base, _sphere32(pw, (1.0, 1.0, 1.0), 6.0), op)), op
+            assert np.array_equal(sel.download(stream), np_op(base, _sphere32(pw, (1.0, 1.0, 1.0), 6.0), op)), op
     for bad in (-1.0, float("nan")):
         with pytest.raises(gs.InvalidArgumentError):
             sel.select_sphere(stream, buf, transforms[0], (0, 0, 0), bad)
@@ -232,78 +226,12 @@ def test_sphere_and_box_general_transform(gs, device, stream):
 # frames
 # ------------------------------------------------------------------------------------------------
 
-class Scene:
-    def __init__(self, gs, ob, device, stream, sh, cov, n, W, H, mode=0, first=7, spatial=True, g=None, **cam_kw):
-        import synth
-        self.gs, self.ob, self.device, self.stream = gs, ob, device, stream
-        self.sh, self.cov, self.n, self.W, self.H = sh, cov, n, W, H
-        self.g = synth.scene(n, first=first) if g is None else g
-        self.pod = gs.GaussianPod(sh, cov)
-        self.pods = self.pod.from_gaussian(self.g)
-        self.ogt = ob.gaussian_transform(sh_deg=3 if sh != gs.SH_NONE else 0, mode=mode)
-        self.omt = ob.model_transform()
-        self.ocam = helpers.default_camera(ob, W, H, **cam_kw)
-        self.gt = gs.GaussianTransformPod.from_buffer_copy(bytes(self.ogt))
-        self.mt = gs.ModelTransformPod.from_buffer_copy(bytes(self.omt))
-        self.cam = helpers.copy_camera(self.ocam, gs.Camera)
-        self.buf = gs.GaussiansBuffer.new_with_pods(device, self.pod, self.pods)
-        if not spatial:
-            self.buf.set_spatial_order(False)
-        self.img = gs.Buffer(device, data=np.full(H * W * 4, f32(np.nan)))
-        self.tiles_x, self.tiles_y = (W + 15) // 16, (H + 15) // 16
-
-    def order(self):
-        return self.buf.download_order(self.stream)
-
-    def twin_pods(self, hidden):
-        """the oracle twin: opacity byte (byte 15 of every record) of the hidden Gaussians := 0"""
-        p = np.array(self.pods, dtype=np.uint8).reshape(self.n, -1).copy()
-        p[np.asarray(hidden, bool), 15] = 0
-        return p.reshape(-1)
-
-    def oracle(self, pods, band=None, ocam=None, recolour=None):
-        ob, ocam = self.ob, ocam or self.ocam
-        proj, tiles = ob.preprocess(self.sh, self.cov, pods, self.ogt, self.omt, ocam, band=band)
-        if recolour is not None:
-            recolour(proj)
-        keys, idx = ob.build_keys(proj, tiles, self.tiles_x, order=self.order())
-        skeys, sidx = ob.sort_pairs(keys, idx)
-        ranges = ob.tile_ranges(skeys, self.tiles_x * self.tiles_y)
-        rgba = ob.blend(proj, sidx, ranges, ocam, band=band, gt=self.ogt)
-        return dict(proj=proj, tiles=np.asarray(tiles), keys=skeys, idx=sidx, ranges=ranges, rgba=rgba)
-
-    def poison(self):
-        self.img.write(self.stream, 0, np.full(self.H * self.W * 4, f32(np.nan)))
-        self.stream.synchronize()
-
-    def render(self, r, band=None, cam=None, **kw):
-        fr = r.render(self.stream, self.buf, self.gt, self.mt, cam or self.cam, self.img.device_ptr(), band=band, **kw)
-        self.stream.synchronize()
-        return fr
-
-    def image(self):
-        return self.img.download(self.stream, f32).reshape(self.H, self.W, 4).copy()
-
-    def selection(self, flags):
-        s = self.gs.Selection(self.device, self.n)
-        s.upload(self.stream, np.asarray(flags, bool))
-        return s
-
-    def release(self):
-        self.img.release()
-        self.buf.destroy()
-
-
-def _rows(band, H):
-    return (0, H) if band is None else (band[0] * 16, min(band[1] * 16, H))
-
-
 def _check_hidden_frame(sc, r, fr, hidden, band=None, cam=None, ocam=None, taps=True):
     """image bit-equal to the oracle twin's; with `taps` also V, D, the sorted keys and caller indices and the projected tap"""
     o = sc.oracle(sc.twin_pods(hidden), band=band, ocam=ocam)
-    y0, y1 = _rows(band, sc.H)
+    y0, y1 = band_rows(band, sc.H)
     img = sc.image()
-    bad = _bits(img[y0:y1]) != _bits(o["rgba"][y0:y1])
+    bad = bits(img[y0:y1]) != bits(o["rgba"][y0:y1])
     assert not bad.any(), "%d words of the image differ from the oracle twin" % bad.sum()
     if not taps:
         return o
@@ -363,11 +291,11 @@ def test_select_visible(gs, ob, device, stream, spatial):
                 got = sel.download(stream)
                 assert np.array_equal(got, want), (name, band, region, m is not None, int((got != want).sum()))
         want = _visible_want(o, 40.5, 30.0, 200.25, 150.0, mask, W, H)
-        for op in OPS:
+        for op in SELECT_OPS:
             base = rng.random(n) < 0.5
             sel.upload(stream, base)
             r.select_visible(stream, sel, 40.5, 30.0, 200.25, 150.0, mask_device_ptr=mask_buf.device_ptr(), op=op)
-            assert np.array_equal(sel.download(stream), _np_op(base, want, op)), (name, op)
+            assert np.array_equal(sel.download(stream), np_op(base, want, op)), (name, op)
     if spatial:
         assert launches[2] == launches[1] + 1, "the second corner frame should take the block list"
     # Gaussians hidden in the frame are not visible
@@ -402,7 +330,7 @@ def test_hide_matches_the_oracle_twin(gs, ob, device, stream, sh, cov):
         sc.poison()
         fr = sc.render(r, band=band, hide=hs)
         _check_hidden_frame(sc, r, fr, hidden, band=band)
-        y0, y1 = _rows(band, H)
+        y0, y1 = band_rows(band, H)
         img = sc.image()
         assert np.isnan(img[:y0]).all() and np.isnan(img[y1:]).all()
     r.destroy(); hs.destroy(); sc.release()
@@ -449,17 +377,9 @@ def test_hide_box_list_frame_and_block_skip(gs, ob, device, stream, spatial):
     r.destroy(); sel.destroy(); sc.release()
 
 
-def _deep_scene(n, first=4242, opacity=250, scale=3.5):
-    import synth
-    g = synth.scene(n, first=first)
-    g["color"][:, 3] = opacity
-    g["scale"] *= f32(scale)
-    return g
-
-
 def test_hide_two_rounds(gs, ob, device, stream):
     n, W, H = 120_000, 640, 360
-    sc = Scene(gs, ob, device, stream, gs.SH_NONE, 0, n, W, H, g=_deep_scene(n))
+    sc = Scene(gs, ob, device, stream, gs.SH_NONE, 0, n, W, H, g=deep_scene(n))
     hidden = np.random.default_rng(2).random(n) < 0.3
     hs = sc.selection(hidden)
     o = sc.oracle(sc.twin_pods(hidden))
@@ -470,7 +390,7 @@ def test_hide_two_rounds(gs, ob, device, stream):
             sc.poison()
             sc.render(r, hide=hs)
             assert r.sort_info().rounds == 2
-            assert np.array_equal(_bits(sc.image()), _bits(o["rgba"])), (k, frame)
+            assert np.array_equal(bits(sc.image()), bits(o["rgba"])), (k, frame)
         r.destroy()
     hs.destroy(); sc.release()
 
@@ -486,7 +406,7 @@ def test_hide_everything_and_shared_selection(gs, ob, device, stream):
     fr = sc.render(r1, hide=hs)
     assert fr.visible == 0 and fr.pairs == 0
     img = sc.image()
-    assert np.array_equal(_bits(img), _bits(sc.oracle(sc.twin_pods(np.ones(n, bool)))["rgba"]))
+    assert np.array_equal(bits(img), bits(sc.oracle(sc.twin_pods(np.ones(n, bool)))["rgba"]))
     assert (img[..., :3] == np.array([0.25, 0.5, 0.75], f32)).all()
     # two renderers share one selection; a change reaches both
     hidden = np.random.default_rng(3).random(n) < 0.5
@@ -540,7 +460,7 @@ def test_hide_with_aux_planes(gs, ob, device, stream):
     cam0 = ob.Camera.from_buffer_copy(bytes(sc.ocam))
     cam0.background[:] = [0.0, 0.0, 0.0]
     o_depth = ob.blend(p, o["idx"], o["ranges"], cam0, gt=sc.ogt)[..., 0]
-    assert np.array_equal(_bits(depth.download(stream, f32).reshape(H, W)), _bits(o_depth))
+    assert np.array_equal(bits(depth.download(stream, f32).reshape(H, W)), bits(o_depth))
     pk = pick.download(stream, np.uint32)
     picked = pk[pk != gs.PICK_NONE]
     assert len(picked) and (picked < n).all() and not hidden[picked].any(), "pick names a hidden Gaussian"
@@ -550,11 +470,6 @@ def test_hide_with_aux_planes(gs, ob, device, stream):
 # ------------------------------------------------------------------------------------------------
 # 6. tint
 # ------------------------------------------------------------------------------------------------
-
-def _tint32(c, a, t):
-    a, t = f32(a), f32(t)
-    return (f32(1.0) - a) * c.astype(f32) + a * t
-
 
 @pytest.mark.parametrize("sh,cov", [(0, 0), (3, 0)])
 def test_tint(gs, ob, device, stream, sh, cov):
@@ -571,7 +486,7 @@ def test_tint(gs, ob, device, stream, sh, cov):
     for rgba in [(1.0, 0.25, 0.0, 0.5), (0.3, 0.7, 0.9, 0.37), (0.3, 0.7, 0.9, 1.0), (0.3, 0.7, 0.9, 0.0)]:
         def recolour(p, rgba=rgba, sel=tinted):
             for ch, t in zip("rgb", rgba[:3]):
-                p[ch][sel] = _tint32(p[ch][sel], rgba[3], t)
+                p[ch][sel] = tint32(p[ch][sel], rgba[3], t)
         o = sc.oracle(sc.pods, recolour=recolour)
         sc.poison()
         sc.render(r, tint=ts, tint_rgba=rgba)
@@ -579,9 +494,9 @@ def test_tint(gs, ob, device, stream, sh, cov):
         keep = tiles > 0
         assert np.array_equal(tiles, o["tiles"])
         assert np.array_equal(proj[keep].tobytes(), o["proj"][keep].tobytes()), rgba
-        assert np.array_equal(_bits(sc.image()), _bits(o["rgba"])), rgba
+        assert np.array_equal(bits(sc.image()), bits(o["rgba"])), rgba
         if rgba[3] == 0.0:
-            assert np.array_equal(_bits(sc.image()), _bits(img_plain))
+            assert np.array_equal(bits(sc.image()), bits(img_plain))
             assert np.array_equal(proj[keep].tobytes(), proj_plain[keep].tobytes())
         if rgba[3] == 1.0:
             for ch, t in zip("rgb", rgba[:3]):
@@ -592,12 +507,12 @@ def test_tint(gs, ob, device, stream, sh, cov):
 
     def recolour(p):
         for ch, t in zip("rgb", rgba[:3]):
-            p[ch][tinted] = _tint32(p[ch][tinted], rgba[3], t)
+            p[ch][tinted] = tint32(p[ch][tinted], rgba[3], t)
     o = sc.oracle(sc.twin_pods(hidden), recolour=recolour)
     sc.poison()
     fr = sc.render(r, hide=hs, tint=ts, tint_rgba=rgba)
     assert fr.visible == int((o["tiles"] > 0).sum())
-    assert np.array_equal(_bits(sc.image()), _bits(o["rgba"]))
+    assert np.array_equal(bits(sc.image()), bits(o["rgba"]))
     proj, tiles = r.download_projected(n)
     assert not tiles[hidden].any() and np.array_equal(tiles, o["tiles"])
     r.destroy(); plain.destroy(); ts.destroy(); hs.destroy(); sc.release()
@@ -633,7 +548,7 @@ def test_plain_case_is_the_aux_frame(gs, ob, device, stream):
             f1 = r1.wait_frame()
         assert f1.launches == f0.launches + extra, (variant, f1.launches, f0.launches)
         assert f1.pairs == f0.pairs and f1.visible == f0.visible
-        assert np.array_equal(_bits(sc.image()), _bits(img0))
+        assert np.array_equal(bits(sc.image()), bits(img0))
     ref.release(); r0.destroy(); r1.destroy(); hs.destroy(); sc.release()
 
 
@@ -676,5 +591,5 @@ def test_unhiding_after_mostly_hidden_frames(gs, ob, device, stream):
     sc.poison()
     fr = sc.render(r, hide=hs, check=True)
     assert fr.flags == 0 and fr.pairs == fp.pairs and fr.visible == fp.visible
-    assert np.array_equal(_bits(sc.image()), _bits(want))
+    assert np.array_equal(bits(sc.image()), bits(want))
     r.destroy(); plain.destroy(); hs.destroy(); sc.release()

@@ -9,13 +9,12 @@ import pytest
 
 import edit_np
 import stats_np
-from test_gpu_edit import ALL_LAYOUTS, _edit, _scene, _want
-from test_gpu_history import FOUR_LAYOUTS, N, _masks, _pods, _rows, _selection
+from records import SELECT_OPS, buffer_rows, edited_pods, np_op, sample_edit, selection_from_mask
+from scenes import ALL_LAYOUTS, FOUR_LAYOUTS, N, history_masks, pod_rows
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-OPS = ["set", "or", "and", "andnot", "xor"]
 # rotation + translation + non-uniform scale
 Q = np.array([0.3, -0.5, 0.2, 0.7])
 MT = dict(pos=(0.5, -0.25, 1.5), rot=tuple((Q / np.linalg.norm(Q)).astype(f32)), scale=(1.25, 0.75, 2.0))
@@ -26,23 +25,19 @@ _VALUES = {}
 
 
 def _values(gs, sh, cov, n=N, seed=3, rows=None):
-    """the nine attributes of the records of _pods(...) under MT / REF; computed once per layout and length"""
+    """the nine attributes of the records of pod_rows(...) under MT / REF; computed once per layout and length"""
     key = (sh, cov, n, seed)
     if rows is not None:
         return stats_np.attributes(sh, cov, rows, ref=REF, **MT)
     if key not in _VALUES:
-        v = stats_np.attributes(sh, cov, _pods(gs, sh, cov, n, seed), ref=REF, **MT) if n else np.zeros((0, 9), f32)
+        v = stats_np.attributes(sh, cov, pod_rows(gs, sh, cov, n, seed), ref=REF, **MT) if n else np.zeros((0, 9), f32)
         v.setflags(write=False)
         _VALUES[key] = v
     return _VALUES[key]
 
 
 def _rows_of(gs, sh, cov, n):
-    return _pods(gs, sh, cov, n) if n else np.zeros((0, gs.GaussianPod(sh, cov).size), np.uint8)
-
-
-def _np_op(d, s, op):
-    return {"set": s, "or": d | s, "and": d & s, "andnot": d & ~s, "xor": d ^ s}[op]
+    return pod_rows(gs, sh, cov, n) if n else np.zeros((0, gs.GaussianPod(sh, cov).size), np.uint8)
 
 
 def _check_stats(got, want, tag):
@@ -91,12 +86,12 @@ def _ranges(v):
 def test_stats_equal_the_restatement(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
     assert pod.size == edit_np.pod_bytes(sh, cov)
-    buf = gs.GaussiansBuffer.new_with_pods(device, pod, _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, pod, pod_rows(gs, sh, cov))
     mt = gs.model_transform_pod(**MT)
     vals = _values(gs, sh, cov)
     assert not np.isfinite(vals[5:8, :3]).any(), "the planted NaN and inf rows reach the attributes"
-    for name, mask in _masks():
-        sel = _selection(gs, device, stream, mask) if mask is not None else None
+    for name, mask in history_masks():
+        sel = selection_from_mask(gs, device, stream, mask)
         got = buf.stats(stream, sel, mt, REF)
         _check_stats(got, stats_np.stats(vals, mask), (sh, cov, name))
         again = buf.stats(stream, sel, mt, REF)
@@ -104,7 +99,7 @@ def test_stats_equal_the_restatement(gs, device, stream, sh, cov):
         if sel is not None:
             sel.destroy()
     # the default transform and the origin as reference, through the same arithmetic
-    plain = stats_np.attributes(sh, cov, _pods(gs, sh, cov))
+    plain = stats_np.attributes(sh, cov, pod_rows(gs, sh, cov))
     _check_stats(buf.stats(stream), stats_np.stats(plain), (sh, cov, "defaults"))
     st = buf.stats(stream, None, mt, REF)
     want = stats_np.stats(vals)
@@ -123,7 +118,7 @@ def test_small_buffers(gs, device, stream, n):
         assert buf.len() == n
         vals = _values(gs, sh, cov, n)
         mask = np.random.default_rng(n).random(n) < 0.5
-        sel = _selection(gs, device, stream, mask)
+        sel = selection_from_mask(gs, device, stream, mask)
         for s, m in ((None, None), (sel, mask)):
             _check_stats(buf.stats(stream, s, mt, REF), stats_np.stats(vals, m), (sh, cov, n, m is not None))
             for attr in (stats_np.Y, stats_np.GREEN, stats_np.SIZE2, stats_np.DIST2):
@@ -135,10 +130,10 @@ def test_small_buffers(gs, device, stream, n):
             assert st.count == 0 and not st.finite.any() and not st.sum.any()
             assert np.isposinf(st.min).all() and np.isneginf(st.max).all()
         for attr in (stats_np.X, stats_np.OPACITY, stats_np.SIZE2):
-            for op in OPS:
+            for op in SELECT_OPS:
                 sel.upload(stream, mask)
                 sel.select_attribute(stream, buf, attr, 0.25, 2.0, op, mt, REF)
-                want = stats_np.pack_bits(_np_op(mask, stats_np.in_range(vals[:, attr], 0.25, 2.0), op))
+                want = stats_np.pack_bits(np_op(mask, stats_np.in_range(vals[:, attr], 0.25, 2.0), op))
                 assert np.array_equal(sel.download_words(stream), want), (sh, cov, n, attr, op)
         sel.destroy()
         buf.destroy()
@@ -151,11 +146,11 @@ def test_small_buffers(gs, device, stream, n):
 @pytest.mark.parametrize("sh,cov", FOUR_LAYOUTS)
 def test_histograms_equal_the_restatement(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
-    buf = gs.GaussiansBuffer.new_with_pods(device, pod, _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, pod, pod_rows(gs, sh, cov))
     mt = gs.model_transform_pod(**MT)
     vals = _values(gs, sh, cov)
-    mask = _masks()[0][1]
-    sel = _selection(gs, device, stream, mask)
+    mask = history_masks()[0][1]
+    sel = selection_from_mask(gs, device, stream, mask)
     count = int(mask.sum())
     clamped = 0
     for attr in range(stats_np.ATTR_COUNT):
@@ -191,7 +186,7 @@ def test_histograms_equal_the_restatement(gs, device, stream, sh, cov):
 @pytest.mark.parametrize("sh,cov", ALL_LAYOUTS)
 def test_select_attribute_equals_the_restatement(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
-    buf = gs.GaussiansBuffer.new_with_pods(device, pod, _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, pod, pod_rows(gs, sh, cov))
     mt = gs.model_transform_pod(**MT)
     vals = _values(gs, sh, cov)
     pre = np.random.default_rng(7).random(N) < 0.4
@@ -202,11 +197,11 @@ def test_select_attribute_equals_the_restatement(gs, device, stream, sh, cov):
         lo, hi = _ranges(v)[1]
         hit = stats_np.in_range(v, lo, hi)
         assert 0 < hit.sum() < N
-        for op in OPS:
+        for op in SELECT_OPS:
             sel.upload(stream, pre)
             sel.select_attribute(stream, buf, attr, lo, hi, op, mt, REF)
             got = sel.download_words(stream)
-            assert np.array_equal(got, stats_np.pack_bits(_np_op(pre, hit, op))), (attr, op)
+            assert np.array_equal(got, stats_np.pack_bits(np_op(pre, hit, op))), (attr, op)
             assert got[-1] & ~tail == 0
         # lo > hi selects nothing; -inf .. +inf selects every value that is not NaN
         sel.upload(stream, pre)
@@ -229,12 +224,12 @@ def test_select_attribute_equals_the_restatement(gs, device, stream, sh, cov):
 @pytest.mark.parametrize("sh,cov", FOUR_LAYOUTS)
 def test_dist2_range_is_select_sphere(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
-    buf = gs.GaussiansBuffer.new_with_pods(device, pod, _pods(gs, sh, cov))
+    buf = gs.GaussiansBuffer.new_with_pods(device, pod, pod_rows(gs, sh, cov))
     mt = gs.model_transform_pod(**MT)
     a, b = gs.Selection(device, N), gs.Selection(device, N)
     pre = np.random.default_rng(8).random(N) < 0.5
     for r in (f32(0.0), f32(4.0), f32(20.0), f32(40.5), f32(1e6)):
-        for op in OPS:
+        for op in SELECT_OPS:
             a.upload(stream, pre)
             b.upload(stream, pre)
             a.select_sphere(stream, buf, mt, REF, float(r), op)
@@ -254,20 +249,20 @@ def test_dist2_range_is_select_sphere(gs, device, stream, sh, cov):
 def test_passes_are_ordered_behind_an_edit_on_another_stream(gs, device, stream):
     sh, cov = 0, 0
     pod = gs.GaussianPod(sh, cov)
-    orig = _pods(gs, sh, cov)
+    orig = pod_rows(gs, sh, cov)
     mask = np.random.default_rng(4).random(N) < 0.3
     s1, s2 = stream, device.create_stream()
     mt = gs.model_transform_pod(**MT)
-    sel, out = _selection(gs, device, s1, mask), gs.Selection(device, N)
+    sel, out = selection_from_mask(gs, device, s1, mask), gs.Selection(device, N)
     s1.synchronize()
-    edited = _want(gs, sh, cov, orig.reshape(-1), mask, 15).reshape(N, pod.size)
+    edited = edited_pods(gs, sh, cov, orig.reshape(-1), mask, 15).reshape(N, pod.size)
     vals = _values(gs, sh, cov, rows=edited)
     before = _values(gs, sh, cov)
     assert (vals[mask][:, [0, 3, 6, 7]] != before[mask][:, [0, 3, 6, 7]]).any(axis=0).all(), "the edit changes the attributes"
     # each pass on stream 2 right behind the edit on stream 1, no host synchronisation in between
     for what in ("stats", "histogram", "select"):
         buf = gs.GaussiansBuffer.new_with_pods(device, pod, orig)
-        buf.edit(s1, sel, _edit(gs, 15))
+        buf.edit(s1, sel, sample_edit(gs, 15))
         if what == "stats":
             _check_stats(buf.stats(s2, sel, mt, REF), stats_np.stats(vals, mask), what)
         elif what == "histogram":
@@ -280,7 +275,7 @@ def test_passes_are_ordered_behind_an_edit_on_another_stream(gs, device, stream)
             assert np.array_equal(got, stats_np.pack_bits(stats_np.in_range(vals[:, stats_np.X], -1.0, 1.0)))
             assert not np.array_equal(got, stats_np.pack_bits(stats_np.in_range(before[:, stats_np.X], -1.0, 1.0)))
         s1.synchronize()
-        assert np.array_equal(_rows(buf, s1), edited)
+        assert np.array_equal(buffer_rows(buf, s1), edited)
         buf.destroy()
     s2.synchronize()
     sel.destroy(); out.destroy()
@@ -294,7 +289,7 @@ def test_passes_are_ordered_behind_an_edit_on_another_stream(gs, device, stream)
 @pytest.mark.parametrize("sh,cov", FOUR_LAYOUTS)
 def test_delete_the_faint_gaussians(gs, device, stream, sh, cov):
     pod = gs.GaussianPod(sh, cov)
-    rows = _pods(gs, sh, cov)
+    rows = pod_rows(gs, sh, cov)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, rows)
     sel = gs.Selection(device, N)
     sel.select_attribute(stream, buf, gs.ATTR_OPACITY, 0.0, 0.1)
@@ -302,8 +297,8 @@ def test_delete_the_faint_gaussians(gs, device, stream, sh, cov):
     assert 0 < faint.sum() < N and sel.count(stream) == int(faint.sum())
     kept = buf.extract(stream, sel, invert=True)
     assert kept.len() == int((~faint).sum())
-    assert np.array_equal(_rows(kept, stream), rows[~faint])
-    assert np.array_equal(_rows(buf, stream), rows)
+    assert np.array_equal(buffer_rows(kept, stream), rows[~faint])
+    assert np.array_equal(buffer_rows(buf, stream), rows)
     kept.destroy(); sel.destroy(); buf.destroy()
 
 
@@ -314,10 +309,10 @@ def test_delete_the_faint_gaussians(gs, device, stream, sh, cov):
 def test_argument_errors_change_nothing(gs, device, stream):
     sh, cov = 0, 0
     pod = gs.GaussianPod(sh, cov)
-    rows = _pods(gs, sh, cov)
+    rows = pod_rows(gs, sh, cov)
     buf = gs.GaussiansBuffer.new_with_pods(device, pod, rows)
     mask = np.random.default_rng(9).random(N) < 0.3
-    sel, short = _selection(gs, device, stream, mask), gs.Selection(device, N - 1)
+    sel, short = selection_from_mask(gs, device, stream, mask), gs.Selection(device, N - 1)
     other = gs.Device(0)          # a second device object: its selections belong to another device
     foreign = gs.Selection(other, N)
     words = sel.download_words(stream)
@@ -378,7 +373,7 @@ def test_argument_errors_change_nothing(gs, device, stream):
     assert select(sl=short._h) == bad and select(sl=foreign._h) == bad
     assert np.array_equal(sel.download_words(stream), words)
     assert not short.download_words(stream).any()
-    assert np.array_equal(_rows(buf, stream), rows)
+    assert np.array_equal(buffer_rows(buf, stream), rows)
     # the Python layer raises the library's error for what only the library can know
     with pytest.raises(gs.InvalidArgumentError):
         buf.stats(stream, short)

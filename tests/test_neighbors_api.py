@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import neighbors_np
+from scenes import hostile_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -182,9 +183,8 @@ def test_restatement_is_symmetric():
 
 def test_positions_are_those_of_the_stats_restatement(gs):
     import stats_np
-    from test_gpu_edit import _scene
     pod = gs.GaussianPod(1, 2)
-    rows = np.asarray(pod.from_gaussian(_scene(40))).reshape(40, pod.size)
+    rows = np.asarray(pod.from_gaussian(hostile_scene(40))).reshape(40, pod.size)
     mt = dict(pos=(0.5, -0.25, 1.5), rot=(0.0, 0.0, 0.0, 1.0), scale=(1.25, 0.75, 2.0))
     pw = neighbors_np.positions(rows, **mt)
     want = stats_np.attributes(1, 2, rows, **mt)[:, :3]

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+from scenes import synthetic_ply
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 EPS = 1e-4  # tests/common/assert.rs:4
 
@@ -149,32 +151,6 @@ def test_vertex_count_larger_than_the_file_is_rejected_up_front(gs):
         gs.PlyGaussians.read_from(ascii_hdr)
 
 
-def _synthetic_ply(n, seed=5):
-    """PlyGaussianPod records with trained-scene statistics (log-scales around -4, logit opacities,
-    unnormalised wxyz quaternions, f_dc / f_rest), plus hostile values in the first records."""
-    import wgpu_3dgs_core_amd as gs
-    rng = np.random.default_rng(seed)
-    p = np.zeros(n, dtype=gs.PLY_GAUSSIAN_DTYPE)
-    p["pos"] = rng.uniform(-10, 10, (n, 3)).astype(np.float32)
-    p["normal"] = rng.standard_normal((n, 3)).astype(np.float32)
-    p["color"] = (rng.standard_normal((n, 3)) * 1.2).astype(np.float32)
-    p["sh"] = (rng.standard_normal((n, 45)) * 0.1).astype(np.float32)
-    p["alpha"] = (rng.standard_normal(n) * 4.0).astype(np.float32)
-    p["scale"] = (rng.standard_normal((n, 3)) * 1.5 - 4.0).astype(np.float32)
-    p["rot"] = rng.standard_normal((n, 4)).astype(np.float32)
-    hostile = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 88.72283, 88.72284, 89.0, -103.97207, -103.97208, -104.5,
-                        -87.4, -95.0, -100.0, -103.28, 1e-30, -1e-30, 50.0, -50.0, 1e30, -1e30], dtype=np.float32)
-    k = min(n, len(hostile))
-    p["scale"][:k, 0] = hostile[:k]
-    p["alpha"][:k] = hostile[:k]
-    p["color"][:k, 1] = hostile[:k]
-    if n > 30:
-        p["rot"][25] = 0.0            # zero quaternion: 0 / 0 -> NaN on both sides
-        p["rot"][26] = (np.inf, 1, 2, 3)
-        p["rot"][27] = 1e-30          # squares underflow
-    return p
-
-
 def test_gs_expf_is_glibc_expf(gs):
     """gs_expf (csrc/gs_convert.h, used by host AND device from_ply) restates the algorithm of glibc's
     expf: same bits as libm on edge cases and on random arguments over the whole range."""
@@ -200,7 +176,7 @@ def test_from_ply_one_million_matches_oracle_libm(gs, ob):
     alpha byte they feed) would not be an error — the reference's own tolerance is 1e-4
     (tests/common/assert.rs:4) — but none occurs on this input."""
     n = 1_000_000
-    p = _synthetic_ply(n)
+    p = synthetic_ply(n)
     g = gs.gaussian_from_ply(p)
     o = ob.gaussians_from_ply(p)
     for f in ("pos", "sh"):

@@ -14,8 +14,10 @@ import sys
 import numpy as np
 import pytest
 
+import cpp_test
 import edit_np
 import stats_np
+from scenes import ALL_LAYOUTS, hostile_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,7 +25,6 @@ ENTRIES = ["gs_gaussians_buffer_stats", "gs_gaussians_buffer_histogram", "gs_sel
 TITLE = "Attribute statistics, histograms and select by attribute range"
 ATTRS = ["GS_ATTR_X", "GS_ATTR_Y", "GS_ATTR_Z", "GS_ATTR_RED", "GS_ATTR_GREEN", "GS_ATTR_BLUE", "GS_ATTR_OPACITY",
          "GS_ATTR_SIZE2", "GS_ATTR_DIST2", "GS_ATTR_COUNT"]
-ALL_LAYOUTS = [(s, c) for s in range(4) for c in range(3)]
 f32 = np.float32
 
 
@@ -208,11 +209,10 @@ def _key(v):
 
 @pytest.mark.parametrize("sh,cov", ALL_LAYOUTS)
 def test_restatement_matches_a_plain_loop(gs, sh, cov):
-    from test_gpu_edit import _scene
     n = 100
     pod = gs.GaussianPod(sh, cov)
     assert pod.size == edit_np.pod_bytes(sh, cov)
-    rows = np.asarray(pod.from_gaussian(_scene(n))).reshape(n, pod.size)
+    rows = np.asarray(pod.from_gaussian(hostile_scene(n))).reshape(n, pod.size)
     got = stats_np.attributes(sh, cov, rows, ref=REF, **MT)
     with np.errstate(all="ignore"):
         want = np.array([_loop_attributes(sh, cov, rows[i].tobytes()) for i in range(n)], f32)
@@ -262,10 +262,9 @@ def test_histogram_equals_numpy_where_both_are_exact(gs, attr):
     """lo = 0, hi = 1, bins = 256 on a byte / 255: v 256 is exact in binary32 (8 bits times a power of two), so the slot is
     floor(256 b / 255) rounded from the nearest binary32 of b / 255 — np.histogram with the edges k / 256 (exact) counts the
     same values per bin, except that it puts v == 1 into the last bin, which here is the `above` slot."""
-    from test_gpu_edit import _scene
     n = 100
     pod = gs.GaussianPod(3, 2)
-    rows = np.asarray(pod.from_gaussian(_scene(n))).reshape(n, pod.size)
+    rows = np.asarray(pod.from_gaussian(hostile_scene(n))).reshape(n, pod.size)
     v = stats_np.attributes(3, 2, rows)[:, attr]
     mask = np.random.default_rng(3).random(n) < 0.4
     h = stats_np.histogram(v, 0.0, 1.0, 256, mask)
@@ -277,12 +276,5 @@ def test_histogram_equals_numpy_where_both_are_exact(gs, attr):
         assert h[row].sum() == int(m.sum())
 
 
-def _build():
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    import wgpu_3dgs_core_amd  # noqa: F401  (builds the library if needed)
-    return ge.build_cpp_stats_test()
-
-
 def test_cpp_stats_compiles():
-    assert os.path.exists(_build())
+    assert os.path.exists(cpp_test.build("stats"))
