@@ -373,6 +373,15 @@ pub struct gs_image_metrics {
     pub ssim_finite: [u64; 3],
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_components_info {
+    pub points: u32,
+    pub components: u32,
+    pub largest: u32,
+    pub largest_label: u32,
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -537,6 +546,9 @@ extern "C" {
     pub fn gs_gzip_fast(bytes: *const c_void, len: usize, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
     pub fn gs_buffer_gzip_fast(b: *mut gs_buffer, s: *mut gs_stream, offset: usize, len: usize, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
     pub fn gs_gaussians_buffer_export_spz_fast(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, options: *const gs_spz_options, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;
+    pub fn gs_gaussians_buffer_components(g: *mut gs_gaussians_buffer, s: *mut gs_stream, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, labels_out: *mut gs_buffer, sizes_out: *mut gs_buffer, info_out: *mut gs_buffer) -> gs_status;
+    pub fn gs_select_components(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, min_size: u32, max_size: u32, op: u32) -> gs_status;
+    pub fn gs_select_connected(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, seeds: *const gs_selection, op: u32) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

@@ -1237,6 +1237,65 @@ gs_status gs_buffer_gzip_fast(gs_buffer *b, gs_stream *s, size_t offset, size_t 
 gs_status gs_gaussians_buffer_export_spz_fast(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *sel, int32_t invert,
                                               const gs_spz_options *options, void *out, size_t capacity, size_t *bytes_out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Clusters: connected components within a radius, select by cluster size (DESIGN.md 3.16;     */
+/* no reference item): "remove small clusters" and "select all of what I clicked"              */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  pw_i, POINT and NEIGHBOUR are those of 3.11 above, unchanged: `among`,
+ * the NULL transform, the radius test in binary32 with r r rounded once on the host.  G is the graph on the points whose edges
+ * are the neighbour pairs; the relation is symmetric, so its components are well defined.  L_i = the smallest caller index of a
+ * point in i's component, GS_COMPONENT_NONE where i is no point.  S_i = the number of points in i's component (a singleton
+ * has 1), 0 where i is no point.  All of these are integers that depend on neither the traversal, the grid, the order in which
+ * lanes win atomics, nor the run: they are bit-defined.
+ *
+ * Cost: the sort and the traversal of 3.11 WITHOUT a cap (every candidate pair is visited once), a lock-free union-find over
+ * the passing pairs, then one pass per plane.  A radius that puts most of the scene inside one ball is quadratic by
+ * definition, as in 3.11; there is no cap and no approximate mode: that choice is the caller's.  The three calls only ENQUEUE.
+ * They share the buffer's scratch with the calls of 3.11 and grow it to 44 bytes per Gaussian (28 of 3.11 and four more words:
+ * parent, root, smallest index and size per root); a call on another stream waits for the previous user of that scratch on
+ * the device.  Calls on ONE buffer from several host threads at once are the caller's to order. */
+#define GS_COMPONENT_NONE 0xFFFFFFFFu
+typedef struct gs_components_info {
+    uint32_t points;         /* the number of points */
+    uint32_t components;     /* the number of i with L_i == i */
+    uint32_t largest;        /* the maximum of S_i; 0 with no point */
+    uint32_t largest_label;  /* the smallest label among the components of that size; GS_COMPONENT_NONE with no point */
+} gs_components_info;
+
+/* labels_out[i] = L_i and sizes_out[i] = S_i, one uint32_t per Gaussian in caller order, into device planes of at least 4 n
+ * bytes; info_out receives the gs_components_info of the graph, 16 bytes (no reference item).  Each of the
+ * three may be NULL, not all of them; bytes behind 4 n (behind 16 for the info) stay as they were.  Read them back with
+ * gs_buffer_download.  Only ENQUEUES on `s` (NULL: the device's internal stream), ordered behind an edit or restore enqueued on
+ * another stream.  A buffer of length 0 is valid and launches nothing: the info is set to that of a graph without points.
+ * GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with planes and info untouched, for a null buffer, three null
+ * outputs, a radius that is negative, NaN or infinite or whose square is not finite in binary32, a plane or info buffer that
+ * is too small or on another device, a selection whose length differs from the buffer's or that belongs to another device, a
+ * buffer of more than 0xfffffff0 Gaussians. */
+gs_status gs_gaussians_buffer_components(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *among,
+                                         const gs_model_transform_pod *model_transform, float radius, gs_buffer *labels_out,
+                                         gs_buffer *sizes_out, gs_buffer *info_out);
+/* sel = sel op {i : i is a point and min_size <= S_i <= max_size} (no reference item): max_size = m - 1 selects
+ * every cluster smaller than m — the floater clumps a neighbour count cannot see.  A Gaussian that is not a point is never
+ * selected, not even with min_size = 0; min_size > max_size selects nothing; max_size = UINT32_MAX is "no upper limit".  Only
+ * ENQUEUES on `s` (NULL: the device's internal stream); the mask is written word-wise as by gs_select_sphere, bits at positions
+ * >= n stay 0; ordered behind an edit or restore enqueued on another stream; a buffer of length 0 only changes the
+ * selection's generation.  GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with the selection unchanged, for a null
+ * selection or buffer, an unknown op, a radius that is negative, NaN or infinite or whose square is not finite in binary32, a
+ * selection (`sel` or `among`) whose length differs from the buffer's or that belongs to another device, a buffer of more than
+ * 0xfffffff0 Gaussians. */
+gs_status gs_select_components(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *gaussians, const gs_selection *among,
+                               const gs_model_transform_pod *model_transform, float radius, uint32_t min_size, uint32_t max_size,
+                               gs_select_op op);
+/* sel = sel op {i : i is a point and its component contains a point j with bit j of `seeds` set}
+ * (no reference item): a picked index (gs_select_range(idx, 1)) grows to the whole object it belongs to.
+ * A seed that is no point seeds nothing; empty seeds select nothing.  `seeds` may be `sel` itself, which grows a selection to whole clusters: the seeds are
+ * read completely before `sel` is written.  Enqueueing, ordering, the mask and the errors are those of gs_select_components,
+ * with `seeds` (not NULL) checked as `among` is. */
+gs_status gs_select_connected(gs_selection *sel, gs_stream *s, gs_gaussians_buffer *gaussians, const gs_selection *among,
+                              const gs_model_transform_pod *model_transform, float radius, const gs_selection *seeds,
+                              gs_select_op op);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

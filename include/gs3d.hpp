@@ -389,6 +389,12 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // enqueues.  counts holds at least 4 len() bytes; read it back with Buffer::download.
     void neighbor_counts(Stream &s, float radius, uint32_t cap, Buffer &counts, const Selection *among = nullptr,
                          const gs_model_transform_pod *mt = nullptr);
+    // the connected components of the neighbour graph within radius (gs3d.h gs_gaussians_buffer_components, DESIGN.md 3.16;
+    // no reference item); only enqueues.  labels[i] = the smallest index of i's component (GS_COMPONENT_NONE: no point),
+    // sizes[i] = its number of points (0: no point), 4 len() bytes each; info = one gs_components_info.  Each may be nullptr,
+    // not all three.
+    void components(Stream &s, float radius, Buffer *labels, Buffer *sizes, Buffer *info, const Selection *among = nullptr,
+                    const gs_model_transform_pod *mt = nullptr);
     // the .spz file image of the records of sel (nullptr: all; invert: of its complement), the payload deflated on the device
     // (gs3d.h gs_gaussians_buffer_export_spz_fast; no reference item); options == nullptr: the defaults.
     // Inflates to what gs_gaussians_buffer_export_spz_decompressed gives; blocking.
@@ -436,6 +442,20 @@ class Selection {
     void select_neighbors(Stream &s, GaussiansBuffer<G> &g, float radius, uint32_t min_count = 0, uint32_t max_count = UINT32_MAX,
                           const Selection *among = nullptr, const gs_model_transform_pod *mt = nullptr, gs_select_op op = GS_SEL_SET) {
         check(gs_select_neighbors(h_, s.raw(), g.raw(), among ? among->raw() : nullptr, mt, radius, min_count, max_count, op));
+    }
+    // sel = sel op {i : min_size <= S_i <= max_size}, S_i the number of points in i's connected component within radius
+    // (gs_select_components; no reference item); only enqueues.  max_size = m - 1: every cluster smaller than m
+    template <class G>
+    void select_components(Stream &s, GaussiansBuffer<G> &g, float radius, uint32_t min_size = 1, uint32_t max_size = UINT32_MAX,
+                           const Selection *among = nullptr, const gs_model_transform_pod *mt = nullptr, gs_select_op op = GS_SEL_SET) {
+        check(gs_select_components(h_, s.raw(), g.raw(), among ? among->raw() : nullptr, mt, radius, min_size, max_size, op));
+    }
+    // sel = sel op {i : i's connected component within radius holds a Gaussian of seeds} (gs_select_connected, DESIGN.md 3.16;
+    // no reference item); only enqueues.  seeds may be *this: the selection grows to whole clusters
+    template <class G>
+    void select_connected(Stream &s, GaussiansBuffer<G> &g, float radius, const Selection &seeds, const Selection *among = nullptr,
+                          const gs_model_transform_pod *mt = nullptr, gs_select_op op = GS_SEL_SET) {
+        check(gs_select_connected(h_, s.raw(), g.raw(), among ? among->raw() : nullptr, mt, radius, seeds.raw(), op));
     }
     // sel = sel op {i : lo <= v_i <= hi}, v the GS_CONTRIB_* value of record i of `contrib` (gs_select_contribution,
     // DESIGN.md 3.5c); only enqueues
@@ -510,6 +530,12 @@ template <class G>
 inline void GaussiansBuffer<G>::neighbor_counts(Stream &s, float radius, uint32_t cap, Buffer &counts, const Selection *among,
                                                 const gs_model_transform_pod *mt) {
     check(gs_gaussians_buffer_neighbor_counts(h_, s.raw(), among ? among->raw() : nullptr, mt, radius, cap, counts.raw()));
+}
+template <class G>
+inline void GaussiansBuffer<G>::components(Stream &s, float radius, Buffer *labels, Buffer *sizes, Buffer *info, const Selection *among,
+                                           const gs_model_transform_pod *mt) {
+    check(gs_gaussians_buffer_components(h_, s.raw(), among ? among->raw() : nullptr, mt, radius, labels ? labels->raw() : nullptr,
+                                         sizes ? sizes->raw() : nullptr, info ? info->raw() : nullptr));
 }
 
 template <class G>

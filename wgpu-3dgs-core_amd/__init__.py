@@ -797,6 +797,9 @@ def pack_device(device, stream, pod, gaussians_buffer, count, pods_buffer):
 
 
 NEIGHBOR_COUNT_MAX = 0xFFFFFFFF      # UINT32_MAX: no cap / no upper limit
+COMPONENT_NONE = 0xFFFFFFFF          # GS_COMPONENT_NONE: the label of a Gaussian that is no point
+# gs_components_info: what GaussiansBuffer.components writes into its info Buffer
+COMPONENTS_INFO_DTYPE = np.dtype([("points", "<u4"), ("components", "<u4"), ("largest", "<u4"), ("largest_label", "<u4")])
 
 
 def _neighbor_args(radius, among, model_transform):
@@ -1165,6 +1168,32 @@ class GaussiansBuffer:
                 out.release()
             raise
         return out
+
+    def components(self, stream, radius, among=None, model_transform=None, labels_out=None, sizes_out=None, info_out=None):
+        """gs_gaussians_buffer_components: the connected components of the neighbour graph within
+        `radius` (points and neighbours as in neighbor_counts).  Returns three Buffers (labels, sizes, info): one uint32 per
+        Gaussian in caller order with the smallest index of its component (COMPONENT_NONE where it is no point), one with
+        the number of points of its component (0 where it is no point), and 16 bytes of COMPONENTS_INFO_DTYPE.  Only
+        enqueues; read them with Buffer.download.  A Buffer that is not given is allocated (and released again if the call
+        fails); one that is given holds at least 4 len() bytes (16 for the info)."""
+        radius, among, mt = _neighbor_args(radius, among, model_transform)
+        outs = [labels_out, sizes_out, info_out]
+        for name, b in zip(("labels_out", "sizes_out", "info_out"), outs):
+            if b is not None and not isinstance(b, Buffer):
+                raise TypeError("%s must be a Buffer or None, not %s" % (name, type(b).__name__))
+        own = []
+        try:
+            for k, size in enumerate((max(4 * self.len(), 4), max(4 * self.len(), 4), 16)):
+                if outs[k] is None:
+                    outs[k] = Buffer(self.device, size=size)
+                    own.append(outs[k])
+            _check(_L.gs_gaussians_buffer_components(self._h, stream._h if stream is not None else None, among, mt, radius,
+                                                     outs[0]._h, outs[1]._h, outs[2]._h))
+        except Exception:
+            for b in own:
+                b.release()
+            raise
+        return tuple(outs)
 
     def destroy(self):
         if self._h:
@@ -1696,6 +1725,37 @@ class Selection:
         op = select_op(op)
         _check(_L.gs_select_neighbors(self._h, stream._h if stream is not None else None, gaussians._h, among, mt, radius,
                                       int(min_count), int(max_count), op))
+
+    def select_components(self, stream, gaussians, radius, min_size=1, max_size=NEIGHBOR_COUNT_MAX, among=None,
+                          model_transform=None, op=SEL_SET):
+        """self = self op {i : min_size <= S_i <= max_size}, S_i = the number of points in the connected component of Gaussian
+        i of `gaussians` within `radius` (gs_select_components; see GaussiansBuffer.components); only
+        enqueues.  max_size = m - 1 selects every cluster smaller than m.  A Gaussian outside `among` or without a finite
+        world position is never selected; min_size > max_size selects nothing."""
+        if not isinstance(gaussians, GaussiansBuffer):
+            raise TypeError("gaussians must be a GaussiansBuffer, not %s" % type(gaussians).__name__)
+        radius, among, mt = _neighbor_args(radius, among, model_transform)
+        for name, v in (("min_size", min_size), ("max_size", max_size)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError("%s must be an integer, not %s" % (name, type(v).__name__))
+            if not 0 <= int(v) <= NEIGHBOR_COUNT_MAX:
+                raise ValueError("%s must be between 0 and 2^32 - 1, not %d" % (name, v))
+        op = select_op(op)
+        _check(_L.gs_select_components(self._h, stream._h if stream is not None else None, gaussians._h, among, mt, radius,
+                                       int(min_size), int(max_size), op))
+
+    def select_connected(self, stream, gaussians, radius, seeds, among=None, model_transform=None, op=SEL_SET):
+        """self = self op {i : the connected component of Gaussian i within `radius` holds a Gaussian of `seeds`}
+        (gs_select_connected); only enqueues.  `seeds` is a Selection of the buffer's length and may be
+        `self`, which grows a selection to whole clusters; a picked index becomes a seed through select_range(idx, 1)."""
+        if not isinstance(gaussians, GaussiansBuffer):
+            raise TypeError("gaussians must be a GaussiansBuffer, not %s" % type(gaussians).__name__)
+        radius, among, mt = _neighbor_args(radius, among, model_transform)
+        if not isinstance(seeds, Selection):
+            raise TypeError("seeds must be a Selection, not %s" % type(seeds).__name__)
+        op = select_op(op)
+        _check(_L.gs_select_connected(self._h, stream._h if stream is not None else None, gaussians._h, among, mt, radius,
+                                      seeds._h, op))
 
     def destroy(self):
         if self._h:

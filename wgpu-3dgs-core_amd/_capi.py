@@ -284,6 +284,9 @@ SIGNATURES = {
     "gs_gzip_fast": (i32, [vp, sz, vp, sz, vp]),
     "gs_buffer_gzip_fast": (i32, [vp, vp, sz, sz, vp, sz, vp]),
     "gs_gaussians_buffer_export_spz_fast": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
+    "gs_gaussians_buffer_components": (i32, [vp, vp, vp, vp, f32, vp, vp, vp]),
+    "gs_select_components": (i32, [vp, vp, vp, vp, vp, f32, u32, u32, i32]),
+    "gs_select_connected": (i32, [vp, vp, vp, vp, vp, f32, vp, i32]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

@@ -175,8 +175,9 @@ struct gs_gaussians_buffer {
     void *concat_offsets = nullptr;
     // gs_gaussians_buffer_stats / _histogram: the partial rows and the device result of the last call
     DevArray stats_scratch;
-    // gs_gaussians_buffer_neighbor_counts / gs_select_neighbors: keys, order, sorted positions and the
-    // sort's histograms of the last call; a call on another stream waits for nb_done before it reuses them
+    // gs_gaussians_buffer_neighbor_counts / gs_select_neighbors and the component calls (§3.16): keys,
+    // order, sorted positions, the union-find words and the sort's histograms of the last call; a call on another stream
+    // waits for nb_done before it reuses them
     DevArray nb_scratch, nb_ghist, nb_digit_totals;
     hipEvent_t nb_done = nullptr;
     hipStream_t nb_stream = nullptr;
@@ -295,6 +296,25 @@ gs_status extract_records(gs_gaussians_buffer *src, gs_stream *s, const gs_selec
 // gs_gaussians_buffer_create_concat_as (as_layout true: every source is converted to (dsh, dcov))
 gs_status concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels, uint32_t count, bool as_layout,
                          int dsh, int dcov, gs_gaussians_buffer **out, uint64_t *counts_out);
+
+// ---- gs_neighbors.hip ----
+gs_status check_neighbor_radius(float radius);
+// What the calls on the neighbour graph share: the cell keys of the points sorted (keys[s], NB_KEY_NONE
+// behind the points), vals[s] = the caller index in sorted slot s, the transformed positions gathered into that order, the
+// caller-order plane of the buffer's scratch and `extra_bytes` more behind it (256-byte aligned), all in g->nb_scratch.
+struct NeighborGrid {
+    const uint64_t *keys = nullptr;
+    const uint32_t *vals = nullptr;
+    const float *sx = nullptr, *sy = nullptr, *sz = nullptr;
+    uint32_t *plane = nullptr;
+    void *extra = nullptr;
+    uint32_t n = 0, nblocks = 0;      // nblocks: of 256 slots
+};
+gs_status neighbor_grid_enqueue(gs_gaussians_buffer *g, hipStream_t st, const gs_selection *among, const gs_model_transform_pod *mt,
+                                float radius, size_t extra_bytes, NeighborGrid &grid);
+// ... and behind the last kernel of the call, on every path: the next call on another stream waits until this one has left
+// the scratch
+gs_status neighbor_scratch_release(gs_gaussians_buffer *g, hipStream_t st);
 
 // ---- gs_deflate.hip ----
 // gs_buffer_gzip_fast without its checks: the gzip member of the `len` device bytes at `bytes` (any

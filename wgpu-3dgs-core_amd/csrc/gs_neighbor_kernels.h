@@ -10,14 +10,9 @@
 // Every operation is rounded (-ffp-contract=off).
 #pragma once
 
-#include "gs_device_common.h"
+#include "gs_neighbor_grid.h"
 
 namespace gs {
-
-constexpr uint32_t NB_CELL_BITS = 21u, NB_CELL_MAX = (1u << NB_CELL_BITS) - 1u;
-constexpr uint64_t NB_KEY_NONE = ~0ull;           // not a point: sorts behind every cell and is never visited
-constexpr uint32_t NB_NOT_A_POINT = 0xffffffffu;  // k_nb_count<true>: the count word of such a Gaussian (a count is < 2^32 - 16)
-constexpr uint32_t NB_SPAN = 6u;                  // the queries that search together lie in one row, at most this many cells apart
 
 // pw of Gaussian i and whether it is a point; `among` = its bit of the mask
 __device__ __forceinline__ bool nb_point(const uint32_t *__restrict__ aos, uint32_t pod_words, uint32_t i, const float M[16],
@@ -126,9 +121,6 @@ __global__ __launch_bounds__(256) void k_nb_gather(const uint32_t *__restrict__ 
     sy[s] = pw[1];
     sz[s] = pw[2];
 }
-
-__device__ __forceinline__ uint32_t nb_readlane(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ float nb_readlane_f(float v, uint32_t l) { return u2f(nb_readlane(f2u(v), l)); }
 
 // counts[vals[s]] = min(c, cap) for the point in sorted slot s; MARK: NB_NOT_A_POINT instead of 0 where there is no point.
 //

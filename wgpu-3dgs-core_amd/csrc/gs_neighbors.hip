@@ -10,29 +10,27 @@ using namespace gsh;
 // neighbour counts, select by neighbourhood
 // ------------------------------------------------------------------------------------------------
 
-static gs_status check_neighbor_radius(float radius) {
+gs_status gsh::check_neighbor_radius(float radius) {
     if (!(radius >= 0.0f) || !std::isfinite(radius) || !std::isfinite(radius * radius))
         return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the radius must be finite and not negative, with a finite square");
     return GS_OK;
 }
 
-// counts[i] = min(c_i, cap) in caller order on `st` (mark: gs::NB_NOT_A_POINT where i is no point); counts == nullptr: the
-// plane of the buffer's scratch, returned in *plane_out.  n > 0, arguments checked.
-static gs_status neighbor_counts_enqueue(gs_gaussians_buffer *g, hipStream_t st, const gs_selection *among,
-                                         const gs_model_transform_pod *mt, float radius, uint32_t cap, bool mark, uint32_t *counts,
-                                         uint32_t **plane_out) {
+// The front of every call on the neighbour graph, on `st`: reserve, bounding box, keys, sort, gather.  n > 0, arguments
+// checked.
+gs_status gsh::neighbor_grid_enqueue(gs_gaussians_buffer *g, hipStream_t st, const gs_selection *among, const gs_model_transform_pod *mt,
+                                     float radius, size_t extra_bytes, NeighborGrid &grid) {
     gs_device *dev = g->buf->dev;
     const uint32_t n = (uint32_t)gs_gaussians_buffer_len(g), pod_words = (uint32_t)(pod_stride(g) / 4);
     const uint32_t nblocks = (n + 255u) / 256u, pgrid = nblocks < 1024u ? nblocks : 1024u;
-    // [keys 0][vals 0][keys 1][vals 1][count plane][bbox partials][bbox]; the sorted positions (3 planes of n floats) take the
-    // key / value pair the sort did not leave its result in
+    // [keys 0][vals 0][keys 1][vals 1][count plane][bbox partials][bbox][extra]; the sorted positions (3 planes of n floats)
+    // take the key / value pair the sort did not leave its result in
     const size_t a8 = ((size_t)n * 8 + 255) & ~(size_t)255, a4 = ((size_t)n * 4 + 255) & ~(size_t)255;
     const size_t part = ((size_t)pgrid * 24 + 255) & ~(size_t)255;
-    GS_TRY(dev_reserve(g->nb_scratch, 2 * (a8 + a4) + a4 + part + 256));
+    GS_TRY(dev_reserve(g->nb_scratch, 2 * (a8 + a4) + a4 + part + 256 + extra_bytes));
     char *base = (char *)g->nb_scratch.ptr;
     void *k2[2] = {base, base + a8 + a4};
     void *v2[2] = {base + a8, base + 2 * a8 + a4};
-    uint32_t *plane = (uint32_t *)(base + 2 * (a8 + a4));
     float *partial = (float *)(base + 2 * (a8 + a4) + a4), *bbox = (float *)(base + 2 * (a8 + a4) + a4 + part);
     // an edit enqueued on another stream still writes the records; a call on another stream still reads the scratch
     GS_TRY(wait_for_edits(g, st));
@@ -59,21 +57,39 @@ static gs_status neighbor_counts_enqueue(gs_gaussians_buffer *g, hipStream_t st,
     const uint32_t *svals = (const uint32_t *)v2[side];
     float *sx = (float *)k2[side ^ 1], *sy = sx + n, *sz = sy + n;      // 12 n bytes <= a8 + a4, the pair is contiguous
     hipLaunchKernelGGL(gs::k_nb_gather, dim3(nblocks), dim3(256), 0, st, aos, pod_words, n, sh, skeys, svals, sx, sy, sz);
-    if (!counts) counts = plane;
+    GS_HIP(hipGetLastError());
+    grid.keys = skeys;
+    grid.vals = svals;
+    grid.sx = sx;
+    grid.sy = sy;
+    grid.sz = sz;
+    grid.plane = (uint32_t *)(base + 2 * (a8 + a4));
+    grid.extra = base + 2 * (a8 + a4) + a4 + part + 256;
+    grid.n = n;
+    grid.nblocks = nblocks;
+    return GS_OK;
+}
+
+// counts[i] = min(c_i, cap) in caller order on `st` (mark: gs::NB_NOT_A_POINT where i is no point); counts == nullptr: the
+// plane of the buffer's scratch, returned in *plane_out.  n > 0, arguments checked.
+static gs_status neighbor_counts_enqueue(gs_gaussians_buffer *g, hipStream_t st, const gs_selection *among,
+                                         const gs_model_transform_pod *mt, float radius, uint32_t cap, bool mark, uint32_t *counts,
+                                         uint32_t **plane_out) {
+    NeighborGrid q;
+    GS_TRY(neighbor_grid_enqueue(g, st, among, mt, radius, 0, q));
+    if (!counts) counts = q.plane;
     const float rr = radius * radius;
     if (mark)
-        hipLaunchKernelGGL(gs::k_nb_count<true>, dim3(nblocks), dim3(256), 0, st, skeys, svals, (const float *)sx, (const float *)sy,
-                           (const float *)sz, n, rr, cap, counts);
+        hipLaunchKernelGGL(gs::k_nb_count<true>, dim3(q.nblocks), dim3(256), 0, st, q.keys, q.vals, q.sx, q.sy, q.sz, q.n, rr, cap, counts);
     else
-        hipLaunchKernelGGL(gs::k_nb_count<false>, dim3(nblocks), dim3(256), 0, st, skeys, svals, (const float *)sx, (const float *)sy,
-                           (const float *)sz, n, rr, cap, counts);
+        hipLaunchKernelGGL(gs::k_nb_count<false>, dim3(q.nblocks), dim3(256), 0, st, q.keys, q.vals, q.sx, q.sy, q.sz, q.n, rr, cap, counts);
     GS_HIP(hipGetLastError());
-    if (plane_out) *plane_out = plane;
+    if (plane_out) *plane_out = q.plane;
     return GS_OK;
 }
 
 // the next call on another stream waits until this one has left the scratch
-static gs_status neighbor_scratch_release(gs_gaussians_buffer *g, hipStream_t st) {
+gs_status gsh::neighbor_scratch_release(gs_gaussians_buffer *g, hipStream_t st) {
     if (!g->nb_done) GS_HIP(hipEventCreateWithFlags(&g->nb_done, hipEventDisableTiming));
     GS_HIP(hipEventRecord(g->nb_done, st));
     g->nb_stream = st;
