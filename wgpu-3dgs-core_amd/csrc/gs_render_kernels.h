@@ -667,14 +667,20 @@ __device__ const float k_ln_opacity_byte[256] = {
 };
 
 // One Gaussian: returns the number of tiles touched (0 = culled) and fills the 48-byte record.
-// Written without early exits: every cull test only clears `ok`, so all the record's loads are
+// Written without per-lane early exits: every cull test only clears `ok`, so all the record's loads are
 // unconditional and the compiler can issue them back to back at the top (memory-level
 // parallelism is what this HBM-bound kernel needs); arithmetic on culled lanes is discarded.
 // The geometry half reads only the position / colour chunk and the covariance words; the colour
-// half (shade_one) reads the SH words.  project_one = both, in the order the spec gives.
-template <int SH, int COV>
-__device__ __forceinline__ uint32_t project_geom(const uint32_t *w, const FrameConsts &fc,
-                                                 uint4 rec[3], float d[3], const float *ln_tab, uint32_t &rows) {
+// half (shade_one) reads the SH words; a kernel calls both, in the order the spec gives.
+// The one branch (WAVE_EXIT): a WAVE none of whose lanes has a radius rect on the screen (or in the band) leaves behind
+// that rect — `dead` — without the rect clip, the corner test and the record arithmetic (nearly half of the function's
+// instructions; in a spatially ordered mirror the Gaussians a view culls fill whole waves).  Every later test only
+// shrinks the rect, so each of its lanes is culled either way; the record it returns is zero and the caller need
+// not store it.  The branch is wave-uniform and sits behind the loads: they stay unconditional.  (k_preprocess takes
+// it; in k_preprocess_banded it cost the instantiations with SH 3 to 10 registers and three of them a wave per SIMD.)
+template <int SH, int COV, bool WAVE_EXIT = false>
+__device__ __forceinline__ uint32_t project_geom(const uint32_t *w, const FrameConsts &fc, uint4 rec[3], float d[3],
+                                                 const float *ln_tab, uint32_t &rows, bool *dead = nullptr) {
     float p[3] = {u2f(w[0]), u2f(w[1]), u2f(w[2])};
     float pw[4], t[4];
     mat4_mul_point(fc.M, p, pw);
@@ -719,6 +725,15 @@ __device__ __forceinline__ uint32_t project_geom(const uint32_t *w, const FrameC
     float fx1 = clampf(floorf((mx + radius) * 0.0625f) + 1.0f, 0.0f, (float)fc.tiles_x);
     float fy0 = clampf(floorf((my - radius) * 0.0625f), lo_y, hi_y);
     float fy1 = clampf(floorf((my + radius) * 0.0625f) + 1.0f, lo_y, hi_y);
+    if constexpr (WAVE_EXIT) {
+        *dead = !__any(ok && (fx1 > fx0) && (fy1 > fy0));
+        if (*dead) {
+            rec[0] = rec[1] = rec[2] = make_uint4(0u, 0u, 0u, 0u);
+            d[0] = d[1] = d[2] = 0.0f;
+            rows = 0u;
+            return 0u;
+        }
+    }
     // the record's quadratic form: power(dx, dy) = qa dx^2 + qb dx dy + qc dy^2
     const float qa = -0.5f * (cc * inv), qb = cb * inv, qc = -0.5f * (ca * inv);
     bool masks_ok = false;
@@ -852,15 +867,6 @@ __device__ __forceinline__ void shade_one(const uint32_t *w, const FrameConsts &
     rec[2].x = f2u(rgb[2]);
 }
 
-template <int SH, int COV>
-__device__ __forceinline__ uint32_t project_one(const uint32_t *w, const FrameConsts &fc,
-                                                uint4 rec[3], const float *ln_tab, uint32_t &rows) {
-    float d[3];
-    uint32_t cnt = project_geom<SH, COV>(w, fc, rec, d, ln_tab, rows);
-    shade_one<SH>(w, fc, d, rec);
-    return cnt;
-}
-
 // 4-byte aligned 16-byte vector: lets 36-byte records be moved with two dwordx4 + one dword
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 constexpr int REC_WORDS = 9;   // blend record: mx, my, ca, cb, cc, opacity, r, g, b  (36 bytes)
@@ -985,7 +991,8 @@ __device__ __forceinline__ void pre_finish_culled(const PreOut &io) {
 // depth key (0xffffffff when culled) and the 8-byte tile rect (0 when culled).  Masking the stores
 // of culled lanes would leave holes in every 64-byte sector, which turns the writes into
 // read-modify-writes and costs 0.15 ms at 10 M Gaussians on a randomly ordered mirror (measured); a
-// dense store of a few don't-care bytes is cheaper.  There is no compaction step: the first pass of
+// dense store of a few don't-care bytes is cheaper.  (A wave whose 64 Gaussians are all culled at the
+// radius rect — `dead`, project_geom — skips its 64 records: whole sectors.)  There is no compaction step: the first pass of
 // the depth sort reads the dense keys and simply does not rank the culled ones.
 //
 // What bounds it (tools/mb/mb_rw.hip, 10 M x 224 B on MI355X): the read pattern alone streams at
@@ -1024,6 +1031,9 @@ __global__ __launch_bounds__(PP_THREADS) void k_preprocess(const uint4 *__restri
     constexpr int NC = NW / 4;
     const uint32_t base = blockIdx.x * PP_CHUNK;
     uint32_t local = 0, local_vis = 0;
+    // (Not pipelined like k_preprocess_banded: requesting Gaussian k + 1's three chunks before Gaussian k is projected
+    // costs 4 registers and a wave per SIMD, 7 -> 6, and the stage came out 0.7 us SLOWER at 1 M, 24.3 against 23.5 us —
+    // NOTES.md Part XII.  The forced two-phase kernel, which prefetches, is no faster on these records either.)
 #pragma unroll 1
     for (int k = 0; k < PP_ITEMS; k++) {
         const uint32_t i = base + k * PP_THREADS + threadIdx.x;
@@ -1046,16 +1056,23 @@ __global__ __launch_bounds__(PP_THREADS) void k_preprocess(const uint4 *__restri
                 w[4 * c + 3] = v[c].w;
             }
             uint4 rec[3];
+            float d[3];
             uint32_t rows;
-            uint32_t cnt = project_one<SH, COV>(w, fc, rec, s_ln, rows);
-            if constexpr (SEL) {
-                ((cnt = sel_hide(sel_arg, i, cnt, rec, rows)), ...);
-                (sel_tint(sel_arg, i, rec), ...);
+            bool dead;
+            uint32_t cnt = project_geom<SH, COV, true>(w, fc, rec, d, s_ln, rows, &dead);
+            // a dead wave: every lane culled, its record zero.  Its 64 records stay as they are: 36 whole 64-byte sectors
+            // that nothing reads
+            if (!dead) {
+                shade_one<SH>(w, fc, d, rec);
+                if constexpr (SEL) {
+                    ((cnt = sel_hide(sel_arg, i, cnt, rec, rows)), ...);
+                    (sel_tint(sel_arg, i, rec), ...);
+                }
+                uint32_t *o = io.recs + (uint64_t)i * REC_WORDS;
+                store16(o, rec[0], fc.wt_records);
+                store16(o + 4, rec[1], fc.wt_records);
+                o[8] = rec[2].x;
             }
-            uint32_t *o = io.recs + (uint64_t)i * REC_WORDS;
-            store16(o, rec[0], fc.wt_records);
-            store16(o + 4, rec[1], fc.wt_records);
-            o[8] = rec[2].x;
             const uint32_t key = cnt ? rec[2].y - io.key_bias : 0xffffffffu;
             io.depth[i] = key;
             if (cnt) atomicAdd(&s_dhist[(key >> io.digit_shift) & io.digit_mask], 1u);
