@@ -533,6 +533,9 @@ extern "C" {
     pub fn gs_layout_convertible(src_sh: u32, src_cov: u32, dst_sh: u32, dst_cov: u32) -> i32;
     pub fn gs_convert_pods(src_sh: u32, src_cov: u32, dst_sh: u32, dst_cov: u32, pods: *const c_void, n: usize, out: *mut c_void) -> gs_status;
     pub fn gs_gaussians_buffer_create_converted(src: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, dst_sh: u32, dst_cov: u32, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
+    pub fn gs_cov3d_decompose(cov: *const f32, rot_xyzw: *mut f32, scale: *mut f32);
+    pub fn gs_decompose_pods(src_sh: u32, src_cov: u32, dst_sh: u32, pods: *const c_void, n: usize, out: *mut c_void) -> gs_status;
+    pub fn gs_gaussians_buffer_create_decomposed(src: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, dst_sh: u32, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
     pub fn gs_gaussians_buffer_create_concat_as(s: *mut gs_stream, srcs: *const *mut gs_gaussians_buffer, sels: *const *const gs_selection, count: u32, dst_sh: u32, dst_cov: u32, out: *mut *mut gs_gaussians_buffer, counts_out: *mut u64) -> gs_status;
     pub fn gs_gaussians_buffer_export_ply(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, out: *mut gs_ply_gaussian_pod, capacity: usize, count_out: *mut u64) -> gs_status;
     pub fn gs_gaussians_buffer_export_spz_decompressed(g: *mut gs_gaussians_buffer, s: *mut gs_stream, sel: *const gs_selection, invert: i32, options: *const gs_spz_options, out: *mut c_void, capacity: usize, bytes_out: *mut usize) -> gs_status;

@@ -1052,6 +1052,27 @@ gs_status gs_convert_pods(gs_sh_config src_sh, gs_cov3d_config src_cov, gs_sh_co
 gs_status gs_gaussians_buffer_create_converted(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel, int32_t invert,
                                                gs_sh_config dst_sh, gs_cov3d_config dst_cov, gs_gaussians_buffer **out,
                                                uint64_t *count_out);
+/* decompose (no reference item): the six terms xx, yx, zx, yy, zy, zz of one symmetric 3x3 covariance, in
+ * the order gs_pack writes them, -> a unit quaternion xyzw with w >= 0 and three scales >= 0 with (R S)(R S)^T = C up to
+ * rounding: cyclic Jacobi with a fixed number of sweeps on the matrix prescaled by an even power of two, every operation a
+ * rounded binary32 one, the same bits on host and device.  The scales come in Jacobi's column order, unsorted; a diagonal
+ * input gives the identity rotation exactly; negative eigenvalues are clamped to 0; an all-zero input gives the identity and
+ * +0 scales, a non-finite word the identity and three NaNs (0x7fc00000).  Host only. */
+void gs_cov3d_decompose(const float cov[6], float rot_xyzw[4], float scale[3]);
+/* Host only: n records of layout (src_sh, src_cov) -> n records of layout (dst_sh, GS_COV3D_ROT_SCALE) (DESIGN.md 3.12a;
+ * no reference item).  Words 0..3 and the SH section as gs_convert_pods converts them; the covariance words, decoded to
+ * binary32 (f16: exactly), go through gs_cov3d_decompose; trailing pad words are zero.  With src_cov == GS_COV3D_ROT_SCALE it
+ * IS gs_convert_pods: all 4 x 3 x 4 combinations are defined.  `out` holds n x gs_pod_size(dst_sh, GS_COV3D_ROT_SCALE) bytes
+ * and does not overlap `pods`.  The per-record function is the one the device kernel calls.  GS_ERR_INVALID_ARGUMENT for a
+ * null pointer or an unknown config; `out` is then untouched. */
+gs_status gs_decompose_pods(gs_sh_config src_sh, gs_cov3d_config src_cov, gs_sh_config dst_sh, const void *pods, size_t n, void *out);
+/* New buffer of layout (dst_sh, GS_COV3D_ROT_SCALE) holding the decomposed records (gs_decompose_pods) of `sel`, caller order
+ * kept: the decomposition is fused with the stable compaction (no reference item).  Blocking; ordering,
+ * argument checks, *count_out, the length-0 result and the spatial-order setting are exactly those of
+ * gs_gaussians_buffer_create_converted, and with a rotation + scale source it IS that call.  This is the way from the eight
+ * covariance layouts to the exports below and into a rotation + scale scene. */
+gs_status gs_gaussians_buffer_create_decomposed(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                                gs_sh_config dst_sh, gs_gaussians_buffer **out, uint64_t *count_out);
 /* gs_gaussians_buffer_create_concat in every respect (1..64 sources on one device, one blocking round trip for the counts,
  * the copies only enqueued, ordering, counts_out, at most 2^32 - 16 records, the spatial-order setting of srcs[0]), but the
  * sources may have ANY layouts: each is converted to (dst_sh, dst_cov), the layout of the new buffer (DESIGN.md 3.12;
@@ -1076,7 +1097,7 @@ gs_status gs_gaussians_buffer_create_concat_as(gs_stream *s, gs_gaussians_buffer
  * buffer or count pointer, a capacity below the count / size, a selection whose length differs from the buffer's or that
  * belongs to another device.  Only the layouts gs_gaussians_buffer_download_gaussians accepts (SH f32 / f16 / snorm8 with
  * rotation + scale) can be exported; the others return its error, GS_ERR_LOSSY_CONFIG with the reference's message, before
- * anything is enqueued. */
+ * anything is enqueued.  A covariance layout with SH is exported through gs_gaussians_buffer_create_decomposed. */
 
 /* Gaussian::to_ply of the selected records on the device (no reference item): *count_out = their number,
  * `out` (capacity in records) receives them.  The source is walked in slices (2 Mi records; GS3D_EXPORT_SLICE=<records, a

@@ -91,7 +91,18 @@ struct GaussianPod {
         check(gs_unpack_to_gaussian(SH, COV, pods.data(), g.size(), g.data()));
         return g;
     }
+    // packed records of this layout -> packed records of layout (TO, rotation + scale), the covariance of a covariance layout
+    // decomposed on the host (gs3d.h gs_decompose_pods; no reference item)
+    template <gs_sh_config TO = SH>
+    static std::vector<uint8_t> decompose(const std::vector<uint8_t> &pods) {
+        const size_t n = pods.size() / size();
+        std::vector<uint8_t> out(n * gs_pod_size(TO, GS_COV3D_ROT_SCALE));
+        if (n) check(gs_decompose_pods(SH, COV, TO, pods.data(), n, out.data()));
+        return out;
+    }
 };
+// one covariance (xx, yx, zx, yy, zy, zz) -> unit quaternion xyzw, w >= 0, and three scales (gs3d.h gs_cov3d_decompose)
+inline void cov3d_decompose(const float cov[6], float rot_xyzw[4], float scale[3]) { gs_cov3d_decompose(cov, rot_xyzw, scale); }
 #define GS3D_POD(S, C, NAME) using NAME = GaussianPod<S, C>;
 GS3D_POD(GS_SH_SINGLE, GS_COV3D_ROT_SCALE, GaussianPodWithShSingleCov3dRotScaleConfigs)
 GS3D_POD(GS_SH_SINGLE, GS_COV3D_SINGLE, GaussianPodWithShSingleCov3dSingleConfigs)
@@ -379,6 +390,12 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     GaussiansBuffer<To> convert(Stream &s, const Selection *sel = nullptr, bool invert = false) const;
     static GaussiansBuffer concat(Stream &s, converted_t, const std::vector<gs_gaussians_buffer *> &srcs,
                                   const std::vector<const Selection *> &sels = {}, std::vector<uint64_t> *counts = nullptr);
+    // decompose<SH>: a new buffer of layout (SH, rotation + scale) with the decomposed records of sel (nullptr: all; invert:
+    // of its complement), caller order kept; blocking (gs3d.h gs_gaussians_buffer_create_decomposed; no
+    // reference item).  The covariance of a covariance layout becomes a unit quaternion and three scales, which the exports
+    // and a rotation + scale scene accept; a rotation + scale source is convert.
+    template <gs_sh_config SH = G::sh>
+    GaussiansBuffer<GaussianPod<SH, GS_COV3D_ROT_SCALE>> decompose(Stream &s, const Selection *sel = nullptr, bool invert = false) const;
     // attribute statistics and histograms over the records of sel (nullptr: all) in one pass on the device (gs3d.h
     // gs_gaussians_buffer_stats / _histogram; no reference item); blocking.  mt == nullptr: the default
     // transform; ref == nullptr: the origin.  histogram: 2 x (bins + 3) counts, row 0 = the selection, row 1 = the others.
@@ -497,6 +514,13 @@ template <class To>
 inline GaussiansBuffer<To> GaussiansBuffer<G>::convert(Stream &s, const Selection *sel, bool invert) const {
     GaussiansBuffer<To> b;
     check(gs_gaussians_buffer_create_converted(h_, s.raw(), sel ? sel->raw() : nullptr, invert ? 1 : 0, To::sh, To::cov3d, &b.h_, nullptr));
+    return b;
+}
+template <class G>
+template <gs_sh_config SH>
+inline GaussiansBuffer<GaussianPod<SH, GS_COV3D_ROT_SCALE>> GaussiansBuffer<G>::decompose(Stream &s, const Selection *sel, bool invert) const {
+    GaussiansBuffer<GaussianPod<SH, GS_COV3D_ROT_SCALE>> b;
+    check(gs_gaussians_buffer_create_decomposed(h_, s.raw(), sel ? sel->raw() : nullptr, invert ? 1 : 0, SH, &b.h_, nullptr));
     return b;
 }
 template <class G>

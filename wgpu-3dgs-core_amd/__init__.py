@@ -235,6 +235,19 @@ class GaussianPod:
         _check(_L.gs_convert_pods(self.sh, self.cov, to.sh, to.cov, _ptr(pods) if n else _ptr(out), n, _ptr(out)))
         return out[:n * to.size]
 
+    def decompose(self, pods, to_sh):
+        """gs_decompose_pods: packed records of this layout -> packed records of layout (to_sh, rotation +
+        scale), on the host, with the per-record function the device kernel calls: the covariance of a covariance layout
+        goes through cov3d_decompose; a rotation + scale source is convert().  Defined for every layout."""
+        to = GaussianPod(to_sh, COV3D_ROT_SCALE)
+        pods = np.ascontiguousarray(pods, dtype=np.uint8).reshape(-1)
+        if pods.size % self.size:
+            raise ValueError("%d bytes are no whole number of %d-byte records" % (pods.size, self.size))
+        n = pods.size // self.size
+        out = np.zeros(max(n * to.size, 1), dtype=np.uint8)
+        _check(_L.gs_decompose_pods(self.sh, self.cov, to.sh, _ptr(pods) if n else _ptr(out), n, _ptr(out)))
+        return out[:n * to.size]
+
     def __repr__(self):
         return self.name
 
@@ -337,6 +350,20 @@ def expf(x):
 def logf(x):
     """gs_logf: the ln of Gaussian::to_ply / to_spz on host and device (csrc/gs_convert.h)"""
     return float(_L.gs_logf(float(x)))
+
+
+def cov3d_decompose(cov):
+    """gs_cov3d_decompose: the six binary32 terms xx, yx, zx, yy, zy, zz of one covariance, or an (n, 6)
+    array of them -> (rot xyzw, scale) as float32 arrays of shape (4,), (3,) or (n, 4), (n, 3).  The function the records
+    of GaussianPod.decompose and GaussiansBuffer.decompose go through, on the host."""
+    c = np.ascontiguousarray(cov, dtype=np.float32)
+    if c.shape[-1:] != (6,) or c.ndim > 2:
+        raise ValueError("a covariance has 6 terms; got an array of shape %r" % (c.shape,))
+    rows = c.reshape(-1, 6)
+    rot, scale = np.zeros((len(rows), 4), np.float32), np.zeros((len(rows), 3), np.float32)
+    for i in range(len(rows)):
+        _L.gs_cov3d_decompose(_ptr(rows[i]), _ptr(rot[i]), _ptr(scale[i]))
+    return (rot[0], scale[0]) if c.ndim == 1 else (rot, scale)
 
 
 def gaussian_to_ply(gaussians):
@@ -980,15 +1007,44 @@ class GaussiansBuffer:
         assert out.len() == count.value
         return out
 
+    def decompose(self, stream, sh=None, selection=None, invert=False):
+        """gs_gaussians_buffer_create_decomposed: a new GaussiansBuffer of layout (sh, rotation + scale)
+        — sh=None: this buffer's SH config — with the records of `selection` (None: all; invert: of its complement) in
+        caller order, the covariance of each decomposed into a unit quaternion and three scales on the device: the way from
+        a covariance layout to export_ply / export_spz / write and into a rotation + scale scene.  Blocking.  Byte-equal to
+        pod.decompose(pods, sh) on the host; for a rotation + scale source it is convert()."""
+        pod = GaussianPod(self.pod.sh if sh is None else sh, COV3D_ROT_SCALE)
+        if selection is not None and not isinstance(selection, Selection):
+            raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
+        h, count = C.c_void_p(), C.c_uint64()
+        _check(_L.gs_gaussians_buffer_create_decomposed(self._h, stream._h if stream is not None else None,
+                                                        selection._h if selection is not None else None,
+                                                        int(bool(invert)), pod.sh, C.byref(h), C.byref(count)))
+        out = GaussiansBuffer(self.device, pod, h)
+        assert out.len() == count.value
+        return out
+
+    def _export_decomposed(self, stream, selection, invert, export):
+        """decompose=True of the exports on a covariance layout: export(tmp) for a temporary rotation + scale buffer that
+        holds the decomposed selection and is destroyed again"""
+        tmp = self.decompose(stream, None, selection, invert)
+        try:
+            return export(tmp)
+        finally:
+            tmp.destroy()
+
     def _export_args(self, stream, selection):
         if selection is not None and not isinstance(selection, Selection):
             raise TypeError("selection must be a Selection or None, not %s" % type(selection).__name__)
         return self._h, stream._h if stream is not None else None, selection._h if selection is not None else None
 
-    def export_ply(self, stream, selection=None, invert=False):
+    def export_ply(self, stream, selection=None, invert=False, decompose=False):
         """gs_gaussians_buffer_export_ply: the records of `selection` (None: all; invert: of its
         complement) as PlyGaussians in caller order — extract(), download_gaussians() and gaussian_to_ply() in one kernel on
-        the device, byte-equal to them.  Blocking."""
+        the device, byte-equal to them.  Blocking.  decompose=True exports a covariance layout through decompose() (DESIGN.md
+        §3.12a) instead of raising LossyConfigError; an SH-less layout raises it either way."""
+        if decompose and self.pod.cov != COV3D_ROT_SCALE:
+            return self._export_decomposed(stream, selection, invert, lambda b: b.export_ply(stream))
         head = self._export_args(stream, selection) + (int(bool(invert)),)
         count = C.c_uint64()
         _check(_L.gs_gaussians_buffer_export_ply(*head, None, 0, C.byref(count)))
@@ -997,20 +1053,25 @@ class GaussiansBuffer:
             _check(_L.gs_gaussians_buffer_export_ply(*head, _ptr(pods), len(pods), C.byref(count)))
         return PlyGaussians(pods[:count.value], True)
 
-    def export_spz(self, stream, selection=None, invert=False, options=None):
+    def export_spz(self, stream, selection=None, invert=False, options=None, decompose=False):
         """gs_gaussians_buffer_export_spz_decompressed: the records of `selection` as SpzGaussians (None:
         spz_options()), the columns encoded on the device — byte-equal to
-        SpzGaussians.from_gaussians_with_options(extract().download_gaussians(), options).  Blocking."""
+        SpzGaussians.from_gaussians_with_options(extract().download_gaussians(), options).  Blocking.  decompose: as
+        export_ply's."""
+        if decompose and self.pod.cov != COV3D_ROT_SCALE:
+            return self._export_decomposed(stream, selection, invert, lambda b: b.export_spz(stream, options=options))
         if options is not None and not isinstance(options, _capi.SpzOptions):
             raise TypeError("options must be spz_options(...) or None, not %s" % type(options).__name__)
         head = self._export_args(stream, selection) + (int(bool(invert)), C.byref(options) if options is not None else None)
         return SpzGaussians(_sized_call(_L.gs_gaussians_buffer_export_spz_decompressed, *head))
 
-    def export_spz_file(self, stream, selection=None, invert=False, options=None, fast=True):
+    def export_spz_file(self, stream, selection=None, invert=False, options=None, fast=True, decompose=False):
         """The .spz file image of the records of `selection` as bytes.  fast=True: gs_gaussians_buffer_export_spz_fast
          — the payload stays on the device and is deflated there, Huffman only; fast=False:
         gs_gaussians_buffer_export_spz, zlib on one host thread.  Both inflate to export_spz(...).payload.  Blocking.  The fast
-        image comes as a bytearray, zlib's as bytes."""
+        image comes as a bytearray, zlib's as bytes.  decompose: as export_ply's."""
+        if decompose and self.pod.cov != COV3D_ROT_SCALE:
+            return self._export_decomposed(stream, selection, invert, lambda b: b.export_spz_file(stream, options=options, fast=fast))
         if options is not None and not isinstance(options, _capi.SpzOptions):
             raise TypeError("options must be spz_options(...) or None, not %s" % type(options).__name__)
         args = self._export_args(stream, selection) + (int(bool(invert)),)
@@ -1022,11 +1083,13 @@ class GaussiansBuffer:
         _check(_L.gs_gaussians_buffer_export_spz_decompressed(*head, None, 0, C.byref(n)))
         return _bounded_call(_L.gs_gaussians_buffer_export_spz_fast, gzip_fast_bound(n.value), *head)
 
-    def write(self, stream, source, selection=None, invert=False, fast=False):
+    def write(self, stream, source, selection=None, invert=False, fast=False, decompose=False):
         """gs_gaussians_buffer_write: the complete file image of the records of `selection` as bytes —
         GaussiansSource.Ply: header + vertices; GaussiansSource.Spz: the gzip member, default options.  Blocking.
         fast=True makes the SPZ member export_spz_file's (deflated on the device, not zlib's bytes); a PLY
-        image has nothing to compress and is the same either way."""
+        image has nothing to compress and is the same either way.  decompose: as export_ply's."""
+        if decompose and self.pod.cov != COV3D_ROT_SCALE:
+            return self._export_decomposed(stream, selection, invert, lambda b: b.write(stream, source, fast=fast))
         if source == GaussiansSource.Internal:
             raise ValueError("cannot write Internal Gaussians to buffer")
         if source not in (GaussiansSource.Ply, GaussiansSource.Spz):
@@ -1047,10 +1110,10 @@ class GaussiansBuffer:
                 return out[:n.value].tobytes()
         return _sized_call(_L.gs_gaussians_buffer_write, *head)
 
-    def write_to_file(self, path, stream=None, selection=None, invert=False, fast=False):
+    def write_to_file(self, path, stream=None, selection=None, invert=False, fast=False, decompose=False):
         """write() into a file; the format follows the suffix: .spz is SPZ, everything else PLY"""
         source = GaussiansSource.Spz if str(path).lower().endswith(".spz") else GaussiansSource.Ply
-        data = self.write(stream, source, selection, invert, fast=fast)
+        data = self.write(stream, source, selection, invert, fast=fast, decompose=decompose)
         with open(path, "wb") as f:
             f.write(data)
 

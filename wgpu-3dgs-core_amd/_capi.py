@@ -271,6 +271,9 @@ SIGNATURES = {
     "gs_layout_convertible": (i32, [i32, i32, i32, i32]),
     "gs_convert_pods": (i32, [i32, i32, i32, i32, vp, sz, vp]),
     "gs_gaussians_buffer_create_converted": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "gs_cov3d_decompose": (None, [vp, vp, vp]),
+    "gs_decompose_pods": (i32, [i32, i32, i32, vp, sz, vp]),
+    "gs_gaussians_buffer_create_decomposed": (i32, [vp, vp, vp, i32, i32, vp, vp]),
     "gs_gaussians_buffer_create_concat_as": (i32, [vp, vp, vp, u32, i32, i32, vp, vp]),
     "gs_gaussians_buffer_export_ply": (i32, [vp, vp, vp, i32, vp, sz, vp]),
     "gs_gaussians_buffer_export_spz_decompressed": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),

@@ -198,6 +198,113 @@ GS_HD inline void ply_to_gaussian_words(const uint32_t *p, uint32_t *g, Sqrt sqr
     }
 }
 
+// ---- covariance -> rotation + scale (no reference item) ----
+
+// One Jacobi rotation of the pair (p, q); r is the third index.  app / aqq / apq: the pair's terms, arp / arq: the other two
+// off-diagonals, (v0p, v0q) .. (v2p, v2q): columns p and q of V.  Skipped exactly when apq == 0: the arithmetic runs anyway
+// (a kernel predicates; what 0 / 0 gives is discarded) and the selects keep the old values bit for bit.  3 divisions and 2
+// square roots, every operation a rounded binary32 one.
+template <class Sqrt>
+GS_HD inline void cov3d_jacobi_rotate(float &app, float &aqq, float &apq, float &arp, float &arq, float &v0p, float &v0q, float &v1p,
+                                      float &v1q, float &v2p, float &v2q, Sqrt sqrtf_cr) {
+    const bool on = apq != 0.0f;
+    const float theta = (aqq - app) / (2.0f * apq);
+    const float t = (theta < 0.0f ? -1.0f : 1.0f) / (cv_u2f(cv_f2u(theta) & 0x7fffffffu) + sqrtf_cr(theta * theta + 1.0f));
+    const float c = 1.0f / sqrtf_cr(t * t + 1.0f);
+    const float s = t * c;
+    const float tapq = t * apq;
+    const float npp = app - tapq, nqq = aqq + tapq;
+    const float nrp = c * arp - s * arq, nrq = s * arp + c * arq;
+    const float n0p = c * v0p - s * v0q, n0q = s * v0p + c * v0q;
+    const float n1p = c * v1p - s * v1q, n1q = s * v1p + c * v1q;
+    const float n2p = c * v2p - s * v2q, n2q = s * v2p + c * v2q;
+    app = on ? npp : app;
+    aqq = on ? nqq : aqq;
+    apq = on ? 0.0f : apq;
+    arp = on ? nrp : arp;
+    arq = on ? nrq : arq;
+    v0p = on ? n0p : v0p;
+    v0q = on ? n0q : v0q;
+    v1p = on ? n1p : v1p;
+    v1q = on ? n1q : v1q;
+    v2p = on ? n2p : v2p;
+    v2q = on ? n2q : v2q;
+}
+
+constexpr int COV3D_JACOBI_SWEEPS = 6;      // fixed (NOTES.md: 5 and 6 sweeps give the same bits on 200 000 covariances)
+
+// decompose: c = the six covariance terms xx, yx, zx, yy, zy, zz as cov3d_from_rot_scale writes them ->
+// q = unit quaternion xyzw with w >= 0, s = the three scales in Jacobi's own column order: (R S)(R S)^T = C up to rounding,
+// negative eigenvalues clamped to 0.  Every operation is a rounded binary32 +, -, *, / or square root in the order written
+// (no contraction), so host and device give the same bits.  `sqrtf_cr`: a correctly rounded binary32 square root, as above.
+template <class Sqrt>
+GS_HD inline void cov3d_decompose(const float c[6], float q[4], float s[3], Sqrt sqrtf_cr) {
+    // 1, 2: non-finite and zero input, from the bits; m = the largest |c_k| (as bits: the order of the magnitudes)
+    uint32_t m = 0u;
+    GS_UNROLL
+    for (int k = 0; k < 6; k++) {
+        const uint32_t a = cv_f2u(c[k]) & 0x7fffffffu;
+        m = a > m ? a : m;
+    }
+    q[0] = 0.0f;
+    q[1] = 0.0f;
+    q[2] = 0.0f;
+    q[3] = 1.0f;
+    if (m >= 0x7f800000u || m == 0u) {
+        s[0] = s[1] = s[2] = cv_u2f(m ? 0x7fc00000u : 0u);
+        return;
+    }
+    // 3: prescale by 2^-e, e even, so that the largest word lands in [1, 4).  A subnormal maximum is first lifted by 2^24
+    // (exact, even), which makes its exponent field >= 2.  Both factors are built from their exponent bits.
+    const uint32_t lift = m < 0x00800000u ? 24u : 0u;
+    const float pre = cv_u2f((127u + lift) << 23);                                      // 2^lift
+    const uint32_t mexp = cv_f2u(cv_u2f(m) * pre) >> 23;                                // biased exponent of the maximum, 1..254
+    const int32_t e = (int32_t)((mexp + 1u) & ~1u) - 128;                               // mexp - 127 rounded down to even, -126..126
+    const float down = cv_u2f((uint32_t)(127 - e) << 23);                               // 2^-e
+    const float up = cv_u2f((uint32_t)(127 + (e - (int32_t)lift) / 2) << 23);           // 2^((e - lift) / 2)
+    float a00 = c[0] * pre * down, a01 = c[1] * pre * down, a02 = c[2] * pre * down;
+    float a11 = c[3] * pre * down, a12 = c[4] * pre * down, a22 = c[5] * pre * down;
+    // 4: cyclic Jacobi, pairs (0,1), (0,2), (1,2), a fixed number of sweeps; v<row><column>
+    float v00 = 1.0f, v01 = 0.0f, v02 = 0.0f, v10 = 0.0f, v11 = 1.0f, v12 = 0.0f, v20 = 0.0f, v21 = 0.0f, v22 = 1.0f;
+    for (int sweep = 0; sweep < COV3D_JACOBI_SWEEPS; sweep++) {
+        cov3d_jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21, sqrtf_cr);      // (0,1), r = 2
+        cov3d_jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22, sqrtf_cr);      // (0,2), r = 1
+        cov3d_jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22, sqrtf_cr);      // (1,2), r = 0
+    }
+    // 5: scales, unsorted; a negative eigenvalue (and -0) gives +0
+    s[0] = sqrtf_cr(a00 > 0.0f ? a00 : 0.0f) * up;
+    s[1] = sqrtf_cr(a11 > 0.0f ? a11 : 0.0f) * up;
+    s[2] = sqrtf_cr(a22 > 0.0f ? a22 : 0.0f) * up;
+    // 6: V -> quaternion with the branches of glam's Quat::from_mat3 (m<column><row> = v<row><column>), normalised as
+    // ply_to_gaussian_words normalises, w >= 0
+    float x, y, z, w;
+    if (v22 <= 0.0f) {
+        const float dif10 = v11 - v00, omm22 = 1.0f - v22;
+        if (dif10 <= 0.0f) {
+            const float four = omm22 - dif10, inv = 0.5f / sqrtf_cr(four);
+            x = four * inv, y = (v10 + v01) * inv, z = (v20 + v02) * inv, w = (v21 - v12) * inv;
+        } else {
+            const float four = omm22 + dif10, inv = 0.5f / sqrtf_cr(four);
+            x = (v10 + v01) * inv, y = four * inv, z = (v21 + v12) * inv, w = (v02 - v20) * inv;
+        }
+    } else {
+        const float sum10 = v11 + v00, opm22 = 1.0f + v22;
+        if (sum10 <= 0.0f) {
+            const float four = opm22 - sum10, inv = 0.5f / sqrtf_cr(four);
+            x = (v20 + v02) * inv, y = (v21 + v12) * inv, z = four * inv, w = (v10 - v01) * inv;
+        } else {
+            const float four = opm22 + sum10, inv = 0.5f / sqrtf_cr(four);
+            x = (v21 - v12) * inv, y = (v02 - v20) * inv, z = (v10 - v01) * inv, w = four * inv;
+        }
+    }
+    const float len = sqrtf_cr(((x * x + y * y) + z * z) + w * w);
+    const bool neg = w < 0.0f;
+    q[0] = neg ? -(x / len) : x / len;
+    q[1] = neg ? -(y / len) : y / len;
+    q[2] = neg ? -(z / len) : z / len;
+    q[3] = neg ? -(w / len) : w / len;
+}
+
 // ---- Gaussian::from_spz (src/gaussian.rs:134-229) over the decompressed columns (spz.rs:739-771) ----
 
 // where the columns of a decompressed SPZ payload start (positions -> alphas -> colors -> scales ->

@@ -214,6 +214,32 @@ __host__ __device__ inline void convert_words(int ssh, int scov, int dsh, int dc
     }
 }
 
+// One POD of layout (ssh, scov) -> one POD of layout (dsh, rot-scale), DESIGN.md §3.12a: words 0..3 and the SH section as
+// convert_words does them; the covariance words, decoded to binary32 (f16: exactly), go through cov3d_decompose; the
+// trailing pad is zero.  A rot-scale source IS convert_words, with its precondition (two different layouts).  Shared by the
+// host path (gs_decompose_pods) and the device kernel (k_decompose_extract).
+template <class Sqrt>
+__host__ __device__ inline void decompose_words(int ssh, int scov, int dsh, const uint32_t *p, uint32_t *o, Sqrt sqrtf_cr) {
+    if (scov == COV_ROT_SCALE) {
+        convert_words(ssh, scov, dsh, COV_ROT_SCALE, p, o);
+        return;
+    }
+    // the head of the record: the conversion that keeps the cov config writes words 0..3 and the SH section, and a cov section
+    // no longer than the one written below
+    convert_words(ssh, scov, dsh, scov, p, o);
+    const uint32_t *c = p + cov_word0(ssh);
+    uint32_t *e = o + cov_word0(dsh);
+    float c6[6], q[4], s[3];
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+        c6[k] = scov == COV_SINGLE ? cv_u2f(c[k]) : cv_f16_to_f32((c[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+    cov3d_decompose(c6, q, s, sqrtf_cr);
+    const int ntail = pod_words(dsh, COV_ROT_SCALE) - cov_word0(dsh);
+#pragma unroll
+    for (int k = 0; k < 10; k++)
+        if (k < ntail) e[k] = k < 4 ? cv_f2u(q[k]) : k < 7 ? cv_f2u(s[k - 4]) : 0u;
+}
+
 // Device side of GaussiansBuffer::download::<Gaussian>: PODs -> struct Gaussian records, LDS-staged on
 // both sides like k_pack_pods (COV is RotScale by construction).
 template <int SH>

@@ -1,5 +1,6 @@
 // gs_relayout.hip — conversion of records between the 12 POD layouts: the pair table, the host
-// conversion, the converted extraction and the concatenation of sources of any layouts (§3.9's, with a target layout).
+// conversion, the converted extraction and the concatenation of sources of any layouts (§3.9's, with a target layout); the
+// decomposition of covariance layouts into rotation + scale (§3.12a), on the host and fused with the extraction.
 // Kernels: gs_relayout_kernels.h; the extraction scan and the plain copy are gs_edit.hip's.
 #include "gs_host.h"
 
@@ -39,17 +40,48 @@ extern "C" gs_status gs_convert_pods(gs_sh_config src_sh, gs_cov3d_config src_co
     return GS_OK;
 }
 
+extern "C" void gs_cov3d_decompose(const float cov[6], float rot_xyzw[4], float scale[3]) {
+    gs::cov3d_decompose(cov, rot_xyzw, scale, [](float v) { return std::sqrt(v); });
+}
+
+extern "C" gs_status gs_decompose_pods(gs_sh_config src_sh, gs_cov3d_config src_cov, gs_sh_config dst_sh, const void *pods, size_t n,
+                                       void *out) {
+    if (src_cov == GS_COV3D_ROT_SCALE) return gs_convert_pods(src_sh, src_cov, dst_sh, GS_COV3D_ROT_SCALE, pods, n, out);
+    if (!pods || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
+    if (!valid_cfg(src_sh, src_cov) || !valid_cfg(dst_sh, GS_COV3D_ROT_SCALE)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "unknown layout config");
+    const size_t ss = (size_t)gs::pod_bytes(src_sh, src_cov), ds = (size_t)gs::pod_bytes(dst_sh, gs::COV_ROT_SCALE);
+    const uint8_t *in = (const uint8_t *)pods;
+    uint8_t *o = (uint8_t *)out;
+    for (size_t i = 0; i < n; i++) {
+        uint32_t pw[56], ow[56];
+        std::memcpy(pw, in + i * ss, ss);
+        gs::decompose_words(src_sh, src_cov, dst_sh, pw, ow, [](float v) { return std::sqrt(v); });      // the same code the device kernel runs
+        std::memcpy(o + i * ds, ow, ds);
+    }
+    return GS_OK;
+}
+
 // one kernel instance per pair of SH configs; the cov configs are kernel arguments
 typedef void (*convert_fn)(const uint4 *, uint4 *, const uint32_t *, uint32_t, uint32_t, const uint32_t *, int, int, uint64_t, uint32_t);
 #define GS_SH_ROW(s) {gs::k_convert_extract<s, 0>, gs::k_convert_extract<s, 1>, gs::k_convert_extract<s, 2>, gs::k_convert_extract<s, 3>}
 static convert_fn k_tbl_convert[4][4] = {GS_SH_ROW(0), GS_SH_ROW(1), GS_SH_ROW(2), GS_SH_ROW(3)};
 #undef GS_SH_ROW
+typedef void (*decompose_fn)(const uint4 *, uint4 *, const uint32_t *, uint32_t, uint32_t, const uint32_t *, int, uint64_t, uint32_t);
+#define GS_SH_ROW(s) {gs::k_decompose_extract<s, 0>, gs::k_decompose_extract<s, 1>, gs::k_decompose_extract<s, 2>, gs::k_decompose_extract<s, 3>}
+static decompose_fn k_tbl_decompose[4][4] = {GS_SH_ROW(0), GS_SH_ROW(1), GS_SH_ROW(2), GS_SH_ROW(3)};
+#undef GS_SH_ROW
 
 // The `total` records the scan counted, converted: src (n records of layout (ssh, scov)) -> records [dst_base, dst_base +
 // total) of dst (layout (dsh, dcov)), packed in index order.  A source that already has the destination layout is copied
-// (k_extract_copy).
+// (k_extract_copy); a covariance source with a rot-scale destination (which only gs_gaussians_buffer_create_decomposed asks
+// for) is decomposed.
 static void convert_extract_enqueue(hipStream_t st, const gs_gaussians_buffer *src, int dsh, int dcov, void *dst, uint64_t dst_base,
                                     const uint32_t *words, uint32_t n, uint32_t invert, const uint32_t *offsets, uint32_t total) {
+    if (dcov == gs::COV_ROT_SCALE && src->cov != gs::COV_ROT_SCALE) {
+        hipLaunchKernelGGL(k_tbl_decompose[src->sh][dsh], dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint4 *)src->buf->ptr,
+                           (uint4 *)dst, words, n, invert, offsets, src->cov, dst_base, total);
+        return;
+    }
     if (src->sh == dsh && src->cov == dcov) {
         const uint32_t nc = (uint32_t)(pod_stride(src) / 16);
         extract_copy_enqueue(st, src->buf->ptr, (uint4 *)dst + dst_base * nc, words, n, invert, offsets, nc, total);
@@ -95,6 +127,20 @@ extern "C" gs_status gs_gaussians_buffer_create_converted(gs_gaussians_buffer *s
     const gs_status rc = extract_records(src, s, sel, invert, dst_sh, dst_cov, out, count_out, &e);
     if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "conversion failed: %s", hipGetErrorString(e));
     return rc;
+}
+
+extern "C" gs_status gs_gaussians_buffer_create_decomposed(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *sel, int32_t invert,
+                                                           gs_sh_config dst_sh, gs_gaussians_buffer **out, uint64_t *count_out) {
+    if (src && out && src->cov != gs::COV_ROT_SCALE) {
+        *out = nullptr;
+        if (count_out) *count_out = 0;
+        if (!valid_cfg(dst_sh, GS_COV3D_ROT_SCALE)) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "unknown layout config");
+        hipError_t e = hipSuccess;
+        const gs_status rc = extract_records(src, s, sel, invert, dst_sh, gs::COV_ROT_SCALE, out, count_out, &e);
+        if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "decomposition failed: %s", hipGetErrorString(e));
+        return rc;
+    }
+    return gs_gaussians_buffer_create_converted(src, s, sel, invert, dst_sh, GS_COV3D_ROT_SCALE, out, count_out);
 }
 
 extern "C" gs_status gs_gaussians_buffer_create_concat_as(gs_stream *s, gs_gaussians_buffer *const *srcs, const gs_selection *const *sels,
