@@ -666,6 +666,46 @@ __device__ const float k_ln_opacity_byte[256] = {
     5.51342869f, 5.51745272f, 5.52146101f, 5.52545309f, 5.52942896f, 5.53338957f, 5.53733444f, 5.54126358f,
 };
 
+// The blend's pixel test as one unsigned compare (GS_BLEND_STEP): entry k >= 1 is bits(L(k)) + 1, where
+// L(k) is the one binary32 with  min(0.99, fl(k / 255) * exp(power)) >= 1/255  <=>  -power <= L(k)  for every float power in
+// [-5.6, -0] and the blend's own exp (not monotone, yet every byte's pass set is up-closed: tools/blend_alpha_limits.c scans
+// all 1 085 485 876 floats of the range; its output, this table included, is profiles/blend_alpha_limits.txt).  Entry 0 is 0:
+// no exponent passes (opacity 0; the null record of the lists carries the same word).
+__device__ const uint32_t k_blend_np_limit[256] = {
+    0x00000000u, 0x33000001u, 0x3f317219u, 0x3f8c9f55u, 0x3fb17219u, 0x3fce0211u, 0x3fe55862u, 0x3ff91395u,
+    0x40051593u, 0x400c9f54u, 0x40135d8fu, 0x4019771fu, 0x401f08b7u, 0x40242822u, 0x4028e651u, 0x402d50b2u,
+    0x40317219u, 0x4035535eu, 0x4038fbdau, 0x403c71b1u, 0x403fba15u, 0x4042d976u, 0x4045d3a5u, 0x4048abf1u,
+    0x404b653du, 0x404e0211u, 0x405084a8u, 0x4052eefeu, 0x405542d7u, 0x405781c7u, 0x4059ad39u, 0x405bc673u,
+    0x405dce9fu, 0x405fc6c9u, 0x4061afe4u, 0x40638ad4u, 0x40655860u, 0x40671948u, 0x4068ce37u, 0x406a77ccu,
+    0x406c169bu, 0x406dab2cu, 0x406f35fcu, 0x4070b782u, 0x4072302bu, 0x4073a05cu, 0x40750877u, 0x407668d3u,
+    0x4077c1c3u, 0x40791397u, 0x407a5e97u, 0x407ba309u, 0x407ce12eu, 0x407e1944u, 0x407f4b84u, 0x40803c13u,
+    0x4080cfafu, 0x408160adu, 0x4081ef27u, 0x40827b30u, 0x408304e0u, 0x40838c48u, 0x4084117du, 0x40849490u,
+    0x40851593u, 0x40859495u, 0x408611a8u, 0x40868cd8u, 0x40870635u, 0x40877dceu, 0x4087f3adu, 0x408867e0u,
+    0x4088da73u, 0x40894b72u, 0x4089bae7u, 0x408a28ddu, 0x408a955fu, 0x408b0075u, 0x408b6a29u, 0x408bd285u,
+    0x408c3991u, 0x408c9f55u, 0x408d03d9u, 0x408d6726u, 0x408dc941u, 0x408e2a34u, 0x408e8a04u, 0x408ee8b9u,
+    0x408f4659u, 0x408fa2e9u, 0x408ffe71u, 0x409058f7u, 0x4090b27fu, 0x40910b0fu, 0x409162adu, 0x4091b95du,
+    0x40920f25u, 0x40926409u, 0x4092b80fu, 0x40930b39u, 0x40935d8fu, 0x4093af12u, 0x4093ffc8u, 0x40944fb4u,
+    0x40949edau, 0x4094ed3fu, 0x40953ae5u, 0x409587d1u, 0x4095d405u, 0x40961f86u, 0x40966a56u, 0x4096b479u,
+    0x4096fdf2u, 0x409746c3u, 0x40978ef0u, 0x4097d67du, 0x40981d6au, 0x409863bbu, 0x4098a973u, 0x4098ee95u,
+    0x40993323u, 0x4099771eu, 0x4099ba8bu, 0x4099fd6bu, 0x409a3fc0u, 0x409a818cu, 0x409ac2d3u, 0x409b0395u,
+    0x409b43d6u, 0x409b8396u, 0x409bc2d8u, 0x409c019fu, 0x409c3febu, 0x409c7dbeu, 0x409cbb1bu, 0x409cf804u,
+    0x409d3478u, 0x409d707du, 0x409dac11u, 0x409de737u, 0x409e21f0u, 0x409e5c3eu, 0x409e9623u, 0x409ecfa0u,
+    0x409f08b7u, 0x409f4168u, 0x409f79b5u, 0x409fb1a0u, 0x409fe92au, 0x40a02055u, 0x40a05720u, 0x40a08d8fu,
+    0x40a0c3a2u, 0x40a0f95au, 0x40a12eb8u, 0x40a163bdu, 0x40a1986cu, 0x40a1ccc5u, 0x40a200c8u, 0x40a23477u,
+    0x40a267d4u, 0x40a29adeu, 0x40a2cd98u, 0x40a30001u, 0x40a3321cu, 0x40a363e8u, 0x40a39569u, 0x40a3c69cu,
+    0x40a3f784u, 0x40a42822u, 0x40a45877u, 0x40a48883u, 0x40a4b847u, 0x40a4e7c5u, 0x40a516fcu, 0x40a545eeu,
+    0x40a5749cu, 0x40a5a306u, 0x40a5d12du, 0x40a5ff11u, 0x40a62cb4u, 0x40a65a17u, 0x40a6873au, 0x40a6b41du,
+    0x40a6e0c2u, 0x40a70d28u, 0x40a73952u, 0x40a7653fu, 0x40a790f0u, 0x40a7bc65u, 0x40a7e7a0u, 0x40a812a1u,
+    0x40a83d68u, 0x40a867f6u, 0x40a8924cu, 0x40a8bc6bu, 0x40a8e652u, 0x40a91002u, 0x40a9397cu, 0x40a962c1u,
+    0x40a98bd2u, 0x40a9b4adu, 0x40a9dd55u, 0x40aa05c9u, 0x40aa2e0bu, 0x40aa561au, 0x40aa7df7u, 0x40aaa5a2u,
+    0x40aacd1du, 0x40aaf468u, 0x40ab1b82u, 0x40ab426du, 0x40ab6928u, 0x40ab8fb5u, 0x40abb614u, 0x40abdc45u,
+    0x40ac0248u, 0x40ac281fu, 0x40ac4dc9u, 0x40ac7347u, 0x40ac9899u, 0x40acbdc0u, 0x40ace2bcu, 0x40ad078eu,
+    0x40ad2c35u, 0x40ad50b2u, 0x40ad7506u, 0x40ad9931u, 0x40adbd33u, 0x40ade10du, 0x40ae04c0u, 0x40ae284au,
+    0x40ae4badu, 0x40ae6ee9u, 0x40ae91ffu, 0x40aeb4edu, 0x40aed7b6u, 0x40aefa5au, 0x40af1cd8u, 0x40af3f31u,
+    0x40af6166u, 0x40af8375u, 0x40afa561u, 0x40afc72au, 0x40afe8ceu, 0x40b00a50u, 0x40b02baeu, 0x40b04ceau,
+    0x40b06e03u, 0x40b08efau, 0x40b0afd0u, 0x40b0d083u, 0x40b0f116u, 0x40b11187u, 0x40b131d8u, 0x40b15209u,
+};
+
 // One Gaussian: returns the number of tiles touched (0 = culled) and fills the 48-byte record.
 // Written without per-lane early exits: every cull test only clears `ok`, so all the record's loads are
 // unconditional and the compiler can issue them back to back at the top (memory-level
@@ -3993,7 +4033,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     constexpr int NL = 2 * G;                 // lists per tile (= NCOL * NROW)
     static_assert(NCOL * NROW == NL && G == NCOL * (NROW / 2), "one list per block, G blocks per wave");
     constexpr uint32_t NULL_REC = BLEND_BATCH;
-    // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, pmin, opacity, r | g, b, -, -} (AUX: {.. | g, b, z', slot}; CONTRIB: {.. | g, b, -, accumulator offset}).  The
+    // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, limit word, opacity, r | g, b, -, -} (Point: pmin for the limit word; AUX: {.. | g, b, z', slot}; CONTRIB: {.. | g, b, -, accumulator offset}).  The
     // lists hold the records' BYTE OFFSETS (16 bits each), so a step's three LDS reads share one address
     // register and differ only in the instruction's immediate offset: no shift / mask per step.
     constexpr uint32_t RS = 48;
@@ -4022,6 +4062,15 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     if (ROUNDS && tk.round == 2u && ((tk.done[tile >> 5] >> (tile & 31u)) & 1u)) return;      // finished in round 1, pixels final
     uint32_t start, end;
     __shared__ uint32_t s_range[2];
+    // Splat: the workgroup's copy of k_blend_np_limit (1 KB; G = 8: LDS 11 400 B of the 11 702 that 14 workgroups per CU allow),
+    // loaded beside the range search and first read behind the batch loop's first barrier.  Against the table read straight
+    // from global memory in the staging (a dependent load behind the record's): the 1 M blend 168.4 vs 170.2 us, the 10 M
+    // blend stage 0.1937 vs 0.1950 ms (NOTES.md Part XIV)
+    __shared__ uint32_t s_limit[MODE == 0 ? 256 : 1];
+    if constexpr (MODE == 0) {
+        s_limit[tid] = k_blend_np_limit[tid];
+        s_limit[tid + BLEND_THREADS] = k_blend_np_limit[tid + BLEND_THREADS];
+    }
     blend_tile_range_wg(tk, ranges, tile, lane, wid, s_range, start, end);
     f32x2 T = {1.0f, 1.0f}, C0 = {0.0f, 0.0f}, C1 = {0.0f, 0.0f}, C2 = {0.0f, 0.0f};
     const bool in0 = px < fc.width && py0 < fc.height, in1 = px < fc.width && py1 < fc.height;
@@ -4072,9 +4121,9 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     f32x2 pyf = {live0 ? (float)py0 + 0.5f : DEAD, live1 ? (float)py1 + 0.5f : DEAD};
     uint32_t remaining = __builtin_amdgcn_readfirstlane(
         (uint32_t)__popcll(__ballot(live0)) + (uint32_t)__popcll(__ballot(live1)));
-    if (tid == 0) {   // the null record: power = 0 everywhere, pmin = 1 -> "power >= pmin" never holds
+    if (tid == 0) {   // the null record: limit word 0 -> "bits(np) < limit" never holds (Point: pmin = 1, its own test)
         *(float4 *)(s_rec + NULL_REC * (RS / 4)) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        *(float4 *)(s_rec + NULL_REC * (RS / 4) + 4) = make_float4(0.0f, 1.0f, 0.0f, 0.0f);
+        *(float4 *)(s_rec + NULL_REC * (RS / 4) + 4) = make_float4(0.0f, MODE == 2 ? 1.0f : 0.0f, 0.0f, 0.0f);
         if constexpr (AUX || CONTRIB) *(float4 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         else *(float2 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float2(0.0f, 0.0f);
     }
@@ -4104,6 +4153,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         // wave ballots in scalar registers (a per-lane array of 2G flags cost 40 vector registers)
         const uint32_t j = b0 + tid;
         float mx = 0.0f, my = 0.0f, ca = 0.0f, cb = 0.0f, cc = 0.0f, thr = 0.0f;
+        uint32_t limit = 0u;
         const bool have = j < end;
         // A wave whose 64 lanes hold no splat (b0 + 64 wid >= end: wave 1 in a tile's last batch of at most 64 pairs) skips the
         // set-ups, the block tests and the list build: all its verdicts are zero.  The branch is wave-uniform, and the
@@ -4125,13 +4175,24 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 const u32x4_a4 r1 = *(const u32x4_a4 *)(rec + 4);
                 const uint32_t r2x = rec[8];
                 mx = u2f(r0.x); my = u2f(r0.y); ca = u2f(r0.z); cb = u2f(r0.w); cc = u2f(r1.x);
+                // Splat and Ellipse: the record's pmin slot carries the limit word of the step's unsigned compare (GS_BLEND_STEP):
+                // bits(L) + 1 with L = the largest -power that passes.  Splat: L(k) of the opacity byte k, exact
+                // (k_blend_np_limit; the opacity of a record is fl(k / 255), which 255 op + 0.5 truncated gives back);
+                // Ellipse: L = -ellipse_pmin.  Point keeps the float word and its own test.
                 float pmin;
-                if constexpr (MODE == 0) pmin = fmaxf(-__logf(255.0f * u2f(r1.y)) - 1.0e-3f, -5.6f);
-                else pmin = fc.ellipse_pmin;
+                if constexpr (MODE == 0) {
+                    limit = s_limit[(uint32_t)(255.0f * u2f(r1.y) + 0.5f) & 255u];
+                    // (limit 0, opacity byte 0: bits 0xffffffff, a NaN, of which the minimum makes 0; the splat enters no list, see
+                    // have_b.  As a select on limit != 0 this cost the contribution instantiations 1-2 registers, G = 2 a wave per SIMD)
+                    pmin = fminf(-u2f(limit - 1u), 0.0f);
+                } else {
+                    pmin = fc.ellipse_pmin;
+                    limit = f2u(fabsf(pmin)) + 1u;
+                }
                 // no constant below pmin: cull_rounding_slack is the whole rounding bound (derived there)
                 thr = (MODE == 0 ? pmin : pmin - 1.0e-3f * fabsf(pmin)) - cull_rounding_slack(mx, my, ca, cb, cc, tx0, ty0);
                 *(float4 *)(s_rec + tid * (RS / 4)) = make_float4(mx, my, ca, cb);
-                *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(cc, pmin, u2f(r1.y), u2f(r1.z));
+                *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(cc, MODE == 2 ? pmin : u2f(limit), u2f(r1.y), u2f(r1.z));
                 if constexpr (AUX)
                     *(float4 *)(s_rec + tid * (RS / 4) + 8) =
                         make_float4(u2f(r1.w), u2f(r2x), u2f(aux.depth_keys[slot] + aux.key_bias), u2f(slot));
@@ -4166,7 +4227,8 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 const float rcc = __builtin_amdgcn_rcpf(cc), rca = __builtin_amdgcn_rcpf(ca);
                 float c_lo[NCOL], c_hi[NCOL], c_q1[NCOL], c_q0[NCOL], c_t[NCOL];
                 uint64_t c_inb[NCOL];
-                const uint64_t have_b = __builtin_amdgcn_ballot_w64(have);
+                // (a record whose limit word is 0 — opacity byte 0 — passes nowhere and enters no list)
+                const uint64_t have_b = __builtin_amdgcn_ballot_w64(have && limit != 0u);
 #pragma unroll
                 for (int c = 0; c < NCOL; c++) {
                     const float x0c = bx0 + (float)BW * (float)c;
@@ -4286,28 +4348,47 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             uint32_t pair = mine[0];
             uint32_t id_A = pair & 0xffffu;
             float4 a_A = *(const float4 *)(rbase + id_A), b_A = *(const float4 *)(rbase + id_A + 16);
-#define GS_BLEND_STEP(AREC, BREC, ID)                                                                          \
+            // The pixel test of Splat and Ellipse is ONE unsigned compare per pixel, bits(np) < limit, with np = -power computed
+            // from the negated products -(ca dx), -(cb dx), -(cc dy) (source modifiers of the same three multiplies: no
+            // instruction more; stored negated, the coefficients cost the staging a register and one instantiation a wave per
+            // SIMD; negation commutes with every rounding, so np is -power bit for bit, but for the sign of a zero) and
+            // limit = bits(L) + 1 from the record's pmin slot.
+            //  - Why it is the old decision.  DESIGN.md §3.5 / §3.6 ask for  power <= 0  and  alpha = min(0.99, op exp(power)) >=
+            //    1/255.  The opacity of a record is fl(k / 255) of its byte k, and over ALL binary32 powers of [-5.6, -0] the
+            //    second test, with this very exp, holds exactly for -power <= L(k): the exp is not monotone (tens of
+            //    thousands of adjacent-float inversions, worst relative drop 8.4e-8), yet no inversion straddles the threshold
+            //    of any byte.  tools/blend_alpha_limits.c scans the whole range and fails otherwise; its output,
+            //    profiles/blend_alpha_limits.txt, holds the table (k_blend_np_limit).  Below -5.6 no byte passes (e^-5.6 < 1/255).
+            //    So p is the alpha test itself, and Splat tests nothing after the exp.  (Ellipse: L = -ellipse_pmin is the
+            //    range test; its flat alpha is still tested.)
+            //  - Why one compare.  For np >= +0 the float order is the unsigned order of the bits; a negative np (power > 0:
+            //    rounding produces it on needles, the oracle skips such pixels) has the top bit set, and every NaN pattern and
+            //    the huge or infinite np of a parked pixel (y = 1e15) lie above bits(5.6).  np is never -0: ca, cc < 0 strictly,
+            //    so (-ca dx) dx and (-cc dy) dy are +0 or larger even where they underflow, a rounded sum is -0 only if both
+            //    addends are, and an exact zero sum is +0.  (Either zero gives e = 1 anyway.)  Limit 0 — the null record,
+            //    opacity byte 0 — passes nowhere.
+            //  - The limit is still the DOMAIN GUARD of the exp below: the integer-add ldexp is valid for arguments in
+            //    [-5.6, 0] only, and L(k) <= ln 255 = 5.55.  The any-lane branch it feeds also skips most steps of a deep
+            //    tile, whose pixels are long finished (round 4 removed test and branch for one build: wrong pixels, and the
+            //    10 M blend 0.157 -> 1.80 ms).
+#define GS_BLEND_STEP(AREC, BREC, ID)                                                                         \
     {                                                                                                         \
         const float dx = AREC.x - pxf;                                                                        \
         const f32x2 dy = f32x2{AREC.y, AREC.y} - pyf;                                                         \
-        const float u = AREC.z * dx, wq = AREC.w * dx;                                                        \
-        const f32x2 v = f32x2{BREC.x, BREC.x} * dy;                                                           \
+        const float u = -(AREC.z * dx), wq = -(AREC.w * dx);                                                  \
+        const f32x2 v = -(f32x2{BREC.x, BREC.x} * dy);                                                        \
         f32x2 t = f32x2{wq, wq} * dy;                                                                         \
         t = pk_fma(v, dy, t);                                                                                 \
-        const f32x2 power = pk_fma(f32x2{u, u}, f32x2{dx, dx}, t);                                            \
+        /* np = -power: see above (Point: unused) */                                                          \
+        const f32x2 np = pk_fma(f32x2{u, u}, f32x2{dx, dx}, t);                                               \
         bool p0, p1;                                                                                          \
         if constexpr (MODE == 2) {                                                                            \
             const f32x2 d2 = f32x2{dx * dx, dx * dx} + dy * dy;                                               \
             p0 = d2.x <= 2.25f && BREC.y <= 0.0f; /* the null record carries pmin = 1 */                      \
             p1 = d2.y <= 2.25f && BREC.y <= 0.0f;                                                             \
         } else {                                                                                              \
-            /* "power >= pmin" (pmin = -ln(255 opacity) - 1e-3 >= -5.6) is more than a pre-test of          */ \
-            /* "alpha >= 1/255": it is the DOMAIN GUARD of the exp below (the integer-add ldexp is only      */ \
-            /* valid for arguments in [-5.6, 0]; finished pixels are parked at y = 1e15, power = -1e30), and */ \
-            /* the any-lane branch it feeds skips most steps of a deep tile, whose pixels are long finished: */ \
-            /* round 4 removed both for one build — wrong pixels, and the 10 M blend 0.157 -> 1.80 ms.       */ \
-            p0 = power.x <= 0.0f && power.x >= BREC.y;                                                        \
-            p1 = power.y <= 0.0f && power.y >= BREC.y;                                                        \
+            p0 = f2u(np.x) < f2u(BREC.y); /* 0 <= -power <= L: see above */                                   \
+            p1 = f2u(np.y) < f2u(BREC.y);                                                                     \
         }                                                                                                     \
         if (__builtin_amdgcn_ballot_w64(p0 || p1) != 0ull) {                                                  \
             float2 cq; /* g, b */                                                                             \
@@ -4324,7 +4405,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             f32x2 alpha;                                                                                      \
             if constexpr (MODE == 0) {                                                                        \
                 /* exp exactly as in k_blend */                                              \
-                const f32x2 tt = power * f32x2{1.44269504088896340736f, 1.44269504088896340736f};             \
+                const f32x2 tt = np * f32x2{-1.44269504088896340736f, -1.44269504088896340736f};              \
                 const f32x2 tm = tt + f32x2{12582912.0f, 12582912.0f};                                        \
                 const f32x2 n = tm - f32x2{12582912.0f, 12582912.0f};                                         \
                 const f32x2 f = tt - n;                                                                       \
@@ -4341,8 +4422,9 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 const float flat = fminf(0.99f, BREC.z);                                                      \
                 alpha = f32x2{flat, flat};                                                                    \
             }                                                                                                 \
-            const bool act0 = p0 && alpha.x >= (1.0f / 255.0f);                                               \
-            const bool act1 = p1 && alpha.y >= (1.0f / 255.0f);                                               \
+            /* Splat: p IS "alpha >= 1/255" (the limit table); Ellipse, Point: the flat alpha is tested */    \
+            const bool act0 = p0 && (MODE == 0 || alpha.x >= (1.0f / 255.0f));                                \
+            const bool act1 = p1 && (MODE == 0 || alpha.y >= (1.0f / 255.0f));                                \
             /* a pixel that skips this splat blends it with alpha 0: T * (1 - 0) == T and */                  \
             /* fma(rgb, 0 * T, C) == C exactly, so no selects are needed on T and C */                        \
             f32x2 alpha_eff = {act0 ? alpha.x : 0.0f, act1 ? alpha.y : 0.0f};                                 \
