@@ -4,6 +4,11 @@
 #   python3 tools/blend_sim.py --staging-table      only the G = 8 staging table: slack 0.1 / 0.01 / 0.0, each with and without
 #                                                   the blocks that are finished at a batch start left off that batch's lists
 #   --drop-finished                                 adds that drop to the G = 8 rows of the default run
+#   python3 tools/blend_sim.py --pixel-pass         only: how pixel-exact the G = 8 lists are (the kernel's block test, slack 0) —
+#                                                   entries with no pixel that passes 0 <= -power <= L, passing pixels per entry,
+#                                                   and the wave-steps of lists rebuilt from "some pixel passes"
+#   python3 tools/blend_sim.py --wave-split         only: wave-steps if the two waves of a tile split its sixteen 4x4 blocks
+#                                                   otherwise than by pixel rows (the eight longest lists to one wave)
 import argparse, os, sys, numpy as np
 _root=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (_root, os.path.join(_root,'tools'), os.path.join(_root,'tests')): sys.path.insert(0,_p)
@@ -12,6 +17,8 @@ _ap=argparse.ArgumentParser()
 _ap.add_argument('--slack',type=float,default=0.1)
 _ap.add_argument('--drop-finished',action='store_true')
 _ap.add_argument('--staging-table',action='store_true')
+_ap.add_argument('--pixel-pass',action='store_true')
+_ap.add_argument('--wave-split',action='store_true')
 ARGS=_ap.parse_args()
 from oracle import binding as ob
 N=1_000_000; sh,cov=3,0
@@ -31,7 +38,7 @@ op=p['opacity'].astype(np.float64)
 pmin=np.maximum(-np.log(255*op)-1e-3,-5.6)
 def pmax(q2,q1,q0,lo,hi):
     t=np.clip(-0.5*q1/q2,lo,hi); return (q2*t+q1)*t+q0
-def touches(rx0,rx1,ry0,ry1,slack=None):
+def touches(rx0,rx1,ry0,ry1,slack=None,pmin=pmin):
     slack=ARGS.slack if slack is None else slack
     dxl=mx-rx1; dxh=mx-rx0; dyl=my-ry1; dyh=my-ry0
     inx=(dxl<=0)&(dxh>=0); iny=(dyl<=0)&(dyh>=0)
@@ -79,6 +86,52 @@ if ARGS.staging_table:
         for drop in (False,True):
             e,s=staging_g8(slack,drop)
             print('| %g | %s | %d | %d |'%(slack,'left off' if drop else 'staged',e,s),flush=True)
+    sys.exit(0)
+if ARGS.pixel_pass or ARGS.wave_split:
+    # the G = 8 lists as the kernel builds them since NOTES.md Part XIV: threshold -L(k) = -ln(255 opacity), no constant, slack 0;
+    # per (tile, batch) the lengths of the sixteen block lists (row-major; lists 0..7 are wave 0's), steps rounded up to even
+    pmin0=np.maximum(-np.log(255*op),-5.6)
+    u,inv=np.unique(tile*1000+batch,return_inverse=True); nb=len(u)
+    L=np.zeros((nb,16),dtype=np.int64); Lx=np.zeros((nb,16),dtype=np.int64)
+    ent=zero=pixpass=full=0
+    for r in range(4):
+        for c in range(4):
+            t=touches(x0+4*c,x0+4*c+3,y0+4*r,y0+4*r+3,0.0,pmin0)
+            L[:,r*4+c]=np.bincount(inv,weights=t,minlength=nb)
+            if ARGS.pixel_pass:
+                cnt=np.zeros(D,dtype=np.int64)
+                for j in range(4):
+                    for i in range(4):
+                        dx=mx-(x0+4*c+i); dy=my-(y0+4*r+j)
+                        pw=ca*dx*dx+cb*dx*dy+cc*dy*dy
+                        cnt+=((pw<=0)&(pw>=pmin0))
+                ent+=int(t.sum()); zero+=int((t&(cnt==0)).sum()); pixpass+=int(cnt[t].sum()); full+=int((t&(cnt==16)).sum())
+                Lx[:,r*4+c]=np.bincount(inv,weights=(cnt>0),minlength=nb)
+    ev=lambda x: ((x+1)//2)*2
+    built=int(ev(L[:,:8].max(1)).sum()+ev(L[:,8:].max(1)).sum())
+    print('batches',nb,'block entries',int(L.sum()),'wave-steps as built',built)
+    if ARGS.pixel_pass:
+        print('entries with no passing pixel %d (%.3f %%); passing pixels per entry %.2f of 16; entries whose 16 pixels all pass %d'
+              %(zero,100.0*zero/ent,pixpass/ent,full))
+        e=int(ev(Lx[:,:8].max(1)).sum()+ev(Lx[:,8:].max(1)).sum())
+        print('wave-steps with lists rebuilt from "some pixel passes" %d (%.4f of as built)'%(e,e/built))
+    if ARGS.wave_split:
+        tl=u//1000
+        first=np.searchsorted(tl,np.arange(8160))
+        tile_tot=np.zeros((8160,16)); np.add.at(tile_tot,tl,L)
+        for name,score in (('the eight longest lists of the first batch to one wave',None),
+                           ('the eight longest by the whole tile\'s totals (not known when the tile starts)',tile_tot)):
+            tot=0
+            for t in range(8160):
+                a=first[t]; b=first[t+1] if t+1<8160 else nb
+                if a>=nb or tl[a]!=t: continue
+                o=np.argsort(-(L[a] if score is None else score[t]),kind='stable')
+                Lt=L[a:b]
+                tot+=ev(Lt[:,o[:8]].max(1)).sum()+ev(Lt[:,o[8:]].max(1)).sum()
+            print('%s: wave-steps %d (%.4f of as built)'%(name,int(tot),tot/built))
+        srt=-np.sort(-L,axis=1)
+        tot=int(ev(srt[:,0]).sum()+ev(srt[:,8]).sum())
+        print('re-sorted in every batch (a bound: a lane\'s pixels are fixed): wave-steps %d (%.4f of as built)'%(tot,tot/built))
     sys.exit(0)
 gid=tile*1000+batch   # (tile,batch) group id
 def grp_sum(mask):

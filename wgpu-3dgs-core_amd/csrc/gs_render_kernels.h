@@ -4033,14 +4033,19 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     constexpr int NL = 2 * G;                 // lists per tile (= NCOL * NROW)
     static_assert(NCOL * NROW == NL && G == NCOL * (NROW / 2), "one list per block, G blocks per wave");
     constexpr uint32_t NULL_REC = BLEND_BATCH;
-    // One 48-byte LDS record per staged splat: {mx, my, ca, cb | cc, limit word, opacity, r | g, b, -, -} (Point: pmin for the limit word; AUX: {.. | g, b, z', slot}; CONTRIB: {.. | g, b, -, accumulator offset}).  The
+    // One 48-byte LDS record per staged splat: {my, mx, cc, ca | opacity, cb, r, limit word | g, b, -, -} (Point: pmin for the limit word; AUX: {.. | g, b, z', slot}; CONTRIB: {.. | g, b, -, accumulator offset}).
+    // The words a step broadcasts to both pixels of a lane (my, cc, opacity, r) are the EVEN words of their 16-byte read: a packed
+    // instruction takes such a word from the low half of an aligned register pair as it lies, while for an odd word of a
+    // four-word read (r as the fourth: one of every two steps) hipcc first copied it into the low half.  The
     // lists hold the records' BYTE OFFSETS (16 bits each), so a step's three LDS reads share one address
     // register and differ only in the instruction's immediate offset: no shift / mask per step.
     constexpr uint32_t RS = 48;
     __shared__ __attribute__((aligned(16))) float s_rec[(BLEND_BATCH + 1) * (RS / 4)];
-    // (behind the lists, G = 8: the dump word — where the lanes that are no member of a list store, see the list build;
-    // written by non-members only, never read)
-    __shared__ __attribute__((aligned(16))) uint16_t s_list_mem[NL * BLEND_BATCH + (G == 8 ? 2 : 0)];
+    // (behind the lists: LIST_PAD null offsets — the blend loop reads one offset ahead of its last step; two, so that the pad is
+    // one 32-bit store — written once, beside the null record; behind them, G = 8: the dump word — where the lanes that are no member of a list store, see the
+    // list build; written by non-members only, never read)
+    constexpr int LIST_PAD = 2;
+    __shared__ __attribute__((aligned(16))) uint16_t s_list_mem[NL * BLEND_BATCH + LIST_PAD + (G == 8 ? 2 : 0)];
     uint16_t(*const s_list)[BLEND_BATCH] = (uint16_t(*)[BLEND_BATCH])s_list_mem;
     // [staging wave][list]; G = 8 packs the counts (<= 64 each) in 16 bits: a wave's 16 counts are two 16-byte reads
     typedef typename std::conditional<G == 8, uint16_t, uint32_t>::type cnt_t;
@@ -4123,9 +4128,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         (uint32_t)__popcll(__ballot(live0)) + (uint32_t)__popcll(__ballot(live1)));
     if (tid == 0) {   // the null record: limit word 0 -> "bits(np) < limit" never holds (Point: pmin = 1, its own test)
         *(float4 *)(s_rec + NULL_REC * (RS / 4)) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        *(float4 *)(s_rec + NULL_REC * (RS / 4) + 4) = make_float4(0.0f, MODE == 2 ? 1.0f : 0.0f, 0.0f, 0.0f);
+        *(float4 *)(s_rec + NULL_REC * (RS / 4) + 4) = make_float4(0.0f, 0.0f, 0.0f, MODE == 2 ? 1.0f : 0.0f);
         if constexpr (AUX || CONTRIB) *(float4 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         else *(float2 *)(s_rec + NULL_REC * (RS / 4) + 8) = make_float2(0.0f, 0.0f);
+        static_assert(LIST_PAD == 2, "the pad is one 32-bit store");
+        *(uint32_t *)(s_list_mem + NL * BLEND_BATCH) = (NULL_REC * RS) * 0x00010001u;
     }
 
     for (uint32_t b0 = start; b0 < end; b0 += BLEND_BATCH) {
@@ -4189,10 +4196,14 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                     pmin = fc.ellipse_pmin;
                     limit = f2u(fabsf(pmin)) + 1u;
                 }
+                // (the record's word order is not the global record's: the stores come first, with the scheduler held behind
+                // them, so that the registers of the shuffle are free again when the threshold's arithmetic needs its own; placed
+                // behind it, <0, 2, true, true, AuxIO> and <2, 2, true, true, AuxIO> took one and four registers more, a wave per SIMD)
+                *(float4 *)(s_rec + tid * (RS / 4)) = make_float4(my, mx, cc, ca);
+                *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(u2f(r1.y), cb, u2f(r1.z), MODE == 2 ? pmin : u2f(limit));
+                __builtin_amdgcn_sched_barrier(0);
                 // no constant below pmin: cull_rounding_slack is the whole rounding bound (derived there)
                 thr = (MODE == 0 ? pmin : pmin - 1.0e-3f * fabsf(pmin)) - cull_rounding_slack(mx, my, ca, cb, cc, tx0, ty0);
-                *(float4 *)(s_rec + tid * (RS / 4)) = make_float4(mx, my, ca, cb);
-                *(float4 *)(s_rec + tid * (RS / 4) + 4) = make_float4(cc, MODE == 2 ? pmin : u2f(limit), u2f(r1.y), u2f(r1.z));
                 if constexpr (AUX)
                     *(float4 *)(s_rec + tid * (RS / 4) + 8) =
                         make_float4(u2f(r1.w), u2f(r2x), u2f(aux.depth_keys[slot] + aux.key_bias), u2f(slot));
@@ -4294,7 +4305,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
 #pragma unroll
             for (int q = 0; q < 8; q++) w[q] = (uint32_t)__builtin_amdgcn_readfirstlane(wv[q]);
             const uint32_t swid = (uint32_t)__builtin_amdgcn_readfirstlane(wid);
-            const uint32_t dump = (uint32_t)(NL * BLEND_BATCH * sizeof(uint16_t));
+            const uint32_t dump = (uint32_t)((NL * BLEND_BATCH + LIST_PAD) * sizeof(uint16_t));
 #pragma unroll
             for (int l = 0; l < NL; l++) {
                 const uint32_t base = swid ? (w[l / 2] >> (16 * (l & 1))) & 0xffffu : 0u;
@@ -4336,18 +4347,25 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         __syncthreads();
 
         if (remaining != 0u) {
-            // Two splats per trip, in registers A and B: while A is blended B's record is already
-            // on its way from LDS and the offsets of the next pair are being read (one 32-bit read:
-            // lists are rows of 16-bit offsets, the trip count is rounded up to even and the padding is the
-            // null index, so the extra step of an odd list blends nothing).  One structured loop,
-            // one conditional block per step: no continue / break inside (hipcc turned those into a
-            // scalar state machine of ~25 instructions and 5 branches per iteration).
-            const uint32_t *mine = (const uint32_t *)s_list[my_list];
+            // Records alternate between registers A and B.  A step begins with the read of the NEXT step's offset — one
+            // 16-bit LDS read, zero-extended, at an immediate offset from the lane's pointer into its list: the lists are
+            // rows of 16-bit byte offsets, and read in pairs as 32-bit words they cost a mask, a shift and the next word's
+            // address per pair — and issues the next record's two reads behind its own pixel test, in front of the branch:
+            // the record is on its way from LDS while this step blends.  An offset's register is free once its step has
+            // issued its third read, so two registers alternate like the records.  A trip of the loop is FOUR steps, so the
+            // pointer moves once per four.  The step count is rounded up to even, not to four — the padding is the null offset,
+            // so the extra step of an odd list blends nothing, but it costs the dozen instructions in front of its branch —
+            // and a two-step remainder follows the loop.  The offsets are read one step ahead without a bound: behind a
+            // row's end lies the next row's first entry (a valid offset or the null fill), behind the last row the pad.
+            // One structured loop, one conditional block per step: no continue / break inside (hipcc turned
+            // those into a scalar state machine of ~25 instructions and 5 branches per iteration).
+            const char *lp = (const char *)s_list[my_list];
             const char *rbase = (const char *)s_rec;
-            const uint32_t trips = (trip + 1u) >> 1;
-            uint32_t pair = mine[0];
-            uint32_t id_A = pair & 0xffffu;
-            float4 a_A = *(const float4 *)(rbase + id_A), b_A = *(const float4 *)(rbase + id_A + 16);
+            const uint32_t trips = (trip + 1u) >> 1, quads = trips >> 1;
+            // (the first offset as the low half of a 32-bit read: with every incoming value a 16-bit read, hipcc carries the
+            // offset around the loop as 16 bits and extends it again where it is used)
+            uint32_t id_A = *(const uint32_t *)lp & 0xffffu, id_B;
+            float4 a_A = *(const float4 *)(rbase + id_A), b_A = *(const float4 *)(rbase + id_A + 16), a_B, b_B;
             // The pixel test of Splat and Ellipse is ONE unsigned compare per pixel, bits(np) < limit, with np = -power computed
             // from the negated products -(ca dx), -(cb dx), -(cc dy) (source modifiers of the same three multiplies: no
             // instruction more; stored negated, the coefficients cost the staging a register and one instantiation a wave per
@@ -4371,12 +4389,12 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             //    [-5.6, 0] only, and L(k) <= ln 255 = 5.55.  The any-lane branch it feeds also skips most steps of a deep
             //    tile, whose pixels are long finished (round 4 removed test and branch for one build: wrong pixels, and the
             //    10 M blend 0.157 -> 1.80 ms).
-#define GS_BLEND_STEP(AREC, BREC, ID)                                                                         \
+#define GS_BLEND_STEP(AREC, BREC, ID, NEXT)                                                                   \
     {                                                                                                         \
-        const float dx = AREC.x - pxf;                                                                        \
-        const f32x2 dy = f32x2{AREC.y, AREC.y} - pyf;                                                         \
-        const float u = -(AREC.z * dx), wq = -(AREC.w * dx);                                                  \
-        const f32x2 v = -(f32x2{BREC.x, BREC.x} * dy);                                                        \
+        const float dx = AREC.y - pxf;                                                                        \
+        const f32x2 dy = f32x2{AREC.x, AREC.x} - pyf;                                                         \
+        const float u = -(AREC.w * dx), wq = -(BREC.y * dx);                                                  \
+        const f32x2 v = -(f32x2{AREC.z, AREC.z} * dy);                                                        \
         f32x2 t = f32x2{wq, wq} * dy;                                                                         \
         t = pk_fma(v, dy, t);                                                                                 \
         /* np = -power: see above (Point: unused) */                                                          \
@@ -4384,12 +4402,13 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         bool p0, p1;                                                                                          \
         if constexpr (MODE == 2) {                                                                            \
             const f32x2 d2 = f32x2{dx * dx, dx * dx} + dy * dy;                                               \
-            p0 = d2.x <= 2.25f && BREC.y <= 0.0f; /* the null record carries pmin = 1 */                      \
-            p1 = d2.y <= 2.25f && BREC.y <= 0.0f;                                                             \
+            p0 = d2.x <= 2.25f && BREC.w <= 0.0f; /* the null record carries pmin = 1 */                      \
+            p1 = d2.y <= 2.25f && BREC.w <= 0.0f;                                                             \
         } else {                                                                                              \
-            p0 = f2u(np.x) < f2u(BREC.y); /* 0 <= -power <= L: see above */                                   \
-            p1 = f2u(np.y) < f2u(BREC.y);                                                                     \
+            p0 = f2u(np.x) < f2u(BREC.w); /* 0 <= -power <= L: see above */                                   \
+            p1 = f2u(np.y) < f2u(BREC.w);                                                                     \
         }                                                                                                     \
+        NEXT /* the next record's reads */                                                                    \
         if (__builtin_amdgcn_ballot_w64(p0 || p1) != 0ull) {                                                  \
             float2 cq; /* g, b */                                                                             \
             float zq = 0.0f; /* AUX: depth, slot; CONTRIB: -, accumulator */                                  \
@@ -4416,10 +4435,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 p = pk_fma(p, f, f32x2{0x1.62e430p-1f, 0x1.62e430p-1f});                                      \
                 p = pk_fma(p, f, f32x2{1.0f, 1.0f});                                                          \
                 const f32x2 e = {u2f(f2u(p.x) + (f2u(tm.x) << 23)), u2f(f2u(p.y) + (f2u(tm.y) << 23))};       \
-                const f32x2 oe = f32x2{BREC.z, BREC.z} * e;                                                   \
+                const f32x2 oe = f32x2{BREC.x, BREC.x} * e;                                                   \
                 alpha = f32x2{fminf(0.99f, oe.x), fminf(0.99f, oe.y)};                                        \
             } else {                                                                                          \
-                const float flat = fminf(0.99f, BREC.z);                                                      \
+                const float flat = fminf(0.99f, BREC.x);                                                      \
                 alpha = f32x2{flat, flat};                                                                    \
             }                                                                                                 \
             /* Splat: p IS "alpha >= 1/255" (the limit table); Ellipse, Point: the flat alpha is tested */    \
@@ -4439,7 +4458,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
                 remaining -= (uint32_t)__popcll(f0) + (uint32_t)__popcll(f1);                                 \
             }                                                                                                 \
             const f32x2 wgt = alpha_eff * T;                                                                  \
-            C0 = pk_fma(f32x2{BREC.w, BREC.w}, wgt, C0);                                                      \
+            C0 = pk_fma(f32x2{BREC.z, BREC.z}, wgt, C0);                                                      \
             C1 = pk_fma(f32x2{cq.x, cq.x}, wgt, C1);                                                          \
             C2 = pk_fma(f32x2{cq.y, cq.y}, wgt, C2);                                                          \
             if constexpr (AUX) {                                                                              \
@@ -4454,16 +4473,28 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             T = test_T;                                                                                       \
         }                                                                                                     \
     }
-            for (uint32_t q = 0; q < trips && remaining != 0u; q++) {
-                const uint32_t id_B = pair >> 16;
-                const float4 a_B = *(const float4 *)(rbase + id_B), b_B = *(const float4 *)(rbase + id_B + 16);
-                pair = mine[q + 1 < (uint32_t)(BLEND_BATCH / 2) ? q + 1 : q];      // offsets of the next trip
-                GS_BLEND_STEP(a_A, b_A, id_A)
-                id_A = pair & 0xffffu;
-                a_A = *(const float4 *)(rbase + id_A);
-                b_A = *(const float4 *)(rbase + id_A + 16);
-                GS_BLEND_STEP(a_B, b_B, id_B)
+#define GS_LIST_ID(K) ((uint32_t) * (const uint16_t *)(lp + 2 * (K)))
+#define GS_LOAD_REC(R)                             \
+    a_##R = *(const float4 *)(rbase + id_##R);     \
+    b_##R = *(const float4 *)(rbase + id_##R + 16);
+            for (uint32_t q = 0; q < quads && remaining != 0u; q++) {
+                id_B = GS_LIST_ID(1);
+                GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
+                id_A = GS_LIST_ID(2);
+                GS_BLEND_STEP(a_B, b_B, id_B, GS_LOAD_REC(A))
+                id_B = GS_LIST_ID(3);
+                GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
+                id_A = GS_LIST_ID(4);      // (step 127: position 128 = the next row's first entry, or the pad)
+                GS_BLEND_STEP(a_B, b_B, id_B, GS_LOAD_REC(A))
+                lp += 8;
             }
+            if ((trips & 1u) != 0u && remaining != 0u) {
+                id_B = GS_LIST_ID(1);
+                GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
+                GS_BLEND_STEP(a_B, b_B, id_B, )
+            }
+#undef GS_LOAD_REC
+#undef GS_LIST_ID
 #undef GS_BLEND_STEP
         }
         if constexpr (CONTRIB) flush_pending = true;
