@@ -6,12 +6,18 @@ tests/test_gpu_deflate.py for the gzip member (gs_gzip_fast of the same bytes), 
 (numpy indexing) and tests/test_gpu_convert.py for a conversion (the host conversion of the selected rows).
 
 3 000 records of SH f32 / rot-scale: three 1024-blocks, the last one partial; every third record selected.  The sliced PLY
-export (two staging buffers, events, a copy stream) is the GS3D_EXPORT_SLICE child of tests/test_gpu_export.py."""
+export (two staging buffers, events, a copy stream) is the GS3D_EXPORT_SLICE child of tests/test_gpu_export.py.
+
+The handle objects hold their members in the same owners: the last tests destroy a renderer whose frame is only enqueued,
+destroy a buffer, a selection, a snapshot and a renderer with every lazily created member alive (three cycles that must
+agree byte for byte), and toggle the timing events."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from frames import Scene
+from helpers import same_bits
 from records import selection_from_mask
 from scenes import export_scene
 
@@ -140,3 +146,97 @@ def test_empty_selection_then_a_selection(gs, device, stream, case, dst):
     assert np.array_equal(got, np.asarray(want).reshape(-1))
     lib.gs_gaussians_buffer_destroy(h)
     empty.destroy()
+
+
+# ---- the handle objects: their members are owners too, and gs_*_destroy is a wait and a delete ----
+
+ENQ_N, ENQ_W, ENQ_H = 2000, 64, 48
+NB_RADIUS = 0.25      # of the neighbour counts: asserted to find neighbours in the 3 000 Gaussians of synth.scene
+
+
+@pytest.fixture(scope="module")
+def enqueued_frame_oracle(gs, ob, device):
+    """the oracle's image of the scene the two destroy-while-enqueued cases render: computed once, read-only"""
+    st = device.create_stream()
+    sc = Scene(gs, ob, device, st, gs.SH_NONE, gs.COV3D_ROT_SCALE, ENQ_N, ENQ_W, ENQ_H)
+    rgba = np.ascontiguousarray(sc.oracle(sc.pods)["rgba"], np.float32).reshape(ENQ_H, ENQ_W, 4)
+    rgba.setflags(write=False)
+    sc.release()
+    st.close()
+    return rgba
+
+
+@pytest.mark.parametrize("close_stream_first", [False, True])
+def test_renderer_destroyed_with_its_frame_only_enqueued(gs, ob, device, stream, enqueued_frame_oracle, close_stream_first):
+    """gs_renderer_destroy waits for the frame before the pinned results, the scratch and the events (timing events
+    included) go: through the stream, or — the stream was closed first — through the end-of-frame event"""
+    st = device.create_stream()
+    sc = Scene(gs, ob, device, st, gs.SH_NONE, gs.COV3D_ROT_SCALE, ENQ_N, ENQ_W, ENQ_H)
+    r = gs.Renderer(device)
+    r.set_timing(True)
+    r.render(st, sc.buf, sc.gt, sc.mt, sc.cam, sc.img.device_ptr(), check=False)
+    if close_stream_first:
+        st.close()
+    r.destroy()
+    got = sc.img.download(stream, np.float32).reshape(ENQ_H, ENQ_W, 4)
+    assert same_bits(got, enqueued_frame_oracle)
+    sc.release()
+    if not close_stream_first:
+        st.close()
+
+
+def _handle_cycle(gs, ob, device, stream):
+    """every lazily created member of a buffer, a selection and a renderer alive, then all of them destroyed"""
+    sc = Scene(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, N, ENQ_W, ENQ_H)
+    assert sc.buf.spatial_order()
+    r = gs.Renderer(device)
+    sc.render(r)                                                  # mirror, order, inverse, block bounds, mirror_ready
+    out = {"image": sc.image().tobytes(), "order": sc.order().tobytes()}
+    sel = gs.Selection(device, N)
+    r.select_visible(stream, sel, 0, 0, ENQ_W, ENQ_H)             # the selection's scratch plane
+    out["count"] = sel.count(stream)                              # ... and its counter
+    out["selection"] = np.asarray(sel.download(stream)).tobytes()
+    assert 0 < out["count"] < N
+    sc.buf.edit(stream, sel, gs.edit(color=gs.color_override((1, 0.5, 0))))      # edit_done
+    s = sc.buf.stats(stream)                                      # stats_scratch
+    out["stats"] = (s.count, s.finite.tobytes(), s.min.tobytes(), s.max.tobytes(), s.sum.tobytes())
+    plane = sc.buf.neighbor_counts(stream, NB_RADIUS)             # nb_scratch, nb_done
+    counts = plane.download(stream, np.uint32)[:N].copy()
+    plane.release()
+    assert counts.max() > 0, "the radius finds no neighbours"
+    out["neighbours"] = counts.tobytes()
+    snap = sc.buf.snapshot(stream, sel)
+    out["snapshot"] = (snap.count, snap.nbytes)
+    assert snap.count == out["count"]
+    out["records"] = np.asarray(sc.buf.download(stream)).tobytes()
+    assert out["records"] != np.asarray(sc.pods).tobytes(), "the colour edit changed nothing"
+    stream.synchronize()
+    snap.destroy()
+    sel.destroy()
+    r.destroy()
+    sc.release()
+    return out
+
+
+def test_handles_destroyed_with_every_lazy_member_alive_three_cycles(gs, ob, device, stream):
+    first = _handle_cycle(gs, ob, device, stream)
+    for cycle in (2, 3):
+        again = _handle_cycle(gs, ob, device, stream)
+        for key, want in first.items():
+            assert again[key] == want, "cycle %d: %s differs from cycle 1" % (cycle, key)
+
+
+def test_timing_toggled_around_two_frames(gs, ob, device, stream):
+    """the timing events are made once, by the first set_timing(True); only frames rendered while it is on are counted"""
+    sc = Scene(gs, ob, device, stream, gs.SH_NONE, gs.COV3D_ROT_SCALE, ENQ_N, ENQ_W, ENQ_H)
+    r = gs.Renderer(device)
+    r.set_timing(True)
+    sc.render(r)
+    r.set_timing(False)
+    sc.render(r)
+    r.set_timing(True)
+    st = r.stats()
+    assert st.timed_frames == 1
+    assert st.stage_ms[8] > 0.0      # ST_FRAME: the whole timed frame
+    r.destroy()
+    sc.release()

@@ -72,8 +72,9 @@ struct FrameShape {
     }
 };
 
-struct gs_renderer {
-    gs_device *dev;
+struct gs_renderer : NoCopy {
+    ~gs_renderer() { if (last_order) gs_buffer_release(last_order); }
+    gs_device *dev = nullptr;
     DevArray order_r2, keep_bits, r2_scan, box_table;         // two-round frames: mirror slots of the Gaussians round 2 keeps, in depth order; one bit per slot
     DevArray recs, depth, rect, sorted_rect, exp_sums, cursors, chunk_tiles, chunk_vis, state, zero_region, scan_tmp, block_list;
     DevArray cull_status;                 // k_block_cull: one (tag << 10 | count) word per group of 256 blocks
@@ -100,24 +101,24 @@ struct gs_renderer {
     DevArray dkeys[2], dvals[2];          // (depth bits - bias, mirror slot), capacity N
     DevArray tkeys[2], tvals[2];          // (tile id, mirror slot), capacity pair_capacity
     DevArray ghist, digit_totals, bucket_starts;
-    gs::FrameResult *results;             // pinned, [2]: one per frame parity
-    uint32_t *host_counters;              // pinned: sizing pass total
-    uint64_t pair_capacity;
+    Pinned<gs::FrameResult> results;      // [2]: one per frame parity
+    Pinned<uint32_t> host_counters;       // sizing pass total
+    uint64_t pair_capacity = 0;
     FrameShape shape;
-    uint32_t gen;                         // frame generation (tags the pinned results)
-    hipEvent_t done[2];                   // end of the frame of each parity
-    bool done_valid[2];
-    uint32_t done_gen[2];
-    uint32_t done_shape[2];               // shape_epoch of the frame behind each done event
+    uint32_t gen = 0;                     // frame generation (tags the pinned results)
+    Event done[2];                        // end of the frame of each parity
+    bool done_valid[2] = {false, false};
+    uint32_t done_gen[2] = {0, 0};
+    uint32_t done_shape[2] = {0, 0};      // shape_epoch of the frame behind each done event
     uint32_t shape_epoch = 0;             // counts the changes of `shape` (a new epoch starts with a sizing frame)
     // last frame (host-side knowledge; V and D live in results[gen & 1])
-    uint64_t n;
-    uint32_t tiles_x, tiles_y, sort_passes;
-    uint32_t key_bias;
-    int dsorted_side, tsorted_side;
-    bool wide_tiles;  // tile keys are u32 (more than 65536 tiles) instead of u16
-    bool rect32;      // the last frame's tile rects are packed (gs::rect_pack32)
-    uint32_t launches;                    // kernel launches of the last frame (diagnostic)
+    uint64_t n = 0;
+    uint32_t tiles_x = 0, tiles_y = 0, sort_passes = 0;
+    uint32_t key_bias = 0;
+    int dsorted_side = 0, tsorted_side = 0;
+    bool wide_tiles = false;  // tile keys are u32 (more than 65536 tiles) instead of u16
+    bool rect32 = false;      // the last frame's tile rects are packed (gs::rect_pack32)
+    uint32_t launches = 0;                // kernel launches of the last frame (diagnostic)
     uint32_t *flags_target = nullptr;     // device word that receives every frame's flags (gs_renderer_set_frame_flags_target)
     // selection frames: the hide / tint masks in mirror-slot order, the per-block "fully hidden" flags,
     // and what each copy was gathered from (SlotMaskKey; generation 0 = nothing cached)
@@ -130,17 +131,17 @@ struct gs_renderer {
     DevArray sel_slots[2], sel_block_hidden;      // [0] hide, [1] tint
     SlotMaskKey sel_key[2];
     uint32_t width = 0, height = 0;       // image size of the last frame (gs_renderer_select_visible)
-    hipStream_t last_stream;
-    bool have_frame;                      // last_stream is meaningful (the null stream is a valid stream)
+    hipStream_t last_stream = nullptr;
+    bool have_frame = false;              // last_stream is meaningful (the null stream is a valid stream)
     bool last_stream_gone = false;        // ... but has been destroyed since (gs_stream_destroy recorded done[gen & 1] on it)
-    gs_buffer *last_order;   // mirror order of the last frame's buffer (null = index order), for the taps
+    gs_buffer *last_order = nullptr;      // a reference: mirror order of the last frame's buffer (null = index order), for the taps
     // timing
-    bool timing;
-    hipEvent_t ev[ST_COUNT + 2];
-    bool ev_valid;
-    bool ev_pending;
-    double stage_ms[ST_COUNT];
-    uint32_t timed_frames;
+    bool timing = false;
+    Event ev[ST_COUNT + 2];               // flags 0; made by the first gs_renderer_set_timing(1)
+    bool ev_valid = false;                // ... all of them
+    bool ev_pending = false;
+    double stage_ms[ST_COUNT] = {};
+    uint32_t timed_frames = 0;
 };
 
 // gs_stream_destroy: the end-of-frame event of every renderer whose last frame is on `st` is recorded now, and the
@@ -158,16 +159,16 @@ void gsh::renderers_leave_stream(gs_device *dev, hipStream_t st) {
 // gs_device_create: both digit widths of the sorts (256 and 512 counters per wave), the scatter's own access pattern
 bool gsh::probe_lds_atomic_order(hipStream_t st) {
     bool ordered = false;
-    uint32_t *bad = nullptr;
-    if (hipMalloc((void **)&bad, 4) == hipSuccess) {
+    {
+        DevMem mem;
         uint32_t h = 1;
-        if (hipMemset(bad, 0, 4) == hipSuccess) {
+        if (mem.alloc_raw(4) == hipSuccess && hipMemset(mem.ptr, 0, 4) == hipSuccess) {
+            uint32_t *bad = (uint32_t *)mem.ptr;
             hipLaunchKernelGGL(gs::k_probe_lds_atomic_order<8>, dim3(512), dim3(gs::SORT_THREADS), 0, st, 8u, 0x3D650001u, bad);
             hipLaunchKernelGGL(gs::k_probe_lds_atomic_order<9>, dim3(512), dim3(gs::SORT_THREADS), 0, st, 8u, 0x3D650002u, bad);
             if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(&h, bad, 4, hipMemcpyDeviceToHost) == hipSuccess) ordered = (h == 0);
         }
-        (void)hipFree(bad);
-    }
+    }      // (the word is freed before the sticky error of a failed step is dropped, as before)
     (void)hipGetLastError();
     return ordered;
 }
@@ -182,51 +183,22 @@ static hipError_t sync_last_frame(gs_renderer *r) {
 extern "C" gs_status gs_renderer_create(gs_device *dev, gs_renderer **out) {
     if (!out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
     GS_TRY(use_device(dev));
-    gs_renderer *r = new gs_renderer();
+    std::unique_ptr<gs_renderer> r(new gs_renderer());
     r->dev = dev;
-    r->host_counters = nullptr;
-    r->results = nullptr;
-    hipError_t e = hipHostMalloc((void **)&r->host_counters, 64, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess)
-        e = hipHostMalloc((void **)&r->results, 2 * sizeof(gs::FrameResult), hipHostMallocMapped | hipHostMallocCoherent);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        // no system-scope fence at the event: what the host reads after it (the frame result) lives in
-        // coherent pinned memory, and images are fetched with copies that synchronise by themselves
-        // (GS3D_EVENT_FENCE=1 asks for the fence)
-        e = hipEventCreateWithFlags(&r->done[i], hipEventDisableTiming | (switches().event_fence ? 0u : hipEventDisableSystemFence));
-        r->done_valid[i] = false;
-        r->done_gen[i] = 0;
-        r->done_shape[i] = 0;
-    }
-    if (e != hipSuccess) {
-        if (r->host_counters) (void)hipHostFree(r->host_counters);
-        if (r->results) (void)hipHostFree(r->results);
-        delete r;
-        return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "renderer allocation failed: %s", hipGetErrorString(e));
-    }
-    std::memset(r->results, 0, 2 * sizeof(gs::FrameResult));
-    r->pair_capacity = 0;
-    r->gen = 0;
-    r->n = 0;
-    r->tiles_x = r->tiles_y = r->sort_passes = 0;
-    r->key_bias = 0;
-    r->dsorted_side = r->tsorted_side = 0;
-    r->wide_tiles = false;
-    r->rect32 = false;
-    r->launches = 0;
-    r->last_stream = nullptr;
-    r->have_frame = false;
-    r->last_order = nullptr;
-    r->timing = false;
-    r->ev_valid = false;
-    r->ev_pending = false;
-    r->timed_frames = 0;
-    for (int i = 0; i < ST_COUNT; i++) r->stage_ms[i] = 0.0;
+    hipError_t e = r->host_counters.alloc(64, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) e = r->results.alloc(2 * sizeof(gs::FrameResult), hipHostMallocMapped | hipHostMallocCoherent);
+    // no system-scope fence at the event: what the host reads after it (the frame result) lives in
+    // coherent pinned memory, and images are fetched with copies that synchronise by themselves
+    // (GS3D_EVENT_FENCE=1 asks for the fence)
+    for (int i = 0; i < 2 && e == hipSuccess; i++)
+        e = r->done[i].create(hipEventDisableTiming | (switches().event_fence ? 0u : hipEventDisableSystemFence));
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "renderer allocation failed: %s", hipGetErrorString(e));
+    std::memset(r->results.ptr, 0, 2 * sizeof(gs::FrameResult));
     {
         std::lock_guard<std::mutex> lock(dev->renderers_mu);
-        dev->renderers.push_back(r);
+        dev->renderers.push_back(r.get());
     }
-    *out = r;
+    *out = r.release();
     return GS_OK;
 }
 
@@ -244,17 +216,6 @@ extern "C" void gs_renderer_destroy(gs_renderer *r) {
             }
     }
     (void)sync_last_frame(r);   // kernels of the last frame write pinned memory
-    DevArray *arrs[] = {&r->recs, &r->depth, &r->rect, &r->sorted_rect, &r->exp_sums, &r->cursors, &r->chunk_tiles, &r->chunk_vis,
-                        &r->state, &r->zero_region, &r->order_r2, &r->keep_bits, &r->r2_scan, &r->box_table, &r->scan_tmp, &r->block_list, &r->cull_status, &r->chunk_hist, &r->dkeys[0], &r->dkeys[1], &r->dvals[0],
-                        &r->dvals[1], &r->tkeys[0], &r->tkeys[1], &r->tvals[0], &r->tvals[1], &r->ghist,
-                        &r->digit_totals, &r->bucket_starts, &r->sel_slots[0], &r->sel_slots[1], &r->sel_block_hidden};
-    for (DevArray *a : arrs) dev_free(*a);
-    if (r->host_counters) (void)hipHostFree(r->host_counters);
-    if (r->results) (void)hipHostFree(r->results);
-    for (auto &e : r->done) (void)hipEventDestroy(e);
-    if (r->last_order) gs_buffer_release(r->last_order);
-    if (r->ev_valid)
-        for (auto &e : r->ev) (void)hipEventDestroy(e);
     delete r;
 }
 
@@ -262,7 +223,9 @@ extern "C" gs_status gs_renderer_set_timing(gs_renderer *r, int32_t enabled) {
     if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
     GS_TRY(use_device(r->dev));
     if (enabled && !r->ev_valid) {
-        for (auto &e : r->ev) GS_HIP(hipEventCreate(&e));
+        // (a call that failed half way left its events with their owners: this one makes the rest)
+        for (auto &e : r->ev)
+            if (!e) GS_HIP_AS("hipEventCreate(&e)", e.create(0));
         r->ev_valid = true;
     }
     r->timing = enabled != 0;
@@ -303,7 +266,7 @@ extern "C" gs_status gs_renderer_reset_stats(gs_renderer *r) {
 }
 
 // result block of the most recent frame (valid once its stream work has completed)
-static const gs::FrameResult &last_result(const gs_renderer *r) { return r->results[r->gen & 1u]; }
+static const gs::FrameResult &last_result(const gs_renderer *r) { return r->results.ptr[r->gen & 1u]; }
 
 extern "C" gs_status gs_renderer_wait_frame(gs_renderer *r, gs_frame_result *out) {
     if (!r) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null renderer");
@@ -1014,67 +977,48 @@ static gs_status build_spatial_order(gs_gaussians_buffer *g, hipStream_t st, siz
     gs_device *dev = g->buf->dev;
     const uint32_t n = (uint32_t)len, pod_words = (uint32_t)(pod_stride(g) / 4);
     DevArray keys[2], vals[2], gh, dt, partial, bbox;
-    gs_status rc = GS_OK;
-    for (int i = 0; i < 2 && rc == GS_OK; i++) {
-        rc = dev_reserve(keys[i], (size_t)n * 4);
-        if (rc == GS_OK) rc = dev_reserve(vals[i], (size_t)n * 4);
+    for (int i = 0; i < 2; i++) {
+        GS_TRY(dev_reserve(keys[i], (size_t)n * 4));
+        GS_TRY(dev_reserve(vals[i], (size_t)n * 4));
     }
     const uint32_t pgrid = n / 256u + 1u < 1024u ? n / 256u + 1u : 1024u;
-    if (rc == GS_OK) rc = dev_reserve(partial, (size_t)pgrid * 24);
-    if (rc == GS_OK) rc = dev_reserve(bbox, 24);
+    GS_TRY(dev_reserve(partial, (size_t)pgrid * 24));
+    GS_TRY(dev_reserve(bbox, 24));
+    // From here on every return, the last one too, frees scratch that the queued kernels may still use, and none waits
+    // for the stream first: it relies on hipFree synchronising the device, as this function always has.
+    hipLaunchKernelGGL(gs::k_bbox_partial, dim3(pgrid), dim3(256), 0, st, (const uint32_t *)g->buf->ptr,
+                       pod_words, n, (float *)partial.ptr);
+    bbox_final_enqueue(st, (const float *)partial.ptr, pgrid, (float *)bbox.ptr);
+    hipLaunchKernelGGL(gs::k_morton_keys, dim3((n + 255u) / 256u), dim3(256), 0, st,
+                       (const uint32_t *)g->buf->ptr, pod_words, n, (const float *)bbox.ptr,
+                       (uint32_t *)keys[0].ptr, (uint32_t *)vals[0].ptr);
+    void *k2[2] = {keys[0].ptr, keys[1].ptr};
+    void *v2[2] = {vals[0].ptr, vals[1].ptr};
     int side = 0;
     uint32_t passes = 0;
-    if (rc == GS_OK) {
-        hipLaunchKernelGGL(gs::k_bbox_partial, dim3(pgrid), dim3(256), 0, st, (const uint32_t *)g->buf->ptr,
-                           pod_words, n, (float *)partial.ptr);
-        bbox_final_enqueue(st, (const float *)partial.ptr, pgrid, (float *)bbox.ptr);
-        hipLaunchKernelGGL(gs::k_morton_keys, dim3((n + 255u) / 256u), dim3(256), 0, st,
-                           (const uint32_t *)g->buf->ptr, pod_words, n, (const float *)bbox.ptr,
-                           (uint32_t *)keys[0].ptr, (uint32_t *)vals[0].ptr);
-        void *k2[2] = {keys[0].ptr, keys[1].ptr};
-        void *v2[2] = {vals[0].ptr, vals[1].ptr};
-        rc = sort_pairs_device<uint32_t>(dev, k2, v2, gh, dt, n, 30, st, side, passes);
-    }
-    if (rc == GS_OK) {
-        // the sorted values ARE the order: keep that array as a ref-counted buffer, free the rest
-        gs_buffer *ob = new gs_buffer();
-        ob->dev = dev;
-        ob->ptr = vals[side].ptr;
-        ob->bytes = (size_t)n * 4;
-        ob->owned = true;
-        ob->refs.store(1);
-        vals[side].ptr = nullptr;
-        vals[side].bytes = 0;
-        if (g->order) gs_buffer_release(g->order);
-        g->order = ob;
-        if (g->inv) (void)hipFree(g->inv);
-        g->inv = nullptr;
-        hipError_t e = hipMalloc(&g->inv, (size_t)n * 4);
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_OUT_OF_MEMORY, (size_t)n * 4, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-        else
-            hipLaunchKernelGGL(gs::k_invert_order, dim3((n + 255u) / 256u), dim3(256), 0, st,
-                               (const uint32_t *)ob->ptr, n, (uint32_t *)g->inv);
-    }
-    if (rc == GS_OK && hipGetLastError() != hipSuccess) rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "spatial order launch failed");
-    // the scratch arrays may still be in use by the queued kernels: hipFree synchronises the device
-    for (int i = 0; i < 2; i++) {
-        dev_free(keys[i]);
-        dev_free(vals[i]);
-    }
-    for (DevArray *a : {&gh, &dt, &partial, &bbox}) dev_free(*a);
-    return rc;
+    GS_TRY(sort_pairs_device<uint32_t>(dev, k2, v2, gh, dt, n, 30, st, side, passes));
+    // the sorted values ARE the order: keep that array as a ref-counted buffer, free the rest
+    if (g->order) gs_buffer_release(g->order);
+    g->order = make_buffer(dev, vals[side].release(), (size_t)n * 4, true);
+    (void)g->inv.free();
+    const hipError_t e = g->inv.alloc_raw((size_t)n * 4);
+    if (e != hipSuccess) return gs_fail(GS_ERR_OUT_OF_MEMORY, (size_t)n * 4, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(gs::k_invert_order, dim3((n + 255u) / 256u), dim3(256), 0, st,
+                       (const uint32_t *)g->order->ptr, n, (uint32_t *)g->inv.ptr);
+    if (hipGetLastError() != hipSuccess) return gs_fail(GS_ERR_HIP, 0, 0, 0, "spatial order launch failed");
+    return GS_OK;
 }
 
 static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
     size_t len = gs_gaussians_buffer_len(g);
     size_t stride = (len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK * gs::PLANAR_BLOCK;   // whole blocks
     uint32_t chunks = (uint32_t)(pod_stride(g) / 16);
-    if (!g->planar || g->planar_stride != stride) {
-        if (g->planar) GS_HIP(hipFree(g->planar));
-        g->planar = nullptr;
-        if (g->block_bounds) GS_HIP(hipFree(g->block_bounds));
-        g->block_bounds = nullptr;
-        GS_HIP(hipMalloc(&g->planar, (stride ? stride : gs::PLANAR_BLOCK) * 16 * chunks));
+    if (!g->planar.ptr || g->planar_stride != stride) {
+        GS_HIP_AS("hipFree(g->planar)", g->planar.free());
+        GS_HIP_AS("hipFree(g->block_bounds)", g->block_bounds.free());
+        // (when this fails the mirror is gone and the stride stale: the next frame comes through here again)
+        GS_HIP_AS("hipMalloc(&g->planar, (stride ? stride : gs::PLANAR_BLOCK) * 16 * chunks)",
+                  g->planar.alloc_raw((stride ? stride : gs::PLANAR_BLOCK) * 16 * chunks));
         g->planar_stride = stride;
         g->mark_all();
     }
@@ -1103,8 +1047,7 @@ static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
             } else {
                 if (g->order) gs_buffer_release(g->order);
                 g->order = nullptr;
-                if (g->inv) GS_HIP(hipFree(g->inv));
-                g->inv = nullptr;
+                GS_HIP_AS("hipFree(g->inv)", g->inv.free());
             }
             lo = 0;
             hi = len;
@@ -1113,28 +1056,29 @@ static gs_status ensure_planar(gs_gaussians_buffer *g, hipStream_t st) {
         if (g->order && lo == 0 && hi == len) {
             uint32_t grid = (uint32_t)((count + gs::REPACK_GROUP - 1) / gs::REPACK_GROUP);
             hipLaunchKernelGGL(gs::k_repack_planar_ordered, dim3(grid), dim3(256), 0, st,
-                               (const uint4 *)g->buf->ptr, (uint4 *)g->planar, (const uint32_t *)g->order->ptr,
+                               (const uint4 *)g->buf->ptr, (uint4 *)g->planar.ptr, (const uint32_t *)g->order->ptr,
                                count, chunks);
         } else if (g->order) {
             uint64_t total = count * chunks;
             uint32_t grid = (uint32_t)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
             hipLaunchKernelGGL(gs::k_repack_planar_scatter, dim3(grid), dim3(256), 0, st,
-                               (const uint4 *)g->buf->ptr, (uint4 *)g->planar, (const uint32_t *)g->inv,
+                               (const uint4 *)g->buf->ptr, (uint4 *)g->planar.ptr, (const uint32_t *)g->inv.ptr,
                                (uint64_t)lo, count, chunks);
         } else {
             uint32_t grid = (uint32_t)((count + gs::REPACK_GROUP - 1) / gs::REPACK_GROUP);
             hipLaunchKernelGGL(gs::k_repack_planar, dim3(grid), dim3(256), 0, st,
-                               (const uint4 *)g->buf->ptr, (uint4 *)g->planar, (uint64_t)lo, count, chunks);
+                               (const uint4 *)g->buf->ptr, (uint4 *)g->planar.ptr, (uint64_t)lo, count, chunks);
         }
         GS_HIP(hipGetLastError());
         // per-block bounds for the preprocess kernels' block culling (recomputed for every block:
         // 48 bytes per Gaussian, cheaper than tracking which blocks a partial update touched)
         const uint32_t nblocks = (uint32_t)((len + gs::PLANAR_BLOCK - 1) / gs::PLANAR_BLOCK);
-        if (!g->block_bounds) GS_HIP(hipMalloc(&g->block_bounds, (stride / gs::PLANAR_BLOCK + 1) * 32));
+        if (!g->block_bounds.ptr)
+            GS_HIP_AS("hipMalloc(&g->block_bounds, (stride / gs::PLANAR_BLOCK + 1) * 32)", g->block_bounds.alloc_raw((stride / gs::PLANAR_BLOCK + 1) * 32));
         hipLaunchKernelGGL(k_tbl_block_bounds[g->sh][g->cov], dim3(nblocks), dim3(gs::PP_THREADS), 0, st,
-                           (const uint4 *)g->planar, (uint32_t)len, (float *)g->block_bounds);
+                           (const uint4 *)g->planar.ptr, (uint32_t)len, (float *)g->block_bounds.ptr);
         GS_HIP(hipGetLastError());
-        if (!g->mirror_ready) GS_HIP(hipEventCreateWithFlags(&g->mirror_ready, hipEventDisableTiming));
+        if (!g->mirror_ready) GS_HIP_AS("hipEventCreateWithFlags(&g->mirror_ready, hipEventDisableTiming)", g->mirror_ready.create());
         GS_HIP(hipEventRecord(g->mirror_ready, st));
         g->mirror_stream = st;
     } else if (g->mirror_ready && st != g->mirror_stream) {
@@ -1233,7 +1177,7 @@ static gsp::History read_history(gs_renderer *r) {
         } else if (!r->done_gen[i]) {
             continue;
         }
-        const gs::FrameResult &fr = r->results[i];
+        const gs::FrameResult &fr = r->results.ptr[i];
         // gen is published last with a system-scope release (publish_result): read it first — and once more behind the
         // fields (a frame two generations on may be overwriting the block while it is read)
         if (__atomic_load_n(&fr.gen, __ATOMIC_ACQUIRE) != r->done_gen[i]) continue;
@@ -1531,10 +1475,10 @@ static gs_status stage_block_cull(Frame &F, gs::PreOut &po) {
     r->cull_last_gen = gen;
     r->cull_last_groups = groups;
     if (F.sel.block_hidden)
-        hipLaunchKernelGGL(gs::k_block_cull<const uint32_t *>, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds, nchunks,
+        hipLaunchKernelGGL(gs::k_block_cull<const uint32_t *>, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds.ptr, nchunks,
                            F.fc, (uint32_t *)r->block_list.ptr, F.state, (uint32_t *)r->cull_status.ptr, tag, groups, F.sel.block_hidden);
     else
-        hipLaunchKernelGGL(gs::k_block_cull<>, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds, nchunks, F.fc,
+        hipLaunchKernelGGL(gs::k_block_cull<>, dim3(groups), dim3(256), 0, F.st, (const float *)F.g->block_bounds.ptr, nchunks, F.fc,
                            (uint32_t *)r->block_list.ptr, F.state, (uint32_t *)r->cull_status.ptr, tag, groups);
     GS_HIP(hipGetLastError());
     r->launches++;
@@ -1548,12 +1492,12 @@ static gs_status stage_block_cull(Frame &F, gs::PreOut &po) {
 // step; steady-state frames take the capacity from the history instead)
 static gs_status stage_sizing(Frame &F) {
     gs_renderer *r = F.r;
-    gs::ScanJob jt{(const uint32_t *)r->chunk_tiles.ptr, (uint32_t *)r->scan_tmp.ptr, r->host_counters, F.nchunks,
+    gs::ScanJob jt{(const uint32_t *)r->chunk_tiles.ptr, (uint32_t *)r->scan_tmp.ptr, r->host_counters.ptr, F.nchunks,
                    r->list_mode ? &F.state->list_blocks : nullptr};
     hipLaunchKernelGGL(gs::k_scan_chunks, dim3(1), dim3(1024), 0, F.st, jt, jt);
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(F.st));
-    const uint32_t d = r->host_counters[0];
+    const uint32_t d = r->host_counters.ptr[0];
     if (d == 0xffffffffu) {
         r->shape = FrameShape();
         return gs_fail(GS_ERR_PAIR_OVERFLOW, F.n, 0, 0,
@@ -1583,7 +1527,7 @@ static gs_status stage_selection(Frame &F) {
         if (k == 0) GS_TRY(dev_reserve(r->sel_block_hidden, F.nc * 4));
         if (!(key == r->sel_key[k])) {
             r->sel_key[k] = gs_renderer::SlotMaskKey();
-            hipLaunchKernelGGL(gs::k_selection_to_slots, dim3(F.nchunks), dim3(gs::PP_THREADS), 0, F.st, (const uint32_t *)sels[k]->words,
+            hipLaunchKernelGGL(gs::k_selection_to_slots, dim3(F.nchunks), dim3(gs::PP_THREADS), 0, F.st, sels[k]->bits(),
                                F.g->order ? (const uint32_t *)F.g->order->ptr : nullptr, F.n, (uint64_t *)r->sel_slots[k].ptr,
                                k == 0 ? (uint32_t *)r->sel_block_hidden.ptr : nullptr);
             GS_HIP(hipGetLastError());
@@ -1626,7 +1570,7 @@ static gs_status stage_preprocess(Frame &F) {
 
     F.fc.mask_culled_records = plan.mask_culled_records;
     F.fc.nt_loads = plan.nt_loads;
-    if (!plan.block_cull || !g->block_bounds) F.fc.cull_gain = 0.0f;
+    if (!plan.block_cull || !g->block_bounds.ptr) F.fc.cull_gain = 0.0f;
 
     gs::PreOut po;
     po.recs = (uint32_t *)r->recs.ptr;
@@ -1637,7 +1581,7 @@ static gs_status stage_preprocess(Frame &F) {
     po.zero_ptr = F.zero;
     po.zero_words = (uint32_t)zero_words;
     po.key_bias = F.near_bits;
-    po.block_bounds = (const float *)g->block_bounds;
+    po.block_bounds = (const float *)g->block_bounds.ptr;
     po.chunk_hist = (uint32_t *)r->chunk_hist.ptr;
     const bool top_hist = plan.depth_msd || plan.partition;      // the chunk rows count the TOP 10 bits (else the LSD sort's first digit)
     po.digit_mask = top_hist ? (1u << gs::MSD_TOP_BITS) - 1u : first_digit_mask(F.nums.dbits, depth_radix_bits(F.nums.dbits));
@@ -1650,10 +1594,10 @@ static gs_status stage_preprocess(Frame &F) {
     const int nt = F.fc.nt_loads ? 1 : 0;
     if (F.fs)
         hipLaunchKernelGGL((plan.banded ? k_tbl_preprocess_banded_sel[nt][switches().pre_serial ? 0 : 1] : k_tbl_preprocess_sel[nt])[g->sh][g->cov],
-                           dim3(F.nchunks), dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar, F.n, F.fc, po, F.sel);
+                           dim3(F.nchunks), dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar.ptr, F.n, F.fc, po, F.sel);
     else
         hipLaunchKernelGGL((plan.banded ? k_tbl_preprocess_banded[nt][switches().pre_serial ? 0 : 1] : k_tbl_preprocess[nt])[g->sh][g->cov], dim3(F.nchunks),
-                           dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar, F.n, F.fc, po);
+                           dim3(gs::PP_THREADS), 0, F.st, (const uint4 *)g->planar.ptr, F.n, F.fc, po);
     GS_HIP(hipGetLastError());
     r->launches++;
     F.marks.mark(ST_SCAN);
@@ -2039,7 +1983,7 @@ static gs_status render_frame(gs_renderer *r, gs_stream *s, gs_gaussians_buffer 
     F.sort.watch = switches().test_rank_watch_set ? switches().test_rank_watch : gen;
     DoneGuard done_guard{r, st, gen, switches().frame_event};
     F.state = (gs::FrameState *)r->state.ptr;
-    F.result = &r->results[gen & 1u];
+    F.result = &r->results.ptr[gen & 1u];
     r->n = n;
     r->tiles_x = fc.tiles_x;
     r->tiles_y = fc.tiles_y;
@@ -2401,38 +2345,26 @@ extern "C" gs_status gs_sort_pairs_u64(gs_device *dev, gs_stream *s, uint64_t *k
     GS_TRY(use_device(dev));
     if (!count) return GS_OK;
     hipStream_t st = stream_of(dev, s);
+    // (the returns after a failed copy or sort free with that work queued, as the common tail did: hipFree waits)
     DevArray k[2], v[2], gh, dt;
-    gs_status rc = GS_OK;
-    for (int i = 0; i < 2 && rc == GS_OK; i++) {
-        rc = dev_reserve(k[i], count * 8);
-        if (rc == GS_OK) rc = dev_reserve(v[i], count * 4);
+    for (int i = 0; i < 2; i++) {
+        GS_TRY(dev_reserve(k[i], count * 8));
+        GS_TRY(dev_reserve(v[i], count * 4));
     }
-    if (rc == GS_OK) {
-        hipError_t e = hipMemcpyAsync(k[0].ptr, keys, count * 8, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(v[0].ptr, values, count * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
-    }
+    hipError_t e = hipMemcpyAsync(k[0].ptr, keys, count * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(v[0].ptr, values, count * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
     int side = 0;
     uint32_t passes = 0;
-    if (rc == GS_OK) {
-        void *k2[2] = {k[0].ptr, k[1].ptr};
-        void *v2[2] = {v[0].ptr, v[1].ptr};
-        rc = sort_pairs_device<uint64_t>(dev, k2, v2, gh, dt, (uint32_t)count, end_bit, st, side, passes);
-    }
-    if (rc == GS_OK) {
-        hipError_t e = hipMemcpyAsync(keys, k[side].ptr, count * 8, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(values, v[side].ptr, count * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    }
-    for (int i = 0; i < 2; i++) {
-        dev_free(k[i]);
-        dev_free(v[i]);
-    }
-    dev_free(gh);
-    dev_free(dt);
-    return rc;
+    void *k2[2] = {k[0].ptr, k[1].ptr};
+    void *v2[2] = {v[0].ptr, v[1].ptr};
+    GS_TRY(sort_pairs_device<uint64_t>(dev, k2, v2, gh, dt, (uint32_t)count, end_bit, st, side, passes));
+    e = hipMemcpyAsync(keys, k[side].ptr, count * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(values, v[side].ptr, count * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+    return GS_OK;
 }
 
 namespace gs {
@@ -2483,29 +2415,27 @@ extern "C" gs_status gs_exclusive_scan_u32(gs_device *dev, gs_stream *s, const u
     uint32_t n = (uint32_t)count;
     uint32_t nchunks = (n + gs::PP_CHUNK - 1) / gs::PP_CHUNK;
     DevArray din, dout, sums, offs, tot;
-    gs_status rc = dev_reserve(din, count * 4);
-    if (rc == GS_OK) rc = dev_reserve(dout, count * 4);
-    if (rc == GS_OK) rc = dev_reserve(sums, (size_t)nchunks * 4);
-    if (rc == GS_OK) rc = dev_reserve(offs, (size_t)nchunks * 4);
-    if (rc == GS_OK) rc = dev_reserve(tot, 16);
+    GS_TRY(dev_reserve(din, count * 4));
+    GS_TRY(dev_reserve(dout, count * 4));
+    GS_TRY(dev_reserve(sums, (size_t)nchunks * 4));
+    GS_TRY(dev_reserve(offs, (size_t)nchunks * 4));
+    GS_TRY(dev_reserve(tot, 16));
     uint32_t total = 0;
-    if (rc == GS_OK) {
-        hipError_t e = hipMemcpyAsync(din.ptr, in, count * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(gs::k_chunk_sums, dim3(nchunks), dim3(gs::PP_THREADS), 0, st,
-                               (const uint32_t *)din.ptr, n, (uint32_t *)sums.ptr);
-            scan_chunks_enqueue(st, (const uint32_t *)sums.ptr, (uint32_t *)offs.ptr, (uint32_t *)tot.ptr, nchunks);
-            hipLaunchKernelGGL(gs::k_chunk_scan_write, dim3(nchunks), dim3(gs::PP_THREADS), 0, st,
-                               (const uint32_t *)din.ptr, (const uint32_t *)offs.ptr, n,
-                               (uint32_t *)dout.ptr);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, count * 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(&total, tot.ptr, 4, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "scan failed: %s", hipGetErrorString(e));
+    hipError_t e = hipMemcpyAsync(din.ptr, in, count * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(gs::k_chunk_sums, dim3(nchunks), dim3(gs::PP_THREADS), 0, st,
+                           (const uint32_t *)din.ptr, n, (uint32_t *)sums.ptr);
+        scan_chunks_enqueue(st, (const uint32_t *)sums.ptr, (uint32_t *)offs.ptr, (uint32_t *)tot.ptr, nchunks);
+        hipLaunchKernelGGL(gs::k_chunk_scan_write, dim3(nchunks), dim3(gs::PP_THREADS), 0, st,
+                           (const uint32_t *)din.ptr, (const uint32_t *)offs.ptr, n,
+                           (uint32_t *)dout.ptr);
+        e = hipGetLastError();
     }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout.ptr, count * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, tot.ptr, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    // (a failure frees with that work queued, as the common tail did: hipFree waits.  *total_out stays 0 then.)
+    if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "scan failed: %s", hipGetErrorString(e));
     if (total_out) *total_out = total;
-    for (DevArray *a : {&din, &dout, &sums, &offs, &tot}) dev_free(*a);
-    return rc;
+    return GS_OK;
 }

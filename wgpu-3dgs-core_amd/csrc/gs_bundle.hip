@@ -20,18 +20,30 @@ typedef void (*bundle_kernel_fn)(gs::BundleArgs, uint32_t);
 static bundle_kernel_fn k_tbl_test_gaussian[4][3] = GS_CFG_TABLE(gs::k_test_gaussian);
 static bundle_kernel_fn k_tbl_unpack_soa[4][3] = GS_CFG_TABLE(gs::k_unpack_soa);
 
-struct gs_bundle {
-    gs_device *dev;
+static void release_group(std::vector<gs_buffer *> &g) {
+    for (gs_buffer *x : g) gs_buffer_release(x);
+    g.clear();
+}
+
+struct gs_bundle : NoCopy {
+    ~gs_bundle() {
+        for (auto &g : groups) release_group(g);
+        if (module) {
+            (void)hipSetDevice(dev->ordinal);
+            (void)hipModuleUnload(module);
+        }
+    }
+    gs_device *dev = nullptr;
     std::string label;
-    gs_kernel_id kernel;
-    int sh, cov;
-    uint32_t workgroup_size;
+    gs_kernel_id kernel = GS_KERNEL_COUNT_;
+    int sh = 0, cov = 0;
+    uint32_t workgroup_size = 0;
     std::vector<uint32_t> layout;                     // bindings per group
     std::vector<std::vector<gs_buffer *>> groups;     // managed bind groups (retained)
-    bool managed;
-    bool has_additional_constant;
-    uint32_t additional_constant;
-    uint32_t last_workgroups;
+    bool managed = false;
+    bool has_additional_constant = false;
+    uint32_t additional_constant = 0;
+    uint32_t last_workgroups = 0;
     // bundles compiled from source (gs_bundle_create_from_source)
     bool from_source = false;
     hipModule_t module = nullptr;
@@ -66,10 +78,6 @@ extern "C" gs_status gs_bundle_create(gs_device *dev, const gs_bundle_desc *desc
     b->cov = desc->cov;
     b->workgroup_size = wg;
     b->layout.assign(desc->bindings_per_group, desc->bindings_per_group + desc->bind_group_count);
-    b->managed = false;
-    b->has_additional_constant = false;
-    b->additional_constant = 0;
-    b->last_workgroups = 0;
     for (uint32_t i = 0; i < desc->constant_count; i++) {
         if (desc->constant_names && desc->constant_names[i] &&
             !std::strcmp(desc->constant_names[i], "additional_constant")) {
@@ -79,11 +87,6 @@ extern "C" gs_status gs_bundle_create(gs_device *dev, const gs_bundle_desc *desc
     }
     *out = b;
     return GS_OK;
-}
-
-static void release_group(std::vector<gs_buffer *> &g) {
-    for (gs_buffer *x : g) gs_buffer_release(x);
-    g.clear();
 }
 
 extern "C" gs_status gs_bundle_set_bind_group(gs_bundle *b, uint32_t index, gs_buffer *const *buffers,
@@ -112,37 +115,24 @@ extern "C" gs_status gs_bundle_create_with_bind_groups(gs_device *dev, const gs_
                                                        const uint32_t *resource_counts,
                                                        uint32_t resource_group_count,
                                                        gs_bundle **out) {
-    gs_bundle *b = nullptr;
-    GS_TRY(gs_bundle_create(dev, desc, &b));
+    gs_bundle *created = nullptr;
+    GS_TRY(gs_bundle_create(dev, desc, &created));
+    std::unique_ptr<gs_bundle> b(created);
     // compute_bundle.rs:161-168
-    if (resource_group_count != b->layout.size()) {
-        size_t layouts = b->layout.size();
-        gs_bundle_destroy(b);
-        return gs_fail(GS_ERR_RESOURCE_COUNT_MISMATCH, resource_group_count, layouts, 0,
+    if (resource_group_count != b->layout.size())
+        return gs_fail(GS_ERR_RESOURCE_COUNT_MISMATCH, resource_group_count, b->layout.size(), 0,
                     "resource count and bind group layout count mismatch: %u != %zu",
-                    resource_group_count, layouts);
-    }
+                    resource_group_count, b->layout.size());
     b->managed = true;
     b->groups.resize(b->layout.size());
-    for (uint32_t i = 0; i < resource_group_count; i++) {
-        gs_status st = gs_bundle_set_bind_group(b, i, resources[i], resource_counts[i]);
-        if (st != GS_OK) {
-            gs_bundle_destroy(b);
-            return st;
-        }
-    }
-    *out = b;
+    for (uint32_t i = 0; i < resource_group_count; i++)
+        GS_TRY(gs_bundle_set_bind_group(b.get(), i, resources[i], resource_counts[i]));
+    *out = b.release();
     return GS_OK;
 }
 
 extern "C" void gs_bundle_destroy(gs_bundle *b) {
-    if (!b) return;
-    for (auto &g : b->groups) release_group(g);
-    if (b->module) {
-        (void)hipSetDevice(b->dev->ordinal);
-        (void)hipModuleUnload(b->module);
-    }
-    delete b;
+    delete b;      // (takes the device only when there is a module to unload, as it always did)
 }
 
 extern "C" gs_status gs_bundle_create_from_source(gs_device *dev, const gs_bundle_source_desc *desc,
@@ -217,27 +207,20 @@ extern "C" gs_status gs_bundle_create_from_source(gs_device *dev, const gs_bundl
     (void)hiprtcGetCode(prog, code.data());
     (void)hiprtcDestroyProgram(&prog);
 
-    gs_bundle *b = new gs_bundle();
+    std::unique_ptr<gs_bundle> b(new gs_bundle());
     b->dev = dev;
     b->label = desc->label ? desc->label : "";
-    b->kernel = GS_KERNEL_COUNT_;
     b->sh = desc->sh;
     b->cov = desc->cov;
     b->workgroup_size = wg;
     b->layout.assign(desc->bindings_per_group, desc->bindings_per_group + desc->bind_group_count);
-    b->managed = false;
-    b->has_additional_constant = false;
-    b->additional_constant = 0;
-    b->last_workgroups = 0;
     b->from_source = true;
     hipError_t he = hipModuleLoadData(&b->module, code.data());
     if (he == hipSuccess) he = hipModuleGetFunction(&b->func, b->module, entry.c_str());
-    if (he != hipSuccess) {
-        gs_bundle_destroy(b);
+    if (he != hipSuccess)
         return gs_fail(GS_ERR_MISSING_ENTRY_POINT, (uint64_t)he, 0, 0, "entry point '%s' not found in the compiled module: %s",
                     desc->entry_point, hipGetErrorString(he));
-    }
-    *out = b;
+    *out = b.release();
     return GS_OK;
 }
 

@@ -110,11 +110,11 @@ static gs_status select_by_component(gs_selection *sel, gs_stream *s, gs_gaussia
         return GS_OK;
     }
     uint32_t *plane = nullptr;
-    gs_status rc = components_enqueue(g, st, among, mt, radius, nullptr, nullptr, nullptr, connected ? (const uint32_t *)seeds->words : nullptr,
+    gs_status rc = components_enqueue(g, st, among, mt, radius, nullptr, nullptr, nullptr, connected ? seeds->bits() : nullptr,
                                       &plane);
     if (rc == GS_OK) {      // only now does `sel` change; the seeds (which may be `sel`) were read by an earlier launch
         sel->generation = next_object_id();
-        hipLaunchKernelGGL(gs::k_cc_select, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)plane, n, lo, hi, sel->words,
+        hipLaunchKernelGGL(gs::k_cc_select, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)plane, n, lo, hi, sel->bits(),
                            (uint32_t)op);
         if (hipGetLastError() != hipSuccess) rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "k_cc_select could not be launched");
     }

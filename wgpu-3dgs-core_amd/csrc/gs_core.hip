@@ -294,20 +294,19 @@ extern "C" gs_status gs_device_create(int32_t ordinal, gs_device **out) {
     GS_HIP(hipGetDeviceProperties(&props, ordinal));
     gs_device *d = new gs_device();
     d->ordinal = ordinal;
-    std::memset(&d->limits, 0, sizeof(d->limits));
     d->limits.max_compute_workgroup_size_x = (uint32_t)props.maxThreadsDim[0];
     d->limits.max_compute_invocations_per_workgroup = (uint32_t)props.maxThreadsPerBlock;
     d->limits.compute_units = (uint32_t)props.multiProcessorCount;
     d->limits.wavefront_size = (uint32_t)props.warpSize;
     d->limits.total_memory_bytes = (uint64_t)props.totalGlobalMem;
     std::snprintf(d->limits.arch_name, sizeof(d->limits.arch_name), "%s", props.gcnArchName);
-    hipError_t se = hipStreamCreateWithFlags(&d->internal, hipStreamNonBlocking);
+    hipError_t se = d->internal.create();
     if (se != hipSuccess) {
         delete d;
         return gs_fail(GS_ERR_HIP, (uint64_t)se, 0, 0, "hipStreamCreate failed: %s", hipGetErrorString(se));
     }
     // the LDS-atomic ordering the fast radix ranking relies on
-    d->lds_atomic_ordered = !env_now("GS3D_DISABLE_FAST_RANK") && probe_lds_atomic_order(d->internal);
+    d->lds_atomic_ordered = !env_now("GS3D_DISABLE_FAST_RANK") && probe_lds_atomic_order(d->internal.s);
     *out = d;
     return GS_OK;
 }
@@ -317,8 +316,6 @@ extern "C" int32_t gs_device_fast_rank(const gs_device *dev) { return dev && dev
 extern "C" void gs_device_destroy(gs_device *dev) {
     if (!dev) return;
     (void)hipSetDevice(dev->ordinal);
-    (void)hipStreamDestroy(dev->internal);
-    dev_free(dev->metrics_scratch);
     delete dev;
 }
 
@@ -339,7 +336,7 @@ extern "C" gs_status gs_stream_create(gs_device *dev, gs_stream **out) {
     GS_TRY(use_device(dev));
     hipStream_t s;
     GS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    *out = new gs_stream{dev, s, true};
+    *out = new gs_stream(dev, s, true);
     return GS_OK;
 }
 
@@ -362,13 +359,13 @@ extern "C" gs_status gs_stream_create_with_priority(gs_device *dev, int32_t prio
                     priority, lo, hi);
     hipStream_t s;
     GS_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority));
-    *out = new gs_stream{dev, s, true};
+    *out = new gs_stream(dev, s, true);
     return GS_OK;
 }
 
 extern "C" gs_status gs_stream_wrap(gs_device *dev, void *hip_stream, gs_stream **out) {
     if (!dev || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
-    *out = new gs_stream{dev, (hipStream_t)hip_stream, false};
+    *out = new gs_stream(dev, (hipStream_t)hip_stream, false);
     return GS_OK;
 }
 
@@ -388,48 +385,32 @@ extern "C" void gs_stream_destroy(gs_stream *s) {
     // (gs_stream_wrap): destroy the gs_stream BEFORE the hipStream_t it wraps.
     (void)hipSetDevice(s->dev->ordinal);
     renderers_leave_stream(s->dev, s->s);
-    if (s->owned) {
-        (void)hipSetDevice(s->dev->ordinal);
-        (void)hipStreamDestroy(s->s);
-    }
     delete s;
 }
 
 gs_buffer *gsh::make_buffer(gs_device *dev, void *ptr, size_t bytes, bool owned) {
-    gs_buffer *b = new gs_buffer();
-    b->dev = dev;
-    b->ptr = ptr;
-    b->bytes = bytes;
-    b->owned = owned;
-    b->refs.store(1);
-    return b;
+    return new gs_buffer{dev, ptr, bytes, owned};
 }
 
 extern "C" gs_status gs_buffer_create(gs_device *dev, size_t bytes, const void *init,
                                       gs_buffer **out) {
     if (!out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null out");
     GS_TRY(use_device(dev));
-    void *p = nullptr;
+    DevMem p;
     // a zero-sized wgpu buffer is legal; keep a 16-byte allocation so the pointer is valid
-    GS_HIP(hipMalloc(&p, bytes ? bytes : 16));
+    GS_HIP_AS("hipMalloc(&p, bytes ? bytes : 16)", p.alloc_raw(bytes ? bytes : 16));
     if (init && bytes) {
-        hipError_t e = hipMemcpy(p, init, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemcpy failed: %s", hipGetErrorString(e));
-        }
+        hipError_t e = hipMemcpy(p.ptr, init, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemcpy failed: %s", hipGetErrorString(e));
     } else if (bytes) {
         // wgpu zero-initialises new buffers.  hipMemset of device memory runs on the null stream and may return before it
         // has run; the caller's streams are non-blocking and do not wait for that stream, so the fill is awaited here —
         // or it may land on top of what the caller writes next
-        hipError_t e = hipMemset(p, 0, bytes);
+        hipError_t e = hipMemset(p.ptr, 0, bytes);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemset failed: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "hipMemset failed: %s", hipGetErrorString(e));
     }
-    *out = make_buffer(dev, p, bytes, true);
+    *out = make_buffer(dev, p.release(), bytes, true);
     return GS_OK;
 }
 
@@ -498,33 +479,26 @@ extern "C" gs_status gs_buffer_download(gs_buffer *b, gs_stream *s, void *dst, s
 // BufferWrapper::prepare_download / map_download (src/buffer/mod.rs:48-101): the copy into a
 // host-visible staging buffer is only ENQUEUED; the caller maps (waits for) it later.
 struct gs_download {
-    gs_device *dev;
-    void *pinned;
-    size_t bytes;
-    hipEvent_t done;
+    gs_device *dev = nullptr;
+    size_t bytes = 0;
+    Event done;
+    Pinned<void> pinned;
 };
 
 extern "C" gs_status gs_buffer_prepare_download(gs_buffer *b, gs_stream *s, gs_download **out) {
     if (!b || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     *out = nullptr;
     GS_TRY(use_device(b->dev));
-    gs_download *d = new gs_download();
+    std::unique_ptr<gs_download> d(new gs_download());
     d->dev = b->dev;
     d->bytes = b->bytes;
-    d->pinned = nullptr;
-    hipError_t e = hipHostMalloc(&d->pinned, b->bytes ? b->bytes : 1, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->done, hipEventDisableTiming);
-    else d->done = nullptr;
+    hipError_t e = d->pinned.alloc(b->bytes ? b->bytes : 1, hipHostMallocDefault);
+    if (e == hipSuccess) e = d->done.create();
     hipStream_t st = stream_of(b->dev, s);
-    if (e == hipSuccess && b->bytes) e = hipMemcpyAsync(d->pinned, b->ptr, b->bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && b->bytes) e = hipMemcpyAsync(d->pinned.ptr, b->ptr, b->bytes, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipEventRecord(d->done, st);
-    if (e != hipSuccess) {
-        if (d->pinned) (void)hipHostFree(d->pinned);
-        if (d->done) (void)hipEventDestroy(d->done);
-        delete d;
-        return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    }
-    *out = d;
+    if (e != hipSuccess) return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
+    *out = d.release();
     return GS_OK;
 }
 
@@ -542,7 +516,7 @@ extern "C" gs_status gs_download_map(gs_download *d, const void **data_out, size
     const hipError_t e = hipEventSynchronize(d->done);
     if (e != hipSuccess)
         return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
-    *data_out = d->pinned;
+    *data_out = d->pinned.ptr;
     if (bytes_out) *bytes_out = d->bytes;
     return GS_OK;
 }
@@ -551,8 +525,6 @@ extern "C" void gs_download_release(gs_download *d) {
     if (!d) return;
     (void)hipSetDevice(d->dev->ordinal);
     (void)hipEventSynchronize(d->done);     // the copy may still be writing the staging memory
-    (void)hipHostFree(d->pinned);
-    (void)hipEventDestroy(d->done);
     delete d;
 }
 
@@ -571,12 +543,6 @@ gs_status gsh::dev_reserve(DevArray &a, size_t bytes) {
     return GS_OK;
 }
 
-void gsh::dev_free(DevArray &a) {
-    if (a.ptr) (void)hipFree(a.ptr);
-    a.ptr = nullptr;
-    a.bytes = 0;
-}
-
 gs_status gsh::dev_alloc(void **out, size_t bytes, uint64_t b, const char *what) {
     *out = nullptr;
     const hipError_t e = hipMalloc(out, bytes);
@@ -591,7 +557,7 @@ gs_status gsh::wait_for_edits(const gs_gaussians_buffer *g, hipStream_t st) {
 }
 
 gs_status gsh::record_edit(gs_gaussians_buffer *g, hipStream_t st) {
-    if (!g->edit_done) GS_HIP(hipEventCreateWithFlags(&g->edit_done, hipEventDisableTiming));
+    if (!g->edit_done) GS_HIP_AS("hipEventCreateWithFlags(&g->edit_done, hipEventDisableTiming)", g->edit_done.create());
     GS_HIP(hipEventRecord(g->edit_done, st));
     g->edit_stream = st;
     return GS_OK;
@@ -604,7 +570,7 @@ gs_status gsh::records_check(const gs_gaussians_buffer *g, const gs_stream *s, c
     a.dev = g->buf->dev;
     a.n = (uint32_t)a.len;
     a.nblocks = (a.n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
-    a.words = sel ? (const uint32_t *)sel->words : nullptr;
+    a.words = sel ? sel->bits() : nullptr;
     a.inv = invert ? 1u : 0u;
     return GS_OK;
 }
@@ -644,17 +610,10 @@ extern "C" gs_status gs_gaussians_buffer_from_buffer(gs_buffer *buffer, gs_sh_co
     g->buf = gs_buffer_retain(buffer);
     g->sh = sh;
     g->cov = cov;
-    g->planar = nullptr;
-    g->planar_stride = 0;
     {   // default: spatial order on; GS3D_SPATIAL_ORDER=0 keeps the mirror in index order
         const char *e = env_now("GS3D_SPATIAL_ORDER");
         g->spatial = !(e && e[0] == '0');
     }
-    g->order = nullptr;
-    g->inv = nullptr;
-    g->block_bounds = nullptr;
-    g->partial_since_order = 0;
-    g->mark_all();
     *out = g;
     return GS_OK;
 }
@@ -792,15 +751,15 @@ static gs_status decode_spz_payload(gs_device *dev, const void *bytes, const gs_
     DevMem staging;
     hipError_t e = staging.alloc_raw(used);
     if (e != hipSuccess) return gs_fail(GS_ERR_OUT_OF_MEMORY, used, 0, 0, "hipMalloc failed: %s", hipGetErrorString(e));
-    if ((e = hipMemcpyAsync(staging.ptr, bytes, used, hipMemcpyHostToDevice, dev->internal)) != hipSuccess)
+    if ((e = hipMemcpyAsync(staging.ptr, bytes, used, hipMemcpyHostToDevice, dev->internal.s)) != hipSuccess)
         return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "upload failed: %s", hipGetErrorString(e));
     const uint8_t *b = (const uint8_t *)staging.ptr;
     gs::SpzView v{b + off[0], b + off[1], b + off[2], b + off[3], b + off[4], b + off[5], h.version, h.fractional_bits, ncoef};
     const uint64_t groups = ((uint64_t)n + gs::PACK_GROUP - 1) / gs::PACK_GROUP;
-    hipLaunchKernelGGL(k_tbl_from_spz[dst->sh][dst->cov], dim3((uint32_t)groups), dim3(256), 0, dev->internal, v, (uint64_t)n,
+    hipLaunchKernelGGL(k_tbl_from_spz[dst->sh][dst->cov], dim3((uint32_t)groups), dim3(256), 0, dev->internal.s, v, (uint64_t)n,
                        (uint32_t *)dst->buf->ptr);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(dev->internal);      // (the staging memory is freed at the return)
+    if (e == hipSuccess) e = hipStreamSynchronize(dev->internal.s);      // (the staging memory is freed at the return)
     if (e != hipSuccess) return gs_fail(GS_ERR_HIP, (uint64_t)e, 0, 0, "SPZ decode kernel failed: %s", hipGetErrorString(e));
     return GS_OK;
 }
@@ -866,16 +825,6 @@ extern "C" gs_status gs_gaussians_buffer_create_from_gaussians(gs_device *dev, g
 extern "C" void gs_gaussians_buffer_destroy(gs_gaussians_buffer *g) {
     if (!g) return;
     (void)hipSetDevice(g->buf->dev->ordinal);
-    if (g->planar) (void)hipFree(g->planar);
-    if (g->inv) (void)hipFree(g->inv);
-    if (g->block_bounds) (void)hipFree(g->block_bounds);
-    if (g->concat_offsets) (void)hipFree(g->concat_offsets);
-    for (DevArray *a : {&g->stats_scratch, &g->nb_scratch, &g->nb_ghist, &g->nb_digit_totals}) dev_free(*a);
-    if (g->nb_done) (void)hipEventDestroy(g->nb_done);
-    if (g->mirror_ready) (void)hipEventDestroy(g->mirror_ready);
-    if (g->edit_done) (void)hipEventDestroy(g->edit_done);
-    if (g->order) gs_buffer_release(g->order);
-    gs_buffer_release(g->buf);
     delete g;
 }
 

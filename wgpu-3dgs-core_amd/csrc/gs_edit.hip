@@ -228,24 +228,22 @@ extern "C" gs_status gs_gaussians_buffer_create_from_selection(gs_gaussians_buff
 // The records of one selection of one buffer, with what restoring them needs: its own copy of the mask and the first
 // snapshot rank of every 1024-block (the exclusive scan of the per-block counts).
 struct gs_snapshot {
-    gs_device *dev;
-    int sh, cov;
-    size_t n, nwords, nblocks;
-    uint64_t count;
-    uint32_t *meta;          // device: nwords mask words, nblocks offsets, the scan's total (one allocation)
-    size_t meta_bytes;
-    void *records;           // device: count records; null while count == 0
-    const uint32_t *words() const { return meta; }
-    uint32_t *offsets() const { return meta + nwords; }
-    uint32_t *total() const { return meta + nwords + nblocks; }
+    gs_device *dev = nullptr;
+    int sh = 0, cov = 0;
+    size_t n = 0, nwords = 0, nblocks = 0;
+    uint64_t count = 0;
+    DevMem meta;             // nwords mask words, nblocks offsets, the scan's total (one allocation)
+    size_t meta_bytes = 0;
+    DevMem records;          // count records; null while count == 0
+    uint32_t *words() const { return (uint32_t *)meta.ptr; }
+    uint32_t *offsets() const { return words() + nwords; }
+    uint32_t *total() const { return words() + nwords + nblocks; }
 };
 
 extern "C" void gs_snapshot_destroy(gs_snapshot *snap) {
     if (!snap) return;
     (void)hipSetDevice(snap->dev->ordinal);
-    if (snap->records) (void)hipFree(snap->records);      // (synchronises the device: a restore in flight finishes first)
-    if (snap->meta) (void)hipFree(snap->meta);
-    delete snap;
+    delete snap;      // (hipFree synchronises the device: a restore in flight finishes first)
 }
 
 extern "C" size_t gs_snapshot_len(const gs_snapshot *snap) { return snap ? snap->n : 0; }
@@ -255,19 +253,19 @@ extern "C" size_t gs_snapshot_bytes(const gs_snapshot *snap) {
 }
 
 // the mask, the scan and the selected records of `g` into an empty snapshot; blocks on r.st.  What it allocates is the
-// snapshot's: the caller destroys that when this fails.
+// snapshot's: the caller deletes that when this fails.
 static gs_status snapshot_fill(const gs_gaussians_buffer *g, const RecordsAccess &r, gs_snapshot *snap) {
-    GS_TRY(dev_alloc((void **)&snap->meta, snap->meta_bytes, 0, "snapshot allocation"));
+    GS_TRY(snap->meta.alloc(snap->meta_bytes, 0, "snapshot allocation"));
     if (!r.n) return GS_OK;
     const uint32_t nwords = (uint32_t)snap->nwords;
     // the mask is copied first and everything below reads the copy: the snapshot does not depend on the selection afterwards
-    hipLaunchKernelGGL(gs::k_snapshot_mask, dim3((nwords + 255u) / 256u), dim3(256), 0, r.st, snap->meta, r.words, nwords, r.n);
+    hipLaunchKernelGGL(gs::k_snapshot_mask, dim3((nwords + 255u) / 256u), dim3(256), 0, r.st, snap->words(), r.words, nwords, r.n);
     uint32_t total = 0;
     GS_TRY(extract_scan(r.st, snap->words(), r.n, 0u, snap->offsets(), snap->total(), &total));
     if (!total) return GS_OK;
     const size_t bytes = (size_t)total * pod_stride(g);
-    GS_TRY(dev_alloc(&snap->records, bytes, bytes, "hipMalloc"));
-    extract_copy_enqueue(r.st, g->buf->ptr, snap->records, snap->words(), r.n, 0u, snap->offsets(), (uint32_t)(pod_stride(g) / 16), total);
+    GS_TRY(snap->records.alloc(bytes, bytes, "hipMalloc"));
+    extract_copy_enqueue(r.st, g->buf->ptr, snap->records.ptr, snap->words(), r.n, 0u, snap->offsets(), (uint32_t)(pod_stride(g) / 16), total);
     hipError_t e = hipGetLastError();
     // the call is blocking anyway; a restore on any stream may follow at once
     if (e == hipSuccess) e = hipStreamSynchronize(r.st);
@@ -281,23 +279,16 @@ extern "C" gs_status gs_gaussians_buffer_snapshot(gs_gaussians_buffer *g, gs_str
     if (!g || !out) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "null argument");
     RecordsAccess r;
     GS_TRY(records_access(g, s, sel, 0, r));
-    gs_snapshot *snap = new gs_snapshot();
+    std::unique_ptr<gs_snapshot> snap(new gs_snapshot());
     snap->dev = r.dev;
     snap->sh = g->sh;
     snap->cov = g->cov;
     snap->n = r.len;
     snap->nwords = (r.len + 31) / 32;
     snap->nblocks = r.nblocks;
-    snap->count = 0;
-    snap->meta = nullptr;
-    snap->records = nullptr;
     snap->meta_bytes = (snap->nwords + snap->nblocks + 1) * 4;
-    const gs_status rc = snapshot_fill(g, r, snap);
-    if (rc != GS_OK) {
-        gs_snapshot_destroy(snap);
-        return rc;
-    }
-    *out = snap;
+    GS_TRY(snapshot_fill(g, r, snap.get()));
+    *out = snap.release();
     return GS_OK;
 }
 
@@ -327,10 +318,10 @@ extern "C" gs_status gs_gaussians_buffer_restore(gs_gaussians_buffer *g, gs_stre
     GS_TRY(wait_for_edits(g, st));
     const uint32_t n = (uint32_t)len, nc = (uint32_t)(pod_stride(g) / 16), count = (uint32_t)snap->count;
     if (exchange)
-        hipLaunchKernelGGL(gs::k_restore<true>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records,
+        hipLaunchKernelGGL(gs::k_restore<true>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records.ptr,
                            snap->words(), n, (const uint32_t *)snap->offsets(), nc, count);
     else
-        hipLaunchKernelGGL(gs::k_restore<false>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records,
+        hipLaunchKernelGGL(gs::k_restore<false>, dim3((n + 255u) / 256u), dim3(256), 0, st, (uint4 *)g->buf->ptr, (uint4 *)snap->records.ptr,
                            snap->words(), n, (const uint32_t *)snap->offsets(), nc, count);
     GS_HIP(hipGetLastError());
     GS_TRY(record_edit(g, st));

@@ -13,19 +13,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #include "gs_kernel_lib.h"
 #include "gs_policy.h"
 
-#define GS_HIP(expr)                                                                              \
+// GS_HIP_AS: the call goes through an owner and keeps the wording it had as a plain HIP call
+#define GS_HIP_AS(text, expr)                                                                     \
     do {                                                                                          \
         hipError_t e_ = (expr);                                                                   \
         if (e_ != hipSuccess)                                                                     \
             return gs_fail(e_ == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP,         \
-                           (uint64_t)e_, 0, 0, "%s failed: %s", #expr, hipGetErrorString(e_));    \
+                           (uint64_t)e_, 0, 0, "%s failed: %s", text, hipGetErrorString(e_));     \
     } while (0)
+#define GS_HIP(expr) GS_HIP_AS(#expr, expr)
 
 #define GS_TRY(expr)                  \
     do {                              \
@@ -44,16 +47,71 @@
 // device / stream / buffer
 // ------------------------------------------------------------------------------------------------
 
-// a device array that grows and never shrinks (hipFree synchronises the device)
-struct DevArray {
+// ---- owners: each holds ONE resource and lets go of it in its destructor, with the device of its holder current ----
+// They serve the temporaries of a call and the members of the handle objects alike: a function that holds one can return
+// early with GS_TRY / GS_HIP, and the destroy function of a handle is a `delete`.  hipFree waits for the device, but the
+// functions do not lean on that: whoever has enqueued work on an owner's memory synchronises the stream(s) before it
+// returns, on every path (the few returns and destroy functions that rely on the wait instead say so).  An enqueue-only
+// call hands its memory on: release().
+namespace gsh {
+// (gs_core.hip) *out = `bytes` of device memory, or null and GS_ERR_OUT_OF_MEMORY / GS_ERR_HIP with the message
+// "<what> failed: ..." (gs_error_info: a = the HIP error, b as given: the size, or 0 at the sites that never reported one)
+gs_status dev_alloc(void **out, size_t bytes, uint64_t b, const char *what);
+
+struct NoCopy {
+    NoCopy() noexcept = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+struct DevMem : NoCopy {
+    ~DevMem() noexcept { if (ptr) (void)hipFree(ptr); }
+    // through dev_alloc, with its error (once per owner) ... and for the sites that word the failure themselves
+    gs_status alloc(size_t bytes, uint64_t b, const char *what) noexcept { return dev_alloc(&ptr, bytes, b, what); }
+    hipError_t alloc_raw(size_t bytes) noexcept { return hipMalloc(&ptr, bytes); }
+    // a member that is allocated anew: null when this succeeds (or held nothing), untouched when hipFree fails
+    hipError_t free() noexcept {
+        const hipError_t e = ptr ? hipFree(ptr) : hipSuccess;
+        if (e == hipSuccess) ptr = nullptr;
+        return e;
+    }
+    void *release() noexcept { void *p = ptr; ptr = nullptr; return p; }
+    void *ptr = nullptr;
+};
+// (converts to its handle, so that a GS_HIP around a call on a member event words its failure as it always did)
+struct Event : NoCopy {
+    ~Event() noexcept { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDisableTiming) noexcept { return hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const noexcept { return e; }
+    hipEvent_t e = nullptr;
+};
+struct Stream : NoCopy {     // hipStreamNonBlocking, or adopted by whoever made it another way
+    ~Stream() noexcept { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() noexcept { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    hipStream_t s = nullptr;
+};
+template <typename T>
+struct Pinned : NoCopy {     // host memory of hipHostMalloc, flags as the site needs them
+    ~Pinned() noexcept { if (ptr) (void)hipHostFree(ptr); }
+    hipError_t alloc(size_t bytes, unsigned flags) noexcept { return hipHostMalloc((void **)&ptr, bytes, flags); }
+    T *ptr = nullptr;
+};
+}  // namespace gsh
+
+// a device array that grows and never shrinks (gsh::dev_reserve; hipFree synchronises the device)
+struct DevArray : gsh::NoCopy {
+    ~DevArray() noexcept { if (ptr) (void)hipFree(ptr); }
+    void *release() noexcept { void *p = ptr; ptr = nullptr; bytes = 0; return p; }
     void *ptr = nullptr;
     size_t bytes = 0;
 };
 
+// ---- the objects behind the handles: every member has an initialiser, every resource an owner (or, for the references
+// to ref-counted buffers, the destructor), so gs_*_destroy is: null check, hipSetDevice, what it waits for, delete ----
+
 struct gs_device {
-    int ordinal;
-    gs_limits limits;
-    hipStream_t internal;  // for blocking helper work
+    int ordinal = 0;
+    gs_limits limits{};
+    gsh::Stream internal;  // for blocking helper work
     // probe result: returning LDS atomics hand out lane-ordered values.  Written by any renderer of the device whose rank
     // watchdog fired (gs_render_frame / gs_renderer_wait_frame, possibly from different host threads) and read once per
     // frame (SortCtx::fast_rank) and by the stand-alone sorts: atomic, relaxed — it only ever goes from true to false.
@@ -68,17 +126,19 @@ struct gs_device {
 };
 
 struct gs_stream {
-    gs_device *dev;
-    hipStream_t s;
-    bool owned;
+    gs_stream(gs_device *d, hipStream_t st, bool owned) : dev(d), s(st) { if (owned) own.s = st; }
+    gs_device *dev = nullptr;
+    hipStream_t s = nullptr;
+    gsh::Stream own;       // `s` again when the handle made it (gs_stream_create*), empty around a wrapped stream
 };
 
+// (ref-counted: gs_buffer_release frees the memory of an owned one with the last reference)
 struct gs_buffer {
-    gs_device *dev;
-    void *ptr;
-    size_t bytes;
-    bool owned;
-    std::atomic<int> refs;
+    gs_device *dev = nullptr;
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    bool owned = false;
+    std::atomic<int> refs{1};
 };
 
 namespace gsh {
@@ -88,10 +148,6 @@ namespace gsh {
 const gsp::Switches &switches();
 gs_status use_device(const gs_device *dev);
 gs_status dev_reserve(DevArray &a, size_t bytes);
-void dev_free(DevArray &a);
-// *out = `bytes` of device memory, or null and GS_ERR_OUT_OF_MEMORY / GS_ERR_HIP with the message "<what> failed: ..."
-// (gs_error_info: a = the HIP error, b as given: the size, or 0 at the sites that never reported one)
-gs_status dev_alloc(void **out, size_t bytes, uint64_t b, const char *what);
 // ids of buffers and generations of selections: unique in the process, never 0
 uint64_t next_object_id();
 // a gs_buffer of one reference over `ptr`: owned (released with hipFree) or borrowed
@@ -99,71 +155,43 @@ gs_buffer *make_buffer(gs_device *dev, void *ptr, size_t bytes, bool owned);
 // `bytes` of device memory into host memory on `st`, awaited; the caller words the failure
 hipError_t fetch(hipStream_t st, void *dst, const void *src, size_t bytes);
 
-// ---- scoped owners of what ONE call holds across its blocking part ----
-// Each frees in its destructor, with the device of use_device() current.  hipFree waits for the device, but the functions
-// do not lean on that: whoever has enqueued work on an owner's memory synchronises the stream(s) before it returns, on every
-// path (the few returns that rely on the wait instead say so).  An enqueue-only call hands its memory on: release().
-struct NoCopy {
-    NoCopy() noexcept = default;
-    NoCopy(const NoCopy &) = delete;
-    NoCopy &operator=(const NoCopy &) = delete;
-};
-struct DevMem : NoCopy {
-    ~DevMem() noexcept { if (ptr) (void)hipFree(ptr); }
-    // through dev_alloc, with its error (once per owner) ... and for the sites that word the failure themselves
-    gs_status alloc(size_t bytes, uint64_t b, const char *what) noexcept { return dev_alloc(&ptr, bytes, b, what); }
-    hipError_t alloc_raw(size_t bytes) noexcept { return hipMalloc(&ptr, bytes); }
-    void *release() noexcept { void *p = ptr; ptr = nullptr; return p; }
-    void *ptr = nullptr;
-};
-struct Event : NoCopy {      // hipEventDisableTiming
-    ~Event() noexcept { if (e) (void)hipEventDestroy(e); }
-    hipError_t create() noexcept { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
-    hipEvent_t e = nullptr;
-};
-struct Stream : NoCopy {     // hipStreamNonBlocking
-    ~Stream() noexcept { if (s) (void)hipStreamDestroy(s); }
-    hipError_t create() noexcept { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
-    hipStream_t s = nullptr;
-};
-// a DevArray that lives for one call (dev_reserve grows it as any other)
-struct ScopedDevArray : DevArray, NoCopy {
-    ~ScopedDevArray() noexcept { dev_free(*this); }
-};
-
 }  // namespace gsh
 
 // ------------------------------------------------------------------------------------------------
 // GaussiansBuffer<G>
 // ------------------------------------------------------------------------------------------------
 
-struct gs_gaussians_buffer {
-    gs_buffer *buf;
-    int sh, cov;
+struct gs_gaussians_buffer : gsh::NoCopy {
+    ~gs_gaussians_buffer() {
+        if (order) gs_buffer_release(order);
+        if (buf) gs_buffer_release(buf);
+    }
+    gs_buffer *buf = nullptr;             // a reference
+    int sh = 0, cov = 0;
     // block-planar mirror read by the preprocess kernel; rebuilt lazily
-    void *planar;
-    size_t planar_stride;  // capacity in Gaussians = len rounded up to whole 1024-blocks
+    gsh::DevMem planar;
+    size_t planar_stride = 0;  // capacity in Gaussians = len rounded up to whole 1024-blocks
     // Gaussians [dirty_lo, dirty_hi) of the AoS buffer are newer than the mirror (empty when lo >= hi).
     // update_range dirties only its own range, so an editor's per-edit update re-mirrors a few
     // Gaussians instead of the whole scene.
-    size_t dirty_lo, dirty_hi;
+    size_t dirty_lo = 0, dirty_hi = (size_t)-1;      // a new buffer is dirty all over
     // spatial mirror order: order[slot] = Gaussian index, inv[index] = slot; both
     // null while the mirror is in index order.  `order` is a ref-counted gs_buffer so that the
     // renderer's parity taps can keep the order of the frame they describe.
-    bool spatial;
-    gs_buffer *order;
-    void *inv;
-    void *block_bounds;      // 8 floats per 1024-slot block (k_block_bounds); null = not available
-    size_t partial_since_order;   // Gaussians rewritten by partial updates since the order was built
+    bool spatial = true;
+    gs_buffer *order = nullptr;           // a reference
+    gsh::DevMem inv;
+    gsh::DevMem block_bounds;     // 8 floats per 1024-slot block (k_block_bounds); null = not available
+    size_t partial_since_order = 0;   // Gaussians rewritten by partial updates since the order was built
     // The mirror is (re)built on the stream of whichever frame first needs it; frames on OTHER streams
     // (several renderers keeping frames in flight on one buffer) wait for this event before reading it.
-    hipEvent_t mirror_ready = nullptr;
+    gsh::Event mirror_ready;
     hipStream_t mirror_stream = nullptr;
     // gs_gaussians_buffer_edit only ENQUEUES its kernel: a mirror rebuild on another stream waits for
     // this event before it reads the AoS records (gsh::wait_for_edits / record_edit).  keep_order: the whole buffer is
     // dirty but no position changed (a colour / opacity edit), so the rebuild repacks through the order it has instead
     // of sorting again.
-    hipEvent_t edit_done = nullptr;
+    gsh::Event edit_done;
     hipStream_t edit_stream = nullptr;
     bool keep_order = false;
     // what a renderer's slot-ordered selection masks were gathered through: this buffer (ids are never
@@ -172,14 +200,14 @@ struct gs_gaussians_buffer {
     uint64_t order_epoch = 0;
     // gs_gaussians_buffer_create_concat: the per-block offsets its copies read; they are only enqueued
     // when the call returns, so the new buffer owns the array
-    void *concat_offsets = nullptr;
+    gsh::DevMem concat_offsets;
     // gs_gaussians_buffer_stats / _histogram: the partial rows and the device result of the last call
     DevArray stats_scratch;
     // gs_gaussians_buffer_neighbor_counts / gs_select_neighbors and the component calls (§3.16): keys,
     // order, sorted positions, the union-find words and the sort's histograms of the last call; a call on another stream
     // waits for nb_done before it reuses them
     DevArray nb_scratch, nb_ghist, nb_digit_totals;
-    hipEvent_t nb_done = nullptr;
+    gsh::Event nb_done;
     hipStream_t nb_stream = nullptr;
     void mark(size_t lo, size_t hi) {
         if (lo >= hi) return;
@@ -194,12 +222,13 @@ struct gs_gaussians_buffer {
 // Gaussian selection: n bits in caller index order.  `generation` changes with every call that may
 // modify the bits (next_object_id: unique across selections), which is how a renderer knows its slot-ordered copy is stale.
 struct gs_selection {
-    gs_device *dev;
-    size_t n, nwords;
-    uint32_t *words;            // device, nwords (at least one word is allocated)
+    gs_device *dev = nullptr;
+    size_t n = 0, nwords = 0;
+    gsh::DevMem words;          // nwords of 32 bits (at least one word is allocated)
     DevArray scratch;           // a plane of the same size for the select ops that scatter their bits (select_visible)
     DevArray counter;           // gs_selection_count's device total
-    uint64_t generation;
+    uint64_t generation = 0;
+    uint32_t *bits() const { return (uint32_t *)words.ptr; }
     uint32_t tail_mask() const { return (n & 31u) ? (1u << (n & 31u)) - 1u : 0xffffffffu; }
     uint32_t grid() const { return nwords < 256u * 1024u ? (uint32_t)((nwords + 255u) / 256u) + 1u : 1024u; }
 };
@@ -207,7 +236,7 @@ struct gs_selection {
 namespace gsh {
 
 inline bool valid_cfg(int sh, int cov) { return sh >= 0 && sh <= 3 && cov >= 0 && cov <= 2; }
-inline hipStream_t stream_of(gs_device *dev, gs_stream *s) { return s ? s->s : dev->internal; }
+inline hipStream_t stream_of(gs_device *dev, gs_stream *s) { return s ? s->s : dev->internal.s; }
 inline size_t pod_stride(const gs_gaussians_buffer *g) { return (size_t)gs::pod_bytes(g->sh, g->cov); }
 inline bool all_finite(const float *v, int n) {
     for (int k = 0; k < n; k++)
@@ -280,7 +309,7 @@ void extract_copy_enqueue(hipStream_t st, const void *src, void *dst, const uint
 // what extraction, conversion and the exports start with: records_access, the scan into an array of the call, its total on
 // the host (n == 0: no array, total 0).  Blocks on x.st.
 struct ExtractScan : RecordsAccess {
-    ScopedDevArray scan;      // the per-1024-block offsets, then the total
+    DevArray scan;            // the per-1024-block offsets, then the total
     uint32_t total = 0;
     const uint32_t *offsets() const { return (const uint32_t *)scan.ptr; }
 };

@@ -44,7 +44,7 @@ gs_status gsh::neighbor_grid_enqueue(gs_gaussians_buffer *g, hipStream_t st, con
     gs::ModelTransform m;
     std::memcpy(&m, mt, sizeof(m));
     gs::model_transform_mat(m, sh.M);
-    const uint32_t *aos = (const uint32_t *)g->buf->ptr, *words = among ? (const uint32_t *)among->words : nullptr;
+    const uint32_t *aos = (const uint32_t *)g->buf->ptr, *words = among ? among->bits() : nullptr;
     hipLaunchKernelGGL(gs::k_nb_bbox_partial, dim3(pgrid), dim3(256), 0, st, aos, pod_words, n, words, sh, partial);
     bbox_final_enqueue(st, partial, pgrid, bbox);
     hipLaunchKernelGGL(gs::k_nb_keys, dim3(nblocks), dim3(256), 0, st, aos, pod_words, n, words, sh, (const float *)bbox, radius,
@@ -90,7 +90,7 @@ static gs_status neighbor_counts_enqueue(gs_gaussians_buffer *g, hipStream_t st,
 
 // the next call on another stream waits until this one has left the scratch
 gs_status gsh::neighbor_scratch_release(gs_gaussians_buffer *g, hipStream_t st) {
-    if (!g->nb_done) GS_HIP(hipEventCreateWithFlags(&g->nb_done, hipEventDisableTiming));
+    if (!g->nb_done) GS_HIP_AS("hipEventCreateWithFlags(&g->nb_done, hipEventDisableTiming)", g->nb_done.create());
     GS_HIP(hipEventRecord(g->nb_done, st));
     g->nb_stream = st;
     return GS_OK;
@@ -150,7 +150,7 @@ extern "C" gs_status gs_select_neighbors(gs_selection *sel, gs_stream *s, gs_gau
     if (rc == GS_OK) {      // only now does `sel` change
         sel->generation = next_object_id();
         hipLaunchKernelGGL(gs::k_nb_select, dim3((n + 255u) / 256u), dim3(256), 0, st, (const uint32_t *)plane, n, min_count, max_count,
-                           sel->words, (uint32_t)op);
+                           sel->bits(), (uint32_t)op);
         if (hipGetLastError() != hipSuccess) rc = gs_fail(GS_ERR_HIP, 0, 0, 0, "k_nb_select could not be launched");
     }
     // the event on every path: an enqueue that failed half-way has still left kernels on the scratch

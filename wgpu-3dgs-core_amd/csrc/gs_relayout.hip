@@ -191,7 +191,7 @@ gs_status gsh::concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, co
         b0 += (n + gs::PLANAR_BLOCK - 1u) / gs::PLANAR_BLOCK;
         if (!n) continue;
         GS_TRY(wait_for_edits(g, st));      // (scans of earlier sources may be in flight: the array's hipFree waits for them)
-        extract_scan_enqueue(st, sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr, n, 0u, scan + block0[i], totals_dev + i);
+        extract_scan_enqueue(st, sels && sels[i] ? sels[i]->bits() : nullptr, n, 0u, scan + block0[i], totals_dev + i);
         e = hipGetLastError();
     }
     // sizing the new buffer needs the totals on the host: the one round trip of the call
@@ -212,7 +212,7 @@ gs_status gsh::concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, co
         for (uint32_t i = 0; i < count; i++) {
             if (!totals[i]) continue;
             const uint32_t n = (uint32_t)gs_gaussians_buffer_len(srcs[i]);
-            const uint32_t *words = sels && sels[i] ? (const uint32_t *)sels[i]->words : nullptr;
+            const uint32_t *words = sels && sels[i] ? sels[i]->bits() : nullptr;
             // both kernels stay inside `total` records from `first`: the part of this source
             convert_extract_enqueue(st, srcs[i], sh, cov, dst->buf->ptr, first, words, n, 0u, scan + block0[i], totals[i]);
             first += totals[i];
@@ -227,7 +227,7 @@ gs_status gsh::concat_records(gs_stream *s, gs_gaussians_buffer *const *srcs, co
             gs_gaussians_buffer_destroy(dst);
             return rc;
         }
-        dst->concat_offsets = scan_mem.release();
+        dst->concat_offsets.ptr = scan_mem.release();
     } else {
         GS_TRY(gs_gaussians_buffer_create(dev, (gs_sh_config)sh, (gs_cov3d_config)cov, nullptr, 0, &dst));
     }

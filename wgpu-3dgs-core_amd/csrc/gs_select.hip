@@ -15,32 +15,27 @@ extern "C" gs_status gs_selection_create(gs_device *dev, size_t n, gs_selection 
     GS_TRY(check_len32(n));
     GS_TRY(use_device(dev));
     const size_t nwords = (n + 31) / 32, bytes = (nwords ? nwords : 1) * 4;
-    DevMem words;
-    GS_TRY(words.alloc(bytes, 0, "selection allocation"));
-    hipError_t e = hipMemset(words.ptr, 0, bytes);
+    std::unique_ptr<gs_selection> sel(new gs_selection());
+    GS_TRY(sel->words.alloc(bytes, 0, "selection allocation"));
+    hipError_t e = hipMemset(sel->words.ptr, 0, bytes);
     // (awaited: the null stream's fill is not ordered against the non-blocking stream of the upload that follows, and a
     // late fill clears a mask that was uploaded and already read once)
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess)
         return gs_fail(e == hipErrorOutOfMemory ? GS_ERR_OUT_OF_MEMORY : GS_ERR_HIP, (uint64_t)e, 0, 0, "selection allocation failed: %s",
                     hipGetErrorString(e));
-    gs_selection *sel = new gs_selection();
     sel->dev = dev;
     sel->n = n;
     sel->nwords = nwords;
-    sel->words = (uint32_t *)words.release();
     sel->generation = next_object_id();
-    *out = sel;
+    *out = sel.release();
     return GS_OK;
 }
 
 extern "C" void gs_selection_destroy(gs_selection *sel) {
     if (!sel) return;
     (void)hipSetDevice(sel->dev->ordinal);
-    (void)hipFree(sel->words);      // (synchronises the device: kernels that still read the mask finish first)
-    dev_free(sel->scratch);
-    dev_free(sel->counter);
-    delete sel;
+    delete sel;      // (hipFree synchronises the device: kernels that still read the mask finish first)
 }
 
 extern "C" size_t gs_selection_len(const gs_selection *sel) { return sel ? sel->n : 0; }
@@ -68,7 +63,7 @@ static gs_status selection_unary(gs_selection *sel, gs_stream *s, uint32_t mode)
     GS_TRY(check_selection(sel, s));
     sel->generation = next_object_id();
     if (!sel->nwords) return GS_OK;
-    hipLaunchKernelGGL(gs::k_sel_unary, dim3(sel->grid()), dim3(256), 0, s->s, sel->words, (uint32_t)sel->nwords, sel->tail_mask(), mode);
+    hipLaunchKernelGGL(gs::k_sel_unary, dim3(sel->grid()), dim3(256), 0, s->s, sel->bits(), (uint32_t)sel->nwords, sel->tail_mask(), mode);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -79,7 +74,7 @@ extern "C" gs_status gs_selection_invert(gs_selection *sel, gs_stream *s) { retu
 gs_status gsh::selection_combine_words(gs_selection *dst, hipStream_t st, gs_select_op op, const uint32_t *src) {
     dst->generation = next_object_id();
     if (!dst->nwords) return GS_OK;
-    hipLaunchKernelGGL(gs::k_sel_combine, dim3(dst->grid()), dim3(256), 0, st, dst->words, src, (uint32_t)dst->nwords, (uint32_t)op);
+    hipLaunchKernelGGL(gs::k_sel_combine, dim3(dst->grid()), dim3(256), 0, st, dst->bits(), src, (uint32_t)dst->nwords, (uint32_t)op);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -89,7 +84,7 @@ extern "C" gs_status gs_selection_combine(gs_selection *dst, gs_stream *s, gs_se
     GS_TRY(check_select_op(op));
     if (!src || src->dev != dst->dev) return gs_fail(GS_ERR_INVALID_ARGUMENT, 0, 0, 0, "the source selection is null or belongs to another device");
     if (src->n != dst->n) return gs_fail(GS_ERR_INVALID_ARGUMENT, src->n, dst->n, 0, "selection lengths differ: %zu != %zu", src->n, dst->n);
-    return selection_combine_words(dst, s->s, op, src->words);
+    return selection_combine_words(dst, s->s, op, src->bits());
 }
 
 extern "C" gs_status gs_selection_upload(gs_selection *sel, gs_stream *s, const uint32_t *words, size_t nwords) {
@@ -98,7 +93,7 @@ extern "C" gs_status gs_selection_upload(gs_selection *sel, gs_stream *s, const 
         return gs_fail(GS_ERR_INVALID_ARGUMENT, nwords, sel->nwords, 0, "a selection of %zu bits takes %zu words", sel->n, sel->nwords);
     sel->generation = next_object_id();
     if (!nwords) return GS_OK;
-    GS_HIP(hipMemcpyAsync(sel->words, words, nwords * 4, hipMemcpyHostToDevice, s->s));
+    GS_HIP(hipMemcpyAsync(sel->bits(), words, nwords * 4, hipMemcpyHostToDevice, s->s));
     return selection_unary(sel, s, 3u);      // bits past n of the last word are dropped
 }
 
@@ -108,7 +103,7 @@ extern "C" gs_status gs_selection_download(gs_selection *sel, gs_stream *s, uint
         return gs_fail(GS_ERR_INVALID_ARGUMENT, nwords, sel->nwords, 0, "a selection of %zu bits takes %zu words", sel->n, sel->nwords);
     if (!nwords) return GS_OK;
     GS_HIP(hipStreamSynchronize(s->s));
-    hipError_t e = hipMemcpy(words, sel->words, nwords * 4, hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(words, sel->bits(), nwords * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return gs_fail(GS_ERR_DOWNLOAD, (uint64_t)e, 0, 0, "download failed: %s", hipGetErrorString(e));
     return GS_OK;
 }
@@ -120,7 +115,7 @@ extern "C" gs_status gs_selection_count(gs_selection *sel, gs_stream *s, uint64_
     if (!sel->nwords) return GS_OK;
     GS_TRY(dev_reserve(sel->counter, 8));
     GS_HIP(hipMemsetAsync(sel->counter.ptr, 0, 8, s->s));
-    hipLaunchKernelGGL(gs::k_sel_count, dim3(sel->grid()), dim3(256), 0, s->s, (const uint32_t *)sel->words, (uint32_t)sel->nwords,
+    hipLaunchKernelGGL(gs::k_sel_count, dim3(sel->grid()), dim3(256), 0, s->s, sel->bits(), (uint32_t)sel->nwords,
                        (unsigned long long *)sel->counter.ptr);
     GS_HIP(hipGetLastError());
     GS_HIP(hipStreamSynchronize(s->s));
@@ -147,10 +142,10 @@ static gs_status select_shape(gs_selection *sel, gs_stream *s, gs_gaussians_buff
     if (!len) return GS_OK;
     const uint32_t n = (uint32_t)len, grid = (n + 255u) / 256u, pod_words = (uint32_t)(pod_stride(g) / 4);
     if (box)
-        hipLaunchKernelGGL(gs::k_select_shape<true>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->words,
+        hipLaunchKernelGGL(gs::k_select_shape<true>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->bits(),
                            (uint32_t)op);
     else
-        hipLaunchKernelGGL(gs::k_select_shape<false>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->words,
+        hipLaunchKernelGGL(gs::k_select_shape<false>, dim3(grid), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr, pod_words, n, sh, sel->bits(),
                            (uint32_t)op);
     GS_HIP(hipGetLastError());
     return GS_OK;
@@ -201,14 +196,14 @@ extern "C" gs_status gs_select_contribution(gs_selection *sel, gs_stream *s, gs_
     sel->generation = next_object_id();
     if (!sel->n) return GS_OK;
     const uint32_t n = (uint32_t)sel->n;
-    hipLaunchKernelGGL(gs::k_select_contrib, dim3((n + 255u) / 256u), dim3(256), 0, s->s, (const uint4 *)contrib->ptr, n, kind, lo, hi, sel->words,
+    hipLaunchKernelGGL(gs::k_select_contrib, dim3((n + 255u) / 256u), dim3(256), 0, s->s, (const uint4 *)contrib->ptr, n, kind, lo, hi, sel->bits(),
                        (uint32_t)op);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
 
 void gsh::sel_range_enqueue(gs_selection *sel, hipStream_t st, uint32_t start, uint32_t end, gs_select_op op) {
-    hipLaunchKernelGGL(gs::k_sel_range, dim3(sel->grid()), dim3(256), 0, st, sel->words, (uint32_t)sel->nwords, start, end, (uint32_t)op);
+    hipLaunchKernelGGL(gs::k_sel_range, dim3(sel->grid()), dim3(256), 0, st, sel->bits(), (uint32_t)sel->nwords, start, end, (uint32_t)op);
 }
 
 extern "C" gs_status gs_select_range(gs_selection *sel, gs_stream *s, size_t start, size_t count, gs_select_op op) {

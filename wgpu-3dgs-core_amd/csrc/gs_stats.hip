@@ -162,7 +162,7 @@ extern "C" gs_status gs_select_attribute(gs_selection *sel, gs_stream *s, gs_gau
     attr_args_fill(a, ad->attr, ad->model_transform, ad->ref);
     const uint32_t n = (uint32_t)len;
     hipLaunchKernelGGL(select_attr_kernel(g, ad->attr), dim3((n + 255u) / 256u), dim3(256), 0, s->s, (const uint32_t *)g->buf->ptr,
-                       (uint32_t)(pod_stride(g) / 4), n, a, lo, hi, sel->words, (uint32_t)op);
+                       (uint32_t)(pod_stride(g) / 4), n, a, lo, hi, sel->bits(), (uint32_t)op);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
