@@ -9,6 +9,12 @@
 #                                                   and the wave-steps of lists rebuilt from "some pixel passes"
 #   python3 tools/blend_sim.py --wave-split         only: wave-steps if the two waves of a tile split its sixteen 4x4 blocks
 #                                                   otherwise than by pixel rows (the eight longest lists to one wave)
+#   python3 tools/blend_sim.py --skip-rate          only: the G = 8 wave-steps in which no pixel of the wave passes — what the any-lane
+#                                                   branch of the trip loop skips — bucketed by the wave's live pixels at the batch
+#                                                   start (the oracle's `stopped` flags on the range cut there): the table behind
+#                                                   BLEND_FREE_MIN_LIVE (csrc/gs_render_kernels.h, NOTES.md Part XVII)
+#   --n <Gaussians>                                 another size of the bench scene (--skip-rate --n 10000000: a deep scene)
+#   --min-live <k>                                  the rule --skip-rate prices (default: BLEND_FREE_MIN_LIVE, read from the kernel header)
 import argparse, os, sys, numpy as np
 _root=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (_root, os.path.join(_root,'tools'), os.path.join(_root,'tests')): sys.path.insert(0,_p)
@@ -19,9 +25,12 @@ _ap.add_argument('--drop-finished',action='store_true')
 _ap.add_argument('--staging-table',action='store_true')
 _ap.add_argument('--pixel-pass',action='store_true')
 _ap.add_argument('--wave-split',action='store_true')
+_ap.add_argument('--skip-rate',action='store_true')
+_ap.add_argument('--n',type=int,default=1_000_000)
+_ap.add_argument('--min-live',type=int,default=None)
 ARGS=_ap.parse_args()
 from oracle import binding as ob
-N=1_000_000; sh,cov=3,0
+N=ARGS.n; sh,cov=3,0
 g=synth.scene(N); pods=ob.pack(sh,cov,g)
 cam=helpers.default_camera(ob,1920,1080)
 gt,mt=ob.gaussian_transform(sh_deg=0),ob.model_transform()
@@ -86,6 +95,75 @@ if ARGS.staging_table:
         for drop in (False,True):
             e,s=staging_g8(slack,drop)
             print('| %g | %s | %d | %d |'%(slack,'left off' if drop else 'staged',e,s),flush=True)
+    sys.exit(0)
+if ARGS.skip_rate:
+    # The G = 8 lists as the kernel builds them (slack 0, as under --pixel-pass).  A wave-step is step s of a wave (tile half) in a
+    # batch, s below the longest of the wave's eight lists; a pixel passes it if it is live at the batch start and
+    # 0 <= -power <= L for entry s of its block's list.  (Pixels that finish inside the batch count as live to its end, as the
+    # flags are the batch start's: the skip share of the late steps of a batch is a little higher than printed.)
+    pmin0=np.maximum(-np.log(255*op),-5.6)
+    u,inv=np.unique(tile*1000+batch,return_inverse=True); nb=len(u)
+    nbat=int(batch.max())+1
+    live_px=np.zeros((nbat,68*16,1920),dtype=bool)        # [batch][y][x]: live at the batch start
+    nt=120*68
+    rng=np.asarray(ob.tile_ranges(keys,nt)).reshape(nt,2).astype(np.int64)
+    for mb in range(nbat):
+        if mb==0: live_px[0,:1080]=True
+        else:
+            r=rng.copy(); r[:,1]=r[:,0]+np.minimum(rng[:,1]-rng[:,0],128*mb)
+            _,st=ob.blend(proj,idx,np.ascontiguousarray(r.astype(np.uint32)),cam,stopped=True)
+            live_px[mb,:1080]=st[:1080,:1920]==0
+    L=np.zeros((nb,16),dtype=np.int64)
+    passed=np.zeros(nb*2*128,dtype=bool)                  # [(batch group, wave, step)]: some pixel of the wave passes
+    txi=tx.astype(np.int64); tyi=ty.astype(np.int64)
+    for r in range(4):
+        for c in range(4):
+            t=touches(x0+4*c,x0+4*c+3,y0+4*r,y0+4*r+3,0.0,pmin0)
+            L[:,r*4+c]=np.bincount(inv,weights=t,minlength=nb)
+            cs=np.cumsum(t); first=np.searchsorted(inv,np.arange(nb))         # (pairs are sorted by tile and position)
+            rank=cs-1-(cs[first]-t[first])[inv]                                # position of an entry in its list
+            any_px=np.zeros(D,dtype=bool)
+            for j in range(4):
+                for i in range(4):
+                    dx=mx-(x0+4*c+i); dy=my-(y0+4*r+j)
+                    pw=ca*dx*dx+cb*dx*dy+cc*dy*dy
+                    any_px|=(pw<=0)&(pw>=pmin0)&live_px[batch,tyi*16+4*r+j,txi*16+4*c+i]
+            sel=t&any_px
+            passed[(inv[sel]*2+r//2)*128+rank[sel]]=True
+    steps=np.stack([L[:,:8].max(1),L[:,8:].max(1)],axis=1).reshape(-1)          # [(batch group, wave)]
+    blended=passed.reshape(nb*2,128).sum(1)
+    gt_,gb_=u//1000,u%1000
+    lv=np.zeros((nb,2),dtype=np.int64)
+    for w in range(2):
+        for j in range(8):
+            rows=live_px[gb_,(gt_//120)*16+8*w+j]                               # [nb][1920]
+            cols=(gt_%120)[:,None]*16+np.arange(16)[None,:]
+            lv[:,w]+=np.take_along_axis(rows,cols,axis=1).sum(1)
+    lv=lv.reshape(-1)
+    run=lv>0                                                                    # a wave with no live pixel enters no loop
+    print('batches',nb,'waves that enter the loop',int(run.sum()),'wave-steps (exact)',int(steps[run].sum()),
+          'rounded up to even',int((((steps+1)//2)*2)[run].sum()))
+    print('| live pixels at the batch start | wave-batches | wave-steps | no pixel passes | share |')
+    for lo in range(1,129,8):
+        b=run&(lv>=lo)&(lv<lo+8)
+        ws,sk=int(steps[b].sum()),int((steps-blended)[b].sum())
+        print('| %d..%d | %d | %d | %d | %s |'%(lo,lo+7,int(b.sum()),ws,sk,'%.4f'%(sk/ws) if ws else '-'))
+    k=ARGS.min_live
+    if k is None:
+        import re
+        k=int(re.search(r'constexpr uint32_t BLEND_FREE_MIN_LIVE = (\d+);',open(os.path.join(_root,'wgpu-3dgs-core_amd','csrc','gs_render_kernels.h')).read()).group(1))
+    f=run&(lv>=k)
+    ws,sk,odd=int(steps[f].sum()),int((steps-blended)[f].sum()),int((steps[f]&1).sum())
+    print('rule: branch-free from %d live pixels: %d wave-batches of %d, %d wave-steps of them %d with no pixel passing (%.4f), %d odd step counts'
+          %(k,int(f.sum()),int(run.sum()),ws,sk,sk/max(ws,1),odd))
+    # the branch-free steps are those of the trips of four; the 0..3 left are branchy steps as before
+    inloop=np.arange(128)[None,:]<(steps//4*4)[:,None]
+    lb=int((passed.reshape(nb*2,128)&inloop)[f].sum()); ls=int((steps//4*4)[f].sum())-lb
+    # against the loop that is branchy throughout (35 per blended step, 12 per skipped one, the count rounded up to even): a step of
+    # a branch-free trip costs 34; the 0..3 remainder steps are branchy steps and cost what they did; an odd count saves its null step
+    print('predicted change of SQ_INSTS_VALU per frame: of these wave-steps %d are in trips of four: -1 x %d blended, +22 x %d skipped; '
+          '%d remainder steps unchanged; -12 x %d rounding steps: sum %d'
+          %(lb+ls,lb,ls,ws-lb-ls,odd,-lb+22*ls-12*odd))
     sys.exit(0)
 if ARGS.pixel_pass or ARGS.wave_split:
     # the G = 8 lists as the kernel builds them since NOTES.md Part XIV: threshold -L(k) = -ln(255 opacity), no constant, slack 0;

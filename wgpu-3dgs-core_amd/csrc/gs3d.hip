@@ -1295,7 +1295,7 @@ struct Frame {
     gs::FrameResult *result = nullptr;
     // slices of zero_region: tile ranges, the two rounds' super-chunk sums, the finished / open tile bits
     uint32_t *zero = nullptr, *esb = nullptr, *esb2 = nullptr, *done_bits = nullptr, *open_bits = nullptr;
-    gs::TileKeys tile_keys{nullptr, nullptr, 0u, 0u, 0u, nullptr, nullptr};   // null keys: the blend reads its ranges from the range array
+    gs::TileKeys tile_keys{nullptr, nullptr, 0u, 0u, 0u, 0u, nullptr, nullptr};   // null keys: the blend reads its ranges from the range array
     gs::SelIO sel{};                  // selection frames: what the preprocess kernels read (stage_selection)
     gs_buffer *contrib = nullptr;     // contribution frames (gs_render_frame_contrib, checked there): the records the blend adds to, or null
     gsp::Requests requests() const {
@@ -1392,6 +1392,7 @@ static gs_status stage_blend(Frame &F, uint32_t round) {
     const int gcol = groups == 2 ? 0 : groups == 8 ? 2 : 1;
     if (round != 0u && groups == 1) return gs_fail(GS_ERR_INVALID_ARGUMENT, round, 0, 0, "two-round frames need the grouped blend");
     F.tile_keys.round = round;
+    F.tile_keys.free_min_live = gsp::plan_blend_free_min_live(switches(), gs::BLEND_FREE_MIN_LIVE);
     if (F.contrib) {
         // the accumulation rides in the grouped blend of the frame's only round (G = 4 where the plain frame would take k_blend)
         typedef void (*contrib_fn)(uint32_t *, const uint32_t *, const uint32_t *, gs::FrameConsts, float4 *,

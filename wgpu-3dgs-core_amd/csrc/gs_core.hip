@@ -72,6 +72,7 @@ static gsp::Switches read_switches() {
     s.tile_masks = (int)env_int("GS3D_TILE_MASKS", s.tile_masks);
     s.depth_msd = (int)env_int("GS3D_DEPTH_MSD", s.depth_msd);
     s.blend_groups = (int)env_int("GS3D_BLEND_GROUPS", s.blend_groups);
+    s.blend_free_body = (int)env_int("GS3D_BLEND_FREE_BODY", s.blend_free_body);
     s.rounds = (int)env_int("GS3D_ROUNDS", s.rounds);
     s.round1 = env_int("GS3D_ROUND1", s.round1);
     s.round_partition = (int)env_int("GS3D_ROUND_PARTITION", s.round_partition);

@@ -35,6 +35,7 @@ struct Switches {
     int tile_masks = -1;            // GS3D_TILE_MASKS=0/1: tile rect version 3 / 4
     int depth_msd = -1;             // GS3D_DEPTH_MSD=0/1: LSD / MSD-first depth sort
     int blend_groups = 0;           // GS3D_BLEND_GROUPS = 1 (half-tile lists), 2 (8x8 blocks), 4 (8x4 blocks) or 8 (4x4 blocks); 0: plan_blend_groups
+    int blend_free_body = -1;       // GS3D_BLEND_FREE_BODY=0/1: the grouped blend's trip loop always branchy / always branch-free; unset: plan_blend_free_min_live
     int rounds = -1;                // GS3D_ROUNDS=0/1: one round / two
     long round1 = 0;                // GS3D_ROUND1=<k>: Gaussians of round 1
     int round_partition = -1;       // GS3D_ROUND_PARTITION=0/1: two-round frames sort each round on its own
@@ -450,6 +451,13 @@ inline void plan_pairs(const History &h, const FrameNums &f, uint64_t pair_capac
 inline int plan_blend_groups(const Switches &sw, uint32_t round) {
     if (sw.blend_groups != 0) return sw.blend_groups;
     return round != 0u ? 4 : 8;
+}
+
+// The grouped blend's choice between the two forms of its trip loop (k_blend_grouped, TileKeys::free_min_live): a wave runs a
+// batch branch-free while at least this many of its 128 pixels are live.  rule: gs::BLEND_FREE_MIN_LIVE.  GS3D_BLEND_FREE_BODY=0
+// pins the branchy form (129: no wave has that many), =1 the branch-free one (0).
+inline uint32_t plan_blend_free_min_live(const Switches &sw, uint32_t rule) {
+    return sw.blend_free_body < 0 ? rule : sw.blend_free_body != 0 ? 0u : 129u;
 }
 
 // round: 0 the frame's only one, else 1 or 2

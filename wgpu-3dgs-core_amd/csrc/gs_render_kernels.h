@@ -3602,9 +3602,14 @@ struct TileKeys {
     // tiles that are not finished (-T: the pixel itself is), a bit in `done` for those that are (their pixels are final);
     // round 2 returns at once for the done tiles and resumes the others.  0: the frame's only round.
     uint32_t round;
+    // k_blend_grouped: a wave runs a batch in the branch-free form of the trip loop while at least this many of its 128 pixels
+    // are live (BLEND_FREE_MIN_LIVE, or GS3D_BLEND_FREE_BODY's pin: 0 always, 129 never).  (In the padding behind `round`: the
+    // argument layout of every blend kernel is what it was.)
+    uint32_t free_min_live;
     uint32_t *done;               // [tiles / 32 + 1], zeroed per frame
     uint32_t *open;               // [tiles / 32 + 1], zeroed per frame: tiles round 1 had pairs for and did not finish
 };
+static_assert(sizeof(TileKeys) == 48, "free_min_live fills the padding behind round: the blend kernels' argument layout is unchanged");
 __device__ __forceinline__ void blend_tile_range(const TileKeys &tk, uint32_t *__restrict__ ranges, uint32_t tile,
                                                  uint32_t lane, bool writer, uint32_t &start, uint32_t &end) {
     if (!tk.keys) {
@@ -3664,6 +3669,13 @@ __device__ __forceinline__ void blend_tile_range_wg(const TileKeys &tk, uint32_t
 
 constexpr int BLEND_THREADS = 128;
 constexpr int BLEND_BATCH = 128;
+// k_blend_grouped: a wave whose live pixels at the top of a batch number at least this many (of its 128) runs the batch in the
+// branch-free form of the trip loop (no any-lane test, no copy of T, exact step count), otherwise in the branchy form, which
+// skips the steps in which none of its pixels passes.  From tools/blend_sim.py --skip-rate (NOTES.md Part XVII): a skipped step
+// costs 12 instructions in the branchy form and 34 in the branch-free one, a blended one 35 against 34, so the forms break
+// even at a skip share of 1 / 23; this is the smallest live count from which every bucket of the simulation — the 1 M bench
+// scene and a deep one — stays under half of that.
+constexpr uint32_t BLEND_FREE_MIN_LIVE = 73;
 
 // One workgroup (2 waves) = one 16x16 tile.  Wave h owns the half-tile of pixel rows 8h..8h+7;
 // each lane owns TWO pixels (x, y) and (x, y+4), so the per-splat arithmetic runs on packed f32
@@ -4033,6 +4045,10 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
     constexpr int NL = 2 * G;                 // lists per tile (= NCOL * NROW)
     static_assert(NCOL * NROW == NL && G == NCOL * (NROW / 2), "one list per block, G blocks per wave");
     constexpr uint32_t NULL_REC = BLEND_BATCH;
+    // The instantiations that carry the branch-free form of the trip loop beside the branchy one (GS_BLEND_STEP_FREE): those that
+    // keep their waves per SIMD with it (NOTES.md Part XVII).  Every AUX instantiation would lose one to three, Splat G = 4
+    // with ROUNDS — the blend of two-round frames — one, and so would one CONTRIB instantiation below G = 8.
+    constexpr bool FREE_BODY = !AUX && !ROUNDS && (!CONTRIB || G == 8);
     // One 48-byte LDS record per staged splat: {my, mx, cc, ca | opacity, cb, r, limit word | g, b, -, -} (Point: pmin for the limit word; AUX: {.. | g, b, z', slot}; CONTRIB: {.. | g, b, -, accumulator offset}).
     // The words a step broadcasts to both pixels of a lane (my, cc, opacity, r) are the EVEN words of their 16-byte read: a packed
     // instruction takes such a word from the low half of an aligned register pair as it lies, while for an odd word of a
@@ -4353,9 +4369,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             // address per pair — and issues the next record's two reads behind its own pixel test, in front of the branch:
             // the record is on its way from LDS while this step blends.  An offset's register is free once its step has
             // issued its third read, so two registers alternate like the records.  A trip of the loop is FOUR steps, so the
-            // pointer moves once per four.  The step count is rounded up to even, not to four — the padding is the null offset,
-            // so the extra step of an odd list blends nothing, but it costs the dozen instructions in front of its branch —
-            // and a two-step remainder follows the loop.  The offsets are read one step ahead without a bound: behind a
+            // pointer moves once per four.  The branchy form rounds the step count up to even, not to four — the padding is
+            // the null offset, so the extra step of an odd list blends nothing, but it costs the dozen instructions in front
+            // of its branch — and leaves a remainder of two steps; the branch-free form takes the exact count and leaves one
+            // of 0..3.  One remainder follows both loops, its steps in the branchy form (as the branch-free arm's own, of
+            // branch-free steps, it cost Splat G = 4 a wave per SIMD).  The offsets are read one step ahead without a bound: behind a
             // row's end lies the next row's first entry (a valid offset or the null fill), behind the last row the pad.
             // One structured loop, one conditional block per step: no continue / break inside (hipcc turned
             // those into a scalar state machine of ~25 instructions and 5 branches per iteration).
@@ -4389,8 +4407,15 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             //    [-5.6, 0] only, and L(k) <= ln 255 = 5.55.  The any-lane branch it feeds also skips most steps of a deep
             //    tile, whose pixels are long finished (round 4 removed test and branch for one build: wrong pixels, and the
             //    10 M blend 0.157 -> 1.80 ms).
-#define GS_BLEND_STEP(AREC, BREC, ID, NEXT)                                                                   \
-    {                                                                                                         \
+            // The step exists in two forms built from the same two pieces, the pixel test (GS_BLEND_TEST) and the blend
+            // (GS_BLEND_BODY).  GS_BLEND_STEP, the BRANCHY form: the body runs behind the any-lane branch, which skips most
+            // steps of a wave whose pixels are finished, and updates T in place.  GS_BLEND_STEP_FREE, the BRANCH-FREE form:
+            // no ballot of the pixel test and no conditional block — a step in which no pixel passes blends with
+            // alpha_eff = 0 on every lane, as a lane beside a passing one always did (the exp of such a lane runs on an np
+            // outside its domain and its result is dropped by the select on act) — and T goes from the pair TIN to the pair
+            // TOUT, which alternate from step to step: there is no join behind a branch, so no phi of T and no copy of it
+            // (NOTES.md Part XVII).  Which form a batch runs: BLEND_FREE_MIN_LIVE, below.
+#define GS_BLEND_TEST(AREC, BREC)                                                                             \
         const float dx = AREC.y - pxf;                                                                        \
         const f32x2 dy = f32x2{AREC.x, AREC.x} - pyf;                                                         \
         const float u = -(AREC.w * dx), wq = -(BREC.y * dx);                                                  \
@@ -4407,9 +4432,9 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
         } else {                                                                                              \
             p0 = f2u(np.x) < f2u(BREC.w); /* 0 <= -power <= L: see above */                                   \
             p1 = f2u(np.y) < f2u(BREC.w);                                                                     \
-        }                                                                                                     \
-        NEXT /* the next record's reads */                                                                    \
-        if (__builtin_amdgcn_ballot_w64(p0 || p1) != 0ull) {                                                  \
+        }
+#define GS_BLEND_BODY(BREC, ID, TIN, TOUT)                                                                    \
+        {                                                                                                     \
             float2 cq; /* g, b */                                                                             \
             float zq = 0.0f; /* AUX: depth, slot; CONTRIB: -, accumulator */                                  \
             uint32_t sq = 0u;                                                                                 \
@@ -4447,55 +4472,105 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_blend_grouped(uint32_t *__res
             /* a pixel that skips this splat blends it with alpha 0: T * (1 - 0) == T and */                  \
             /* fma(rgb, 0 * T, C) == C exactly, so no selects are needed on T and C */                        \
             f32x2 alpha_eff = {act0 ? alpha.x : 0.0f, act1 ? alpha.y : 0.0f};                                 \
-            f32x2 test_T = T * (f32x2{1.0f, 1.0f} - alpha_eff);                                               \
+            f32x2 test_T = TIN * (f32x2{1.0f, 1.0f} - alpha_eff);                                             \
             /* (no "act &&": a pixel that skips the splat has test_T == T, and T of a live, finished or */     \
             /* out-of-image pixel is never below 1e-4) */                                                     \
             const bool fin0 = test_T.x < 0.0001f, fin1 = test_T.y < 0.0001f;                                  \
             const uint64_t f0 = __builtin_amdgcn_ballot_w64(fin0), f1 = __builtin_amdgcn_ballot_w64(fin1);    \
             if ((f0 | f1) != 0ull) { /* rare: some pixel reached T < 1e-4 -> it stops here */                 \
-                if (fin0) { pyf.x = DEAD; alpha_eff.x = 0.0f; test_T.x = T.x; }                               \
-                if (fin1) { pyf.y = DEAD; alpha_eff.y = 0.0f; test_T.y = T.y; }                               \
+                if (fin0) { pyf.x = DEAD; alpha_eff.x = 0.0f; test_T.x = TIN.x; }                             \
+                if (fin1) { pyf.y = DEAD; alpha_eff.y = 0.0f; test_T.y = TIN.y; }                             \
                 remaining -= (uint32_t)__popcll(f0) + (uint32_t)__popcll(f1);                                 \
             }                                                                                                 \
-            const f32x2 wgt = alpha_eff * T;                                                                  \
+            const f32x2 wgt = alpha_eff * TIN;                                                                \
             C0 = pk_fma(f32x2{BREC.z, BREC.z}, wgt, C0);                                                      \
             C1 = pk_fma(f32x2{cq.x, cq.x}, wgt, C1);                                                          \
             C2 = pk_fma(f32x2{cq.y, cq.y}, wgt, C2);                                                          \
             if constexpr (AUX) {                                                                              \
                 D = pk_fma(f32x2{zq, zq}, wgt, D);                                                            \
-                pk0 = alpha_eff.x > 0.0f && T.x > aux.tcut ? sq : pk0;                                        \
-                pk1 = alpha_eff.y > 0.0f && T.y > aux.tcut ? sq : pk1;                                        \
+                pk0 = alpha_eff.x > 0.0f && TIN.x > aux.tcut ? sq : pk0;                                      \
+                pk1 = alpha_eff.y > 0.0f && TIN.y > aux.tcut ? sq : pk1;                                      \
             }                                                                                                 \
             if constexpr (CONTRIB) { /* wgt = 0 exactly where the step is no contribution (alpha_eff = 0) */  \
                 if (__builtin_amdgcn_ballot_w64(wgt.x > 0.0f || wgt.y > 0.0f) != 0ull)                        \
                     contrib_add<GL>(s_qh, s_max, sq, wgt.x, wgt.y, lg);                                       \
             }                                                                                                 \
-            T = test_T;                                                                                       \
-        }                                                                                                     \
+            TOUT = test_T;                                                                                    \
+        }
+#define GS_BLEND_STEP(AREC, BREC, ID, NEXT)                                                                   \
+    {                                                                                                         \
+        GS_BLEND_TEST(AREC, BREC)                                                                             \
+        NEXT /* the next record's reads */                                                                    \
+        if (__builtin_amdgcn_ballot_w64(p0 || p1) != 0ull) GS_BLEND_BODY(BREC, ID, T, T)                      \
+    }
+#define GS_BLEND_STEP_FREE(AREC, BREC, ID, NEXT, TIN, TOUT)                                                   \
+    {                                                                                                         \
+        GS_BLEND_TEST(AREC, BREC)                                                                             \
+        NEXT                                                                                                  \
+        GS_BLEND_BODY(BREC, ID, TIN, TOUT)                                                                    \
+        /* (the sums are due HERE: hipcc sank the four steps' accumulations into the loop's latch, behind the */ \
+        /* rare blocks, and kept every step's weight and colours alive until there: 102 registers) */         \
+        asm volatile("" : "+v"(C0), "+v"(C1), "+v"(C2));                                                      \
     }
 #define GS_LIST_ID(K) ((uint32_t) * (const uint16_t *)(lp + 2 * (K)))
 #define GS_LOAD_REC(R)                             \
     a_##R = *(const float4 *)(rbase + id_##R);     \
     b_##R = *(const float4 *)(rbase + id_##R + 16);
-            for (uint32_t q = 0; q < quads && remaining != 0u; q++) {
-                id_B = GS_LIST_ID(1);
-                GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
-                id_A = GS_LIST_ID(2);
-                GS_BLEND_STEP(a_B, b_B, id_B, GS_LOAD_REC(A))
-                id_B = GS_LIST_ID(3);
-                GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
-                id_A = GS_LIST_ID(4);      // (step 127: position 128 = the next row's first entry, or the pad)
-                GS_BLEND_STEP(a_B, b_B, id_B, GS_LOAD_REC(A))
-                lp += 8;
+            // Which form runs is wave-uniform and chosen once per batch, from the wave's live pixels at the top of the
+            // batch (tk.free_min_live: BLEND_FREE_MIN_LIVE, or what GS3D_BLEND_FREE_BODY pins).
+            const bool free_body = FREE_BODY && remaining >= tk.free_min_live;
+            if (free_body) {
+                // trip / 4 trips; the 0..3 steps left are the remainder's, below.  T alternates between two register pairs
+                // and is back in its own after a trip's four steps.
+                f32x2 T1;
+                for (uint32_t q = 0; q < (trip >> 2) && remaining != 0u; q++) {
+                    id_B = GS_LIST_ID(1);
+                    GS_BLEND_STEP_FREE(a_A, b_A, id_A, GS_LOAD_REC(B), T, T1)
+                    id_A = GS_LIST_ID(2);
+                    GS_BLEND_STEP_FREE(a_B, b_B, id_B, GS_LOAD_REC(A), T1, T)
+                    id_B = GS_LIST_ID(3);
+                    GS_BLEND_STEP_FREE(a_A, b_A, id_A, GS_LOAD_REC(B), T, T1)
+                    id_A = GS_LIST_ID(4);
+                    GS_BLEND_STEP_FREE(a_B, b_B, id_B, GS_LOAD_REC(A), T1, T)
+                    lp += 8;
+                }
             }
-            if ((trips & 1u) != 0u && remaining != 0u) {
+            // (two conditionals in a row, not if / else: with the two forms as the arms of one conditional hipcc kept the
+            // pixel state of the branch-free arm in registers of its own, copied in and out: 80 registers for 70)
+            if (!free_body) {
+                for (uint32_t q = 0; q < quads && remaining != 0u; q++) {
+                    id_B = GS_LIST_ID(1);
+                    GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
+                    id_A = GS_LIST_ID(2);
+                    GS_BLEND_STEP(a_B, b_B, id_B, GS_LOAD_REC(A))
+                    id_B = GS_LIST_ID(3);
+                    GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
+                    id_A = GS_LIST_ID(4);      // (step 127: position 128 = the next row's first entry, or the pad)
+                    GS_BLEND_STEP(a_B, b_B, id_B, GS_LOAD_REC(A))
+                    lp += 8;
+                }
+            }
+            // (every remainder step but the third reads the next offset and record, also where it is the last: what lies
+            // behind a row's last entry is valid, see above)
+            const uint32_t rem = free_body ? trip & 3u : (trips & 1u) << 1;
+            if (rem != 0u && remaining != 0u) {
                 id_B = GS_LIST_ID(1);
                 GS_BLEND_STEP(a_A, b_A, id_A, GS_LOAD_REC(B))
-                GS_BLEND_STEP(a_B, b_B, id_B, )
+                if ((rem & 2u) != 0u) {
+                    // (also the branchy loop's two-step remainder reads one offset and record ahead in its second step now —
+                    // in bounds, position 126 at most, and unused.  With that step written twice, once without the read,
+                    // Splat G = 4 took 82 registers for 72: NOTES.md Part XVII)
+                    id_A = GS_LIST_ID(2);
+                    GS_BLEND_STEP(a_B, b_B, id_B, GS_LOAD_REC(A))
+                    if ((rem & 1u) != 0u) GS_BLEND_STEP(a_A, b_A, id_A, )
+                }
             }
 #undef GS_LOAD_REC
 #undef GS_LIST_ID
+#undef GS_BLEND_STEP_FREE
 #undef GS_BLEND_STEP
+#undef GS_BLEND_BODY
+#undef GS_BLEND_TEST
         }
         if constexpr (CONTRIB) flush_pending = true;
     }
