@@ -552,6 +552,7 @@ extern "C" {
     pub fn gs_gaussians_buffer_components(g: *mut gs_gaussians_buffer, s: *mut gs_stream, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, labels_out: *mut gs_buffer, sizes_out: *mut gs_buffer, info_out: *mut gs_buffer) -> gs_status;
     pub fn gs_select_components(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, min_size: u32, max_size: u32, op: u32) -> gs_status;
     pub fn gs_select_connected(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, seeds: *const gs_selection, op: u32) -> gs_status;
+    pub fn gs_gaussians_buffer_create_simplified(src: *mut gs_gaussians_buffer, s: *mut gs_stream, among: *const gs_selection, cell_size: f32, dst_sh: u32, dst_cov: u32, cell_of_out: *mut gs_buffer, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

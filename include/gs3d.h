@@ -1317,6 +1317,56 @@ gs_status gs_select_connected(gs_selection *sel, gs_stream *s, gs_gaussians_buff
                               const gs_model_transform_pod *model_transform, float radius, const gs_selection *seeds,
                               gs_select_op op);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Simplify: merge the Gaussians of each grid cell into one (no reference       */
+/* item): a preview, a far level of detail, a scene that has to fit a smaller card              */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  CELLS are those of 3.11 for radius = cell_size on the STORED positions
+ * (no model transform): Gaussian i is a POINT iff it is in `among` (NULL: all) and its three position words are finite; its
+ * cell is the 3 x 21-bit key of 3.11, computed in binary64 from the bounding box of the points and
+ * h = max(cell_size (1 + 2^-10), extent 2^-21 (1 + 2^-10), 2^-62), so cell membership is bit-defined.  Non-points are dropped.
+ * Record k of the result is the k-th occupied cell in ascending key order (z, y, x); K = the number of occupied cells.
+ *
+ * A cell with ONE member yields that record as gs_convert_pods converts it (gs_decompose_pods where the source is a covariance
+ * layout and the destination rotation + scale), bit for bit: an isolated Gaussian stays what it was.
+ *
+ * A cell with m >= 2 members: every value is decoded to binary32 as gs_unpack_to_gaussian decodes the source layout;
+ * alpha_i = byte 3 of word 3 / 255, Sigma_i = the decoded 3D covariance, s_i = (S00 + S11) + S22 (GS_ATTR_SIZE2),
+ * w_i = alpha_i s_i; if W = sum w_i is not > 0 or any w_i is not finite, w_i = 1 for the whole cell.  With c = the cell's
+ * centre lo + (cell + 0.5) h rounded to binary32 per axis and d_i = p_i - c:
+ *   position   c + delta,  delta = sum w_i d_i / W
+ *   covariance sum w_i (Sigma_i + d_i d_i^T) / W - delta delta^T, each diagonal term clamped at 0 from below (moments about the
+ *              cell centre: the cancellation is bounded by h^2, not by the scene's coordinates)
+ *   rgb, each of the 45 SH coefficients   sum w_i x_i / W; a colour byte is trunc(255 x + 0.5), saturated
+ *   opacity    clamp(W / ((S00 + S11) + S22), 0, 1) on the merged covariance, 0 if that trace is not > 0; with the w_i = 1
+ *              fallback clamp(sum alpha_i / m, 0, 1).  Opacity x size mass is kept: a cell of m identical Gaussians gives back
+ *              that Gaussian's position, covariance, colour and SH with the opacity min(1, m alpha).
+ * The merged record is the (SH f32, cov f32) record of these values, converted to the destination as gs_convert_pods converts
+ * it (a rotation + scale destination: as gs_decompose_pods does, through the device twin of gs_cov3d_decompose).
+ * The sums are binary32, added in a fixed shape without floating-point atomics: the same input gives the same bytes on every
+ * call, as gs_gaussians_buffer_stats promises for its sums.  THE SHAPE ITSELF IS NOT PART OF THE DEFINITION: a merged cell
+ * agrees with a binary64 evaluation of the formulas within (m + 16) 2^-24 sum w_i |t_i| / W per value (t_i: the summed term;
+ * a position adds 2^-24 |p| for the rounding of c + delta), not bit for bit. */
+
+/* *out = the simplified buffer of layout (dst_sh, dst_cov) — ALL 12 source and all 12 destination layouts are defined, because
+ * a covariance is produced here, not converted — and *count_out (or NULL) = K.  cell_of_out (or NULL): a device plane of at
+ * least 4 n bytes; word i receives the output index of the cell Gaussian i went into, 0xffffffff where i is not a point:
+ * this is how a caller carries labels, scores or a selection across the merge.  BLOCKING, like
+ * gs_gaussians_buffer_create_from_selection: one 4-byte round trip for K.  Ordered behind an edit or restore enqueued on
+ * another stream; shares the buffer's scratch with the calls of 3.11 / 3.16 (28 bytes per Gaussian of 3.11, 4 per 256
+ * Gaussians for the cell counts, 4 per Gaussian for the cells that are merged again with unit weights, 512 per 64 Gaussians
+ * for the sums of cells that cross a wave: 40 bytes per Gaussian) and records its event on every path.  The result takes the source's
+ * spatial-order setting; the source is not changed.  n = 0 or K = 0 gives the valid length-0 buffer of the destination layout.
+ * GS_ERR_INVALID_ARGUMENT, before anything is enqueued or allocated, with *out = NULL, *count_out = 0 and the plane
+ * untouched, for a null src or out, an unknown config, a cell_size that is negative, NaN or infinite or whose square is not
+ * finite in binary32, a selection whose length differs from the buffer's or that belongs to another device, a plane that is
+ * too small or on another device, a buffer of more than 0xfffffff0 Gaussians. */
+gs_status gs_gaussians_buffer_create_simplified(gs_gaussians_buffer *src, gs_stream *s, const gs_selection *among,
+                                                float cell_size, gs_sh_config dst_sh, gs_cov3d_config dst_cov,
+                                                gs_buffer *cell_of_out /* or NULL */, gs_gaussians_buffer **out,
+                                                uint64_t *count_out /* or NULL */);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

@@ -412,6 +412,12 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // not all three.
     void components(Stream &s, float radius, Buffer *labels, Buffer *sizes, Buffer *info, const Selection *among = nullptr,
                     const gs_model_transform_pod *mt = nullptr);
+    // simplify<To>: a new buffer of layout To (default: this one's; every layout is a valid target) in which the Gaussians
+    // of among (nullptr: all) that share a grid cell of side cell_size are merged into one, in cell order; blocking (gs3d.h
+    // gs_gaussians_buffer_create_simplified; no reference item).  cell_of (nullptr, or at least 4 len()
+    // bytes): word i = the record of the result Gaussian i went into, 0xffffffff where it is no point.
+    template <class To = G>
+    GaussiansBuffer<To> simplify(Stream &s, float cell_size, const Selection *among = nullptr, Buffer *cell_of = nullptr) const;
     // the .spz file image of the records of sel (nullptr: all; invert: of its complement), the payload deflated on the device
     // (gs3d.h gs_gaussians_buffer_export_spz_fast; no reference item); options == nullptr: the defaults.
     // Inflates to what gs_gaussians_buffer_export_spz_decompressed gives; blocking.
@@ -560,6 +566,15 @@ inline void GaussiansBuffer<G>::components(Stream &s, float radius, Buffer *labe
                                            const gs_model_transform_pod *mt) {
     check(gs_gaussians_buffer_components(h_, s.raw(), among ? among->raw() : nullptr, mt, radius, labels ? labels->raw() : nullptr,
                                          sizes ? sizes->raw() : nullptr, info ? info->raw() : nullptr));
+}
+
+template <class G>
+template <class To>
+inline GaussiansBuffer<To> GaussiansBuffer<G>::simplify(Stream &s, float cell_size, const Selection *among, Buffer *cell_of) const {
+    GaussiansBuffer<To> b;
+    check(gs_gaussians_buffer_create_simplified(h_, s.raw(), among ? among->raw() : nullptr, cell_size, To::sh, To::cov3d,
+                                                cell_of ? cell_of->raw() : nullptr, &b.h_, nullptr));
+    return b;
 }
 
 template <class G>

@@ -1258,6 +1258,36 @@ class GaussiansBuffer:
             raise
         return tuple(outs)
 
+    def simplify(self, stream, cell_size, pod=None, among=None, cell_of_out=None):
+        """gs_gaussians_buffer_create_simplified: a new GaussiansBuffer of layout `pod` (None: this
+        buffer's; every layout is a valid target) in which the Gaussians of `among` (None: all) that share a grid cell of
+        side `cell_size` on their stored positions are merged into one — opacity x size weighted mean, second moments about
+        the cell centre, opacity x size mass kept — in ascending cell order; a Gaussian alone in its cell is converted bit for
+        bit.  Blocking.  cell_of_out: True for a new Buffer, or a Buffer of at least 4 len() bytes; then (buffer, cell_of) is
+        returned and word i of the plane is the record Gaussian i went into, 0xffffffff where it is not in `among` or has no
+        finite position."""
+        cell_size, among, _ = _neighbor_args(cell_size, among, None)
+        pod = self.pod if pod is None else pod
+        if not isinstance(pod, GaussianPod):
+            raise TypeError("pod must be a GaussianPod or None, not %s" % type(pod).__name__)
+        own = cell_of_out is True
+        if own:
+            cell_of_out = Buffer(self.device, size=max(4 * self.len(), 4))
+        elif cell_of_out is not None and not isinstance(cell_of_out, Buffer):
+            raise TypeError("cell_of_out must be a Buffer, True or None, not %s" % type(cell_of_out).__name__)
+        h, count = C.c_void_p(), C.c_uint64()
+        try:
+            _check(_L.gs_gaussians_buffer_create_simplified(self._h, stream._h if stream is not None else None, among, cell_size,
+                                                            pod.sh, pod.cov, cell_of_out._h if cell_of_out is not None else None,
+                                                            C.byref(h), C.byref(count)))
+        except Exception:
+            if own:
+                cell_of_out.release()
+            raise
+        out = GaussiansBuffer(self.device, pod, h)
+        assert out.len() == count.value
+        return out if cell_of_out is None else (out, cell_of_out)
+
     def destroy(self):
         if self._h:
             _L.gs_gaussians_buffer_destroy(self._h)

@@ -290,6 +290,7 @@ SIGNATURES = {
     "gs_gaussians_buffer_components": (i32, [vp, vp, vp, vp, f32, vp, vp, vp]),
     "gs_select_components": (i32, [vp, vp, vp, vp, vp, f32, u32, u32, i32]),
     "gs_select_connected": (i32, [vp, vp, vp, vp, vp, f32, vp, i32]),
+    "gs_gaussians_buffer_create_simplified": (i32, [vp, vp, vp, f32, i32, i32, vp, vp, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

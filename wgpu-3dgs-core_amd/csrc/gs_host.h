@@ -335,6 +335,7 @@ struct NeighborGrid {
     const uint64_t *keys = nullptr;
     const uint32_t *vals = nullptr;
     const float *sx = nullptr, *sy = nullptr, *sz = nullptr;
+    const float *bbox = nullptr;      // lo xyz, hi xyz of the points (k_bbox_final): what nb_grid makes the cells from
     uint32_t *plane = nullptr;
     void *extra = nullptr;
     uint32_t n = 0, nblocks = 0;      // nblocks: of 256 slots

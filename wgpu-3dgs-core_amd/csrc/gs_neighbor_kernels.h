@@ -66,28 +66,7 @@ __global__ __launch_bounds__(256) void k_nb_bbox_partial(const uint32_t *__restr
     }
 }
 
-// The cell side from the bounding box (k_bbox_final) and the radius, in binary64:
-//   h = max(r (1 + 2^-10), extent 2^-21 (1 + 2^-10), 2^-62)
-// r (1 + 2^-10): the margin of DESIGN.md §3.11; extent 2^-21: 21 bits per axis cover the box WITHOUT a cap on the
-// resolution where r is larger (a far outlier only grows the box); 2^-62: r = 0, and every difference whose square is
-// subnormal in binary32 (< 2^-63) stays inside one cell side.  No point: lo = 0.
-__device__ __forceinline__ double nb_grid(const float *__restrict__ bbox, float radius, double lo[3]) {
-    double ext = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const bool any = bbox[a] <= bbox[3 + a];
-        lo[a] = any ? (double)bbox[a] : 0.0;
-        ext = fmax(ext, any ? (double)bbox[3 + a] - (double)bbox[a] : 0.0);
-    }
-    const double margin = 1.0 + 0x1p-10;
-    const double h = fmax(fmax((double)radius * margin, ext * 0x1p-21 * margin), 0x1p-62);
-    return 1.0 / h;
-}
-
-__device__ __forceinline__ uint32_t nb_cell(float v, double lo, double inv_h) {
-    const double u = ((double)v - lo) * inv_h;      // >= 0: lo is the smallest coordinate of a point
-    return u >= (double)NB_CELL_MAX ? NB_CELL_MAX : (u > 0.0 ? (uint32_t)u : 0u);
-}
+// (nb_grid and nb_cell, the cell side and the cell of a coordinate: gs_neighbor_grid.h)
 
 // keys[i] = the cell key of Gaussian i (NB_KEY_NONE: not a point), vals[i] = i
 __global__ __launch_bounds__(256) void k_nb_keys(const uint32_t *__restrict__ aos, uint32_t pod_words, uint32_t n,

@@ -63,6 +63,7 @@ gs_status gsh::neighbor_grid_enqueue(gs_gaussians_buffer *g, hipStream_t st, con
     grid.sx = sx;
     grid.sy = sy;
     grid.sz = sz;
+    grid.bbox = bbox;
     grid.plane = (uint32_t *)(base + 2 * (a8 + a4));
     grid.extra = base + 2 * (a8 + a4) + a4 + part + 256;
     grid.n = n;
