@@ -87,6 +87,9 @@ pub const GS_CONTRIB_MAX: u32 = 2;
 
 pub const GS_COMPARE_SSIM: u32 = 1;
 
+pub const GS_KNN_KTH_DIST2: u32 = 0;
+pub const GS_KNN_MEAN_DIST: u32 = 1;
+
 #[repr(C)] pub struct gs_device { _private: [u8; 0] }
 #[repr(C)] pub struct gs_stream { _private: [u8; 0] }
 #[repr(C)] pub struct gs_buffer { _private: [u8; 0] }
@@ -382,6 +385,17 @@ pub struct gs_components_info {
     pub largest_label: u32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_knn_summary_result {
+    pub points: u64,
+    pub complete: u64,
+    pub min: f32,
+    pub max: f32,
+    pub sum: f64,
+    pub sum_sq: f64,
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -553,6 +567,9 @@ extern "C" {
     pub fn gs_select_components(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, min_size: u32, max_size: u32, op: u32) -> gs_status;
     pub fn gs_select_connected(sel: *mut gs_selection, s: *mut gs_stream, gaussians: *mut gs_gaussians_buffer, among: *const gs_selection, model_transform: *const gs_model_transform_pod, radius: f32, seeds: *const gs_selection, op: u32) -> gs_status;
     pub fn gs_gaussians_buffer_create_simplified(src: *mut gs_gaussians_buffer, s: *mut gs_stream, among: *const gs_selection, cell_size: f32, dst_sh: u32, dst_cov: u32, cell_of_out: *mut gs_buffer, out: *mut *mut gs_gaussians_buffer, count_out: *mut u64) -> gs_status;
+    pub fn gs_gaussians_buffer_knn(g: *mut gs_gaussians_buffer, s: *mut gs_stream, among: *const gs_selection, queries: *const gs_selection, model_transform: *const gs_model_transform_pod, k: u32, radius: f32, dist2_out: *mut gs_buffer, index_out: *mut gs_buffer) -> gs_status;
+    pub fn gs_select_knn(sel: *mut gs_selection, s: *mut gs_stream, dist2_plane: *const gs_buffer, k: u32, kind: u32, lo: f32, hi: f32, op: u32) -> gs_status;
+    pub fn gs_knn_summary(s: *mut gs_stream, dist2_plane: *const gs_buffer, n: u64, k: u32, kind: u32, out: *mut gs_knn_summary_result) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
 }

@@ -1367,6 +1367,69 @@ gs_status gs_gaussians_buffer_create_simplified(gs_gaussians_buffer *src, gs_str
                                                 gs_buffer *cell_of_out /* or NULL */, gs_gaussians_buffer **out,
                                                 uint64_t *count_out /* or NULL */);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Nearest neighbours: k-NN distances, select by them, their summary (no       */
+/* reference item): the radius the calls of 3.11 / 3.16 / 3.17 need, statistical outliers     */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  pw_i, POINT, `among`, the NULL transform and the binary32 squared
+ * distance d2(i, j) = (d.x d.x + d.y d.y) + d.z d.z, d = pw_i - pw_j, are those of 3.11, unchanged: every operation rounded,
+ * nothing fused, rr = r r rounded once on the host.  For a point i, a radius r and 1 <= k <= 16 the CANDIDATES are the points
+ * j != i with d2(i, j) <= rr, ordered by the pair (bits of d2, caller index j), smaller first: d2 is never negative and never
+ * NaN for points, so the bit order is the value order, and equal distances go to the smaller caller index.  The ROW of i is
+ * the first min(k, candidates) of them — k values d2_t ascending and k indices j_t — padded with +inf and GS_KNN_NONE; it is
+ * COMPLETE iff there are at least k candidates.  The row depends on neither the traversal, the grid nor the cell size, and a
+ * complete row is the same for every larger radius: it is bit-defined, indices included.
+ *
+ * A STATISTIC maps a row to one binary32 value v.  GS_KNN_KTH_DIST2: v = d2_{k-1}.  GS_KNN_MEAN_DIST: v = s / (float)k with
+ * s = ((sqrtf(d2_0) + sqrtf(d2_1)) + ...) + sqrtf(d2_{k-1}), the correctly rounded root and quotient.  Both are +inf for an
+ * incomplete row and undefined for a row whose first value is NaN: such a row belongs to no point.
+ *
+ * Cost: the sort and the traversal of 3.11 without a cap; each point keeps its k best candidates in registers, and its
+ * acceptance bound shrinks from rr to its k-th distance once it holds k.  A radius far above the k-th distances costs what
+ * the count of 3.11 costs at that radius: quadratic when most of the scene is in one ball. */
+#define GS_KNN_NONE 0xFFFFFFFFu
+#define GS_KNN_MAX_K 16
+enum { GS_KNN_KTH_DIST2 = 0, GS_KNN_MEAN_DIST = 1 };
+
+/* The rows of the Gaussians of `queries` (NULL: all) in caller order, record-major: the row of Gaussian i is dist2_out[i k ..
+ * i k + k) (binary32) and index_out[i k .. i k + k) (uint32_t; index_out may be NULL) (no reference item).
+ * Each plane holds at least 4 k n bytes on the buffer's device; bytes behind 4 k n and every row outside `queries` keep every
+ * byte.  A written row of a Gaussian that is no point (outside `among`, or not finite) is all NaN / GS_KNN_NONE.  Only
+ * ENQUEUES on `s` (NULL: the device's internal stream), ordered behind an edit or restore enqueued on another stream; shares
+ * the buffer's scratch and its event with the calls of 3.11.  A buffer of length 0 is valid and launches nothing.
+ * GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with the planes untouched, for a null buffer or distance plane, a
+ * radius that is negative, NaN or infinite or whose square is not finite in binary32, k outside 1..16, a plane that is too
+ * small or on another device, a selection (`among` or `queries`) whose length differs from the buffer's or that belongs to
+ * another device, a buffer of more than 0xfffffff0 Gaussians. */
+gs_status gs_gaussians_buffer_knn(gs_gaussians_buffer *g, gs_stream *s, const gs_selection *among, const gs_selection *queries,
+                                  const gs_model_transform_pod *model_transform, uint32_t k, float radius, gs_buffer *dist2_out,
+                                  gs_buffer *index_out /* or NULL */);
+/* sel = sel op {i : row i is a point's and lo <= v_i <= hi}, v = the statistic `kind` of row i of the plane, computed from the
+ * plane alone: n = gs_selection_len(sel) rows of k values (no reference item).  A NaN row is never selected;
+ * lo > hi selects nothing; infinite bounds are allowed, and lo = hi = +inf selects exactly the incomplete rows.  Only ENQUEUES
+ * on `s` (NULL: the device's internal stream); the mask is written word-wise as by gs_select_sphere.
+ * GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with the selection unchanged, for a null selection or plane, an
+ * unknown op or kind, k outside 1..16, a NaN bound, a plane that is smaller than 4 k n bytes or on another device. */
+gs_status gs_select_knn(gs_selection *sel, gs_stream *s, const gs_buffer *dist2_plane, uint32_t k, uint32_t kind, float lo,
+                        float hi, gs_select_op op);
+/* What gs_knn_summary fills (no reference item).  points: the rows whose first value is not NaN; complete:
+ * those of them that are complete.  min / max of v over the complete rows by the order of the bit patterns, +inf / -inf when
+ * there are none; sum and sum_sq of v and v v over the complete rows, widened to binary64 and added in a fixed shape (no
+ * floating-point atomics): the same bits from run to run. */
+typedef struct gs_knn_summary_result {
+    uint64_t points, complete;
+    float min, max;
+    double sum, sum_sq;
+} gs_knn_summary_result;
+/* The summary of the statistic `kind` over the n rows of k values of a distance plane (no reference item):
+ * mean = sum / complete and variance = sum_sq / complete - mean mean are the caller's, in binary64.  BLOCKING on `s` (NULL:
+ * the device's internal stream), like gs_gaussians_buffer_stats.  n = 0 is valid: counts 0, min +inf, max -inf.
+ * GS_ERR_INVALID_ARGUMENT, with *out untouched, for a null plane or out, an unknown kind, k outside 1..16, n above 0xfffffff0,
+ * a plane smaller than 4 k n bytes. */
+gs_status gs_knn_summary(gs_stream *s, const gs_buffer *dist2_plane, uint64_t n, uint32_t k, uint32_t kind,
+                         gs_knn_summary_result *out);
+
 /* Stand-alone device primitives used by the frame (also exported for tests and callers):
  * stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, end_bit) — host buffers in/out,
  * blocking; and exclusive prefix sum of u32. */

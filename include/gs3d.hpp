@@ -418,6 +418,12 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // bytes): word i = the record of the result Gaussian i went into, 0xffffffff where it is no point.
     template <class To = G>
     GaussiansBuffer<To> simplify(Stream &s, float cell_size, const Selection *among = nullptr, Buffer *cell_of = nullptr) const;
+    // the k nearest other Gaussians of among (nullptr: all) within radius of every Gaussian of queries (nullptr: all): row i
+    // of dist2 = k binary32 squared distances ascending, padded with +inf; row i of index (nullptr: not wanted) = their
+    // indices, padded with GS_KNN_NONE; NaN rows where i is no point (gs3d.h gs_gaussians_buffer_knn; no
+    // reference item); only enqueues.  A plane holds at least 4 k len() bytes; rows outside queries keep their bytes.
+    void knn(Stream &s, uint32_t k, float radius, Buffer &dist2, Buffer *index = nullptr, const Selection *among = nullptr,
+             const Selection *queries = nullptr, const gs_model_transform_pod *mt = nullptr);
     // the .spz file image of the records of sel (nullptr: all; invert: of its complement), the payload deflated on the device
     // (gs3d.h gs_gaussians_buffer_export_spz_fast; no reference item); options == nullptr: the defaults.
     // Inflates to what gs_gaussians_buffer_export_spz_decompressed gives; blocking.
@@ -479,6 +485,12 @@ class Selection {
     void select_connected(Stream &s, GaussiansBuffer<G> &g, float radius, const Selection &seeds, const Selection *among = nullptr,
                           const gs_model_transform_pod *mt = nullptr, gs_select_op op = GS_SEL_SET) {
         check(gs_select_connected(h_, s.raw(), g.raw(), among ? among->raw() : nullptr, mt, radius, seeds.raw(), op));
+    }
+    // sel = sel op {i : row i is a point's and lo <= v_i <= hi}, v the GS_KNN_* statistic of row i of the len() rows of k
+    // values in dist2, a plane of GaussiansBuffer::knn (gs_select_knn; no reference item); only enqueues.
+    // lo = hi = +inf: exactly the incomplete rows
+    void select_knn(Stream &s, const Buffer &dist2, uint32_t k, uint32_t kind, float lo, float hi, gs_select_op op = GS_SEL_SET) {
+        check(gs_select_knn(h_, s.raw(), dist2.raw(), k, kind, lo, hi, op));
     }
     // sel = sel op {i : lo <= v_i <= hi}, v the GS_CONTRIB_* value of record i of `contrib` (gs_select_contribution,
     // DESIGN.md 3.5c); only enqueues
@@ -575,6 +587,20 @@ inline GaussiansBuffer<To> GaussiansBuffer<G>::simplify(Stream &s, float cell_si
     check(gs_gaussians_buffer_create_simplified(h_, s.raw(), among ? among->raw() : nullptr, cell_size, To::sh, To::cov3d,
                                                 cell_of ? cell_of->raw() : nullptr, &b.h_, nullptr));
     return b;
+}
+
+template <class G>
+inline void GaussiansBuffer<G>::knn(Stream &s, uint32_t k, float radius, Buffer &dist2, Buffer *index, const Selection *among,
+                                    const Selection *queries, const gs_model_transform_pod *mt) {
+    check(gs_gaussians_buffer_knn(h_, s.raw(), among ? among->raw() : nullptr, queries ? queries->raw() : nullptr, mt, k, radius,
+                                  dist2.raw(), index ? index->raw() : nullptr));
+}
+// the summary of the GS_KNN_* statistic over the n rows of k values in dist2 (gs3d.h gs_knn_summary; no
+// reference item); blocking
+inline gs_knn_summary_result knn_summary(Stream &s, const Buffer &dist2, uint64_t n, uint32_t k, uint32_t kind) {
+    gs_knn_summary_result r;
+    check(gs_knn_summary(s.raw(), dist2.raw(), n, k, kind, &r));
+    return r;
 }
 
 template <class G>

@@ -846,6 +846,71 @@ def _neighbor_args(radius, among, model_transform):
             C.byref(model_transform) if model_transform is not None else None)
 
 
+KNN_NONE = 0xFFFFFFFF                # GS_KNN_NONE: the index of a padding entry of a k-NN row
+KNN_MAX_K = 16                       # GS_KNN_MAX_K
+KNN_KTH_DIST2, KNN_MEAN_DIST = 0, 1  # GS_KNN_*: the statistic select_knn / knn_summary take of a row
+_KNN_KINDS = {"kth_dist2": KNN_KTH_DIST2, "mean_dist": KNN_MEAN_DIST}
+
+
+def _knn_k(k):
+    """k of the k-NN calls, checked before any library call: an integer in 1..KNN_MAX_K"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError("k must be an integer, not %s" % type(k).__name__)
+    if not 1 <= int(k) <= KNN_MAX_K:
+        raise ValueError("k must be between 1 and %d, not %d" % (KNN_MAX_K, k))
+    return int(k)
+
+
+def knn_kind(kind):
+    """GS_KNN_* from its number or name ('kth_dist2', 'mean_dist'); ValueError for anything else."""
+    if isinstance(kind, str) and kind.lower() in _KNN_KINDS:
+        return _KNN_KINDS[kind.lower()]
+    if isinstance(kind, (int, np.integer)) and not isinstance(kind, bool) and int(kind) in (KNN_KTH_DIST2, KNN_MEAN_DIST):
+        return int(kind)
+    raise ValueError("unknown k-NN statistic %r (one of %s)" % (kind, ", ".join(_KNN_KINDS)))
+
+
+@dataclasses.dataclass
+class KnnSummary:
+    """gs_knn_summary_result: the rows of a distance plane that are a point's, those that are complete, and over the
+    complete rows' statistic v its bit-defined min and max (+inf / -inf without one) and the binary64 sums of v and v v."""
+    points: int
+    complete: int
+    min: np.float32
+    max: np.float32
+    sum: float
+    sum_sq: float
+
+    @property
+    def mean(self):
+        return self.sum / self.complete if self.complete else float("nan")
+
+    @property
+    def std(self):
+        """the population standard deviation, in binary64"""
+        if not self.complete:
+            return float("nan")
+        return float(np.sqrt(max(self.sum_sq / self.complete - self.mean * self.mean, 0.0)))
+
+
+def knn_summary(stream, dist2_plane, n, k, kind=KNN_KTH_DIST2):
+    """gs_knn_summary: a KnnSummary of the statistic `kind` (KNN_KTH_DIST2, KNN_MEAN_DIST or their
+    names) over the n rows of k values of `dist2_plane`, a Buffer GaussiansBuffer.knn filled.  Blocking."""
+    if stream is not None and not isinstance(stream, Stream):
+        raise TypeError("stream must be a Stream or None, not %s" % type(stream).__name__)
+    if not isinstance(dist2_plane, Buffer):
+        raise TypeError("dist2_plane must be a Buffer, not %s" % type(dist2_plane).__name__)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise TypeError("n must be an integer, not %s" % type(n).__name__)
+    if int(n) < 0:
+        raise ValueError("n must be >= 0, not %d" % n)
+    k, kind = _knn_k(k), knn_kind(kind)
+    out = _capi.KnnSummaryRecord()
+    _check(_L.gs_knn_summary(stream._h if stream is not None else None, dist2_plane._h, int(n), k, kind, C.byref(out)))
+    return KnnSummary(points=int(out.points), complete=int(out.complete), min=np.float32(out.min), max=np.float32(out.max),
+                      sum=float(out.sum), sum_sq=float(out.sum_sq))
+
+
 class GaussiansBuffer:
     """GaussiansBuffer<G> — src/buffer/gaussian.rs:17-229."""
 
@@ -1287,6 +1352,91 @@ class GaussiansBuffer:
         out = GaussiansBuffer(self.device, pod, h)
         assert out.len() == count.value
         return out if cell_of_out is None else (out, cell_of_out)
+
+    def knn(self, stream, k, radius, among=None, queries=None, model_transform=None, dist2_out=None, index_out=None,
+            indices=False):
+        """gs_gaussians_buffer_knn: a Buffer of k binary32 values per Gaussian in caller order, row i at
+        i k: the squared distances from Gaussian i to its k nearest other Gaussians of `among` (None: all) within `radius`,
+        ascending, ties to the smaller index, padded with +inf where fewer than k lie within the radius; all NaN where i is
+        not in `among` or has no finite world position.  indices=True (or an index_out Buffer): (dist2, index) is returned,
+        the second plane holding the uint32 indices of those neighbours, KNN_NONE in the padding.  `queries` (a Selection;
+        None: all) names the rows that are written: every other row of a Buffer that is given keeps its bytes.  Only
+        enqueues; read the planes with Buffer.download.  A Buffer that is given holds at least 4 k len() bytes."""
+        k = _knn_k(k)
+        radius, among, mt = _neighbor_args(radius, among, model_transform)
+        if queries is not None and not isinstance(queries, Selection):
+            raise TypeError("queries must be a Selection or None, not %s" % type(queries).__name__)
+        for name, b in (("dist2_out", dist2_out), ("index_out", index_out)):
+            if b is not None and not isinstance(b, Buffer):
+                raise TypeError("%s must be a Buffer or None, not %s" % (name, type(b).__name__))
+        if not isinstance(indices, bool):
+            raise TypeError("indices must be a bool, not %s" % type(indices).__name__)
+        own = []
+        try:
+            if dist2_out is None:
+                dist2_out = Buffer(self.device, size=max(4 * k * self.len(), 4))
+                own.append(dist2_out)
+            if index_out is None and indices:
+                index_out = Buffer(self.device, size=max(4 * k * self.len(), 4))
+                own.append(index_out)
+            _check(_L.gs_gaussians_buffer_knn(self._h, stream._h if stream is not None else None, among,
+                                              queries._h if queries is not None else None, mt, k, radius, dist2_out._h,
+                                              index_out._h if index_out is not None else None))
+        except Exception:
+            for b in own:
+                b.release()
+            raise
+        return dist2_out if index_out is None else (dist2_out, index_out)
+
+    def knn_auto(self, stream, k, among=None, model_transform=None, radius0=None, max_passes=24):
+        """The k-NN rows without a radius guess: (dist2, index, radius, passes).  A host policy over knn, select_knn and
+        Selection.count (not normative): the bounds and the point count come from stats(); the first pass
+        writes every row at radius0 (None: half the largest extent times (k / points)^(1/3)); while rows are incomplete,
+        the radius is below the diagonal of the bounding box and passes remain, the radius doubles and the incomplete rows
+        alone are searched again.  A complete row is the same at every larger radius, so the planes equal those of one knn
+        call at the returned radius bit for bit.  Blocks once per pass (the count of incomplete rows)."""
+        k = _knn_k(k)
+        if not isinstance(stream, Stream):
+            raise TypeError("stream must be a Stream, not %s" % type(stream).__name__)
+        _neighbor_args(0.0, among, model_transform)
+        if isinstance(max_passes, bool) or not isinstance(max_passes, (int, np.integer)):
+            raise TypeError("max_passes must be an integer, not %s" % type(max_passes).__name__)
+        if int(max_passes) < 1:
+            raise ValueError("max_passes must be at least 1, not %d" % max_passes)
+        if radius0 is not None:
+            radius0 = np.float32(_neighbor_args(radius0, None, None)[0])
+        st = self.stats(stream, selection=among, model_transform=model_transform)
+        points = int(st.finite[:3].min())
+        lo, hi = st.bounds
+        ext = (hi.astype(np.float64) - lo.astype(np.float64)) if points else np.zeros(3)
+        diagonal = float(np.sqrt((ext * ext).sum()))
+        limit = np.float32(1.8e19)      # the largest radius whose binary32 square is finite, rounded down
+        if radius0 is None:
+            radius0 = np.float32(min(0.5 * float(ext.max()) * (k / points) ** (1.0 / 3.0), float(limit))) if points else np.float32(0.0)
+        radius, n = radius0, self.len()
+        dist2, index = self.knn(stream, k, float(radius), among=among, model_transform=model_transform, indices=True)
+        passes, todo = 1, None
+        try:
+            while passes < int(max_passes) and float(radius) < diagonal and radius < limit:
+                if todo is None:
+                    todo = Selection(self.device, n)
+                todo.select_knn(stream, dist2, k, KNN_KTH_DIST2, float("inf"), float("inf"))
+                if not todo.count(stream):
+                    break
+                radius = min(radius * np.float32(2.0), limit) if radius > 0 else np.float32(min(diagonal * 2.0 ** -10, float(limit)))
+                self.knn(stream, k, float(radius), among=among, queries=todo, model_transform=model_transform, dist2_out=dist2,
+                         index_out=index)
+                passes += 1
+            stream.synchronize()
+        except Exception:
+            dist2.release()
+            index.release()
+            raise
+        finally:
+            if todo is not None:
+                stream.synchronize()
+                todo.destroy()
+        return dist2, index, float(radius), passes
 
     def destroy(self):
         if self._h:
@@ -1849,6 +1999,59 @@ class Selection:
         op = select_op(op)
         _check(_L.gs_select_connected(self._h, stream._h if stream is not None else None, gaussians._h, among, mt, radius,
                                       seeds._h, op))
+
+    def select_knn(self, stream, dist2_plane, k, kind, lo, hi, op=SEL_SET):
+        """self = self op {i : row i is a point's and lo <= v_i <= hi}, v = the statistic `kind` (KNN_KTH_DIST2: the k-th
+        squared distance; KNN_MEAN_DIST: the mean distance to the k neighbours; or their names) of row i of `dist2_plane`, a
+        Buffer of len(self) rows of k values that GaussiansBuffer.knn filled (gs_select_knn); only
+        enqueues.  v of an incomplete row is +inf: lo = hi = inf selects exactly those.  A NaN row is never selected;
+        infinite bounds are allowed, NaN bounds are not; lo > hi selects nothing."""
+        if not isinstance(dist2_plane, Buffer):
+            raise TypeError("dist2_plane must be a Buffer, not %s" % type(dist2_plane).__name__)
+        k, kind = _knn_k(k), knn_kind(kind)
+        for name, v in (("lo", lo), ("hi", hi)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError("%s must be a number, not %s" % (name, type(v).__name__))
+        lo, hi = float(lo), float(hi)
+        if lo != lo or hi != hi:
+            raise ValueError("a bound of the range is NaN")
+        op = select_op(op)
+        _check(_L.gs_select_knn(self._h, stream._h if stream is not None else None, dist2_plane._h, k, kind, lo, hi, op))
+
+    def select_statistical_outliers(self, stream, gaussians, k=8, sigma=2.0, among=None, model_transform=None, op=SEL_SET,
+                                    radius0=None, max_passes=24):
+        """self = self op {the statistical outliers of `gaussians`}: (threshold, radius).  The filter of PCL / Open3D as a
+        host policy over GaussiansBuffer.knn_auto, knn_summary and select_knn (not normative): v_i = the
+        mean distance from Gaussian i to its k nearest neighbours, threshold = mean + sigma std of v over the complete rows
+        in binary64, and every Gaussian with v_i > threshold is selected — a row that is still incomplete at the radius
+        knn_auto ended with has v = +inf and is an outlier too.  Gaussians outside `among` or without a finite world
+        position are never selected.  Blocking."""
+        if not isinstance(gaussians, GaussiansBuffer):
+            raise TypeError("gaussians must be a GaussiansBuffer, not %s" % type(gaussians).__name__)
+        k = _knn_k(k)
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)):
+            raise TypeError("sigma must be a number, not %s" % type(sigma).__name__)
+        if not np.isfinite(sigma):
+            raise ValueError("sigma must be finite, not %r" % (sigma,))
+        op = select_op(op)
+        if len(self) != gaussians.len():
+            raise ValueError("the selection has %d bits, the buffer %d Gaussians" % (len(self), gaussians.len()))
+        dist2, index, radius, _ = gaussians.knn_auto(stream, k, among=among, model_transform=model_transform, radius0=radius0,
+                                                     max_passes=max_passes)
+        try:
+            s = knn_summary(stream, dist2, len(self), k, KNN_MEAN_DIST)
+            threshold = s.mean + float(sigma) * s.std if s.complete else float("inf")
+            # the smallest binary32 above the threshold: the range of select_knn is closed
+            with np.errstate(over="ignore"):
+                lo = np.float32(threshold)
+            if float(lo) <= threshold:
+                lo = np.nextafter(lo, np.float32(np.inf))
+            self.select_knn(stream, dist2, k, KNN_MEAN_DIST, float(lo), float("inf"), op)
+            stream.synchronize()
+        finally:
+            dist2.release()
+            index.release()
+        return threshold, radius
 
     def destroy(self):
         if self._h:

@@ -78,6 +78,11 @@ class Stats(C.Structure):
     _fields_ = [("count", u64), ("attr", AttributeStats * 9)]
 
 
+class KnnSummaryRecord(C.Structure):
+    """gs_knn_summary_result: what gs_knn_summary fills"""
+    _fields_ = [("points", u64), ("complete", u64), ("min", f32), ("max", f32), ("sum", C.c_double), ("sum_sq", C.c_double)]
+
+
 class ImageCompareDesc(C.Structure):
     """gs_image_compare_desc: flags, data range and the optional device planes of gs_image_compare"""
     _fields_ = [("flags", u32), ("data_range", f32), ("err_plane", vp), ("ssim_plane", vp), ("reserved", u32 * 4)]
@@ -291,6 +296,9 @@ SIGNATURES = {
     "gs_select_components": (i32, [vp, vp, vp, vp, vp, f32, u32, u32, i32]),
     "gs_select_connected": (i32, [vp, vp, vp, vp, vp, f32, vp, i32]),
     "gs_gaussians_buffer_create_simplified": (i32, [vp, vp, vp, f32, i32, i32, vp, vp, vp]),
+    "gs_gaussians_buffer_knn": (i32, [vp, vp, vp, vp, vp, u32, f32, vp, vp]),
+    "gs_select_knn": (i32, [vp, vp, vp, u32, u32, f32, f32, i32]),
+    "gs_knn_summary": (i32, [vp, vp, u64, u32, u32, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
 }

@@ -1,9 +1,9 @@
-// gs_device_common.h — what the kernel headers of the render, pack, select, edit, relayout, stats and neighbour units share beyond
+// gs_device_common.h — what the kernel headers of the render, pack, select, edit, relayout, stats, neighbour and k-NN units share beyond
 // gs_kernel_lib.h (gs_bundle_kernels.h needs only that one): WAVE and PLANAR_BLOCK, the wave / block primitives,
 // attr_finite, the selection-mask helpers (SEL_*, sel_apply, SelectShape, wave_selection_mask) and the two scalar encoders
 // that both the pack kernels and the edit kernel use.  It holds no kernel: every *_kernels.h is included by exactly one
 // translation unit of the library — but gs_pack_kernels.h, whose per-record functions the relayout unit
-// shares with gs_core.hip — this header by seven of them.
+// shares with gs_core.hip — this header by eight of them.
 #pragma once
 
 #include "gs_kernel_lib.h"
@@ -101,6 +101,14 @@ __device__ __forceinline__ uint32_t block_exclusive_scan_256(uint32_t v, uint32_
 __device__ __forceinline__ uint64_t wave_reduce_add64(uint64_t v) {
 #pragma unroll
     for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor((unsigned long long)v, d, WAVE);
+    return v;
+}
+
+// wave sum of a double in a fixed shape (a butterfly: both partners of a step add the same two values), uniform in
+// every lane; all 64 lanes active (gs_stats_kernels.h, gs_knn_kernels.h)
+__device__ __forceinline__ double wave_reduce_add_f64(double v) {
+#pragma unroll
+    for (int d = WAVE / 2; d > 0; d >>= 1) v = v + __shfl_xor(v, d, WAVE);
     return v;
 }
 

@@ -1,5 +1,5 @@
-// gs_neighbor_grid.h — what the two kernel headers that walk the sorted cell grid share (gs_neighbor_kernels.h: DESIGN.md
-// §3.11; gs_component_kernels.h: §3.16): the layout of a cell key and the wave broadcast.  No kernel lives here.
+// gs_neighbor_grid.h — what the kernel headers that walk the sorted cell grid share (gs_neighbor_kernels.h: DESIGN.md
+// §3.11; gs_component_kernels.h: §3.16; gs_knn_kernels.h: §3.18): the layout of a cell key and the wave broadcast.  No kernel lives here.
 #pragma once
 
 #include "gs_device_common.h"

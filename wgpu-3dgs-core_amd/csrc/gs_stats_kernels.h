@@ -67,13 +67,7 @@ __device__ __forceinline__ uint64_t wave_selection_mask_uniform(const uint32_t *
            ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(m >> 32)) << 32);
 }
 
-// wave sum of a double in a fixed shape (a butterfly: both partners of a step add the same two values), uniform in
-// every lane; all 64 lanes active
-__device__ __forceinline__ double wave_reduce_add_f64(double v) {
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) v = v + __shfl_xor(v, d, WAVE);
-    return v;
-}
+// (wave_reduce_add_f64, the wave sum of a double in a fixed shape: gs_device_common.h, shared with gs_knn_kernels.h)
 
 // ---- gs_select_attribute -------------------------------------------------------------------------------------------
 
