@@ -396,6 +396,18 @@ pub struct gs_knn_summary_result {
     pub sum_sq: f64,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct gs_pair_sums {
+    pub pairs: u64,
+    pub sp: [f64; 3],
+    pub sq: [f64; 3],
+    pub spq: [f64; 9],
+    pub spp: f64,
+    pub sqq: f64,
+    pub sdd: f64,
+}
+
 #[link(name = "gs3d_hip")]
 extern "C" {
     pub fn gs_last_error(out: *mut gs_error_info);
@@ -572,4 +584,8 @@ extern "C" {
     pub fn gs_knn_summary(s: *mut gs_stream, dist2_plane: *const gs_buffer, n: u64, k: u32, kind: u32, out: *mut gs_knn_summary_result) -> gs_status;
     pub fn gs_sort_pairs_u64(dev: *mut gs_device, s: *mut gs_stream, keys: *mut u64, values: *mut u32, count: u64, end_bit: u32) -> gs_status;
     pub fn gs_exclusive_scan_u32(dev: *mut gs_device, s: *mut gs_stream, r#in: *const u32, out: *mut u32, count: u64, total_out: *mut u64) -> gs_status;
+    pub fn gs_gaussians_buffer_knn_between(queries_buf: *mut gs_gaussians_buffer, target: *mut gs_gaussians_buffer, s: *mut gs_stream, queries: *const gs_selection, among: *const gs_selection, query_transform: *const gs_model_transform_pod, target_transform: *const gs_model_transform_pod, k: u32, radius: f32, dist2_out: *mut gs_buffer, index_out: *mut gs_buffer) -> gs_status;
+    pub fn gs_gaussians_buffer_pair_sums(queries_buf: *mut gs_gaussians_buffer, target: *mut gs_gaussians_buffer, s: *mut gs_stream, queries: *const gs_selection, query_transform: *const gs_model_transform_pod, target_transform: *const gs_model_transform_pod, index_plane: *const gs_buffer, k: u32, out: *mut gs_pair_sums) -> gs_status;
+    pub fn gs_rigid_fit(sums: *const gs_pair_sums, with_scale: i32, delta_out: *mut gs_model_transform_pod, rms_out: *mut f64) -> gs_status;
+    pub fn gs_model_transform_compose(delta: *const gs_model_transform_pod, m: *const gs_model_transform_pod, out: *mut gs_model_transform_pod);
 }

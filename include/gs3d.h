@@ -1438,6 +1438,78 @@ gs_status gs_sort_pairs_u64(gs_device *dev, gs_stream *s, uint64_t *keys, uint32
 gs_status gs_exclusive_scan_u32(gs_device *dev, gs_stream *s, const uint32_t *in, uint32_t *out,
                                 uint64_t count, uint64_t *total_out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Nearest neighbours between two buffers: rows, overlap select, rigid fit (no */
+/* reference item): which Gaussians of A have a counterpart in B, how far apart, which transform */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The definition (no reference item).  Two buffers, each with its own model transform (NULL: the default pod):
+ * pw of a Gaussian of either side is M (p, 1) under ITS transform, in the arithmetic of 3.11; d2(i, j) = (d.x d.x + d.y d.y) +
+ * d.z d.z with d = pw_i - pw_j is the binary32 squared distance of 3.11 / 3.18, every operation rounded, nothing fused, rr = r r
+ * rounded once on the host.  A TARGET POINT is a Gaussian of the target that belongs to `among` (NULL: all) and whose pw is
+ * finite.  A QUERY is a Gaussian of the query buffer that belongs to `queries` (NULL: all); it is a point iff its pw is finite.
+ * The CANDIDATES of a query point i are ALL target points j with d2(i, j) <= rr — there is no self-exclusion, the buffers are two
+ * — ordered by the pair (bits of d2, target caller index j), smaller first.  The ROW of i is the first min(k, candidates) of
+ * them, padded with +inf and GS_KNN_NONE; it is COMPLETE iff there are at least k.  The row depends on neither the traversal,
+ * the grid nor the cell size, and a complete row is the same for every larger radius: it is bit-defined, indices included.
+ * The planes are those of 3.18, so gs_select_knn and gs_knn_summary take them unchanged, with n = the QUERY buffer's length.
+ *
+ * The rows of the queries in QUERY caller order, record-major: row i is dist2_out[i k .. i k + k) (binary32) and index_out[i k
+ * .. i k + k) (uint32_t TARGET caller indices; index_out may be NULL).  Each plane holds at least 4 k n_q bytes on the buffers'
+ * device; bytes behind 4 k n_q and every row outside `queries` keep every byte.  A written row of a query that is no point is
+ * all NaN / GS_KNN_NONE; a target without points gives all-incomplete rows.  Only ENQUEUES on `s` (NULL: the device's internal
+ * stream), ordered behind an edit or restore of EITHER buffer enqueued on another stream; takes and releases the neighbour
+ * scratch and event of BOTH buffers (3.11).  n_q = 0 is valid and launches nothing.
+ * GS_ERR_INVALID_ARGUMENT, before anything is enqueued and with the planes untouched, for a null buffer or distance plane,
+ * queries_buf == target (that is gs_gaussians_buffer_knn), buffers of different devices, a radius that is negative, NaN or
+ * infinite or whose square is not finite in binary32, k outside 1..16, a plane that is too small or on another device, a
+ * selection whose length differs from its buffer's or that belongs to another device, either buffer above 0xfffffff0
+ * Gaussians. */
+gs_status gs_gaussians_buffer_knn_between(gs_gaussians_buffer *queries_buf, gs_gaussians_buffer *target, gs_stream *s,
+                                          const gs_selection *queries /* of queries_buf, or NULL */,
+                                          const gs_selection *among /* of target, or NULL */,
+                                          const gs_model_transform_pod *query_transform /* or NULL */,
+                                          const gs_model_transform_pod *target_transform /* or NULL */, uint32_t k, float radius,
+                                          gs_buffer *dist2_out, gs_buffer *index_out /* or NULL */);
+/* What gs_gaussians_buffer_pair_sums fills (no reference item): 152 bytes.  Query i of `queries` (NULL: all)
+ * forms a PAIR with j = index_plane[i k] iff j < len(target) and both pw are finite, so an index at or beyond the target's
+ * length (GS_KNN_NONE, or the bytes of a row that was never written) is never dereferenced.  p = pw_i and q = pw_j in binary32
+ * as above, then widened.  pairs: their number; sp, sq: the sums of p and q; spq: row-major, spq[3 a + b] = the sum of p_a q_b
+ * (exact products); spp, sqq: the sums of (x x + y y) + z z; sdd: the sum of |p - q|^2, computed in binary64 from the widened
+ * coordinates the same way.  Every sum is added in the fixed shape of gs_gaussians_buffer_stats (wave, LDS in wave order, one
+ * finishing workgroup; no floating-point atomics): the same bits from run to run. */
+typedef struct gs_pair_sums {
+    uint64_t pairs;
+    double sp[3], sq[3], spq[9], spp, sqq, sdd;
+} gs_pair_sums;
+/* The sums over the pairs that the first column of an index plane of gs_gaussians_buffer_knn_between names (DESIGN.md 3.19;
+ * no reference item).  `queries` is the selection given to that call, or a subset of it; the transforms are the ones the pairs are
+ * measured under (the caller's to keep equal to the search's).  BLOCKING on `s` (NULL: the device's internal stream), like
+ * gs_gaussians_buffer_stats; a query buffer of length 0 gives all zeros.  GS_ERR_INVALID_ARGUMENT, with *out untouched, for a
+ * null buffer, plane or out, buffers of different devices, k outside 1..16, a plane smaller than 4 k n_q bytes or on another
+ * device, a selection whose length differs from the query buffer's or that belongs to another device, either buffer above
+ * 0xfffffff0 Gaussians. */
+gs_status gs_gaussians_buffer_pair_sums(gs_gaussians_buffer *queries_buf, gs_gaussians_buffer *target, gs_stream *s,
+                                        const gs_selection *queries /* or NULL */,
+                                        const gs_model_transform_pod *query_transform /* or NULL */,
+                                        const gs_model_transform_pod *target_transform /* or NULL */, const gs_buffer *index_plane,
+                                        uint32_t k, gs_pair_sums *out);
+/* The similarity transform `delta` that brings the p of the pairs onto their q in the least-squares sense, from the sums alone:
+ * host, binary64, no device (no reference item).  Horn's closed form: centroids, H = spq - sp sq^T / pairs, the
+ * largest eigenvector of the symmetric 4 x 4 matrix of H by cyclic Jacobi with a fixed count of 12 sweeps, the quaternion
+ * normalised to w >= 0; scale 1, or with_scale != 0 the least-squares uniform scale; t = mean q - s R mean p.  *rms_out (may be
+ * NULL) = sqrt(sdd / pairs), the RMS distance of the pairs as they came in.  delta acts in world space AFTER the query's
+ * transform: composed with it (below) it is the query transform of the next search.  GS_ERR_INVALID_ARGUMENT, with the
+ * outputs untouched, for a null sums or delta_out, fewer than 3 pairs, a sum that is not finite, p without spread, a rotation
+ * the pairs do not determine (collinear p or q: the two largest eigenvalues closer than 2^-40 of the matrix norm), a scale
+ * that is not positive. */
+gs_status gs_rigid_fit(const gs_pair_sums *sums, int32_t with_scale, gs_model_transform_pod *delta_out, double *rms_out /* or NULL */);
+/* out = the pod of delta o m for a delta of uniform scale s_d = delta->scale[0] (no reference item): rot = r_d r
+ * (quaternion product), scale = s_d scale, pos = s_d R_d pos + t_d, in binary64, rounded once; exact as a matrix product even
+ * when m scales non-uniformly, because the scale of a pod acts before its rotation.  out may be delta or m; a null argument
+ * does nothing. */
+void gs_model_transform_compose(const gs_model_transform_pod *delta, const gs_model_transform_pod *m, gs_model_transform_pod *out);
+
 #ifdef __cplusplus
 }
 #endif

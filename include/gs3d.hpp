@@ -424,6 +424,18 @@ class GaussiansBuffer {   // src/buffer/gaussian.rs:17-229
     // reference item); only enqueues.  A plane holds at least 4 k len() bytes; rows outside queries keep their bytes.
     void knn(Stream &s, uint32_t k, float radius, Buffer &dist2, Buffer *index = nullptr, const Selection *among = nullptr,
              const Selection *queries = nullptr, const gs_model_transform_pod *mt = nullptr);
+    // the k nearest Gaussians of ANOTHER buffer (among: a selection of target, nullptr: all) within radius of every Gaussian of
+    // queries (nullptr: all) of this one, each side under its own transform: the planes of knn, row i in this buffer's order,
+    // index holding target indices (gs3d.h gs_gaussians_buffer_knn_between; no reference item); only enqueues.
+    template <class T>
+    void knn_to(Stream &s, GaussiansBuffer<T> &target, uint32_t k, float radius, Buffer &dist2, Buffer *index = nullptr,
+                const Selection *queries = nullptr, const Selection *among = nullptr, const gs_model_transform_pod *mt = nullptr,
+                const gs_model_transform_pod *target_mt = nullptr);
+    // the sums over the pairs (Gaussian i of queries, Gaussian index[i k] of target) that gs_rigid_fit reads; an index at or
+    // beyond target.len() names no pair (gs3d.h gs_gaussians_buffer_pair_sums; no reference item); blocking.
+    template <class T>
+    gs_pair_sums pair_sums(Stream &s, GaussiansBuffer<T> &target, const Buffer &index, uint32_t k = 1, const Selection *queries = nullptr,
+                           const gs_model_transform_pod *mt = nullptr, const gs_model_transform_pod *target_mt = nullptr);
     // the .spz file image of the records of sel (nullptr: all; invert: of its complement), the payload deflated on the device
     // (gs3d.h gs_gaussians_buffer_export_spz_fast; no reference item); options == nullptr: the defaults.
     // Inflates to what gs_gaussians_buffer_export_spz_decompressed gives; blocking.
@@ -600,6 +612,38 @@ inline void GaussiansBuffer<G>::knn(Stream &s, uint32_t k, float radius, Buffer 
 inline gs_knn_summary_result knn_summary(Stream &s, const Buffer &dist2, uint64_t n, uint32_t k, uint32_t kind) {
     gs_knn_summary_result r;
     check(gs_knn_summary(s.raw(), dist2.raw(), n, k, kind, &r));
+    return r;
+}
+
+template <class G>
+template <class T>
+inline void GaussiansBuffer<G>::knn_to(Stream &s, GaussiansBuffer<T> &target, uint32_t k, float radius, Buffer &dist2, Buffer *index,
+                                       const Selection *queries, const Selection *among, const gs_model_transform_pod *mt,
+                                       const gs_model_transform_pod *target_mt) {
+    check(gs_gaussians_buffer_knn_between(h_, target.raw(), s.raw(), queries ? queries->raw() : nullptr, among ? among->raw() : nullptr, mt,
+                                          target_mt, k, radius, dist2.raw(), index ? index->raw() : nullptr));
+}
+template <class G>
+template <class T>
+inline gs_pair_sums GaussiansBuffer<G>::pair_sums(Stream &s, GaussiansBuffer<T> &target, const Buffer &index, uint32_t k,
+                                                  const Selection *queries, const gs_model_transform_pod *mt,
+                                                  const gs_model_transform_pod *target_mt) {
+    gs_pair_sums r;
+    check(gs_gaussians_buffer_pair_sums(h_, target.raw(), s.raw(), queries ? queries->raw() : nullptr, mt, target_mt, index.raw(), k, &r));
+    return r;
+}
+// the similarity transform that brings the p of the pairs onto their q, acting in world space after the query's transform;
+// *rms (nullptr: not wanted) = the RMS distance of the pairs as they came in (gs3d.h gs_rigid_fit; no reference
+// item); host only
+inline gs_model_transform_pod rigid_fit(const gs_pair_sums &sums, bool with_scale = false, double *rms = nullptr) {
+    gs_model_transform_pod d;
+    check(gs_rigid_fit(&sums, with_scale ? 1 : 0, &d, rms));
+    return d;
+}
+// the pod of delta o m for a delta of uniform scale (gs3d.h gs_model_transform_compose; no reference item)
+inline gs_model_transform_pod compose(const gs_model_transform_pod &delta, const gs_model_transform_pod &m) {
+    gs_model_transform_pod r;
+    gs_model_transform_compose(&delta, &m, &r);
     return r;
 }
 

@@ -911,6 +911,103 @@ def knn_summary(stream, dist2_plane, n, k, kind=KNN_KTH_DIST2):
                       sum=float(out.sum), sum_sq=float(out.sum_sq))
 
 
+@dataclasses.dataclass
+class PairSums:
+    """gs_pair_sums: the number of pairs (p of the query side, q of the target side) and the binary64 sums
+    of p, q, p_a q_b (3 x 3, row a), |p|^2, |q|^2 and |p - q|^2 over them."""
+    pairs: int
+    sp: np.ndarray
+    sq: np.ndarray
+    spq: np.ndarray
+    spp: float
+    sqq: float
+    sdd: float
+
+    @property
+    def rms(self):
+        """sqrt(sdd / pairs): the RMS distance of the pairs; NaN without one"""
+        return float(np.sqrt(self.sdd / self.pairs)) if self.pairs else float("nan")
+
+    def record(self):
+        """the 152 bytes of the C record"""
+        r = _capi.PairSumsRecord()
+        r.pairs = int(self.pairs)
+        r.sp[:] = [float(v) for v in np.asarray(self.sp, np.float64).reshape(3)]
+        r.sq[:] = [float(v) for v in np.asarray(self.sq, np.float64).reshape(3)]
+        r.spq[:] = [float(v) for v in np.asarray(self.spq, np.float64).reshape(9)]
+        r.spp, r.sqq, r.sdd = float(self.spp), float(self.sqq), float(self.sdd)
+        return r
+
+    @staticmethod
+    def from_record(r):
+        return PairSums(pairs=int(r.pairs), sp=np.array(r.sp[:], np.float64), sq=np.array(r.sq[:], np.float64),
+                        spq=np.array(r.spq[:], np.float64).reshape(3, 3), spp=float(r.spp), sqq=float(r.sqq), sdd=float(r.sdd))
+
+
+def rigid_fit(sums, scale=False):
+    """gs_rigid_fit: (delta, rms).  delta: the ModelTransformPod of the rotation, translation and — with
+    scale=True — uniform scale that brings the p of the pairs of `sums` (a PairSums) onto their q in the least-squares
+    sense, Horn's closed form in binary64 on the host; it acts in world space AFTER the query side's transform
+    (compose_model_transform).  rms: sqrt(sdd / pairs) of the pairs as they came in.  InvalidArgumentError for fewer than
+    3 pairs, a sum that is not finite, or pairs that determine no rotation."""
+    if not isinstance(sums, PairSums):
+        raise TypeError("sums must be a PairSums, not %s" % type(sums).__name__)
+    if not isinstance(scale, bool):
+        raise TypeError("scale must be a bool, not %s" % type(scale).__name__)
+    rec, delta, rms = sums.record(), ModelTransformPod(), C.c_double()
+    _check(_L.gs_rigid_fit(C.byref(rec), 1 if scale else 0, C.byref(delta), C.byref(rms)))
+    return delta, rms.value
+
+
+def compose_model_transform(delta, m):
+    """gs_model_transform_compose: the ModelTransformPod of delta o m for a `delta` of uniform scale:
+    rot = r_d r, scale = s_d scale, pos = s_d R_d pos + t_d."""
+    for name, v in (("delta", delta), ("m", m)):
+        if not isinstance(v, ModelTransformPod):
+            raise TypeError("%s must be a ModelTransformPod, not %s" % (name, type(v).__name__))
+    out = ModelTransformPod()
+    _L.gs_model_transform_compose(C.byref(delta), C.byref(m), C.byref(out))
+    return out
+
+
+@dataclasses.dataclass
+class Chamfer:
+    """What GaussiansBuffer.chamfer_to returns: the KnnSummary (k = 1, KNN_MEAN_DIST) of each direction.  mean_*: the mean
+    distance to the nearest Gaussian of the other buffer over those that have one within the radius (NaN without any);
+    incomplete_*: the Gaussians with a finite position that have none."""
+    to_target: KnnSummary
+    from_target: KnnSummary
+
+    @property
+    def mean_to(self):
+        return self.to_target.mean
+
+    @property
+    def mean_from(self):
+        return self.from_target.mean
+
+    @property
+    def incomplete_to(self):
+        return self.to_target.points - self.to_target.complete
+
+    @property
+    def incomplete_from(self):
+        return self.from_target.points - self.from_target.complete
+
+    @property
+    def distance(self):
+        """the symmetric Chamfer distance: mean_to + mean_from"""
+        return self.mean_to + self.mean_from
+
+
+@dataclasses.dataclass
+class AlignReport:
+    """What GaussiansBuffer.align_to did: one (pairs, rms) entry per iteration, measured BEFORE that iteration's fit, and why
+    it stopped: 'converged' (the RMS fell by less than rms_tol of itself), 'pairs' (fewer than 3) or 'iterations'."""
+    iterations: list
+    stopped: str
+
+
 class GaussiansBuffer:
     """GaussiansBuffer<G> — src/buffer/gaussian.rs:17-229."""
 
@@ -1437,6 +1534,142 @@ class GaussiansBuffer:
                 stream.synchronize()
                 todo.destroy()
         return dist2, index, float(radius), passes
+
+    def _between_args(self, target, queries, among, model_transform, target_transform):
+        """the arguments the calls between two buffers share, checked before any library call"""
+        if not isinstance(target, GaussiansBuffer):
+            raise TypeError("target must be a GaussiansBuffer, not %s" % type(target).__name__)
+        if target is self:
+            raise ValueError("target is this buffer: that is knn()")
+        for name, v in (("queries", queries), ("among", among)):
+            if v is not None and not isinstance(v, Selection):
+                raise TypeError("%s must be a Selection or None, not %s" % (name, type(v).__name__))
+        for name, v in (("model_transform", model_transform), ("target_transform", target_transform)):
+            if v is not None and not isinstance(v, ModelTransformPod):
+                raise TypeError("%s must be a ModelTransformPod or None, not %s" % (name, type(v).__name__))
+
+    def knn_to(self, stream, target, k, radius, queries=None, among=None, model_transform=None, target_transform=None,
+               dist2_out=None, index_out=None, indices=False):
+        """gs_gaussians_buffer_knn_between: a Buffer of k binary32 values per Gaussian of THIS buffer in
+        caller order, row i at i k: the squared distances from Gaussian i (under model_transform) to its k nearest Gaussians
+        of `target` (another GaussiansBuffer, under target_transform; `among`, a Selection of the target, None: all) within
+        `radius`, ascending, ties to the smaller target index, padded with +inf; all NaN where i has no finite world
+        position.  indices=True (or an index_out Buffer): (dist2, index), the second plane holding the uint32 TARGET indices,
+        KNN_NONE in the padding.  `queries` (a Selection of this buffer; None: all) names the rows that are written.  Only
+        enqueues; the planes are those of knn(): select_knn and knn_summary take them with n = self.len()."""
+        k = _knn_k(k)
+        radius, _, _ = _neighbor_args(radius, None, None)
+        self._between_args(target, queries, among, model_transform, target_transform)
+        for name, b in (("dist2_out", dist2_out), ("index_out", index_out)):
+            if b is not None and not isinstance(b, Buffer):
+                raise TypeError("%s must be a Buffer or None, not %s" % (name, type(b).__name__))
+        if not isinstance(indices, bool):
+            raise TypeError("indices must be a bool, not %s" % type(indices).__name__)
+        own = []
+        try:
+            if dist2_out is None:
+                dist2_out = Buffer(self.device, size=max(4 * k * self.len(), 4))
+                own.append(dist2_out)
+            if index_out is None and indices:
+                index_out = Buffer(self.device, size=max(4 * k * self.len(), 4))
+                own.append(index_out)
+            _check(_L.gs_gaussians_buffer_knn_between(
+                self._h, target._h, stream._h if stream is not None else None, queries._h if queries is not None else None,
+                among._h if among is not None else None, C.byref(model_transform) if model_transform is not None else None,
+                C.byref(target_transform) if target_transform is not None else None, k, radius, dist2_out._h,
+                index_out._h if index_out is not None else None))
+        except Exception:
+            for b in own:
+                b.release()
+            raise
+        return dist2_out if index_out is None else (dist2_out, index_out)
+
+    def pair_sums(self, stream, target, index_plane, k=1, queries=None, model_transform=None, target_transform=None):
+        """gs_gaussians_buffer_pair_sums: the PairSums over the pairs (Gaussian i of this buffer, Gaussian
+        index_plane[i k] of `target`) for the i of `queries` (the Selection given to knn_to, or a subset; None: all) — an
+        index at or beyond target.len() names no pair and is never followed.  Blocking; the same bits from run to run."""
+        k = _knn_k(k)
+        self._between_args(target, queries, None, model_transform, target_transform)
+        if not isinstance(index_plane, Buffer):
+            raise TypeError("index_plane must be a Buffer, not %s" % type(index_plane).__name__)
+        out = _capi.PairSumsRecord()
+        _check(_L.gs_gaussians_buffer_pair_sums(
+            self._h, target._h, stream._h if stream is not None else None, queries._h if queries is not None else None,
+            C.byref(model_transform) if model_transform is not None else None,
+            C.byref(target_transform) if target_transform is not None else None, index_plane._h, k, C.byref(out)))
+        return PairSums.from_record(out)
+
+    def chamfer_to(self, stream, target, radius, model_transform=None, target_transform=None):
+        """The two-sided Chamfer distance to `target` within `radius`, without a download of the planes: a Chamfer of the mean
+        nearest-neighbour distance from this buffer to the target and back, over the Gaussians that have a neighbour within
+        the radius, and the numbers that have none (`incomplete`).  Two knn_to calls with k = 1 and two
+        knn_summary(KNN_MEAN_DIST) (a host policy).  Blocking."""
+        if not isinstance(stream, Stream):
+            raise TypeError("stream must be a Stream, not %s" % type(stream).__name__)
+        radius, _, _ = _neighbor_args(radius, None, None)
+        self._between_args(target, None, None, model_transform, target_transform)
+        sides = []
+        for a, b, ma, mb in ((self, target, model_transform, target_transform), (target, self, target_transform, model_transform)):
+            plane = a.knn_to(stream, b, 1, radius, model_transform=ma, target_transform=mb)
+            try:
+                sides.append(knn_summary(stream, plane, a.len(), 1, KNN_MEAN_DIST))
+            finally:
+                stream.synchronize()
+                plane.release()
+        return Chamfer(to_target=sides[0], from_target=sides[1])
+
+    def align_to(self, stream, target, radius, queries=None, among=None, model_transform=None, target_transform=None, scale=False,
+                 max_iterations=32, rms_tol=1e-4):
+        """ICP of this buffer onto `target` (a host policy): (pod, report).  Edits nothing: every iteration
+        runs knn_to (k = 1, indices) under the current transform — model_transform (None: the default pod) composed with
+        the fits so far —, then pair_sums, and, unless it stops, rigid_fit and compose_model_transform.  It stops when the
+        RMS of the pairs has not fallen by more than rms_tol of its previous value, or is at most rms_tol x radius
+        ('converged'), when there are fewer than 3 pairs ('pairs'), or after max_iterations ('iterations').  pod: the
+        ModelTransformPod the last entry of the report was measured under; bake it with edit(TRANSFORM | ROTATE_SH) or
+        pass it as the frame's model transform.  report: an AlignReport with one (pairs, rms) per iteration.  Only pairs
+        within `radius` count, so the radius is the largest misalignment that can be undone.  `queries` subsamples this
+        buffer, `among` the target.  Blocking."""
+        if not isinstance(stream, Stream):
+            raise TypeError("stream must be a Stream, not %s" % type(stream).__name__)
+        radius, _, _ = _neighbor_args(radius, None, None)
+        self._between_args(target, queries, among, model_transform, target_transform)
+        if not isinstance(scale, bool):
+            raise TypeError("scale must be a bool, not %s" % type(scale).__name__)
+        if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)):
+            raise TypeError("max_iterations must be an integer, not %s" % type(max_iterations).__name__)
+        if int(max_iterations) < 1:
+            raise ValueError("max_iterations must be at least 1, not %d" % max_iterations)
+        if isinstance(rms_tol, bool) or not isinstance(rms_tol, (int, float, np.integer, np.floating)):
+            raise TypeError("rms_tol must be a number, not %s" % type(rms_tol).__name__)
+        if not (np.isfinite(rms_tol) and rms_tol >= 0):
+            raise ValueError("rms_tol must be finite and >= 0, not %r" % (rms_tol,))
+        current = model_transform if model_transform is not None else model_transform_pod()
+        size = max(4 * self.len(), 4)
+        dist2, index = Buffer(self.device, size=size), Buffer(self.device, size=size)
+        entries, stopped, previous = [], "iterations", None
+        try:
+            for it in range(int(max_iterations)):
+                self.knn_to(stream, target, 1, radius, queries=queries, among=among, model_transform=current,
+                            target_transform=target_transform, dist2_out=dist2, index_out=index)
+                sums = self.pair_sums(stream, target, index, 1, queries=queries, model_transform=current,
+                                      target_transform=target_transform)
+                entries.append((sums.pairs, sums.rms))
+                if sums.pairs < 3:
+                    stopped = "pairs"
+                    break
+                if sums.rms <= float(rms_tol) * radius or (previous is not None and not previous - sums.rms > float(rms_tol) * previous):
+                    stopped = "converged"
+                    break
+                if it + 1 == int(max_iterations):
+                    break
+                delta, _ = rigid_fit(sums, scale)
+                current = compose_model_transform(delta, current)
+                previous = sums.rms
+        finally:
+            stream.synchronize()
+            dist2.release()
+            index.release()
+        return current, AlignReport(iterations=entries, stopped=stopped)
 
     def destroy(self):
         if self._h:
@@ -2017,6 +2250,28 @@ class Selection:
             raise ValueError("a bound of the range is NaN")
         op = select_op(op)
         _check(_L.gs_select_knn(self._h, stream._h if stream is not None else None, dist2_plane._h, k, kind, lo, hi, op))
+
+    def select_near(self, stream, gaussians, target, radius, among=None, model_transform=None, target_transform=None, op=SEL_SET):
+        """self = self op {i : Gaussian i of `gaussians` has a Gaussian of `target` within `radius`}: the overlap of two
+        scans (a host policy).  knn_to with k = 1, then select_knn(KNN_KTH_DIST2, 0, r r): a row without a
+        neighbour is +inf, a Gaussian without a finite world position NaN, and neither is selected.  `among`: a Selection of
+        the target.  len(self) == gaussians.len().  Blocking."""
+        if not isinstance(stream, Stream):
+            raise TypeError("stream must be a Stream, not %s" % type(stream).__name__)
+        if not isinstance(gaussians, GaussiansBuffer):
+            raise TypeError("gaussians must be a GaussiansBuffer, not %s" % type(gaussians).__name__)
+        radius, _, _ = _neighbor_args(radius, None, None)
+        gaussians._between_args(target, None, among, model_transform, target_transform)
+        op = select_op(op)
+        if len(self) != gaussians.len():
+            raise ValueError("the selection has %d bits, the buffer %d Gaussians" % (len(self), gaussians.len()))
+        dist2 = gaussians.knn_to(stream, target, 1, radius, among=among, model_transform=model_transform, target_transform=target_transform)
+        try:
+            rr = np.float32(radius) * np.float32(radius)
+            self.select_knn(stream, dist2, 1, KNN_KTH_DIST2, 0.0, float(rr), op)
+        finally:
+            stream.synchronize()
+            dist2.release()
 
     def select_statistical_outliers(self, stream, gaussians, k=8, sigma=2.0, among=None, model_transform=None, op=SEL_SET,
                                     radius0=None, max_passes=24):

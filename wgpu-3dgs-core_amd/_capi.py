@@ -83,6 +83,12 @@ class KnnSummaryRecord(C.Structure):
     _fields_ = [("points", u64), ("complete", u64), ("min", f32), ("max", f32), ("sum", C.c_double), ("sum_sq", C.c_double)]
 
 
+class PairSumsRecord(C.Structure):
+    """gs_pair_sums: what gs_gaussians_buffer_pair_sums fills and gs_rigid_fit reads (152 bytes)"""
+    _fields_ = [("pairs", u64), ("sp", C.c_double * 3), ("sq", C.c_double * 3), ("spq", C.c_double * 9), ("spp", C.c_double),
+                ("sqq", C.c_double), ("sdd", C.c_double)]
+
+
 class ImageCompareDesc(C.Structure):
     """gs_image_compare_desc: flags, data range and the optional device planes of gs_image_compare"""
     _fields_ = [("flags", u32), ("data_range", f32), ("err_plane", vp), ("ssim_plane", vp), ("reserved", u32 * 4)]
@@ -301,6 +307,10 @@ SIGNATURES = {
     "gs_knn_summary": (i32, [vp, vp, u64, u32, u32, vp]),
     "gs_sort_pairs_u64": (i32, [vp, vp, vp, vp, u64, u32]),
     "gs_exclusive_scan_u32": (i32, [vp, vp, vp, vp, u64, vp]),
+    "gs_gaussians_buffer_knn_between": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, f32, vp, vp]),
+    "gs_gaussians_buffer_pair_sums": (i32, [vp, vp, vp, vp, vp, vp, vp, u32, vp]),
+    "gs_rigid_fit": (i32, [vp, i32, vp, vp]),
+    "gs_model_transform_compose": (None, [vp, vp, vp]),
 }
 
 _lib = None
