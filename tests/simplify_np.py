@@ -15,6 +15,7 @@ import numpy as np
 
 import convert_np
 from edit_np import pod_bytes
+from records import selection_from_mask
 
 f32, f64 = np.float32, np.float64
 CELL_BITS = 21
@@ -154,10 +155,11 @@ def color_bytes(x):
         return np.where(v > 0, np.minimum(np.floor(v), 255.0), 0.0).astype(np.int64)
 
 
-def check_merged(got_wide, w, only=None):
+def check_merged(got_wide, w, only=None, require_finite=False):
     """got_wide: the (SH f32, cov f32) records of the device, K x 224 bytes; w: merge(...).  Every cell with m >= 2 (and in
     `only`, a bool mask over the cells) is compared value by value against the witness within its bound, colour and opacity
-    bytes within 1.  Returns the number of cells compared."""
+    bytes within 1.  A value whose witness or bound is not finite is left out of the comparison; with require_finite there
+    must be none: every value of every picked cell is compared.  Returns the number of cells compared."""
     rows = np.asarray(got_wide, np.uint8).reshape(-1, pod_bytes(0, 1))
     assert len(rows) == w["K"], (len(rows), w["K"])
     pick = w["m"] >= 2
@@ -169,10 +171,14 @@ def check_merged(got_wide, w, only=None):
         for name in ("pos", "cov", "sh"):
             want, tol, have = w[name][pick], w[name + "_tol"][pick], g[name][pick]
             fin = np.isfinite(want) & np.isfinite(tol)
+            if require_finite:
+                assert fin.all(), (name, "left out of the comparison", int((~fin).sum()), np.argwhere(~fin)[:4].tolist())
             err = np.abs(have - want)
             worst = np.where(fin, err - tol, -1.0)
             assert (worst <= 0).all(), (name, float(worst.max()), np.argwhere(worst > 0)[:4].tolist(),
                                         float((err / np.where(tol > 0, tol, 1.0))[fin].max()))
+    if require_finite:
+        assert np.isfinite(w["rgb"][pick]).all() and np.isfinite(w["alpha"][pick]).all(), "colour or opacity left to the NaN rule"
     assert (np.abs(g["rgba"][pick, :3] - color_bytes(w["rgb"][pick])) <= 1).all(), "colour bytes"
     assert (np.abs(g["rgba"][pick, 3] - color_bytes(w["alpha"][pick])) <= 1).all(), "opacity bytes"
     return int(pick.sum())
@@ -188,3 +194,145 @@ def expected_singletons(gs, spod, dpod, pods, c):
     else:
         out = spod.convert(src, dpod)
     return one, np.asarray(out, np.uint8).reshape(-1, dpod.size)
+
+
+# ---- records from decoded values -------------------------------------------------------------------------------------
+
+def pack_wide(d):
+    """decode()'s dict -> (SH f32, cov f32) records, flat bytes: pos | rgba | sh | cov | pad, 224 bytes each.  The inverse of
+    decode(0, 1, .): a test sets covariance words (or any other value) in the dict and packs it"""
+    n = len(d["pos"])
+    rows = np.zeros((n, pod_bytes(0, 1)), np.uint8)
+    rows[:, :12] = np.ascontiguousarray(d["pos"], f32).reshape(n, 3).view(np.uint8)
+    rows[:, 12:16] = np.asarray(d["rgba"], np.uint8).reshape(n, 4)
+    rows[:, 16:196] = np.ascontiguousarray(d["sh"], f32).reshape(n, 45).view(np.uint8)
+    rows[:, 196:220] = np.ascontiguousarray(d["cov"], f32).reshape(n, 6).view(np.uint8)
+    return rows.reshape(-1)
+
+
+# ---- constructed runs ------------------------------------------------------------------------------------------------
+# The kernels see the Gaussians sorted by cell key, 64 sorted slots per wave, 256 per block, the slots without a point behind
+# the points.  line_scene puts a known number of points into each cell of one row of cells, so which run a sorted slot
+# belongs to is known by design; wave_partials says from the definition alone what each wave of slots has to hand on.
+
+def line_scene(counts, cell_size, rng, among_tail=0):
+    """(pos float32[n, 3], among bool[n] or None): counts[j] points in cell j of one row of cells along x, for which
+    cells(pos, cell_size, among)["count"] is exactly `counts`.  h = float32(cell_size) (1 + 2^-10) is the cell side (the
+    extent of a few cells is far from the second regime); x = x0 + (j + f) h with f uniform in [0.2, 0.8]: far from a cell
+    face against the binary32 rounding of x; y and z within a tenth of a cell; the first member of cell 0 sits exactly on
+    the low corner of the box, so the grid starts where the design says.  among_tail more Gaussians, in and around the
+    row, are excluded by `among`: they sort behind the points.  The caller order is a random permutation."""
+    counts = np.asarray(counts, np.int64)
+    assert counts.ndim == 1 and (counts > 0).all()
+    P, n = int(counts.sum()), int(counts.sum()) + among_tail
+    h = float(f32(cell_size)) * (1.0 + 2.0 ** -10)
+    lo = np.array([-0.375, 0.5, 0.25])      # exact in binary32
+    j = np.repeat(np.arange(len(counts)), counts).astype(f64)
+    pos = np.empty((n, 3), f64)
+    pos[:P, 0] = lo[0] + (j + rng.uniform(0.2, 0.8, P)) * h
+    pos[:P, 1:] = lo[1:] + rng.uniform(0.0, 0.1, (P, 2)) * h
+    pos[0] = lo
+    pos[P:, 0] = lo[0] + rng.uniform(-1.0, len(counts) + 1.0, among_tail) * h      # beyond both ends of the row too
+    pos[P:, 1:] = lo[1:] + rng.uniform(-0.5, 0.5, (among_tail, 2)) * h
+    among = np.arange(n) < P
+    perm = rng.permutation(n)
+    return pos[perm].astype(f32), (among[perm] if among_tail else None)
+
+
+W_NONE, W_OPEN, W_MIDDLE, W_LAST = "none", "open", "middle", "last"
+
+
+def wave_partials(c):
+    """From cells(): what every wave of 64 sorted slots hands on, by the definition of a run (not by the kernel's flags).
+    dict(incoming[g]: the run that holds the wave's first slot also holds the slot before it — W_MIDDLE if it also holds
+    the first slot of the next wave, W_LAST if it ends here, else W_NONE; outgoing[g]: W_OPEN if the run that holds the
+    wave's last slot starts in this wave and holds the next wave's first slot, else W_NONE; partials[k]: the waves run k
+    touches — a run that crosses a wave edge leaves that many partials).  The slots behind the points hold no run."""
+    n, P, K = len(c["pt"]), len(c["order"]), c["K"]
+    nwaves = (n + 63) // 64
+    first = np.asarray(c["first"], np.int64)
+    end = first + np.asarray(c["count"], np.int64)      # one past the run
+    run = np.full(64 * (nwaves + 1), -1, np.int64)
+    run[:P] = np.repeat(np.arange(K), c["count"])
+    incoming, outgoing = [], []
+    for g in range(nwaves):
+        a, b = 64 * g, 64 * g + 64
+        r = run[a]
+        came_in = g > 0 and r >= 0 and run[a - 1] == r
+        incoming.append(W_NONE if not came_in else W_MIDDLE if run[b] == r else W_LAST)
+        r = run[b - 1]
+        outgoing.append(W_OPEN if r >= 0 and run[b] == r and first[r] >= a else W_NONE)
+    return dict(incoming=incoming, outgoing=outgoing, partials=(end - 1) // 64 - first // 64 + 1)
+
+
+# The run shapes of the tests: name -> (points per cell, Gaussians excluded by `among`, what the shape is for).  Cell size
+# RUN_CELL.  tests/test_simplify_api.py proves what the table covers; tests/test_gpu_simplify_runs.py runs it.
+RUN_CELL = 0.25
+RUN_SHAPES = {
+    "a": ([40, 24, 5, 59], 0, "a run ends in lane 63, the next heads lane 0"),
+    "b": ([64, 64, 3], 0, "runs that are exactly one wave"),
+    "c": ([63, 2, 63], 0, "a run of two over a wave edge: two partials of one member each"),
+    "d": ([255, 2, 30], 0, "a run of two over a block edge"),
+    "e": ([63, 1, 1, 10], 0, "singletons in lane 63 and in lane 0"),
+    "f": ([64, 192, 5], 0, "open from lane 0, middle waves, last in lane 63"),
+    "g": ([10, 200, 7], 0, "open, middle and last, none aligned"),
+    "h": ([1, 64 * 63 + 2, 9], 0, "a long run of 64 partials: the last one ends the first chunk of the walk"),
+    "i": ([1, 64 * 64 + 2, 9], 0, "a long run of 65 partials: the last one heads the second chunk"),
+    "j": ([63, 64 * 64 + 2, 9], 0, "a long run of 66 partials, open in lane 63"),
+    "k": ([30, 100, 100, 3], 0, "a wave that closes one crossing run and opens the next"),
+    "l": ([5, 187], 0, "the last run ends at slot n - 1, n a multiple of 64"),
+    "m": ([6, 250], 0, "the last run ends at slot n - 1, n a multiple of 256"),
+    "n": ([5, 187], 70, "non-points fill a whole wave behind the points"),
+    "o": ([10, 200, 7], 70, "non-points directly behind a run that ends inside a wave"),
+}
+
+
+def run_shape(name):
+    """(pos, among, counts) of a shape of RUN_SHAPES; the same every time"""
+    counts, tail, _ = RUN_SHAPES[name]
+    pos, among = line_scene(counts, RUN_CELL, np.random.default_rng(1000 + ord(name)), tail)
+    return pos, among, np.asarray(counts, np.int64)
+
+
+# ---- a device call against the witness -------------------------------------------------------------------------------
+
+WIDE = (0, 1)                       # SH f32, cov f32: what the merged values are read from
+
+
+def witness(sh, cov, pods, cell_size, among=None):
+    d = decode(sh, cov, pods)
+    c = cells(d["pos"], cell_size, among)
+    return d, c, merge(d, c)
+
+
+def simplify(gs, device, stream, src, pods, cell_size, dst=None, among=None):
+    """-> (bytes of the result, the cell plane uint32[n], K)"""
+    spod = gs.GaussianPod(*src)
+    n = len(pods) // spod.size
+    buf = gs.GaussiansBuffer.new_with_pods(device, spod, pods) if n else gs.GaussiansBuffer.new_empty(device, spod, 0)
+    sel = selection_from_mask(gs, device, stream, among)
+    out, plane = buf.simplify(stream, cell_size, None if dst is None else gs.GaussianPod(*dst), sel, cell_of_out=True)
+    assert out.pod == (spod if dst is None else gs.GaussianPod(*dst))
+    got, cell_of, K = out.download(stream), plane.download(stream, np.uint32)[:n].copy(), out.len()
+    assert np.array_equal(buf.download(stream), pods), "the source is untouched"
+    out.destroy(); plane.release(); buf.destroy()
+    if sel is not None:
+        sel.destroy()
+    return got, cell_of, K
+
+
+def check_against_witness(gs, device, stream, src, pods, cell_size, among=None, require_finite=False):
+    """simplify into (SH f32, cov f32) and compare everything: K and the cell plane exactly, the merged cells within the
+    witness's bound (check_merged), the cells of one member bit for bit with the host's conversion; returns (cells, merged
+    witness, device bytes)"""
+    d, c, w = witness(*src, pods, cell_size, among)
+    got, cell_of, K = simplify(gs, device, stream, src, pods, cell_size, WIDE, among)
+    assert K == c["K"] and np.array_equal(cell_of, c["cell_of"]), (K, c["K"], int((cell_of != c["cell_of"]).sum()))
+    if K:
+        check_merged(got, w, require_finite=require_finite)
+        one, want = expected_singletons(gs, gs.GaussianPod(*src), gs.GaussianPod(*WIDE), pods, c)
+        have = np.asarray(got).reshape(-1, pod_bytes(*WIDE))[one]
+        assert np.array_equal(have, want), (len(one), int((have != want).any(axis=1).sum()))
+    else:
+        assert got.size == 0
+    return c, w, got

@@ -11,7 +11,7 @@ import pytest
 import simplify_np as sn
 from frames import render_image
 from helpers import same_bits
-from records import diff, selection_from_mask
+from records import diff
 from records import rows as _rows
 from scenes import ALL_LAYOUTS
 
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 N = 5003
-WIDE = (0, 1)                       # SH f32, cov f32: what the merged values are read from
+WIDE = sn.WIDE
 THREE_SOURCES = [(0, 0), (1, 2), (2, 1)]
 _CACHE = {}
 
@@ -36,41 +36,7 @@ def set_pods(gs, sh, cov, n=N):
     return _CACHE[key]
 
 
-def witness(sh, cov, pods, cell_size, among=None):
-    d = sn.decode(sh, cov, pods)
-    c = sn.cells(d["pos"], cell_size, among)
-    return d, c, sn.merge(d, c)
-
-
-def simplify(gs, device, stream, src, pods, cell_size, dst=None, among=None):
-    """-> (bytes of the result, the cell plane uint32[n], K)"""
-    spod = gs.GaussianPod(*src)
-    n = len(pods) // spod.size
-    buf = gs.GaussiansBuffer.new_with_pods(device, spod, pods) if n else gs.GaussiansBuffer.new_empty(device, spod, 0)
-    sel = selection_from_mask(gs, device, stream, among)
-    out, plane = buf.simplify(stream, cell_size, None if dst is None else gs.GaussianPod(*dst), sel, cell_of_out=True)
-    assert out.pod == (spod if dst is None else gs.GaussianPod(*dst))
-    got, cell_of, K = out.download(stream), plane.download(stream, np.uint32)[:n].copy(), out.len()
-    assert np.array_equal(buf.download(stream), pods), "the source is untouched"
-    out.destroy(); plane.release(); buf.destroy()
-    if sel is not None:
-        sel.destroy()
-    return got, cell_of, K
-
-
-def check_against_witness(gs, device, stream, src, pods, cell_size, among=None):
-    """simplify into (SH f32, cov f32) and compare everything; returns (cells, merged witness, device bytes)"""
-    d, c, w = witness(*src, pods, cell_size, among)
-    got, cell_of, K = simplify(gs, device, stream, src, pods, cell_size, WIDE, among)
-    assert K == c["K"] and np.array_equal(cell_of, c["cell_of"]), (K, c["K"], int((cell_of != c["cell_of"]).sum()))
-    if K:
-        sn.check_merged(got, w)
-        one, want = sn.expected_singletons(gs, gs.GaussianPod(*src), gs.GaussianPod(*WIDE), pods, c)
-        have = _rows(got, 224)[one]
-        assert np.array_equal(have, want), (len(one), int((have != want).any(axis=1).sum()))
-    else:
-        assert got.size == 0
-    return c, w, got
+witness, simplify, check_against_witness = sn.witness, sn.simplify, sn.check_against_witness      # shared with test_gpu_simplify_runs.py
 
 
 # ---- cells and counts ----------------------------------------------------------------------------------------------------

@@ -174,3 +174,49 @@ def test_merged_covariances_are_symmetric_positive_semidefinite_and_keep_the_mas
         run = o[c["first"][k]:c["first"][k] + c["count"][k]]
         assert (w["pos"][k] >= d["pos"][run].min(axis=0) - 1e-12).all() and (w["pos"][k] <= d["pos"][run].max(axis=0) + 1e-12).all()
     assert (w["pos_tol"] > 0).all() and (w["pos_tol"] < 1e-4).all() and (w["cov_tol"] >= 0).all()
+
+
+# ---- the constructed run shapes: what the table of simplify_np.RUN_SHAPES covers ------------------------------------------
+
+def test_pack_wide_is_the_inverse_of_decode():
+    d = _decoded(37, 5)
+    back = sn.decode(0, 1, sn.pack_wide(d))
+    assert all(np.array_equal(np.asarray(back[k]).view(np.uint8), np.asarray(d[k]).view(np.uint8)) for k in ("pos", "rgba", "sh", "cov"))
+    assert sn.pack_wide(d).size == 37 * 224 and not sn.pack_wide(d).reshape(37, 224)[:, 220:].any()
+
+
+def test_run_shapes_have_the_designed_counts_and_cover_every_wave_state():
+    """The proof that tests/test_gpu_simplify_runs.py reaches what it claims: every shape has exactly the designed members
+    per cell in sorted order, and over the whole table every pair (what came into a wave, what goes on from it) that can
+    occur does occur, as do crossing runs of exactly 2, 64, 65 and 66 partials."""
+    pairs, partials, per = set(), set(), {}
+    for name, (counts, tail, _) in sn.RUN_SHAPES.items():
+        pos, among, want = sn.run_shape(name)
+        assert len(pos) == sum(counts) + tail and (among is None) == (tail == 0)
+        c = sn.cells(pos, sn.RUN_CELL, among)
+        assert c["K"] == len(counts) and np.array_equal(c["count"], want), (name, c["count"].tolist())
+        assert c["h"] == float(f32(sn.RUN_CELL)) * (1.0 + 2.0 ** -10), "the first grid regime"
+        assert not np.array_equal(c["order"], np.arange(len(c["order"]))), "the caller order is permuted"
+        if tail:
+            assert (~c["pt"]).sum() == tail and (c["cell_of"][~among] == sn.NOT_A_POINT).all()
+        wp = sn.wave_partials(c)
+        assert len(wp["incoming"]) == len(wp["outgoing"]) == (len(pos) + 63) // 64
+        per[name] = list(zip(wp["incoming"], wp["outgoing"]))
+        pairs |= set(per[name])
+        partials |= set(int(x) for x in wp["partials"] if x >= 2)
+    N_, O_, M_, L_ = sn.W_NONE, sn.W_OPEN, sn.W_MIDDLE, sn.W_LAST
+    # (middle, open) cannot occur: a run that came in and goes on fills the wave, so no run starts in it
+    assert pairs == {(N_, N_), (N_, O_), (L_, N_), (L_, O_), (M_, N_)}, pairs
+    assert {2, 64, 65, 66} <= partials, sorted(partials)
+    # ... and shape by shape what the table says of it
+    assert per["a"] == [(N_, N_), (N_, N_)] and per["b"] == [(N_, N_)] * 3
+    assert per["c"] == [(N_, O_), (L_, N_)] and per["d"][3:] == [(L_, O_), (L_, N_)]
+    assert per["e"] == [(N_, N_), (N_, N_)]
+    assert per["f"] == [(N_, N_), (N_, O_), (M_, N_), (L_, N_), (N_, N_)]
+    assert per["g"] == [(N_, O_), (M_, N_), (M_, N_), (L_, N_)]
+    for name, waves in (("h", 64), ("i", 65), ("j", 66)):
+        assert per[name][0] == (N_, O_) and per[name][1:waves - 1] == [(M_, N_)] * (waves - 2) and per[name][waves - 1] == (L_, N_)
+        assert len(per[name]) == waves
+    assert per["k"] == [(N_, O_), (M_, N_), (L_, O_), (L_, N_)]
+    assert per["l"][-1] == (L_, N_) and len(per["l"]) == 3 and per["m"][-1] == (L_, N_) and len(per["m"]) == 4
+    assert per["n"] == per["l"] + [(N_, N_)] * 2 and per["o"][:4] == per["g"]
